@@ -25,6 +25,9 @@ Also reported in the same JSON line:
                walks it (the near form of exact re-treeing) AND with VK_SCENE_EMPIRICAL_TREES), of C2 in the empirical form and with
                VK_SCENE_FAST_ACCEL, each verified the same way and, on a rebuilt tree, compared bit for bit with the same workload's frame
                on the tree as handed over (N = 1 only; --no-also skips them)
+
+--dump-outputs DIR writes the frame of the last timed step to DIR (dump_outputs): the inputs (scene seed 1, render seed 2) are
+fixed, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -198,6 +201,30 @@ def verify_against_oracle(O, hs, cam, img, width, spp, depth, budget_samples=1.5
             "ok": bool(err < 1e-4 and np.isfinite(img).all()), "oracle_seconds": round(time.perf_counter() - t0, 2)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 21     # a frame too large to dump whole: this many pixels of it (24 MiB of RGB + 16 MiB of indices)
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame the last timed step produced (what a caller of vk_render_device receives; (h, w, 3), y up, or with
+    --rgb8 the gathered bytes, top row first) as float32 .npy files, for comparing two builds output for output.  A frame larger
+    than DUMP_MAX_BYTES is dumped as a fixed, seeded sample of its pixels: frame_sample.npy (n, 3) and frame_sample_index.npy
+    (n,), the row-major pixel indices as float64.  Returns {file name: shape}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_MAX_BYTES:
+        arrays = {"frame": frame}
+    else:
+        px = frame.reshape(-1, frame.shape[-1])
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(px.shape[0], min(px.shape[0], DUMP_SAMPLE_PIXELS), replace=False))
+        arrays = {"frame_sample": px[idx], "frame_sample_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name + ".npy": list(a.shape) for name, a in arrays.items()}
+
+
 def usable_cpus():
     """CPUs this process may really use: its affinity mask, capped by the cgroup's CPU quota (os.cpu_count() is the machine's)."""
     try:
@@ -268,7 +295,11 @@ def main():
     ap.add_argument("--in-library", action="store_true",
                     help="N GPUs from ONE process through vk_scene_create_multi (the library deals tiles, gathers on device 0) "
                          "instead of one process per GPU; run without torchrun")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/*.npy (float32; a fixed, seeded pixel sample when it exceeds 64 MiB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # `python bench.py --gpus N` (no launcher): start the N ranks ourselves, one process per GPU, as a CHILD process —
     # never exec: nothing in this process has touched the GPU yet, and nothing will — relay its output and exit with its code.
@@ -597,6 +628,9 @@ def main():
     main_res = run_workload(args.workload, args.steps, args.warmup, args.spp, want_cpu=(n_gpus == 1 and not args.no_cpu), bvh=args.bvh,
                             fast_accel=args.fast_accel, live_traffic=(n_gpus == 1 and world == 1 and not args.no_traffic and not rehearsal),
                             handed_over_tree=args.reference_tree, empirical=args.empirical_trees)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, main_res["_frame"])
     also = []
     handed_over = None
     frames = {}            # workload -> its frame on the tree as handed over
@@ -665,6 +699,8 @@ def main():
             out["distributed"] = r["distributed"]
         if r.get("in_library"):
             out["in_library"] = r["in_library"]
+        if dumped:
+            out["dumped_outputs"] = dumped
         print(json.dumps(out), flush=True)
         if r["verified"] and not r["verified"].get("ok", False):
             print("bench.py: the timed framebuffer does NOT match the oracle", file=sys.stderr)

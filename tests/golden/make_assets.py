@@ -2,17 +2,18 @@
 scene.rs:230,355-398,588,822) to gzip'd binary PPM (P6: the decoded 8-bit RGB bytes, row 0 = top, exactly the buffer
 `png::Reader::next_frame` fills) under tests/golden/assets/.  These are DATA fixtures: the PNG decode (`png 0.16.6`) is
 third-party and lossless, so any correct decoder yields the same bytes; the host mirror (vecchio_amd/host) reads the .ppm.gz
-where the reference reads the .png.  Run in the build container (the reference is not present on the GPU box):
-    python tests/golden/make_assets.py
+where the reference reads the .png.  Run where a checkout of the reference is at hand:
+    python tests/golden/make_assets.py <reference checkout>
 """
 import gzip
 import hashlib
 import os
+import sys
 
 import numpy as np
 from PIL import Image
 
-SRC = "/root/reference/assets"
+SRC = os.path.join(sys.argv[1], "assets")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
 os.makedirs(OUT, exist_ok=True)
 for name in ("earthmap", "bowser_face", "bowser_top", "bowser_back", "bowser_side", "twitter"):

@@ -2,16 +2,17 @@
 artefact, sample/therestofyourlife.png (HEAD cornell_box(), scene.rs:630-730, rendered by
 HEAD main.rs: 900x900, background 0).  The PNG stores Vec3::to_color output (vec3.rs:54-61:
 sqrt gamma, clamp 0.999, *256, truncate), so linear radiance ~ ((v + 0.5) / 256)^2.
-Run in the build container (the reference is not present on the GPU box):
-    python tests/golden/make_cornell_blocks.py
+Run where a checkout of the reference is at hand:
+    python tests/golden/make_cornell_blocks.py <reference checkout>
 """
 import json
 import os
+import sys
 
 import numpy as np
 from PIL import Image
 
-SRC = "/root/reference/sample/therestofyourlife.png"
+SRC = os.path.join(sys.argv[1], "sample", "therestofyourlife.png")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cornell_blocks.json")
 
 img = np.asarray(Image.open(SRC).convert("RGB")).astype(np.float64)

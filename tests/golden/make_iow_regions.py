@@ -15,15 +15,16 @@ horizon), Metal with fuzz 0, Lambertian::scatter's cosine law and Vec3::to_color
     glass_lower           lower half of the Dielectric(1.5) r=1 sphere at (0,1,0) (scene.rs:226-228): refracted ground/sky
 
 Region rectangles are (row0, row1, col0, col1) in PNG coordinates (row 0 = top), chosen by eye on the PNG.
-Run in the build container (the reference is not present on the GPU box):
-    python tests/golden/make_iow_regions.py
+Run where a checkout of the reference is at hand:
+    python tests/golden/make_iow_regions.py <reference checkout>
 """
 import os
+import sys
 
 import numpy as np
 from PIL import Image
 
-SRC = "/root/reference/sample/inoneweekend.png"
+SRC = os.path.join(sys.argv[1], "sample", "inoneweekend.png")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "iow_regions.npz")
 
 PER_PIXEL = {"sky_left": (0, 120, 0, 320), "sky_right": (0, 120, 860, 1024), "metal_cap": (70, 190, 560, 780)}

@@ -30,14 +30,15 @@ compared STATISTICALLY, through quantities that do not depend on those draws, or
 
 For every region the fixture holds BxB-pixel block means of the linear colour (inverse of Vec3::to_color, vec3.rs:54-61), the
 PNG's per-pixel noise (neighbour differences) and which blocks contain clamped pixels.
-Run in the build container (the reference is not present on the GPU box):   python tests/golden/make_nextweek_regions.py
+Run where a checkout of the reference is at hand:   python tests/golden/make_nextweek_regions.py <reference checkout>
 """
 import os
+import sys
 
 import numpy as np
 from PIL import Image
 
-SRC = "/root/reference/sample/thenextweek.png"
+SRC = os.path.join(sys.argv[1], "sample", "thenextweek.png")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "nextweek_regions.npz")
 B = 10
 REGIONS = {   # (row0, row1, col0, col1), multiples of B
