@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define VK_ABI_VERSION 6   /* 6: VK_SCENE_RCCL_GATHER, vk_scene_info.gather, vk_gather_backends; 5: rebuilt trees by default only where their exactness is proven; VK_SCENE_EMPIRICAL_TREES; vk_scene_info.tree */
+#define VK_ABI_VERSION 7   /* 7: progressive rendering (vk_progress_*; vk_scene_desc unchanged: descriptions stamped 6 are accepted); 6: VK_SCENE_RCCL_GATHER, vk_scene_info.gather, vk_gather_backends; 5: rebuilt trees by default only where their exactness is proven; VK_SCENE_EMPIRICAL_TREES; vk_scene_info.tree */
 
 /* ---- status codes (reference convention is panic!/unwrap, main.rs:166,202) ---------- */
 enum {
@@ -158,7 +158,7 @@ typedef struct vk_perlin {     /* material.rs:306-311 */
 
 /* ---- the flattened scene ------------------------------------------------------------ */
 typedef struct vk_scene_desc {
-    uint32_t abi_version;      /* must be VK_ABI_VERSION */
+    uint32_t abi_version;      /* VK_ABI_VERSION (6 is accepted too: the description has not changed since) */
     uint32_t n_bvh;            const vk_bvh_node *bvh;
     uint32_t n_spheres;        const vk_sphere *spheres;
     uint32_t n_moving_spheres; const vk_moving_sphere *moving_spheres;
@@ -400,6 +400,52 @@ int vk_scene_last_clamped_samples(vk_scene *scene, uint64_t *count_out);
 /* Exact re-treeing (see vk_scene_desc.flags): samples of the last render that were rendered by the second launch, on the tree as
  * handed over; waits for the render's end. */
 int vk_scene_last_requeued_samples(vk_scene *scene, uint64_t *count_out);
+
+/* ---- progressive rendering (ABI 7) ---------------------------------------------------
+ * replaces: nothing (the reference renders each frame in one go, main.rs:181-198).  A vk_progress accumulates ONE frame — one camera, one
+ * vk_render_params — over successive sample WINDOWS: a preview after every step, a stop when the image is good enough, a time budget
+ * spent in slices, short launches on a shared card.  params->samples_per_pixel at create is the frame's BUDGET: the steps together may
+ * render at most that many samples per pixel.
+ *
+ * Bit-identity.  Every sample is keyed by its index (RNG keyed by (seed, pixel, sample)) and pixel sums are exact 64-bit fixed point, so
+ * a step renders samples [samples_done, samples_done + n) of every pixel of the partition and adds them into running sums that live in
+ * the handle (one set per device of the scene).  After any sequence of steps the image written is, bit for bit, the image vk_render
+ * gives with the same params at samples_per_pixel = samples_done — as long as no sample was clamped (vk_progress_info.clamped_samples
+ * == 0): the clamp (see vk_stats.clamped_samples) is the one of the BUDGET's one-shot frame, so the final image of a frame rendered to
+ * its budget is vk_render's image of the budget exactly, clamped samples or not.
+ *
+ * Calls.  A step writes the running mean as vk_render / vk_render_device write theirs: f32 with y up, or with params->output_format ==
+ * VK_OUTPUT_RGB8 bytes with the top row first; only this partition's tiles are written.  n_samples == 0, samples_done + n_samples >
+ * budget, a null handle and the argument checks of vk_render each return VK_ERR_BAD_ARG, enqueue nothing and leave the handle as it was.
+ * The rule "at most one render in flight per vk_scene" covers vk_render and progress steps together: they may be interleaved on one
+ * scene (stream-ordered), the running sums belong to the handle.  Destroy the handle before its scene.                           */
+typedef struct vk_progress vk_progress;   /* opaque */
+enum { VK_PROGRESS_STDERR = 1 };          /* also keep the error moments (24 more bytes per pixel and device) */
+typedef struct vk_progress_info {
+    uint32_t samples_done;     /* samples 0 .. samples_done-1 of every pixel of the partition are in the sums */
+    uint32_t samples_budget;   /* params->samples_per_pixel at create: the frame's total, fixes the clamp */
+    uint32_t steps;            /* windows since create / reset */
+    uint32_t flags;            /* VK_PROGRESS_* of create */
+    uint64_t clamped_samples;  /* since create / reset (vk_stats.clamped_samples) */
+} vk_progress_info;
+int vk_progress_create(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t flags, vk_progress **out);
+/* blocking; out: a host buffer as vk_render's.  stats_out: this window's samples, kernel time and clamped samples */
+int vk_progress_step(vk_progress *pr, uint32_t n_samples, void *out, vk_stats *stats_out);
+/* as vk_render_device: d_out on the scene's device (devices[0] of a multi-device scene), enqueued on hip_stream without a host wait */
+int vk_progress_step_device(vk_progress *pr, uint32_t n_samples, void *d_out, void *hip_stream, vk_stats *stats_out);
+/* back to sample 0 (waits for the last step); cam NULL = keep the camera */
+int vk_progress_reset(vk_progress *pr, const vk_camera *cam);
+/* The batch-means standard error of the current mean, per component (host buffer, width*height*3 floats, y up; this partition's pixels
+ * only):   sqrt( (sum_j n_j m_j^2 - N m^2) / ((k - 1) N) )   with k the steps, n_j and m_j window j's length and own mean (from its exact
+ * sum), N = samples_done and m the running mean.  Needs VK_PROGRESS_STDERR and k >= 2 (else VK_ERR_BAD_ARG); waits for the last step.
+ * What it is NOT: it treats the windows as independent batches (they are: disjoint samples of independent RNG streams), but with k
+ * windows it is itself an estimate from k - 1 degrees of freedom — noisy for small k (k = 4: about 40 % off in either direction) — and
+ * a firefly (one bright sample) makes it heavy-tailed: its window's mean stands out, the estimate jumps, and a pixel whose fireflies
+ * have not been drawn yet reports an error far too small.  Not on the hot path.                                                  */
+int vk_progress_stderr(vk_progress *pr, float *out);
+/* waits for the last step */
+int vk_progress_get_info(vk_progress *pr, vk_progress_info *out);
+void vk_progress_destroy(vk_progress *pr);   /* NULL: nothing */
 
 /* test/diagnostic entry points (vk_debug_*) are declared in vecchio_amd_debug.h */
 

@@ -518,9 +518,23 @@ void judge_frame(vk_scene *s, int b) {
     }
 }
 
-// Enqueues one render of this call's tile partition into the f32 framebuffer d_out (device memory of s->device) on `st`.
+// Progressive rendering (vk_progress_*): what one window of a handle asks of one device part.  p->samples_per_pixel is the WINDOW's
+// length then (units, redo queues and the probe are sized by it); the clamp comes from the budget, so that clamping matches the one-shot
+// frame of `budget` samples and `budget` samples can never overflow the running sums.
+struct AccumDesc {
+    uint32_t sample_base;          // the window's first sample
+    uint32_t budget;               // the frame's total (vk_progress_info.samples_budget)
+    uint32_t done;                 // samples in the running sums after this window
+    long long *run;                // [width*height*3] running fixed-point sums, on the part's device
+    double *m2;                    // [width*height*3] sum of n_j m_j^2 (VK_PROGRESS_STDERR), or null
+    unsigned long long *clamped;   // running clamped-sample count
+    hipEvent_t ev_done;            // recorded behind the window's accumulate kernel
+};
+
+// Enqueues one render of this call's tile partition into the f32 framebuffer d_out (device memory of s->device) on `st`.  With `acc`
+// (progressive rendering): one window of samples, added into acc's running sums, d_out = their running mean.
 int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params *p, float *d_out, hipStream_t st, bool want_debug,
-    vk_stats *stats) {
+    vk_stats *stats, const AccumDesc *acc = nullptr) {
     HIP_TRY(hipSetDevice(s->device));
     const TileGeom g(p);
     KArgs A;
@@ -574,7 +588,8 @@ int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params
     A.counter = s->counter;
     A.clamped = reinterpret_cast<unsigned long long *>(s->counter) + 1;     // bytes 8..15 of the counter block
     A.launch_units = s->counter + 4;                                         // bytes 16..23: units pulled by each launch of a dual launch
-    A.accum_clamp = accum_clamp_for(p->samples_per_pixel);
+    A.accum_clamp = accum_clamp_for(acc ? acc->budget : p->samples_per_pixel);
+    A.sample_base = acc ? acc->sample_base : 0u;
     A.shade_defer = SHADE_DEFER;          // (C5: 1 / 2 / 4 / 8 -> 573 / 588 / 593 / 603-at-pw-2)
     if (s->env.shade_defer >= 1 && s->env.shade_defer <= 64) A.shade_defer = (uint32_t)s->env.shade_defer;   // diagnostics
     // scenes beyond an XCD's L2 (C5: a leaf every 6 box steps, every gather a possible L2 miss): pending sphere tests are served
@@ -601,6 +616,7 @@ int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params
         HIP_TRY(hipMemsetAsync(s->counter, 0, 32, st));
         int rc = tile_move<TM_ZERO_F32>(nullptr, d_out, p, g, st);
         if (rc != VK_OK) return rc;
+        if (acc) HIP_TRY(hipEventRecord(acc->ev_done, st));     // (every sample is (0,0,0): the running sums stay 0, so does their mean)
         HIP_TRY(hipEventRecord(s->ev1, st));
         s->last_timed = true;
         s->redo_last = false; s->dual_last = false;      // (nothing was launched: no second launch, no unit split to judge)
@@ -797,7 +813,17 @@ int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params
             s->plan_copied = true;
         } else s->plan_copied = false;
     }
-    {
+    if (acc) {
+        // progressive: the window's sums into the running sums, the running mean into d_out (the window's sums stay in s->accum until
+        // here, so the fallback above re-renders this window only and earlier windows are untouched)
+        uint32_t blocks = (uint32_t)((n_pixels + 255) / 256);
+        hipLaunchKernelGGL(accumulate_resolve_kernel, dim3(blocks), dim3(256), 0, st, (const long long *)A.accum, acc->run, acc->m2, d_out,
+                           p->width, p->height, p->samples_per_pixel, acc->done, A.tiles_x, A.tile_rank, A.tile_world,
+                           (const unsigned long long *)A.clamped, acc->clamped);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(acc->ev_done, st));
+        if (stats) stats->kernel_launches = 2;
+    } else {
         uint32_t blocks = (uint32_t)((n_pixels + 255) / 256);
         hipLaunchKernelGGL(resolve_kernel, dim3(blocks), dim3(256), 0, st, (const long long *)A.accum, d_out, p->width, p->height,
                            p->samples_per_pixel, A.tiles_x, A.tile_rank, A.tile_world);
@@ -811,20 +837,22 @@ int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params
 
 // One device: render (f32) and, for RGB8 output, the fused output stage of this partition.
 int enqueue_render_single(vk_scene *s, const vk_camera *cam, const vk_render_params *p, void *d_out, hipStream_t st, bool want_debug,
-    vk_stats *stats) {
-    if (p->output_format == VK_OUTPUT_F32) return enqueue_render_f32(s, cam, p, reinterpret_cast<float *>(d_out), st, want_debug, stats);
+    vk_stats *stats, const AccumDesc *acc) {
+    if (p->output_format == VK_OUTPUT_F32) return enqueue_render_f32(s, cam, p, reinterpret_cast<float *>(d_out), st, want_debug, stats, acc);
     HIP_TRY(hipSetDevice(s->device));
     int rc = ensure(s->fb, s->fb_bytes, (size_t)p->width * p->height * 3 * sizeof(float));
     if (rc != VK_OK) return rc;
-    rc = enqueue_render_f32(s, cam, p, s->fb, st, want_debug, stats);
+    rc = enqueue_render_f32(s, cam, p, s->fb, st, want_debug, stats, acc);
     if (rc != VK_OK) return rc;
     return tile_move<TM_CONVERT_U8>(s->fb, d_out, p, TileGeom(p), st);
 }
 
 // Multi-device group: part j renders the tiles {t : t = R + W*(j + n*i)} of this call's partition (R of W) on its
 // own device and stream, packs them into a slab (RGB8: through to_color, 4x smaller), the slab travels to devices[0] with
-// ONE peer copy (xGMI), and devices[0] scatters the slabs into the caller's image on the caller's stream.
-int enqueue_render_multi(vk_scene *grp, const vk_camera *cam, const vk_render_params *p, void *d_out, hipStream_t st0, vk_stats *stats) {
+// ONE peer copy (xGMI), and devices[0] scatters the slabs into the caller's image on the caller's stream.  acc (progressive rendering):
+// one descriptor per part, holding that part's running sums on its own device.
+int enqueue_render_multi(vk_scene *grp, const vk_camera *cam, const vk_render_params *p, void *d_out, hipStream_t st0, vk_stats *stats,
+    const AccumDesc *acc) {
     const uint32_t n = (uint32_t)grp->parts.size();
     const TileGeom g(p);
     const bool u8 = p->output_format == VK_OUTPUT_RGB8;
@@ -846,7 +874,7 @@ int enqueue_render_multi(vk_scene *grp, const vk_camera *cam, const vk_render_pa
         if (rc != VK_OK) return rc;
         vk_stats sj;
         memset(&sj, 0, sizeof(sj));
-        rc = enqueue_render_f32(q, cam, &pj, q->fb, q->stream, false, &sj);
+        rc = enqueue_render_f32(q, cam, &pj, q->fb, q->stream, false, &sj, acc ? &acc[j] : nullptr);
         if (rc != VK_OK) return rc;
         samples += sj.samples; launches += sj.kernel_launches;
         size_t bytes = (size_t)gj.n_local * 64u * slot_bytes;
@@ -908,14 +936,14 @@ int enqueue_render_multi(vk_scene *grp, const vk_camera *cam, const vk_render_pa
 }
 
 int enqueue_render(vk_scene *s, const vk_camera *cam, const vk_render_params *p, void *d_out, hipStream_t st, bool want_debug,
-    vk_stats *stats) {
+    vk_stats *stats, const AccumDesc *acc = nullptr) {
     int rc = check_render_args(s, cam, p);
     if (rc != VK_OK) return rc;
     if (!s->parts.empty()) {
         if (want_debug) return fail(VK_ERR_UNSUPPORTED, "per-sample debug output is single-device only");
-        return enqueue_render_multi(s, cam, p, d_out, st, stats);
+        return enqueue_render_multi(s, cam, p, d_out, st, stats, acc);
     }
-    return enqueue_render_single(s, cam, p, d_out, st, want_debug, stats);
+    return enqueue_render_single(s, cam, p, d_out, st, want_debug, stats, acc);
 }
 
 void destroy_one(vk_scene *s) {
@@ -1386,7 +1414,7 @@ int vk_scene_last_requeued_samples(vk_scene *s, uint64_t *out) {
 }
 
 static int render_host(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, void *out_host, vk_stats *stats_out,
-    float *debug_out) {
+    float *debug_out, const AccumDesc *acc = nullptr) {
     if (!out_host) return fail(VK_ERR_BAD_ARG, "null framebuffer");
     int rc = check_render_args(scene, cam, params);
     if (rc != VK_OK) return rc;
@@ -1404,7 +1432,7 @@ static int render_host(vk_scene *scene, const vk_camera *cam, const vk_render_pa
     double ms = 0.0;
     {
         memset(&st, 0, sizeof(st));
-        rc = enqueue_render(scene, cam, params, d_img, nullptr, debug_out != nullptr, &st);
+        rc = enqueue_render(scene, cam, params, d_img, nullptr, debug_out != nullptr, &st, acc);
         if (rc != VK_OK) return rc;
         HIP_TRY(hipStreamSynchronize(nullptr));
         uint64_t requeued = 0;
@@ -1453,6 +1481,218 @@ int vk_debug_render_samples(vk_scene *scene, const vk_camera *cam, const vk_rend
     if (!samples_out) return fail(VK_ERR_BAD_ARG, "null samples buffer");
     if (params && params->output_format != VK_OUTPUT_F32) return fail(VK_ERR_BAD_ARG, "per-sample debug output needs VK_OUTPUT_F32");
     return guarded([&]() -> int { return render_host(scene, cam, params, rgb_out, nullptr, samples_out); });
+}
+
+}  // extern "C"
+
+// ---- progressive rendering (ABI 7): one camera + one vk_render_params, running sums on every device part of the scene.  A step is an
+// ordinary render of the sample window [done, done + n) (KArgs::sample_base) whose resolve is replaced by accumulate_resolve_kernel.
+struct vk_progress {
+    vk_scene *scene = nullptr;
+    vk_camera cam;
+    vk_render_params params;       // samples_per_pixel = the budget
+    uint32_t flags = 0, done = 0, steps = 0;
+    struct Part {                  // one per device part (the scene itself for a one-device scene)
+        int device = 0;
+        long long *run = nullptr;
+        double *m2 = nullptr;
+        unsigned long long *clamped = nullptr;
+        hipEvent_t ev = nullptr;
+    };
+    std::vector<Part> parts;
+    size_t n_words = 0;            // width*height*3
+};
+
+namespace {
+
+void progress_free(vk_progress *pr) {
+    for (auto &q : pr->parts) {
+        (void)hipSetDevice(q.device);
+        if (q.ev) { (void)hipEventSynchronize(q.ev); (void)hipEventDestroy(q.ev); }
+        for (void *p : {(void *)q.run, (void *)q.m2, (void *)q.clamped}) if (p) (void)hipFree(p);
+    }
+    (void)hipGetLastError();
+    delete pr;
+}
+
+// waits for the handle's last step on every part
+int progress_wait(vk_progress *pr) {
+    for (auto &q : pr->parts) {
+        HIP_TRY(hipSetDevice(q.device));
+        HIP_TRY(hipEventSynchronize(q.ev));
+    }
+    return VK_OK;
+}
+
+// back to sample 0: the running sums, error moments and clamped count := 0 (after the last step, before anything later)
+int progress_zero(vk_progress *pr) {
+    int rc = progress_wait(pr);
+    if (rc != VK_OK) return rc;
+    for (auto &q : pr->parts) {
+        HIP_TRY(hipSetDevice(q.device));
+        HIP_TRY(hipMemset(q.run, 0, pr->n_words * sizeof(long long)));
+        if (q.m2) HIP_TRY(hipMemset(q.m2, 0, pr->n_words * sizeof(double)));
+        HIP_TRY(hipMemset(q.clamped, 0, sizeof(unsigned long long)));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipEventRecord(q.ev, nullptr));      // (progress_wait has an event to wait for before the first step)
+    }
+    pr->done = 0; pr->steps = 0;
+    return VK_OK;
+}
+
+// the argument checks of a step (nothing is enqueued, the handle is not touched when one fails); pw = the window's params
+int progress_step_args(vk_progress *pr, uint32_t n, vk_render_params &pw) {
+    if (!pr) return fail(VK_ERR_BAD_ARG, "null progress handle");
+    if (n == 0) return fail(VK_ERR_BAD_ARG, "n_samples must be >= 1");
+    if ((uint64_t)pr->done + n > pr->params.samples_per_pixel) return fail(VK_ERR_BAD_ARG, "samples_done + n_samples exceeds the budget");
+    pw = pr->params;
+    pw.samples_per_pixel = n;
+    return check_render_args(pr->scene, &pr->cam, &pw);
+}
+
+std::vector<AccumDesc> progress_descs(vk_progress *pr, uint32_t n) {
+    std::vector<AccumDesc> d(pr->parts.size());
+    for (size_t j = 0; j < d.size(); j++) {
+        const auto &q = pr->parts[j];
+        d[j].sample_base = pr->done; d[j].budget = pr->params.samples_per_pixel; d[j].done = pr->done + n;
+        d[j].run = q.run; d[j].m2 = q.m2; d[j].clamped = q.clamped; d[j].ev_done = q.ev;
+    }
+    return d;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_progress_create(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t flags, vk_progress **out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    *out = nullptr;
+    if (flags & ~(uint32_t)VK_PROGRESS_STDERR) return fail(VK_ERR_BAD_ARG, "unknown progress flags");
+    int rc = check_render_args(scene, cam, params);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        vk_progress *pr = new vk_progress;
+        pr->scene = scene; pr->cam = *cam; pr->params = *params; pr->flags = flags;
+        pr->n_words = (size_t)params->width * params->height * 3;
+        std::vector<vk_scene *> parts = scene->parts;
+        if (parts.empty()) parts.push_back(scene);
+        for (vk_scene *q : parts) {
+            vk_progress::Part P;
+            P.device = q->device;
+            pr->parts.push_back(P);
+            auto &R = pr->parts.back();
+            int e = VK_OK;
+            auto alloc = [&](void **ptr, size_t bytes) {
+                if (e == VK_OK && hipMalloc(ptr, bytes) != hipSuccess) { (void)hipGetLastError(); e = fail(VK_ERR_OOM, "out of device memory"); }
+            };
+            if (hipSetDevice(q->device) != hipSuccess) e = fail(VK_ERR_HIP, "hipSetDevice failed");
+            alloc(reinterpret_cast<void **>(&R.run), pr->n_words * sizeof(long long));
+            if (flags & VK_PROGRESS_STDERR) alloc(reinterpret_cast<void **>(&R.m2), pr->n_words * sizeof(double));
+            alloc(reinterpret_cast<void **>(&R.clamped), sizeof(unsigned long long));
+            if (e == VK_OK && hipEventCreateWithFlags(&R.ev, hipEventDisableTiming) != hipSuccess) e = fail(VK_ERR_HIP, "hipEventCreate failed");
+            if (e != VK_OK) { progress_free(pr); return e; }
+        }
+        int z = progress_zero(pr);
+        if (z != VK_OK) { progress_free(pr); return z; }
+        *out = pr;
+        return VK_OK;
+    });
+}
+
+int vk_progress_step(vk_progress *pr, uint32_t n_samples, void *out, vk_stats *stats_out) {
+    vk_render_params pw;
+    int rc = progress_step_args(pr, n_samples, pw);
+    if (rc != VK_OK) return rc;
+    if (!out) return fail(VK_ERR_BAD_ARG, "null framebuffer");
+    return guarded([&]() -> int {
+        const std::vector<AccumDesc> d = progress_descs(pr, n_samples);
+        int r = render_host(pr->scene, &pr->cam, &pw, out, stats_out, nullptr, d.data());
+        if (r != VK_OK) return r;
+        pr->done += n_samples; pr->steps++;
+        return VK_OK;
+    });
+}
+
+int vk_progress_step_device(vk_progress *pr, uint32_t n_samples, void *d_out, void *hip_stream, vk_stats *stats_out) {
+    vk_render_params pw;
+    int rc = progress_step_args(pr, n_samples, pw);
+    if (rc != VK_OK) return rc;
+    if (!d_out) return fail(VK_ERR_BAD_ARG, "null framebuffer");
+    return guarded([&]() -> int {
+        const std::vector<AccumDesc> d = progress_descs(pr, n_samples);
+        int r = enqueue_render(pr->scene, &pr->cam, &pw, d_out, reinterpret_cast<hipStream_t>(hip_stream), false, stats_out, d.data());
+        if (r != VK_OK) return r;
+        pr->done += n_samples; pr->steps++;
+        return VK_OK;
+    });
+}
+
+int vk_progress_reset(vk_progress *pr, const vk_camera *cam) {
+    if (!pr) return fail(VK_ERR_BAD_ARG, "null progress handle");
+    if (cam) {
+        int rc = check_render_args(pr->scene, cam, &pr->params);
+        if (rc != VK_OK) return rc;
+    }
+    return guarded([&]() -> int {
+        int rc = progress_zero(pr);
+        if (rc != VK_OK) return rc;
+        if (cam) pr->cam = *cam;
+        return VK_OK;
+    });
+}
+
+int vk_progress_get_info(vk_progress *pr, vk_progress_info *out) {
+    if (!pr || !out) return fail(VK_ERR_BAD_ARG, "null argument");
+    int rc = progress_wait(pr);
+    if (rc != VK_OK) return rc;
+    uint64_t clamped = 0;
+    for (auto &q : pr->parts) {
+        unsigned long long v = 0;
+        HIP_TRY(hipSetDevice(q.device));
+        HIP_TRY(hipMemcpy(&v, q.clamped, sizeof(v), hipMemcpyDeviceToHost));
+        clamped += v;
+    }
+    out->samples_done = pr->done; out->samples_budget = pr->params.samples_per_pixel; out->steps = pr->steps; out->flags = pr->flags;
+    out->clamped_samples = clamped;
+    return VK_OK;
+}
+
+// Batch means over the steps (not on the hot path): per component sqrt((sum_j n_j m_j^2 - N m^2) / ((k - 1) N)).  The parts' sums are
+// zero outside their own tiles, so the whole partition's are their sum.
+int vk_progress_stderr(vk_progress *pr, float *out) {
+    if (!pr || !out) return fail(VK_ERR_BAD_ARG, "null argument");
+    if (!(pr->flags & VK_PROGRESS_STDERR)) return fail(VK_ERR_BAD_ARG, "the handle was created without VK_PROGRESS_STDERR");
+    if (pr->steps < 2) return fail(VK_ERR_BAD_ARG, "the standard error needs two steps or more");
+    int rc = progress_wait(pr);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        std::vector<long long> run(pr->n_words, 0), r(pr->n_words);
+        std::vector<double> m2(pr->n_words, 0.0), m(pr->n_words);
+        for (auto &q : pr->parts) {
+            HIP_TRY(hipSetDevice(q.device));
+            HIP_TRY(hipMemcpy(r.data(), q.run, pr->n_words * sizeof(long long), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(m.data(), q.m2, pr->n_words * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < pr->n_words; i++) { run[i] += r[i]; m2[i] += m[i]; }
+        }
+        const vk_render_params &p = pr->params;
+        const uint32_t world = p.tile_world ? p.tile_world : 1u, tiles_x = (p.width + TILE - 1) / TILE;
+        const double N = (double)pr->done, k = (double)pr->steps;
+        for (uint32_t y = 0; y < p.height; y++)
+            for (uint32_t x = 0; x < p.width; x++) {
+                if (((y / TILE) * tiles_x + x / TILE) % world != p.tile_rank) continue;
+                for (int c = 0; c < 3; c++) {
+                    const size_t i = ((size_t)y * p.width + x) * 3 + c;
+                    const double mean = (double)run[i] / (double)ACCUM_SCALE / N;
+                    const double v = (m2[i] - N * mean * mean) / ((k - 1.0) * N);
+                    out[i] = (float)sqrt(v > 0.0 ? v : 0.0);
+                }
+            }
+        return VK_OK;
+    });
+}
+
+void vk_progress_destroy(vk_progress *pr) {
+    if (pr) progress_free(pr);
 }
 
 size_t vk_tile_slab_bytes(uint32_t width, uint32_t height, uint32_t output_format, uint32_t tile_rank, uint32_t tile_world) {

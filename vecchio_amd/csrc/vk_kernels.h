@@ -66,6 +66,9 @@ struct KArgs {
     uint2 *redo_list; uint32_t *redo_count; const uint32_t *redo_plan; uint32_t redo_region_cap; uint32_t list_mode;
     // diagnostic builds (-DVK_WAVE_TIMES, with the environment's VK_WAVE_TIMES=1): per wave {start, last unit pull, end}, 100 MHz ticks
     unsigned long long *wave_times;
+    // progressive rendering (vk_progress_step): this launch renders the sample WINDOW [sample_base, sample_base + C.spp) of every pixel;
+    // 0 for vk_render.  A unit's samples are numbered from it, so the RNG keys (seed, pixel, sample) are those of the one-shot frame.
+    uint32_t sample_base;
 };
 constexpr uint32_t REDO_REGIONS = 512u;
 constexpr uint32_t REDO_COUNT_STRIDE = 16u;        // uint32 words between two regions' counters
@@ -449,7 +452,7 @@ __device__ __forceinline__ void shade_refill_body(Lane &L, bool is_shade, bool e
             uint32_t xy = __float_as_uint(cold[CF_XY * 64 + lane]);
             size_t pix = (size_t)(xy >> 16) * C.width + (xy & 0xFFFFu);
             float4 *dbg = KARG(P, debug);
-            if (dbg) dbg[pix * C.spp + __float_as_uint(cold[CF_SAMPLE * 64 + lane])] = make_float4(L.acc.x, L.acc.y, L.acc.z,
+            if (dbg) dbg[pix * C.spp + (__float_as_uint(cold[CF_SAMPLE * 64 + lane]) - KARG(P, sample_base))] = make_float4(L.acc.x, L.acc.y, L.acc.z,
                 __uint_as_float(L.rng.ctr));
             long long *acc = KARG(P, accum);
             if (acc && isfinite(L.acc.x) && isfinite(L.acc.y) && isfinite(L.acc.z)) {   // main.rs:192-194; c += color (main.rs:193)
@@ -536,6 +539,7 @@ __device__ __forceinline__ void shade_refill_body(Lane &L, bool is_shade, bool e
             const uint32_t s1 = (uint32_t)(((uint64_t)C.spp * (chunk + 1)) / n_chunks);
             txy = ((tile % tiles_x) * TILE) | (((tile / tiles_x) * TILE) << 16);
             next = 0u; total = 64u * (s1 - s0);
+            s0 += KARG(P, sample_base);                                           // the window's first sample (0: vk_render)
             if (lane == 0) { wstate[WS_TXY] = txy; wstate[WS_S0] = s0; wstate[WS_TOTAL] = total; }
             }
         }
@@ -982,6 +986,34 @@ __global__ void resolve_kernel(const long long *accum, float *out, uint32_t widt
     out[(size_t)pix * 3 + 0] = ((float)a[0] * inv_scale) / n;
     out[(size_t)pix * 3 + 1] = ((float)a[1] * inv_scale) / n;
     out[(size_t)pix * 3 + 2] = ((float)a[2] * inv_scale) / n;
+}
+
+// Progressive rendering (vk_progress_step): behind a window's launches, for the pixels of this call's tile partition, ONE pass that
+//   * adds the window's fixed-point sums (accum, zeroed per window) into the handle's running sums — integer adds, exact: after any
+//     sequence of windows the running sums are the one-shot frame's sums of the same samples, bit for bit;
+//   * writes the running mean with resolve_kernel's arithmetic, so that the image is the one vk_render gives at spp = samples done;
+//   * with error moments on (m2 != null), adds n_j m_j^2 per component: m_j = the window's own mean, from its exact sum (batch means,
+//     vk_progress_stderr).
+// Thread 0 also adds the window's clamped-sample count (counter block bytes 8..15) to the handle's.
+__global__ void accumulate_resolve_kernel(const long long *accum, long long *run, double *m2, float *out, uint32_t width, uint32_t height,
+                                          uint32_t window, uint32_t done, uint32_t tiles_x, uint32_t tile_rank, uint32_t tile_world,
+                                          const unsigned long long *win_clamped, unsigned long long *run_clamped) {
+    uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix == 0) *run_clamped += *win_clamped;
+    uint32_t n_pixels = width * height;
+    if (pix >= n_pixels) return;
+    uint32_t x = pix % width, y = pix / width;
+    uint32_t tile = (y / TILE) * tiles_x + (x / TILE);
+    if (tile % tile_world != tile_rank) return;
+    float n = (float)done;
+    const float inv_scale = 1.0f / ACCUM_SCALE;
+    for (int c = 0; c < 3; c++) {
+        const size_t i = (size_t)pix * 3 + c;
+        const long long w = accum[i], r = run[i] + w;
+        run[i] = r;
+        out[i] = ((float)r * inv_scale) / n;
+        if (m2) { const double s = (double)w * (1.0 / (double)ACCUM_SCALE); m2[i] += s * s / (double)window; }
+    }
 }
 
 // Vec3::to_color (vec3.rs:44-61): sqrt gamma, hand-written clamp (NaN falls through it), *256, `as u32`

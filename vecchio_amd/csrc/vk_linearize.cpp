@@ -1273,7 +1273,8 @@ struct Builder {
 
     bool run() {
         if (!d) return fail(VK_ERR_BAD_ARG, "null scene description");
-        if (d->abi_version != VK_ABI_VERSION) return fail(VK_ERR_BAD_ARG, "abi version mismatch");
+        // (ABI 7 left vk_scene_desc as ABI 6 had it)
+        if (d->abi_version != VK_ABI_VERSION && d->abi_version != 6u) return fail(VK_ERR_BAD_ARG, "abi version mismatch");
         L.tie_base_rect = d->n_spheres; L.tie_base_box = d->n_spheres + d->n_rects;
         L.tie_base_list = d->n_spheres + d->n_rects + d->n_lists;
         if (!materials_and_textures()) return false;

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
 ASSETS_DIR = os.path.join(os.path.dirname(_HERE), "tests", "golden", "assets")
 
-VK_ABI_VERSION = 6
+VK_ABI_VERSION = 7
 VK_OK, VK_ERR_BAD_ARG, VK_ERR_UNSUPPORTED, VK_ERR_HIP, VK_ERR_NO_DEVICE, VK_ERR_OOM = range(6)
 
 (VK_KIND_NONE, VK_KIND_BVH, VK_KIND_SPHERE, VK_KIND_MOVING_SPHERE, VK_KIND_RECT, VK_KIND_LIST,
@@ -29,6 +29,7 @@ VK_SCENE_FAST_ACCEL = 1
 VK_SCENE_REFERENCE_TREE = 2
 VK_SCENE_EMPIRICAL_TREES = 4
 VK_SCENE_RCCL_GATHER = 8
+VK_PROGRESS_STDERR = 1
 
 
 def make_ref(kind, index, flip=False):
@@ -140,6 +141,11 @@ class PartInfo(C.Structure):
                 ("can_access_landing_device", C.c_uint32), ("kernel_ms", C.c_double)]
 
 
+class ProgressInfo(C.Structure):
+    _fields_ = [("samples_done", C.c_uint32), ("samples_budget", C.c_uint32), ("steps", C.c_uint32), ("flags", C.c_uint32),
+                ("clamped_samples", C.c_uint64)]
+
+
 VK_TREE_HANDED_OVER, VK_TREE_REBUILT_PROVEN, VK_TREE_REBUILT_EMPIRICAL, VK_TREE_REBUILT_FAST, VK_TREE_REBUILT_NEAR, VK_TREE_REBUILT_GRID = range(6)
 VK_GATHER_NONE, VK_GATHER_PEER_COPY, VK_GATHER_RCCL = range(3)
 
@@ -199,6 +205,8 @@ DEVICE_SYMBOLS = [
     "vk_render", "vk_render_device", "vk_to_color_device", "vk_scene_get_info", "vk_scene_create_multi",
     "vk_scene_last_kernel_ms", "vk_scene_last_clamped_samples", "vk_scene_last_requeued_samples", "vk_scene_part_info",
     "vk_tile_slab_bytes", "vk_pack_tiles_device", "vk_unpack_tiles_device",
+    "vk_progress_create", "vk_progress_step", "vk_progress_step_device", "vk_progress_reset", "vk_progress_stderr",
+    "vk_progress_get_info", "vk_progress_destroy",
 ]
 
 
@@ -239,6 +247,20 @@ def _bind(lib):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.vk_scene_get_info.restype = C.c_int
     lib.vk_scene_get_info.argtypes = [C.c_void_p, C.POINTER(SceneInfo)]
+    lib.vk_progress_create.restype = C.c_int
+    lib.vk_progress_create.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.vk_progress_step.restype = C.c_int
+    lib.vk_progress_step.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_progress_step_device.restype = C.c_int
+    lib.vk_progress_step_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_progress_reset.restype = C.c_int
+    lib.vk_progress_reset.argtypes = [C.c_void_p, C.POINTER(Camera)]
+    lib.vk_progress_stderr.restype = C.c_int
+    lib.vk_progress_stderr.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_progress_get_info.restype = C.c_int
+    lib.vk_progress_get_info.argtypes = [C.c_void_p, C.POINTER(ProgressInfo)]
+    lib.vk_progress_destroy.restype = None
+    lib.vk_progress_destroy.argtypes = [C.c_void_p]
 
 
 _dbg = None

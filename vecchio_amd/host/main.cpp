@@ -2,11 +2,15 @@
 // scene, build the BVH, upload once, then per Camera of cam_iter: render through the C ABI
 // (the call that replaces main.rs:181-198), write output_%04d.ppm, print the frame time.
 // The reference hard-codes scene/width/spp/depth (main.rs:28-29,159-167,171); here they are
-// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1]
+// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1]
+// steps > 1: each frame is rendered progressively (vk_progress_*) in `steps` equal sample windows; after each window the running image
+// is written to output_%04d_step%02d.ppm and the samples done and the image's mean relative standard error are printed.  The final
+// output_%04d.ppm is byte-identical to the one of steps = 1.
 // Texture images are read from ./assets (as in the reference) or $VECCHIO_ASSETS: <name>.ppm.gz, see host_api.h.
 #include <dlfcn.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -24,7 +28,7 @@ static T sym(void *h, const char *name) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <balls_demo|random_spheres_demo|random_spheres_iow|perlin_demo|bowser_demo|cornell_box|final_scene|"
-                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed]\n", argv[0]);
+                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps]\n", argv[0]);
         return 2;
     }
     const char *name = argv[1];
@@ -33,6 +37,9 @@ int main(int argc, char **argv) {
     uint32_t depth = argc > 4 ? (uint32_t)atoi(argv[4]) : 100;       // main.rs:29
     int frames = argc > 5 ? atoi(argv[5]) : 1;
     uint64_t seed = argc > 6 ? strtoull(argv[6], nullptr, 10) : 1;
+    uint32_t steps = argc > 7 ? (uint32_t)atoi(argv[7]) : 1;
+    if (steps < 1) steps = 1;
+    if (steps > spp) steps = spp;                                     // every window holds at least one sample
 
     std::string dir = argv[0];
     size_t slash = dir.find_last_of('/');
@@ -43,6 +50,10 @@ int main(int argc, char **argv) {
     auto p_render = sym<int (*)(vk_scene *, const vk_camera *, const vk_render_params *, float *, vk_stats *)>(h, "vk_render");
     auto p_destroy = sym<void (*)(vk_scene *)>(h, "vk_scene_destroy");
     auto p_err = sym<const char *(*)()>(h, "vk_last_error");
+    auto p_pcreate = sym<int (*)(vk_scene *, const vk_camera *, const vk_render_params *, uint32_t, vk_progress **)>(h, "vk_progress_create");
+    auto p_pstep = sym<int (*)(vk_progress *, uint32_t, void *, vk_stats *)>(h, "vk_progress_step");
+    auto p_pstderr = sym<int (*)(vk_progress *, float *)>(h, "vk_progress_stderr");
+    auto p_pdestroy = sym<void (*)(vk_progress *)>(h, "vk_progress_destroy");
 
     fprintf(stderr, "Generating scene...\n");                        // main.rs:157
     vkh_scene *hs = vkh_scene_build(name, seed);
@@ -64,7 +75,34 @@ int main(int argc, char **argv) {
     while (file_idx < frames && vkh_scene_next_camera(hs, &cam)) {   // main.rs:176
         auto start = std::chrono::steady_clock::now();
         vk_stats st{};
-        if (p_render(scene, &cam, &rp, pixels.data(), &st) != VK_OK) { fprintf(stderr, "vk_render: %s\n", p_err()); return 1; }
+        if (steps == 1) {
+            if (p_render(scene, &cam, &rp, pixels.data(), &st) != VK_OK) { fprintf(stderr, "vk_render: %s\n", p_err()); return 1; }
+        } else {
+            vk_progress *pr = nullptr;
+            if (p_pcreate(scene, &cam, &rp, VK_PROGRESS_STDERR, &pr) != VK_OK) { fprintf(stderr, "vk_progress_create: %s\n", p_err()); return 1; }
+            std::vector<float> err(pixels.size());
+            uint32_t done = 0;
+            for (uint32_t k = 0; k < steps; k++) {
+                const uint32_t n = (uint32_t)((uint64_t)spp * (k + 1) / steps) - done;
+                vk_stats sw{};
+                if (p_pstep(pr, n, pixels.data(), &sw) != VK_OK) { fprintf(stderr, "vk_progress_step: %s\n", p_err()); return 1; }
+                done += n;
+                st.samples += sw.samples; st.kernel_ms += sw.kernel_ms; st.kernel_launches += sw.kernel_launches;
+                char sfn[64];
+                snprintf(sfn, sizeof sfn, "output_%04d_step%02u.ppm", file_idx, k);
+                if (vkh_write_ppm(sfn, pixels.data(), width, height)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }
+                // mean relative standard error over the pixel components with a non-zero mean (needs two windows)
+                double rel = 0.0; size_t cnt = 0;
+                if (k >= 1) {
+                    if (p_pstderr(pr, err.data()) != VK_OK) { fprintf(stderr, "vk_progress_stderr: %s\n", p_err()); return 1; }
+                    for (size_t i = 0; i < pixels.size(); i++)
+                        if (pixels[i] > 0.0f && std::isfinite(err[i])) { rel += (double)err[i] / (double)pixels[i]; cnt++; }
+                }
+                if (k >= 1) fprintf(stderr, "  %s: %u/%u samples, mean relative standard error %.4f\n", sfn, done, spp, cnt ? rel / (double)cnt : 0.0);
+                else fprintf(stderr, "  %s: %u/%u samples, mean relative standard error n/a (one window)\n", sfn, done, spp);
+            }
+            p_pdestroy(pr);
+        }
         char fn[64];
         snprintf(fn, sizeof fn, "output_%04d.ppm", file_idx);         // main.rs:201
         if (vkh_write_ppm(fn, pixels.data(), width, height)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }

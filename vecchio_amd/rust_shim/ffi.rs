@@ -11,11 +11,12 @@ use std::ffi::CStr;
 use std::os::raw::{c_char, c_int, c_void};
 
 pub type vk_ref = u32;
-pub const VK_ABI_VERSION: u32 = 6;
+pub const VK_ABI_VERSION: u32 = 7;
 pub const VK_SCENE_FAST_ACCEL: u32 = 1;
 pub const VK_SCENE_REFERENCE_TREE: u32 = 2;
 pub const VK_SCENE_EMPIRICAL_TREES: u32 = 4;
 pub const VK_SCENE_RCCL_GATHER: u32 = 8;
+pub const VK_PROGRESS_STDERR: u32 = 1;
 pub const VK_REF_FLIP: u32 = 0x0800_0000;
 pub const VK_KIND_BVH: u32 = 1;
 pub const VK_KIND_SPHERE: u32 = 2;
@@ -77,7 +78,11 @@ pub struct vk_render_params {
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_stats { pub samples: u64, pub seconds: f64, pub kernel_ms: f64, pub kernel_launches: u32, pub scene_in_lds: u32, pub clamped_samples: u64 }
 
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_progress_info { pub samples_done: u32, pub samples_budget: u32, pub steps: u32, pub flags: u32, pub clamped_samples: u64 }
+
 #[repr(C)] pub struct vk_scene { _private: [u8; 0] }
+#[repr(C)] pub struct vk_progress { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -95,6 +100,13 @@ extern "C" {
     pub fn vk_tile_slab_bytes(width: u32, height: u32, output_format: u32, tile_rank: u32, tile_world: u32) -> usize;
     pub fn vk_pack_tiles_device(scene: *mut vk_scene, d_fb: *const c_void, width: u32, height: u32, output_format: u32, tile_rank: u32, tile_world: u32, d_slab: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn vk_unpack_tiles_device(scene: *mut vk_scene, d_slab: *const c_void, width: u32, height: u32, output_format: u32, tile_rank: u32, tile_world: u32, d_img: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn vk_progress_create(scene: *mut vk_scene, cam: *const vk_camera, params: *const vk_render_params, flags: u32, out: *mut *mut vk_progress) -> c_int;
+    pub fn vk_progress_step(pr: *mut vk_progress, n_samples: u32, out: *mut c_void, stats: *mut vk_stats) -> c_int;
+    pub fn vk_progress_step_device(pr: *mut vk_progress, n_samples: u32, d_out: *mut c_void, stream: *mut c_void, stats: *mut vk_stats) -> c_int;
+    pub fn vk_progress_reset(pr: *mut vk_progress, cam: *const vk_camera) -> c_int;
+    pub fn vk_progress_stderr(pr: *mut vk_progress, out: *mut f32) -> c_int;
+    pub fn vk_progress_get_info(pr: *mut vk_progress, out: *mut vk_progress_info) -> c_int;
+    pub fn vk_progress_destroy(pr: *mut vk_progress);
 }
 
 /// What `flatten()` pushes into (flatten.rs).  One record per Arc; shared Arcs are de-duplicated
@@ -163,3 +175,37 @@ impl GpuScene {
     }
 }
 impl Drop for GpuScene { fn drop(&mut self) { unsafe { vk_scene_destroy(self.handle) } } }
+
+/// One frame accumulated over sample windows (vk_progress_*): `step` renders the next `n` samples per pixel and leaves the running mean
+/// in `pixels` — bit for bit what `GpuScene::render` gives at that many samples.  Borrows the scene: it is dropped before it.
+pub struct GpuProgress<'a> { handle: *mut vk_progress, _scene: &'a GpuScene }
+
+impl GpuScene {
+    /// `params.samples_per_pixel` is the frame's budget; `with_stderr` keeps the error moments for `stderr`.
+    pub fn progress(&self, cam: &vk_camera, params: &vk_render_params, with_stderr: bool) -> Result<GpuProgress<'_>, std::io::Error> {
+        let mut h: *mut vk_progress = std::ptr::null_mut();
+        check(unsafe { vk_progress_create(self.handle, cam, params, if with_stderr { VK_PROGRESS_STDERR } else { 0 }, &mut h) })?;
+        Ok(GpuProgress { handle: h, _scene: self })
+    }
+}
+
+impl<'a> GpuProgress<'a> {
+    pub fn step(&mut self, n: u32, pixels: &mut [[f32; 3]]) -> Result<vk_stats, std::io::Error> {
+        let mut st = vk_stats::default();
+        check(unsafe { vk_progress_step(self.handle, n, pixels.as_mut_ptr() as *mut c_void, &mut st) })?;
+        Ok(st)
+    }
+    /// per-component standard error of the running mean (batch means over the steps; needs `with_stderr` and two steps)
+    pub fn stderr(&mut self, out: &mut [[f32; 3]]) -> Result<(), std::io::Error> {
+        check(unsafe { vk_progress_stderr(self.handle, out.as_mut_ptr() as *mut f32) })
+    }
+    pub fn info(&mut self) -> Result<vk_progress_info, std::io::Error> {
+        let mut i = vk_progress_info::default();
+        check(unsafe { vk_progress_get_info(self.handle, &mut i) })?;
+        Ok(i)
+    }
+    pub fn reset(&mut self, cam: Option<&vk_camera>) -> Result<(), std::io::Error> {
+        check(unsafe { vk_progress_reset(self.handle, cam.map_or(std::ptr::null(), |c| c as *const vk_camera)) })
+    }
+}
+impl<'a> Drop for GpuProgress<'a> { fn drop(&mut self) { unsafe { vk_progress_destroy(self.handle) } } }

@@ -4,6 +4,7 @@ HostScene  = a scene built by the C++ mirror of scene.rs (libvecchio_host.so) an
              into a vk_scene_desc (what the Rust shim's flatten() would hand over).
 DeviceScene = that description uploaded through the C ABI (vk_scene_create) to one MI355X;
              render() is one call of the drop-in for main.rs:181-198.
+Progress   = one frame of a DeviceScene accumulated over successive sample windows (vk_progress_*).
 """
 import ctypes as C
 
@@ -140,6 +141,11 @@ class DeviceScene:
         check(self._lib, self._lib.vk_unpack_tiles_device(self._h, C.c_void_p(d_slab), width, height, output_format, tile_rank, tile_world,
                                                           C.c_void_p(d_img), C.c_void_p(stream or 0)))
 
+    def progress(self, cam, params, stderr=False):
+        """A progressive render of ONE frame (vk_progress_create): params.samples_per_pixel is the budget, step(n) renders the next n
+        samples per pixel and returns the running mean — bit for bit the image render() gives at samples_per_pixel = samples done."""
+        return Progress(self, cam, params, stderr)
+
     def to_color_device(self, d_rgb, width, height, d_rgb8, stream=None):
         check(self._lib, self._lib.vk_to_color_device(self._h, C.c_void_p(d_rgb), width, height, C.c_void_p(d_rgb8), C.c_void_p(stream or 0)))
 
@@ -147,6 +153,71 @@ class DeviceScene:
         if self._h:
             self._lib.vk_scene_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Progress:
+    """vk_progress handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed)."""
+
+    def __init__(self, scene, cam, params, stderr=False):
+        self._lib = scene._lib
+        self._scene = scene
+        self.params = params
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_progress_create(scene._h, C.byref(cam), C.byref(params),
+                                                      ffi.VK_PROGRESS_STDERR if stderr else 0, C.byref(h)))
+        self._h = h
+
+    def step(self, n, out=None):
+        """Render the next n samples per pixel; returns (image, vk_stats of the window): float32 (height, width, 3) with y = 0 the bottom
+        row, or uint8 with row 0 the top row (VK_OUTPUT_RGB8).  Only this partition's pixels of `out` are written."""
+        p = self.params
+        dt = np.uint8 if p.output_format == ffi.VK_OUTPUT_RGB8 else np.float32
+        if out is None:
+            out = np.zeros((p.height, p.width, 3), dtype=dt)
+        assert out.dtype == dt and out.flags.c_contiguous and out.size == p.width * p.height * 3
+        stats = ffi.Stats()
+        check(self._lib, self._lib.vk_progress_step(self._h, n, out.ctypes.data_as(C.c_void_p), C.byref(stats)))
+        return out, stats
+
+    def step_device(self, n, d_ptr, stream=None):
+        """Enqueue the next n samples per pixel; the running mean goes to device memory at d_ptr on `stream` (no host sync)."""
+        stats = ffi.Stats()
+        check(self._lib, self._lib.vk_progress_step_device(self._h, n, C.c_void_p(d_ptr), C.c_void_p(stream or 0), C.byref(stats)))
+        return stats
+
+    def stderr(self):
+        """Batch-means standard error of the running mean, float32 (height, width, 3), y = 0 the bottom row (needs stderr=True and two
+        steps or more)."""
+        p = self.params
+        out = np.zeros((p.height, p.width, 3), np.float32)
+        check(self._lib, self._lib.vk_progress_stderr(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def info(self):
+        inf = ffi.ProgressInfo()
+        check(self._lib, self._lib.vk_progress_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def reset(self, cam=None):
+        """Back to sample 0, with a new camera or the same one."""
+        check(self._lib, self._lib.vk_progress_reset(self._h, C.byref(cam) if cam is not None else None))
+
+    def close(self):
+        if self._h:
+            self._lib.vk_progress_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:
