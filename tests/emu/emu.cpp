@@ -49,6 +49,8 @@ static DScene scene_view(const LinearScene &LS, std::vector<DItem> &both) {
         use_grid(S);
         // (test switch: no dilation — the walk then visits the cells on the ray's exact path only, and part F's control shows what is lost)
         if (const char *e = getenv("EMU_GRID_NO_DILATION")) { if (e[0] == '1') { S.grid.k = 0.0f; S.grid.slack = 0.0f; } }
+        // (the same for the large spheres' common gate alone: the box around them as it stands)
+        if (const char *e = getenv("EMU_GRID_NO_GATE_DILATION")) { if (e[0] == '1') { S.grid.gscale = 0.0f; S.grid.gextra = 0.0f; } }
         // the grid form: a failed segment requeues its sample (trace_one: the whole sample again on reference_view), whether the device
         // walks the grid from LDS or from global memory
         return S;
@@ -820,8 +822,11 @@ int emu_unit_chain(const vk_scene_desc *desc, uint32_t sidx, const float o[3], c
 // eligible for the grid form): the closest hit of the grid walk — begin_segment, grid_step, prim_step, exactly as the device runs them
 // — against the closest hit over ALL spheres, tested one by one with the same Sphere::hit arithmetic.  Rays where they hurt: origins on
 // spheres, in them, far away (out to 1e4), directions along the layer, and lines that pass a random sphere at (1 + delta) radii, delta
-// where the f32 discriminant reports hits that are not there.  counts = {rays, rays with a hit, rays whose two answers differ};
-// viol = the first such ray (o, d, T grid, T brute force).
+// where the f32 discriminant reports hits that are not there.  The spheres tested for every segment (refs[0, n_always): the ground, the
+// large ones behind their common gate) are few among hundreds: a quarter of the rays past a sphere pass one of THEM, and one ray in eight
+// starts near the layer and passes one of them — far from the layer, such a sphere's false roots lie farther from it than anything
+// measured at the layer allows for.  counts = {rays, rays with a hit, rays whose two answers differ}; viol = the first such ray (o, d,
+// T grid, T brute force).
 int emu_grid_claims(const vk_scene_desc *desc, uint64_t n, uint64_t seed, uint64_t counts[3], float viol[8]) {
     LinearScene LS;
     int st = linearize_env(desc, LS, g_err);
@@ -834,24 +839,35 @@ int emu_grid_claims(const vk_scene_desc *desc, uint64_t n, uint64_t seed, uint64
     Lcg g(seed);
     counts[0] = counts[1] = counts[2] = 0;
     const double U24 = 1.0 / 16777216.0;
-    const uint32_t ns = S.n_spheres;
+    const uint32_t ns = S.n_spheres, n_alw = S.grid.n_always;
+    const DGrid &G = S.grid;
     for (uint64_t it = 0; it < n; it++) {
-        const DSphere sp = S.spheres[(uint32_t)(g.uni() * ns) % ns];
-        const double R = sp.r, c[3] = {sp.cx, sp.cy, sp.cz};
-        // the origin: on a sphere, inside one, near, far
-        const double pick = g.uni();
-        const double rho = pick < 0.3 ? R * (1.0 + 1e-4) : pick < 0.4 ? R * g.uni() : pick < 0.7 ? g.log_uni(1.5 * R, 50.0) : g.log_uni(50.0, 1e4);
-        double od[3] = {g.uni() - .5, g.uni() - .5, g.uni() - .5};
-        if (g.uni() < 0.5) od[1] = std::fabs(od[1]) * (g.uni() < 0.5 ? 1.0 : 0.05);        // above the layer, often low above it
-        const double on = std::sqrt(od[0] * od[0] + od[1] * od[1] + od[2] * od[2]) + 1e-30;
-        const V3 o = v3((float)(c[0] + od[0] / on * rho), (float)(c[1] + od[1] / on * rho), (float)(c[2] + od[2] / on * rho));
-        // the direction: anywhere, along the layer, or past ANOTHER sphere at (1 + delta) of its radius
+        // the origin: on a sphere, inside one, near, far — or near the layer: in its box or up to four times its height above it
+        const bool at_layer = n_alw != 0u && g.uni() < 0.125;
+        V3 o;
+        if (at_layer) {
+            const double hy = (double)G.hi[1] - (double)G.lo[1];
+            o = v3((float)(G.lo[0] + g.uni() * ((double)G.hi[0] - G.lo[0])), (float)(G.lo[1] + g.uni() * 5.0 * hy),
+                   (float)(G.lo[2] + g.uni() * ((double)G.hi[2] - G.lo[2])));
+        } else {
+            const DSphere sp = S.spheres[(uint32_t)(g.uni() * ns) % ns];
+            const double R = sp.r, c[3] = {sp.cx, sp.cy, sp.cz};
+            const double pick = g.uni();
+            const double rho = pick < 0.3 ? R * (1.0 + 1e-4) : pick < 0.4 ? R * g.uni() : pick < 0.7 ? g.log_uni(1.5 * R, 50.0) : g.log_uni(50.0, 1e4);
+            double od[3] = {g.uni() - .5, g.uni() - .5, g.uni() - .5};
+            if (g.uni() < 0.5) od[1] = std::fabs(od[1]) * (g.uni() < 0.5 ? 1.0 : 0.05);        // above the layer, often low above it
+            const double on = std::sqrt(od[0] * od[0] + od[1] * od[1] + od[2] * od[2]) + 1e-30;
+            o = v3((float)(c[0] + od[0] / on * rho), (float)(c[1] + od[1] / on * rho), (float)(c[2] + od[2] / on * rho));
+        }
+        // the direction: anywhere, along the layer, or past ANOTHER sphere at (1 + delta) of its radius — one tested for every segment
+        // from near the layer, and for a quarter of the other rays
         double dd[3];
-        const double kind = g.uni();
+        const double kind = at_layer ? 1.0 : g.uni();
         if (kind < 0.25) { dd[0] = g.uni() - .5; dd[1] = g.uni() - .5; dd[2] = g.uni() - .5; }
         else if (kind < 0.45) { dd[0] = g.uni() - .5; dd[1] = (g.uni() - .5) * 0.02; dd[2] = g.uni() - .5; }
         else {
-            const DSphere tq = S.spheres[(uint32_t)(g.uni() * ns) % ns];
+            const bool alw = n_alw != 0u && (at_layer || g.uni() < 0.25);
+            const DSphere tq = alw ? S.spheres[VKD_INDEX(S.grid_refs[(uint32_t)(g.uni() * n_alw) % n_alw])] : S.spheres[(uint32_t)(g.uni() * ns) % ns];
             const double tr = tq.r, tc[3] = {tq.cx, tq.cy, tq.cz};
             double oc[3] = {tc[0] - o.x, tc[1] - o.y, tc[2] - o.z};
             const double dist = std::sqrt(oc[0] * oc[0] + oc[1] * oc[1] + oc[2] * oc[2]) + 1e-30;

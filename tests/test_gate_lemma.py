@@ -269,3 +269,42 @@ def test_the_grids_dilation_is_not_idle(lem, monkeypatch):
     assert lem.emu_grid_claims(hs.desc, 150_000, 1, cnt, v) == 0
     print(f"no dilation: {cnt[2]} of {cnt[0]} rays differ")
     assert cnt[2] > 20
+
+
+# The large spheres' common gate, against large spheres FAR from the layer.  A world of the grid form: a 10 x 10 layer of r = 0.2 spheres
+# at pitch 1, a ground sphere, and one large sphere (2.5 .. 64 median radii: behind the common gate) 2 000 or 10 000 from the layer.  From
+# an origin near the layer such a sphere's false roots lie up to b (rho + R) from it, three orders of magnitude beyond any dilation
+# measured at the layer; the gate must be dilated by the gated spheres' OWN distance and radius.  The same sphere standing in the layer is
+# the control every version of the gate passed.
+FAR_SPHERES = {"r0.6_at_2000": ((2000.0, 0.6, 5.0), 0.6), "r2_at_10000": ((10000.0, 2.0, 5.0), 2.0), "r0.6_in_the_layer": ((5.0, 0.6, 5.0), 0.6)}
+
+
+def far_sphere_claims(lem, which, n, seed):
+    from test_retree import far_sphere_world
+    lem.emu_grid_claims.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+    g, desc = far_sphere_world(*FAR_SPHERES[which])
+    cnt = (C.c_uint64 * 3)(); v = (C.c_float * 8)()
+    assert lem.emu_grid_claims(desc, n, seed, cnt, v) == 0, "not a world the grid form applies to"
+    return cnt, v
+
+
+@pytest.mark.parametrize("which", sorted(FAR_SPHERES))
+def test_the_large_spheres_gate_holds_for_spheres_far_from_the_layer(which, lem, monkeypatch):
+    for k in ("EMU_GRID_NO_DILATION", "EMU_GRID_NO_GATE_DILATION", "EMU_GRID"):
+        monkeypatch.delenv(k, raising=False)
+    for seed in (1, 2):
+        cnt, v = far_sphere_claims(lem, which, 400_000, seed)
+        assert cnt[2] == 0, f"{which}: {cnt[2]} of {cnt[0]} rays, e.g. o {list(v[0:3])} d {list(v[3:6])} grid {v[6]} all spheres {v[7]}"
+        assert cnt[1] > 0.5 * cnt[0]
+        print(f"{which} seed {seed}: 0 of {cnt[0]} rays ({cnt[1]} with a hit)")
+
+
+def test_the_large_spheres_gate_dilation_is_not_idle(lem, monkeypatch):
+    """control of the test above: with the common gate's dilation switched off (the box around the large spheres as it stands) the far
+    spheres' candidates ARE missed"""
+    monkeypatch.delenv("EMU_GRID_NO_DILATION", raising=False)
+    monkeypatch.setenv("EMU_GRID_NO_GATE_DILATION", "1")
+    for which in ("r0.6_at_2000", "r2_at_10000"):
+        cnt, v = far_sphere_claims(lem, which, 400_000, 1)
+        print(f"{which}, no gate dilation: {cnt[2]} of {cnt[0]} rays differ")
+        assert cnt[2] > 20

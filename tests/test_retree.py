@@ -233,10 +233,19 @@ class LayerWorld(SphereCrowd):
     """Worlds the GRID form applies to (vk_linearize.cpp rt_build_grid): hundreds of small spheres in a layer across y — on a jittered
     grid, in rows, in a ring, or scattered; layers far from the coordinate origin (rounding of the cell arithmetic), very thin and four
     times thicker ones, radii mixed within the 2.5-median-radii class — plus a ground sphere and a few large ones, random tree shapes as
-    in SphereCrowd; cameras inside the layer, above it, far from it, grazing it."""
+    in SphereCrowd; cameras inside the layer, above it, far from it, grazing it.  far_gated: one or two more large spheres (2.5 .. 64
+    median radii: behind the large spheres' common gate) 10^2 .. 10^4 outside the layer, a camera in or just above the layer grazing one
+    of them with a narrow view — from there such a sphere's false roots lie farther from it than anything measured at the layer; layers
+    of at most 20 x 20 spheres (staged in LDS on the device)."""
+    def __init__(self, seed, far_gated=False):
+        super().__init__(seed)
+        self.far_gated = far_gated
+
     def build(self, far=None):
         r = self.r
         n_side = int(r.choice([9, 14, 24, 40]))
+        if self.far_gated:
+            n_side = min(n_side, 20)
         pitch = float(r.choice([0.5, 1.0, 2.5]))
         rad = float(r.choice([0.05, 0.2, 0.45])) * pitch
         centre = np.array([0.0, 0.0, 0.0]) if r.uniform() < 0.5 else r.uniform(-1.0, 1.0, 3) * np.array([3000.0, 40.0, 3000.0])
@@ -263,6 +272,14 @@ class LayerWorld(SphereCrowd):
         for _ in range(int(r.integers(0, 4))):                                       # large spheres standing in the layer
             big = rad * float(r.uniform(4.0, 9.0))
             objs.append(self.one(centre + np.array([r.uniform(-3, 3) * pitch, big, r.uniform(-3, 3) * pitch]), big, m=self.surface[int(r.integers(0, 4))]))
+        gated = []
+        if self.far_gated:
+            for _ in range(int(r.integers(1, 3))):
+                big, dist, a = rad * float(r.uniform(3.0, 40.0)), float(np.exp(r.uniform(np.log(1e2), np.log(1e4)))), r.uniform(0, 6.28)
+                lift = big if r.uniform() < 0.5 else big + r.uniform(0.0, 0.2) * dist                # on the ground's level, or raised
+                c = centre + np.array([(0.5 * n_side * pitch + dist) * np.cos(a), lift, (0.5 * n_side * pitch + dist) * np.sin(a)])
+                gated.append((c, big))
+                objs.append(self.one(c, big, m=self.surface[int(r.integers(0, 4))]))
         order = r.permutation(len(objs))
         world, _ = self.tree([objs[i] for i in order])
         desc = self.d.finish(world, [])
@@ -278,18 +295,40 @@ class LayerWorld(SphereCrowd):
         else:              # grazing
             lf = centre + np.array([2.0 * ext * np.cos(ang), 3.0 * rad, 2.0 * ext * np.sin(ang)]); la = centre + np.array([0.0, rad, 0.0])
         cam = camera(tuple(float(x) for x in lf), tuple(float(x) for x in la), vfov=float(r.choice([3.0, 25.0, 60.0])) if view != 2 else 2.0)
+        if self.far_gated:        # in or just above the layer, the view grazing a far sphere's rim
+            c, big = gated[int(r.integers(0, len(gated)))]
+            b = r.uniform(0, 6.28)
+            lf = centre + np.array([0.3 * ext * np.cos(b), float(r.choice([2.5, 4.0, 8.0])) * rad, 0.3 * ext * np.sin(b)])
+            w = (c - lf) / np.linalg.norm(c - lf)
+            side = np.cross(w, r.normal(size=3)); side /= np.linalg.norm(side)
+            la = c + side * big * r.uniform(1.0, 1.5)
+            cam = camera(tuple(float(x) for x in lf), tuple(float(x) for x in la), vfov=float(r.choice([0.2, 1.0, 4.0])))
         return desc, cam, params(32, 24, 3, max_depth=int(r.choice([3, 12, 50])), seed=int(r.integers(1, 1000)),
                                  integrator=ffi.VK_INTEGRATOR_SCATTER, background=ffi.VK_BACKGROUND_SKY)
 
 
-@pytest.mark.parametrize("seed", range(40))
+def far_sphere_world(c, rad):
+    """the world of the large spheres' gate test (tests/test_gate_lemma.py part F): a 10 x 10 layer of r = 0.2 spheres at pitch 1, a
+    ground sphere of radius 1 000, and one large sphere of radius `rad` at `c`; returns (the generator, which keeps the arrays alive;
+    the description)"""
+    g = SphereCrowd(1)
+    m = g.surface[0]
+    objs = [g.one((float(i), 0.2, float(j)), 0.2, m=m) for i in range(10) for j in range(10)]
+    objs.append(g.one((5.0, -1000.0, 5.0), 1000.0, m=m))                       # the ground: tested for every segment, never gated
+    objs.append(g.one(c, rad, m=g.surface[2]))
+    world, _ = g.tree(objs)
+    return g, g.d.finish(world, [])
+
+
+@pytest.mark.parametrize("seed", range(56))
 def test_grid_form_on_layer_worlds_is_the_handed_over_tree_per_sample(seed, oracle, emu, built, monkeypatch):
-    """the GRID form on forty random layer worlds: every sample the oracle's (equal draw counts, |dRGB|) and the handed-over tree's bit
-    for bit; the grid walk's closest hit the closest hit over ALL spheres for 20 000 adversarial rays (tests/emu emu_grid_claims); and
-    the same world on the near / unit form's TREE (EMU_GRID=0), which a scene too large for LDS is walked on"""
+    """the GRID form on forty random layer worlds, and sixteen with large spheres far outside the layer (seeds 40 on): every sample the
+    oracle's (equal draw counts, |dRGB|) and the handed-over tree's bit for bit; the grid walk's closest hit the closest hit over ALL
+    spheres for 20 000 adversarial rays, 60 000 with the far spheres (tests/emu emu_grid_claims); and the same world on the near / unit
+    form's TREE (EMU_GRID=0), which a scene too large for LDS is walked on"""
     import ctypes as C
     import emu_ffi
-    desc, cam, p = LayerWorld(9000 + seed).build()
+    desc, cam, p = LayerWorld(9000 + seed, far_gated=seed >= 40).build()
     img_o, ps_o = oracle.render_samples(desc, cam, p)
     desc.contents.flags = ffi.VK_SCENE_REFERENCE_TREE
     img_r, ps_r, steps_r, info_r = emu.render_samples(desc, cam, p)
@@ -299,7 +338,7 @@ def test_grid_form_on_layer_worlds_is_the_handed_over_tree_per_sample(seed, orac
     lib.emu_grid_claims.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
     cnt = (C.c_uint64 * 3)(); v = (C.c_float * 8)()
     monkeypatch.delenv("EMU_GRID", raising=False)
-    assert lib.emu_grid_claims(desc, 20000, seed + 1, cnt, v) == 0, "not a world the grid form applies to"
+    assert lib.emu_grid_claims(desc, 60000 if seed >= 40 else 20000, seed + 1, cnt, v) == 0, "not a world the grid form applies to"
     assert cnt[2] == 0, f"{cnt[2]} of {cnt[0]} rays, e.g. o {list(v[0:3])} d {list(v[3:6])} grid {v[6]} all spheres {v[7]}"
     for env in ({}, {"EMU_GRID": "0"}, {"EMU_GRID": "0", "EMU_GLOBAL_VARIANT": "1"}):
         for k in ("EMU_GRID", "EMU_GLOBAL_VARIANT"):
@@ -359,13 +398,13 @@ def test_a_tree_whose_boxes_do_not_hold_their_spheres_is_walked_as_handed_over(o
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("seed", range(24))
+@pytest.mark.parametrize("seed", range(36))
 def test_grid_form_on_layer_worlds_on_the_gpu(seed, device, oracle):
-    """the GRID form through the C ABI on random layer worlds (LayerWorld above): every sample the oracle's, and the handed-over tree's
-    bit for bit"""
+    """the GRID form through the C ABI on random layer worlds (LayerWorld above; from seed 24 on with large spheres far outside the
+    layer, which are staged in LDS and walked on the grid): every sample the oracle's, and the handed-over tree's bit for bit"""
     from test_gpu_parity import compare_samples, device_samples
     from vecchio_amd import DeviceScene
-    desc, cam, p = LayerWorld(9100 + seed).build()
+    desc, cam, p = LayerWorld(9100 + seed, far_gated=seed >= 24).build()
     img_o, ps_o = oracle.render_samples(desc, cam, p)
     out = []
     for flags in (0, ffi.VK_SCENE_REFERENCE_TREE):
@@ -374,11 +413,34 @@ def test_grid_form_on_layer_worlds_on_the_gpu(seed, device, oracle):
         if flags == 0:      # (the grid form where the scene fits LDS — most of these — else the near form's tree, exact too)
             assert ds.info().tree in (ffi.VK_TREE_REBUILT_GRID, ffi.VK_TREE_REBUILT_NEAR, ffi.VK_TREE_REBUILT_PROVEN), ds.info().tree
             assert ds.info().tree == ffi.VK_TREE_REBUILT_GRID or not ds.info().lds_bytes
+            assert ds.info().tree == ffi.VK_TREE_REBUILT_GRID or seed < 24
         img_d, ps_d = device_samples(ds, cam, p)
         compare_samples(ps_o, ps_d, img_o, img_d)
         out.append(ps_d)
         ds.close()
     assert np.array_equal(out[0].view(np.uint32), out[1].view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c,rad", [((2000.0, 0.6, 5.0), 0.6), ((10000.0, 2.0, 5.0), 2.0)])
+def test_grid_frame_of_a_far_large_sphere_is_the_handed_over_trees(c, rad, device):
+    """a full frame of the large spheres' gate test world (far_sphere_world above) from a camera in the layer, grazing the far sphere's
+    rim: on the grid, staged in LDS, it is the handed-over tree's bit for bit"""
+    from vecchio_amd import DeviceScene
+    g, desc = far_sphere_world(c, rad)
+    lf = (4.5, 0.3, 4.5)
+    cam = camera(lf, (c[0], c[1], c[2] + 1.2 * rad), vfov=1.0, aspect=16.0 / 9.0)
+    p = params(640, 360, 64, max_depth=50, seed=5, integrator=ffi.VK_INTEGRATOR_SCATTER, background=ffi.VK_BACKGROUND_SKY)
+    imgs = []
+    for flags in (0, ffi.VK_SCENE_REFERENCE_TREE):
+        desc.contents.flags = flags
+        ds = DeviceScene(desc)
+        if flags == 0:
+            assert ds.info().tree == ffi.VK_TREE_REBUILT_GRID and ds.info().lds_bytes, (ds.info().tree, ds.info().lds_bytes)
+        imgs.append(ds.render(cam, p)[0])
+        ds.close()
+    assert np.isfinite(imgs[1]).all() and imgs[1].max() > 0.0
+    assert np.array_equal(imgs[0].view(np.uint32), imgs[1].view(np.uint32)), int((imgs[0] != imgs[1]).any(axis=2).sum())
 
 
 @pytest.mark.gpu

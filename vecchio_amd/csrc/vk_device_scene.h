@@ -103,8 +103,9 @@ struct DGrid {
     float k, r2, slack;           // the dilation: dl = k (s + r2) + slack
     uint32_t n_always;            // refs[0, n_always): the spheres tested for every segment; cells' lists follow
     // ... of which the LAST n_gated (large spheres, but not the ground's size) only when the ray passes the box [alo, ahi] around them,
-    // dilated like the layer's
+    // dilated by their own bound: dl_g = gscale dl_cap + gextra (dl_cap = k (D_far + r2) + slack, the layer's; gscale = 1)
     uint32_t n_gated; float alo[3], ahi[3];
+    float gscale, gextra;
 };
 
 // What the kernel sees.  All pointers are device (or, in the CPU emulator, host) addresses.

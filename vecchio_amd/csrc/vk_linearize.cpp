@@ -1019,6 +1019,24 @@ struct Builder {
         G.n_always = (uint32_t)always.size();
         G.n_gated = n_gated;
         for (int a = 0; a < 3; a++) { G.alo[a] = n_gated ? alo[a] : 0.0f; G.ahi[a] = n_gated ? ahi[a] : 0.0f; }
+        // the gate's own dilation (docs/gate_lemma.md section 8): a candidate of gated sphere X lies within b (rho_X + R_X) of it, and
+        // rho_X <= D_far + e_X, e_X the distance of X's centre from the layer's box (D_far: the origin's distance from that box's far
+        // corner).  The layer's cap k (D_far + r2) + slack already covers b D_far; the gate adds k (max_X (e_X + R_X) - r2) and the slab
+        // test's rounding at the gate box's coordinates (2^-19 of them, as 2 m_reg at the layer's).  A gated sphere may stand anywhere:
+        // 10^4 from the layer its candidates lie ~14 from it, where the layer's cap alone is ~0.02.
+        double reach_g = 0.0, maxabs_g = 0.0;
+        for (uint32_t r : always) {
+            const DSphere &sp = L.spheres[VKD_INDEX(r)];
+            if (!((double)sp.r <= 64.0 * r_med)) continue;
+            const double c[3] = {sp.cx, sp.cy, sp.cz};
+            double e2 = 0.0;
+            for (int a = 0; a < 3; a++) { const double e = std::max(std::max((double)G.lo[a] - c[a], c[a] - (double)G.hi[a]), 0.0); e2 += e * e; }
+            reach_g = std::max(reach_g, std::sqrt(e2) + (double)sp.r);
+        }
+        for (int a = 0; a < 3; a++) maxabs_g = std::max(maxabs_g, std::max(std::fabs((double)G.alo[a]), std::fabs((double)G.ahi[a])));
+        G.gscale = 1.0f;
+        G.gextra = std::nextafter((float)((double)G.k * std::max(reach_g - (double)G.r2, 0.0) * (1.0 + 1e-6) +
+                                          2.0 * std::max(m_reg, maxabs_g / 1048576.0) - (double)G.slack), INFINITY);
         if (getenv("VK_RETREE_DEBUG"))
             fprintf(stderr, "vecchio_amd: exact re-treeing, grid form: %zu spheres in %u x %u cells of %g (%zu references), %zu tested always\n",
                 field.size(), nu, nv, h, L.grid_refs.size() - 1u - always.size(), always.size());

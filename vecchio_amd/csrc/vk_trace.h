@@ -853,7 +853,8 @@ VK_HD void prim_step(Lane &L, const DScene &S, const Mem &M) {
 // [t_lo, t_hi] (clipped to the segment's range [ta, min(tb, T)]), and over that range its minor coordinate covers [v_lo, v_hi]: the
 // cells of the column within e of that are visited.  Every cell within e of the ray's path is: a point of the path lies in some
 // column's dilated strip at a parameter inside that column's range.  The reciprocals are the lane's (1 ulp, times gate_scale: undone
-// here), floor() of a quotient may land a cell off: dl carries 2 m_reg for that (vk_linearize.cpp rt_build_grid).
+// here), floor() of a quotient may land a cell off: dl carries 2 m_reg for that (vk_linearize.cpp rt_build_grid).  The large spheres
+// tested behind one gate need not stand in the layer: that gate is dilated by their own bound (DGrid::gextra), not by dlc alone.
 // the segment's set-up (begin_segment): its parameter range inside the layer's dilated box, the dilation, the first column
 VK_HD void grid_begin(Lane &L, const DScene &S) {
     const DGrid &G = S.grid;
@@ -877,10 +878,12 @@ VK_HD void grid_begin(Lane &L, const DScene &S) {
     ta = fmaxf(ta, fminf(w0, w1)); tb = fminf(tb, fmaxf(w0, w1));
     L.ta = ta; L.tb = tb; L.dl = dl;
     if (G.n_gated != 0u) {
-        // the large spheres' common gate: a candidate of one of them lies within dlc of it, hence of their box
-        const float p0 = ((G.alo[0] - dlc) - L.o.x) * ix_, p1 = ((G.ahi[0] + dlc) - L.o.x) * ix_;
-        const float q0 = ((G.alo[1] - dlc) - L.o.y) * iy_, q1 = ((G.ahi[1] + dlc) - L.o.y) * iy_;
-        const float r0 = ((G.alo[2] - dlc) - L.o.z) * iz_, r1 = ((G.ahi[2] + dlc) - L.o.z) * iz_;
+        // the large spheres' common gate: a candidate of one of them lies within b (rho + R) of it, hence of their box — rho and R its
+        // own, which may be far from the layer's: dlc plus what THEY add (gextra, vk_linearize.cpp rt_build_grid)
+        const float dlg = __builtin_fmaf(G.gscale, dlc, G.gextra);
+        const float p0 = ((G.alo[0] - dlg) - L.o.x) * ix_, p1 = ((G.ahi[0] + dlg) - L.o.x) * ix_;
+        const float q0 = ((G.alo[1] - dlg) - L.o.y) * iy_, q1 = ((G.ahi[1] + dlg) - L.o.y) * iy_;
+        const float r0 = ((G.alo[2] - dlg) - L.o.z) * iz_, r1 = ((G.ahi[2] + dlg) - L.o.z) * iz_;
         const float gin = fmaxf(fmaxf(fminf(p0, p1), fminf(q0, q1)), fmaxf(fminf(r0, r1), 0.0f));
         const float gout = fminf(fminf(fmaxf(p0, p1), fmaxf(q0, q1)), fmaxf(r0, r1));
         if (gin > gout * 1.000001f + 1e-30f) L.end = G.n_always - G.n_gated;      // (a NaN anywhere: tested)
