@@ -21,6 +21,30 @@ extern "C" {
  * before the finite filter (main.rs:192), [+3] = the sample's u32 draw count (bit pattern) */
 int vk_debug_render_samples(vk_scene *scene, const vk_camera *cam, const vk_render_params *params,
                             float *rgb_out, float *samples_out);
+/* the render_kernel launches of a scene's last frame (host bookkeeping, tests): the role of each launch, the kernel instance
+ * (the template key of render_kernel<F, LDS_SCENE, MINW, STATS, COST, GRID>) and its shape */
+enum {
+    VK_LAUNCH_MAIN = 0,          /* the frame's launch (single-launch shape) */
+    VK_LAUNCH_DUAL_1024 = 1,     /* the dual launch of sphere-only scenes staged in LDS: its 1024-thread workgroups ... */
+    VK_LAUNCH_DUAL_768 = 2,      /* ... and its 768-thread workgroups on the scene's second stream */
+    VK_LAUNCH_PROBE = 3,         /* the probe launch of the dearest-first tile order (COST build) */
+    VK_LAUNCH_REDO = 4,          /* exact re-treeing: the second launch, the queued samples on the tree as handed over */
+    VK_LAUNCH_FALLBACK = 5       /* exact re-treeing: the fallback launch behind it (returns at once unless a queue overflowed) */
+};
+typedef struct vk_debug_launch {
+    uint32_t role;               /* VK_LAUNCH_* */
+    uint32_t features;           /* F */
+    uint32_t lds_scene;          /* LDS_SCENE: the scene staged in LDS */
+    uint32_t minw;               /* MINW: waves per SIMD of the build */
+    uint32_t cost;               /* COST: the probe build */
+    uint32_t grid_form;          /* GRID: the grid form of exact re-treeing */
+    uint32_t grid_size;          /* workgroups */
+    uint32_t block_size;         /* threads per workgroup */
+    uint32_t shmem_bytes;        /* dynamic LDS bytes per workgroup */
+} vk_debug_launch;
+/* copies the first min(cap, *n) records of the last frame's launches into out (null when cap is 0); *n = how many there were.
+ * A multi-device scene lists its parts' launches in part order. */
+int vk_debug_last_launches(vk_scene *scene, vk_debug_launch *out, uint32_t cap, uint32_t *n);
 /* render with the instrumented build of the sphere-only kernel and return the wave scheduler's
  * counters: [0] box steps (wave level) [1] lanes with box work summed over them [2] PRIM phases
  * [3] lanes with primitive work in them [4] SHADE+REFILL phases [5] lanes in them [6] rounds

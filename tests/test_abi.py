@@ -63,6 +63,31 @@ def test_struct_layout_matches_header(built, tmp_path):
     assert sizes["vk_bvh_node"] == 32      # the canonical 32-byte node record
 
 
+def test_launch_log_layout_matches_debug_header(built, tmp_path):
+    """vk_debug_launch (include/vecchio_amd_debug.h) and its VK_LAUNCH_* roles against the ctypes mirror, field by field"""
+    hdr = os.path.join(ROOT, "include", "vecchio_amd_debug.h")
+    fields = [f[0] for f in ffi.DebugLaunch._fields_]
+    roles = ["VK_LAUNCH_MAIN", "VK_LAUNCH_DUAL_1024", "VK_LAUNCH_DUAL_768", "VK_LAUNCH_PROBE", "VK_LAUNCH_REDO", "VK_LAUNCH_FALLBACK"]
+    body = 'printf("sizeof %zu\\n", sizeof(vk_debug_launch));' + "".join(
+        f'printf("{f} %zu\\n", offsetof(vk_debug_launch, {f}));' for f in fields) + "".join(f'printf("{r} %d\\n", (int){r});' for r in roles)
+    src = tmp_path / "launch.c"
+    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{hdr}"\nint main(){{ {body} return 0; }}\n')
+    exe = tmp_path / "launch"
+    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
+    out = subprocess.check_output([str(exe)]).decode().split()
+    got = dict(zip(out[0::2], map(int, out[1::2])))
+    assert got["sizeof"] == C.sizeof(ffi.DebugLaunch)
+    for f in fields:
+        assert got[f] == getattr(ffi.DebugLaunch, f).offset, f
+    for r in roles:
+        assert got[r] == getattr(ffi, r), r
+    lib = ffi.load_device_lib()
+    assert lib.vk_debug_last_launches.argtypes[1] is C.POINTER(ffi.DebugLaunch)
+    n = C.c_uint32(7)
+    assert lib.vk_debug_last_launches(None, None, 0, C.byref(n)) == ffi.VK_ERR_BAD_ARG       # (no scene: refused, nothing written)
+    assert n.value == 7
+
+
 def test_rccl_gather_backend_resolves_without_being_linked(built):
     """VK_SCENE_RCCL_GATHER (ABI 6): the in-library gather of a multi-device scene as grouped ncclSend / ncclRecv (north_star: "RCCL over
     xGMI only for the final framebuffer gather").  librccl.so is loaded on request — the product library must not depend on it — and

@@ -118,8 +118,9 @@ int guarded(Fn &&f) {
     }
 }
 
-// Diagnostic switches (environment), read ONCE per scene at creation: none changes results except the sum grouping of
-// VK_CHUNK_CAP.  DESIGN.md §6 lists them.
+// Diagnostic switches (environment), read ONCE per scene at creation: none changes a pixel (VK_CHUNK_CAP included: pixel sums are
+// fixed-point integers, so their grouping into units does not matter; tests/test_gpu_launch_matrix.py checks every switch bit for bit).
+// DESIGN.md §6 lists them.
 struct EnvSwitches {
     bool force_full_variant = false;   // VK_FORCE_FULL_VARIANT=1: run the everything-kernel
     bool no_lds_scene = false;         // VK_NO_LDS_SCENE=1: traverse from global memory at full occupancy
@@ -251,6 +252,8 @@ struct vk_scene {
     hipEvent_t ev_begin = nullptr;               // group: recorded on the caller's stream at the start of a frame
     // group, VK_SCENE_RCCL_GATHER: one communicator per part (rank j = devices[j]); empty = peer copies
     std::vector<ncclComm_t> comms;
+    // the render_kernel launches of the last frame (vk_debug_last_launches: tests); host bookkeeping, cleared per frame
+    std::vector<vk_debug_launch> launch_log;
 };
 
 namespace {
@@ -313,7 +316,7 @@ void plan_residency(vk_scene *s, size_t hot) {
     // The near form of exact re-treeing walks a failed segment again in place: both trees in items[], i.e. global memory — unless its
     // reach spans the small spheres' whole box: then hardly a segment fails (the InOneWeekend scene: 3 in 10^5), a failed one may as well
     // requeue its whole sample, and the scene is staged in LDS like any other (7 520 against the unit form's 7 285 Msamples/s at 256 spp)
-    const bool near_needs_global = s->host->near_form && !s->grid_on && (s->env.near_lds >= 0 ? s->env.near_lds == 0 : !s->host->near_spans);
+    const bool near_needs_global = spheres_only && s->host->near_form && !s->grid_on && (s->env.near_lds >= 0 ? s->env.near_lds == 0 : !s->host->near_spans);
     const uint32_t per_simd = spheres_only ? s->sphere_waves : (pick_variant(s) == (uint32_t)VKF_ALL_SCENE ? (uint32_t)VK_ALL_MINW
                                                                                                            : (uint32_t)VK_CORNELL_MINW);   // = MINW of launch_variant
     uint32_t cap = 4 * per_simd;                                             // waves per CU the variant's register budget admits
@@ -348,6 +351,13 @@ void plan_residency(vk_scene *s, size_t hot) {
     }
 }
 
+void log_launch(vk_scene *s, uint32_t role, uint32_t F, bool lds, int minw, bool cost, bool gridf, uint32_t grid, uint32_t block, size_t shmem) {
+    vk_debug_launch r;
+    r.role = role; r.features = F; r.lds_scene = lds; r.minw = (uint32_t)minw; r.cost = cost; r.grid_form = gridf;
+    r.grid_size = grid; r.block_size = block; r.shmem_bytes = (uint32_t)shmem;
+    s->launch_log.push_back(r);
+}
+
 template <uint32_t F, int MINW_SPHERES = 6>
 int launch_variant(vk_scene *s, const KArgs &A, bool lds, dim3 grid, size_t shmem, hipStream_t st, bool cost) {
     // Register budget: every variant is held to 80 VGPRs = 6 waves per SIMD, 24 per CU.  The sphere-only kernels fit (76).  The
@@ -365,23 +375,32 @@ int launch_variant(vk_scene *s, const KArgs &A, bool lds, dim3 grid, size_t shme
     // scratch per lane, 2 TB per frame) weigh more than the eighth wave: 6 / 7 / 8 waves per SIMD -> 1 112 / 1 163 / 1 076 Msamples/s.
     // Seven: 72 VGPRs, shading inline, seven 256-thread workgroups per CU.
     constexpr int MINW_G = ((F & ~(uint32_t)VKF_INTEG_PDF) == 0u) ? 7 : MINW;
-    auto go = [&](auto kernel) -> int {
+    // Only the sphere-only kernels walk the rebuilt trees of exact re-treeing (segment_unsafe, the requeue, the redo walk in place) and only
+    // F == 0 has a grid build: any other instance is handed the tree as handed over (create_on_device), never a rebuilt view
+    if ((F & ~(uint32_t)VKF_INTEG_PDF) != 0u && (A.S.grid.nu != 0u || A.S.t_pad > 0.0f || A.S.walk_start != 0u))
+        return fail(VK_ERR_BAD_ARG, "internal error: a view of a rebuilt tree for a kernel that cannot walk it");
+    if (F != 0u && A.S.grid.nu != 0u) return fail(VK_ERR_BAD_ARG, "internal error: the grid form for a kernel without a grid build");
+    const uint32_t role = cost ? VK_LAUNCH_PROBE : (A.list_mode == 1u ? VK_LAUNCH_REDO : (A.list_mode == 2u ? VK_LAUNCH_FALLBACK : VK_LAUNCH_MAIN));
+    auto go = [&](auto kernel, bool l, int minw, bool gridf) -> int {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
         hipLaunchKernelGGL(kernel, grid, dim3(s->wg_threads), shmem, st, A);
+        log_launch(s, role, F, l, minw, cost, gridf, grid.x, s->wg_threads, shmem);
         return VK_OK;
     };
     int rc;
     if constexpr (F == 0u) {
         if (A.S.grid.nu != 0u) {      // the grid form of exact re-treeing (DGrid): worlds without lights, i.e. the scatter integrator's
-            if (cost) rc = lds ? go(&render_kernel<F, true, MINW, false, true, true>) : go(&render_kernel<F, false, MINW_G, false, true, true>);
-            else rc = lds ? go(&render_kernel<F, true, MINW, false, false, true>) : go(&render_kernel<F, false, MINW_G, false, false, true>);
+            if (cost) rc = lds ? go(&render_kernel<F, true, MINW, false, true, true>, true, MINW, true)
+                               : go(&render_kernel<F, false, MINW_G, false, true, true>, false, MINW_G, true);
+            else rc = lds ? go(&render_kernel<F, true, MINW, false, false, true>, true, MINW, true)
+                          : go(&render_kernel<F, false, MINW_G, false, false, true>, false, MINW_G, true);
             if (rc != VK_OK) return rc;
             HIP_TRY(hipGetLastError());
             return VK_OK;
         }
     }
-    if (cost) rc = lds ? go(&render_kernel<F, true, MINW, false, true>) : go(&render_kernel<F, false, MINW_G, false, true>);
-    else rc = lds ? go(&render_kernel<F, true, MINW, false, false>) : go(&render_kernel<F, false, MINW_G, false, false>);
+    if (cost) rc = lds ? go(&render_kernel<F, true, MINW, false, true>, true, MINW, false) : go(&render_kernel<F, false, MINW_G, false, true>, false, MINW_G, false);
+    else rc = lds ? go(&render_kernel<F, true, MINW, false, false>, true, MINW, false) : go(&render_kernel<F, false, MINW_G, false, false>, false, MINW_G, false);
     if (rc != VK_OK) return rc;
     HIP_TRY(hipGetLastError());
     return VK_OK;
@@ -401,6 +420,8 @@ int launch_dual(vk_scene *s, const KArgs &A, size_t per_wave, hipStream_t st) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)s->num_cus), dim3(1024), shm_a, st, A);
     hipLaunchKernelGGL(kernel, dim3((unsigned)s->num_cus), dim3(768), shm_b, st2, A);
     HIP_TRY(hipGetLastError());
+    log_launch(s, VK_LAUNCH_DUAL_1024, F, true, 7, false, GRID, (uint32_t)s->num_cus, 1024u, shm_a);
+    log_launch(s, VK_LAUNCH_DUAL_768, F, true, 7, false, GRID, (uint32_t)s->num_cus, 768u, shm_b);
     HIP_TRY(hipEventRecord(s->ev_join, st2));
     HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));              // the resolve kernel waits for both
     s->dual_last = true;
@@ -536,6 +557,7 @@ struct AccumDesc {
 int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params *p, float *d_out, hipStream_t st, bool want_debug,
     vk_stats *stats, const AccumDesc *acc = nullptr) {
     HIP_TRY(hipSetDevice(s->device));
+    s->launch_log.clear();
     const TileGeom g(p);
     KArgs A;
     memset(&A, 0, sizeof(A));
@@ -998,8 +1020,11 @@ int create_on_device(const std::shared_ptr<const LinearScene> &host, int device,
     // (exact re-treeing: the second launch stages the tree as handed over instead of the rebuilt one, whichever is larger counts)
     size_t hot = std::max(H.items.size(), H.ref_items.size()) * sizeof(DItem) + H.spheres.size() * sizeof(DSphere) +
                  H.boxes.size() * sizeof(DBox);
+    // Only the sphere-only kernels walk a rebuilt tree of exact re-treeing (segment_unsafe, the requeue, the grid build): a scene that runs
+    // another instance (VK_FORCE_FULL_VARIANT=1) is uploaded with the tree as handed over (ref_items) in items[], for every launch of it
+    const bool rebuilt = !H.ref_items.empty() && pick_variant(s.get()) == 0u;
     // the grid form (DGrid): the first launch stages the table [cells | refs] instead of a tree, the second one the tree as handed over
-    bool grid = H.grid.nu != 0u && !H.ref_items.empty() && !s->env.no_grid;
+    bool grid = H.grid.nu != 0u && rebuilt && !s->env.no_grid;
     const size_t grid_table_bytes = grid ? ((H.grid_cells.size() + H.grid_refs.size()) * sizeof(uint32_t) + 31u) / 32u * 32u : 0u;
     // (the probe and the diagnostic builds walk the rebuilt TREE, which therefore counts too where the scene is staged in LDS)
     if (grid) hot = std::max(grid_table_bytes, std::max(H.ref_items.size(), H.items.size()) * sizeof(DItem)) + H.spheres.size() * sizeof(DSphere);
@@ -1018,7 +1043,7 @@ int create_on_device(const std::shared_ptr<const LinearScene> &host, int device,
         plan_residency(s.get(), hot);
     }
     D.gate_scale = 1.0f; D.tmin_gate = T_MIN;
-    if (!H.ref_items.empty()) {
+    if (rebuilt) {
         // Exact re-treeing (vk_trace.h).  Staged in LDS: the rebuilt tree is the scene's, the tree as handed over serves the second launch
         // (`exact`).  Traversed from global memory: both trees in one array, early segments are walked again in place (DScene::walk_start).
         const DScene hv = H.host_view();
@@ -1060,6 +1085,9 @@ int create_on_device(const std::shared_ptr<const LinearScene> &host, int device,
             D.n_items = (uint32_t)both.size(); D.n_world_items = (uint32_t)both.size(); D.walk_start = walk_start;
             D.unit_tree = D.items;       // (the tree as handed over comes first, item for item)
         }
+    } else if (!H.ref_items.empty()) {
+        UP(ref_items, items);        // (the tree as handed over, as s->ref_view has it)
+        D.n_items = (uint32_t)H.ref_items.size(); D.n_world_items = D.n_items;
     } else {
         UP(items, items);
         D.n_items = (uint32_t)H.items.size(); D.n_world_items = H.world_items;
@@ -1069,7 +1097,7 @@ int create_on_device(const std::shared_ptr<const LinearScene> &host, int device,
     UP(materials, materials); UP(sphere_material, sphere_material); UP(textures, textures); UP(images, images);
     UP(image_bytes, image_bytes);
     UP(perlins, perlins); UP(lights, lights);
-    if (!H.tie_rank.empty()) UP(tie_rank, tie_rank);
+    if (!H.tie_rank.empty() && (rebuilt || H.ref_items.empty())) UP(tie_rank, tie_rank);
 #undef UP
     D.tie_base_rect = H.tie_base_rect; D.tie_base_box = H.tie_base_box; D.tie_base_list = H.tie_base_list;
     D.fast_div = H.host_view().fast_div;
@@ -1257,8 +1285,9 @@ int vk_scene_get_info(const vk_scene *s, vk_scene_info *out) {
     out->device_bytes = b;
     out->lds_bytes = one->lds_bytes;
     out->features = pick_variant(one);
-    out->tree = !H.ref_items.empty() ? (one->grid_on ? VK_TREE_REBUILT_GRID : H.near_form ? VK_TREE_REBUILT_NEAR : (H.proven ? VK_TREE_REBUILT_PROVEN : VK_TREE_REBUILT_EMPIRICAL))
-                                     : (!H.tie_rank.empty() ? VK_TREE_REBUILT_FAST : VK_TREE_HANDED_OVER);
+    const bool rebuilt = !H.ref_items.empty() && pick_variant(one) == 0u;      // (see create_on_device)
+    out->tree = rebuilt ? (one->grid_on ? VK_TREE_REBUILT_GRID : H.near_form ? VK_TREE_REBUILT_NEAR : (H.proven ? VK_TREE_REBUILT_PROVEN : VK_TREE_REBUILT_EMPIRICAL))
+                                     : (!H.tie_rank.empty() && H.ref_items.empty() ? VK_TREE_REBUILT_FAST : VK_TREE_HANDED_OVER);
     out->gather = s->parts.empty() ? VK_GATHER_NONE : (s->comms.empty() ? VK_GATHER_PEER_COPY : VK_GATHER_RCCL);
     out->tree_suspended_frames = 0;
     for (const vk_scene *q : (s->parts.empty() ? std::vector<vk_scene *>{const_cast<vk_scene *>(s)} : s->parts))
@@ -1481,6 +1510,17 @@ int vk_debug_render_samples(vk_scene *scene, const vk_camera *cam, const vk_rend
     if (!samples_out) return fail(VK_ERR_BAD_ARG, "null samples buffer");
     if (params && params->output_format != VK_OUTPUT_F32) return fail(VK_ERR_BAD_ARG, "per-sample debug output needs VK_OUTPUT_F32");
     return guarded([&]() -> int { return render_host(scene, cam, params, rgb_out, nullptr, samples_out); });
+}
+
+// test hook: the render_kernel launches of the scene's last frame (vk_scene::launch_log)
+int vk_debug_last_launches(vk_scene *scene, vk_debug_launch *out, uint32_t cap, uint32_t *n) {
+    if (!scene || !n || (cap && !out)) return fail(VK_ERR_BAD_ARG, "null argument");
+    std::vector<vk_debug_launch> all;
+    for (const vk_scene *q : (scene->parts.empty() ? std::vector<vk_scene *>{scene} : scene->parts))
+        all.insert(all.end(), q->launch_log.begin(), q->launch_log.end());
+    *n = (uint32_t)all.size();
+    for (uint32_t k = 0; k < cap && k < *n; k++) out[k] = all[k];
+    return VK_OK;
 }
 
 }  // extern "C"

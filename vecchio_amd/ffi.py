@@ -150,6 +150,15 @@ VK_TREE_HANDED_OVER, VK_TREE_REBUILT_PROVEN, VK_TREE_REBUILT_EMPIRICAL, VK_TREE_
 VK_GATHER_NONE, VK_GATHER_PEER_COPY, VK_GATHER_RCCL = range(3)
 
 
+class DebugLaunch(C.Structure):
+    """vk_debug_launch of include/vecchio_amd_debug.h: one render_kernel launch of a scene's last frame"""
+    _fields_ = [("role", C.c_uint32), ("features", C.c_uint32), ("lds_scene", C.c_uint32), ("minw", C.c_uint32), ("cost", C.c_uint32),
+                ("grid_form", C.c_uint32), ("grid_size", C.c_uint32), ("block_size", C.c_uint32), ("shmem_bytes", C.c_uint32)]
+
+
+(VK_LAUNCH_MAIN, VK_LAUNCH_DUAL_1024, VK_LAUNCH_DUAL_768, VK_LAUNCH_PROBE, VK_LAUNCH_REDO, VK_LAUNCH_FALLBACK) = range(6)
+
+
 _host = None
 _dev = None
 
@@ -261,6 +270,9 @@ def _bind(lib):
     lib.vk_progress_get_info.argtypes = [C.c_void_p, C.POINTER(ProgressInfo)]
     lib.vk_progress_destroy.restype = None
     lib.vk_progress_destroy.argtypes = [C.c_void_p]
+    # the test hooks of include/vecchio_amd_debug.h that the product library carries too
+    lib.vk_debug_last_launches.restype = C.c_int
+    lib.vk_debug_last_launches.argtypes = [C.c_void_p, C.POINTER(DebugLaunch), C.c_uint32, C.POINTER(C.c_uint32)]
 
 
 _dbg = None
@@ -285,6 +297,15 @@ def load_debug_lib():
     lib.vk_debug_math.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     _dbg = lib
     return lib
+
+
+def last_launches(lib, handle):
+    """the render_kernel launches of the scene's last frame (vk_debug_last_launches), as a list of DebugLaunch"""
+    n = C.c_uint32()
+    assert lib.vk_debug_last_launches(handle, None, 0, C.byref(n)) == VK_OK, lib.vk_last_error().decode()
+    out = (DebugLaunch * max(1, n.value))()
+    assert lib.vk_debug_last_launches(handle, out, n.value, C.byref(n)) == VK_OK, lib.vk_last_error().decode()
+    return list(out[:n.value])
 
 
 def load_device_lib():
