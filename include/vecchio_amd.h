@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define VK_ABI_VERSION 7   /* 7: progressive rendering (vk_progress_*; vk_scene_desc unchanged: descriptions stamped 6 are accepted); 6: VK_SCENE_RCCL_GATHER, vk_scene_info.gather, vk_gather_backends; 5: rebuilt trees by default only where their exactness is proven; VK_SCENE_EMPIRICAL_TREES; vk_scene_info.tree */
+#define VK_ABI_VERSION 7   /* 7: progressive rendering (vk_progress_*; adaptive sampling added later as new symbols only, no struct changed: vk_progress_set_adaptive, vk_progress_tile_samples; vk_scene_desc unchanged: descriptions stamped 6 are accepted); 6: VK_SCENE_RCCL_GATHER, vk_scene_info.gather, vk_gather_backends; 5: rebuilt trees by default only where their exactness is proven; VK_SCENE_EMPIRICAL_TREES; vk_scene_info.tree */
 
 /* ---- status codes (reference convention is panic!/unwrap, main.rs:166,202) ---------- */
 enum {
@@ -446,6 +446,41 @@ int vk_progress_stderr(vk_progress *pr, float *out);
 /* waits for the last step */
 int vk_progress_get_info(vk_progress *pr, vk_progress_info *out);
 void vk_progress_destroy(vk_progress *pr);   /* NULL: nothing */
+
+/* ---- adaptive sampling (additive symbols of ABI 7) -----------------------------------------------------------------------------
+ * Tiles whose error has converged stop; the others go on.  Adaptivity is per 8x8 tile of this call's partition, switched on for a
+ * handle created with VK_PROGRESS_STDERR, before its first step since create / reset.  After every window each active tile is judged ON
+ * THE DEVICE: a pixel has converged when for every component c
+ *     v_c <= (abs_tol + rel_tol * |mean_c|)^2,   mean_c = run_c / 2^26 / N,   v_c = (m2_c - N * mean_c * mean_c) / ((k - 1) * N)
+ * — the variance vk_progress_stderr squares, evaluated in double with its operation order (no contraction), N = samples_done and k =
+ * steps.  A tile converges when all its in-image pixels have, with N >= min_samples and k >= min_steps.  A converged tile is FROZEN
+ * until reset: it renders no more samples and its pixels keep being written with their frozen mean; every preview is complete.  The
+ * active tiles share one count, samples_done; the budget check stays samples_done + n <= budget.
+ *
+ * Bit-identity.  After any sequence of steps, a pixel of tile t is, bit for bit, vk_render's pixel at samples_per_pixel = N_t (same
+ * seed), N_t the tile's count (vk_progress_tile_samples) — f32 and RGB8, exact when clamped_samples == 0 (the clamp is the budget's).
+ * vk_progress_stderr uses each tile's own N_t and k_t.  When no tile is active a step renders nothing, leaves the image as it was and
+ * returns VK_OK; samples_done still advances (it counts the windows' samples), no tile's count changes.
+ * vk_stats.samples of a step: exact from vk_progress_step; from vk_progress_step_device it is the count the host last learned (the
+ * previous window's, if it has finished, else the partition's) — vk_adaptive_info.samples_rendered is always exact.
+ * Tightening the tolerance later and resuming frozen tiles are not offered.  vk_progress_reset makes every tile active again and keeps
+ * the parameters.                                                                                                                   */
+typedef struct vk_adaptive_params {
+    float abs_tol, rel_tol;      /* per component: stderr_c <= abs_tol + rel_tol * |mean_c|  (finite, >= 0) */
+    uint32_t min_samples;        /* no tile stops with fewer samples ... */
+    uint32_t min_steps;          /* ... or fewer windows (>= 2: the estimate needs two) */
+} vk_adaptive_params;
+/* VK_ERR_BAD_ARG, the handle unchanged: a null handle or ap, a handle without VK_PROGRESS_STDERR, min_steps < 2, a negative or non-finite
+ * tolerance, a call after a step (since create / reset).  Called again before the first step: the new parameters. */
+int vk_progress_set_adaptive(vk_progress *pr, const vk_adaptive_params *ap);
+typedef struct vk_adaptive_info {
+    uint32_t tiles_total;        /* tiles of this partition */
+    uint32_t tiles_active;       /* of them not frozen (all of them without vk_progress_set_adaptive) */
+    uint64_t samples_rendered;   /* pixel-samples in the running sums, summed over the partition's in-image pixels */
+} vk_adaptive_info;
+/* per tile of the image (tiles_x * tiles_y, row-major, tile row 0 = bottom like the f32 image): samples in its running sums, 0 outside
+ * the partition; out and info may each be NULL.  Any handle (without adaptivity every tile has samples_done).  Waits for the last step. */
+int vk_progress_tile_samples(vk_progress *pr, uint32_t *out, vk_adaptive_info *info);
 
 /* test/diagnostic entry points (vk_debug_*) are declared in vecchio_amd_debug.h */
 

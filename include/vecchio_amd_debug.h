@@ -45,6 +45,9 @@ typedef struct vk_debug_launch {
 /* copies the first min(cap, *n) records of the last frame's launches into out (null when cap is 0); *n = how many there were.
  * A multi-device scene lists its parts' launches in part order. */
 int vk_debug_last_launches(vk_scene *scene, vk_debug_launch *out, uint32_t cap, uint32_t *n);
+/* a progressive handle's raw running fixed-point sums and error moments (width*height*3 each, y up, summed over the device parts):
+ * what the adaptive judge reads.  Either may be NULL; m2 needs VK_PROGRESS_STDERR.  Waits for the last step. */
+int vk_debug_progress_moments(vk_progress *pr, long long *run, double *m2);
 /* render with the instrumented build of the sphere-only kernel and return the wave scheduler's
  * counters: [0] box steps (wave level) [1] lanes with box work summed over them [2] PRIM phases
  * [3] lanes with primitive work in them [4] SHADE+REFILL phases [5] lanes in them [6] rounds

@@ -69,6 +69,9 @@ struct KArgs {
     // progressive rendering (vk_progress_step): this launch renders the sample WINDOW [sample_base, sample_base + C.spp) of every pixel;
     // 0 for vk_render.  A unit's samples are numbered from it, so the RNG keys (seed, pixel, sample) are those of the one-shot frame.
     uint32_t sample_base;
+    // adaptive progressive rendering (vk_progress_set_adaptive): the number of active tiles, in device memory (written by the compaction
+    // ahead of the launch); units are then those of the first *active_count slots of tile_order (the active list).  Null: n_local_tiles.
+    const uint32_t *active_count;
 };
 constexpr uint32_t REDO_REGIONS = 512u;
 constexpr uint32_t REDO_COUNT_STRIDE = 16u;        // uint32 words between two regions' counters
@@ -524,7 +527,10 @@ __device__ __forceinline__ void shade_refill_body(Lane &L, bool is_shade, bool e
             { unsigned long long *wt = KARG(P, wave_times);
               if (wt && lane == 0) wt[3u * ((blockIdx.x + (blockDim.x == 1024u ? 0u : gridDim.x)) * 16u + (threadIdx.x >> 6)) + 1u] = wall_clock64(); }
 #endif
-            if (unit >= KARG(P, n_local_tiles) * n_chunks) {                      // the launch's units are all handed out:
+            // adaptive windows: the units of the active tiles only (a uniform load, once per unit pull)
+            const uint32_t *ac = KARG(P, active_count);
+            const uint32_t n_tiles = ac ? __builtin_amdgcn_readfirstlane(*ac) : KARG(P, n_local_tiles);
+            if (unit >= n_tiles * n_chunks) {                                     // the launch's units are all handed out:
                 need = false;                                                     // these lanes idle until the wave's last path ends
                 break;
             }
@@ -1013,6 +1019,123 @@ __global__ void accumulate_resolve_kernel(const long long *accum, long long *run
         run[i] = r;
         out[i] = ((float)r * inv_scale) / n;
         if (m2) { const double s = (double)w * (1.0 / (double)ACCUM_SCALE); m2[i] += s * s / (double)window; }
+    }
+}
+
+// ---- adaptive progressive rendering (vk_progress_set_adaptive) ---------------------------------------------------------------------
+// Per local tile slot i of a part (tile = tile_rank + i * tile_world): tile_n[i] = the samples a CONVERGED tile froze with (0 = still
+// active, its count is the handle's samples done), tile_k[i] = its windows.  A window renders the active tiles only (KArgs::tile_order
+// = the active list, KArgs::active_count = its length), so a frozen tile's running sums stop at tile_n[i] samples.
+
+// Compaction, 1: active slots per 1024-slot block of the tile order (ord = the probe's dearest-first order, or null = raster order).
+__global__ void __launch_bounds__(1024) adaptive_count_kernel(const uint32_t *ord, const uint32_t *tile_n, uint32_t n_local,
+                                                              uint32_t *block_count) {
+    __shared__ uint32_t wc[16];
+    const uint32_t i = blockIdx.x * 1024u + threadIdx.x, lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const bool act = i < n_local && tile_n[ord ? ord[i] : i] == 0u;
+    const unsigned long long m = __ballot(act);
+    if (lane == 0) wc[w] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (int k = 0; k < 16; k++) s += wc[k];
+        block_count[blockIdx.x] = s;
+    }
+}
+
+// Compaction, 2: every block adds up the counts of the blocks before it and writes its active slots in order behind them (stable:
+// the list is the order filtered, the same on every run); the last block writes the list's length.
+__global__ void __launch_bounds__(1024) adaptive_scatter_kernel(const uint32_t *ord, const uint32_t *tile_n, uint32_t n_local,
+                                                                const uint32_t *block_count, uint32_t *list, uint32_t *count) {
+    __shared__ uint32_t part[1024];
+    __shared__ uint32_t wc[16];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t s = 0;
+    for (uint32_t b = threadIdx.x; b < blockIdx.x; b += 1024u) s += block_count[b];
+    part[threadIdx.x] = s;
+    const uint32_t i = blockIdx.x * 1024u + threadIdx.x;
+    const uint32_t slot = i < n_local ? (ord ? ord[i] : i) : 0u;
+    const bool act = i < n_local && tile_n[slot] == 0u;
+    const unsigned long long m = __ballot(act);
+    if (lane == 0) wc[w] = (uint32_t)__popcll(m);
+    __syncthreads();
+    for (uint32_t h = 512u; h > 0u; h >>= 1) {          // the blocks before this one: a tree sum (integers: exact in any order)
+        if (threadIdx.x < h) part[threadIdx.x] += part[threadIdx.x + h];
+        __syncthreads();
+    }
+    uint32_t base = part[0];
+    for (uint32_t k = 0; k < w; k++) base += wc[k];
+    if (act) list[base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = slot;
+    if (blockIdx.x == gridDim.x - 1u && threadIdx.x == 0) {
+        uint32_t t = part[0];
+        for (int k = 0; k < 16; k++) t += wc[k];
+        *count = t;
+    }
+}
+
+// The resolve of an adaptive window: accumulate_resolve_kernel for the active tiles (mean over `done` samples), and for the frozen ones
+// their running sums over tile_n samples — which the window did not touch (it rendered no unit of theirs: accum is 0 there).  Every
+// pixel of the partition is written, so that every preview is complete.
+__global__ void adaptive_resolve_kernel(const long long *accum, long long *run, double *m2, float *out, uint32_t width, uint32_t height,
+                                        uint32_t window, uint32_t done, uint32_t tiles_x, uint32_t tile_rank, uint32_t tile_world,
+                                        const uint32_t *tile_n, const unsigned long long *win_clamped, unsigned long long *run_clamped) {
+    uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix == 0) *run_clamped += *win_clamped;
+    uint32_t n_pixels = width * height;
+    if (pix >= n_pixels) return;
+    uint32_t x = pix % width, y = pix / width;
+    uint32_t tile = (y / TILE) * tiles_x + (x / TILE);
+    if (tile % tile_world != tile_rank) return;
+    const uint32_t frozen = tile_n[tile / tile_world];
+    const float inv_scale = 1.0f / ACCUM_SCALE;
+    if (frozen != 0u) {
+        const float n = (float)frozen;
+        for (int c = 0; c < 3; c++) out[(size_t)pix * 3 + c] = ((float)run[(size_t)pix * 3 + c] * inv_scale) / n;
+        return;
+    }
+    float n = (float)done;
+    for (int c = 0; c < 3; c++) {
+        const size_t i = (size_t)pix * 3 + c;
+        const long long w = accum[i], r = run[i] + w;
+        run[i] = r;
+        out[i] = ((float)r * inv_scale) / n;
+        if (m2) { const double s = (double)w * (1.0 / (double)ACCUM_SCALE); m2[i] += s * s / (double)window; }
+    }
+}
+
+// The judge, behind the adaptive resolve: one wave per active tile, one lane per pixel.  A pixel has converged when for every component
+//   v <= (abs_tol + rel_tol |mean|)^2,   mean = run / 2^26 / N,   v = (m2 - N mean^2) / ((k - 1) N)
+// in double, with vk_progress_stderr's operation order (built without contraction: a numpy restatement reproduces every decision).  A
+// tile converges when all its in-image pixels have (lanes outside the image do not vote) and the gates (min_samples, min_steps: `gate`)
+// are met; it is then frozen at (done, steps).  The tiles left active, and their in-image pixels, are counted into left[0] and
+// left_px (zeroed before): the host sizes the next window from them.
+__global__ void adaptive_judge_kernel(const long long *run, const double *m2, uint32_t width, uint32_t height, uint32_t tiles_x,
+                                      uint32_t tile_rank, uint32_t tile_world, uint32_t n_local, uint32_t done, uint32_t steps, uint32_t gate,
+                                      float abs_tol, float rel_tol, uint32_t *tile_n, uint32_t *tile_k, uint32_t *left,
+                                      unsigned long long *left_px) {
+    const uint32_t slot = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    if (slot >= n_local || tile_n[slot] != 0u) return;         // (uniform per wave)
+    const uint32_t tile = tile_rank + slot * tile_world;
+    const uint32_t px = (tile % tiles_x) * TILE + (lane & 7u), py = (tile / tiles_x) * TILE + (lane >> 3);
+    const bool inside = px < width && py < height;
+    bool conv = true;
+    if (inside && gate) {
+        const double N = (double)done, k = (double)steps, at = (double)abs_tol, rt = (double)rel_tol;
+        for (int c = 0; c < 3; c++) {
+            const size_t i = ((size_t)py * width + px) * 3 + c;
+            const double mean = (double)run[i] / (double)ACCUM_SCALE / N;
+            const double v = (m2[i] - N * mean * mean) / ((k - 1.0) * N);
+            const double tol = at + rt * fabs(mean);
+            conv = conv && v <= tol * tol;
+        }
+    }
+    const unsigned long long in_mask = __ballot(inside), conv_mask = __ballot(conv);
+    if (lane != 0) return;
+    if (gate && conv_mask == ~0ull) {
+        tile_n[slot] = done; tile_k[slot] = steps;
+    } else {
+        atomicAdd(left, 1u);
+        atomicAdd(left_px, (unsigned long long)__popcll(in_mask));
     }
 }
 

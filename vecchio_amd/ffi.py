@@ -146,6 +146,16 @@ class ProgressInfo(C.Structure):
                 ("clamped_samples", C.c_uint64)]
 
 
+class AdaptiveParams(C.Structure):
+    """vk_adaptive_params (vk_progress_set_adaptive)"""
+    _fields_ = [("abs_tol", C.c_float), ("rel_tol", C.c_float), ("min_samples", C.c_uint32), ("min_steps", C.c_uint32)]
+
+
+class AdaptiveInfo(C.Structure):
+    """vk_adaptive_info (vk_progress_tile_samples)"""
+    _fields_ = [("tiles_total", C.c_uint32), ("tiles_active", C.c_uint32), ("samples_rendered", C.c_uint64)]
+
+
 VK_TREE_HANDED_OVER, VK_TREE_REBUILT_PROVEN, VK_TREE_REBUILT_EMPIRICAL, VK_TREE_REBUILT_FAST, VK_TREE_REBUILT_NEAR, VK_TREE_REBUILT_GRID = range(6)
 VK_GATHER_NONE, VK_GATHER_PEER_COPY, VK_GATHER_RCCL = range(3)
 
@@ -215,7 +225,7 @@ DEVICE_SYMBOLS = [
     "vk_scene_last_kernel_ms", "vk_scene_last_clamped_samples", "vk_scene_last_requeued_samples", "vk_scene_part_info",
     "vk_tile_slab_bytes", "vk_pack_tiles_device", "vk_unpack_tiles_device",
     "vk_progress_create", "vk_progress_step", "vk_progress_step_device", "vk_progress_reset", "vk_progress_stderr",
-    "vk_progress_get_info", "vk_progress_destroy",
+    "vk_progress_get_info", "vk_progress_destroy", "vk_progress_set_adaptive", "vk_progress_tile_samples",
 ]
 
 
@@ -270,9 +280,15 @@ def _bind(lib):
     lib.vk_progress_get_info.argtypes = [C.c_void_p, C.POINTER(ProgressInfo)]
     lib.vk_progress_destroy.restype = None
     lib.vk_progress_destroy.argtypes = [C.c_void_p]
+    lib.vk_progress_set_adaptive.restype = C.c_int
+    lib.vk_progress_set_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveParams)]
+    lib.vk_progress_tile_samples.restype = C.c_int
+    lib.vk_progress_tile_samples.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AdaptiveInfo)]
     # the test hooks of include/vecchio_amd_debug.h that the product library carries too
     lib.vk_debug_last_launches.restype = C.c_int
     lib.vk_debug_last_launches.argtypes = [C.c_void_p, C.POINTER(DebugLaunch), C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.vk_debug_progress_moments.restype = C.c_int
+    lib.vk_debug_progress_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 _dbg = None

@@ -81,6 +81,12 @@ pub struct vk_stats { pub samples: u64, pub seconds: f64, pub kernel_ms: f64, pu
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_progress_info { pub samples_done: u32, pub samples_budget: u32, pub steps: u32, pub flags: u32, pub clamped_samples: u64 }
 
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_adaptive_params { pub abs_tol: f32, pub rel_tol: f32, pub min_samples: u32, pub min_steps: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_adaptive_info { pub tiles_total: u32, pub tiles_active: u32, pub samples_rendered: u64 }
+
 #[repr(C)] pub struct vk_scene { _private: [u8; 0] }
 #[repr(C)] pub struct vk_progress { _private: [u8; 0] }
 
@@ -107,6 +113,8 @@ extern "C" {
     pub fn vk_progress_stderr(pr: *mut vk_progress, out: *mut f32) -> c_int;
     pub fn vk_progress_get_info(pr: *mut vk_progress, out: *mut vk_progress_info) -> c_int;
     pub fn vk_progress_destroy(pr: *mut vk_progress);
+    pub fn vk_progress_set_adaptive(pr: *mut vk_progress, ap: *const vk_adaptive_params) -> c_int;
+    pub fn vk_progress_tile_samples(pr: *mut vk_progress, out: *mut u32, info: *mut vk_adaptive_info) -> c_int;
 }
 
 /// What `flatten()` pushes into (flatten.rs).  One record per Arc; shared Arcs are de-duplicated
@@ -206,6 +214,16 @@ impl<'a> GpuProgress<'a> {
     }
     pub fn reset(&mut self, cam: Option<&vk_camera>) -> Result<(), std::io::Error> {
         check(unsafe { vk_progress_reset(self.handle, cam.map_or(std::ptr::null(), |c| c as *const vk_camera)) })
+    }
+    /// adaptive sampling: converged tiles stop (needs `with_stderr`; before the first step since create / reset)
+    pub fn set_adaptive(&mut self, ap: &vk_adaptive_params) -> Result<(), std::io::Error> {
+        check(unsafe { vk_progress_set_adaptive(self.handle, ap) })
+    }
+    /// samples per 8x8 tile (`tiles_x * tiles_y`, tile row 0 at the bottom; 0 outside the partition) and the active count
+    pub fn tile_samples(&mut self, out: &mut [u32]) -> Result<vk_adaptive_info, std::io::Error> {
+        let mut i = vk_adaptive_info::default();
+        check(unsafe { vk_progress_tile_samples(self.handle, out.as_mut_ptr(), &mut i) })?;
+        Ok(i)
     }
 }
 impl<'a> Drop for GpuProgress<'a> { fn drop(&mut self) { unsafe { vk_progress_destroy(self.handle) } } }

@@ -141,10 +141,18 @@ class DeviceScene:
         check(self._lib, self._lib.vk_unpack_tiles_device(self._h, C.c_void_p(d_slab), width, height, output_format, tile_rank, tile_world,
                                                           C.c_void_p(d_img), C.c_void_p(stream or 0)))
 
-    def progress(self, cam, params, stderr=False):
+    def progress(self, cam, params, stderr=False, adaptive=None):
         """A progressive render of ONE frame (vk_progress_create): params.samples_per_pixel is the budget, step(n) renders the next n
-        samples per pixel and returns the running mean — bit for bit the image render() gives at samples_per_pixel = samples done."""
-        return Progress(self, cam, params, stderr)
+        samples per pixel and returns the running mean — bit for bit the image render() gives at samples_per_pixel = samples done.
+        adaptive=dict(abs_tol=, rel_tol=, min_samples=, min_steps=): converged tiles stop (Progress.set_adaptive; implies stderr)."""
+        pr = Progress(self, cam, params, stderr or adaptive is not None)
+        if adaptive is not None:
+            try:
+                pr.set_adaptive(**adaptive)
+            except Exception:
+                pr.close()
+                raise
+        return pr
 
     def to_color_device(self, d_rgb, width, height, d_rgb8, stream=None):
         check(self._lib, self._lib.vk_to_color_device(self._h, C.c_void_p(d_rgb), width, height, C.c_void_p(d_rgb8), C.c_void_p(stream or 0)))
@@ -198,6 +206,29 @@ class Progress:
         out = np.zeros((p.height, p.width, 3), np.float32)
         check(self._lib, self._lib.vk_progress_stderr(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def set_adaptive(self, abs_tol=0.0, rel_tol=0.0, min_samples=0, min_steps=2):
+        """Adaptive sampling (vk_progress_set_adaptive): after every window a tile whose pixels all have, per component,
+        stderr <= abs_tol + rel_tol * |mean| (and min_samples samples, min_steps windows) is frozen; before the first step."""
+        ap = ffi.AdaptiveParams(abs_tol, rel_tol, min_samples, min_steps)
+        check(self._lib, self._lib.vk_progress_set_adaptive(self._h, C.byref(ap)))
+
+    def tile_samples(self):
+        """(samples per tile as uint32 (tiles_y, tiles_x), tile row 0 at the bottom and 0 outside the partition; vk_adaptive_info)"""
+        p = self.params
+        out = np.zeros(((p.height + 7) // 8, (p.width + 7) // 8), np.uint32)
+        inf = ffi.AdaptiveInfo()
+        check(self._lib, self._lib.vk_progress_tile_samples(self._h, out.ctypes.data_as(C.c_void_p), C.byref(inf)))
+        return out, inf
+
+    def moments(self):
+        """(running fixed-point sums as int64, error moments as float64 or None), each (height, width, 3) y up: vk_debug_progress_moments"""
+        p = self.params
+        run = np.zeros((p.height, p.width, 3), np.int64)
+        m2 = np.zeros((p.height, p.width, 3), np.float64) if self.info().flags & ffi.VK_PROGRESS_STDERR else None
+        check(self._lib, self._lib.vk_debug_progress_moments(self._h, run.ctypes.data_as(C.c_void_p),
+                                                             m2.ctypes.data_as(C.c_void_p) if m2 is not None else None))
+        return run, m2
 
     def info(self):
         inf = ffi.ProgressInfo()
