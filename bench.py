@@ -8,7 +8,9 @@ BASELINE config C2, InOneWeekend random-spheres scene, 1920x1080, 1024 spp, max_
 the ranks (fixed total work => "strong" scaling) and the step ends with the framebuffer gather
 to rank 0 — the path's only exchange.
 
-Also reported in the same JSON line:
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the JSON
+line; the fields below are null there (`also` empty), and with N > 1 `gathered_image_equals_one_gpu_render` too.  With --full,
+each is measured by a run of its own after the timed steps and reported in the same JSON line:
   verified     the framebuffer of the LAST TIMED STEP, compared on a sparse tile subset (all over the frame, at
                the full spp) with the oracle's render of the same pixels: pixels checked, max |dRGB|
   roofline     algorithmic bytes per launch (SURVEY §8d formula, visit counts from the oracle's counters on a
@@ -25,6 +27,7 @@ Also reported in the same JSON line:
                walks it (the near form of exact re-treeing) AND with VK_SCENE_EMPIRICAL_TREES), of C2 in the empirical form and with
                VK_SCENE_FAST_ACCEL, each verified the same way and, on a rebuilt tree, compared bit for bit with the same workload's frame
                on the tree as handed over (N = 1 only; --no-also skips them)
+  distributed / in_library  (N > 1) the gathered frame against ONE device's render of the whole frame, bit for bit
 
 --dump-outputs DIR writes the frame of the last timed step to DIR (dump_outputs): the inputs (scene seed 1, render seed 2) are
 fixed, so two builds run with the same arguments can be compared output for output.
@@ -274,16 +277,20 @@ def main():
                     help="host-side BVH builder: the reference's BVHNode::new (default; what a drop-in host hands over) "
                          "or the host mirror's SAH builder over the same objects (SURVEY 8f-2)")
     ap.add_argument("--spp", type=int, default=0, help="override spp (marks the result as non-headline)")
-    ap.add_argument("--cpu-spp", type=int, default=0, help="spp of the bounded CPU sample (0 = size it to ~15 s of CPU work)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the post-run check of the timed framebuffer against the oracle")
-    ap.add_argument("--no-also", action="store_true", help="skip the single steps of the other BASELINE configs")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline: the oracle check of the timed frame, roofline, physical "
+                         "bounds, HBM traffic, CPU baseline, the other trees and BASELINE configs, the multi-GPU frame against one GPU's "
+                         "(the --no-* options below leave out parts of it)")
+    ap.add_argument("--cpu-spp", type=int, default=0, help="--full: spp of the bounded CPU sample (0 = size it to ~15 s of CPU work)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the post-run check of the timed framebuffer against the oracle")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the single steps of the other trees and BASELINE configs")
     ap.add_argument("--reference-tree", action="store_true", help="set VK_SCENE_REFERENCE_TREE: walk only the tree handed over (no exact "
                     "re-treeing of scenes of spheres only)")
     ap.add_argument("--empirical-trees", action="store_true", help="set VK_SCENE_EMPIRICAL_TREES: rebuilt trees also where their exactness is "
                     "measured, not proven (include/vecchio_amd.h)")
     ap.add_argument("--no-traffic", action="store_true",
-                    help="do not measure the HBM traffic of a launch now (two one-step child runs under rocprofv3 --pmc); "
+                    help="--full: do not measure the HBM traffic of a launch now (one-step child runs under rocprofv3 --pmc); "
                          "roofline.traffic then comes from the committed profile")
     ap.add_argument("--fast-accel", action="store_true",
                     help="set VK_SCENE_FAST_ACCEL in the scene description: the library rebuilds draw-free subtrees with its SAH builder "
@@ -339,9 +346,11 @@ def main():
         n_vis = torch.cuda.device_count()
         in_lib_devices = [i % n_vis for i in range(args.gpus)] if rehearsal else list(range(args.gpus))
 
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import oracle_ffi as O
-    cores = usable_cpus()          # threads for the oracle: affinity mask capped by the cgroup quota
+    O = cores = None
+    if args.full:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import oracle_ffi as O
+        cores = usable_cpus()          # threads for the oracle: affinity mask capped by the cgroup quota
 
     TREE_NAMES = {0: "handed over", 1: "rebuilt, proven (exact re-treeing with grown gates)", 2: "rebuilt, empirical (VK_SCENE_EMPIRICAL_TREES)",
                   3: "rebuilt object by object (VK_SCENE_FAST_ACCEL)",
@@ -429,6 +438,15 @@ def main():
         if rank == 0:
             value = total_samples * steps / elapsed / 1e6
             final = (full if world > 1 else fb).cpu().numpy()    # the image the last timed step produced
+            k_ms = float(np.mean(kernel_ms)) if kernel_ms else None
+            res = {"value": round(value, 2), "ms_per_step": round(elapsed / steps * 1e3, 3), "steps": steps, "warmup": warmup,
+                   "physical": None, "kernel_ms": k_ms, "requeued_samples": ds.last_requeued_samples(),
+                   "label": label, "integrator": "scatter" if hs.integrator else "pdf", "bvh_items": info.n_items, "tree": TREE_NAMES.get(info.tree),
+                   "scene_in_lds": bool(info.lds_bytes), "verified": None, "roofline": None, "cpu_baseline": None,
+                   "tree_code": info.tree, "_frame": final}
+        if rank == 0 and args.full:
+            # --full: the companions of the headline, each a run of its own after the timed steps (the oracle on the CPU, the kernel's
+            # per-lane code on the host, profiler child runs)
             verified = None
             rgb8_gathered = world > 1 and args.rgb8
             if not args.no_verify and not rgb8_gathered:
@@ -493,7 +511,6 @@ def main():
                 nb, _ns = emu_ffi.take_visit_counts()
                 walked = {"box_tests": nb / float(ps_e.shape[0]), "oracle_box_tests": c["n_aabb"] / float(c["samples"])}
                 bps_walked = bps - 32.0 * (walked["oracle_box_tests"] - walked["box_tests"])
-            k_ms = float(np.mean(kernel_ms)) if kernel_ms else None
             # measured HBM traffic and instruction counts per launch: PMC counters cannot be collected from inside this
             # process, so they come from the committed rocprofv3 passes of this same command (profiles/, tools/experiments/prof_r02.sh):
             # WRITE_SIZE*1024 + 2*FETCH_SIZE*1024 (gfx950: FETCH_SIZE counts half the bytes of wide reads -> upper bound)
@@ -569,21 +586,19 @@ def main():
                                 "a physical bound (it can exceed 1): the physical one is `issue`",
                         "issue": issue}
             physical = physical_bounds(c, local_samples, k_ms * 1e-3, bool(info.lds_bytes), issue, walked) if k_ms else None
-            res = {"value": round(value, 2), "ms_per_step": round(elapsed / steps * 1e3, 3), "steps": steps, "warmup": warmup,
-                   "physical": physical, "kernel_ms": k_ms, "requeued_samples": ds.last_requeued_samples(),
-                   "label": label, "integrator": "scatter" if hs.integrator else "pdf", "bvh_items": info.n_items, "tree": TREE_NAMES.get(info.tree),
-                   "scene_in_lds": bool(info.lds_bytes), "verified": verified, "roofline": roof, "cpu_baseline": cpu,
-                   "tree_code": info.tree, "_frame": final}
+            res.update(physical=physical, verified=verified, roofline=roof, cpu_baseline=cpu)
         if args.in_library and rank == 0:
             # The same self-diagnosing block for ONE process driving N devices (vk_scene_create_multi): what ran where — every share's
             # device, PCI bus id, whether it can address devices[0] (else its slab goes through host memory), its kernel time in the last
-            # timed frame — how the slabs travelled, and the gathered frame against ONE device's render of the whole frame.
+            # timed frame — how the slabs travelled, and (--full) the gathered frame against ONE device's render of the whole frame.
             from vecchio_amd import ffi
             parts = ds.parts()
-            ds1 = DeviceScene(hs.desc, device=in_lib_devices[0])
-            ref, _ = ds1.render(cam, hs.params(width, spp, depth, seed=2))
-            ds1.close()
-            same = bool(np.array_equal(final.view(np.uint32), ref.view(np.uint32)))
+            same = None
+            if args.full:
+                ds1 = DeviceScene(hs.desc, device=in_lib_devices[0])
+                ref, _ = ds1.render(cam, hs.params(width, spp, depth, seed=2))
+                ds1.close()
+                same = bool(np.array_equal(final.view(np.uint32), ref.view(np.uint32)))
             res["in_library"] = {"devices": in_lib_devices, "distinct_devices": len(set(in_lib_devices)), "parts": parts,
                                  "gather": {ffi.VK_GATHER_NONE: "none (one device)", ffi.VK_GATHER_PEER_COPY: "hipMemcpyPeerAsync",
                                             ffi.VK_GATHER_RCCL: "RCCL (grouped ncclSend / ncclRecv)"}.get(info.gather),
@@ -591,36 +606,39 @@ def main():
                                  "slowest_part_kernel_ms": max(p["kernel_ms"] for p in parts),
                                  "gathered_image_equals_one_gpu_render": same}
             print(f"bench.py: in-library, {len(parts)} parts on {len(set(in_lib_devices))} device(s), gather by {res['in_library']['gather']}, "
-                  f"gathered image bit-identical to the 1-GPU render: {same}", file=sys.stderr)
-            assert same, "the in-library multi-device image differs from the one-GPU render"
+                  "gathered image bit-identical to the 1-GPU render: " + (str(same) if args.full else "not compared (--full)"), file=sys.stderr)
+            assert same is not False, "the in-library multi-device image differs from the one-GPU render"
         if world > 1:
-            # what a driver needs to see that N ranks really ran: every rank's device, and the gathered image against ONE device's
-            # render of the whole frame (bit-identical by construction: order-independent fixed-point pixel sums)
+            # what a driver needs to see that N ranks really ran: every rank's device, and (--full) the gathered image against ONE
+            # device's render of the whole frame (bit-identical by construction: order-independent fixed-point pixel sums)
             names = [None] * world
             me = {"rank": rank, "local_rank": local_rank, "device_index": dev_index, "device": torch.cuda.get_device_name(dev_index),
                   "pci_bus_id": getattr(torch.cuda.get_device_properties(dev_index), "pci_bus_id", None), "pid": os.getpid()}
             dist.all_gather_object(names, me)
             if rank == 0:
-                ds1 = DeviceScene(hs.desc, device=dev_index)
-                ref, _ = ds1.render(cam, hs.params(width, spp, depth, seed=2))
-                if args.rgb8:
-                    # the gathered frame is bytes (to_color fused into the exchange): against ONE device's own RGB8 output of the whole
-                    # frame; the oracle check then runs on that device's f32 frame
-                    from vecchio_amd import ffi
-                    ref8, _ = ds1.render(cam, hs.params(width, spp, depth, seed=2, output_format=ffi.VK_OUTPUT_RGB8))
-                    same = bool((full.cpu().numpy() == ref8).all())
-                    if not args.no_verify:
-                        res["verified"] = verify_against_oracle(O, hs, cam, ref, width, spp, depth)
-                        res["verified"]["note"] = "the one-GPU f32 frame, whose RGB8 output the gathered frame equals byte for byte"
-                else:
-                    same = bool((full.cpu().numpy() == ref).all())
-                ds1.close()
+                same = None
+                if args.full:
+                    ds1 = DeviceScene(hs.desc, device=dev_index)
+                    ref, _ = ds1.render(cam, hs.params(width, spp, depth, seed=2))
+                    if args.rgb8:
+                        # the gathered frame is bytes (to_color fused into the exchange): against ONE device's own RGB8 output of the
+                        # whole frame; the oracle check then runs on that device's f32 frame
+                        from vecchio_amd import ffi
+                        ref8, _ = ds1.render(cam, hs.params(width, spp, depth, seed=2, output_format=ffi.VK_OUTPUT_RGB8))
+                        same = bool((full.cpu().numpy() == ref8).all())
+                        if not args.no_verify:
+                            res["verified"] = verify_against_oracle(O, hs, cam, ref, width, spp, depth)
+                            res["verified"]["note"] = "the one-GPU f32 frame, whose RGB8 output the gathered frame equals byte for byte"
+                    else:
+                        same = bool((full.cpu().numpy() == ref).all())
+                    ds1.close()
                 res["distributed"] = {"world_size": dist.get_world_size(), "backend": dist.get_backend(), "ranks": names,
                                       "distinct_devices": len({(n["device_index"]) for n in names}),
                                       "gathered_image_equals_one_gpu_render": same,
                                       "self_launched": os.environ.get("VK_BENCH_SELF_LAUNCHED") == "1"}
-                print(f"bench.py: {world} ranks ({dist.get_backend()}), gathered image bit-identical to the 1-GPU render: {same}", file=sys.stderr)
-                assert same, "the gathered multi-rank image differs from the one-GPU render"
+                print(f"bench.py: {world} ranks ({dist.get_backend()}), gathered image bit-identical to the 1-GPU render: "
+                      + (str(same) if args.full else "not compared (--full)"), file=sys.stderr)
+                assert same is not False, "the gathered multi-rank image differs from the one-GPU render"
         ds.close()
         hs.close()
         return res
@@ -635,7 +653,7 @@ def main():
     handed_over = None
     frames = {}            # workload -> its frame on the tree as handed over
     exact_mismatch = []    # a tree that claims the handed-over tree's results and does not deliver them
-    if n_gpus == 1 and not args.no_also and not args.spp and not args.reference_tree and rank == 0:
+    if args.full and n_gpus == 1 and not args.no_also and not args.spp and not args.reference_tree and rank == 0:
         # the same workload on the tree of the description alone: the number the rebuilt tree has to be read against
         r = run_workload(args.workload, 1, 1, 0, handed_over_tree=True)
         # ... and the frame the default has to EQUAL, bit for bit: the last timed frame of the headline against this one (exact re-treeing
@@ -649,7 +667,7 @@ def main():
         if not same:
             exact_mismatch.append(f"{args.workload} default ({main_res['tree']}) differs from the tree as handed over in "
                                   f"{int((main_res['_frame'] != frames[args.workload]).any(axis=2).sum())} pixels")
-    if n_gpus == 1 and not args.no_also and args.workload == "C2" and not args.spp:
+    if args.full and n_gpus == 1 and not args.no_also and args.workload == "C2" and not args.spp:
         # (C5: on the tree as handed over first — the frame its default, the near form of exact re-treeing, must equal)
         for name, spp_o, fa, ho, emp in (("C4", 0, False, False, False), ("C3", 0, False, False, False), ("C5", 0, False, True, False),
                                          ("C5", 0, False, False, False), ("C5", 0, False, False, True), ("C2", 0, False, False, True),
@@ -684,6 +702,7 @@ def main():
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic" if not rehearsal else "synthetic (REHEARSAL: all ranks on one GPU, gloo)",
+            "full": args.full,       # False: the companions below (verified, roofline, ...) were not measured (null)
             "config": {"workload": r["label"], "scene_seed": 1, "render_seed": 2,
                        "integrator": r["integrator"], "tiles": "8x8 round-robin over ranks", "multi_gpu": mode,
                        "bvh_builder": args.bvh, "bvh_items": r["bvh_items"], "scene_in_lds": r["scene_in_lds"],

@@ -140,7 +140,7 @@ def test_tile_partition_covers_image_once():
 def test_bench_gpus_n_without_a_launcher_starts_n_ranks(device):
     """`python bench.py --gpus 2` — the driver's command shape, no torchrun — must start two ranks itself (as a CHILD process of
     a parent that never touches the GPU), render the frame tile-parallel, gather it and say so in its JSON line: world size,
-    backend, one device record per rank, and the gathered image bit-identical to ONE device's render of the whole frame.
+    backend, one device record per rank, and (--full) the gathered image bit-identical to ONE device's render of the whole frame.
     Rehearsal on the box's single GPU: both ranks on device 0, gloo instead of RCCL (VK_BENCH_REHEARSAL=1)."""
     import json
     import subprocess
@@ -148,13 +148,13 @@ def test_bench_gpus_n_without_a_launcher_starts_n_ranks(device):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--spp", "16",
-                        "--no-cpu", "--no-also", "--no-traffic"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu", "--no-also", "--no-traffic"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
     # ... and with the output stage fused into the exchange (RGB8 slabs)
     r8 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--spp", "16",
-                         "--no-cpu", "--no-also", "--no-traffic", "--rgb8"], env=env, capture_output=True, text=True, timeout=600)
+                         "--full", "--no-cpu", "--no-also", "--no-traffic", "--rgb8"], env=env, capture_output=True, text=True, timeout=600)
     assert r8.returncode == 0, r8.stdout[-2000:] + r8.stderr[-4000:]
     d8 = json.loads([l for l in r8.stdout.splitlines() if l.startswith("{")][-1])
     assert d8["distributed"]["gathered_image_equals_one_gpu_render"] is True and d8["verified"]["ok"] is True
