@@ -59,7 +59,8 @@ int vk_debug_progress_moments(vk_progress *pr, long long *run, double *m2);
  * summed over the exit tests.                                                                                   */
 int vk_debug_phase_stats(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint64_t out[24]);
 /* evaluate the shared host/device arithmetic ON THE DEVICE (host arrays in/out):
- * op 0 sin, 1 cos, 2 ln, 3 asin, 4 atan2(a,b), 5 pow5, 6 a/b, 7 sqrt(a), 8 draws, 9 a*b+a  */
+ * op 0 sin, 1 cos, 2 ln, 3 asin, 4 atan2(a,b), 5 pow5, 6 a/b, 7 sqrt(a), 8 draws, 9 a*b+a, 10 the sphere test's a/b,
+ * 11 / 12 sincos .s / .c, 13 / 14 the samplers' sincos (0 <= a < 2^22) .s / .c                                      */
 int vk_debug_math(int device, int op, const float *a, const float *b, float *out, size_t n);
 
 #ifdef __cplusplus

@@ -1234,6 +1234,10 @@ void oracle_math(int op, const float *a, const float *b, float *out, size_t n) {
             case 3: out[i] = vk::asinf_(a[i]); break;
             case 4: out[i] = vk::atan2f_(a[i], b[i]); break;
             case 5: out[i] = vk::pow5f_(a[i]); break;
+            case 11: out[i] = vk::sincosf_(a[i]).s; break;        // (6-10: the device probe's IEEE / division checks)
+            case 12: out[i] = vk::sincosf_(a[i]).c; break;
+            case 13: out[i] = vk::sincosf_small_(a[i]).s; break;
+            case 14: out[i] = vk::sincosf_small_(a[i]).c; break;
             default: out[i] = 0.0f;
         }
     }

@@ -59,7 +59,8 @@ int oracle_sample(const vk_scene_desc *desc, const vk_camera *cam, const vk_rend
 int oracle_hit(const vk_scene_desc *desc, const float origin[3], const float dir[3], float time,
                float tmin, float tmax, uint64_t seed, float rec_out[11]);
 
-/* shared-math probes (unit tests against libm): op 0 sin,1 cos,2 log,3 asin,4 atan2(a,b),5 pow5 */
+/* shared-math probes (unit tests): op 0 sin,1 cos,2 log,3 asin,4 atan2(a,b),5 pow5, 11/12 sincos .s/.c, 13/14 sincos_small .s/.c
+ * (the numbers of the device probe, vk_debug_math)                                                                          */
 void oracle_math(int op, const float *a, const float *b, float *out, size_t n);
 /* draw probes: kind 0 gen_f32, 1 gen_range(lo,hi), 2 gen_index(n) (as float) */
 void oracle_draws(uint64_t seed, uint32_t pixel, uint32_t sample, int kind, float lo, float hi,

@@ -68,6 +68,60 @@ def test_device_arithmetic_is_bit_identical_to_host(device, oracle):
     assert np.array_equal(dev(9, a, b), (a * b).astype(np.float32) + a)
 
 
+def test_device_math_equals_host_over_the_domain(device, oracle):
+    """The inputs of tests/test_math_domain.py on the device, bit for bit against the host's build of the same header (the oracle):
+    the stride-61 sweep of all 2^32 bit patterns, the special values, the samplers' angles, the neighbourhood of the reduction
+    switch at +-2^22, asin near +-1, the ln ranges, and for atan2 the random bit-pattern pairs, the C99 special pairs and the
+    extreme ratios; sincos (ops 11 / 12) and the samplers' bounded sincos (13 / 14, on its domain [+0, 2^22)) included.  Then the
+    device directly against the correctly rounded reference on a sample of each, so that a common-mode change cannot hide behind
+    the equality."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    import math_domain as MD
+    lib = ffi.load_debug_lib()
+
+    def dev(op, x, y=None):
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.zeros_like(x) if y is None else np.ascontiguousarray(y, np.float32)
+        assert 0 < x.size <= 1 << 24
+        out = np.empty_like(x)
+        assert lib.vk_debug_math(0, op, x.ctypes.data, y.ctypes.data, out.ctypes.data, x.size) == 0, lib.vk_last_error()
+        return out
+
+    # (a, b) = the arguments of the probe: unary ops read a; atan2 is atan2(a, b)
+    ya, xa = MD.atan2_random_pairs(1 << 22, seed=21)
+    pairs = [(ya, xa), MD.atan2_special_pairs(), MD.atan2_extreme_pairs()]
+    jobs = [(x, None, (0, 1, 2, 3, 5, 11, 12)) for x in list(MD.sweep_chunks()) + [MD.specials(), MD.switch_neighbourhood(),
+            MD.asin_near_one()] + list(MD.sampler_angles()) + list(MD.log_ranges())] + [(a, b, (4,)) for a, b in pairs]
+
+    def host(job):
+        a, b, ops = job
+        return [oracle.math(op, a, b) for op in ops]
+
+    n = 0
+    width = max(1, min(16, len(os.sched_getaffinity(0))))
+    with ThreadPoolExecutor(width) as pool:
+        for g in range(0, len(jobs), width):                     # (a group at a time: bounded memory)
+            group = jobs[g:g + width]
+            for (a, b, ops), want in zip(group, pool.map(host, group)):
+                for op, w in zip(ops, want):
+                    d = ~MD.same(dev(op, a, b), w)
+                    assert not d.any(), f"op {op}: {int(d.sum())} of {a.size} device results differ from the host's, e.g. at {a[d][:4]}"
+                    n += a.size
+                x = a[(a >= 0) & (a < 2.0 ** 22) & ~np.signbit(a)]
+                if b is None and x.size:                         # the samplers' sincos on its domain, against sinf_ / cosf_
+                    assert np.array_equal(dev(13, x).view(np.uint32), dev(0, x).view(np.uint32))
+                    assert np.array_equal(dev(14, x).view(np.uint32), dev(1, x).view(np.uint32))
+    assert n > 7 * 70_000_000
+    # the device against the correctly rounded reference itself: every 16th chunk of the sweep, the specials, the switch
+    sample = [np.concatenate(list(MD.sweep_chunks())[::16]), MD.specials(), MD.switch_neighbourhood()]
+    for fn in MD.UNARY:
+        for x in sample:
+            assert MD.same(dev(MD.OP[fn], x), MD.correctly_rounded(fn, x)).all(), fn
+    for a, b in pairs:
+        assert MD.same(dev(4, a, b), MD.correctly_rounded("atan2", a, b)).all()
+
+
 def test_quotients_by_a_shared_reciprocal_are_the_divisions(device):
     """vk_trace.h div_by_a: the sphere test's n / |d|^2 from a reciprocal refined once and two fma corrections, in the range it is used
     in (|d|^2 in 3e-12 .. 3e12, |n| < 2^54, quotients down to far below tmin): 2^26 pairs, every one the correctly rounded quotient."""

@@ -1207,6 +1207,10 @@ __global__ void math_probe_kernel(int op, const float *a, const float *b, float 
             r = vk::gen_range(g, -1.0f, 1.0f) + vk::gen_f32(g); break; }
         case 9: r = a[i] * b[i] + a[i]; break;   // must stay an unfused mul+add
         case 10: r = div_by_a(a[i], b[i], refined_rcp(b[i]), true); break;      // the sphere test's quotient by a shared reciprocal
+        case 11: r = vk::sincosf_(a[i]).s; break;
+        case 12: r = vk::sincosf_(a[i]).c; break;
+        case 13: r = vk::sincosf_small_(a[i]).s; break;       // (0 <= a < 2^22 only)
+        case 14: r = vk::sincosf_small_(a[i]).c; break;
     }
     out[i] = r;
 }

@@ -8,7 +8,8 @@
 // is replaced by a counter-based one keyed (seed, pixel, sample) and the transcendental
 // functions are implemented here from +,-,*,/ only (IEEE, no FMA contraction: every
 // translation unit that includes this file is compiled with -ffp-contract=off), which makes
-// host and device results identical by construction.  tests/ checks them against libm.
+// host and device results identical by construction.  tests/test_math_domain.py checks them against
+// the correctly rounded value over the whole f32 domain.
 //
 // The float mappings of the draws follow rand 0.7.3 (Cargo.lock; third-party, not vendored,
 // restated from its published algorithm):
@@ -165,11 +166,16 @@ VK_HD uint32_t usize_low8(float f) {
 }
 
 // ---------------------------------------------------------------------------------------
-// transcendental functions: evaluated in f64 with +,-,*,/ only, rounded once to f32.
-// (f32 results are within ~0.5000001 ulp of the true value; they agree with a correctly
-// rounded libm except on the rare argument that falls within 1e-9 ulp of a rounding tie.)
+// transcendental functions: evaluated in f64 with +,-,*,/ only (the reduction of large sin / cos
+// arguments in integer arithmetic), rounded once to f32.  tests/test_math_domain.py holds sin, cos,
+// sincos, ln, asin, atan2 and x^5 to the correctly rounded value (a float64 reference, settled by
+// mpmath near rounding ties) over a stride-61 sweep of all 2^32 inputs, the ranges the render path
+// uses and the special values (signed zeros, subnormals, FLT_MAX, inf, NaN; C99 Annex F for atan2):
+// 0 ulp everywhere it looks.  tests/test_gpu_parity.py checks the device bit for bit on the same inputs.
 
-// reduce x to r in [-pi/4, pi/4], returns quadrant (low 2 bits valid)
+// reduce x to r in [-pi/4, pi/4], returns quadrant (low 2 bits valid).  Two-constant Cody-Waite: the
+// product kd * PIO2_1 is exact while kd has at most 20 bits, so this is accurate for |x| < 2^22 only
+// (rem_pio2f sends larger arguments to rem_pio2_large).
 VK_HD int rem_pio2(double x, double &r) {
     const double TWO_OVER_PI = 6.36619772367581382433e-01;
     const double PIO2_1 = 1.57079632673412561417e+00;   // first 33 bits of pi/2
@@ -179,6 +185,86 @@ VK_HD int rem_pio2(double x, double &r) {
     kd = kd - MAGIC;
     r = (x - kd * PIO2_1) - kd * PIO2_1T;
     return (int)(long long)kd;
+}
+
+// 32-bit word k of the binary expansion of 2/pi after one word of leading zeros: word k >= 1 holds bits 32k-31 .. 32k of
+// 2/pi = 0.A2F9836E 4E441529 ... (hex).  Selected by comparisons, not read from an array, so the device needs neither constant
+// memory nor scratch for it.
+VK_HD uint32_t two_over_pi_word(int k) {
+    return k == 1 ? 0xA2F9836Eu : k == 2 ? 0x4E441529u : k == 3 ? 0xFC2757D1u : k == 4 ? 0xF534DDC0u
+         : k == 5 ? 0xDB629599u : k == 6 ? 0x3C439041u : k == 7 ? 0xFE5163ABu : k == 8 ? 0xDEBBC561u : 0u;
+}
+
+// high 64 bits of the 128-bit product a * b
+VK_HD uint64_t mul_hi64(uint64_t a, uint64_t b) {
+    uint64_t a0 = (uint32_t)a, a1 = a >> 32, b0 = (uint32_t)b, b1 = b >> 32;
+    uint64_t lh = a0 * b1, hl = a1 * b0;
+    uint64_t mid = ((a0 * b0) >> 32) + (uint32_t)lh + (uint32_t)hl;
+    return a1 * b1 + (lh >> 32) + (hl >> 32) + (mid >> 32);
+}
+
+// rem_pio2 for |x| >= 2^22 (Payne-Hanek, in integers): x = m 2^e with a 24-bit integer m and e in [-1, 104].  Bits of 2/pi above
+// weight 2^(1-e) contribute multiples of 4 to x * 2/pi and are skipped; the 128 bits from there on, W, give
+// x * 2/pi = m W 2^-126 (mod 4) with an error below 2^-102.  Bits 126-127 of m W are the quadrant, bits 0-125 the fraction, of
+// which the 64 leading significant ones are multiplied by pi/2 in 64-bit fixed point (relative error < 2^-61 before the one
+// rounding to f64).  Integer steps, one correctly rounded f64 addition and a multiplication by a power of two: host and device
+// agree by construction.  inf / NaN: r = NaN.
+struct Reduced { double r; int q; };
+VK_HD Reduced rem_pio2_large(float xf) {
+    uint32_t u = f32_bits(xf);
+    uint32_t be = (u >> 23) & 0xFFu;
+    double r;
+    if (be == 0xFFu) { Reduced o; o.r = (double)(xf - xf); o.q = 0; return o; }
+    uint64_t m = (u & 0x7FFFFFu) | 0x800000u;
+    int p = (int)be - 120;                       // bit position of the window in the zero-prefixed table: (e - 1) + 31, e = be - 150
+    int w = p >> 5, sh = p & 31;
+    uint32_t t0 = two_over_pi_word(w), t1 = two_over_pi_word(w + 1), t2 = two_over_pi_word(w + 2),
+             t3 = two_over_pi_word(w + 3), t4 = two_over_pi_word(w + 4);
+    uint64_t w0 = (uint32_t)((((uint64_t)t0 << 32) | t1) >> (32 - sh)), w1 = (uint32_t)((((uint64_t)t1 << 32) | t2) >> (32 - sh)),
+             w2 = (uint32_t)((((uint64_t)t2 << 32) | t3) >> (32 - sh)), w3 = (uint32_t)((((uint64_t)t3 << 32) | t4) >> (32 - sh));
+    // m W mod 2^128 in 32-bit limbs (each m * w_j < 2^56)
+    uint64_t c = m * w3;
+    uint32_t l0 = (uint32_t)c;
+    c = m * w2 + (c >> 32);
+    uint32_t l1 = (uint32_t)c;
+    c = m * w1 + (c >> 32);
+    uint32_t l2 = (uint32_t)c;
+    c = m * w0 + (c >> 32);
+    uint32_t l3 = (uint32_t)c;
+    int q = (int)(l3 >> 30);
+    // the fraction scaled by 2^128, rounded to the nearest quadrant: |f| <= 1/2
+    uint64_t fhi = ((uint64_t)l3 << 34) | ((uint64_t)l2 << 2) | (l1 >> 30), flo = ((uint64_t)l1 << 34) | ((uint64_t)l0 << 2);
+    bool neg = (fhi >> 63) != 0;
+    if (neg) {                                   // f - 1: magnitude 2^128 - f
+        q += 1;
+        fhi = ~fhi; flo = ~flo + 1u;
+        if (flo == 0u) fhi += 1u;
+    }
+    int lz = 0;
+    if (fhi == 0u) { fhi = flo; flo = 0u; lz = 64; }
+    if (fhi == 0u) { r = 0.0; q = 0; }           // (not reached: m W would be an exact multiple of 2^126)
+    else {
+        int s = __builtin_clzll(fhi);
+        fhi = s ? (fhi << s) | (flo >> (64 - s)) : fhi;
+        lz += s;
+        uint64_t h = mul_hi64(fhi, 0xC90FDAA22168C235ull);    // pi/2 = 0xC90FDAA22168C235 2^-63 (rounded)
+        double hd = (double)(uint32_t)(h >> 32) * 4294967296.0 + (double)(uint32_t)h;
+        r = hd * bits_f64((uint64_t)(1023 - 63 - lz) << 52);
+        if (neg) r = -r;
+    }
+    if (u >> 31) { q = -q; r = -r; }
+    Reduced o;
+    o.r = r; o.q = q;
+    return o;
+}
+
+// x = q pi/2 + r, |r| <= pi/4 (+ rounding), for every f32 x; r = NaN for inf / NaN
+VK_HD int rem_pio2f(float xf, double &r) {
+    double x = (double)xf;
+    if (x > -4194304.0 && x < 4194304.0) return rem_pio2(x, r);
+    Reduced o = rem_pio2_large(xf);      // |x| >= 2^22: a checker / marble texture far from the origin at most
+    r = o.r;
+    return o.q;
 }
 
 VK_HD double k_sin(double r) {
@@ -207,26 +293,24 @@ VK_COLD float sinf_(float x) { return ::sinf(x); }
 VK_COLD float cosf_(float x) { return ::cosf(x); }
 struct SinCos { float s, c; };
 VK_COLD SinCos sincosf_(float x) { SinCos o; o.s = ::sinf(x); o.c = ::cosf(x); return o; }
+VK_COLD SinCos sincosf_small_(float x) { return sincosf_(x); }
 VK_COLD float logf_(float x) { return ::logf(x); }
 VK_COLD float atan2f_(float y, float x) { return ::atan2f(y, x); }
 VK_COLD float asinf_(float x) { return ::asinf(x); }
 VK_HD float pow5f_(float x) { return ::powf(x, 5.0f); }
 #else
+// sin(+-0) = +-0: k_sin(-0) alone gives +0
 VK_COLD float sinf_(float xf) {
-    double x = (double)xf;
-    if (!(x > -1.0e9 && x < 1.0e9)) return xf - xf;  // inf/NaN -> NaN; |x|>=1e9 unsupported -> 0
     double r;
-    int q = rem_pio2(x, r);
+    int q = rem_pio2f(xf, r);
     double v = (q & 1) ? k_cos(r) : k_sin(r);
     if (q & 2) v = -v;
-    return (float)v;
+    return xf == 0.0f ? xf : (float)v;
 }
 
 VK_COLD float cosf_(float xf) {
-    double x = (double)xf;
-    if (!(x > -1.0e9 && x < 1.0e9)) return xf - xf;
     double r;
-    int q = rem_pio2(x, r);
+    int q = rem_pio2f(xf, r);
     double v = (q & 1) ? k_sin(r) : k_cos(r);
     if ((q + 1) & 2) v = -v;
     return (float)v;
@@ -235,12 +319,8 @@ VK_COLD float cosf_(float xf) {
 // sin and cos of the same angle, bit-identical to sinf_(x) and cosf_(x) (one reduction, one
 // evaluation of each kernel polynomial)
 struct SinCos { float s, c; };
-VK_COLD SinCos sincosf_(float xf) {
+VK_HD SinCos sincos_reduced(double r, int q) {
     SinCos o;
-    double x = (double)xf;
-    if (!(x > -1.0e9 && x < 1.0e9)) { o.s = xf - xf; o.c = xf - xf; return o; }
-    double r;
-    int q = rem_pio2(x, r);
     double ks = k_sin(r), kc = k_cos(r);
     double vs = (q & 1) ? kc : ks;
     double vc = (q & 1) ? ks : kc;
@@ -249,6 +329,21 @@ VK_COLD SinCos sincosf_(float xf) {
     o.s = (float)vs;
     o.c = (float)vc;
     return o;
+}
+VK_COLD SinCos sincosf_(float xf) {
+    double r;
+    int q = rem_pio2f(xf, r);
+    SinCos o = sincos_reduced(r, q);
+    if (xf == 0.0f) o.s = xf;
+    return o;
+}
+
+// sincosf_ for 0 <= x < 2^22, not -0 (the samplers' angles 2 pi u, u in [0, 1)): the same bits there, without the large-argument
+// reduction and the zero test
+VK_COLD SinCos sincosf_small_(float xf) {
+    double r;
+    int q = rem_pio2((double)xf, r);
+    return sincos_reduced(r, q);
 }
 
 // natural log (hittable.rs:473); x is a 24-bit draw in [0,1) there, general f32 supported

@@ -1107,7 +1107,12 @@ VK_COLD V3 texture_value(const DTexture *textures, const DImage *images, const u
         const DTexture &t = textures[tex];
         if (t.kind == VK_TEX_SOLID) return v3(t.r, t.g, t.b);
         if (t.kind == VK_TEX_CHECKER) {  // material.rs:250-258
-            float sins = vk::sinf_(10.0f * p.x) * vk::sinf_(10.0f * p.y) * vk::sinf_(10.0f * p.z);
+            float sins = 1.0f;      // (one sinf_ in a loop: three inlined side by side spill in the shading function)
+#pragma nounroll
+            for (int k = 0; k < 3; k++) {
+                float s = vk::sinf_(10.0f * (k == 0 ? p.x : k == 1 ? p.y : p.z));
+                sins = k == 0 ? s : sins * s;
+            }
             tex = sins < 0.0f ? t.a : t.b_;
             continue;
         }
@@ -1180,7 +1185,7 @@ VK_HD V3 random_cosine_direction(Rng &g) {
     float r1 = vk::gen_f32(g), r2 = vk::gen_f32(g);
     float z = sqrtf(1.0f - r2);
     float phi = 2.0f * r1 * PI_F;
-    vk::SinCos sc = vk::sincosf_(phi);
+    vk::SinCos sc = vk::sincosf_small_(phi);      // phi in [0, 2 pi]
     float x = sc.c * sqrtf(r2);
     float y = sc.s * sqrtf(r2);
     return v3(x, y, z);
@@ -1189,7 +1194,7 @@ VK_HD V3 lambertian_random(Rng &g) {
     float a = vk::gen_0_to(g, 2.0f * PI_F);                   // gen_range(0, 2 pi)
     float z = vk::gen_pm1(g);                                 // gen_range(-1, 1)
     float r = sqrtf(1.0f - z * z);
-    vk::SinCos sc = vk::sincosf_(a);
+    vk::SinCos sc = vk::sincosf_small_(a);
     return v3(r * sc.c, r * sc.s, z);
 }
 VK_HD V3 reflect(V3 v, V3 n) { return v - n * dot(v, n) * 2.0f; }  // util.rs:14-16
@@ -1265,7 +1270,7 @@ VK_HD V3 random_to_sphere(Rng &g, float radius, float distance_squared) {  // hi
     float r1 = vk::gen_f32(g), r2 = vk::gen_f32(g);
     float z = 1.0f + r2 * (sqrtf(1.0f - radius * radius / distance_squared) - 1.0f);
     float phi = 2.0f * PI_F * r1;
-    vk::SinCos sc = vk::sincosf_(phi);
+    vk::SinCos sc = vk::sincosf_small_(phi);      // phi in [0, 2 pi]
     float x = sc.c * (1.0f - z * z);
     float y = sc.s * (1.0f - z * z);
     return v3(x, y, z);
