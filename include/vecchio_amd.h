@@ -482,6 +482,41 @@ typedef struct vk_adaptive_info {
  * the partition; out and info may each be NULL.  Any handle (without adaptivity every tile has samples_done).  Waits for the last step. */
 int vk_progress_tile_samples(vk_progress *pr, uint32_t *out, vk_adaptive_info *info);
 
+/* ---- first-hit buffers, "AOVs" (additive symbols of ABI 7) ----------------------------------------------------------------------
+ * replaces: nothing (the reference writes radiance only).  The first hit's albedo, normal, depth and coverage of exactly the primary rays
+ * that vk_render's radiance samples use — what a denoiser or a compositor takes next to the noisy colour.  Per pixel of this call's tile
+ * partition (pixels outside it are left untouched), in vk_render's f32 layout (y = 0 the bottom row): albedo and normal 3 floats per
+ * pixel, depth and coverage 1.  Any of the four buffers may be NULL (not wanted), not all four.
+ *   Samples.  first_sample .. first_sample + spp - 1, spp = params->samples_per_pixel.  Sample s is the primary ray of radiance sample s
+ *     (stream (seed, pixel, s), camera draws first); a ConstantMedium draws its distance from that same stream after them, so sample s
+ *     sees the first hit radiance sample s sees.
+ *   First hit.  BVHNode::hit (accel.rs:58-83) with tmin 0.001, tmax inf on the tree AS HANDED OVER, also where vk_render walks a rebuilt
+ *     one (exact re-treeing: the tree its second launch walks; none of the rebuilt forms is used).  A VK_SCENE_FAST_ACCEL scene keeps no
+ *     copy of the tree as handed over on the device: there the rebuilt tree (the one vk_render walks, ties as the reference breaks them)
+ *     is walked.
+ *   Albedo of a hit: Lambertian / Metal / Isotropic the texture value at (u, v, p); Dielectric (1,1,1); DiffuseLight emitted(rec) (front
+ *     faces only, material.rs:218-225) clamped to [0, 1]; SpecDiffuse pct * A(specular) + (1 - pct) * A(diffuse) in f32, recursively,
+ *     0 below 8 SpecDiffuse levels.  A miss: the background the radiance sees (sky or solid), clamped to [0, 1].
+ *   Normal of a hit: HitRec.normal in world space, face-oriented (set_face_normal); (0,0,0) for a medium hit and for a miss.
+ *   Depth of a hit: t * |d| in f32, the distance from the sample's ray origin.
+ *   Dropped samples: a sample with a non-finite albedo, normal or depth component adds to no sum and not to `hits`, but counts in n = spp.
+ *   Aggregation, exact and in a fixed order: f32 sums in increasing sample order, then albedo = sum / (float)n, normal = sum / (float)n
+ *     (misses included, not renormalised), depth = sum / (float)hits or +INFINITY without a hit, coverage = (float)hits / (float)n.  One
+ *     value per (scene, camera, seed, window), whatever the launch shape.
+ *   Arguments: vk_render's checks (null pointers, size, spp in 1..2^26, time0 < time1, ranges, tile_rank < tile_world), and also
+ *     VK_ERR_BAD_ARG with nothing enqueued for output_format != VK_OUTPUT_F32, four NULL buffers, first_sample + spp > 2^32 - 1.
+ *     max_depth and integrator are ignored.
+ *   Scene state: "at most one render in flight per vk_scene" covers these calls too.  They touch nothing that describes vk_render's last
+ *     frame (vk_scene_last_kernel_ms, the clamped and requeued counts, vk_debug_last_launches, the rebuilt tree's suspension) and no
+ *     vk_progress handle.  stats_out: the AOV samples traced (partition pixels x spp), kernel_ms (vk_render_aov only), kernel_launches;
+ *     clamped_samples = 0, scene_in_lds = 0 (the walk reads global memory).
+ *   Multi-device scenes: the whole call runs on devices[0].                                                                      */
+int vk_render_aov(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
+                  float *albedo, float *normal, float *depth, float *coverage, vk_stats *stats_out);
+/* device buffers on the scene's device (devices[0] of a multi-device scene), enqueued on hip_stream, no host wait */
+int vk_render_aov_device(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
+                         void *d_albedo, void *d_normal, void *d_depth, void *d_coverage, void *hip_stream, vk_stats *stats_out);
+
 /* test/diagnostic entry points (vk_debug_*) are declared in vecchio_amd_debug.h */
 
 #ifdef __cplusplus

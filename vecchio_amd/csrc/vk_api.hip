@@ -255,6 +255,9 @@ struct vk_scene {
     std::vector<ncclComm_t> comms;
     // the render_kernel launches of the last frame (vk_debug_last_launches: tests); host bookkeeping, cleared per frame
     std::vector<vk_debug_launch> launch_log;
+    // vk_render_aov: its own events and output buffers, so that nothing that describes vk_render's last frame is touched
+    hipEvent_t aov_ev0 = nullptr, aov_ev1 = nullptr;
+    float *aov_buf = nullptr; size_t aov_bytes = 0;
 };
 
 namespace {
@@ -442,7 +445,8 @@ int launch_by_features(vk_scene *s, uint32_t F, const KArgs &A, bool lds, dim3 g
     }
 }
 
-int check_render_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p) {
+// the checks of every call that takes a camera and render parameters (vk_render, vk_progress_create, vk_render_aov)
+int check_call_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p) {
     if (!scene || !cam || !p) return fail(VK_ERR_BAD_ARG, "null argument");
     if (p->width < 2 || p->height < 2) return fail(VK_ERR_BAD_ARG,
         "width and height must be >= 2 (u,v divide by width-1/height-1, main.rs:187-188)");
@@ -455,6 +459,12 @@ int check_render_args(vk_scene *scene, const vk_camera *cam, const vk_render_par
     if (p->output_format > VK_OUTPUT_RGB8) return fail(VK_ERR_BAD_ARG, "bad output_format");
     uint32_t world = p->tile_world ? p->tile_world : 1;
     if (p->tile_rank >= world) return fail(VK_ERR_BAD_ARG, "tile_rank >= tile_world");
+    return VK_OK;
+}
+
+int check_render_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p) {
+    int rc = check_call_args(scene, cam, p);
+    if (rc != VK_OK) return rc;
     const LinearScene &H = *scene->host;
     if (p->integrator == VK_INTEGRATOR_PDF && H.lights.empty())
         return fail(VK_ERR_UNSUPPORTED, "PDF integrator with an empty lights list (Vec::random unwraps None, hittable.rs:431)");
@@ -1026,11 +1036,13 @@ void destroy_one(vk_scene *s) {
     for (void *p : s->allocs) (void)hipFree(p);
     for (void *p : {(void *)s->counter, (void *)s->fb, (void *)s->fb8, (void *)s->accum, (void *)s->debug, (void *)s->phase_stats,
         (void *)s->tile_cost,
-                    (void *)s->tile_order, (void *)s->order_hist, (void *)s->slab, (void *)s->redo_list, (void *)s->redo_count})
+                    (void *)s->tile_order, (void *)s->order_hist, (void *)s->slab, (void *)s->redo_list, (void *)s->redo_count,
+                    (void *)s->aov_buf})
         if (p) (void)hipFree(p);
     if (s->plan_host) (void)hipHostFree(s->plan_host);
     if (s->landing) { (void)hipSetDevice(s->landing_device); (void)hipFree(s->landing); (void)hipSetDevice(s->device); }
-    for (hipEvent_t e : {s->ev0, s->ev1, s->ev_landed, s->ev_begin, s->ev_fork, s->ev_join, s->ev_plan[0], s->ev_plan[1]})
+    for (hipEvent_t e : {s->ev0, s->ev1, s->ev_landed, s->ev_begin, s->ev_fork, s->ev_join, s->ev_plan[0], s->ev_plan[1], s->aov_ev0,
+                         s->aov_ev1})
         if (e) (void)hipEventDestroy(e);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     if (s->stream2) (void)hipStreamDestroy(s->stream2);
@@ -1571,6 +1583,136 @@ int vk_debug_last_launches(vk_scene *scene, vk_debug_launch *out, uint32_t cap, 
     *n = (uint32_t)all.size();
     for (uint32_t k = 0; k < cap && k < *n; k++) out[k] = all[k];
     return VK_OK;
+}
+
+}  // extern "C"
+
+// ---- first-hit buffers (vk_render_aov): one launch of aov_kernel on the scene's device (devices[0] of a multi-device scene), on its own
+// events and output buffers.  Nothing that describes vk_render's last frame (events, counters, launch log, verdicts on the rebuilt tree) is
+// read or written, and no progress handle's sums.
+namespace {
+
+// The tree the first-hit walk runs on: the tree as handed over.  Where the scene has a second launch (exact re-treeing staged in LDS, or
+// the grid form) that is s->ref_view, the REDO launch's view; where both trees share items[] (exact re-treeing from global memory) it is
+// their first part, whose exits lead past the rebuilt tree (vk_linearize.cpp combined_items) — the in-place redo walk's tree.  Anywhere
+// else the scene holds one tree: the one handed over, or under VK_SCENE_FAST_ACCEL the rebuilt one (with its tie table), which is then
+// also what vk_render walks — such a scene has no copy of the tree as handed over on the device.
+DScene aov_view(const vk_scene *s) {
+    if (s->exact) return s->ref_view;
+    DScene v = s->dev;
+    if (v.walk_start != 0u) {
+        v.walk_start = 0u; v.primary_ref = 0u; v.t_pad = 0.0f; v.gate_scale = 1.0f; v.tmin_gate = T_MIN; v.tie_rank = nullptr;
+        v.ref_items = nullptr; v.n_ref_items = 0u;
+    }
+    return v;
+}
+
+int check_aov_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p, uint32_t first_sample, const void *const bufs[4]) {
+    int rc = check_call_args(scene, cam, p);
+    if (rc != VK_OK) return rc;
+    if (p->output_format != VK_OUTPUT_F32) return fail(VK_ERR_BAD_ARG, "first-hit buffers are f32 only (output_format must be VK_OUTPUT_F32)");
+    if (!bufs[0] && !bufs[1] && !bufs[2] && !bufs[3]) return fail(VK_ERR_BAD_ARG, "no first-hit buffer wanted (all four are null)");
+    if ((uint64_t)first_sample + p->samples_per_pixel > 0xFFFFFFFFull) return fail(VK_ERR_BAD_ARG,
+        "first_sample + samples_per_pixel exceeds 2^32 - 1");
+    return VK_OK;
+}
+
+// floats per pixel of albedo, normal, depth, coverage
+constexpr uint32_t AOV_COMPONENTS[4] = {3u, 3u, 1u, 1u};
+
+int enqueue_aov(vk_scene *q, const vk_camera *cam, const vk_render_params *p, uint32_t first_sample, float *const d[4], hipStream_t st,
+    bool timed) {
+    HIP_TRY(hipSetDevice(q->device));
+    const TileGeom g(p);
+    AovArgs A;
+    memset(&A, 0, sizeof(A));
+    A.S = aov_view(q);
+    if (A.S.grid.nu != 0u || A.S.t_pad != 0.0f || A.S.walk_start != 0u || A.S.gate_scale != 1.0f || A.S.primary_ref != 0u)
+        return fail(VK_ERR_BAD_ARG, "internal error: the first-hit walk needs a tree view without the rebuilt forms' gates");
+    A.C.cam = *cam;
+    A.C.width = p->width; A.C.height = p->height; A.C.spp = p->samples_per_pixel; A.C.max_depth = 0u;
+    A.C.seed = p->seed; A.C.integrator = p->integrator; A.C.background = p->background;
+    A.C.bg[0] = p->background_color[0]; A.C.bg[1] = p->background_color[1]; A.C.bg[2] = p->background_color[2];
+    A.albedo = d[0]; A.normal = d[1]; A.depth = d[2]; A.coverage = d[3];
+    A.first_sample = first_sample; A.tiles_x = g.tiles_x; A.tile_rank = g.rank; A.tile_world = g.world; A.n_local = g.n_local;
+    if (timed) {
+        if (!q->aov_ev0) HIP_TRY(hipEventCreate(&q->aov_ev0));
+        if (!q->aov_ev1) HIP_TRY(hipEventCreate(&q->aov_ev1));
+        HIP_TRY(hipEventRecord(q->aov_ev0, st));
+    }
+    if (g.n_local != 0u) {
+        const dim3 grid((g.n_local + AOV_BLOCK / 64 - 1) / (AOV_BLOCK / 64));
+        // a sphere-only world: the fused sphere path (C2); anything else: the everything-variant
+        if (q->host->features == 0u) hipLaunchKernelGGL(aov_kernel<0u>, grid, dim3(AOV_BLOCK), 0, st, A);
+        else hipLaunchKernelGGL(aov_kernel<(uint32_t)VKF_ALL_SCENE>, grid, dim3(AOV_BLOCK), 0, st, A);
+        HIP_TRY(hipGetLastError());
+    }
+    if (timed) HIP_TRY(hipEventRecord(q->aov_ev1, st));
+    return VK_OK;
+}
+
+void aov_stats(const vk_render_params *p, vk_stats *st) {
+    const TileGeom g(p);
+    memset(st, 0, sizeof(*st));
+    st->samples = partition_samples(p, g);
+    st->kernel_launches = g.n_local != 0u ? 1u : 0u;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_render_aov(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample, float *albedo, float *normal,
+    float *depth, float *coverage, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        float *host[4] = {albedo, normal, depth, coverage};
+        int rc = check_aov_args(scene, cam, params, first_sample, reinterpret_cast<const void *const *>(host));
+        if (rc != VK_OK) return rc;
+        const auto t0 = std::chrono::steady_clock::now();
+        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        HIP_TRY(hipSetDevice(q->device));
+        const size_t n_pixels = (size_t)params->width * params->height;
+        size_t floats = 0;
+        for (int k = 0; k < 4; k++) if (host[k]) floats += n_pixels * AOV_COMPONENTS[k];
+        rc = ensure(q->aov_buf, q->aov_bytes, floats * sizeof(float));
+        if (rc != VK_OK) return rc;
+        float *dev[4] = {nullptr, nullptr, nullptr, nullptr};
+        size_t at = 0;
+        for (int k = 0; k < 4; k++) if (host[k]) { dev[k] = q->aov_buf + at; at += n_pixels * AOV_COMPONENTS[k]; }
+        // a partition: the caller's pixels outside it must come back untouched
+        const bool partial = (params->tile_world ? params->tile_world : 1u) > 1u;
+        if (partial)
+            for (int k = 0; k < 4; k++)
+                if (host[k]) HIP_TRY(hipMemcpy(dev[k], host[k], n_pixels * AOV_COMPONENTS[k] * sizeof(float), hipMemcpyHostToDevice));
+        rc = enqueue_aov(q, cam, params, first_sample, dev, nullptr, true);
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipEventSynchronize(q->aov_ev1));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, q->aov_ev0, q->aov_ev1));
+        for (int k = 0; k < 4; k++)
+            if (host[k]) HIP_TRY(hipMemcpy(host[k], dev[k], n_pixels * AOV_COMPONENTS[k] * sizeof(float), hipMemcpyDeviceToHost));
+        if (stats_out) {
+            aov_stats(params, stats_out);
+            stats_out->kernel_ms = (double)ms;
+            stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return VK_OK;
+    });
+}
+
+int vk_render_aov_device(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample, void *d_albedo,
+    void *d_normal, void *d_depth, void *d_coverage, void *hip_stream, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        float *dev[4] = {static_cast<float *>(d_albedo), static_cast<float *>(d_normal), static_cast<float *>(d_depth),
+                         static_cast<float *>(d_coverage)};
+        int rc = check_aov_args(scene, cam, params, first_sample, reinterpret_cast<const void *const *>(dev));
+        if (rc != VK_OK) return rc;
+        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        rc = enqueue_aov(q, cam, params, first_sample, dev, reinterpret_cast<hipStream_t>(hip_stream), false);
+        if (rc != VK_OK) return rc;
+        if (stats_out) aov_stats(params, stats_out);
+        return VK_OK;
+    });
 }
 
 }  // extern "C"

@@ -1158,6 +1158,44 @@ __global__ void to_color_kernel(const float *rgb, uint32_t width, uint32_t heigh
     out[i] = to_color_u8(rgb[((size_t)y * width + x) * 3 + c]);
 }
 
+// ---- first-hit buffers (vk_render_aov): albedo, normal, depth and coverage of the primary rays of samples
+// [first_sample, first_sample + C.spp) of every pixel of this call's tile partition.  One 8x8 tile per wave (coherent primary rays,
+// each tile row's eight lanes store 96 contiguous bytes), the samples in increasing order inside the lane, f32 sums: the result does not
+// depend on the launch shape.  The walk is vk_trace.h's per-lane one (begin_segment / traverse_step / build_record) on GlobalMem.
+struct AovArgs {
+    DScene S;                // a tree view (vk_api.hip aov_view): grid.nu == 0, no rebuilt-form gates
+    RenderConsts C;          // C.spp = the window's length
+    float *albedo, *normal, *depth, *coverage;   // f32, y up, each may be null
+    uint32_t first_sample, tiles_x, tile_rank, tile_world, n_local;
+};
+constexpr int AOV_BLOCK = 256;       // 4 waves = 4 tiles per workgroup
+template <uint32_t F>
+__global__ __launch_bounds__(AOV_BLOCK) void aov_kernel(AovArgs A) {
+    const uint32_t lane = threadIdx.x & 63u, local = blockIdx.x * (AOV_BLOCK / 64) + (threadIdx.x >> 6);
+    if (local >= A.n_local) return;
+    const uint32_t tile = A.tile_rank + local * A.tile_world;
+    const uint32_t x = (tile % A.tiles_x) * TILE + (lane & 7u), y = (tile / A.tiles_x) * TILE + (lane >> 3);
+    if (x >= A.C.width || y >= A.C.height) return;
+    const GlobalMem M{A.S.items, A.S.spheres, A.S.sphere_mat, A.S.boxes};
+    V3 sa = v3s(0.0f), sn = v3s(0.0f);
+    float sd = 0.0f;
+    uint32_t hits = 0u;
+#pragma unroll 1
+    for (uint32_t k = 0; k < A.C.spp; k++) {
+        Lane L;
+        V3 a, n; float dp; bool h;
+        if (!aov_sample<F, GlobalMem>(L, A.S, M, A.C, x, y, A.first_sample + k, a, n, dp, h)) continue;    // dropped: counts in n only
+        sa = sa + a; sn = sn + n;
+        if (h) { sd += dp; hits++; }
+    }
+    const float fn = (float)A.C.spp;
+    const size_t pix = (size_t)y * A.C.width + x;
+    if (A.albedo) { A.albedo[pix * 3 + 0] = sa.x / fn; A.albedo[pix * 3 + 1] = sa.y / fn; A.albedo[pix * 3 + 2] = sa.z / fn; }
+    if (A.normal) { A.normal[pix * 3 + 0] = sn.x / fn; A.normal[pix * 3 + 1] = sn.y / fn; A.normal[pix * 3 + 2] = sn.z / fn; }
+    if (A.depth) A.depth[pix] = hits ? sd / (float)hits : INFINITY;
+    if (A.coverage) A.coverage[pix] = (float)hits / fn;
+}
+
 // ---- tile slabs: the pixels of one tile partition (tiles t = rank + i*world, i = 0..n_local) packed tile by tile,
 // 64 pixel slots per tile, 3 components per slot.  A multi-device scene moves one slab per device to devices[0]
 // (the path's only exchange) and de-interleaves it there; RGB8 output packs bytes (to_color fused: 4x less traffic).

@@ -1146,6 +1146,53 @@ VK_HD V3 material_color(const DScene &S, const DMaterial &m, const Rec &R, const
         pt.py, pt.pz);
 }
 
+// ------------------------------------------------------------------ first-hit albedo (vk_render_aov, include/vecchio_amd.h)
+// [0, 1] per component; a NaN stays NaN (the sample is then dropped by the caller)
+VK_HD V3 clamp01(V3 a) {
+    auto c = [](float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); };
+    return v3(c(a.x), c(a.y), c(a.z));
+}
+// The albedo of material `mi` at the hit R: the texture value of Lambertian / Metal / Isotropic, (1,1,1) for Dielectric, DiffuseLight's
+// emitted(rec) (front faces only, material.rs:218-225) clamped to [0, 1], SpecDiffuse pct * A(specular) + (1 - pct) * A(diffuse) in that
+// order.  A SpecDiffuse below 8 SpecDiffuse levels (the guard of shade_core's loop) has albedo 0.  The mix tree is walked in post-order
+// with an explicit stack of 8 levels (no recursion: no dynamic stack, and the texture code is inlined once).
+template <uint32_t F>
+VK_HD V3 aov_leaf_albedo(const DScene &S, const DMaterial &m, const Rec &R) {
+    if (m.kind == VK_MAT_DIELECTRIC) return v3s(1.0f);
+    if (m.kind == VK_MAT_DIFFUSE_LIGHT) return R.front ? clamp01(material_color<F>(S, m, R, no_pre_turb())) : v3s(0.0f);
+    if (m.kind == VK_MAT_SPEC_DIFFUSE) return v3s(0.0f);           // (past the guard)
+    return material_color<F>(S, m, R, no_pre_turb());
+}
+template <uint32_t F>
+VK_HD V3 aov_albedo(const DScene &S, uint32_t mi, const Rec &R) {
+    if constexpr ((F & VKF_SPEC_DIFFUSE) == 0u) {
+        return aov_leaf_albedo<F>(S, S.materials[mi], R);
+    } else {
+        uint32_t node[8]; V3 spec[8];
+        uint32_t second = 0u;      // bit k: level k is on its diffuse child, its specular albedo is in spec[k]
+        int depth = 0;
+        uint32_t cur = mi;
+        for (;;) {
+            const DMaterial &m = S.materials[cur];
+            if (m.kind == VK_MAT_SPEC_DIFFUSE && depth < 8) {
+                node[depth] = cur; second &= ~(1u << depth); depth++;
+                cur = m.ab & 0xFFFFu;
+                continue;
+            }
+            V3 val = aov_leaf_albedo<F>(S, m, R);
+            for (;;) {
+                if (depth == 0) return val;
+                const int k = depth - 1;
+                const DMaterial &q = S.materials[node[k]];
+                if (!(second & (1u << k))) { spec[k] = val; second |= 1u << k; cur = q.ab >> 16; break; }
+                const float pct = q.param, rest = 1.0f - pct;
+                val = v3(pct * spec[k].x + rest * val.x, pct * spec[k].y + rest * val.y, pct * spec[k].z + rest * val.z);
+                depth = k;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ samplers (util.rs:31-63, material.rs:51-58)
 VK_HD V3 random_in_unit_sphere(Rng &g) {
     for (;;) {
@@ -1485,6 +1532,34 @@ VK_HD bool shade(Lane &L, const DScene &S, const Mem &M, const RenderConsts &C) 
     if (!shade_core<F, Mem>(L, S, M, C, o, d, time)) return false;
     begin_segment<Mem::ISHIFT, fused_box<F, Mem>(), spheres_only<F>()>(L, S, o, d, time);
     return true;
+}
+
+// ------------------------------------------------------------------ first-hit buffers (vk_render_aov, include/vecchio_amd.h)
+VK_HD bool finite_f(float x) { return (vk::f32_bits(x) & 0x7F800000u) != 0x7F800000u; }
+VK_HD bool finite3(V3 a) { return finite_f(a.x) && finite_f(a.y) && finite_f(a.z); }
+
+// Sample `sample` of pixel (x, y): the primary ray of radiance sample `sample` (start_sample_core, its stream continues into a
+// ConstantMedium's draw), walked to its first hit on S (which must be a tree view: no grid, no rebuilt-form gates), and what the
+// first-hit buffers take of it.  Returns false when the sample is dropped (a non-finite component).
+template <uint32_t F, class Mem>
+VK_HD bool aov_sample(Lane &L, const DScene &S, const Mem &M, const RenderConsts &C, uint32_t x, uint32_t y, uint32_t sample, V3 &albedo,
+    V3 &normal, float &depth, bool &hit) {
+    V3 o, d; float time;
+    start_sample_core(L, C, x, y, sample, o, d, time);
+    begin_segment<Mem::ISHIFT, fused_box<F, Mem>(), spheres_only<F>()>(L, S, o, d, time);
+    while (traversing(L)) traverse_step<F, Mem>(L, S, M);
+    hit = L.best_prim != 0u;
+    normal = v3s(0.0f); depth = 0.0f;
+    if (!hit) {                                               // the background the radiance sees (main.rs:150-152)
+        albedo = clamp01(background_of(C, C.background == VK_BACKGROUND_SKY ? unit(L.wd) : L.wd));
+        return finite3(albedo);
+    }
+    Rec R;
+    build_record<F, Mem>(L, S, M, R);
+    albedo = aov_albedo<F>(S, R.mat, R);
+    if (!((F & VKF_MEDIUM) && VKD_KIND(L.best_prim) == DK_MEDIUM)) normal = R.n;   // (a medium's (1,0,0) is arbitrary: 0)
+    depth = L.T * sqrtf(length2(L.wd));
+    return finite3(albedo) && finite3(normal) && finite_f(depth);
 }
 
 }  // namespace vkd

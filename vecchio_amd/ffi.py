@@ -226,6 +226,7 @@ DEVICE_SYMBOLS = [
     "vk_tile_slab_bytes", "vk_pack_tiles_device", "vk_unpack_tiles_device",
     "vk_progress_create", "vk_progress_step", "vk_progress_step_device", "vk_progress_reset", "vk_progress_stderr",
     "vk_progress_get_info", "vk_progress_destroy", "vk_progress_set_adaptive", "vk_progress_tile_samples",
+    "vk_render_aov", "vk_render_aov_device",
 ]
 
 
@@ -284,6 +285,12 @@ def _bind(lib):
     lib.vk_progress_set_adaptive.argtypes = [C.c_void_p, C.POINTER(AdaptiveParams)]
     lib.vk_progress_tile_samples.restype = C.c_int
     lib.vk_progress_tile_samples.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AdaptiveInfo)]
+    lib.vk_render_aov.restype = C.c_int
+    lib.vk_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_render_aov_device.restype = C.c_int
+    lib.vk_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     # the test hooks of include/vecchio_amd_debug.h that the product library carries too
     lib.vk_debug_last_launches.restype = C.c_int
     lib.vk_debug_last_launches.argtypes = [C.c_void_p, C.POINTER(DebugLaunch), C.c_uint32, C.POINTER(C.c_uint32)]

@@ -2,10 +2,13 @@
 // scene, build the BVH, upload once, then per Camera of cam_iter: render through the C ABI
 // (the call that replaces main.rs:181-198), write output_%04d.ppm, print the frame time.
 // The reference hard-codes scene/width/spp/depth (main.rs:28-29,159-167,171); here they are
-// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1]
+// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0]
 // steps > 1: each frame is rendered progressively (vk_progress_*) in `steps` equal sample windows; after each window the running image
 // is written to output_%04d_step%02d.ppm and the samples done and the image's mean relative standard error are printed.  The final
 // output_%04d.ppm is byte-identical to the one of steps = 1.
+// aov_spp > 0: each frame also writes its f32 image as output_%04d.pfm and the first-hit buffers of samples 0 .. aov_spp-1
+// (vk_render_aov) as output_%04d_albedo.pfm, _normal.pfm (PF, 3 channels), _depth.pfm and _coverage.pfm (Pf, 1 channel): little-endian
+// (scale -1), rows bottom to top as PFM stores them — the library's y-up buffers as they are.  What a denoiser takes; the .ppm is unchanged.
 // Texture images are read from ./assets (as in the reference) or $VECCHIO_ASSETS: <name>.ppm.gz, see host_api.h.
 #include <dlfcn.h>
 
@@ -18,6 +21,16 @@
 
 #include "host_api.h"
 
+// PFM: "PF" (3 channels) or "Pf" (1), width height, scale -1 = little-endian floats, rows bottom to top
+static bool write_pfm(const char *fn, const float *data, uint32_t width, uint32_t height, int channels) {
+    FILE *f = fopen(fn, "wb");
+    if (!f) { fprintf(stderr, "cannot write %s\n", fn); return false; }
+    fprintf(f, "%s\n%u %u\n-1\n", channels == 3 ? "PF" : "Pf", width, height);
+    const size_t n = (size_t)width * height * channels;
+    const bool ok = fwrite(data, sizeof(float), n, f) == n;      // (gfx950 hosts are little-endian)
+    return fclose(f) == 0 && ok;
+}
+
 template <class T>
 static T sym(void *h, const char *name) {
     void *p = dlsym(h, name);
@@ -28,7 +41,7 @@ static T sym(void *h, const char *name) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <balls_demo|random_spheres_demo|random_spheres_iow|perlin_demo|bowser_demo|cornell_box|final_scene|"
-                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps]\n", argv[0]);
+                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp]\n", argv[0]);
         return 2;
     }
     const char *name = argv[1];
@@ -38,6 +51,7 @@ int main(int argc, char **argv) {
     int frames = argc > 5 ? atoi(argv[5]) : 1;
     uint64_t seed = argc > 6 ? strtoull(argv[6], nullptr, 10) : 1;
     uint32_t steps = argc > 7 ? (uint32_t)atoi(argv[7]) : 1;
+    uint32_t aov_spp = argc > 8 ? (uint32_t)atoi(argv[8]) : 0;
     if (steps < 1) steps = 1;
     if (steps > spp) steps = spp;                                     // every window holds at least one sample
 
@@ -54,6 +68,8 @@ int main(int argc, char **argv) {
     auto p_pstep = sym<int (*)(vk_progress *, uint32_t, void *, vk_stats *)>(h, "vk_progress_step");
     auto p_pstderr = sym<int (*)(vk_progress *, float *)>(h, "vk_progress_stderr");
     auto p_pdestroy = sym<void (*)(vk_progress *)>(h, "vk_progress_destroy");
+    auto p_aov = sym<int (*)(vk_scene *, const vk_camera *, const vk_render_params *, uint32_t, float *, float *, float *, float *, vk_stats *)>(
+        h, "vk_render_aov");
 
     fprintf(stderr, "Generating scene...\n");                        // main.rs:157
     vkh_scene *hs = vkh_scene_build(name, seed);
@@ -106,6 +122,24 @@ int main(int argc, char **argv) {
         char fn[64];
         snprintf(fn, sizeof fn, "output_%04d.ppm", file_idx);         // main.rs:201
         if (vkh_write_ppm(fn, pixels.data(), width, height)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }
+        if (aov_spp > 0) {
+            const size_t np = (size_t)width * height;
+            std::vector<float> albedo(np * 3), normal(np * 3), zdepth(np), coverage(np);
+            vk_render_params ap = rp;
+            ap.samples_per_pixel = aov_spp;
+            vk_stats as{};
+            if (p_aov(scene, &cam, &ap, 0, albedo.data(), normal.data(), zdepth.data(), coverage.data(), &as) != VK_OK) {
+                fprintf(stderr, "vk_render_aov: %s\n", p_err()); return 1; }
+            const struct { const char *suffix; const float *data; int ch; } outs[] = {
+                {"", pixels.data(), 3}, {"_albedo", albedo.data(), 3}, {"_normal", normal.data(), 3}, {"_depth", zdepth.data(), 1},
+                {"_coverage", coverage.data(), 1}};
+            for (const auto &o : outs) {
+                char pfn[64];
+                snprintf(pfn, sizeof pfn, "output_%04d%s.pfm", file_idx, o.suffix);
+                if (!write_pfm(pfn, o.data, width, height, o.ch)) return 1;
+            }
+            fprintf(stderr, "  first-hit buffers of %u samples per pixel: kernel %.2f ms\n", aov_spp, as.kernel_ms);
+        }
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
         fprintf(stderr, "Wrote frame %s in %.3fs (kernel %.1f ms, %.1f Msamples/s)\n", fn, secs, st.kernel_ms,
                 st.kernel_ms > 0 ? (double)st.samples / st.kernel_ms / 1e3 : 0.0);   // main.rs:215

@@ -115,6 +115,12 @@ extern "C" {
     pub fn vk_progress_destroy(pr: *mut vk_progress);
     pub fn vk_progress_set_adaptive(pr: *mut vk_progress, ap: *const vk_adaptive_params) -> c_int;
     pub fn vk_progress_tile_samples(pr: *mut vk_progress, out: *mut u32, info: *mut vk_adaptive_info) -> c_int;
+    // first-hit buffers (additive symbols of ABI 7): any of the four may be null, not all four
+    pub fn vk_render_aov(scene: *mut vk_scene, cam: *const vk_camera, params: *const vk_render_params, first_sample: u32,
+                         albedo: *mut f32, normal: *mut f32, depth: *mut f32, coverage: *mut f32, stats_out: *mut vk_stats) -> c_int;
+    pub fn vk_render_aov_device(scene: *mut vk_scene, cam: *const vk_camera, params: *const vk_render_params, first_sample: u32,
+                                d_albedo: *mut c_void, d_normal: *mut c_void, d_depth: *mut c_void, d_coverage: *mut c_void,
+                                hip_stream: *mut c_void, stats_out: *mut vk_stats) -> c_int;
 }
 
 /// What `flatten()` pushes into (flatten.rs).  One record per Arc; shared Arcs are de-duplicated

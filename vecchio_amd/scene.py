@@ -100,6 +100,35 @@ class DeviceScene:
         check(self._lib, self._lib.vk_render(self._h, C.byref(cam), C.byref(params), out.ctypes.data_as(C.c_void_p), C.byref(stats)))
         return out, stats
 
+    AOV_CHANNELS = ("albedo", "normal", "depth", "coverage")
+
+    def render_aov(self, cam, params, first_sample=0, want=AOV_CHANNELS, out=None):
+        """First-hit buffers of samples [first_sample, first_sample + params.samples_per_pixel) (vk_render_aov): a dict with the wanted
+        channels as float32 arrays, y = 0 the bottom row — albedo and normal (height, width, 3), depth and coverage (height, width) —
+        and the stats.  out: a dict of arrays to write into (pixels outside this call's tile partition keep their values)."""
+        want = tuple(want)
+        unknown = set(want) - set(self.AOV_CHANNELS)
+        if unknown:
+            raise ValueError(f"unknown AOV channel(s) {sorted(unknown)}; choose from {self.AOV_CHANNELS}")
+        bufs = dict(out or {})
+        for ch in want:
+            if ch not in bufs:
+                shape = (params.height, params.width, 3) if ch in ("albedo", "normal") else (params.height, params.width)
+                bufs[ch] = np.zeros(shape, dtype=np.float32)
+            assert bufs[ch].dtype == np.float32 and bufs[ch].flags.c_contiguous
+        ptrs = [C.c_void_p(bufs[ch].ctypes.data) if ch in want else None for ch in self.AOV_CHANNELS]
+        stats = ffi.Stats()
+        check(self._lib, self._lib.vk_render_aov(self._h, C.byref(cam), C.byref(params), first_sample, *ptrs, C.byref(stats)))
+        return {ch: bufs[ch] for ch in want}, stats
+
+    def render_aov_device(self, cam, params, first_sample, d_albedo=0, d_normal=0, d_depth=0, d_coverage=0, stream=None):
+        """Enqueue the first-hit buffers into device memory (vk_render_aov_device, no host sync); a 0 pointer = not wanted."""
+        stats = ffi.Stats()
+        check(self._lib, self._lib.vk_render_aov_device(self._h, C.byref(cam), C.byref(params), first_sample, C.c_void_p(d_albedo or None),
+                                                        C.c_void_p(d_normal or None), C.c_void_p(d_depth or None),
+                                                        C.c_void_p(d_coverage or None), C.c_void_p(stream or 0), C.byref(stats)))
+        return stats
+
     def render_device(self, cam, params, d_ptr, stream=None):
         """Enqueue a render into device memory at d_ptr on `stream` (no host sync)."""
         stats = ffi.Stats()
