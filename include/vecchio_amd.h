@@ -517,6 +517,65 @@ int vk_render_aov(vk_scene *scene, const vk_camera *cam, const vk_render_params 
 int vk_render_aov_device(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
                          void *d_albedo, void *d_normal, void *d_depth, void *d_coverage, void *hip_stream, vk_stats *stats_out);
 
+/* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
+ * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
+ * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):
+ * color, stderr3, albedo, normal and out 3 floats per pixel, depth 1.  color and out are required; each of stderr3, albedo, normal and
+ * depth may be NULL, which switches its term off.  out must not overlap an input.  The filter needs a pixel's neighbours: it works on
+ * the whole image (no tile partition), on devices[0] of a multi-device scene.
+ *
+ * The filter, exactly.  Everything is f32, unfused, in the order written, with + - * /, sqrtf, fabsf, fmaxf (which returns its other
+ * argument when one is a NaN) and compares only; tests/denoise_ref.py restates it in numpy and the two agree bit for bit (a NaN's
+ * payload aside).  E(x) = t^8 with t = fmaxf(0, 1 - x * 0.125f), by three squarings: a compact-support stand-in for exp(-x).
+ *   Prepare, per pixel p.  a_c = fmaxf(albedo_c, albedo_floor), or 1 without albedo; I_c = color_c / a_c.  With stderr3: s_c = stderr_c /
+ *     a_c, sd = (0.2126f*s_r + 0.7152f*s_g) + 0.0722f*s_b, V = sd * sd (the components taken as fully correlated: an upper bound, on
+ *     purpose); without: V = 0.  p is INVALID if a component of color (or of stderr3, when given) is not finite: it is never a
+ *     neighbour and its out is its color, unchanged.  Normal: l2 = (n_x*n_x + n_y*n_y) + n_z*n_z; l2 < 1e-12f or not finite (a miss, a
+ *     medium hit): p has NO NORMAL; else n^ = n / sqrtf(l2).  Depth: z = depth if finite, else +inf.  Depth slope: g_x = (z(x+1) -
+ *     z(x-1)) * 0.5f where both neighbours are in the image and finite, else the one-sided difference z(x+1) - z or z - z(x-1) that
+ *     is, else 0; g_y likewise; both 0 when z is +inf.
+ *   Pass i = 0 .. levels-1, s = 2^i, per valid pixel p.  Y = (0.2126f*I_r + 0.7152f*I_g) + 0.0722f*I_b of the current image.
+ *     Vg_p = (sum of k3 * V_q) / (sum of k3) over the 3x3 adjacent pixels q that are in the image and valid, rows bottom to top, x
+ *     ascending, k3 = (1 2 1; 2 4 2; 1 2 1), both sums from 0.
+ *     Taps q = p + s*(dx, dy), dy = -2..2 outer, dx = -2..2 inner, ascending; taps outside the image or invalid are skipped.
+ *     h = k[|dx|] * k[|dy|], k = (3/8, 1/4, 1/16).  The centre tap has w = h.  For the others:
+ *       w_n: normal off: 1.  Both without normal: 1; one without: 0; else fmaxf(0, (n^p_x*n^q_x + n^p_y*n^q_y) + n^p_z*n^q_z), squared
+ *         normal_squarings times.
+ *       x_z: depth off: 0.  Both depths +inf: 0; one: the tap is skipped; else fabsf(z_p - z_q) / (sigma_z * (fabsf(g_x*(float)(s*dx) +
+ *         g_y*(float)(s*dy)) + 0.001f*z_p)).
+ *       x_l: stderr3 off: 0; else fabsf(Y_p - Y_q) / (sigma_l * sqrtf(Vg_p) + 1e-6f).
+ *       w = ((h * w_n) * E(x_z)) * E(x_l).
+ *     In tap order from 0: W += w, J_c += w * I_q,c, U += (w*w) * V_q.  Then I'_p,c = J_c / W, V'_p = U / (W*W)  (W >= 9/64).
+ *   Finish.  out_c = I_c * a_c.
+ * Scratch (two ping-pong images and the packed guides, 56 bytes per pixel) belongs to the scene handle, is allocated on first use and
+ * regrown when a larger image comes.  "At most one render in flight per vk_scene" covers these calls; they touch nothing that describes
+ * vk_render's last frame and no vk_progress handle.
+ * VK_ERR_BAD_ARG, nothing enqueued, out untouched: null scene / dp / color / out, zero or too large a size (vk_render's limits),
+ * levels outside 1..8, normal_squarings > 10, a sigma_l, sigma_z or albedo_floor that is not finite or not > 0, flags != 0, out
+ * overlapping an input.                                                                                                           */
+typedef struct vk_denoise_params {
+    uint32_t width, height;
+    uint32_t levels;            /* 1..8 passes; pass i has tap spacing s = 2^i            */
+    uint32_t normal_squarings;  /* 0..10: w_n = max(0, cos)^(2^normal_squarings)          */
+    float sigma_l;              /* colour tolerance, in standard errors of the luminance  */
+    float sigma_z;              /* depth tolerance, in units of the local depth slope     */
+    float albedo_floor;         /* > 0: demodulation divides by max(albedo, albedo_floor) */
+    uint32_t flags;             /* 0                                                       */
+} vk_denoise_params;
+/* levels 5, normal_squarings 7, sigma_l 4, sigma_z 1, albedo_floor 1e-3 (what was tried).  Touches no device. */
+int vk_denoise_default_params(uint32_t width, uint32_t height, vk_denoise_params *out);
+/* host buffers; blocking.  stats_out: samples = pixels, kernel_ms (HIP events around the passes), kernel_launches = 1 + levels */
+int vk_denoise(vk_scene *scene, const vk_denoise_params *dp, const float *color, const float *stderr3,
+               const float *albedo, const float *normal, const float *depth, float *out, vk_stats *stats_out);
+/* device buffers on the scene's device (devices[0] of a multi-device scene), enqueued on hip_stream, no host wait */
+int vk_denoise_device(vk_scene *scene, const vk_denoise_params *dp, const void *d_color, const void *d_stderr3,
+                      const void *d_albedo, const void *d_normal, const void *d_depth, void *d_out, void *hip_stream);
+/* vk_progress_stderr into device memory on the scene's device: the same formula in double with the same operation order, bit-identical
+ * to the host call; the same argument checks; this partition's pixels only, others untouched.  Waits for the handle's last step, then
+ * enqueues on hip_stream without a further host wait.  A handle on a multi-device scene returns VK_ERR_UNSUPPORTED (its moments live on
+ * several devices): vk_progress_stderr stays the way there. */
+int vk_progress_stderr_device(vk_progress *pr, void *d_out, void *hip_stream);
+
 /* test/diagnostic entry points (vk_debug_*) are declared in vecchio_amd_debug.h */
 
 #ifdef __cplusplus

@@ -48,6 +48,13 @@ int vk_debug_last_launches(vk_scene *scene, vk_debug_launch *out, uint32_t cap, 
 /* a progressive handle's raw running fixed-point sums and error moments (width*height*3 each, y up, summed over the device parts):
  * what the adaptive judge reads.  Either may be NULL; m2 needs VK_PROGRESS_STDERR.  Waits for the last step. */
 int vk_debug_progress_moments(vk_progress *pr, long long *run, double *m2);
+/* Which form of the level kernel vk_denoise / vk_denoise_device launch on this scene from now on (vk_kernels.h): VK_DENOISE_FORM_AUTO
+ * (the default) = per level the form that was measured faster; _PLAIN = one thread per pixel, every tap a global load, at every level;
+ * _STAGED = the LDS-staged form at every level it exists for (tap spacing <= 32), plain beyond.  The results are bit-identical. */
+enum { VK_DENOISE_FORM_AUTO = 0, VK_DENOISE_FORM_PLAIN = 1, VK_DENOISE_FORM_STAGED = 2 };
+int vk_debug_denoise_form(vk_scene *scene, int form);
+/* HIP-event times (ms) of the last vk_denoise on this scene: ms_out[0] the prepare kernel, ms_out[1 + i] level i (0 beyond `levels`) */
+int vk_debug_denoise_last_ms(vk_scene *scene, double ms_out[9]);
 /* render with the instrumented build of the sphere-only kernel and return the wave scheduler's
  * counters: [0] box steps (wave level) [1] lanes with box work summed over them [2] PRIM phases
  * [3] lanes with primitive work in them [4] SHADE+REFILL phases [5] lanes in them [6] rounds

@@ -258,6 +258,14 @@ struct vk_scene {
     // vk_render_aov: its own events and output buffers, so that nothing that describes vk_render's last frame is touched
     hipEvent_t aov_ev0 = nullptr, aov_ev1 = nullptr;
     float *aov_buf = nullptr; size_t aov_bytes = 0;
+    // vk_denoise: the filter's scratch (two ping-pong images, the packed guides, the depth slopes), the device copies of vk_denoise's
+    // host images, its own events (before the prepare kernel, behind it, behind every level), the levels of the last timed call and the
+    // form the level kernels are launched in (vk_debug_denoise_form)
+    uint8_t *dn_buf = nullptr; size_t dn_bytes = 0;
+    float *dn_io = nullptr; size_t dn_io_bytes = 0;
+    hipEvent_t dn_ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint32_t dn_last_levels = 0;
+    int dn_form = 0;
 };
 
 namespace {
@@ -1037,8 +1045,9 @@ void destroy_one(vk_scene *s) {
     for (void *p : {(void *)s->counter, (void *)s->fb, (void *)s->fb8, (void *)s->accum, (void *)s->debug, (void *)s->phase_stats,
         (void *)s->tile_cost,
                     (void *)s->tile_order, (void *)s->order_hist, (void *)s->slab, (void *)s->redo_list, (void *)s->redo_count,
-                    (void *)s->aov_buf})
+                    (void *)s->aov_buf, (void *)s->dn_buf, (void *)s->dn_io})
         if (p) (void)hipFree(p);
+    for (hipEvent_t e : s->dn_ev) if (e) (void)hipEventDestroy(e);
     if (s->plan_host) (void)hipHostFree(s->plan_host);
     if (s->landing) { (void)hipSetDevice(s->landing_device); (void)hipFree(s->landing); (void)hipSetDevice(s->device); }
     for (hipEvent_t e : {s->ev0, s->ev1, s->ev_landed, s->ev_begin, s->ev_fork, s->ev_join, s->ev_plan[0], s->ev_plan[1], s->aov_ev0,
@@ -1717,6 +1726,171 @@ int vk_render_aov_device(vk_scene *scene, const vk_camera *cam, const vk_render_
 
 }  // extern "C"
 
+// ---- the denoiser (vk_denoise): denoise_prepare_kernel, then one level kernel per pass (vk_kernels.h), on the scene's device (devices[0]
+// of a multi-device scene), on scratch and events of its own: nothing that describes vk_render's last frame is read or written.
+namespace {
+
+// Per level the form that was measured faster on the MI355X (tools/denoise_report.py): the staged form up to tap
+// spacing 8 (1920x1080: 0.111-0.121 ms against 0.135-0.139 ms a level), the plain form from 16 on (0.132 against 0.149 ms at 16, 0.129
+// against 0.200 ms at 32: the halo outgrows the tile).  The staged form exists up to DN_STAGED_MAX_S (48 KB of LDS per workgroup there).
+constexpr int DN_STAGED_MAX_S = 32;
+constexpr int DN_STAGED_AUTO_MAX_S = 8;
+// images of vk_denoise: color, stderr3, albedo, normal, depth, out
+constexpr uint32_t DN_COMPONENTS[6] = {3u, 3u, 3u, 3u, 1u, 3u};
+
+int check_denoise_args(vk_scene *scene, const vk_denoise_params *dp, const void *const img[6]) {
+    if (!scene || !dp || !img[0] || !img[5]) return fail(VK_ERR_BAD_ARG, "null argument");
+    if (dp->width == 0 || dp->height == 0) return fail(VK_ERR_BAD_ARG, "width and height must be >= 1");
+    if ((uint64_t)dp->width * dp->height > (1ull << 31) / 3 || dp->width > 65535u || dp->height > 65535u) return fail(VK_ERR_BAD_ARG,
+        "image too large");
+    if (dp->levels < 1u || dp->levels > 8u) return fail(VK_ERR_BAD_ARG, "levels must be in 1..8");
+    if (dp->normal_squarings > 10u) return fail(VK_ERR_BAD_ARG, "normal_squarings must be in 0..10");
+    for (float v : {dp->sigma_l, dp->sigma_z, dp->albedo_floor})
+        if (!std::isfinite(v) || !(v > 0.0f)) return fail(VK_ERR_BAD_ARG, "sigma_l, sigma_z and albedo_floor must be finite and > 0");
+    if (dp->flags != 0u) return fail(VK_ERR_BAD_ARG, "unknown denoise flags");
+    const size_t n = (size_t)dp->width * dp->height;
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(img[5]), o1 = o0 + n * 3 * sizeof(float);
+    for (int k = 0; k < 5; k++) {
+        if (!img[k]) continue;
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(img[k]), i1 = i0 + n * DN_COMPONENTS[k] * sizeof(float);
+        if (i0 < o1 && o0 < i1) return fail(VK_ERR_BAD_ARG, "out overlaps an input");
+    }
+    return VK_OK;
+}
+
+int enqueue_denoise(vk_scene *q, const vk_denoise_params *dp, const float *const d[6], hipStream_t st, bool timed) {
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t n = (size_t)dp->width * dp->height;
+    int rc = ensure(q->dn_buf, q->dn_bytes, n * (3 * sizeof(float4) + sizeof(float2)));
+    if (rc != VK_OK) return rc;
+    float4 *P[2] = {reinterpret_cast<float4 *>(q->dn_buf), reinterpret_cast<float4 *>(q->dn_buf) + n};
+    DnArgs A;
+    memset(&A, 0, sizeof(A));
+    A.G = reinterpret_cast<float4 *>(q->dn_buf) + 2 * n;
+    A.S = reinterpret_cast<float2 *>(reinterpret_cast<float4 *>(q->dn_buf) + 3 * n);
+    A.color = d[0]; A.stderr3 = d[1]; A.albedo = d[2]; A.normal = d[3]; A.depth = d[4]; A.out = const_cast<float *>(d[5]);
+    A.width = dp->width; A.height = dp->height; A.normal_squarings = dp->normal_squarings;
+    A.sigma_l = dp->sigma_l; A.sigma_z = dp->sigma_z; A.albedo_floor = dp->albedo_floor;
+    const uint32_t guides = (d[1] ? DN_HAS_STDERR : 0u) | (d[2] ? DN_HAS_ALBEDO : 0u) | (d[3] ? DN_HAS_NORMAL : 0u) | (d[4] ? DN_HAS_DEPTH : 0u);
+    if (timed) {
+        for (uint32_t k = 0; k < dp->levels + 2u; k++) if (!q->dn_ev[k]) HIP_TRY(hipEventCreate(&q->dn_ev[k]));
+        HIP_TRY(hipEventRecord(q->dn_ev[0], st));
+    }
+    const dim3 grid((dp->width + DN_SX - 1) / DN_SX, (dp->height + DN_R - 1) / DN_R);
+    A.flags = guides; A.Pout = P[0]; A.s = 1;
+    hipLaunchKernelGGL(denoise_prepare_kernel, grid, dim3(DN_BLOCK), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    if (timed) HIP_TRY(hipEventRecord(q->dn_ev[1], st));
+    for (uint32_t i = 0; i < dp->levels; i++) {
+        A.s = 1 << i;
+        A.Pin = P[i & 1u]; A.Pout = P[(i & 1u) ^ 1u];
+        A.flags = guides | (i + 1u == dp->levels ? DN_LAST : 0u);
+        const bool staged = q->dn_form == VK_DENOISE_FORM_PLAIN ? false
+            : A.s <= (q->dn_form == VK_DENOISE_FORM_STAGED ? DN_STAGED_MAX_S : DN_STAGED_AUTO_MAX_S);
+        if (staged) {
+            // one workgroup per DN_SX columns and DN_R rows of one residue class of y mod s
+            const uint32_t per_class = ((dp->height + (uint32_t)A.s - 1u) / (uint32_t)A.s + DN_R - 1) / DN_R;
+            hipLaunchKernelGGL(denoise_level_staged_kernel, dim3(grid.x, (uint32_t)A.s * per_class), dim3(DN_BLOCK), dn_staged_lds_bytes(A.s),
+                               st, A);
+        } else {
+            hipLaunchKernelGGL(denoise_level_plain_kernel, grid, dim3(DN_BLOCK), 0, st, A);
+        }
+        HIP_TRY(hipGetLastError());
+        if (timed) HIP_TRY(hipEventRecord(q->dn_ev[2 + i], st));
+    }
+    if (timed) q->dn_last_levels = dp->levels;
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_denoise_default_params(uint32_t width, uint32_t height, vk_denoise_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    memset(out, 0, sizeof(*out));
+    out->width = width; out->height = height;
+    out->levels = 5u; out->normal_squarings = 7u;
+    out->sigma_l = 4.0f; out->sigma_z = 1.0f; out->albedo_floor = 1e-3f;
+    return VK_OK;
+}
+
+int vk_denoise(vk_scene *scene, const vk_denoise_params *dp, const float *color, const float *stderr3, const float *albedo,
+    const float *normal, const float *depth, float *out, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        const float *host[6] = {color, stderr3, albedo, normal, depth, out};
+        int rc = check_denoise_args(scene, dp, reinterpret_cast<const void *const *>(host));
+        if (rc != VK_OK) return rc;
+        const auto t0 = std::chrono::steady_clock::now();
+        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        HIP_TRY(hipSetDevice(q->device));
+        const size_t n = (size_t)dp->width * dp->height;
+        size_t floats = 0;
+        for (int k = 0; k < 6; k++) if (host[k]) floats += n * DN_COMPONENTS[k];
+        rc = ensure(q->dn_io, q->dn_io_bytes, floats * sizeof(float));
+        if (rc != VK_OK) return rc;
+        const float *dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        size_t at = 0;
+        for (int k = 0; k < 6; k++) {
+            if (!host[k]) continue;
+            dev[k] = q->dn_io + at;
+            if (k < 5) HIP_TRY(hipMemcpy(q->dn_io + at, host[k], n * DN_COMPONENTS[k] * sizeof(float), hipMemcpyHostToDevice));
+            at += n * DN_COMPONENTS[k];
+        }
+        rc = enqueue_denoise(q, dp, dev, nullptr, true);
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipEventSynchronize(q->dn_ev[1 + dp->levels]));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, q->dn_ev[0], q->dn_ev[1 + dp->levels]));
+        HIP_TRY(hipMemcpy(out, dev[5], n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        if (stats_out) {
+            memset(stats_out, 0, sizeof(*stats_out));
+            stats_out->samples = n;
+            stats_out->kernel_ms = (double)ms;
+            stats_out->kernel_launches = 1u + dp->levels;
+            stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return VK_OK;
+    });
+}
+
+int vk_denoise_device(vk_scene *scene, const vk_denoise_params *dp, const void *d_color, const void *d_stderr3, const void *d_albedo,
+    const void *d_normal, const void *d_depth, void *d_out, void *hip_stream) {
+    return guarded([&]() -> int {
+        const float *dev[6] = {static_cast<const float *>(d_color), static_cast<const float *>(d_stderr3), static_cast<const float *>(d_albedo),
+                               static_cast<const float *>(d_normal), static_cast<const float *>(d_depth), static_cast<const float *>(d_out)};
+        int rc = check_denoise_args(scene, dp, reinterpret_cast<const void *const *>(dev));
+        if (rc != VK_OK) return rc;
+        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        return enqueue_denoise(q, dp, dev, reinterpret_cast<hipStream_t>(hip_stream), false);
+    });
+}
+
+int vk_debug_denoise_form(vk_scene *scene, int form) {
+    if (!scene) return fail(VK_ERR_BAD_ARG, "null scene");
+    if (form < VK_DENOISE_FORM_AUTO || form > VK_DENOISE_FORM_STAGED) return fail(VK_ERR_BAD_ARG, "unknown denoise form");
+    (scene->parts.empty() ? scene : scene->parts[0])->dn_form = form;
+    return VK_OK;
+}
+
+int vk_debug_denoise_last_ms(vk_scene *scene, double ms_out[9]) {
+    if (!scene || !ms_out) return fail(VK_ERR_BAD_ARG, "null argument");
+    vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+    if (q->dn_last_levels == 0u) return fail(VK_ERR_BAD_ARG, "no vk_denoise on this scene yet");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(q->device));
+        HIP_TRY(hipEventSynchronize(q->dn_ev[1 + q->dn_last_levels]));
+        for (uint32_t k = 0; k < 9u; k++) {
+            float ms = 0.0f;
+            if (k <= q->dn_last_levels) HIP_TRY(hipEventElapsedTime(&ms, q->dn_ev[k], q->dn_ev[k + 1]));
+            ms_out[k] = (double)ms;
+        }
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
 // ---- progressive rendering (ABI 7): one camera + one vk_render_params, running sums on every device part of the scene.  A step is an
 // ordinary render of the sample window [done, done + n) (KArgs::sample_base) whose resolve is replaced by accumulate_resolve_kernel.
 struct vk_progress {
@@ -2067,6 +2241,28 @@ int vk_progress_stderr(vk_progress *pr, float *out) {
                     out[i] = (float)sqrt(v > 0.0 ? v : 0.0);
                 }
             }
+        return VK_OK;
+    });
+}
+
+// the same on the device (progress_stderr_kernel), for a handle whose moments live on one device
+int vk_progress_stderr_device(vk_progress *pr, void *d_out, void *hip_stream) {
+    if (!pr || !d_out) return fail(VK_ERR_BAD_ARG, "null argument");
+    if (!(pr->flags & VK_PROGRESS_STDERR)) return fail(VK_ERR_BAD_ARG, "the handle was created without VK_PROGRESS_STDERR");
+    if (pr->steps < 2) return fail(VK_ERR_BAD_ARG, "the standard error needs two steps or more");
+    if (pr->parts.size() != 1) return fail(VK_ERR_UNSUPPORTED,
+        "the handle's moments live on several devices: use vk_progress_stderr (host) on a multi-device scene");
+    int rc = progress_wait(pr);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        const auto &q = pr->parts[0];
+        const vk_render_params &p = pr->params;
+        HIP_TRY(hipSetDevice(q.device));
+        const size_t n = (size_t)p.width * p.height;
+        hipLaunchKernelGGL(progress_stderr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream),
+                           (const long long *)q.run, (const double *)q.m2, (const uint32_t *)q.tile_n, (const uint32_t *)q.tile_k, pr->done,
+                           pr->steps, p.width, p.height, (p.width + TILE - 1) / TILE, q.rank, q.world, static_cast<float *>(d_out));
+        HIP_TRY(hipGetLastError());
         return VK_OK;
     });
 }

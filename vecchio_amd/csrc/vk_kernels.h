@@ -1226,6 +1226,216 @@ __global__ void tile_move_kernel(const void *src, void *dst, uint32_t width, uin
     }
 }
 
+// ---- the denoiser (vk_denoise): an edge-avoiding, variance-guided a-trous wavelet filter over one frame, f32, unfused, in the order the
+// header (include/vecchio_amd.h) writes down; tests/denoise_ref.py restates it in numpy and the results agree bit for bit.
+//   P[pixel] = (I_r, I_g, I_b, V)   demodulated colour and the variance of its luminance; V = -1 marks an INVALID pixel (V is >= 0 or NaN
+//                                   otherwise), which is also what the staged form stores for a slot outside the image
+//   G[pixel] = (n_x, n_y, n_z, z)   unit normal, (0,0,0) = no normal (a unit vector is never that); depth, +inf = nothing hit
+//   S[pixel] = (g_x, g_y)           the depth slope
+// denoise_prepare_kernel packs them, one level kernel per pass reads P (ping) and writes P (pong); the last pass remodulates into `out`.
+constexpr uint32_t DN_HAS_STDERR = 1u, DN_HAS_ALBEDO = 2u, DN_HAS_NORMAL = 4u, DN_HAS_DEPTH = 8u, DN_LAST = 16u;
+struct DnArgs {
+    const float4 *Pin; float4 *Pout; float4 *G; float2 *S;          // (prepare writes Pout, G and S)
+    const float *color, *stderr3, *albedo, *normal, *depth;         // prepare: all five; the last level: color and albedo
+    float *out;                                                     // the last level
+    uint32_t width, height, flags, normal_squarings;
+    int s;                                                          // tap spacing of this level
+    float sigma_l, sigma_z, albedo_floor;
+};
+constexpr int DN_BLOCK = 256, DN_SX = 64, DN_R = 4;                 // a workgroup: DN_R rows of DN_SX pixels, one wave per row
+
+__device__ __forceinline__ bool dn_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+__device__ __forceinline__ float dn_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+// E(x) = max(0, 1 - x/8)^8: a compact-support stand-in for exp(-x); fmaxf drops a NaN, so E(NaN) = 0
+__device__ __forceinline__ float dn_falloff(float x) {
+    float t = fmaxf(0.0f, 1.0f - x * 0.125f);
+    t = t * t; t = t * t;
+    return t * t;
+}
+
+__global__ __launch_bounds__(DN_BLOCK) void denoise_prepare_kernel(DnArgs A) {
+    const int x = (int)(blockIdx.x * DN_SX + (threadIdx.x & 63u)), y = (int)(blockIdx.y * DN_R + (threadIdx.x >> 6));
+    const int w = (int)A.width, h = (int)A.height;
+    if (x >= w || y >= h) return;
+    const size_t p = (size_t)y * A.width + x;
+    const float c0 = A.color[p * 3], c1 = A.color[p * 3 + 1], c2 = A.color[p * 3 + 2];
+    bool valid = dn_finite(c0) && dn_finite(c1) && dn_finite(c2);
+    float a0 = 1.0f, a1 = 1.0f, a2 = 1.0f;
+    if (A.flags & DN_HAS_ALBEDO) {
+        a0 = fmaxf(A.albedo[p * 3], A.albedo_floor); a1 = fmaxf(A.albedo[p * 3 + 1], A.albedo_floor);
+        a2 = fmaxf(A.albedo[p * 3 + 2], A.albedo_floor);
+    }
+    float V = 0.0f;
+    if (A.flags & DN_HAS_STDERR) {
+        const float e0 = A.stderr3[p * 3], e1 = A.stderr3[p * 3 + 1], e2 = A.stderr3[p * 3 + 2];
+        valid = valid && dn_finite(e0) && dn_finite(e1) && dn_finite(e2);
+        const float sd = dn_lum(e0 / a0, e1 / a1, e2 / a2);
+        V = sd * sd;
+    }
+    A.Pout[p] = valid ? make_float4(c0 / a0, c1 / a1, c2 / a2, V) : make_float4(c0, c1, c2, -1.0f);
+    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (A.flags & DN_HAS_NORMAL) {
+        const float n0 = A.normal[p * 3], n1 = A.normal[p * 3 + 1], n2 = A.normal[p * 3 + 2];
+        const float l2 = (n0 * n0 + n1 * n1) + n2 * n2;
+        if (!(l2 < 1e-12f) && dn_finite(l2)) { const float l = sqrtf(l2); g.x = n0 / l; g.y = n1 / l; g.z = n2 / l; }
+    }
+    float2 sl = make_float2(0.0f, 0.0f);
+    if (A.flags & DN_HAS_DEPTH) {
+        const float z = A.depth[p];
+        g.w = dn_finite(z) ? z : INFINITY;
+        if (dn_finite(z)) {
+            const float zl = x > 0 ? A.depth[p - 1] : INFINITY, zr = x + 1 < w ? A.depth[p + 1] : INFINITY;
+            const float zd = y > 0 ? A.depth[p - A.width] : INFINITY, zu = y + 1 < h ? A.depth[p + A.width] : INFINITY;
+            const bool l = dn_finite(zl), r = dn_finite(zr), d = dn_finite(zd), u = dn_finite(zu);
+            sl.x = (l && r) ? (zr - zl) * 0.5f : (r ? zr - z : (l ? z - zl : 0.0f));
+            sl.y = (d && u) ? (zu - zd) * 0.5f : (u ? zu - z : (d ? z - zd : 0.0f));
+        }
+    }
+    A.G[p] = g; A.S[p] = sl;
+}
+
+// One pass for the pixel (x, y), both forms: tap(dx, dy, Pq, Gq) fetches the tap at (x + s dx, y + s dy), false = outside the image.
+template <class Tap>
+__device__ __forceinline__ void dn_level_pixel(const DnArgs &A, int x, int y, Tap tap) {
+    const int w = (int)A.width, h = (int)A.height;
+    const size_t p = (size_t)y * A.width + x;
+    const float4 Pp = A.Pin[p];
+    if (Pp.w < 0.0f) {            // invalid: passes through, and comes out as the colour it came in with
+        if (A.flags & DN_LAST) { A.out[p * 3] = A.color[p * 3]; A.out[p * 3 + 1] = A.color[p * 3 + 1]; A.out[p * 3 + 2] = A.color[p * 3 + 2]; }
+        else A.Pout[p] = Pp;
+        return;
+    }
+    const float4 Gp = A.G[p];
+    const float2 Sp = A.S[p];
+    const float Yp = dn_lum(Pp.x, Pp.y, Pp.z);
+    float den_l = 1.0f;
+    if (A.flags & DN_HAS_STDERR) {       // V through (1 2 1; 2 4 2; 1 2 1) over the adjacent valid pixels
+        float acc = 0.0f, ws = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; dy++)
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx++) {
+                const int qx = x + dx, qy = y + dy;
+                if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+                const float v = A.Pin[(size_t)qy * A.width + qx].w;
+                if (v < 0.0f) continue;
+                const float kw = (dx == 0 ? 2.0f : 1.0f) * (dy == 0 ? 2.0f : 1.0f);
+                acc += kw * v; ws += kw;
+            }
+        den_l = A.sigma_l * sqrtf(acc / ws) + 1e-6f;
+    }
+    const bool p_flat = Gp.x == 0.0f && Gp.y == 0.0f && Gp.z == 0.0f, p_far = Gp.w == INFINITY;
+    float W = 0.0f, J0 = 0.0f, J1 = 0.0f, J2 = 0.0f, U = 0.0f;
+#pragma unroll 1
+    for (int dy = -2; dy <= 2; dy++) {
+        const float ky = dy == 0 ? 0.375f : ((dy == 1 || dy == -1) ? 0.25f : 0.0625f);
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const float hk = (dx == 0 ? 0.375f : ((dx == 1 || dx == -1) ? 0.25f : 0.0625f)) * ky;
+            float4 Pq = Pp, Gq = Gp;
+            float wt = hk;
+            if (dx != 0 || dy != 0) {
+                if (!tap(dx, dy, Pq, Gq)) continue;
+                if (Pq.w < 0.0f) continue;
+                float wn = 1.0f, xz = 0.0f, xl = 0.0f;
+                if (A.flags & DN_HAS_NORMAL) {
+                    const bool q_flat = Gq.x == 0.0f && Gq.y == 0.0f && Gq.z == 0.0f;
+                    if (!(p_flat && q_flat)) {          // (one without a normal: the dot product is 0)
+                        wn = fmaxf(0.0f, (Gp.x * Gq.x + Gp.y * Gq.y) + Gp.z * Gq.z);
+                        for (uint32_t i = 0; i < A.normal_squarings; i++) wn = wn * wn;
+                    }
+                }
+                if (A.flags & DN_HAS_DEPTH) {
+                    const bool q_far = Gq.w == INFINITY;
+                    if (p_far != q_far) continue;
+                    if (!p_far) xz = fabsf(Gp.w - Gq.w) /
+                        (A.sigma_z * (fabsf(Sp.x * (float)(A.s * dx) + Sp.y * (float)(A.s * dy)) + 0.001f * Gp.w));
+                }
+                if (A.flags & DN_HAS_STDERR) xl = fabsf(Yp - dn_lum(Pq.x, Pq.y, Pq.z)) / den_l;
+                wt = ((hk * wn) * dn_falloff(xz)) * dn_falloff(xl);
+            }
+            W += wt; J0 += wt * Pq.x; J1 += wt * Pq.y; J2 += wt * Pq.z; U += (wt * wt) * Pq.w;
+        }
+    }
+    const float i0 = J0 / W, i1 = J1 / W, i2 = J2 / W;
+    if (A.flags & DN_LAST) {
+        float a0 = 1.0f, a1 = 1.0f, a2 = 1.0f;
+        if (A.flags & DN_HAS_ALBEDO) {
+            a0 = fmaxf(A.albedo[p * 3], A.albedo_floor); a1 = fmaxf(A.albedo[p * 3 + 1], A.albedo_floor);
+            a2 = fmaxf(A.albedo[p * 3 + 2], A.albedo_floor);
+        }
+        A.out[p * 3] = i0 * a0; A.out[p * 3 + 1] = i1 * a1; A.out[p * 3 + 2] = i2 * a2;
+    } else {
+        A.Pout[p] = make_float4(i0, i1, i2, U / (W * W));
+    }
+}
+
+// the plain form: one thread per pixel, every tap two 16-byte global loads.  The yardstick of the staged form, and the form of the
+// levels where staging does not pay (or does not fit).
+__global__ __launch_bounds__(DN_BLOCK) void denoise_level_plain_kernel(DnArgs A) {
+    const int x = (int)(blockIdx.x * DN_SX + (threadIdx.x & 63u)), y = (int)(blockIdx.y * DN_R + (threadIdx.x >> 6));
+    const int w = (int)A.width, h = (int)A.height;
+    if (x >= w || y >= h) return;
+    dn_level_pixel(A, x, y, [&](int dx, int dy, float4 &Pq, float4 &Gq) {
+        const int qx = x + A.s * dx, qy = y + A.s * dy;
+        if (qx < 0 || qx >= w || qy < 0 || qy >= h) return false;
+        const size_t q = (size_t)qy * A.width + qx;
+        Pq = A.Pin[q]; Gq = A.G[q];
+        return true;
+    });
+}
+
+// the staged form: a workgroup owns DN_SX contiguous x and the DN_R rows y0, y0 + s, .. of one residue class of y mod s, whose taps
+// are each other's.  It stages the DN_R + 4 rows y0 - 2s .. y0 + (DN_R + 1)s of DN_SX + 4s pixels in LDS, coalesced (a slot outside the
+// image is stored as an invalid pixel, which the tap loop skips like the plain form's bounds test), and serves the 25 taps from there:
+// (DN_R + 4)(DN_SX + 4s) / (DN_R DN_SX) staged pixels per output instead of 24.  P and G are separate arrays, so a wave's 64 lanes read 64
+// consecutive 16-byte slots: no bank conflict.  Dynamic LDS: dn_staged_lds_bytes(s).
+__host__ __device__ constexpr uint32_t dn_staged_lds_bytes(int s) { return (uint32_t)((DN_R + 4) * (DN_SX + 4 * s) * 2 * 16); }
+__global__ __launch_bounds__(DN_BLOCK) void denoise_level_staged_kernel(DnArgs A) {
+    extern __shared__ float4 dn_lds[];
+    const int w = (int)A.width, h = (int)A.height, s = A.s, cols = DN_SX + 4 * s, slots = (DN_R + 4) * cols;
+    float4 *sP = dn_lds, *sG = dn_lds + slots;
+    const int x0 = (int)blockIdx.x * DN_SX;
+    const int y0 = (int)(blockIdx.y % (uint32_t)s) + s * (int)(blockIdx.y / (uint32_t)s) * DN_R;
+    for (int i = (int)threadIdx.x; i < slots; i += DN_BLOCK) {
+        const int j = i / cols, c = i - j * cols;
+        const int qx = x0 - 2 * s + c, qy = y0 + (j - 2) * s;
+        float4 P = make_float4(0.0f, 0.0f, 0.0f, -1.0f), G = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (qx >= 0 && qx < w && qy >= 0 && qy < h) { const size_t q = (size_t)qy * A.width + qx; P = A.Pin[q]; G = A.G[q]; }
+        sP[i] = P; sG[i] = G;
+    }
+    __syncthreads();
+    const int tx = (int)(threadIdx.x & 63u), k = (int)(threadIdx.x >> 6);
+    const int x = x0 + tx, y = y0 + k * s;
+    if (x >= w || y >= h) return;
+    dn_level_pixel(A, x, y, [&](int dx, int dy, float4 &Pq, float4 &Gq) {
+        const int i = (k + 2 + dy) * cols + tx + 2 * s + s * dx;
+        Pq = sP[i]; Gq = sG[i];
+        return true;
+    });
+}
+
+// vk_progress_stderr on the device: the same expression in double, in the host call's operation order (no contraction), per pixel of the
+// partition; N and k are the tile's own where adaptive sampling froze it.
+__global__ void progress_stderr_kernel(const long long *run, const double *m2, const uint32_t *tile_n, const uint32_t *tile_k, uint32_t done,
+                                       uint32_t steps, uint32_t width, uint32_t height, uint32_t tiles_x, uint32_t tile_rank,
+                                       uint32_t tile_world, float *out) {
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= (size_t)width * height) return;
+    const uint32_t x = (uint32_t)(pix % width), y = (uint32_t)(pix / width);
+    const uint32_t t = (y / TILE) * tiles_x + x / TILE;
+    if (t % tile_world != tile_rank) return;
+    const uint32_t slot = (t - tile_rank) / tile_world;
+    const uint32_t tn = tile_n ? tile_n[slot] : 0u;
+    const double N = (double)(tn ? tn : done), k = (double)(tn ? tile_k[slot] : steps);
+    for (int c = 0; c < 3; c++) {
+        const size_t i = pix * 3 + c;
+        const double mean = (double)run[i] / (double)ACCUM_SCALE / N;
+        const double v = (m2[i] - N * mean * mean) / ((k - 1.0) * N);
+        out[i] = (float)sqrt(v > 0.0 ? v : 0.0);
+    }
+}
+
 #ifdef VK_DEBUG_LIB
 // device math probe (tests: GPU transcendental/draw functions are bit-identical to the host's)
 __global__ void math_probe_kernel(int op, const float *a, const float *b, float *out, size_t n) {

@@ -156,6 +156,13 @@ class AdaptiveInfo(C.Structure):
     _fields_ = [("tiles_total", C.c_uint32), ("tiles_active", C.c_uint32), ("samples_rendered", C.c_uint64)]
 
 
+class DenoiseParams(C.Structure):
+    """vk_denoise_params (vk_denoise)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("levels", C.c_uint32), ("normal_squarings", C.c_uint32),
+                ("sigma_l", C.c_float), ("sigma_z", C.c_float), ("albedo_floor", C.c_float), ("flags", C.c_uint32)]
+
+
+VK_DENOISE_FORM_AUTO, VK_DENOISE_FORM_PLAIN, VK_DENOISE_FORM_STAGED = range(3)      # vk_debug_denoise_form
 VK_TREE_HANDED_OVER, VK_TREE_REBUILT_PROVEN, VK_TREE_REBUILT_EMPIRICAL, VK_TREE_REBUILT_FAST, VK_TREE_REBUILT_NEAR, VK_TREE_REBUILT_GRID = range(6)
 VK_GATHER_NONE, VK_GATHER_PEER_COPY, VK_GATHER_RCCL = range(3)
 
@@ -227,6 +234,7 @@ DEVICE_SYMBOLS = [
     "vk_progress_create", "vk_progress_step", "vk_progress_step_device", "vk_progress_reset", "vk_progress_stderr",
     "vk_progress_get_info", "vk_progress_destroy", "vk_progress_set_adaptive", "vk_progress_tile_samples",
     "vk_render_aov", "vk_render_aov_device",
+    "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
 ]
 
 
@@ -291,6 +299,18 @@ def _bind(lib):
     lib.vk_render_aov_device.restype = C.c_int
     lib.vk_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_denoise_default_params.restype = C.c_int
+    lib.vk_denoise_default_params.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams)]
+    lib.vk_denoise.restype = C.c_int
+    lib.vk_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)] + [C.c_void_p] * 6 + [C.POINTER(Stats)]
+    lib.vk_denoise_device.restype = C.c_int
+    lib.vk_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)] + [C.c_void_p] * 7
+    lib.vk_progress_stderr_device.restype = C.c_int
+    lib.vk_progress_stderr_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_debug_denoise_form.restype = C.c_int
+    lib.vk_debug_denoise_form.argtypes = [C.c_void_p, C.c_int]
+    lib.vk_debug_denoise_last_ms.restype = C.c_int
+    lib.vk_debug_denoise_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 9)]
     # the test hooks of include/vecchio_amd_debug.h that the product library carries too
     lib.vk_debug_last_launches.restype = C.c_int
     lib.vk_debug_last_launches.argtypes = [C.c_void_p, C.POINTER(DebugLaunch), C.c_uint32, C.POINTER(C.c_uint32)]

@@ -2,13 +2,15 @@
 // scene, build the BVH, upload once, then per Camera of cam_iter: render through the C ABI
 // (the call that replaces main.rs:181-198), write output_%04d.ppm, print the frame time.
 // The reference hard-codes scene/width/spp/depth (main.rs:28-29,159-167,171); here they are
-// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0]
+// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0]
 // steps > 1: each frame is rendered progressively (vk_progress_*) in `steps` equal sample windows; after each window the running image
 // is written to output_%04d_step%02d.ppm and the samples done and the image's mean relative standard error are printed.  The final
 // output_%04d.ppm is byte-identical to the one of steps = 1.
 // aov_spp > 0: each frame also writes its f32 image as output_%04d.pfm and the first-hit buffers of samples 0 .. aov_spp-1
 // (vk_render_aov) as output_%04d_albedo.pfm, _normal.pfm (PF, 3 channels), _depth.pfm and _coverage.pfm (Pf, 1 channel): little-endian
 // (scale -1), rows bottom to top as PFM stores them — the library's y-up buffers as they are.  What a denoiser takes; the .ppm is unchanged.
+// denoise = 1 (needs steps >= 2 and aov_spp > 0): each frame is also denoised on the device (vk_denoise with the library's default parameters)
+// from its final mean, its final standard error and the first-hit buffers, and written as output_%04d_denoised.ppm and .pfm.
 // Texture images are read from ./assets (as in the reference) or $VECCHIO_ASSETS: <name>.ppm.gz, see host_api.h.
 #include <dlfcn.h>
 
@@ -41,7 +43,7 @@ static T sym(void *h, const char *name) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <balls_demo|random_spheres_demo|random_spheres_iow|perlin_demo|bowser_demo|cornell_box|final_scene|"
-                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp]\n", argv[0]);
+                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise]\n", argv[0]);
         return 2;
     }
     const char *name = argv[1];
@@ -52,8 +54,13 @@ int main(int argc, char **argv) {
     uint64_t seed = argc > 6 ? strtoull(argv[6], nullptr, 10) : 1;
     uint32_t steps = argc > 7 ? (uint32_t)atoi(argv[7]) : 1;
     uint32_t aov_spp = argc > 8 ? (uint32_t)atoi(argv[8]) : 0;
+    const bool denoise = argc > 9 && atoi(argv[9]) != 0;
     if (steps < 1) steps = 1;
     if (steps > spp) steps = spp;                                     // every window holds at least one sample
+    if (denoise && (steps < 2 || aov_spp == 0)) {
+        fprintf(stderr, "denoise = 1 needs the standard error and the first-hit buffers: steps >= 2 and aov_spp > 0\n");
+        return 2;
+    }
 
     std::string dir = argv[0];
     size_t slash = dir.find_last_of('/');
@@ -70,6 +77,9 @@ int main(int argc, char **argv) {
     auto p_pdestroy = sym<void (*)(vk_progress *)>(h, "vk_progress_destroy");
     auto p_aov = sym<int (*)(vk_scene *, const vk_camera *, const vk_render_params *, uint32_t, float *, float *, float *, float *, vk_stats *)>(
         h, "vk_render_aov");
+    auto p_dn_defaults = sym<int (*)(uint32_t, uint32_t, vk_denoise_params *)>(h, "vk_denoise_default_params");
+    auto p_denoise = sym<int (*)(vk_scene *, const vk_denoise_params *, const float *, const float *, const float *, const float *, const float *,
+                                 float *, vk_stats *)>(h, "vk_denoise");
 
     fprintf(stderr, "Generating scene...\n");                        // main.rs:157
     vkh_scene *hs = vkh_scene_build(name, seed);
@@ -91,12 +101,13 @@ int main(int argc, char **argv) {
     while (file_idx < frames && vkh_scene_next_camera(hs, &cam)) {   // main.rs:176
         auto start = std::chrono::steady_clock::now();
         vk_stats st{};
+        std::vector<float> err;                                       // the final standard error (steps >= 2)
         if (steps == 1) {
             if (p_render(scene, &cam, &rp, pixels.data(), &st) != VK_OK) { fprintf(stderr, "vk_render: %s\n", p_err()); return 1; }
         } else {
             vk_progress *pr = nullptr;
             if (p_pcreate(scene, &cam, &rp, VK_PROGRESS_STDERR, &pr) != VK_OK) { fprintf(stderr, "vk_progress_create: %s\n", p_err()); return 1; }
-            std::vector<float> err(pixels.size());
+            err.resize(pixels.size());
             uint32_t done = 0;
             for (uint32_t k = 0; k < steps; k++) {
                 const uint32_t n = (uint32_t)((uint64_t)spp * (k + 1) / steps) - done;
@@ -139,6 +150,20 @@ int main(int argc, char **argv) {
                 if (!write_pfm(pfn, o.data, width, height, o.ch)) return 1;
             }
             fprintf(stderr, "  first-hit buffers of %u samples per pixel: kernel %.2f ms\n", aov_spp, as.kernel_ms);
+            if (denoise) {
+                vk_denoise_params dp;
+                std::vector<float> clean(np * 3);
+                vk_stats ds{};
+                if (p_dn_defaults(width, height, &dp) != VK_OK ||
+                    p_denoise(scene, &dp, pixels.data(), err.data(), albedo.data(), normal.data(), zdepth.data(), clean.data(), &ds) != VK_OK) {
+                    fprintf(stderr, "vk_denoise: %s\n", p_err()); return 1; }
+                char dfn[64];
+                snprintf(dfn, sizeof dfn, "output_%04d_denoised.ppm", file_idx);
+                if (vkh_write_ppm(dfn, clean.data(), width, height)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }
+                snprintf(dfn, sizeof dfn, "output_%04d_denoised.pfm", file_idx);
+                if (!write_pfm(dfn, clean.data(), width, height, 3)) return 1;
+                fprintf(stderr, "  denoised (%u levels): kernels %.2f ms\n", dp.levels, ds.kernel_ms);
+            }
         }
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
         fprintf(stderr, "Wrote frame %s in %.3fs (kernel %.1f ms, %.1f Msamples/s)\n", fn, secs, st.kernel_ms,

@@ -87,6 +87,9 @@ pub struct vk_adaptive_params { pub abs_tol: f32, pub rel_tol: f32, pub min_samp
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_adaptive_info { pub tiles_total: u32, pub tiles_active: u32, pub samples_rendered: u64 }
 
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_denoise_params { pub width: u32, pub height: u32, pub levels: u32, pub normal_squarings: u32, pub sigma_l: f32, pub sigma_z: f32, pub albedo_floor: f32, pub flags: u32 }
+
 #[repr(C)] pub struct vk_scene { _private: [u8; 0] }
 #[repr(C)] pub struct vk_progress { _private: [u8; 0] }
 
@@ -121,6 +124,14 @@ extern "C" {
     pub fn vk_render_aov_device(scene: *mut vk_scene, cam: *const vk_camera, params: *const vk_render_params, first_sample: u32,
                                 d_albedo: *mut c_void, d_normal: *mut c_void, d_depth: *mut c_void, d_coverage: *mut c_void,
                                 hip_stream: *mut c_void, stats_out: *mut vk_stats) -> c_int;
+    // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
+    pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
+    pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,
+                      normal: *const f32, depth: *const f32, out: *mut f32, stats_out: *mut vk_stats) -> c_int;
+    pub fn vk_denoise_device(scene: *mut vk_scene, dp: *const vk_denoise_params, d_color: *const c_void, d_stderr3: *const c_void,
+                             d_albedo: *const c_void, d_normal: *const c_void, d_depth: *const c_void, d_out: *mut c_void,
+                             hip_stream: *mut c_void) -> c_int;
+    pub fn vk_progress_stderr_device(pr: *mut vk_progress, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
 }
 
 /// What `flatten()` pushes into (flatten.rs).  One record per Arc; shared Arcs are de-duplicated

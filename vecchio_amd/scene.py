@@ -129,6 +129,40 @@ class DeviceScene:
                                                         C.c_void_p(d_coverage or None), C.c_void_p(stream or 0), C.byref(stats)))
         return stats
 
+    def denoise_params(self, width, height, **overrides):
+        """vk_denoise_default_params for a width x height image, with fields overridden by keyword (levels=, sigma_l=, ...)"""
+        dp = ffi.DenoiseParams()
+        check(self._lib, self._lib.vk_denoise_default_params(width, height, C.byref(dp)))
+        for k, v in overrides.items():
+            if k not in dict(ffi.DenoiseParams._fields_):
+                raise ValueError(f"unknown vk_denoise_params field {k!r}")
+            setattr(dp, k, v)
+        return dp
+
+    def denoise(self, color, stderr=None, albedo=None, normal=None, depth=None, params=None, out=None):
+        """Denoise a frame (vk_denoise): color (height, width, 3) float32 with y = 0 the bottom row, as render() gives it; the optional
+        guides in the same layout — stderr (Progress.stderr()), albedo and normal (height, width, 3), depth (height, width), as
+        render_aov() gives them; None switches a guide's term off.  params: a vk_denoise_params (denoise_params()), default = the
+        library's defaults for this size.  Returns (image, vk_stats)."""
+        h, w = color.shape[:2]
+        dp = params if params is not None else self.denoise_params(w, h)
+        if out is None:
+            out = np.zeros((h, w, 3), np.float32)
+        ptrs = []
+        for a, shape in ((color, (h, w, 3)), (stderr, (h, w, 3)), (albedo, (h, w, 3)), (normal, (h, w, 3)), (depth, (h, w)), (out, (h, w, 3))):
+            if a is not None:
+                assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == shape, (a.dtype, a.shape, shape)
+            ptrs.append(C.c_void_p(a.ctypes.data) if a is not None else None)
+        stats = ffi.Stats()
+        check(self._lib, self._lib.vk_denoise(self._h, C.byref(dp), *ptrs, C.byref(stats)))
+        return out, stats
+
+    def denoise_device(self, params, d_color, d_out, d_stderr=0, d_albedo=0, d_normal=0, d_depth=0, stream=None):
+        """Enqueue the denoiser on device buffers (vk_denoise_device, no host sync); a 0 pointer switches a guide's term off."""
+        check(self._lib, self._lib.vk_denoise_device(self._h, C.byref(params), C.c_void_p(d_color), C.c_void_p(d_stderr or None),
+                                                     C.c_void_p(d_albedo or None), C.c_void_p(d_normal or None),
+                                                     C.c_void_p(d_depth or None), C.c_void_p(d_out), C.c_void_p(stream or 0)))
+
     def render_device(self, cam, params, d_ptr, stream=None):
         """Enqueue a render into device memory at d_ptr on `stream` (no host sync)."""
         stats = ffi.Stats()
@@ -235,6 +269,11 @@ class Progress:
         out = np.zeros((p.height, p.width, 3), np.float32)
         check(self._lib, self._lib.vk_progress_stderr(self._h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def stderr_device(self, d_ptr, stream=None):
+        """stderr() into device memory at d_ptr (vk_progress_stderr_device: width*height*3 floats, this partition's pixels only), enqueued
+        on `stream`; bit-identical to stderr().  Not for handles on a multi-device scene."""
+        check(self._lib, self._lib.vk_progress_stderr_device(self._h, C.c_void_p(d_ptr), C.c_void_p(stream or 0)))
 
     def set_adaptive(self, abs_tol=0.0, rel_tol=0.0, min_samples=0, min_steps=2):
         """Adaptive sampling (vk_progress_set_adaptive): after every window a tile whose pixels all have, per component,
