@@ -576,6 +576,77 @@ int vk_denoise_device(vk_scene *scene, const vk_denoise_params *dp, const void *
  * several devices): vk_progress_stderr stays the way there. */
 int vk_progress_stderr_device(vk_progress *pr, void *d_out, void *hip_stream);
 
+/* ---- temporal accumulation: reproject and blend the frames of a moving camera (additive symbols of ABI 7) -----------------------------
+ * replaces: nothing (the reference's frame loop, main.rs:176, starts every frame from nothing).  The temporal half of SVGF, in front of
+ * vk_denoise: a frame's noisy colour, its standard error, its first-hit buffers and its camera go in; each pixel's first hit is
+ * reprojected into the previous frame's camera, the accumulated history is fetched there with validated bilinear taps and blended with
+ * the frame, the variance is propagated, and the result is kept as the next frame's history.  out_color and out_stderr3 have the shapes
+ * vk_denoise takes: render -> AOV -> accumulate -> denoise.  All images are in vk_render's f32 layout (y = 0 the bottom row): color,
+ * stderr3, albedo, normal, out_color and out_stderr3 3 floats per pixel, depth and out_history 1.  color, normal, depth, out_color and cam
+ * are required (no reprojection without geometry); albedo may be NULL (no demodulation); stderr3 may be NULL (the variance is 0;
+ * out_stderr3 must be NULL too); out_stderr3 and out_history may be NULL.  The call works on the whole image (no tile partition), on the
+ * scene's device (devices[0] of a multi-device scene).  The scene is static by construction (a description is immutable after
+ * vk_scene_create); the caller changes the seed per frame, so that frames are independent.
+ *
+ * The definition, exactly.  Everything is f32, unfused, in the order written, with + - * /, sqrtf, fabsf, fmaxf, fminf, floorf and
+ * compares only; a . b = (a_x*b_x + a_y*b_y) + a_z*b_z; tests/temporal_ref.py restates it in numpy and the two agree bit for bit.
+ * Primes denote the previous frame: its camera (o' = origin, llc', H' = horizontal, V' = vertical, w') and its stored history.
+ *   Prepare, per pixel p = (x, y).  a_c = fmaxf(albedo_c, albedo_floor), or 1 without albedo; I_c = color_c / a_c; S_c = stderr_c / a_c,
+ *     Vc_c = S_c * S_c (0 without stderr3): the variance per component, so that the output feeds vk_denoise's stderr3.  p is INVALID if a
+ *     component of color (or of stderr3, when given) is not finite: out_color is its color and out_stderr3 its stderr3, unchanged,
+ *     out_history 0; it is stored with N = 0 and is never a tap.  Normal: l2 = n . n; l2 < 1e-12f or not finite: p has NO NORMAL; else
+ *     n^ = n / sqrtf(l2).  Depth: z = depth if finite, else +inf (a miss).
+ *   First-hit point.  s = ((float)x + 0.5f) / (float)(width-1), t = ((float)y + 0.5f) / (float)(height-1) (main.rs:187); d = ((llc + H*s)
+ *     + V*t) - origin: the pixel centre through the lens centre (the lens offset is ignored); len = sqrtf(d . d).  A hit: e = (origin +
+ *     d * (z / len)) - o'.  A miss: e = d (a point at infinity: only the rotation matters).
+ *   Projection into the previous camera.  q = llc' - o', fw = -(q . w'), ew = -(e . w').  Not ew > 0: no history.  g = e * (fw / ew) - q;
+ *     s' = (g . H') / (H' . H'), t' = (g . V') / (V' . V'); px = s' * (float)(width-1) - 0.5f, py = t' * (float)(height-1) - 0.5f.  Not
+ *     (px > -1 and px < (float)width and py > -1 and py < (float)height): no history.
+ *   Taps.  x0 = floorf(px), fx = px - x0, y0 = floorf(py), fy = py - y0.  Four taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), in
+ *     that order, with the weights b = (1-fx)*(1-fy), fx*(1-fy), (1-fx)*fy, fx*fy.  A tap outside the image is skipped.  A tap q is
+ *     CONSISTENT when N'_q > 0, and: depth — for a miss pixel z'_q is +inf; for a hit, with ze = sqrtf(e . e), fabsf(z'_q - ze) <=
+ *     depth_tol * ze; and normal — both without a normal: consistent; one without: not; else n^_p . n^'_q >= normal_cos_min.
+ *   Sums over the consistent taps, in tap order, each from 0: W += b, J_c += b * I'_q,c, U_c += b * V'_q,c, M += b * N'_q.
+ *   Blend.  If W >= 0.01f: I_h = J / W, V_h = U / W, N_h = M / W (the variance of resampled, correlated taps is bounded by their weighted
+ *     mean: an upper bound, on purpose); N = fminf(N_h + 1.0f, (float)max_history), alpha = 1.0f / N, k = 1.0f - alpha; I'_c = k * I_h,c
+ *     + alpha * I_c, V'_c = (k*k) * V_h,c + (alpha*alpha) * Vc_c.  Otherwise (also: the first frame after create or reset): no history,
+ *     I' = I, V' = Vc, N = 1.
+ *   Finish.  out_color_c = I'_c * a_c, out_stderr3_c = sqrtf(V'_c) * a_c, out_history = N.  (I', V', N, n^, z) and cam become the history.
+ *     vk_temporal_info.pixels_with_history counts the pixels of the last frame that took the W >= 0.01f branch.
+ * What this is not.  First-hit reprojection is wrong for what is seen in a mirror or through glass: such pixels keep their history and
+ * lag; only max_history bounds the lag.  Nothing detects a changed scene (impossible through this ABI).  Depth of field and motion blur
+ * are reprojected through the lens centre at the averaged depth.
+ * The handle owns the history on the scene's device: two ping-pong sets of three float4 planes, (I_r, I_g, I_b, N), (V_r, V_g, V_b, z),
+ * (n^_x, n^_y, n^_z, -), 48 bytes per pixel each, and the previous camera.  "At most one render in flight per vk_scene" covers these
+ * calls too; they touch nothing that describes vk_render's last frame and no vk_progress handle.
+ * VK_ERR_BAD_ARG, nothing enqueued, handle and outputs untouched: null required pointers, width or height < 2 or beyond vk_render's
+ * limits, max_history outside 1..65535, depth_tol not finite or not > 0, normal_cos_min not finite or outside -1..1, albedo_floor not
+ * finite or not > 0, flags != 0, an output overlapping an input or another output, out_stderr3 without stderr3.  Any other error
+ * (VK_ERR_HIP, VK_ERR_OOM) may come after the frame was enqueued: the handle may have advanced to it while the host outputs were not
+ * written; vk_temporal_reset before the handle is used again.                                                                       */
+typedef struct vk_temporal vk_temporal;            /* opaque; owns the history, on the scene's device */
+typedef struct vk_temporal_params {
+    uint32_t width, height;      /* >= 2 each (the pixel-centre mapping divides by width-1), vk_render's upper limits */
+    uint32_t max_history;        /* 1..65535: the history length N is capped here; blend factor alpha = 1/N */
+    float depth_tol;             /* a tap is consistent when |z_tap - z_expected| <= depth_tol * z_expected   (finite, > 0) */
+    float normal_cos_min;        /* ... and n_p . n_tap >= normal_cos_min                                     (finite, -1..1) */
+    float albedo_floor;          /* > 0, as vk_denoise_params.albedo_floor */
+    uint32_t flags;              /* 0 */
+} vk_temporal_params;
+typedef struct vk_temporal_info { uint32_t frames; uint32_t width, height; uint64_t pixels_with_history; /* of the last frame */ } vk_temporal_info;
+/* max_history 32, depth_tol 0.02, normal_cos_min 0.9, albedo_floor 1e-3 (the sweep).  Touches no device. */
+int vk_temporal_default_params(uint32_t width, uint32_t height, vk_temporal_params *out);
+int vk_temporal_create(vk_scene *scene, const vk_temporal_params *tp, vk_temporal **out);
+/* host buffers; blocking.  stats_out: samples = pixels, kernel_ms (HIP events around the kernel), kernel_launches = 1 */
+int vk_temporal_accumulate(vk_temporal *t, const vk_camera *cam, const float *color, const float *stderr3, const float *albedo,
+                           const float *normal, const float *depth, float *out_color, float *out_stderr3, float *out_history, vk_stats *stats_out);
+/* device buffers on the scene's device, enqueued on hip_stream, no host wait; successive frames of one handle go on one stream */
+int vk_temporal_accumulate_device(vk_temporal *t, const vk_camera *cam, const void *d_color, const void *d_stderr3, const void *d_albedo,
+                                  const void *d_normal, const void *d_depth, void *d_out_color, void *d_out_stderr3, void *d_out_history, void *hip_stream);
+int vk_temporal_reset(vk_temporal *t);            /* forget the history; the next frame is a first frame */
+int vk_temporal_get_info(vk_temporal *t, vk_temporal_info *out);   /* waits for the last frame */
+void vk_temporal_destroy(vk_temporal *t);          /* NULL: nothing; destroy before its scene */
+
 /* test/diagnostic entry points (vk_debug_*) are declared in vecchio_amd_debug.h */
 
 #ifdef __cplusplus

@@ -5,4 +5,4 @@ vecchio_amd/host (C++ mirror of the reference's Rust host side).  This package i
 ctypes plumbing that tests and bench.py use to reach them.
 """
 from . import ffi  # noqa: F401
-from .scene import DeviceScene, HostScene, Progress  # noqa: F401
+from .scene import DeviceScene, HostScene, Progress, Temporal  # noqa: F401

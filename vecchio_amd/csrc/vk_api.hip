@@ -1891,6 +1891,215 @@ int vk_debug_denoise_last_ms(vk_scene *scene, double ms_out[9]) {
 
 }  // extern "C"
 
+// ---- temporal accumulation (vk_temporal_*): temporal_accumulate_kernel (vk_kernels.h) on the scene's device (devices[0] of a
+// multi-device scene).  The handle owns everything it touches: the two histories, the device copies of the host call's images, the
+// counter and its events; nothing of the scene handle is read but its device.
+struct vk_temporal {
+    int device = 0;
+    vk_temporal_params tp{};
+    float4 *hist = nullptr;                         // two histories of three planes of width*height float4 each
+    unsigned long long *count = nullptr;            // pixels_with_history of the last frame
+    float *io = nullptr; size_t io_bytes = 0;       // vk_temporal_accumulate's images on the device
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;        // around the last frame's kernel (ev1: what vk_temporal_get_info waits for)
+    uint32_t frames = 0;                            // since create or reset
+    uint32_t cur = 0;                               // the history the last frame wrote
+    vk_camera prev{};                               // the last frame's camera
+};
+
+namespace {
+
+// images of vk_temporal_accumulate: color, stderr3, albedo, normal, depth, out_color, out_stderr3, out_history
+constexpr uint32_t TA_COMPONENTS[8] = {3u, 3u, 3u, 3u, 1u, 3u, 3u, 1u};
+
+int check_temporal_params(const vk_temporal_params *tp) {
+    if (tp->width < 2u || tp->height < 2u) return fail(VK_ERR_BAD_ARG, "width and height must be >= 2");
+    if ((uint64_t)tp->width * tp->height > (1ull << 31) / 3 || tp->width > 65535u || tp->height > 65535u) return fail(VK_ERR_BAD_ARG,
+        "image too large");
+    if (tp->max_history < 1u || tp->max_history > 65535u) return fail(VK_ERR_BAD_ARG, "max_history must be in 1..65535");
+    if (!std::isfinite(tp->depth_tol) || !(tp->depth_tol > 0.0f)) return fail(VK_ERR_BAD_ARG, "depth_tol must be finite and > 0");
+    if (!std::isfinite(tp->normal_cos_min) || !(tp->normal_cos_min >= -1.0f && tp->normal_cos_min <= 1.0f)) return fail(VK_ERR_BAD_ARG,
+        "normal_cos_min must be finite and in -1..1");
+    if (!std::isfinite(tp->albedo_floor) || !(tp->albedo_floor > 0.0f)) return fail(VK_ERR_BAD_ARG, "albedo_floor must be finite and > 0");
+    if (tp->flags != 0u) return fail(VK_ERR_BAD_ARG, "unknown temporal flags");
+    return VK_OK;
+}
+
+int check_temporal_args(vk_temporal *t, const vk_camera *cam, const void *const img[8]) {
+    if (!t || !cam || !img[0] || !img[3] || !img[4] || !img[5]) return fail(VK_ERR_BAD_ARG, "null argument");
+    if (img[6] && !img[1]) return fail(VK_ERR_BAD_ARG, "out_stderr3 needs stderr3");
+    const size_t n = (size_t)t->tp.width * t->tp.height;
+    for (int k = 5; k < 8; k++) {
+        if (!img[k]) continue;
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(img[k]), o1 = o0 + n * TA_COMPONENTS[k] * sizeof(float);
+        for (int j = 0; j < k; j++) {
+            if (!img[j]) continue;
+            const uintptr_t i0 = reinterpret_cast<uintptr_t>(img[j]), i1 = i0 + n * TA_COMPONENTS[j] * sizeof(float);
+            if (i0 < o1 && o0 < i1) return fail(VK_ERR_BAD_ARG, "an output overlaps an input or another output");
+        }
+    }
+    return VK_OK;
+}
+
+inline float dot3(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+int enqueue_temporal(vk_temporal *t, const vk_camera *cam, const float *const d[8], hipStream_t st, bool timed) {
+    HIP_TRY(hipSetDevice(t->device));
+    const size_t n = (size_t)t->tp.width * t->tp.height;
+    const uint32_t next = t->cur ^ 1u;
+    TaArgs A;
+    memset(&A, 0, sizeof(A));
+    A.Hin = t->hist + (size_t)t->cur * 3 * n; A.Hout = t->hist + (size_t)next * 3 * n;
+    A.color = d[0]; A.stderr3 = d[1]; A.albedo = d[2]; A.normal = d[3]; A.depth = d[4];
+    A.out_color = const_cast<float *>(d[5]); A.out_stderr3 = const_cast<float *>(d[6]); A.out_history = const_cast<float *>(d[7]);
+    A.count = t->count;
+    A.width = t->tp.width; A.height = t->tp.height;
+    A.flags = (d[1] ? TA_HAS_STDERR : 0u) | (d[2] ? TA_HAS_ALBEDO : 0u) | (t->frames > 0u ? TA_HAS_HISTORY : 0u);
+    A.max_history = (float)t->tp.max_history; A.depth_tol = t->tp.depth_tol; A.normal_cos_min = t->tp.normal_cos_min;
+    A.albedo_floor = t->tp.albedo_floor;
+    const vk_camera &c = *cam, &pc = t->prev;
+    for (int k = 0; k < 3; k++) {
+        A.o[k] = c.origin[k]; A.llc[k] = c.lower_left_corner[k]; A.H[k] = c.horizontal[k]; A.V[k] = c.vertical[k];
+        A.po[k] = pc.origin[k]; A.pq[k] = pc.lower_left_corner[k] - pc.origin[k]; A.pw[k] = pc.w[k];
+        A.pH[k] = pc.horizontal[k]; A.pV[k] = pc.vertical[k];
+    }
+    A.fw = -dot3(A.pq, A.pw); A.HH = dot3(A.pH, A.pH); A.VV = dot3(A.pV, A.pV);
+    HIP_TRY(hipMemsetAsync(t->count, 0, sizeof(unsigned long long), st));
+    if (timed) HIP_TRY(hipEventRecord(t->ev0, st));
+    const dim3 grid((t->tp.width + DN_SX - 1) / DN_SX, (t->tp.height + DN_R - 1) / DN_R);
+    hipLaunchKernelGGL(temporal_accumulate_kernel, grid, dim3(DN_BLOCK), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(t->ev1, st));
+    t->cur = next; t->frames++; t->prev = *cam;
+    return VK_OK;
+}
+
+void temporal_free(vk_temporal *t) {
+    (void)hipSetDevice(t->device);
+    if (t->ev1) (void)hipEventSynchronize(t->ev1);
+    for (void *p : {(void *)t->hist, (void *)t->count, (void *)t->io}) if (p) (void)hipFree(p);
+    for (hipEvent_t e : {t->ev0, t->ev1}) if (e) (void)hipEventDestroy(e);
+    delete t;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_temporal_default_params(uint32_t width, uint32_t height, vk_temporal_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    memset(out, 0, sizeof(*out));
+    out->width = width; out->height = height;
+    out->max_history = 32u; out->depth_tol = 0.02f; out->normal_cos_min = 0.9f; out->albedo_floor = 1e-3f;
+    return VK_OK;
+}
+
+int vk_temporal_create(vk_scene *scene, const vk_temporal_params *tp, vk_temporal **out) {
+    if (!tp || !out) return fail(VK_ERR_BAD_ARG, "null argument");
+    int rc = check_temporal_params(tp);
+    if (rc != VK_OK) return rc;
+    if (!scene) return fail(VK_ERR_BAD_ARG, "null scene");
+    return guarded([&]() -> int {
+        vk_temporal *t = new vk_temporal();
+        t->device = (scene->parts.empty() ? scene : scene->parts[0])->device;
+        t->tp = *tp;
+        const size_t n = (size_t)tp->width * tp->height;
+        int e = VK_OK;
+        auto tryhip = [&](hipError_t r, const char *what) {
+            if (e == VK_OK && r != hipSuccess) e = fail(r == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string(what) + ": " +
+                hipGetErrorString(r));
+        };
+        tryhip(hipSetDevice(t->device), "hipSetDevice");
+        if (e == VK_OK) tryhip(hipMalloc(reinterpret_cast<void **>(&t->hist), 6 * n * sizeof(float4)), "hipMalloc (history)");
+        if (e == VK_OK) tryhip(hipMalloc(reinterpret_cast<void **>(&t->count), sizeof(unsigned long long)), "hipMalloc");
+        if (e == VK_OK) tryhip(hipMemset(t->count, 0, sizeof(unsigned long long)), "hipMemset");
+        if (e == VK_OK) tryhip(hipEventCreate(&t->ev0), "hipEventCreate");
+        if (e == VK_OK) tryhip(hipEventCreate(&t->ev1), "hipEventCreate");
+        if (e != VK_OK) { temporal_free(t); return e; }
+        *out = t;
+        return VK_OK;
+    });
+}
+
+int vk_temporal_accumulate(vk_temporal *t, const vk_camera *cam, const float *color, const float *stderr3, const float *albedo,
+    const float *normal, const float *depth, float *out_color, float *out_stderr3, float *out_history, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        float *const host[8] = {const_cast<float *>(color), const_cast<float *>(stderr3), const_cast<float *>(albedo),
+                                const_cast<float *>(normal), const_cast<float *>(depth), out_color, out_stderr3, out_history};
+        int rc = check_temporal_args(t, cam, reinterpret_cast<const void *const *>(host));
+        if (rc != VK_OK) return rc;
+        const auto t0 = std::chrono::steady_clock::now();
+        HIP_TRY(hipSetDevice(t->device));
+        const size_t n = (size_t)t->tp.width * t->tp.height;
+        size_t floats = 0;
+        for (int k = 0; k < 8; k++) if (host[k]) floats += n * TA_COMPONENTS[k];
+        rc = ensure(t->io, t->io_bytes, floats * sizeof(float));
+        if (rc != VK_OK) return rc;
+        const float *dev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        size_t at = 0;
+        for (int k = 0; k < 8; k++) {
+            if (!host[k]) continue;
+            dev[k] = t->io + at;
+            if (k < 5) HIP_TRY(hipMemcpy(t->io + at, host[k], n * TA_COMPONENTS[k] * sizeof(float), hipMemcpyHostToDevice));
+            at += n * TA_COMPONENTS[k];
+        }
+        rc = enqueue_temporal(t, cam, dev, nullptr, true);
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipEventSynchronize(t->ev1));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
+        for (int k = 5; k < 8; k++)
+            if (host[k]) HIP_TRY(hipMemcpy(host[k], dev[k], n * TA_COMPONENTS[k] * sizeof(float), hipMemcpyDeviceToHost));
+        if (stats_out) {
+            memset(stats_out, 0, sizeof(*stats_out));
+            stats_out->samples = n;
+            stats_out->kernel_ms = (double)ms;
+            stats_out->kernel_launches = 1u;
+            stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return VK_OK;
+    });
+}
+
+int vk_temporal_accumulate_device(vk_temporal *t, const vk_camera *cam, const void *d_color, const void *d_stderr3, const void *d_albedo,
+    const void *d_normal, const void *d_depth, void *d_out_color, void *d_out_stderr3, void *d_out_history, void *hip_stream) {
+    return guarded([&]() -> int {
+        const float *dev[8] = {static_cast<const float *>(d_color), static_cast<const float *>(d_stderr3), static_cast<const float *>(d_albedo),
+                               static_cast<const float *>(d_normal), static_cast<const float *>(d_depth), static_cast<const float *>(d_out_color),
+                               static_cast<const float *>(d_out_stderr3), static_cast<const float *>(d_out_history)};
+        int rc = check_temporal_args(t, cam, reinterpret_cast<const void *const *>(dev));
+        if (rc != VK_OK) return rc;
+        return enqueue_temporal(t, cam, dev, reinterpret_cast<hipStream_t>(hip_stream), false);
+    });
+}
+
+int vk_temporal_reset(vk_temporal *t) {
+    if (!t) return fail(VK_ERR_BAD_ARG, "null temporal handle");
+    t->frames = 0;                                   // (the histories stay where they are: a first frame reads none)
+    return VK_OK;
+}
+
+int vk_temporal_get_info(vk_temporal *t, vk_temporal_info *out) {
+    if (!t || !out) return fail(VK_ERR_BAD_ARG, "null argument");
+    return guarded([&]() -> int {
+        memset(out, 0, sizeof(*out));
+        out->frames = t->frames; out->width = t->tp.width; out->height = t->tp.height;
+        if (t->frames > 0u) {
+            unsigned long long c = 0;
+            HIP_TRY(hipSetDevice(t->device));
+            HIP_TRY(hipEventSynchronize(t->ev1));
+            HIP_TRY(hipMemcpy(&c, t->count, sizeof(c), hipMemcpyDeviceToHost));
+            out->pixels_with_history = c;
+        }
+        return VK_OK;
+    });
+}
+
+void vk_temporal_destroy(vk_temporal *t) {
+    if (t) temporal_free(t);
+}
+
+}  // extern "C"
+
 // ---- progressive rendering (ABI 7): one camera + one vk_render_params, running sums on every device part of the scene.  A step is an
 // ordinary render of the sample window [done, done + n) (KArgs::sample_base) whose resolve is replaced by accumulate_resolve_kernel.
 struct vk_progress {

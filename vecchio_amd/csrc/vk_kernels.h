@@ -1436,6 +1436,127 @@ __global__ void progress_stderr_kernel(const long long *run, const double *m2, c
     }
 }
 
+// ---- temporal accumulation (vk_temporal_accumulate): one pass, one thread per pixel, f32, unfused, in the order the header
+// (include/vecchio_amd.h) writes down; tests/temporal_ref.py restates it in numpy and the results agree bit for bit.  The history is three
+// float4 planes of width*height pixels each, so that a tap is three 16-byte loads:
+//   H[pixel]      = (I_r, I_g, I_b, N)   accumulated demodulated colour and its history length; N = 0: an INVALID pixel, never a tap
+//   H[n + pixel]  = (V_r, V_g, V_b, z)   its variance per component; the depth of the frame that wrote it, +inf = nothing hit
+//   H[2n + pixel] = (n_x, n_y, n_z, -)   that frame's unit normal, (0,0,0) = no normal
+// A frame reads Hin (what the previous frame wrote) and writes Hout.  A workgroup is DN_R rows of DN_SX pixels, one wave per row: under a
+// small camera step a wave's taps fall in two or three contiguous rows of the history.  The cameras and the projection constants (q, fw,
+// H'.H', V'.V') come as kernel arguments: wave-uniform, held in SGPRs.  pixels_with_history: one ballot and one vector atomic per wave.
+constexpr uint32_t TA_HAS_STDERR = 1u, TA_HAS_ALBEDO = 2u, TA_HAS_HISTORY = 4u;
+struct TaArgs {
+    const float4 *Hin; float4 *Hout;
+    const float *color, *stderr3, *albedo, *normal, *depth;
+    float *out_color, *out_stderr3, *out_history;                   // (the last two may be null)
+    unsigned long long *count;
+    uint32_t width, height, flags;
+    float max_history, depth_tol, normal_cos_min, albedo_floor;
+    float o[3], llc[3], H[3], V[3];                                 // this frame's camera
+    float po[3], pq[3], pw[3], pH[3], pV[3];                        // the previous frame's: o', q = llc' - o', w', H', V'
+    float fw, HH, VV;                                               // -(q . w'), H' . H', V' . V'
+};
+
+__device__ __forceinline__ float ta_dot(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+
+__global__ __launch_bounds__(DN_BLOCK) void temporal_accumulate_kernel(TaArgs A) {
+    const int x = (int)(blockIdx.x * DN_SX + (threadIdx.x & 63u)), y = (int)(blockIdx.y * DN_R + (threadIdx.x >> 6));
+    const int w = (int)A.width, h = (int)A.height;
+    bool took = false;
+    if (x < w && y < h) {
+        const size_t n = (size_t)A.width * A.height, p = (size_t)y * A.width + x;
+        const float c0 = A.color[p * 3], c1 = A.color[p * 3 + 1], c2 = A.color[p * 3 + 2];
+        bool valid = dn_finite(c0) && dn_finite(c1) && dn_finite(c2);
+        float e0 = 0.0f, e1 = 0.0f, e2 = 0.0f;
+        if (A.flags & TA_HAS_STDERR) {
+            e0 = A.stderr3[p * 3]; e1 = A.stderr3[p * 3 + 1]; e2 = A.stderr3[p * 3 + 2];
+            valid = valid && dn_finite(e0) && dn_finite(e1) && dn_finite(e2);
+        }
+        if (!valid) {                 // passes through, and is stored as a pixel that is never a tap
+            A.out_color[p * 3] = c0; A.out_color[p * 3 + 1] = c1; A.out_color[p * 3 + 2] = c2;
+            if (A.out_stderr3) { A.out_stderr3[p * 3] = e0; A.out_stderr3[p * 3 + 1] = e1; A.out_stderr3[p * 3 + 2] = e2; }
+            if (A.out_history) A.out_history[p] = 0.0f;
+            const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            A.Hout[p] = zero; A.Hout[n + p] = zero; A.Hout[2 * n + p] = zero;
+        } else {
+            float a0 = 1.0f, a1 = 1.0f, a2 = 1.0f;
+            if (A.flags & TA_HAS_ALBEDO) {
+                a0 = fmaxf(A.albedo[p * 3], A.albedo_floor); a1 = fmaxf(A.albedo[p * 3 + 1], A.albedo_floor);
+                a2 = fmaxf(A.albedo[p * 3 + 2], A.albedo_floor);
+            }
+            float I0 = c0 / a0, I1 = c1 / a1, I2 = c2 / a2;
+            float V0 = 0.0f, V1 = 0.0f, V2 = 0.0f;
+            if (A.flags & TA_HAS_STDERR) {
+                const float s0 = e0 / a0, s1 = e1 / a1, s2 = e2 / a2;
+                V0 = s0 * s0; V1 = s1 * s1; V2 = s2 * s2;
+            }
+            float n0 = A.normal[p * 3], n1 = A.normal[p * 3 + 1], n2 = A.normal[p * 3 + 2];
+            const float l2 = ta_dot(n0, n1, n2, n0, n1, n2);
+            const bool p_flat = !(!(l2 < 1e-12f) && dn_finite(l2));
+            if (p_flat) { n0 = 0.0f; n1 = 0.0f; n2 = 0.0f; }
+            else { const float l = sqrtf(l2); n0 = n0 / l; n1 = n1 / l; n2 = n2 / l; }
+            float z = A.depth[p];
+            if (!dn_finite(z)) z = INFINITY;
+            float N = 1.0f;
+            if (A.flags & TA_HAS_HISTORY) {
+                const float s = ((float)x + 0.5f) / (float)(w - 1), t = ((float)y + 0.5f) / (float)(h - 1);
+                const float d0 = ((A.llc[0] + A.H[0] * s) + A.V[0] * t) - A.o[0], d1 = ((A.llc[1] + A.H[1] * s) + A.V[1] * t) - A.o[1],
+                            d2 = ((A.llc[2] + A.H[2] * s) + A.V[2] * t) - A.o[2];
+                const bool miss = z == INFINITY;
+                float g0 = d0, g1 = d1, g2 = d2, ze = 0.0f;            // e, then g
+                if (!miss) {
+                    const float r = z / sqrtf(ta_dot(d0, d1, d2, d0, d1, d2));
+                    g0 = (A.o[0] + d0 * r) - A.po[0]; g1 = (A.o[1] + d1 * r) - A.po[1]; g2 = (A.o[2] + d2 * r) - A.po[2];
+                    ze = sqrtf(ta_dot(g0, g1, g2, g0, g1, g2));
+                }
+                const float ew = -ta_dot(g0, g1, g2, A.pw[0], A.pw[1], A.pw[2]);
+                if (ew > 0.0f) {
+                    const float r = A.fw / ew;
+                    g0 = g0 * r - A.pq[0]; g1 = g1 * r - A.pq[1]; g2 = g2 * r - A.pq[2];
+                    const float px = (ta_dot(g0, g1, g2, A.pH[0], A.pH[1], A.pH[2]) / A.HH) * (float)(w - 1) - 0.5f;
+                    const float py = (ta_dot(g0, g1, g2, A.pV[0], A.pV[1], A.pV[2]) / A.VV) * (float)(h - 1) - 0.5f;
+                    if (px > -1.0f && px < (float)w && py > -1.0f && py < (float)h) {
+                        const float xf = floorf(px), yf = floorf(py), fx = px - xf, fy = py - yf;
+                        const int x0 = (int)xf, y0 = (int)yf;
+                        float W = 0.0f, J0 = 0.0f, J1 = 0.0f, J2 = 0.0f, U0 = 0.0f, U1 = 0.0f, U2 = 0.0f, M = 0.0f;
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
+                            const float b = ((k & 1) ? fx : 1.0f - fx) * ((k >> 1) ? fy : 1.0f - fy);
+                            if (qx < 0 || qx >= w || qy < 0 || qy >= h) continue;
+                            const size_t q = (size_t)qy * A.width + qx;
+                            const float4 hi = A.Hin[q], hv = A.Hin[n + q], hn = A.Hin[2 * n + q];
+                            if (!(hi.w > 0.0f)) continue;
+                            if (miss ? !(hv.w == INFINITY) : !(fabsf(hv.w - ze) <= A.depth_tol * ze)) continue;
+                            const bool q_flat = hn.x == 0.0f && hn.y == 0.0f && hn.z == 0.0f;
+                            if (p_flat != q_flat) continue;
+                            if (!p_flat && !(ta_dot(n0, n1, n2, hn.x, hn.y, hn.z) >= A.normal_cos_min)) continue;
+                            W += b; J0 += b * hi.x; J1 += b * hi.y; J2 += b * hi.z;
+                            U0 += b * hv.x; U1 += b * hv.y; U2 += b * hv.z; M += b * hi.w;
+                        }
+                        if (W >= 0.01f) {
+                            took = true;
+                            N = fminf(M / W + 1.0f, A.max_history);
+                            const float alpha = 1.0f / N, k = 1.0f - alpha, kk = k * k, aa = alpha * alpha;
+                            I0 = k * (J0 / W) + alpha * I0; I1 = k * (J1 / W) + alpha * I1; I2 = k * (J2 / W) + alpha * I2;
+                            V0 = kk * (U0 / W) + aa * V0; V1 = kk * (U1 / W) + aa * V1; V2 = kk * (U2 / W) + aa * V2;
+                        }
+                    }
+                }
+            }
+            A.out_color[p * 3] = I0 * a0; A.out_color[p * 3 + 1] = I1 * a1; A.out_color[p * 3 + 2] = I2 * a2;
+            if (A.out_stderr3) {
+                A.out_stderr3[p * 3] = sqrtf(V0) * a0; A.out_stderr3[p * 3 + 1] = sqrtf(V1) * a1; A.out_stderr3[p * 3 + 2] = sqrtf(V2) * a2;
+            }
+            if (A.out_history) A.out_history[p] = N;
+            A.Hout[p] = make_float4(I0, I1, I2, N); A.Hout[n + p] = make_float4(V0, V1, V2, z); A.Hout[2 * n + p] = make_float4(n0, n1, n2, 0.0f);
+        }
+    }
+    const unsigned long long m = __ballot(took);
+    if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(A.count, (unsigned long long)__popcll(m));
+}
+
 #ifdef VK_DEBUG_LIB
 // device math probe (tests: GPU transcendental/draw functions are bit-identical to the host's)
 __global__ void math_probe_kernel(int op, const float *a, const float *b, float *out, size_t n) {

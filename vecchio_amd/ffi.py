@@ -162,6 +162,17 @@ class DenoiseParams(C.Structure):
                 ("sigma_l", C.c_float), ("sigma_z", C.c_float), ("albedo_floor", C.c_float), ("flags", C.c_uint32)]
 
 
+class TemporalParams(C.Structure):
+    """vk_temporal_params (vk_temporal_create)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("max_history", C.c_uint32), ("depth_tol", C.c_float),
+                ("normal_cos_min", C.c_float), ("albedo_floor", C.c_float), ("flags", C.c_uint32)]
+
+
+class TemporalInfo(C.Structure):
+    """vk_temporal_info (vk_temporal_get_info)"""
+    _fields_ = [("frames", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("pixels_with_history", C.c_uint64)]
+
+
 VK_DENOISE_FORM_AUTO, VK_DENOISE_FORM_PLAIN, VK_DENOISE_FORM_STAGED = range(3)      # vk_debug_denoise_form
 VK_TREE_HANDED_OVER, VK_TREE_REBUILT_PROVEN, VK_TREE_REBUILT_EMPIRICAL, VK_TREE_REBUILT_FAST, VK_TREE_REBUILT_NEAR, VK_TREE_REBUILT_GRID = range(6)
 VK_GATHER_NONE, VK_GATHER_PEER_COPY, VK_GATHER_RCCL = range(3)
@@ -235,6 +246,8 @@ DEVICE_SYMBOLS = [
     "vk_progress_get_info", "vk_progress_destroy", "vk_progress_set_adaptive", "vk_progress_tile_samples",
     "vk_render_aov", "vk_render_aov_device",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
+    "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
+    "vk_temporal_get_info", "vk_temporal_destroy",
 ]
 
 
@@ -307,6 +320,20 @@ def _bind(lib):
     lib.vk_denoise_device.argtypes = [C.c_void_p, C.POINTER(DenoiseParams)] + [C.c_void_p] * 7
     lib.vk_progress_stderr_device.restype = C.c_int
     lib.vk_progress_stderr_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_temporal_default_params.restype = C.c_int
+    lib.vk_temporal_default_params.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(TemporalParams)]
+    lib.vk_temporal_create.restype = C.c_int
+    lib.vk_temporal_create.argtypes = [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(C.c_void_p)]
+    lib.vk_temporal_accumulate.restype = C.c_int
+    lib.vk_temporal_accumulate.argtypes = [C.c_void_p, C.POINTER(Camera)] + [C.c_void_p] * 8 + [C.POINTER(Stats)]
+    lib.vk_temporal_accumulate_device.restype = C.c_int
+    lib.vk_temporal_accumulate_device.argtypes = [C.c_void_p, C.POINTER(Camera)] + [C.c_void_p] * 9
+    lib.vk_temporal_reset.restype = C.c_int
+    lib.vk_temporal_reset.argtypes = [C.c_void_p]
+    lib.vk_temporal_get_info.restype = C.c_int
+    lib.vk_temporal_get_info.argtypes = [C.c_void_p, C.POINTER(TemporalInfo)]
+    lib.vk_temporal_destroy.restype = None
+    lib.vk_temporal_destroy.argtypes = [C.c_void_p]
     lib.vk_debug_denoise_form.restype = C.c_int
     lib.vk_debug_denoise_form.argtypes = [C.c_void_p, C.c_int]
     lib.vk_debug_denoise_last_ms.restype = C.c_int

@@ -2,7 +2,7 @@
 // scene, build the BVH, upload once, then per Camera of cam_iter: render through the C ABI
 // (the call that replaces main.rs:181-198), write output_%04d.ppm, print the frame time.
 // The reference hard-codes scene/width/spp/depth (main.rs:28-29,159-167,171); here they are
-// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0]
+// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0]
 // steps > 1: each frame is rendered progressively (vk_progress_*) in `steps` equal sample windows; after each window the running image
 // is written to output_%04d_step%02d.ppm and the samples done and the image's mean relative standard error are printed.  The final
 // output_%04d.ppm is byte-identical to the one of steps = 1.
@@ -11,6 +11,10 @@
 // (scale -1), rows bottom to top as PFM stores them — the library's y-up buffers as they are.  What a denoiser takes; the .ppm is unchanged.
 // denoise = 1 (needs steps >= 2 and aov_spp > 0): each frame is also denoised on the device (vk_denoise with the library's default parameters)
 // from its final mean, its final standard error and the first-hit buffers, and written as output_%04d_denoised.ppm and .pfm.
+// temporal = 1 (needs steps >= 2 and aov_spp > 0): the frames share one temporal accumulator (vk_temporal_* with the library's default
+// parameters); frame i is rendered with seed + 1 + i, so that the frames are independent, reprojected into the history and written as
+// output_%04d_temporal.ppm and .pfm; with denoise = 1 the denoised files are filtered from the accumulated colour and standard error.
+// With temporal = 0 the seed does not change and every file is what it was.
 // Texture images are read from ./assets (as in the reference) or $VECCHIO_ASSETS: <name>.ppm.gz, see host_api.h.
 #include <dlfcn.h>
 
@@ -43,7 +47,7 @@ static T sym(void *h, const char *name) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <balls_demo|random_spheres_demo|random_spheres_iow|perlin_demo|bowser_demo|cornell_box|final_scene|"
-                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise]\n", argv[0]);
+                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal]\n", argv[0]);
         return 2;
     }
     const char *name = argv[1];
@@ -55,10 +59,15 @@ int main(int argc, char **argv) {
     uint32_t steps = argc > 7 ? (uint32_t)atoi(argv[7]) : 1;
     uint32_t aov_spp = argc > 8 ? (uint32_t)atoi(argv[8]) : 0;
     const bool denoise = argc > 9 && atoi(argv[9]) != 0;
+    const bool temporal = argc > 10 && atoi(argv[10]) != 0;
     if (steps < 1) steps = 1;
     if (steps > spp) steps = spp;                                     // every window holds at least one sample
     if (denoise && (steps < 2 || aov_spp == 0)) {
         fprintf(stderr, "denoise = 1 needs the standard error and the first-hit buffers: steps >= 2 and aov_spp > 0\n");
+        return 2;
+    }
+    if (temporal && (steps < 2 || aov_spp == 0)) {
+        fprintf(stderr, "temporal = 1 needs the standard error and the first-hit buffers: steps >= 2 and aov_spp > 0\n");
         return 2;
     }
 
@@ -80,6 +89,12 @@ int main(int argc, char **argv) {
     auto p_dn_defaults = sym<int (*)(uint32_t, uint32_t, vk_denoise_params *)>(h, "vk_denoise_default_params");
     auto p_denoise = sym<int (*)(vk_scene *, const vk_denoise_params *, const float *, const float *, const float *, const float *, const float *,
                                  float *, vk_stats *)>(h, "vk_denoise");
+    auto p_tp_defaults = sym<int (*)(uint32_t, uint32_t, vk_temporal_params *)>(h, "vk_temporal_default_params");
+    auto p_tcreate = sym<int (*)(vk_scene *, const vk_temporal_params *, vk_temporal **)>(h, "vk_temporal_create");
+    auto p_taccum = sym<int (*)(vk_temporal *, const vk_camera *, const float *, const float *, const float *, const float *, const float *,
+                                float *, float *, float *, vk_stats *)>(h, "vk_temporal_accumulate");
+    auto p_tinfo = sym<int (*)(vk_temporal *, vk_temporal_info *)>(h, "vk_temporal_get_info");
+    auto p_tdestroy = sym<void (*)(vk_temporal *)>(h, "vk_temporal_destroy");
 
     fprintf(stderr, "Generating scene...\n");                        // main.rs:157
     vkh_scene *hs = vkh_scene_build(name, seed);
@@ -96,10 +111,17 @@ int main(int argc, char **argv) {
     rp.integrator = integ; rp.background = bg; rp.background_color[0] = bgc[0]; rp.background_color[1] = bgc[1];
     rp.background_color[2] = bgc[2];
     rp.tile_rank = 0; rp.tile_world = 1;
+    vk_temporal *history = nullptr;
+    if (temporal) {
+        vk_temporal_params tp;
+        if (p_tp_defaults(width, height, &tp) != VK_OK || p_tcreate(scene, &tp, &history) != VK_OK) {
+            fprintf(stderr, "vk_temporal_create: %s\n", p_err()); return 1; }
+    }
     vk_camera cam;
     int file_idx = 0;
     while (file_idx < frames && vkh_scene_next_camera(hs, &cam)) {   // main.rs:176
         auto start = std::chrono::steady_clock::now();
+        if (temporal) rp.seed = seed + 1 + (uint64_t)file_idx;        // independent frames
         vk_stats st{};
         std::vector<float> err;                                       // the final standard error (steps >= 2)
         if (steps == 1) {
@@ -150,12 +172,30 @@ int main(int argc, char **argv) {
                 if (!write_pfm(pfn, o.data, width, height, o.ch)) return 1;
             }
             fprintf(stderr, "  first-hit buffers of %u samples per pixel: kernel %.2f ms\n", aov_spp, as.kernel_ms);
+            const float *dn_color = pixels.data(), *dn_err = err.data();
+            std::vector<float> acc, acc_err;
+            if (temporal) {
+                acc.resize(np * 3); acc_err.resize(np * 3);
+                vk_stats ts{};
+                vk_temporal_info ti{};
+                if (p_taccum(history, &cam, pixels.data(), err.data(), albedo.data(), normal.data(), zdepth.data(), acc.data(), acc_err.data(),
+                             nullptr, &ts) != VK_OK || p_tinfo(history, &ti) != VK_OK) {
+                    fprintf(stderr, "vk_temporal_accumulate: %s\n", p_err()); return 1; }
+                char tfn[64];
+                snprintf(tfn, sizeof tfn, "output_%04d_temporal.ppm", file_idx);
+                if (vkh_write_ppm(tfn, acc.data(), width, height)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }
+                snprintf(tfn, sizeof tfn, "output_%04d_temporal.pfm", file_idx);
+                if (!write_pfm(tfn, acc.data(), width, height, 3)) return 1;
+                fprintf(stderr, "  accumulated: %.1f %% of the pixels with history, kernel %.2f ms\n",
+                        100.0 * (double)ti.pixels_with_history / (double)np, ts.kernel_ms);
+                dn_color = acc.data(); dn_err = acc_err.data();
+            }
             if (denoise) {
                 vk_denoise_params dp;
                 std::vector<float> clean(np * 3);
                 vk_stats ds{};
                 if (p_dn_defaults(width, height, &dp) != VK_OK ||
-                    p_denoise(scene, &dp, pixels.data(), err.data(), albedo.data(), normal.data(), zdepth.data(), clean.data(), &ds) != VK_OK) {
+                    p_denoise(scene, &dp, dn_color, dn_err, albedo.data(), normal.data(), zdepth.data(), clean.data(), &ds) != VK_OK) {
                     fprintf(stderr, "vk_denoise: %s\n", p_err()); return 1; }
                 char dfn[64];
                 snprintf(dfn, sizeof dfn, "output_%04d_denoised.ppm", file_idx);
@@ -170,6 +210,7 @@ int main(int argc, char **argv) {
                 st.kernel_ms > 0 ? (double)st.samples / st.kernel_ms / 1e3 : 0.0);   // main.rs:215
         file_idx++;
     }
+    if (history) p_tdestroy(history);
     p_destroy(scene);
     vkh_scene_free(hs);
     return 0;

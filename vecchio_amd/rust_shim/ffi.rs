@@ -90,8 +90,15 @@ pub struct vk_adaptive_info { pub tiles_total: u32, pub tiles_active: u32, pub s
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_denoise_params { pub width: u32, pub height: u32, pub levels: u32, pub normal_squarings: u32, pub sigma_l: f32, pub sigma_z: f32, pub albedo_floor: f32, pub flags: u32 }
 
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_temporal_params { pub width: u32, pub height: u32, pub max_history: u32, pub depth_tol: f32, pub normal_cos_min: f32, pub albedo_floor: f32, pub flags: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, pub pixels_with_history: u64 }
+
 #[repr(C)] pub struct vk_scene { _private: [u8; 0] }
 #[repr(C)] pub struct vk_progress { _private: [u8; 0] }
+#[repr(C)] pub struct vk_temporal { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -132,6 +139,20 @@ extern "C" {
                              d_albedo: *const c_void, d_normal: *const c_void, d_depth: *const c_void, d_out: *mut c_void,
                              hip_stream: *mut c_void) -> c_int;
     pub fn vk_progress_stderr_device(pr: *mut vk_progress, d_out: *mut c_void, hip_stream: *mut c_void) -> c_int;
+    // temporal accumulation (additive symbols of ABI 7): color, normal, depth, out_color and cam are required; stderr3, albedo,
+    // out_stderr3 and out_history may be null (out_stderr3 needs stderr3)
+    pub fn vk_temporal_default_params(width: u32, height: u32, out: *mut vk_temporal_params) -> c_int;
+    pub fn vk_temporal_create(scene: *mut vk_scene, tp: *const vk_temporal_params, out: *mut *mut vk_temporal) -> c_int;
+    pub fn vk_temporal_accumulate(t: *mut vk_temporal, cam: *const vk_camera, color: *const f32, stderr3: *const f32, albedo: *const f32,
+                                  normal: *const f32, depth: *const f32, out_color: *mut f32, out_stderr3: *mut f32,
+                                  out_history: *mut f32, stats_out: *mut vk_stats) -> c_int;
+    pub fn vk_temporal_accumulate_device(t: *mut vk_temporal, cam: *const vk_camera, d_color: *const c_void, d_stderr3: *const c_void,
+                                         d_albedo: *const c_void, d_normal: *const c_void, d_depth: *const c_void,
+                                         d_out_color: *mut c_void, d_out_stderr3: *mut c_void, d_out_history: *mut c_void,
+                                         hip_stream: *mut c_void) -> c_int;
+    pub fn vk_temporal_reset(t: *mut vk_temporal) -> c_int;
+    pub fn vk_temporal_get_info(t: *mut vk_temporal, out: *mut vk_temporal_info) -> c_int;
+    pub fn vk_temporal_destroy(t: *mut vk_temporal);
 }
 
 /// What `flatten()` pushes into (flatten.rs).  One record per Arc; shared Arcs are de-duplicated

@@ -5,6 +5,7 @@ HostScene  = a scene built by the C++ mirror of scene.rs (libvecchio_host.so) an
 DeviceScene = that description uploaded through the C ABI (vk_scene_create) to one MI355X;
              render() is one call of the drop-in for main.rs:181-198.
 Progress   = one frame of a DeviceScene accumulated over successive sample windows (vk_progress_*).
+Temporal   = the frames of a moving camera reprojected and blended into a history (vk_temporal_*).
 """
 import ctypes as C
 
@@ -217,6 +218,17 @@ class DeviceScene:
                 raise
         return pr
 
+    def temporal(self, width, height, **overrides):
+        """A temporal accumulator for width x height frames of this scene (vk_temporal_create): the library's default parameters with
+        fields overridden by keyword (max_history=, depth_tol=, normal_cos_min=, albedo_floor=).  Use as a context manager, or close()."""
+        tp = ffi.TemporalParams()
+        check(self._lib, self._lib.vk_temporal_default_params(width, height, C.byref(tp)))
+        for k, v in overrides.items():
+            if k not in dict(ffi.TemporalParams._fields_):
+                raise ValueError(f"unknown vk_temporal_params field {k!r}")
+            setattr(tp, k, v)
+        return Temporal(self, tp)
+
     def to_color_device(self, d_rgb, width, height, d_rgb8, stream=None):
         check(self._lib, self._lib.vk_to_color_device(self._h, C.c_void_p(d_rgb), width, height, C.c_void_p(d_rgb8), C.c_void_p(stream or 0)))
 
@@ -310,6 +322,71 @@ class Progress:
     def close(self):
         if self._h:
             self._lib.vk_progress_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Temporal:
+    """vk_temporal handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed)."""
+
+    def __init__(self, scene, params):
+        self._lib = scene._lib
+        self._scene = scene
+        self.params = params
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_temporal_create(scene._h, C.byref(params), C.byref(h)))
+        self._h = h
+
+    def accumulate(self, cam, color, normal, depth, stderr=None, albedo=None, want_history=False):
+        """Blend a frame into the history (vk_temporal_accumulate): color and normal (height, width, 3) float32 with y = 0 the bottom
+        row, depth (height, width), as render() and render_aov() give them, under the camera `cam`; stderr (Progress.stderr()) and
+        albedo are optional.  Returns (color, stderr or None, history length per pixel or None, vk_stats): the first two are what
+        DeviceScene.denoise() takes."""
+        h, w = self.params.height, self.params.width
+        out = np.zeros((h, w, 3), np.float32)
+        out_se = np.zeros((h, w, 3), np.float32) if stderr is not None else None
+        out_n = np.zeros((h, w), np.float32) if want_history else None
+        ptrs = []
+        for a, shape in ((color, (h, w, 3)), (stderr, (h, w, 3)), (albedo, (h, w, 3)), (normal, (h, w, 3)), (depth, (h, w)),
+                         (out, (h, w, 3)), (out_se, (h, w, 3)), (out_n, (h, w))):
+            if a is not None:
+                assert a.dtype == np.float32 and a.flags.c_contiguous and a.shape == shape, (a.dtype, a.shape, shape)
+            ptrs.append(C.c_void_p(a.ctypes.data) if a is not None else None)
+        stats = ffi.Stats()
+        check(self._lib, self._lib.vk_temporal_accumulate(self._h, C.byref(cam), *ptrs, C.byref(stats)))
+        return out, out_se, out_n, stats
+
+    def accumulate_device(self, cam, d_color, d_normal, d_depth, d_out_color, d_stderr=0, d_albedo=0, d_out_stderr=0, d_out_history=0,
+                          stream=None):
+        """Enqueue a frame on device buffers (vk_temporal_accumulate_device, no host sync); a 0 pointer = not given / not wanted."""
+        check(self._lib, self._lib.vk_temporal_accumulate_device(
+            self._h, C.byref(cam), C.c_void_p(d_color), C.c_void_p(d_stderr or None), C.c_void_p(d_albedo or None), C.c_void_p(d_normal),
+            C.c_void_p(d_depth), C.c_void_p(d_out_color), C.c_void_p(d_out_stderr or None), C.c_void_p(d_out_history or None),
+            C.c_void_p(stream or 0)))
+
+    def reset(self):
+        """Forget the history: the next frame is a first frame."""
+        check(self._lib, self._lib.vk_temporal_reset(self._h))
+
+    def info(self):
+        inf = ffi.TemporalInfo()
+        check(self._lib, self._lib.vk_temporal_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def close(self):
+        if self._h:
+            self._lib.vk_temporal_destroy(self._h)
             self._h = None
 
     def __enter__(self):
