@@ -164,6 +164,7 @@ struct HitRec {  // hittable.rs:11-31
     bool front;
     const Material *material;
     uint32_t material_index;
+    bool medium = false;      // (tests only, never read by the radiance path) the record was filled by ConstantMedium::hit
     void set_face_normal(const Ray &r, Vec3 outward_normal) {  // hittable.rs:23-30
         front = r.direction.dot(outward_normal) < 0.0f;
         normal = front ? outward_normal : -outward_normal;
@@ -530,7 +531,7 @@ struct Sphere : Hittable {  // hittable.rs:46-121
                     ret.p = r.at(temp);
                     ret.normal = (r.at(temp) - center) / radius;
                     ret.t = temp; ret.u = 0.0f; ret.v = 0.0f; ret.front = false;
-                    ret.material = material; ret.material_index = mi;
+                    ret.material = material; ret.material_index = mi; ret.medium = false;
                     ret.set_face_normal(r, (ret.p - center) / radius);
                     spherical((ret.p - center) / radius, ret.u, ret.v);
                     return true;
@@ -576,7 +577,7 @@ struct MovingSphere : Hittable {  // hittable.rs:136-197
                     ret.p = r.at(temp);
                     ret.normal = (r.at(temp) - center(r.time)) / radius;
                     ret.t = temp; ret.u = 0.0f; ret.v = 0.0f; ret.front = false;
-                    ret.material = material; ret.material_index = mi;
+                    ret.material = material; ret.material_index = mi; ret.medium = false;
                     ret.set_face_normal(r, (ret.p - center(r.time)) / radius);
                     spherical((ret.p - center(r.time)) / radius, ret.u, ret.v);
                     return true;
@@ -601,7 +602,7 @@ struct Rect : Hittable {  // hittable.rs:199-292
         float u = (a - c0) / (c1 - c0);
         float v = (b - d0) / (d1 - d0);
         ret.p = r.at(t); ret.normal = Vec3::new_const(0.0f); ret.t = t; ret.u = u; ret.v = v; ret.front = false;
-        ret.material = mat; ret.material_index = mi;
+        ret.material = mat; ret.material_index = mi; ret.medium = false;
         ret.set_face_normal(r, outward_normal);
         return true;
     }
@@ -675,7 +676,7 @@ struct ConstantMedium : Hittable {  // hittable.rs:436-498
                 float t = rec1.t + hit_distance / ray_length;
                 out.p = r.at(t); out.normal = Vec3(1.0f, 0.0f, 0.0f); out.t = t;
                 out.u = rec1.u; out.v = rec1.v; out.front = true;
-                out.material = phase_function; out.material_index = mi;
+                out.material = phase_function; out.material_index = mi; out.medium = true;
                 return true;
             }
         }
@@ -899,7 +900,7 @@ struct Scene {
         return out;
     }
 
-    bool build(const vk_scene_desc *desc) {
+    bool build(const vk_scene_desc *desc, bool textures_only = false) {
         d = desc;
         if (!desc) return fail("null scene desc");
         if (desc->abi_version != VK_ABI_VERSION) return fail("abi version mismatch");
@@ -940,6 +941,7 @@ struct Scene {
                 c->odd = textures[t.a].get(); c->even = textures[t.b].get();
             }
         }
+        if (textures_only) return true;      // (oracle_texture_values)
         materials.resize(desc->n_materials);
         for (uint32_t i = 0; i < desc->n_materials; i++) {
             const vk_material &m = desc->materials[i];
@@ -1223,6 +1225,77 @@ int oracle_hit(const vk_scene_desc *desc, const float origin[3], const float dir
         rec_out[10] = (float)rec.material_index;
     }
     return h ? 1 : 0;
+}
+
+int oracle_first_hits(const vk_scene_desc *desc, const vk_camera *cam_in, const vk_render_params *params, uint32_t first_sample,
+                      uint32_t n_samples, oracle_first_hit *out, int n_threads) {
+    g_err.clear();
+    if (!out || n_samples == 0) { g_err = "null output / no samples"; return VK_ERR_BAD_ARG; }
+    if (!check_params(cam_in, params)) return VK_ERR_BAD_ARG;
+    if ((uint64_t)first_sample + n_samples > 0xFFFFFFFFull) { g_err = "sample window exceeds 2^32 - 1"; return VK_ERR_BAD_ARG; }
+    Scene scene;
+    if (!scene.build(desc)) return VK_ERR_BAD_ARG;
+    const vk_render_params p = *params;
+    Camera cam(*cam_in);
+    if (n_threads < 1) n_threads = 1;
+    const uint32_t tiles_x = (p.width + 7) / 8, tiles_y = (p.height + 7) / 8;
+    const uint32_t tile_world = p.tile_world ? p.tile_world : 1;
+    std::atomic<uint32_t> next_tile(0);
+    auto worker = [&]() {
+        g_cnt = oracle_counters();
+        for (;;) {
+            uint32_t tile = next_tile.fetch_add(1);
+            if (tile >= tiles_x * tiles_y) break;
+            if (tile % tile_world != p.tile_rank % tile_world) continue;
+            const uint32_t x0 = (tile % tiles_x) * 8, y0 = (tile / tiles_x) * 8;
+            for (uint32_t y = y0; y < y0 + 8 && y < p.height; y++)
+            for (uint32_t x = x0; x < x0 + 8 && x < p.width; x++) {
+                uint32_t i = y * p.width + x;
+                for (uint32_t k = 0; k < n_samples; k++) {
+                    vk::Rng rng = vk::rng_for_sample(p.seed, i, first_sample + k);      // main.rs:186 (the sample's own stream)
+                    g_rng = &rng;
+                    // trace_sample up to and including ray_color's world.hit (main.rs:187-190, 130)
+                    float u = ((float)x + gen_f32()) / (float)(p.width - 1);
+                    float v = ((float)y + gen_f32()) / (float)(p.height - 1);
+                    Ray ray = cam.get_ray(u, v);
+                    g_nonfinite_segment = nonfinite_ray(ray) ? 1u : 0u;
+                    HitRec c;
+                    bool h = scene.world->hit(ray, 0.001f, INFINITY, c);
+                    oracle_first_hit &o = out[(size_t)i * n_samples + k];
+                    memset(&o, 0, sizeof(o));
+                    for (int a = 0; a < 3; a++) { o.origin[a] = ray.origin[a]; o.direction[a] = ray.direction[a]; }
+                    o.time = ray.time;
+                    o.hit = h ? 1u : 0u;
+                    if (h) {
+                        for (int a = 0; a < 3; a++) { o.p[a] = c.p[a]; o.normal[a] = c.normal[a]; }
+                        o.t = c.t; o.u = c.u; o.v = c.v; o.front = c.front ? 1u : 0u; o.material = c.material_index;
+                        o.medium = c.medium ? 1u : 0u;
+                    }
+                }
+            }
+        }
+        g_rng = nullptr;
+    };
+    std::vector<std::thread> ths;
+    for (int t = 1; t < n_threads; t++) ths.emplace_back(worker);
+    worker();
+    for (auto &t : ths) t.join();
+    return VK_OK;
+}
+
+int oracle_texture_values(const vk_scene_desc *desc, uint32_t texture_index, size_t n, const float *uvp, float *out) {
+    g_err.clear();
+    Scene scene;
+    if (!scene.build(desc, true)) return VK_ERR_BAD_ARG;
+    if (texture_index >= scene.textures.size()) { g_err = "texture index out of range"; return VK_ERR_BAD_ARG; }
+    g_cnt = oracle_counters();
+    const Texture *t = scene.textures[texture_index].get();
+    for (size_t k = 0; k < n; k++) {
+        const float *q = uvp + 5 * k;
+        Vec3 c = t->value(q[0], q[1], Vec3(q[2], q[3], q[4]));
+        out[3 * k + 0] = c.x; out[3 * k + 1] = c.y; out[3 * k + 2] = c.z;
+    }
+    return VK_OK;
 }
 
 void oracle_math(int op, const float *a, const float *b, float *out, size_t n) {

@@ -59,6 +59,22 @@ int oracle_sample(const vk_scene_desc *desc, const vk_camera *cam, const vk_rend
 int oracle_hit(const vk_scene_desc *desc, const float origin[3], const float dir[3], float time,
                float tmin, float tmax, uint64_t seed, float rec_out[11]);
 
+/* The first hit of radiance sample s, from the sample's own stream: for every pixel of the call's tile partition and every sample
+ * s in [first_sample, first_sample + n_samples), exactly what the sample loop does up to and including ray_color's world.hit
+ * (main.rs:186-190, 130) — the sample's stream seeded, the two jitter draws, Camera::get_ray's draws, then the one hit call, whose
+ * ConstantMedium draws continue that stream — and nothing after it.  out[pixel * n_samples + (s - first_sample)]; pixels outside
+ * the partition are left as they are.  `medium`: the closest hit's record was filled by ConstantMedium::hit (hittable.rs:453-493). */
+typedef struct oracle_first_hit {
+    float origin[3], direction[3], time;      /* the primary ray                                          */
+    float p[3], normal[3], t, u, v;           /* the hit record (hit != 0 only)                           */
+    uint32_t hit, front, material, medium;
+} oracle_first_hit;
+int oracle_first_hits(const vk_scene_desc *desc, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
+                      uint32_t n_samples, oracle_first_hit *out, int n_threads);
+
+/* Texture::value of texture `texture_index` (material.rs:228-434) at n points: uvp = n x {u, v, p.x, p.y, p.z}, out = n x rgb */
+int oracle_texture_values(const vk_scene_desc *desc, uint32_t texture_index, size_t n, const float *uvp, float *out);
+
 /* shared-math probes (unit tests): op 0 sin,1 cos,2 log,3 asin,4 atan2(a,b),5 pow5, 11/12 sincos .s/.c, 13/14 sincos_small .s/.c
  * (the numbers of the device probe, vk_debug_math)                                                                          */
 void oracle_math(int op, const float *a, const float *b, float *out, size_t n);

@@ -1,9 +1,12 @@
-"""Per-sample references for the first-hit buffers (vk_render_aov), built from the CPU oracle (which stays as it is).  TESTS ONLY.
+"""Per-sample references for the first-hit buffers (vk_render_aov), built from the CPU oracle.  TESTS ONLY.
 
-(a) rays and hits: Camera::get_ray (main.rs:111-120, in start_sample_core's draw order) restated in numpy float32 from the sample's own
-    draws (oracle_draws), then oracle_hit for p, normal, t, u, v, front and material.  Coverage, depth and normal; albedo where the
-    material's texture is solid (checker of solids through the oracle's own sin).  Valid for media-free scenes only: oracle_hit draws a
-    medium's distance from a stream of its own.
+(a) rays and hits, for every scene: oracle_first_hits (oracle/oracle.h) runs the radiance sample loop up to and including its first
+    world.hit — the sample's own stream, the jitter and camera draws, then the hit call whose ConstantMedium draws continue that stream —
+    and returns the ray, the hit record and whether ConstantMedium::hit filled it.  From those, by the rules of include/vecchio_amd.h:
+    coverage; depth f32(t) * sqrt(f32(d.d)); the normal, (0,0,0) for a medium hit; the albedo from the material and the oracle's own
+    Texture::value (oracle_texture_values: solid, checker, image and noise alike), the phase function's texture for a medium hit.
+    primary_ray restates the camera draws in numpy float32 from the bare draw stream (oracle_draws): tests/test_aov_emu.py pins
+    oracle_first_hits' rays to it bit for bit.
 (b) emitter substitution, for albedo on every scene, media included: every material becomes a DiffuseLight whose emit texture is its
     albedo texture ((1,1,1) for Dielectric, a solid mix for a SpecDiffuse of solids, the emit colour clamped to [0, 1] for a light), and
     the oracle renders it with the SCATTER integrator: per sample the radiance is then the texture value at the first hit, or the
@@ -82,69 +85,63 @@ def _clamp01(a):
     return np.where(a < 0, f32(0), np.where(a > 1, f32(1), a)).astype(f32)
 
 
+def _length(d):
+    """sqrt(f32(d.d)) of direction(s) d (..., 3), the products summed in x, y, z order"""
+    d = np.asarray(d, f32)
+    return np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2], dtype=f32)
+
+
 def background(p, d):
+    """the background the radiance sample sees along direction(s) d (..., 3), clamped to [0, 1]"""
+    d = np.asarray(d, f32)
     if p.background == ffi.VK_BACKGROUND_SKY:
-        n = np.sqrt(f32(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), dtype=f32)
-        t = f32(0.5) * (d[1] / n + f32(1.0))
-        return _clamp01(np.array([1, 1, 1], f32) * (f32(1.0) - t) + np.array([0.5, 0.7, 1.0], f32) * t)
-    return _clamp01(list(p.background_color))
+        t = f32(0.5) * (d[..., 1] / _length(d) + f32(1.0))
+        return _clamp01((f32(1.0) - t)[..., None] * np.array([1, 1, 1], f32) + t[..., None] * np.array([0.5, 0.7, 1.0], f32))
+    return np.broadcast_to(_clamp01(list(p.background_color)), d.shape).copy()
 
 
-def _tex_value(oracle, desc, tex, p):
-    """texture value of a solid, or a checker of solids (material.rs:250-258); None for image / noise (ref (b) covers those)"""
-    for _ in range(16):
-        t = desc.textures[tex]
-        if t.kind == ffi.VK_TEX_SOLID:
-            return np.array(list(t.color), f32)
-        if t.kind != ffi.VK_TEX_CHECKER:
-            return None
-        sins = oracle.math(0, np.array([f32(10.0) * f32(p[0]), f32(10.0) * f32(p[1]), f32(10.0) * f32(p[2])], f32))
-        tex = t.a if (sins[0] * sins[1]) * sins[2] < 0 else t.b
-    return np.zeros(3, f32)
-
-
-def _albedo_a(oracle, desc, mi, rec, level=0):
+def _albedo_a(oracle, desc_ptr, mi, fh, level=0):
+    """albedo (n, 3) of material mi at the n hit records fh (material.rs; include/vecchio_amd.h vk_render_aov)"""
+    desc = desc_ptr.contents
     m = desc.materials[mi]
+    n = fh.shape[0]
     if m.kind == ffi.VK_MAT_DIELECTRIC:
-        return np.ones(3, f32)
-    if m.kind == ffi.VK_MAT_DIFFUSE_LIGHT:
-        if not rec["front"]:
-            return np.zeros(3, f32)
-        v = _tex_value(oracle, desc, m.texture, rec["p"])
-        return None if v is None else _clamp01(v)
+        return np.ones((n, 3), f32)
     if m.kind == ffi.VK_MAT_SPEC_DIFFUSE:
         if level >= 8:
-            return np.zeros(3, f32)
-        a, b = _albedo_a(oracle, desc, m.a, rec, level + 1), _albedo_a(oracle, desc, m.b, rec, level + 1)
-        if a is None or b is None:
-            return None
+            return np.zeros((n, 3), f32)
+        a, b = _albedo_a(oracle, desc_ptr, m.a, fh, level + 1), _albedo_a(oracle, desc_ptr, m.b, fh, level + 1)
         pct = f32(m.param)
         return (pct * a + (f32(1.0) - pct) * b).astype(f32)
-    return _tex_value(oracle, desc, m.texture, rec["p"])
+    v = oracle.texture_values(desc_ptr, m.texture, fh["u"], fh["v"], fh["p"])
+    if m.kind == ffi.VK_MAT_DIFFUSE_LIGHT:           # emitted(): front faces only (material.rs:218-225), clamped
+        return np.where((fh["front"] != 0)[:, None], _clamp01(v), f32(0.0)).astype(f32)
+    return v
 
 
 def ref_a(oracle, desc_ptr, cam, p, samples):
-    """per pixel (h, w) and sample: dict of arrays — coverage (0/1), depth (inf on a miss), normal, albedo (NaN where not restated);
-    each of shape (len(samples), h, w[, 3]); 'dropped' marks samples with a non-finite component"""
-    desc = desc_ptr.contents
+    """per sample of `samples` and pixel: dict of arrays — coverage (0/1), depth (inf on a miss), normal, albedo, each of shape
+    (len(samples), h, w[, 3]); 'medium' (bool: the first hit is a ConstantMedium's) and 'dropped' (bool: a non-finite component, the
+    sample adds to no sum); 'origin', 'direction', 'time': the primary ray"""
     n = len(samples)
-    out = dict(albedo=np.full((n, p.height, p.width, 3), np.nan, f32), normal=np.zeros((n, p.height, p.width, 3), f32),
-               depth=np.full((n, p.height, p.width), np.inf, f32), coverage=np.zeros((n, p.height, p.width), f32))
+    shape = (n, p.height, p.width)
+    fh = np.zeros(shape, dtype=oracle.FIRST_HIT_DTYPE)
     for k, s in enumerate(samples):
-        for y in range(p.height):
-            for x in range(p.width):
-                o, d, t = primary_ray(oracle, cam, p, x, y, s)
-                rec = oracle.hit(desc_ptr, o, d, float(t))
-                if rec is None:
-                    out["albedo"][k, y, x] = background(p, d)
-                    continue
-                out["coverage"][k, y, x] = 1.0
-                out["normal"][k, y, x] = rec["normal"]
-                out["depth"][k, y, x] = f32(rec["t"]) * np.sqrt(f32(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]), dtype=f32)
-                a = _albedo_a(oracle, desc, rec["material"], rec)
-                if a is not None:
-                    out["albedo"][k, y, x] = a
-    return out
+        fh[k] = oracle.first_hits(desc_ptr, cam, p, s, 1)[:, :, 0]
+    hit = fh["hit"] != 0
+    medium = hit & (fh["medium"] != 0)
+    d = fh["direction"]
+    albedo = np.full(shape + (3,), np.nan, f32)
+    albedo[~hit] = background(p, d[~hit])
+    for mi in np.unique(fh["material"][hit]):
+        sel = hit & (fh["material"] == mi)
+        albedo[sel] = _albedo_a(oracle, desc_ptr, int(mi), fh[sel])
+    normal = np.where((hit & ~medium)[..., None], fh["normal"], f32(0.0)).astype(f32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        depth = np.where(hit, fh["t"] * _length(d), f32(np.inf)).astype(f32)
+    ok = np.isfinite(albedo).all(-1) & np.isfinite(normal).all(-1) & (~hit | np.isfinite(depth))
+    return dict(albedo=albedo, normal=normal, depth=depth, coverage=hit.astype(f32), medium=medium, dropped=~ok,
+                origin=fh["origin"].copy(), direction=d.copy(), time=fh["time"].copy(), material=fh["material"].copy())
 
 
 # ---------------------------------------------------------------- (b) emitter substitution

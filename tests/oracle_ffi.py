@@ -21,6 +21,18 @@ class Counters(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class FirstHit(C.Structure):
+    """oracle_first_hit (oracle/oracle.h)"""
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3), ("time", C.c_float), ("p", C.c_float * 3),
+                ("normal", C.c_float * 3), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("hit", C.c_uint32),
+                ("front", C.c_uint32), ("material", C.c_uint32), ("medium", C.c_uint32)]
+
+
+FIRST_HIT_DTYPE = np.dtype([("origin", "<f4", 3), ("direction", "<f4", 3), ("time", "<f4"), ("p", "<f4", 3), ("normal", "<f4", 3),
+                            ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("hit", "<u4"), ("front", "<u4"), ("material", "<u4"),
+                            ("medium", "<u4")])
+assert FIRST_HIT_DTYPE.itemsize == C.sizeof(FirstHit) == 80
+
 _lib = None
 
 
@@ -40,6 +52,11 @@ def load():
     lib.oracle_hit.restype = C.c_int
     lib.oracle_hit.argtypes = [C.POINTER(ffi.SceneDesc), ffi.F3, ffi.F3, C.c_float, C.c_float, C.c_float, C.c_uint64,
                                C.POINTER(C.c_float * 11)]
+    lib.oracle_first_hits.restype = C.c_int
+    lib.oracle_first_hits.argtypes = [C.POINTER(ffi.SceneDesc), C.POINTER(ffi.Camera), C.POINTER(ffi.RenderParams), C.c_uint32,
+                                      C.c_uint32, C.c_void_p, C.c_int]
+    lib.oracle_texture_values.restype = C.c_int
+    lib.oracle_texture_values.argtypes = [C.POINTER(ffi.SceneDesc), C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.oracle_math.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     lib.oracle_draws.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_float, C.c_uint32, C.c_void_p, C.c_size_t]
     lib.oracle_last_error.restype = C.c_char_p
@@ -92,6 +109,30 @@ def hit(desc, origin, direction, time=0.0, tmin=0.001, tmax=float("inf"), seed=0
         return None
     r = list(rec)
     return dict(p=r[0:3], normal=r[3:6], t=r[6], u=r[7], v=r[8], front=bool(r[9]), material=int(r[10]))
+
+
+def first_hits(desc, cam, params, first_sample, n_samples, threads=None):
+    """the first hit of radiance samples first_sample .. first_sample + n_samples - 1 of every pixel, each from its own stream: a
+    structured array (height, width, n_samples) of FIRST_HIT_DTYPE"""
+    lib = load()
+    out = np.zeros((params.height, params.width, n_samples), dtype=FIRST_HIT_DTYPE)
+    threads = threads or min(len(os.sched_getaffinity(0)), 32)
+    st = lib.oracle_first_hits(desc, C.byref(cam), C.byref(params), first_sample, n_samples, out.ctypes.data, threads)
+    if st != 0:
+        raise RuntimeError(f"oracle status {st}: {lib.oracle_last_error().decode()}")
+    return out
+
+
+def texture_values(desc, texture_index, u, v, p):
+    """Texture::value of one texture at n points (u[n], v[n], p[n, 3]): rgb (n, 3)"""
+    lib = load()
+    uvp = np.ascontiguousarray(np.concatenate([np.asarray(u, np.float32).reshape(-1, 1), np.asarray(v, np.float32).reshape(-1, 1),
+                                               np.asarray(p, np.float32).reshape(-1, 3)], axis=1), dtype=np.float32)
+    out = np.zeros((uvp.shape[0], 3), dtype=np.float32)
+    st = lib.oracle_texture_values(desc, texture_index, uvp.shape[0], uvp.ctypes.data, out.ctypes.data)
+    if st != 0:
+        raise RuntimeError(f"oracle status {st}: {lib.oracle_last_error().decode()}")
+    return out
 
 
 def math(op, a, b=None):

@@ -1,12 +1,20 @@
-"""First-hit buffers (vk_render_aov) on the MI355X: per sample against the two oracle references of tests/aov_ref.py, the same first hit as
-the radiance sample, medium statistics, exact aggregation, every call shape bit for bit, non-interference with vk_render and progress
-handles, invalid calls."""
+"""First-hit buffers (vk_render_aov) on the MI355X: per sample against the two oracle references of tests/aov_ref.py — media scenes
+included, every sample compared: a medium's distance comes from the radiance sample's own stream (oracle_first_hits) — on every view of a
+scene the first-hit walk runs on (each form of exact re-treeing bit for bit against the tree as handed over, in a child process per
+form; VK_SCENE_FAST_ACCEL), both kernel instances, the same first hit as the radiance sample, medium statistics, exact aggregation with
+dropped samples, every call shape bit for bit, non-interference with vk_render and progress handles, invalid calls.  tests/test_aov_emu.py
+is the CPU counterpart and holds the shared scenes.  Run with -s for the largest differences per channel."""
 import ctypes as C
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 import aov_ref
+import special_scenes
+import test_aov_emu as shared
 from descs import Desc, camera, params
 from test_fuzz_scenes import Gen
 from vecchio_amd import DeviceScene, HostScene, ffi
@@ -14,6 +22,7 @@ from vecchio_amd import DeviceScene, HostScene, ffi
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMED = ("cornell_box", "random_spheres_iow", "bowser_demo", "perlin_demo", "balls_demo")
 
 
@@ -38,14 +47,17 @@ def singles(ds, cam, p, samples):
     return [ds.render_aov(cam, q, first_sample=s)[0] for s in samples]
 
 
-def media_free(desc):
-    return desc.contents.n_media == 0
-
-
 def _check_against_a(ds, desc, cam, p, oracle, samples=(0, 1)):
     got = singles(ds, cam, p, samples)
     ref = aov_ref.ref_a(oracle, desc, cam, p, list(samples))
+    assert np.isfinite(ref["albedo"]).all() and not ref["dropped"].any()         # no sample is left out of a comparison
+    worst = shared.Worst()
     for k, g in enumerate(got):
+        worst.add(g, ref, k)
+    print("\n   device vs oracle:", worst)
+    for k, g in enumerate(got):
+        med = ref["medium"][k]
+        assert (g["normal"][med] == 0).all() and (g["coverage"][med] == 1).all()
         np.testing.assert_array_equal(g["coverage"], ref["coverage"][k])
         hit = ref["coverage"][k] == 1
         np.testing.assert_allclose(g["normal"], ref["normal"][k], atol=1e-4)
@@ -77,13 +89,178 @@ def test_named_scene_per_sample_against_oracle(name, device, oracle):
         ds.close()
 
 
-@pytest.mark.parametrize("seed", [2, 3, 4, 6, 8, 9])      # the media-free graphs among tests/test_fuzz_scenes.py Gen(1000 + 0..11)
+@pytest.mark.parametrize("seed", shared.FUZZ_SEEDS)      # tests/test_fuzz_scenes.py Gen(1000 + seed), with and without media
 def test_fuzz_graph_per_sample_against_oracle(seed, device, oracle):
     g, desc, cam, p = fuzz(seed)
-    assert media_free(desc)
     ds = DeviceScene(desc)
     try:
         _check_against_a(ds, desc, cam, p, oracle)
+    finally:
+        ds.close()
+
+
+def _media_scene(name):
+    if name in NAMED_MEDIA:
+        return named(name, width=16)
+    if name in shared.EXTRA:
+        return shared.EXTRA[name]()
+    return shared.special(name)
+
+
+NAMED_MEDIA = ("final_scene", "final_scene_nextweek")
+
+
+@pytest.mark.parametrize("name", NAMED_MEDIA + ("media_and_textures", "fog", "camera_inside_medium"))
+def test_media_scene_per_sample_against_oracle(name, device, oracle):
+    """several media along a ray, a medium under a transform, a Boxy boundary, the camera inside a medium, the single-object BVH node
+    that draws its medium twice: normal, depth, coverage and albedo of every sample"""
+    keep, desc, cam, p = _media_scene(name)
+    ds = DeviceScene(desc)
+    try:
+        _check_against_a(ds, desc, cam, p, oracle, samples=(0, 1, 2, 3))
+        ref = aov_ref.ref_a(oracle, desc, cam, p, [0, 1, 2, 3])
+        shared.assert_both_kinds_of_hit(ref)
+    finally:
+        ds.close()
+
+
+@pytest.mark.parametrize("name", sorted(special_scenes.ALL))
+def test_special_scene_per_sample_against_oracle(name, device, oracle):
+    keep, desc, cam, p = shared.special(name)
+    ds = DeviceScene(desc)
+    try:
+        _check_against_a(ds, desc, cam, p, oracle)
+    finally:
+        ds.close()
+
+
+# ---------------------------------------------------------------- every view of a scene the first-hit walk runs on (vk_api.hip aov_view)
+# name -> scene, scene seed, environment of the child (the switches are read at scene creation), debug library?, tree, staged in LDS?
+FORMS = {
+    "grid_lds": ("random_spheres_iow", 1, {}, False, "VK_TREE_REBUILT_GRID", True),
+    "near_lds": ("random_spheres_iow", 3, {"VK_NO_GRID": "1"}, False, "VK_TREE_REBUILT_NEAR", True),
+    "near_global": ("stress_spheres:30", 1, {}, False, "VK_TREE_REBUILT_NEAR", False),        # both trees in one items[]
+    "unit_lds": ("random_spheres_iow", 1, {"VK_NEAR_FIRST": "0", "VK_NO_GRID": "1"}, True, "VK_TREE_REBUILT_PROVEN", True),
+}
+FORM_W, FORM_SAMPLES = 48, (0, 1)
+
+_FORM_CHILD = """
+import sys, ctypes as C
+sys.path.insert(0, %(root)r); sys.path.insert(0, %(tests)r)
+import numpy as np
+from vecchio_amd import DeviceScene, HostScene, ffi
+lib = ffi.load_debug_lib() if %(debug)r else None
+res = {}
+for flags in (0, ffi.VK_SCENE_REFERENCE_TREE):
+    hs = HostScene(%(scene)r, %(seed)d); hs.desc.contents.flags = flags; cam = hs.next_camera()
+    ds = DeviceScene(hs.desc, lib=lib) if lib is not None else DeviceScene(hs.desc)
+    img, st = ds.render(cam, hs.params(128, 8, 50, seed=3))
+    tree, in_lds, features = ds.info().tree, bool(st.scene_in_lds), ds.info().features
+    got = []
+    for s in %(samples)r:
+        got.append(ds.render_aov(cam, hs.params(%(w)d, 1, 50, seed=7, height=%(w)d), first_sample=s)[0])
+    again, _ = ds.render(cam, hs.params(128, 8, 50, seed=3))
+    assert np.array_equal(img.view(np.uint32), again.view(np.uint32))
+    res[flags] = (tree, in_lds, features, got)
+    ds.close(); hs.close()
+tree, in_lds, features, got = res[0]
+rtree, _, rfeatures, rgot = res[ffi.VK_SCENE_REFERENCE_TREE]
+assert tree == ffi.%(tree)s and in_lds == %(in_lds)r, (tree, in_lds)
+assert rtree == ffi.VK_TREE_HANDED_OVER, rtree
+assert features == 0 and rfeatures == 0, (features, rfeatures)
+for a, b in zip(got, rgot):
+    for ch in ("albedo", "normal", "depth", "coverage"):
+        assert np.array_equal(a[ch].view(np.uint32), b[ch].view(np.uint32)), ch
+np.savez(%(out)r, **{"%%s_%%d" %% (ch, k): g[ch] for k, g in enumerate(got) for ch in g})
+print("FORM OK", tree, in_lds)
+"""
+
+
+@pytest.mark.parametrize("form", sorted(FORMS))
+def test_every_tree_view_gives_the_handed_over_trees_first_hits(form, device, oracle, tmp_path):
+    """One sphere-only world per form of exact re-treeing, each in a fresh child process (the switches are read at scene creation).  The
+    child asserts the form it runs (vk_scene_info.tree, vk_stats.scene_in_lds of a vk_render) and that the per-sample buffers are those
+    of the same world created with VK_SCENE_REFERENCE_TREE, bit for bit; the buffers then meet reference (a) here."""
+    scene, seed, env, debug, tree, in_lds = FORMS[form]
+    out = str(tmp_path / "aov.npz")
+    code = _FORM_CHILD % dict(root=ROOT, tests=os.path.join(ROOT, "tests"), debug=debug, scene=scene, seed=seed, samples=FORM_SAMPLES,
+                              w=FORM_W, tree=tree, in_lds=in_lds, out=out)
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "FORM OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    z = np.load(out)
+    hs = HostScene(scene, seed)
+    cam = hs.next_camera()
+    p = hs.params(FORM_W, 1, 50, seed=7, height=FORM_W)
+    ref = aov_ref.ref_a(oracle, hs.desc, cam, p, list(FORM_SAMPLES))
+    assert np.isfinite(ref["albedo"]).all() and not ref["dropped"].any() and 0 < ref["coverage"].sum()
+    worst = shared.Worst()
+    for k in range(len(FORM_SAMPLES)):
+        g = {ch: z["%s_%d" % (ch, k)] for ch in aov_ref.CHANNELS}
+        np.testing.assert_array_equal(g["coverage"], ref["coverage"][k])
+        hit = ref["coverage"][k] == 1
+        np.testing.assert_allclose(g["normal"], ref["normal"][k], atol=1e-4)
+        np.testing.assert_allclose(g["depth"][hit], ref["depth"][k][hit], rtol=1e-5)
+        assert np.isinf(g["depth"][~hit]).all()
+        np.testing.assert_allclose(g["albedo"], ref["albedo"][k], atol=1e-4)
+        worst.add(g, ref, k)
+    print("\n   %s, device vs oracle:" % form, worst)
+    hs.close()
+
+
+def _fast_accel_scenes():
+    from test_retree import Crowd
+    out = {"crowd%d" % k: (lambda k=k: (None,) + Crowd(5000 + k).build()) for k in range(4)}
+
+    def iow():
+        hs = HostScene("random_spheres_iow", 1)
+        hs.desc.contents.flags = ffi.VK_SCENE_FAST_ACCEL
+        return hs, hs.desc, hs.next_camera(), hs.params(24, 1, 50, seed=7, height=24)
+    out["random_spheres_iow"] = iow
+    return out
+
+
+@pytest.mark.parametrize("name", ["crowd0", "crowd1", "crowd2", "crowd3", "random_spheres_iow"])
+def test_fast_accel_first_hits_against_oracle(name, device, oracle):
+    """VK_SCENE_FAST_ACCEL: the walk runs on the rebuilt tree with its tie table.  The scenes are those on which the suite requires the
+    radiance under this flag to be the reference's (tests/test_retree.py: the crowds, the InOneWeekend world)."""
+    keep, desc, cam, p = _fast_accel_scenes()[name]()
+    assert desc.contents.flags == ffi.VK_SCENE_FAST_ACCEL
+    ds = DeviceScene(desc)
+    try:
+        _check_against_a(ds, desc, cam, p, oracle)
+    finally:
+        ds.close()
+
+
+def test_both_kernel_instances_are_rendered(device, oracle):
+    """aov_kernel<0> for a world of spheres only, aov_kernel<VKF_ALL_SCENE> for anything else (vk_api.hip enqueue_aov): by the scenes'
+    features, since the launch log is vk_render's and first-hit calls leave it alone"""
+    seen = set()
+    for name in ("random_spheres_iow", "cornell_box"):
+        hs, desc, cam, p = named(name)
+        ds = DeviceScene(desc)
+        try:
+            seen.add(ds.info().features == 0)
+            _check_against_a(ds, desc, cam, p, oracle)
+        finally:
+            ds.close()
+    assert seen == {False, True}
+
+
+@pytest.mark.parametrize("name", sorted(shared.DROPPED))
+def test_dropped_samples_count_in_n_only(name, device, oracle):
+    """samples with a non-finite albedo (NaN / infinite texture components on Lambertian spheres and on a phase function) add to no sum
+    and not to hits, but count in n: a multi-sample window against the aggregate of the single-sample calls, bit for bit, with pixels
+    whose coverage is below 1 because of the drop alone"""
+    keep, desc, cam, p = shared.DROPPED[name]()
+    n = p.samples_per_pixel
+    ds = DeviceScene(desc)
+    try:
+        assert (ds.info().features == 0) == (name == "dropped_spheres")
+        one = singles(ds, cam, p, range(n))
+        window, st = ds.render_aov(cam, p)
+        ref = aov_ref.ref_a(oracle, desc, cam, p, list(range(n)))
+        print("\n   dropped samples, pixels partly dropped:", shared.check_dropped_window(name, p, one, window, ref))
     finally:
         ds.close()
 
@@ -98,13 +275,7 @@ def test_media_scene_albedo_against_substitution(name, device, oracle):
         ds.close()
 
 
-def _fog_scene():
-    d = Desc()
-    emit = (0.3, 0.6, 0.9)
-    back = d.xy_rect(-20, 20, -20, 20, -5.0, d.light(*emit))
-    fog = d.medium(d.sphere((0, 0, 0), 2.0, d.lambertian(0.5, 0.5, 0.5)), 0.4, d.mat(ffi.VK_MAT_ISOTROPIC, d.solid(0.8, 0.2, 0.2)))
-    world = d.big_box(fog, back)
-    return d, d.finish(world), emit
+_fog_scene = shared.fog_scene
 
 
 def test_same_first_hit_as_the_radiance_sample(device):
