@@ -517,6 +517,51 @@ int vk_render_aov(vk_scene *scene, const vk_camera *cam, const vk_render_params 
 int vk_render_aov_device(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
                          void *d_albedo, void *d_normal, void *d_depth, void *d_coverage, void *hip_stream, vk_stats *stats_out);
 
+/* ---- specular guides: the buffers above, followed through mirrors and glass (additive symbols of ABI 7) ---------------------------
+ * replaces: nothing.  vk_render_aov stops at the first hit: a glass sphere is albedo (1,1,1) with a smooth normal, a polished metal one
+ * tint, and what is seen in or through them reaches a denoiser or a reprojection unguided.  vk_render_guides follows perfect-specular
+ * ("delta") interactions to the first surface that is not one and reports THAT surface.  vk_render_aov is unchanged.
+ * Layouts, the sample window, the tile partition, the argument checks, the scene-state rules, the multi-device rule and stats_out are
+ * vk_render_aov's; `bounces` is a fifth optional buffer, 1 float per pixel; any of the five may be NULL, not all five.  Also
+ * VK_ERR_BAD_ARG with nothing enqueued: a null gp, max_bounces > 8, fuzz_max not finite or < 0, flags != 0.
+ * Per sample s of pixel p, everything f32 and unfused in the reference's order:
+ *   Segment 0 is vk_render_aov's: the primary ray of radiance sample s and its first hit, on the same tree view (a medium's draw
+ *     continues the sample's stream).  thr = (1,1,1), len = 0, b = 0.
+ *   Delta hit: the closest hit is not a medium's, and its material is Dielectric, or Metal with fuzz <= fuzz_max.  (A SpecDiffuse is
+ *     not a delta material, whatever its children.)
+ *   Continuation, while the hit is a delta hit and b < max_bounces: len += t * |d| (|d| = sqrtf(d.d), as the depth rule has it); the next
+ *     ray starts at rec.p with the sample's time; Metal: direction reflect(unit(d), n) (material.rs:118-132 without the fuzz term),
+ *     thr = thr * texture value at (u, v, p); Dielectric: exactly the operations of material.rs:150-175 with the Schlick draw skipped
+ *     — eta = front ? 1 / ir : ir, cos = fminf(dot(-unit(d), n), 1), sin = sqrtf(1 - cos * cos), reflect when eta * sin > 1, refract
+ *     (util.rs:18-23) otherwise — thr unchanged; b += 1; BVHNode::hit with tmin 0.001, tmax inf on the same tree view.  A
+ *     ConstantMedium met on continuation segment b (1..8) draws from a fresh stream rng_for_sample(cseed, 0, 0), cseed = seed +
+ *     0x9E3779B97F4A7C15 * ((((u64)pixel << 32) | sample) * 16 + b) in wrapping u64.
+ *   Terminal surface, the last surface hit: a continuation segment that misses leaves the delta hit it started from as the terminal
+ *     surface — normal that hit's, depth = len (which holds the segment that reached it), albedo = thr * clamp01(background(direction of
+ *     the missing segment)), the sky unitised as for a first-hit miss.  Otherwise albedo = thr * (the first-hit albedo rule at the
+ *     terminal hit), normal by the first-hit rule ((0,0,0) for a medium), depth = len + t * |d|.  A primary miss is vk_render_aov's.
+ *     `hit` is the primary ray's: coverage equals vk_render_aov's.
+ *   Dropped samples and aggregation are vk_render_aov's; bounces = (sum of b over the kept samples, as an integer) / (float)n.
+ *   max_bounces = 0 returns vk_render_aov's four buffers bit for bit.
+ * What this is not.  The depth is the unfolded path length, a "virtual" depth: reprojecting with it is right for a planar mirror and
+ * only approximate for a curved one (the virtual image of a curved mirror does not lie at that distance).  Glass shows its refraction
+ * only, never its Fresnel reflection: the Schlick-weighted choice is not drawn, so a pane's faint mirror image has no guide.  One
+ * path per sample: no separate reflection and refraction layers, no motion vectors.                                              */
+typedef struct vk_guide_params {
+    uint32_t max_bounces;        /* continuations per sample, 0..8 */
+    float fuzz_max;              /* a Metal of fuzz <= fuzz_max is a mirror */
+    uint32_t flags;              /* 0 */
+} vk_guide_params;
+/* max_bounces 4, fuzz_max 0, flags 0; touches no device */
+int vk_guide_default_params(vk_guide_params *out);
+int vk_render_guides(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
+                     const vk_guide_params *gp, float *albedo, float *normal, float *depth, float *coverage, float *bounces,
+                     vk_stats *stats_out);
+/* device buffers on the scene's device (devices[0] of a multi-device scene), enqueued on hip_stream, no host wait */
+int vk_render_guides_device(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
+                            const vk_guide_params *gp, void *d_albedo, void *d_normal, void *d_depth, void *d_coverage, void *d_bounces,
+                            void *hip_stream, vk_stats *stats_out);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

@@ -1616,21 +1616,25 @@ DScene aov_view(const vk_scene *s) {
     return v;
 }
 
-int check_aov_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p, uint32_t first_sample, const void *const bufs[4]) {
+// n_bufs: 4 (vk_render_aov) or 5 (vk_render_guides: bounces too)
+int check_aov_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p, uint32_t first_sample, const void *const *bufs,
+    int n_bufs) {
     int rc = check_call_args(scene, cam, p);
     if (rc != VK_OK) return rc;
     if (p->output_format != VK_OUTPUT_F32) return fail(VK_ERR_BAD_ARG, "first-hit buffers are f32 only (output_format must be VK_OUTPUT_F32)");
-    if (!bufs[0] && !bufs[1] && !bufs[2] && !bufs[3]) return fail(VK_ERR_BAD_ARG, "no first-hit buffer wanted (all four are null)");
+    // (vk_render_guides has refused five null buffers already, before it looked at the scene: check_guide_args)
+    if (n_bufs == 4 && !bufs[0] && !bufs[1] && !bufs[2] && !bufs[3]) return fail(VK_ERR_BAD_ARG, "no first-hit buffer wanted (all four are null)");
     if ((uint64_t)first_sample + p->samples_per_pixel > 0xFFFFFFFFull) return fail(VK_ERR_BAD_ARG,
         "first_sample + samples_per_pixel exceeds 2^32 - 1");
     return VK_OK;
 }
 
-// floats per pixel of albedo, normal, depth, coverage
-constexpr uint32_t AOV_COMPONENTS[4] = {3u, 3u, 1u, 1u};
+// floats per pixel of albedo, normal, depth, coverage (and vk_render_guides' bounces)
+constexpr uint32_t AOV_COMPONENTS[5] = {3u, 3u, 1u, 1u, 1u};
 
+// gp != nullptr: the specular guides (specular_guides_kernel) with d_bounces as the fifth buffer, otherwise the first-hit buffers
 int enqueue_aov(vk_scene *q, const vk_camera *cam, const vk_render_params *p, uint32_t first_sample, float *const d[4], hipStream_t st,
-    bool timed) {
+    bool timed, const vk_guide_params *gp = nullptr, float *d_bounces = nullptr) {
     HIP_TRY(hipSetDevice(q->device));
     const TileGeom g(p);
     AovArgs A;
@@ -1652,7 +1656,12 @@ int enqueue_aov(vk_scene *q, const vk_camera *cam, const vk_render_params *p, ui
     if (g.n_local != 0u) {
         const dim3 grid((g.n_local + AOV_BLOCK / 64 - 1) / (AOV_BLOCK / 64));
         // a sphere-only world: the fused sphere path (C2); anything else: the everything-variant
-        if (q->host->features == 0u) hipLaunchKernelGGL(aov_kernel<0u>, grid, dim3(AOV_BLOCK), 0, st, A);
+        if (gp) {
+            GuideArgs G;
+            G.A = A; G.bounces = d_bounces; G.max_bounces = gp->max_bounces; G.fuzz_max = gp->fuzz_max;
+            if (q->host->features == 0u) hipLaunchKernelGGL(specular_guides_kernel<0u>, grid, dim3(AOV_BLOCK), 0, st, G);
+            else hipLaunchKernelGGL(specular_guides_kernel<(uint32_t)VKF_ALL_SCENE>, grid, dim3(AOV_BLOCK), 0, st, G);
+        } else if (q->host->features == 0u) hipLaunchKernelGGL(aov_kernel<0u>, grid, dim3(AOV_BLOCK), 0, st, A);
         else hipLaunchKernelGGL(aov_kernel<(uint32_t)VKF_ALL_SCENE>, grid, dim3(AOV_BLOCK), 0, st, A);
         HIP_TRY(hipGetLastError());
     }
@@ -1667,6 +1676,52 @@ void aov_stats(const vk_render_params *p, vk_stats *st) {
     st->kernel_launches = g.n_local != 0u ? 1u : 0u;
 }
 
+// The host-pointer call of vk_render_aov (n_bufs 4, gp null) and vk_render_guides (n_bufs 5): the wanted buffers staged side by side in the
+// scene's own device buffer, one timed launch, the copies back.  The arguments have been checked.
+int render_aov_host(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample, float *const host[5],
+    int n_bufs, const vk_guide_params *gp, vk_stats *stats_out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+    HIP_TRY(hipSetDevice(q->device));
+    const size_t n_pixels = (size_t)params->width * params->height;
+    size_t floats = 0;
+    for (int k = 0; k < n_bufs; k++) if (host[k]) floats += n_pixels * AOV_COMPONENTS[k];
+    int rc = ensure(q->aov_buf, q->aov_bytes, floats * sizeof(float));
+    if (rc != VK_OK) return rc;
+    float *dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t at = 0;
+    for (int k = 0; k < n_bufs; k++) if (host[k]) { dev[k] = q->aov_buf + at; at += n_pixels * AOV_COMPONENTS[k]; }
+    // a partition: the caller's pixels outside it must come back untouched
+    const bool partial = (params->tile_world ? params->tile_world : 1u) > 1u;
+    if (partial)
+        for (int k = 0; k < n_bufs; k++)
+            if (host[k]) HIP_TRY(hipMemcpy(dev[k], host[k], n_pixels * AOV_COMPONENTS[k] * sizeof(float), hipMemcpyHostToDevice));
+    rc = enqueue_aov(q, cam, params, first_sample, dev, nullptr, true, gp, dev[4]);
+    if (rc != VK_OK) return rc;
+    HIP_TRY(hipEventSynchronize(q->aov_ev1));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, q->aov_ev0, q->aov_ev1));
+    for (int k = 0; k < n_bufs; k++)
+        if (host[k]) HIP_TRY(hipMemcpy(host[k], dev[k], n_pixels * AOV_COMPONENTS[k] * sizeof(float), hipMemcpyDeviceToHost));
+    if (stats_out) {
+        aov_stats(params, stats_out);
+        stats_out->kernel_ms = (double)ms;
+        stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return VK_OK;
+}
+
+// vk_render_guides' own checks, made first (they need no scene), then the first-hit checks with five buffers
+int check_guide_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p, uint32_t first_sample, const vk_guide_params *gp,
+    const void *const bufs[5]) {
+    if (!gp) return fail(VK_ERR_BAD_ARG, "null guide parameters");
+    if (gp->max_bounces > 8u) return fail(VK_ERR_BAD_ARG, "guide max_bounces exceeds 8");
+    if (!(gp->fuzz_max >= 0.0f) || !(gp->fuzz_max < INFINITY)) return fail(VK_ERR_BAD_ARG, "guide fuzz_max must be finite and >= 0");
+    if (gp->flags != 0u) return fail(VK_ERR_BAD_ARG, "guide flags must be 0");
+    if (!bufs[0] && !bufs[1] && !bufs[2] && !bufs[3] && !bufs[4]) return fail(VK_ERR_BAD_ARG, "no guide buffer wanted (all five are null)");
+    return check_aov_args(scene, cam, p, first_sample, bufs, 5);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1674,38 +1729,10 @@ extern "C" {
 int vk_render_aov(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample, float *albedo, float *normal,
     float *depth, float *coverage, vk_stats *stats_out) {
     return guarded([&]() -> int {
-        float *host[4] = {albedo, normal, depth, coverage};
-        int rc = check_aov_args(scene, cam, params, first_sample, reinterpret_cast<const void *const *>(host));
+        float *host[5] = {albedo, normal, depth, coverage, nullptr};
+        int rc = check_aov_args(scene, cam, params, first_sample, reinterpret_cast<const void *const *>(host), 4);
         if (rc != VK_OK) return rc;
-        const auto t0 = std::chrono::steady_clock::now();
-        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
-        HIP_TRY(hipSetDevice(q->device));
-        const size_t n_pixels = (size_t)params->width * params->height;
-        size_t floats = 0;
-        for (int k = 0; k < 4; k++) if (host[k]) floats += n_pixels * AOV_COMPONENTS[k];
-        rc = ensure(q->aov_buf, q->aov_bytes, floats * sizeof(float));
-        if (rc != VK_OK) return rc;
-        float *dev[4] = {nullptr, nullptr, nullptr, nullptr};
-        size_t at = 0;
-        for (int k = 0; k < 4; k++) if (host[k]) { dev[k] = q->aov_buf + at; at += n_pixels * AOV_COMPONENTS[k]; }
-        // a partition: the caller's pixels outside it must come back untouched
-        const bool partial = (params->tile_world ? params->tile_world : 1u) > 1u;
-        if (partial)
-            for (int k = 0; k < 4; k++)
-                if (host[k]) HIP_TRY(hipMemcpy(dev[k], host[k], n_pixels * AOV_COMPONENTS[k] * sizeof(float), hipMemcpyHostToDevice));
-        rc = enqueue_aov(q, cam, params, first_sample, dev, nullptr, true);
-        if (rc != VK_OK) return rc;
-        HIP_TRY(hipEventSynchronize(q->aov_ev1));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, q->aov_ev0, q->aov_ev1));
-        for (int k = 0; k < 4; k++)
-            if (host[k]) HIP_TRY(hipMemcpy(host[k], dev[k], n_pixels * AOV_COMPONENTS[k] * sizeof(float), hipMemcpyDeviceToHost));
-        if (stats_out) {
-            aov_stats(params, stats_out);
-            stats_out->kernel_ms = (double)ms;
-            stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
-        return VK_OK;
+        return render_aov_host(scene, cam, params, first_sample, host, 4, nullptr, stats_out);
     });
 }
 
@@ -1714,10 +1741,47 @@ int vk_render_aov_device(vk_scene *scene, const vk_camera *cam, const vk_render_
     return guarded([&]() -> int {
         float *dev[4] = {static_cast<float *>(d_albedo), static_cast<float *>(d_normal), static_cast<float *>(d_depth),
                          static_cast<float *>(d_coverage)};
-        int rc = check_aov_args(scene, cam, params, first_sample, reinterpret_cast<const void *const *>(dev));
+        int rc = check_aov_args(scene, cam, params, first_sample, reinterpret_cast<const void *const *>(dev), 4);
         if (rc != VK_OK) return rc;
         vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
         rc = enqueue_aov(q, cam, params, first_sample, dev, reinterpret_cast<hipStream_t>(hip_stream), false);
+        if (rc != VK_OK) return rc;
+        if (stats_out) aov_stats(params, stats_out);
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- specular guides (vk_render_guides): vk_render_aov's launcher, checks, events and staging buffer around specular_guides_kernel
+extern "C" {
+
+int vk_guide_default_params(vk_guide_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null guide parameters");
+    out->max_bounces = 4u; out->fuzz_max = 0.0f; out->flags = 0u;
+    return VK_OK;
+}
+
+int vk_render_guides(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
+    const vk_guide_params *gp, float *albedo, float *normal, float *depth, float *coverage, float *bounces, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        float *host[5] = {albedo, normal, depth, coverage, bounces};
+        int rc = check_guide_args(scene, cam, params, first_sample, gp, reinterpret_cast<const void *const *>(host));
+        if (rc != VK_OK) return rc;
+        return render_aov_host(scene, cam, params, first_sample, host, 5, gp, stats_out);
+    });
+}
+
+int vk_render_guides_device(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
+    const vk_guide_params *gp, void *d_albedo, void *d_normal, void *d_depth, void *d_coverage, void *d_bounces, void *hip_stream,
+    vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        float *dev[5] = {static_cast<float *>(d_albedo), static_cast<float *>(d_normal), static_cast<float *>(d_depth),
+                         static_cast<float *>(d_coverage), static_cast<float *>(d_bounces)};
+        int rc = check_guide_args(scene, cam, params, first_sample, gp, reinterpret_cast<const void *const *>(dev));
+        if (rc != VK_OK) return rc;
+        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        rc = enqueue_aov(q, cam, params, first_sample, dev, reinterpret_cast<hipStream_t>(hip_stream), false, gp, dev[4]);
         if (rc != VK_OK) return rc;
         if (stats_out) aov_stats(params, stats_out);
         return VK_OK;

@@ -1196,6 +1196,51 @@ __global__ __launch_bounds__(AOV_BLOCK) void aov_kernel(AovArgs A) {
     if (A.coverage) A.coverage[pix] = (float)hits / fn;
 }
 
+// ---- specular guides (vk_render_guides): the first-hit kernel's launch shape, tile walk and aggregation around vk_trace.h guide_sample,
+// whose bounce loop runs inside the lane (a tile's lanes stay together through a large mirror or glass sphere).  bounces: the
+// continuations of the kept samples, summed as integers (at most 8 * 2^26), over (float)n.
+struct GuideArgs {
+    AovArgs A;
+    float *bounces;          // f32, y up, may be null
+    uint32_t max_bounces; float fuzz_max;
+};
+template <uint32_t F>
+__global__ __launch_bounds__(AOV_BLOCK) void specular_guides_kernel(GuideArgs G) {
+    const AovArgs &A = G.A;
+    const uint32_t lane = threadIdx.x & 63u, local = blockIdx.x * (AOV_BLOCK / 64) + (threadIdx.x >> 6);
+    if (local >= A.n_local) return;
+    const uint32_t tile = A.tile_rank + local * A.tile_world;
+    const uint32_t x = (tile % A.tiles_x) * TILE + (lane & 7u), y = (tile / A.tiles_x) * TILE + (lane >> 3);
+    if (x >= A.C.width || y >= A.C.height) return;
+    const GlobalMem M{A.S.items, A.S.spheres, A.S.sphere_mat, A.S.boxes};
+    // the running sums live in private memory between samples (touched once per sample, outside the walk), not in registers across it
+    volatile float sum[7];
+    volatile uint32_t cnt[2];
+    for (int i = 0; i < 7; i++) sum[i] = 0.0f;
+    cnt[0] = 0u; cnt[1] = 0u;
+#pragma unroll 1
+    for (uint32_t k = 0; k < A.C.spp; k++) {
+        Lane L;
+        V3 a, n; float dp; bool h; uint32_t b;
+        const bool kept = guide_sample<F, GlobalMem>(L, A.S, M, A.C, G.max_bounces, G.fuzz_max, x, y, A.first_sample + k, a, n, dp, h, b);
+        if (!kept) continue;                                   // dropped: counts in n only
+        sum[0] = sum[0] + a.x; sum[1] = sum[1] + a.y; sum[2] = sum[2] + a.z;
+        sum[3] = sum[3] + n.x; sum[4] = sum[4] + n.y; sum[5] = sum[5] + n.z;
+        cnt[1] = cnt[1] + b;
+        if (h) { sum[6] = sum[6] + dp; cnt[0] = cnt[0] + 1u; }
+    }
+    const V3 sa = v3(sum[0], sum[1], sum[2]), sn = v3(sum[3], sum[4], sum[5]);
+    const float sd = sum[6];
+    const uint32_t hits = cnt[0], sb = cnt[1];
+    const float fn = (float)A.C.spp;
+    const size_t pix = (size_t)y * A.C.width + x;
+    if (A.albedo) { A.albedo[pix * 3 + 0] = sa.x / fn; A.albedo[pix * 3 + 1] = sa.y / fn; A.albedo[pix * 3 + 2] = sa.z / fn; }
+    if (A.normal) { A.normal[pix * 3 + 0] = sn.x / fn; A.normal[pix * 3 + 1] = sn.y / fn; A.normal[pix * 3 + 2] = sn.z / fn; }
+    if (A.depth) A.depth[pix] = hits ? sd / (float)hits : INFINITY;
+    if (A.coverage) A.coverage[pix] = (float)hits / fn;
+    if (G.bounces) G.bounces[pix] = (float)sb / fn;
+}
+
 // ---- tile slabs: the pixels of one tile partition (tiles t = rank + i*world, i = 0..n_local) packed tile by tile,
 // 64 pixel slots per tile, 3 components per slot.  A multi-device scene moves one slab per device to devices[0]
 // (the path's only exchange) and de-interleaves it there; RGB8 output packs bytes (to_color fused: 4x less traffic).

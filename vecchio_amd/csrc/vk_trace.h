@@ -1562,5 +1562,80 @@ VK_HD bool aov_sample(Lane &L, const DScene &S, const Mem &M, const RenderConsts
     return finite3(albedo) && finite3(normal) && finite_f(depth);
 }
 
+// ------------------------------------------------------------------ specular guides (vk_render_guides, include/vecchio_amd.h)
+// The stream a ConstantMedium met on continuation segment b (1..8) of sample (pixel, sample) draws from: rng_for_sample(cseed, 0, 0)
+VK_HD Rng guide_segment_rng(uint64_t seed, uint32_t pixel, uint32_t sample, uint32_t b) {
+    const uint64_t cseed = seed + 0x9E3779B97F4A7C15ull * (((((uint64_t)pixel << 32) | (uint64_t)sample) * 16ull) + (uint64_t)b);
+    return vk::rng_for_sample(cseed, 0u, 0u);
+}
+// Sample `sample` of pixel (x, y): aov_sample's primary ray and first hit, then — while the hit is a delta hit (Dielectric, or Metal of
+// fuzz <= fuzz_max; never a medium) and fewer than max_bounces continuations were made — the mirror direction of Metal::scatter without
+// its fuzz term, or Dielectric::scatter's direction with the Schlick draw skipped (reflect under total internal reflection, refract
+// otherwise), walked on the same tree view.  The terminal surface's albedo times the Metal tints passed (thr), its normal, the path
+// length to it, and the number of continuations.  `hit` is the primary ray's.  The new ray is derived after the walk, from the record
+// (as shade_core does); what lives across a walk is thr, the length so far, the bounce count and the delta hit's normal (what a
+// continuation that misses reports).  Returns false when the sample is dropped (a non-finite component).
+template <uint32_t F, class Mem>
+VK_HD bool guide_sample(Lane &L, const DScene &S, const Mem &M, const RenderConsts &C, uint32_t max_bounces, float fuzz_max, uint32_t x,
+    uint32_t y, uint32_t sample, V3 &albedo, V3 &normal, float &depth, bool &hit, uint32_t &bounces) {
+    V3 o, d; float time;
+    start_sample_core(L, C, x, y, sample, o, d, time);
+    // What survives a walk — thr, len, the delta hit's normal, b — is parked in private memory (8 dwords, written where the next ray
+    // is derived and read after the walk, never inside it): in registers it costs the sphere-only kernel two waves per SIMD.  `volatile`
+    // is what keeps it there; the compiler turns these accesses into flat loads and stores to the private aperture at system scope,
+    // not scratch_* instructions.  A plain array between empty asm memory fences does give scratch_* accesses, but the fences cost
+    // registers elsewhere (78 VGPRs and 6 waves, 131 and 3 for the everything-variant), so it is not used.
+    volatile float park[8];
+    for (int i = 0; i < 8; i++) park[i] = i < 3 ? 1.0f : 0.0f;        // thr (1,1,1); len 0; normal (0,0,0); b 0
+    uint32_t b;
+    for (;;) {                                                // one begin_segment and one walk for the primary ray and the continuations
+        begin_segment<Mem::ISHIFT, fused_box<F, Mem>(), spheres_only<F>()>(L, S, o, d, time);
+        while (traversing(L)) traverse_step<F, Mem>(L, S, M);
+        const V3 thr = v3(park[0], park[1], park[2]);
+        const float len = park[3];
+        b = (uint32_t)park[7];
+        if (L.best_prim == 0u) {
+            // a primary miss (thr = 1, len = 0, normal = 0: vk_render_aov's miss), or a continuation's: the delta hit it left is the
+            // terminal surface, the parked normal is that hit's and len reaches it
+            albedo = thr * clamp01(background_of(C, C.background == VK_BACKGROUND_SKY ? unit(L.wd) : L.wd));
+            normal = v3(park[4], park[5], park[6]);
+            depth = len;
+            hit = b != 0u;
+            break;
+        }
+        hit = true;
+        Rec R;
+        build_record<F, Mem>(L, S, M, R);
+        const bool medium = (F & VKF_MEDIUM) && VKD_KIND(L.best_prim) == DK_MEDIUM;
+        const DMaterial &m = S.materials[R.mat];
+        const float seg = L.T * sqrtf(length2(L.wd));
+        const bool delta = !medium && (m.kind == VK_MAT_DIELECTRIC || (m.kind == VK_MAT_METAL && m.param <= fuzz_max));
+        if (!delta || b >= max_bounces) {                     // the terminal surface
+            albedo = thr * aov_albedo<F>(S, R.mat, R);
+            normal = medium ? v3s(0.0f) : R.n;
+            depth = len + seg;
+            break;
+        }
+        park[3] = len + seg;
+        const V3 ud = unit(L.wd);
+        if (m.kind == VK_MAT_METAL) {                         // material.rs:118-132 without the fuzz term
+            d = reflect(ud, R.n);
+            const V3 t2 = thr * material_color<F>(S, m, R, no_pre_turb());
+            park[0] = t2.x; park[1] = t2.y; park[2] = t2.z;
+        } else {                                              // material.rs:150-175 without the Schlick draw
+            float eta = R.front ? 1.0f / m.param : m.param;
+            float cos_theta = fminf(dot(-ud, R.n), 1.0f);
+            float sin_theta = sqrtf(1.0f - cos_theta * cos_theta);
+            d = (eta * sin_theta > 1.0f) ? reflect(ud, R.n) : refract(ud, R.n, eta);
+        }
+        o = R.p; time = L.time;
+        b += 1u;
+        park[4] = R.n.x; park[5] = R.n.y; park[6] = R.n.z; park[7] = (float)b;
+        if (F & VKF_MEDIUM) L.rng = guide_segment_rng(C.seed, L.pixel, L.sample, b);
+    }
+    bounces = b;
+    return finite3(albedo) && finite3(normal) && finite_f(depth);
+}
+
 }  // namespace vkd
 #endif

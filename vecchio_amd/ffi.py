@@ -156,6 +156,11 @@ class AdaptiveInfo(C.Structure):
     _fields_ = [("tiles_total", C.c_uint32), ("tiles_active", C.c_uint32), ("samples_rendered", C.c_uint64)]
 
 
+class GuideParams(C.Structure):
+    """vk_guide_params (vk_render_guides)"""
+    _fields_ = [("max_bounces", C.c_uint32), ("fuzz_max", C.c_float), ("flags", C.c_uint32)]
+
+
 class DenoiseParams(C.Structure):
     """vk_denoise_params (vk_denoise)"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("levels", C.c_uint32), ("normal_squarings", C.c_uint32),
@@ -245,6 +250,7 @@ DEVICE_SYMBOLS = [
     "vk_progress_create", "vk_progress_step", "vk_progress_step_device", "vk_progress_reset", "vk_progress_stderr",
     "vk_progress_get_info", "vk_progress_destroy", "vk_progress_set_adaptive", "vk_progress_tile_samples",
     "vk_render_aov", "vk_render_aov_device",
+    "vk_guide_default_params", "vk_render_guides", "vk_render_guides_device",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -312,6 +318,14 @@ def _bind(lib):
     lib.vk_render_aov_device.restype = C.c_int
     lib.vk_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_guide_default_params.restype = C.c_int
+    lib.vk_guide_default_params.argtypes = [C.POINTER(GuideParams)]
+    lib.vk_render_guides.restype = C.c_int
+    lib.vk_render_guides.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.POINTER(GuideParams)] + \
+        [C.c_void_p] * 5 + [C.POINTER(Stats)]
+    lib.vk_render_guides_device.restype = C.c_int
+    lib.vk_render_guides_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.POINTER(GuideParams)] + \
+        [C.c_void_p] * 6 + [C.POINTER(Stats)]
     lib.vk_denoise_default_params.restype = C.c_int
     lib.vk_denoise_default_params.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams)]
     lib.vk_denoise.restype = C.c_int

@@ -2,7 +2,7 @@
 // scene, build the BVH, upload once, then per Camera of cam_iter: render through the C ABI
 // (the call that replaces main.rs:181-198), write output_%04d.ppm, print the frame time.
 // The reference hard-codes scene/width/spp/depth (main.rs:28-29,159-167,171); here they are
-// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0]
+// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0] [guide_bounces=0]
 // steps > 1: each frame is rendered progressively (vk_progress_*) in `steps` equal sample windows; after each window the running image
 // is written to output_%04d_step%02d.ppm and the samples done and the image's mean relative standard error are printed.  The final
 // output_%04d.ppm is byte-identical to the one of steps = 1.
@@ -15,6 +15,10 @@
 // parameters); frame i is rendered with seed + 1 + i, so that the frames are independent, reprojected into the history and written as
 // output_%04d_temporal.ppm and .pfm; with denoise = 1 the denoised files are filtered from the accumulated colour and standard error.
 // With temporal = 0 the seed does not change and every file is what it was.
+// guide_bounces > 0 (needs aov_spp > 0; at most 8): the specular guides of the same samples (vk_render_guides, max_bounces = guide_bounces,
+// the other parameters the library's defaults) are written as output_%04d_guide_albedo.pfm, _guide_normal.pfm, _guide_depth.pfm and
+// _guide_bounces.pfm, and the temporal and denoise steps take their albedo, normal and depth from them instead of from the first-hit
+// buffers.  0 or absent: no such call is made and every file is what it was.
 // Texture images are read from ./assets (as in the reference) or $VECCHIO_ASSETS: <name>.ppm.gz, see host_api.h.
 #include <dlfcn.h>
 
@@ -47,7 +51,7 @@ static T sym(void *h, const char *name) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <balls_demo|random_spheres_demo|random_spheres_iow|perlin_demo|bowser_demo|cornell_box|final_scene|"
-                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal]\n", argv[0]);
+                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal] [guide_bounces]\n", argv[0]);
         return 2;
     }
     const char *name = argv[1];
@@ -60,6 +64,7 @@ int main(int argc, char **argv) {
     uint32_t aov_spp = argc > 8 ? (uint32_t)atoi(argv[8]) : 0;
     const bool denoise = argc > 9 && atoi(argv[9]) != 0;
     const bool temporal = argc > 10 && atoi(argv[10]) != 0;
+    const uint32_t guide_bounces = argc > 11 ? (uint32_t)atoi(argv[11]) : 0;
     if (steps < 1) steps = 1;
     if (steps > spp) steps = spp;                                     // every window holds at least one sample
     if (denoise && (steps < 2 || aov_spp == 0)) {
@@ -68,6 +73,10 @@ int main(int argc, char **argv) {
     }
     if (temporal && (steps < 2 || aov_spp == 0)) {
         fprintf(stderr, "temporal = 1 needs the standard error and the first-hit buffers: steps >= 2 and aov_spp > 0\n");
+        return 2;
+    }
+    if (guide_bounces > 0 && aov_spp == 0) {
+        fprintf(stderr, "guide_bounces > 0 renders the guides of the first-hit samples: aov_spp > 0\n");
         return 2;
     }
 
@@ -86,6 +95,9 @@ int main(int argc, char **argv) {
     auto p_pdestroy = sym<void (*)(vk_progress *)>(h, "vk_progress_destroy");
     auto p_aov = sym<int (*)(vk_scene *, const vk_camera *, const vk_render_params *, uint32_t, float *, float *, float *, float *, vk_stats *)>(
         h, "vk_render_aov");
+    auto p_gp_defaults = sym<int (*)(vk_guide_params *)>(h, "vk_guide_default_params");
+    auto p_guides = sym<int (*)(vk_scene *, const vk_camera *, const vk_render_params *, uint32_t, const vk_guide_params *, float *, float *,
+                                float *, float *, float *, vk_stats *)>(h, "vk_render_guides");
     auto p_dn_defaults = sym<int (*)(uint32_t, uint32_t, vk_denoise_params *)>(h, "vk_denoise_default_params");
     auto p_denoise = sym<int (*)(vk_scene *, const vk_denoise_params *, const float *, const float *, const float *, const float *, const float *,
                                  float *, vk_stats *)>(h, "vk_denoise");
@@ -172,13 +184,35 @@ int main(int argc, char **argv) {
                 if (!write_pfm(pfn, o.data, width, height, o.ch)) return 1;
             }
             fprintf(stderr, "  first-hit buffers of %u samples per pixel: kernel %.2f ms\n", aov_spp, as.kernel_ms);
+            // what the temporal and denoise steps are guided by: the first-hit buffers, or the specular guides
+            const float *g_albedo = albedo.data(), *g_normal = normal.data(), *g_depth = zdepth.data();
+            std::vector<float> galbedo, gnormal, gdepth, gbounces;
+            if (guide_bounces > 0) {
+                galbedo.resize(np * 3); gnormal.resize(np * 3); gdepth.resize(np); gbounces.resize(np);
+                vk_guide_params gp;
+                vk_stats gs{};
+                if (p_gp_defaults(&gp) != VK_OK) { fprintf(stderr, "vk_guide_default_params: %s\n", p_err()); return 1; }
+                gp.max_bounces = guide_bounces;
+                if (p_guides(scene, &cam, &ap, 0, &gp, galbedo.data(), gnormal.data(), gdepth.data(), nullptr, gbounces.data(), &gs) != VK_OK) {
+                    fprintf(stderr, "vk_render_guides: %s\n", p_err()); return 1; }
+                const struct { const char *suffix; const float *data; int ch; } gouts[] = {
+                    {"_guide_albedo", galbedo.data(), 3}, {"_guide_normal", gnormal.data(), 3}, {"_guide_depth", gdepth.data(), 1},
+                    {"_guide_bounces", gbounces.data(), 1}};
+                for (const auto &o : gouts) {
+                    char pfn[64];
+                    snprintf(pfn, sizeof pfn, "output_%04d%s.pfm", file_idx, o.suffix);
+                    if (!write_pfm(pfn, o.data, width, height, o.ch)) return 1;
+                }
+                fprintf(stderr, "  specular guides, at most %u bounces: kernel %.2f ms\n", guide_bounces, gs.kernel_ms);
+                g_albedo = galbedo.data(); g_normal = gnormal.data(); g_depth = gdepth.data();
+            }
             const float *dn_color = pixels.data(), *dn_err = err.data();
             std::vector<float> acc, acc_err;
             if (temporal) {
                 acc.resize(np * 3); acc_err.resize(np * 3);
                 vk_stats ts{};
                 vk_temporal_info ti{};
-                if (p_taccum(history, &cam, pixels.data(), err.data(), albedo.data(), normal.data(), zdepth.data(), acc.data(), acc_err.data(),
+                if (p_taccum(history, &cam, pixels.data(), err.data(), g_albedo, g_normal, g_depth, acc.data(), acc_err.data(),
                              nullptr, &ts) != VK_OK || p_tinfo(history, &ti) != VK_OK) {
                     fprintf(stderr, "vk_temporal_accumulate: %s\n", p_err()); return 1; }
                 char tfn[64];
@@ -195,7 +229,7 @@ int main(int argc, char **argv) {
                 std::vector<float> clean(np * 3);
                 vk_stats ds{};
                 if (p_dn_defaults(width, height, &dp) != VK_OK ||
-                    p_denoise(scene, &dp, dn_color, dn_err, albedo.data(), normal.data(), zdepth.data(), clean.data(), &ds) != VK_OK) {
+                    p_denoise(scene, &dp, dn_color, dn_err, g_albedo, g_normal, g_depth, clean.data(), &ds) != VK_OK) {
                     fprintf(stderr, "vk_denoise: %s\n", p_err()); return 1; }
                 char dfn[64];
                 snprintf(dfn, sizeof dfn, "output_%04d_denoised.ppm", file_idx);

@@ -91,6 +91,9 @@ pub struct vk_adaptive_info { pub tiles_total: u32, pub tiles_active: u32, pub s
 pub struct vk_denoise_params { pub width: u32, pub height: u32, pub levels: u32, pub normal_squarings: u32, pub sigma_l: f32, pub sigma_z: f32, pub albedo_floor: f32, pub flags: u32 }
 
 #[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_guide_params { pub max_bounces: u32, pub fuzz_max: f32, pub flags: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_temporal_params { pub width: u32, pub height: u32, pub max_history: u32, pub depth_tol: f32, pub normal_cos_min: f32, pub albedo_floor: f32, pub flags: u32 }
 
 #[repr(C)] #[derive(Copy, Clone, Default)]
@@ -131,6 +134,15 @@ extern "C" {
     pub fn vk_render_aov_device(scene: *mut vk_scene, cam: *const vk_camera, params: *const vk_render_params, first_sample: u32,
                                 d_albedo: *mut c_void, d_normal: *mut c_void, d_depth: *mut c_void, d_coverage: *mut c_void,
                                 hip_stream: *mut c_void, stats_out: *mut vk_stats) -> c_int;
+    // specular guides (additive symbols of ABI 7): the first-hit buffers followed through mirrors and glass; any of the five may be null
+    pub fn vk_guide_default_params(out: *mut vk_guide_params) -> c_int;
+    pub fn vk_render_guides(scene: *mut vk_scene, cam: *const vk_camera, params: *const vk_render_params, first_sample: u32,
+                            gp: *const vk_guide_params, albedo: *mut f32, normal: *mut f32, depth: *mut f32, coverage: *mut f32,
+                            bounces: *mut f32, stats_out: *mut vk_stats) -> c_int;
+    pub fn vk_render_guides_device(scene: *mut vk_scene, cam: *const vk_camera, params: *const vk_render_params, first_sample: u32,
+                                   gp: *const vk_guide_params, d_albedo: *mut c_void, d_normal: *mut c_void, d_depth: *mut c_void,
+                                   d_coverage: *mut c_void, d_bounces: *mut c_void, hip_stream: *mut c_void,
+                                   stats_out: *mut vk_stats) -> c_int;
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

@@ -130,6 +130,49 @@ class DeviceScene:
                                                         C.c_void_p(d_coverage or None), C.c_void_p(stream or 0), C.byref(stats)))
         return stats
 
+    GUIDE_CHANNELS = AOV_CHANNELS + ("bounces",)
+
+    def guide_params(self, **overrides):
+        """The library's default vk_guide_params (max_bounces 4, fuzz_max 0), with fields overridden by keyword."""
+        gp = ffi.GuideParams()
+        check(self._lib, self._lib.vk_guide_default_params(C.byref(gp)))
+        for k, v in overrides.items():
+            if k not in dict(ffi.GuideParams._fields_):
+                raise ValueError(f"unknown vk_guide_params field {k!r}")
+            setattr(gp, k, v)
+        return gp
+
+    def render_guides(self, cam, params, first_sample=0, guide=None, want=GUIDE_CHANNELS, out=None):
+        """Specular guides of samples [first_sample, first_sample + params.samples_per_pixel) (vk_render_guides): render_aov()'s
+        buffers followed through mirrors and glass to the first rough surface, plus 'bounces' (height, width), the mean number of
+        continuations.  guide: a vk_guide_params (guide_params()), default = the library's.  Returns (dict, vk_stats)."""
+        want = tuple(want)
+        unknown = set(want) - set(self.GUIDE_CHANNELS)
+        if unknown or not want:
+            raise ValueError(f"want must be a non-empty subset of {self.GUIDE_CHANNELS}, got {want}")
+        gp = guide if guide is not None else self.guide_params()
+        bufs = dict(out or {})
+        for ch in want:
+            shape = (params.height, params.width, 3) if ch in ("albedo", "normal") else (params.height, params.width)
+            if ch not in bufs:
+                bufs[ch] = np.zeros(shape, dtype=np.float32)
+            assert bufs[ch].dtype == np.float32 and bufs[ch].flags.c_contiguous
+        ptrs = [C.c_void_p(bufs[ch].ctypes.data) if ch in want else None for ch in self.GUIDE_CHANNELS]
+        stats = ffi.Stats()
+        check(self._lib, self._lib.vk_render_guides(self._h, C.byref(cam), C.byref(params), first_sample, C.byref(gp), *ptrs,
+                                                    C.byref(stats)))
+        return {ch: bufs[ch] for ch in want}, stats
+
+    def render_guides_device(self, cam, params, first_sample, guide=None, d_albedo=0, d_normal=0, d_depth=0, d_coverage=0, d_bounces=0,
+                             stream=None):
+        """Enqueue the specular guides into device memory (vk_render_guides_device, no host sync); a 0 pointer = not wanted."""
+        gp = guide if guide is not None else self.guide_params()
+        stats = ffi.Stats()
+        ptrs = [C.c_void_p(p or None) for p in (d_albedo, d_normal, d_depth, d_coverage, d_bounces)]
+        check(self._lib, self._lib.vk_render_guides_device(self._h, C.byref(cam), C.byref(params), first_sample, C.byref(gp), *ptrs,
+                                                           C.c_void_p(stream or 0), C.byref(stats)))
+        return stats
+
     def denoise_params(self, width, height, **overrides):
         """vk_denoise_default_params for a width x height image, with fields overridden by keyword (levels=, sigma_l=, ...)"""
         dp = ffi.DenoiseParams()
