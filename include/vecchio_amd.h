@@ -562,6 +562,60 @@ int vk_render_guides_device(vk_scene *scene, const vk_camera *cam, const vk_rend
                             const vk_guide_params *gp, void *d_albedo, void *d_normal, void *d_depth, void *d_coverage, void *d_bounces,
                             void *hip_stream, vk_stats *stats_out);
 
+/* ---- ray queries: closest hits for caller-supplied rays (additive symbols of ABI 7) -------------------------------------------------
+ * replaces: world.hit(&ray, 0.001, tmax) of main.rs:130, for rays the CALLER supplies (autofocus, picking, collision of an orbiting
+ * camera, visibility probes, a wavefront integrator of the caller's own).  Ray i of the batch gives the result of
+ * BVHNode::hit(&Ray{origin, direction, time}, 0.001, tmax) (accel.rs:58-83), everything f32 and unfused in the reference's order.
+ *   Tree view.  The one vk_render_aov walks: the tree AS HANDED OVER, also where vk_render walks a grid, a near or a unit form; under
+ *     VK_SCENE_FAST_ACCEL the rebuilt tree (ties as the reference breaks them).
+ *   tmin is 0.001 (VK_RAY_TMIN) for every ray, as at every call site of the reference; there is no per-ray tmin.
+ *   tmax.  The closest-so-far distance starts at the ray's tmax instead of infinity.  With nothing accepted yet a Rect at exactly tmax is
+ *     accepted (hittable.rs:232 rejects `t > tmax` only) and a Sphere, a MovingSphere or a Boxy / list is not (hittable.rs:75, :386).  A
+ *     ray whose tmax is a NaN or <= VK_RAY_TMIN misses without a walk.  +INFINITY is main.rs:130's call.
+ *   Media.  A ConstantMedium met by ray i draws from the stream rng_for_sample(seed + 0x9E3779B97F4A7C15 * (first_index + i), 0, 0), in
+ *     wrapping u64: one fresh stream per ray.  A batch cut into pieces whose first_index continue each other gives the same bytes.
+ *   The record of a hit is the reference's HitRec in world space: p, normal (face-oriented, set_face_normal), t, u, v (Sphere and
+ *     MovingSphere: get_sphere_uv, always; Rect and Boxy faces: the rect's; a medium: its boundary's entry hit's), front; `material` the
+ *     description's material index; `medium` = 1 when ConstantMedium::hit filled the record (normal (1,0,0), front 1).  `object` names the
+ *     record of the description whose own hit() produced the winner, as a vk_ref with the flip bit clear: VK_KIND_SPHERE,
+ *     VK_KIND_MOVING_SPHERE or VK_KIND_RECT and its index — for a face of a Boxy the vk_rect of that side of its list — or, for a medium
+ *     hit, VK_KIND_MEDIUM and the vk_medium's index.
+ *   A miss: hit = 0, t = +INFINITY, every other field 0.
+ *   Non-finite rays are the reference's: a NaN or infinite component passes every AxisBB::hit (f32::min / max drop the NaN quotients)
+ *     and fails every Sphere::hit, so in a world of spheres the ray misses (without a walk).  Rect::hit rejects with `<` and `>` only, which
+ *     a NaN passes: such a ray can "hit" a Rect with a NaN t, here as there.  direction is not normalised and may be zero (a miss on
+ *     spheres).
+ *   Arguments: VK_ERR_BAD_ARG with nothing enqueued and the outputs untouched for a null scene or params, null rays or hits with n_rays
+ *     > 0, flags != 0, n_rays > 2^32.  n_rays == 0: VK_OK, nothing done (stats_out zeroed).
+ *   Scene state: vk_render_aov's rules.  The call is the scene's one render in flight; it touches nothing that describes vk_render's last
+ *     frame and no vk_progress or vk_temporal handle.  A multi-device scene runs the call on devices[0].  stats_out: samples = n_rays,
+ *     kernel_ms (vk_trace_rays only: summed over its chunks), kernel_launches, scene_in_lds = 0.
+ *   vk_trace_rays stages rays and hits through scratch of the scene handle (allocated on first use, regrown, at most 2^20 rays at a time:
+ *     longer batches run in chunks, which first_index makes invisible).  The first ray query of a scene also uploads the tables that map
+ *     device primitives back to the description (4 bytes per sphere, moving sphere, rect and medium, 24 per Boxy).                    */
+#define VK_RAY_TMIN 0.001f            /* the reference's tmin at every call site (main.rs:130) */
+typedef struct vk_ray {               /* 32 bytes */
+    float origin[3]; float tmax;
+    float direction[3]; float time;   /* not normalised, as Ray (main.rs:32-36) */
+} vk_ray;
+typedef struct vk_hit {               /* 64 bytes */
+    float p[3]; float t;
+    float normal[3]; float u;
+    float v; uint32_t hit; uint32_t front; uint32_t material;
+    vk_ref object; uint32_t medium; uint32_t _pad[2];
+} vk_hit;
+typedef struct vk_trace_params {
+    uint64_t seed;               /* of the media's streams */
+    uint64_t first_index;        /* index of rays[0] in the caller's batch */
+    uint32_t flags;              /* 0 */
+    uint32_t _pad;
+} vk_trace_params;
+int vk_trace_rays(vk_scene *scene, const vk_trace_params *params, const vk_ray *rays, uint64_t n_rays, vk_hit *hits,
+                  vk_stats *stats_out);
+/* device buffers on the scene's device (devices[0] of a multi-device scene), 16-byte aligned, enqueued on hip_stream, no host wait */
+int vk_trace_rays_device(vk_scene *scene, const vk_trace_params *params, const void *d_rays, uint64_t n_rays, void *d_hits,
+                         void *hip_stream, vk_stats *stats_out);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

@@ -195,7 +195,8 @@ def build_emu(force=False):
     """Test-only host build of the kernel's per-lane logic (tests/emu)."""
     edir = os.path.join(ROOT, "tests", "emu")
     out = os.path.join(edir, "_build", "libemu.so")
-    srcs = [os.path.join(edir, "emu.cpp"), os.path.join(edir, "emu_guides.cpp"), os.path.join(CSRC, "vk_linearize.cpp")]
+    srcs = [os.path.join(edir, "emu.cpp"), os.path.join(edir, "emu_guides.cpp"), os.path.join(edir, "emu_rays.cpp"),
+            os.path.join(CSRC, "vk_linearize.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h")]
     if force or _newer(out, deps, CXXFLAGS):

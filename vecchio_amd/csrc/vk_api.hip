@@ -258,6 +258,11 @@ struct vk_scene {
     // vk_render_aov: its own events and output buffers, so that nothing that describes vk_render's last frame is touched
     hipEvent_t aov_ev0 = nullptr, aov_ev1 = nullptr;
     float *aov_buf = nullptr; size_t aov_bytes = 0;
+    // vk_trace_rays: the provenance tables (uploaded by the scene's first ray query), the staging buffer of the host variant (rays, then
+    // hits) and its events
+    bool prov_ready = false; DProvenance prov = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    uint8_t *ray_buf = nullptr; size_t ray_bytes = 0;
+    hipEvent_t ray_ev0 = nullptr, ray_ev1 = nullptr;
     // vk_denoise: the filter's scratch (two ping-pong images, the packed guides, the depth slopes), the device copies of vk_denoise's
     // host images, its own events (before the prepare kernel, behind it, behind every level), the levels of the last timed call and the
     // form the level kernels are launched in (vk_debug_denoise_form)
@@ -1045,13 +1050,13 @@ void destroy_one(vk_scene *s) {
     for (void *p : {(void *)s->counter, (void *)s->fb, (void *)s->fb8, (void *)s->accum, (void *)s->debug, (void *)s->phase_stats,
         (void *)s->tile_cost,
                     (void *)s->tile_order, (void *)s->order_hist, (void *)s->slab, (void *)s->redo_list, (void *)s->redo_count,
-                    (void *)s->aov_buf, (void *)s->dn_buf, (void *)s->dn_io})
+                    (void *)s->aov_buf, (void *)s->dn_buf, (void *)s->dn_io, (void *)s->ray_buf})
         if (p) (void)hipFree(p);
     for (hipEvent_t e : s->dn_ev) if (e) (void)hipEventDestroy(e);
     if (s->plan_host) (void)hipHostFree(s->plan_host);
     if (s->landing) { (void)hipSetDevice(s->landing_device); (void)hipFree(s->landing); (void)hipSetDevice(s->device); }
     for (hipEvent_t e : {s->ev0, s->ev1, s->ev_landed, s->ev_begin, s->ev_fork, s->ev_join, s->ev_plan[0], s->ev_plan[1], s->aov_ev0,
-                         s->aov_ev1})
+                         s->aov_ev1, s->ray_ev0, s->ray_ev1})
         if (e) (void)hipEventDestroy(e);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     if (s->stream2) (void)hipStreamDestroy(s->stream2);
@@ -1784,6 +1789,114 @@ int vk_render_guides_device(vk_scene *scene, const vk_camera *cam, const vk_rend
         rc = enqueue_aov(q, cam, params, first_sample, dev, reinterpret_cast<hipStream_t>(hip_stream), false, gp, dev[4]);
         if (rc != VK_OK) return rc;
         if (stats_out) aov_stats(params, stats_out);
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- ray queries (vk_trace_rays): trace_rays_kernel on the tree view of the first-hit buffers (aov_view), on the scene's device
+// (devices[0] of a multi-device scene), with events and a staging buffer of its own: nothing that describes vk_render's last frame is
+// read or written.
+namespace {
+
+constexpr uint64_t RAY_CHUNK = 1ull << 20;      // rays staged at a time by the host variant (96 MiB of scratch)
+
+int check_trace_args(vk_scene *scene, const vk_trace_params *tp, const void *rays, uint64_t n_rays, const void *hits) {
+    if (!scene || !tp) return fail(VK_ERR_BAD_ARG, "null argument (scene or trace parameters)");
+    if (tp->flags != 0u) return fail(VK_ERR_BAD_ARG, "trace flags must be 0");
+    if (n_rays > (1ull << 32)) return fail(VK_ERR_BAD_ARG, "n_rays exceeds 2^32");
+    if (n_rays != 0u && (!rays || !hits)) return fail(VK_ERR_BAD_ARG, "null rays or hits with n_rays > 0");
+    return VK_OK;
+}
+
+// the provenance tables, on the device with the scene's first ray query (freed with the scene's other uploads)
+int ensure_provenance(vk_scene *q) {
+    if (q->prov_ready) return VK_OK;
+    const LinearScene &H = *q->host;
+    int rc;
+    if ((rc = upload(q, H.src_sphere, q->prov.sphere)) != VK_OK) return rc;
+    if ((rc = upload(q, H.src_moving, q->prov.moving)) != VK_OK) return rc;
+    if ((rc = upload(q, H.src_rect, q->prov.rect)) != VK_OK) return rc;
+    if ((rc = upload(q, H.src_box_face, q->prov.box_face)) != VK_OK) return rc;
+    if ((rc = upload(q, H.src_medium, q->prov.medium)) != VK_OK) return rc;
+    q->prov_ready = true;
+    return VK_OK;
+}
+
+// one launch for rays [0, n) of d_rays, whose first ray is ray `first_index` of the caller's batch
+int enqueue_trace(vk_scene *q, const vk_trace_params *tp, uint64_t first_index, const void *d_rays, uint64_t n, void *d_hits, hipStream_t st) {
+    TraceArgs A;
+    memset(&A, 0, sizeof(A));
+    A.S = aov_view(q);
+    if (A.S.grid.nu != 0u || A.S.t_pad != 0.0f || A.S.walk_start != 0u || A.S.gate_scale != 1.0f || A.S.primary_ref != 0u)
+        return fail(VK_ERR_BAD_ARG, "internal error: a ray query needs a tree view without the rebuilt forms' gates");
+    A.P = q->prov;
+    A.rays = static_cast<const float4 *>(d_rays); A.hits = static_cast<uint4 *>(d_hits);
+    A.seed = tp->seed; A.first_index = first_index; A.n_rays = n;
+    const dim3 grid((uint32_t)((n + AOV_BLOCK - 1) / AOV_BLOCK));
+    // as enqueue_aov chooses: a sphere-only world the fused sphere path, anything else the everything-variant
+    if (q->host->features == 0u) hipLaunchKernelGGL(trace_rays_kernel<0u>, grid, dim3(AOV_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL(trace_rays_kernel<(uint32_t)VKF_ALL_SCENE>, grid, dim3(AOV_BLOCK), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_trace_rays(vk_scene *scene, const vk_trace_params *params, const vk_ray *rays, uint64_t n_rays, vk_hit *hits, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        int rc = check_trace_args(scene, params, rays, n_rays, hits);
+        if (rc != VK_OK) return rc;
+        if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
+        if (n_rays == 0u) return VK_OK;
+        const auto t0 = std::chrono::steady_clock::now();
+        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        HIP_TRY(hipSetDevice(q->device));
+        if ((rc = ensure_provenance(q)) != VK_OK) return rc;
+        const uint64_t cap = n_rays < RAY_CHUNK ? n_rays : RAY_CHUNK;
+        if ((rc = ensure(q->ray_buf, q->ray_bytes, (size_t)cap * (sizeof(vk_ray) + sizeof(vk_hit)))) != VK_OK) return rc;
+        if (!q->ray_ev0) HIP_TRY(hipEventCreate(&q->ray_ev0));
+        if (!q->ray_ev1) HIP_TRY(hipEventCreate(&q->ray_ev1));
+        // (the buffer may be larger than this call needs: the hits start behind THIS call's rays)
+        uint8_t *d_rays = q->ray_buf, *d_hits = q->ray_buf + (size_t)cap * sizeof(vk_ray);
+        double ms_sum = 0.0;
+        uint64_t launches = 0;
+        for (uint64_t at = 0; at < n_rays; at += cap) {
+            const uint64_t n = n_rays - at < cap ? n_rays - at : cap;
+            HIP_TRY(hipMemcpy(d_rays, rays + at, (size_t)n * sizeof(vk_ray), hipMemcpyHostToDevice));
+            HIP_TRY(hipEventRecord(q->ray_ev0, nullptr));
+            if ((rc = enqueue_trace(q, params, params->first_index + at, d_rays, n, d_hits, nullptr)) != VK_OK) return rc;
+            HIP_TRY(hipEventRecord(q->ray_ev1, nullptr));
+            HIP_TRY(hipEventSynchronize(q->ray_ev1));
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, q->ray_ev0, q->ray_ev1));
+            ms_sum += (double)ms; launches++;
+            HIP_TRY(hipMemcpy(hits + at, d_hits, (size_t)n * sizeof(vk_hit), hipMemcpyDeviceToHost));
+        }
+        if (stats_out) {
+            stats_out->samples = n_rays; stats_out->kernel_ms = ms_sum; stats_out->kernel_launches = (uint32_t)launches;
+            stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return VK_OK;
+    });
+}
+
+int vk_trace_rays_device(vk_scene *scene, const vk_trace_params *params, const void *d_rays, uint64_t n_rays, void *d_hits, void *hip_stream,
+    vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        int rc = check_trace_args(scene, params, d_rays, n_rays, d_hits);
+        if (rc != VK_OK) return rc;
+        if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
+        if (n_rays == 0u) return VK_OK;
+        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        HIP_TRY(hipSetDevice(q->device));
+        if ((rc = ensure_provenance(q)) != VK_OK) return rc;
+        if ((rc = enqueue_trace(q, params, params->first_index, d_rays, n_rays, d_hits, reinterpret_cast<hipStream_t>(hip_stream))) != VK_OK)
+            return rc;
+        if (stats_out) { stats_out->samples = n_rays; stats_out->kernel_launches = 1u; }
         return VK_OK;
     });
 }

@@ -169,6 +169,11 @@ struct DScene {
     const uint32_t *unit_item; const DItem *unit_tree;
 };
 
+// Provenance (vk_trace_rays' `object`; filled by the lineariser, uploaded on a scene's first ray query — no other kernel sees it): the
+// description index of every device sphere, moving sphere, rect and medium record, and of the vk_rect behind each face of a DBox
+// (box_face[box * 6 + face]).
+struct DProvenance { const uint32_t *sphere, *moving, *rect, *box_face, *medium; };
+
 // A view that walks the grid (grid.nu != 0) instead of the rebuilt tree: the grid form is sound for every ordinary ray wherever it
 // starts, so the tree forms' conditions — the trusted ball, the near form's reach — do not apply (vk_trace.h segment_unsafe keeps the
 // safe-winner test).  A view that walks the TREE of a world that also has a grid must keep them: drop_grid().

@@ -1241,6 +1241,34 @@ __global__ __launch_bounds__(AOV_BLOCK) void specular_guides_kernel(GuideArgs G)
     if (G.bounces) G.bounces[pix] = (float)sb / fn;
 }
 
+// ---- ray queries (vk_trace_rays): vk_trace.h trace_ray for rays read from memory, one ray per lane, 64 consecutive rays per wave.  A
+// lane reads its vk_ray as two 16-byte loads and writes its vk_hit as four 16-byte stores.  No LDS, no atomics: ray i's result depends
+// on (scene, ray i, seed, first_index + i) alone.  The walk is aov_kernel's, on the same tree view.
+struct TraceArgs {
+    DScene S;                // a tree view (vk_api.hip aov_view)
+    DProvenance P;
+    const float4 *rays;      // vk_ray[n_rays]
+    uint4 *hits;             // vk_hit[n_rays]
+    uint64_t seed, first_index, n_rays;
+};
+template <uint32_t F>
+__global__ __launch_bounds__(AOV_BLOCK) void trace_rays_kernel(TraceArgs A) {
+    const uint64_t i = (uint64_t)blockIdx.x * AOV_BLOCK + threadIdx.x;
+    if (i >= A.n_rays) return;
+    const float4 r0 = A.rays[i * 2u], r1 = A.rays[i * 2u + 1u];
+    const GlobalMem M{A.S.items, A.S.spheres, A.S.sphere_mat, A.S.boxes};
+    Lane L;
+    RayHit H;
+    trace_ray<F, GlobalMem>(L, A.S, M, A.P, v3(r0.x, r0.y, r0.z), v3(r1.x, r1.y, r1.z), r1.w, r0.w, ray_seed(A.seed, A.first_index + i), H);
+    uint32_t w[16];
+    hit_words(H, w);
+    uint4 *out = A.hits + i * 4u;
+    out[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    out[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    out[2] = make_uint4(w[8], w[9], w[10], w[11]);
+    out[3] = make_uint4(w[12], w[13], w[14], w[15]);
+}
+
 // ---- tile slabs: the pixels of one tile partition (tiles t = rank + i*world, i = 0..n_local) packed tile by tile,
 // 64 pixel slots per tile, 3 components per slot.  A multi-device scene moves one slab per device to devices[0]
 // (the path's only exchange) and de-interleaves it there; RGB8 output packs bytes (to_color fused: 4x less traffic).

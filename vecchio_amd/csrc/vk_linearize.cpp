@@ -50,6 +50,10 @@ DScene LinearScene::host_view() const {
     return s;
 }
 
+DProvenance LinearScene::host_provenance() const {
+    return DProvenance{src_sphere.data(), src_moving.data(), src_rect.data(), src_box_face.data(), src_medium.data()};
+}
+
 std::vector<DItem> LinearScene::combined_items(uint32_t &walk_start) const {
     const uint32_t n_ref = (uint32_t)ref_items.size(), n_new = (uint32_t)items.size(), total = n_ref + 1u + n_new;
     std::vector<DItem> out;
@@ -215,6 +219,7 @@ struct Builder {
         DBox b; memset(&b, 0, sizeof(b));
         b.p0[0] = p0x; b.p0[1] = p0y; b.p0[2] = p0z; b.p1x = p1x; b.p1y = p1y; b.p1z = p1z; b.mat = q[0]->material;
         L.boxes.push_back(b);
+        for (int f = 0; f < 6; f++) L.src_box_face.push_back(VK_REF_INDEX(d->list_items[l.first + f]));
         L.features |= VKF_BOX;
         out = (uint32_t)L.boxes.size() - 1;
         box_memo[idx] = out;
@@ -237,6 +242,7 @@ struct Builder {
         } else return fail(VK_ERR_UNSUPPORTED, "device path: ConstantMedium boundary must be a Sphere, MovingSphere, Rect or Boxy");
         dm.neg_inv_density = m.neg_inv_density; dm.mat = m.material;
         L.media.push_back(dm);
+        L.src_medium.push_back(idx);
         L.features |= VKF_MEDIUM;
         out = (uint32_t)L.media.size() - 1;
         medium_memo[idx] = out;
@@ -1301,6 +1307,7 @@ struct Builder {
             if (s.material >= d->n_materials) return fail(VK_ERR_BAD_ARG, "material index out of range");
             L.spheres.push_back(DSphere{s.center[0], s.center[1], s.center[2], s.radius});
             L.sphere_mat.push_back(s.material);
+            L.src_sphere.push_back(i);
             const DMaterial &sm = L.materials[s.material];
             // (tex_kind is only set for materials that read a texture)
             if (sm.tex_kind == VK_TEX_NOISE && L.n_noise_spheres != 0xFFFFFFFFu) {
@@ -1318,6 +1325,7 @@ struct Builder {
             for (int k = 0; k < 3; k++) { m.c0[k] = s.center0[k]; m.c1[k] = s.center1[k]; }
             m.t0 = s.time0; m.t1 = s.time1; m.r = s.radius; m.mat = s.material;
             L.moving.push_back(m);
+            L.src_moving.push_back(i);
         }
         for (uint32_t i = 0; i < d->n_rects; i++) {
             const vk_rect &s = d->rects[i];
@@ -1327,6 +1335,7 @@ struct Builder {
             q.c0 = s.c0; q.c1 = s.c1; q.d0 = s.d0; q.d1 = s.d1; q.k = s.k;
             q.axes = (uint32_t)s.axis0 | ((uint32_t)s.axis1 << 2) | ((uint32_t)s.axis2 << 4); q.mat = s.material;
             L.rects.push_back(q);
+            L.src_rect.push_back(i);
         }
         if (!check_ref(d->world)) return false;
         if (VK_REF_KIND(d->world) == VK_KIND_BVH) {

@@ -54,11 +54,15 @@ struct LinearScene {
     // the GRID form (DGrid): grid.nu != 0 when the world is eligible (vk_linearize.cpp rt_build_grid)
     DGrid grid = {};
     std::vector<uint32_t> grid_cells, grid_refs;
+    // provenance (vk_trace_rays' `object`): the description index every device primitive came from — per sphere, moving sphere, rect and
+    // medium record, and per face of a DBox the vk_rect of that side of its list (6 per box, DBox's face order)
+    std::vector<uint32_t> src_sphere, src_moving, src_rect, src_box_face, src_medium;
     uint32_t features = 0;
     uint32_t n_prims = 0;
     uint32_t world_items = 0;   // items[0, world_items) is the world BVH; instance child ranges follow
 
     DScene host_view() const;   // DScene whose pointers address these vectors
+    DProvenance host_provenance() const;   // likewise
     // exact re-treeing, for a scene traversed from global memory: [ref_items | sentinel | items] in one array (see DScene::walk_start)
     std::vector<DItem> combined_items(uint32_t &walk_start) const;
 };

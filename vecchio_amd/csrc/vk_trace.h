@@ -412,8 +412,10 @@ VK_HD bool origin_untrusted(const DScene &S, V3 o) {
 VK_HD void grid_begin(Lane &L, const DScene &S);
 // redo (exact re-treeing of a scene traversed from global memory, DScene::walk_start != 0): this lane walks the tree as handed over,
 // items[0, walk_start - 1), on unscaled distances
+// t0: the closest-so-far distance the walk starts with (positive, not a NaN): +inf at every call site of the reference's ray_color; a ray
+// query's tmax (trace_ray)
 template <uint32_t ISHIFT = 0, bool FUSED = false, bool TIGHT = FUSED>
-VK_HD void begin_segment(Lane &L, const DScene &S, V3 o, V3 d, float time, bool redo = false) {
+VK_HD void begin_segment(Lane &L, const DScene &S, V3 o, V3 d, float time, bool redo = false, float t0 = INFINITY) {
     L.wo = o; L.wd = d; L.time = time;
     // (both trees in items[]: a segment that starts outside the trusted ball is the handed-over tree's from the start — segment_unsafe
     // would send it there after a wasted walk)
@@ -426,7 +428,7 @@ VK_HD void begin_segment(Lane &L, const DScene &S, V3 o, V3 d, float time, bool 
     // the grid form: refs[0, n_always) first (a segment walked again — scenes in global memory keep the tree as handed over in items[],
     // walk_start = its length — walks that tree instead)
     if (TIGHT && S.grid.nu != 0u && !redo) grid_begin(L, S);
-    L.T = INFINITY; L.best_prim = 0; L.best_inst = -1; L.best_aux = 0.0f;
+    L.T = t0; L.best_prim = 0; L.best_inst = -1; L.best_aux = 0.0f;
     // A ray with a NaN (or infinite) direction or origin hits EVERY box — f32::min/max drop the NaN quotients, accel.rs:21-31 —
     // and no sphere: Sphere::hit's discriminant is NaN (hittable.rs:66-70).  The reference walks its whole tree for such a ray
     // and returns None; in a scene of spheres only (nothing draws during traversal) the walk has no other effect, so it is
@@ -1000,7 +1002,8 @@ VK_HD bool mat_wants_uv(const DMaterial &m) {
     return m.kind == VK_MAT_SPEC_DIFFUSE || (m.kind != VK_MAT_DIELECTRIC && (m.tex_kind == VK_TEX_IMAGE || m.tex_kind == VK_TEX_CHECKER));
 }
 
-template <uint32_t F, class Mem>
+// ALL_UV: u and v as the reference's HitRec always has them (a ray query's record), not only where the material reads them
+template <uint32_t F, class Mem, bool ALL_UV = false>
 VK_HD void build_record(const Lane &L, const DScene &S, const Mem &M, Rec &R) {
     V3 o = L.wo, d = L.wd;
     if (F & VKF_INSTANCE) ray_in_instance(S, L.best_inst, L.wo, L.wd, o, d);
@@ -1013,7 +1016,7 @@ VK_HD void build_record(const Lane &L, const DScene &S, const Mem &M, Rec &R) {
         R.front = true;
         R.mat = m.mat;
         R.u = 0.0f; R.v = 0.0f;
-        if ((F & VKF_TEXTURES) && mat_wants_uv(S.materials[m.mat])) {   // rec1.u, rec1.v of the boundary's entry hit
+        if (ALL_UV || ((F & VKF_TEXTURES) && mat_wants_uv(S.materials[m.mat]))) {   // rec1.u, rec1.v of the boundary's entry hit
             float a = length2(d), t1; uint32_t it;
             if (boundary_t(S, M, m.boundary, o, d, a, L.time, -INFINITY, INFINITY, t1, it)) {
                 Rec B;
@@ -1029,8 +1032,8 @@ VK_HD void build_record(const Lane &L, const DScene &S, const Mem &M, Rec &R) {
         if (f & 1u) R.front = !R.front;              // odd sides are FlipFace-wrapped (hittable.rs:327-352)
         if (ref & DREF_FLIP) R.front = !R.front;
     } else {
-        bool want_uv = false;
-        if (F & VKF_TEXTURES) {
+        bool want_uv = ALL_UV;
+        if (!ALL_UV && (F & VKF_TEXTURES)) {
             uint32_t mi = (k == DK_SPHERE) ? M.smat(VKD_INDEX(ref))
                                            : (k == DK_RECT ? S.rects[VKD_INDEX(ref)].mat : S.moving[VKD_INDEX(ref)].mat);
             want_uv = mat_wants_uv(S.materials[mi]);
@@ -1635,6 +1638,41 @@ VK_HD bool guide_sample(Lane &L, const DScene &S, const Mem &M, const RenderCons
     }
     bounces = b;
     return finite3(albedo) && finite3(normal) && finite_f(depth);
+}
+
+// ------------------------------------------------------------------ ray queries (vk_trace_rays, include/vecchio_amd.h)
+struct RayHit { Rec R; float t; uint32_t hit, object, medium; };
+// the stream a ConstantMedium met by ray `index` of a batch draws from: rng_for_sample(ray_seed, 0, 0)
+VK_HD uint64_t ray_seed(uint64_t seed, uint64_t index) { return seed + 0x9E3779B97F4A7C15ull * index; }
+// world.hit(&Ray{o, d, time}, T_MIN, tmax) on S (which must be a tree view: no grid, no rebuilt-form gates): begin_segment with tmax as
+// the closest distance so far, the walk, the full record (u and v always), and the description record whose own hit() produced the
+// winner (P).  A tmax that is a NaN or <= T_MIN misses without a walk (the walk's bounds need a positive tmax).
+template <uint32_t F, class Mem>
+VK_HD void trace_ray(Lane &L, const DScene &S, const Mem &M, const DProvenance &P, V3 o, V3 d, float time, float tmax, uint64_t rseed,
+    RayHit &H) {
+    H.R.p = v3s(0.0f); H.R.n = v3s(0.0f); H.R.u = 0.0f; H.R.v = 0.0f; H.R.front = false; H.R.mat = 0u;
+    H.t = INFINITY; H.hit = 0u; H.object = 0u; H.medium = 0u;
+    if (!(tmax > T_MIN)) return;
+    L.depth = 0u; L.pixel = 0u; L.sample = 0u;
+    if (F & VKF_MEDIUM) L.rng = vk::rng_for_sample(rseed, 0u, 0u);
+    begin_segment<Mem::ISHIFT, fused_box<F, Mem>(), spheres_only<F>()>(L, S, o, d, time, false, tmax);
+    while (traversing(L)) traverse_step<F, Mem>(L, S, M);
+    if (L.best_prim == 0u) return;
+    build_record<F, Mem, true>(L, S, M, H.R);
+    H.t = L.T; H.hit = 1u;
+    const uint32_t k = VKD_KIND(L.best_prim), idx = VKD_INDEX(L.best_prim);
+    if ((F & VKF_MEDIUM) && k == DK_MEDIUM) { H.object = VK_MAKE_REF(VK_KIND_MEDIUM, P.medium[idx]); H.medium = 1u; }
+    else if ((F & VKF_BOX) && k == DK_BOX) H.object = VK_MAKE_REF(VK_KIND_RECT, P.box_face[idx * 6u + vk::f32_bits(L.best_aux)]);
+    else if ((F & VKF_RECT) && k == DK_RECT) H.object = VK_MAKE_REF(VK_KIND_RECT, P.rect[idx]);
+    else if ((F & VKF_MOVING) && k == DK_MOVING) H.object = VK_MAKE_REF(VK_KIND_MOVING_SPHERE, P.moving[idx]);
+    else H.object = VK_MAKE_REF(VK_KIND_SPHERE, P.sphere[idx]);
+}
+// vk_hit as its sixteen 32-bit words
+VK_HD void hit_words(const RayHit &H, uint32_t w[16]) {
+    w[0] = vk::f32_bits(H.R.p.x); w[1] = vk::f32_bits(H.R.p.y); w[2] = vk::f32_bits(H.R.p.z); w[3] = vk::f32_bits(H.t);
+    w[4] = vk::f32_bits(H.R.n.x); w[5] = vk::f32_bits(H.R.n.y); w[6] = vk::f32_bits(H.R.n.z); w[7] = vk::f32_bits(H.R.u);
+    w[8] = vk::f32_bits(H.R.v); w[9] = H.hit; w[10] = H.R.front ? 1u : 0u; w[11] = H.R.mat;
+    w[12] = H.object; w[13] = H.medium; w[14] = 0u; w[15] = 0u;
 }
 
 }  // namespace vkd

@@ -156,6 +156,26 @@ class AdaptiveInfo(C.Structure):
     _fields_ = [("tiles_total", C.c_uint32), ("tiles_active", C.c_uint32), ("samples_rendered", C.c_uint64)]
 
 
+class Ray(C.Structure):
+    """vk_ray (vk_trace_rays): tmax = inf for the reference's own call"""
+    _fields_ = [("origin", C.c_float * 3), ("tmax", C.c_float), ("direction", C.c_float * 3), ("time", C.c_float)]
+
+
+class Hit(C.Structure):
+    """vk_hit (vk_trace_rays)"""
+    _fields_ = [("p", C.c_float * 3), ("t", C.c_float), ("normal", C.c_float * 3), ("u", C.c_float), ("v", C.c_float),
+                ("hit", C.c_uint32), ("front", C.c_uint32), ("material", C.c_uint32), ("object", C.c_uint32), ("medium", C.c_uint32),
+                ("_pad", C.c_uint32 * 2)]
+
+
+class TraceParams(C.Structure):
+    """vk_trace_params (vk_trace_rays)"""
+    _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+VK_RAY_TMIN = 0.001
+
+
 class GuideParams(C.Structure):
     """vk_guide_params (vk_render_guides)"""
     _fields_ = [("max_bounces", C.c_uint32), ("fuzz_max", C.c_float), ("flags", C.c_uint32)]
@@ -251,6 +271,7 @@ DEVICE_SYMBOLS = [
     "vk_progress_get_info", "vk_progress_destroy", "vk_progress_set_adaptive", "vk_progress_tile_samples",
     "vk_render_aov", "vk_render_aov_device",
     "vk_guide_default_params", "vk_render_guides", "vk_render_guides_device",
+    "vk_trace_rays", "vk_trace_rays_device",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -326,6 +347,11 @@ def _bind(lib):
     lib.vk_render_guides_device.restype = C.c_int
     lib.vk_render_guides_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.POINTER(GuideParams)] + \
         [C.c_void_p] * 6 + [C.POINTER(Stats)]
+    lib.vk_trace_rays.restype = C.c_int
+    lib.vk_trace_rays.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_trace_rays_device.restype = C.c_int
+    lib.vk_trace_rays_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                         C.POINTER(Stats)]
     lib.vk_denoise_default_params.restype = C.c_int
     lib.vk_denoise_default_params.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams)]
     lib.vk_denoise.restype = C.c_int

@@ -93,6 +93,17 @@ pub struct vk_denoise_params { pub width: u32, pub height: u32, pub levels: u32,
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_guide_params { pub max_bounces: u32, pub fuzz_max: f32, pub flags: u32 }
 
+// ray queries: a caller-supplied ray (tmax: f32::INFINITY for main.rs:130's call), its closest hit, the batch parameters
+pub const VK_RAY_TMIN: f32 = 0.001;
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_ray { pub origin: [f32; 3], pub tmax: f32, pub direction: [f32; 3], pub time: f32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_hit { pub p: [f32; 3], pub t: f32, pub normal: [f32; 3], pub u: f32, pub v: f32, pub hit: u32, pub front: u32, pub material: u32, pub object: vk_ref, pub medium: u32, pub _pad: [u32; 2] }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_trace_params { pub seed: u64, pub first_index: u64, pub flags: u32, pub _pad: u32 }
+
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_temporal_params { pub width: u32, pub height: u32, pub max_history: u32, pub depth_tol: f32, pub normal_cos_min: f32, pub albedo_floor: f32, pub flags: u32 }
 
@@ -143,6 +154,11 @@ extern "C" {
                                    gp: *const vk_guide_params, d_albedo: *mut c_void, d_normal: *mut c_void, d_depth: *mut c_void,
                                    d_coverage: *mut c_void, d_bounces: *mut c_void, hip_stream: *mut c_void,
                                    stats_out: *mut vk_stats) -> c_int;
+    // ray queries (additive symbols of ABI 7): world.hit(&ray, 0.001, tmax) for rays the caller supplies; hits[i] answers rays[i]
+    pub fn vk_trace_rays(scene: *mut vk_scene, params: *const vk_trace_params, rays: *const vk_ray, n_rays: u64, hits: *mut vk_hit,
+                         stats_out: *mut vk_stats) -> c_int;
+    pub fn vk_trace_rays_device(scene: *mut vk_scene, params: *const vk_trace_params, d_rays: *const c_void, n_rays: u64,
+                                d_hits: *mut c_void, hip_stream: *mut c_void, stats_out: *mut vk_stats) -> c_int;
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

@@ -64,6 +64,24 @@ class HostScene:
             pass
 
 
+# numpy twins of vk_ray and vk_hit (DeviceScene.trace_rays)
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmax", "<f4"), ("direction", "<f4", 3), ("time", "<f4")])
+HIT_DTYPE = np.dtype([("p", "<f4", 3), ("t", "<f4"), ("normal", "<f4", 3), ("u", "<f4"), ("v", "<f4"), ("hit", "<u4"), ("front", "<u4"),
+                      ("material", "<u4"), ("object", "<u4"), ("medium", "<u4"), ("_pad", "<u4", 2)])
+assert RAY_DTYPE.itemsize == C.sizeof(ffi.Ray) == 32 and HIT_DTYPE.itemsize == C.sizeof(ffi.Hit) == 64
+
+
+def make_rays(origin, direction, time=0.0, tmax=np.inf):
+    """A RAY_DTYPE array from origins and directions (n, 3) and per-ray or scalar times and tmax."""
+    origin = np.asarray(origin, np.float32).reshape(-1, 3)
+    rays = np.zeros(origin.shape[0], RAY_DTYPE)
+    rays["origin"] = origin
+    rays["direction"] = np.asarray(direction, np.float32).reshape(-1, 3)
+    rays["time"] = time
+    rays["tmax"] = tmax
+    return rays
+
+
 def check(lib, status):
     if status != ffi.VK_OK:
         raise RuntimeError(f"vecchio_amd status {status}: {lib.vk_last_error().decode()}")
@@ -129,6 +147,40 @@ class DeviceScene:
                                                         C.c_void_p(d_normal or None), C.c_void_p(d_depth or None),
                                                         C.c_void_p(d_coverage or None), C.c_void_p(stream or 0), C.byref(stats)))
         return stats
+
+    def trace_rays(self, rays, seed=0, first_index=0, out=None, stream=None, return_stats=False):
+        """Closest hits of caller-supplied rays (vk_trace_rays): rays is a RAY_DTYPE array (make_rays()) or anything of 32 bytes per
+        ray that views as one; returns a HIT_DTYPE array, hits[i] answering rays[i].  Device tensors (objects with data_ptr(): a
+        (n, 8) float32 tensor of rays on this scene's device) go through vk_trace_rays_device on `stream` without a host wait and
+        return an (n, 16) int32 tensor — view it as HIT_DTYPE after copying it to the host — or write into `out`."""
+        tp = ffi.TraceParams(seed & 0xFFFFFFFFFFFFFFFF, first_index, 0, 0)
+        stats = ffi.Stats()
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8 != 0:
+                raise ValueError("device rays must be a contiguous float32 tensor of 8 floats per ray")
+            n = rays.numel() // 8
+            if out is None:
+                out = torch.empty((n, 16), dtype=torch.int32, device=rays.device)
+            if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != n * 16:
+                raise ValueError("device hits must be a contiguous int32 tensor of 16 words per ray")
+            check(self._lib, self._lib.vk_trace_rays_device(self._h, C.byref(tp), C.c_void_p(rays.data_ptr() if n else None), n,
+                                                            C.c_void_p(out.data_ptr() if n else None), C.c_void_p(stream or 0),
+                                                            C.byref(stats)))
+            return (out, stats) if return_stats else out
+        rays = np.ascontiguousarray(rays)
+        if rays.dtype != RAY_DTYPE:
+            if rays.nbytes % 32 != 0 or rays.dtype.itemsize not in (4, 32):
+                raise ValueError("rays must be a RAY_DTYPE array (or float32 data of 8 floats per ray)")
+            rays = rays.reshape(-1).view(RAY_DTYPE)
+        rays = rays.reshape(-1)
+        if out is None:
+            out = np.zeros(rays.shape[0], HIT_DTYPE)
+        assert out.dtype == HIT_DTYPE and out.flags.c_contiguous and out.shape == rays.shape
+        n = rays.shape[0]
+        check(self._lib, self._lib.vk_trace_rays(self._h, C.byref(tp), C.c_void_p(rays.ctypes.data if n else None), n,
+                                                 C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
+        return (out, stats) if return_stats else out
 
     GUIDE_CHANNELS = AOV_CHANNELS + ("bounces",)
 
