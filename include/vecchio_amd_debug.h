@@ -69,6 +69,9 @@ int vk_debug_phase_stats(vk_scene *scene, const vk_camera *cam, const vk_render_
  * op 0 sin, 1 cos, 2 ln, 3 asin, 4 atan2(a,b), 5 pow5, 6 a/b, 7 sqrt(a), 8 draws, 9 a*b+a, 10 the sphere test's a/b,
  * 11 / 12 sincos .s / .c, 13 / 14 the samplers' sincos (0 <= a < 2^22) .s / .c                                      */
 int vk_debug_math(int device, int op, const float *a, const float *b, float *out, size_t n);
+/* libvecchio_amd_debug.so only: how many device resources the library's handles (scenes, progressive and temporal handles) own right
+ * now: out[0] device buffers, [1] pinned host buffers, [2] events, [3] streams.  Back at its earlier value once a handle is destroyed. */
+int vk_debug_live_objects(uint64_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -72,13 +72,7 @@ struct FusedMem : GlobalMem { static constexpr bool FUSED_BOX = true; };
 
 // the scene as handed over: what a sample dropped by exact re-treeing is rendered on (vk_api.hip builds the same view for the
 // second launch)
-static DScene reference_view(const DScene &S) {
-    DScene r = S;
-    r.items = S.ref_items; r.n_items = S.n_ref_items; r.n_world_items = S.n_ref_items;
-    r.ref_items = nullptr; r.n_ref_items = 0; r.t_pad = 0.0f; r.gate_scale = 1.0f; r.tmin_gate = T_MIN; r.tie_rank = nullptr;
-    r.grid.nu = 0u;
-    return r;
-}
+static DScene reference_view(const DScene &S) { return handed_over_view(S); }
 
 template <uint32_t F, class Mem = GlobalMem>
 static void trace_one(const DScene &S, const GlobalMem &M0, const RenderConsts &C, uint32_t pixel, uint32_t sample, V3 &rgb,
@@ -350,7 +344,7 @@ int emu_aov(const vk_scene_desc *desc, const vk_camera *cam, const vk_render_par
     int st = linearize(desc, LS, g_err, opt);
     if (st != VK_OK) return st;
     DScene S = LS.host_view();
-    if (S.grid.nu != 0u || S.t_pad != 0.0f || S.walk_start != 0u || S.gate_scale != 1.0f || S.primary_ref != 0u || S.tie_rank) {
+    if (!is_plain_tree_view(S) || S.tie_rank) {
         g_err = "the tree as handed over came with a rebuilt form's gates"; return VK_ERR_BAD_ARG; }
     GlobalMem M{S.items, S.spheres, S.sphere_mat, S.boxes};
     RenderConsts C = make_consts(cam, p);

@@ -63,7 +63,7 @@ int emu_guides(const vk_scene_desc *desc, const vk_camera *cam, const vk_render_
     int st = linearize(desc, LS, g_guides_err, opt);
     if (st != VK_OK) return st;
     DScene S = LS.host_view();
-    if (S.grid.nu != 0u || S.t_pad != 0.0f || S.walk_start != 0u || S.gate_scale != 1.0f || S.primary_ref != 0u || S.tie_rank) {
+    if (!is_plain_tree_view(S) || S.tie_rank) {
         g_guides_err = "the tree as handed over came with a rebuilt form's gates"; return VK_ERR_BAD_ARG; }
     GlobalMem M{S.items, S.spheres, S.sphere_mat, S.boxes};
     RenderConsts C;

@@ -42,7 +42,7 @@ int emu_rays(const vk_scene_desc *desc, uint64_t seed, uint64_t first_index, con
     int st = linearize(desc, LS, g_rays_err, opt);
     if (st != VK_OK) return st;
     DScene S = LS.host_view();
-    if (S.grid.nu != 0u || S.t_pad != 0.0f || S.walk_start != 0u || S.gate_scale != 1.0f || S.primary_ref != 0u) {
+    if (!is_plain_tree_view(S)) {
         g_rays_err = "the tree view came with a rebuilt form's gates"; return VK_ERR_BAD_ARG; }
     const GlobalMem M{S.items, S.spheres, S.sphere_mat, S.boxes};
     const DProvenance P = LS.host_provenance();

@@ -27,9 +27,10 @@ def test_exports_every_declared_symbol(built):
     assert {"vk_scene_create", "vk_render", "vk_render_device", "vk_scene_destroy", "vk_last_error", "vk_abi_version",
             "vk_device_count", "vk_to_color_device", "vk_scene_create_multi", "vk_debug_render_samples"} <= set(names)
     lib = C.CDLL(ffi.device_lib_path())
-    # the two diagnostic entry points of vecchio_amd_debug.h that need instrumented kernel builds live in libvecchio_amd_debug.so (the same
-    # sources with -DVK_DEBUG_LIB), which exports everything; the product library exports everything else and NOT those two
-    debug_only = {"vk_debug_phase_stats", "vk_debug_math"}
+    # the diagnostic entry points of vecchio_amd_debug.h that need instrumented kernel builds, and the live-object counter, live in
+    # libvecchio_amd_debug.so (the same sources with -DVK_DEBUG_LIB), which exports everything; the product library exports everything
+    # else and NOT those
+    debug_only = {"vk_debug_phase_stats", "vk_debug_math", "vk_debug_live_objects"}
     missing = [n for n in names if not hasattr(lib, n) and n not in debug_only]
     assert not missing, f"declared in include/*.h but not exported by the product library: {missing}"
     assert not [n for n in debug_only if hasattr(lib, n)]

@@ -168,6 +168,13 @@ struct EnvSwitches {
 
 }  // namespace
 
+#include "vk_resources.h"      // (uses fail() and HIP_TRY)
+using vkr::DeviceBuffer;
+using vkr::Event;
+using vkr::PinnedBuffer;
+using vkr::Stream;
+static_assert(vkd::HANDED_OVER_T_MIN == T_MIN, "handed_over_view's tmin_gate is vk_trace.h's T_MIN");
+
 // =========================================================================================
 // One vk_scene = the linearised scene resident on ONE device plus the per-launch scratch of the (at most one)
 // render in flight on it.  A multi-device scene (vk_scene_create_multi) is a group handle: `parts` holds one
@@ -177,125 +184,147 @@ struct vk_scene {
     std::shared_ptr<const LinearScene> host;   // shared by the parts of a multi-device scene
     DScene dev;                // device pointers
     EnvSwitches env;
-    std::vector<void *> allocs;
-    uint32_t *counter = nullptr;
-    float *fb = nullptr; size_t fb_bytes = 0;        // f32 framebuffer (vk_render; RGB8 output; the parts' render targets)
-    uint8_t *fb8 = nullptr; size_t fb8_bytes = 0;    // RGB8 image for vk_render with VK_OUTPUT_RGB8
-    long long *accum = nullptr; size_t accum_bytes = 0;   // fixed-point pixel sums of the render in flight
-    float4 *debug = nullptr; size_t debug_bytes = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<DeviceBuffer<>> allocs;        // the uploads `dev` (and rays.prov) point into
+    DeviceBuffer<uint32_t> counter;
+    DeviceBuffer<float> fb;                    // f32 framebuffer (vk_render; RGB8 output; the parts' render targets)
+    DeviceBuffer<uint8_t> fb8;                 // RGB8 image for vk_render with VK_OUTPUT_RGB8
+    DeviceBuffer<long long> accum;             // fixed-point pixel sums of the render in flight
+    DeviceBuffer<float4> debug;
+    Event ev0, ev1;
     int num_cus = 256;
-    uint32_t lds_bytes = 0;    // hot-record bytes staged per workgroup (0 = not LDS resident)
-    bool grid_on = false;      // the grid form of exact re-treeing is this scene's walk (DGrid)
-    uint32_t grid_slots = 0;   // the grid form: size of the table [cells | refs] in 32-byte units (KArgs::lds_items of its launches)
-    size_t hot_bytes = 0;      // items + spheres + boxes: what traversal gathers from
-    uint32_t wg_threads = 512; // workgroup size chosen by plan_residency()
-    uint32_t sphere_waves = 6; // waves per SIMD of the sphere-only variant (8 was measured 3 % slower: it spills)
-    uint32_t wgs_per_cu = 2;
-    // Seven waves per SIMD for sphere-only scenes staged in LDS: ONE 1024-thread and ONE 768-thread workgroup per CU, i.e. two
-    // concurrent launches of the same kernel pulling from the same unit counter (plan_residency); the second one runs on `stream2`.
-    bool dual_launch = false;
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // Self-check of the dual launch: the two launches must OVERLAP, or the first one does all the work at 16 waves per CU.  Each
-    // launch counts the units it pulls (two words of the counter block); the 768-thread launch should get ~12/28 of them.  A frame in
-    // which one launch got under a tenth counts as a strike; after two strikes in a row the scene uses the single-launch shape for
-    // good.  Checked where the caller synchronises anyway (vk_scene_last_kernel_ms, vk_render).
-    bool dual_last = false;        // the last render used the dual launch
-    int dual_strikes = 0;
     bool last_timed = false;
-    // Exact re-treeing (vk_trace.h): the scene's own tree is a rebuilt one; samples it cannot vouch for are queued by the first launch
-    // and rendered by a second one on `ref_view`, the scene as handed over.  redo_count: REDO_REGIONS counters + the 3 plan words.
-    bool exact = false;            // host->ref_items is there and the switch VK_EXACT_RETREE is not 0
-    DScene ref_view;
-    uint2 *redo_list = nullptr; size_t redo_bytes = 0;
-    uint32_t *redo_count = nullptr;
-    bool redo_last = false;        // the last render had a second launch
-    unsigned long long *wave_times = nullptr;      // VK_WAVE_TIMES=1 (diagnostics)
-    // The rebuilt tree is SUSPENDED for a while when a frame sends more than a quarter of its samples through the second launch, or
-    // overflows the queues between the launches (the fallback launch then renders the frame a third time): the scene renders on the tree
-    // as handed over until frame `exact_resume`, then tries again; every relapse doubles the pause (32 frames .. 4096).  An animation
-    // that passes through one bad viewpoint loses the rebuilt tree for a few dozen frames, not for good.  The verdict on a frame is read
-    // from `plan_host` (pinned; copied behind the frame's last kernel) when the NEXT frame is enqueued, without waiting, or where the
-    // caller synchronises anyway (vk_scene_last_requeued_samples).
-    uint64_t frame_no = 0, exact_resume = 0, exact_pause = 32;
-    // Two verdict slots, used in turn: [4] words of a frame's redo_plan each, an event recorded right behind the copy, the samples of the
-    // partition the frame covered.  A caller that always enqueues frame N + 1 before frame N has finished (vk_render_device in a
-    // pipeline) still has frame N - 1's verdict taken when it enqueues frame N + 1: the verdict does not wait for the MOST RECENT frame.
-    uint32_t *plan_host = nullptr;     // [2][4]
-    hipEvent_t ev_plan[2] = {nullptr, nullptr};
-    bool plan_pending[2] = {false, false};      // a frame with a second launch has been enqueued and its plan not judged yet
-    uint64_t plan_samples[2] = {0, 0};
-    int plan_last = 0;                 // the slot of the last frame with a second launch
-    bool plan_copied = false;          // ... whose plan did travel to that slot
-    uint64_t redo_last_samples = 0;    // samples of the partition the last render covered
-    unsigned long long *phase_stats = nullptr;   // device, 24 counters (diagnostic kernel build)
+    DeviceBuffer<unsigned long long> wave_times;    // VK_WAVE_TIMES=1 (diagnostics)
+    DeviceBuffer<unsigned long long> phase_stats;   // device, 24 counters (diagnostic kernel build)
     bool want_phase_stats = false;
-    // heavy-first tile order: per-tile times of the probe launch and the order derived from them
-    uint32_t *tile_cost = nullptr, *tile_order = nullptr, *order_hist = nullptr;
-    size_t tile_cost_n = 0, tile_order_n = 0;
-    // Frame-to-frame reuse of the order: the frames of an animation (and the steps of a benchmark) see nearly the same tile costs,
-    // so the order found for a partition is kept while the partition's geometry is the same, the camera has hardly moved and the
-    // order is younger than ORDER_MAX_AGE frames; then the probe launch and the three sorting kernels are skipped (~1.7 ms of a
-    // 1/8 share of C2's 42 ms).  The order never changes a pixel, so a stale one only costs balance.
-    struct {
-        uint32_t width = 0, height = 0, rank = 0, world = 0, depth = 0, age = 0;
-        float org[3] = {0, 0, 0}, llc[3] = {0, 0, 0};
-        bool valid = false;
-    } order_for;
-    // ---- multi-device group (empty for an ordinary scene)
-    std::vector<vk_scene *> parts;
-    // a part's own stream, its slab (on its device), the slab's landing buffer on devices[0] and the event that says it landed
-    hipStream_t stream = nullptr;
-    uint8_t *slab = nullptr; size_t slab_bytes = 0;
-    uint8_t *landing = nullptr; size_t landing_bytes = 0; int landing_device = 0;
-    hipEvent_t ev_landed = nullptr;
-    hipEvent_t ev_begin = nullptr;               // group: recorded on the caller's stream at the start of a frame
-    // group, VK_SCENE_RCCL_GATHER: one communicator per part (rank j = devices[j]); empty = peer copies
-    std::vector<ncclComm_t> comms;
     // the render_kernel launches of the last frame (vk_debug_last_launches: tests); host bookkeeping, cleared per frame
     std::vector<vk_debug_launch> launch_log;
-    // vk_render_aov: its own events and output buffers, so that nothing that describes vk_render's last frame is touched
-    hipEvent_t aov_ev0 = nullptr, aov_ev1 = nullptr;
-    float *aov_buf = nullptr; size_t aov_bytes = 0;
-    // vk_trace_rays: the provenance tables (uploaded by the scene's first ray query), the staging buffer of the host variant (rays, then
-    // hits) and its events
-    bool prov_ready = false; DProvenance prov = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint8_t *ray_buf = nullptr; size_t ray_bytes = 0;
-    hipEvent_t ray_ev0 = nullptr, ray_ev1 = nullptr;
-    // vk_denoise: the filter's scratch (two ping-pong images, the packed guides, the depth slopes), the device copies of vk_denoise's
-    // host images, its own events (before the prepare kernel, behind it, behind every level), the levels of the last timed call and the
-    // form the level kernels are launched in (vk_debug_denoise_form)
-    uint8_t *dn_buf = nullptr; size_t dn_bytes = 0;
-    float *dn_io = nullptr; size_t dn_io_bytes = 0;
-    hipEvent_t dn_ev[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    uint32_t dn_last_levels = 0;
-    int dn_form = 0;
+
+    // ---- the residency plan (plan_residency)
+    struct Residency {
+        uint32_t lds_bytes = 0;    // hot-record bytes staged per workgroup (0 = not LDS resident)
+        bool grid_on = false;      // the grid form of exact re-treeing is this scene's walk (DGrid)
+        uint32_t grid_slots = 0;   // the grid form: size of the table [cells | refs] in 32-byte units (KArgs::lds_items of its launches)
+        size_t hot_bytes = 0;      // items + spheres + boxes: what traversal gathers from
+        uint32_t wg_threads = 512; // workgroup size chosen by plan_residency()
+        uint32_t sphere_waves = 6; // waves per SIMD of the sphere-only variant (8 was measured 3 % slower: it spills)
+        uint32_t wgs_per_cu = 2;
+        // Seven waves per SIMD for sphere-only scenes staged in LDS: ONE 1024-thread and ONE 768-thread workgroup per CU, i.e. two
+        // concurrent launches of the same kernel pulling from the same unit counter (plan_residency); the second one runs on
+        // `dual.stream2`.
+        bool dual_launch = false;
+    } plan;
+
+    // ---- the dual launch (launch_dual)
+    struct Dual {
+        Stream stream2;
+        Event ev_fork, ev_join;
+        // Self-check of the dual launch: the two launches must OVERLAP, or the first one does all the work at 16 waves per CU.  Each
+        // launch counts the units it pulls (two words of the counter block); the 768-thread launch should get ~12/28 of them.  A frame
+        // in which one launch got under a tenth counts as a strike; after two strikes in a row the scene uses the single-launch shape
+        // for good.  Checked where the caller synchronises anyway (vk_scene_last_kernel_ms, vk_render).
+        bool last = false;         // the last render used the dual launch
+        int strikes = 0;
+    } dual;
+
+    // ---- exact re-treeing (vk_trace.h): the scene's own tree is a rebuilt one; samples it cannot vouch for are queued by the first
+    // launch and rendered by a second one on `ref_view`, the scene as handed over.  redo_count: REDO_REGIONS counters + the 3 plan words.
+    struct Exact {
+        bool on = false;               // host->ref_items is there and the switch VK_EXACT_RETREE is not 0
+        DScene ref_view;
+        DeviceBuffer<uint2> redo_list;
+        DeviceBuffer<uint32_t> redo_count;
+        bool redo_last = false;        // the last render had a second launch
+        // The rebuilt tree is SUSPENDED for a while when a frame sends more than a quarter of its samples through the second launch, or
+        // overflows the queues between the launches (the fallback launch then renders the frame a third time): the scene renders on the
+        // tree as handed over until frame `resume`, then tries again; every relapse doubles the pause (32 frames .. 4096).  An animation
+        // that passes through one bad viewpoint loses the rebuilt tree for a few dozen frames, not for good.  The verdict on a frame is
+        // read from `plan_host` (pinned; copied behind the frame's last kernel) when the NEXT frame is enqueued, without waiting, or
+        // where the caller synchronises anyway (vk_scene_last_requeued_samples).
+        uint64_t frame_no = 0, resume = 0, pause = 32;
+        // Two verdict slots, used in turn: [4] words of a frame's redo_plan each, an event recorded right behind the copy, the samples
+        // of the partition the frame covered.  A caller that always enqueues frame N + 1 before frame N has finished (vk_render_device
+        // in a pipeline) still has frame N - 1's verdict taken when it enqueues frame N + 1: the verdict does not wait for the MOST
+        // RECENT frame.
+        PinnedBuffer<uint32_t> plan_host;  // [2][4]
+        Event ev_plan[2];
+        bool plan_pending[2] = {false, false};      // a frame with a second launch has been enqueued and its plan not judged yet
+        uint64_t plan_samples[2] = {0, 0};
+        int plan_last = 0;                 // the slot of the last frame with a second launch
+        bool plan_copied = false;          // ... whose plan did travel to that slot
+        uint64_t redo_last_samples = 0;    // samples of the partition the last render covered
+    } exact;
+
+    // ---- heavy-first tile order: per-tile times of the probe launch and the order derived from them
+    struct TileOrder {
+        DeviceBuffer<uint32_t> cost, order, hist;
+        // Frame-to-frame reuse of the order: the frames of an animation (and the steps of a benchmark) see nearly the same tile costs,
+        // so the order found for a partition is kept while the partition's geometry is the same, the camera has hardly moved and the
+        // order is younger than ORDER_MAX_AGE frames; then the probe launch and the three sorting kernels are skipped (~1.7 ms of a
+        // 1/8 share of C2's 42 ms).  The order never changes a pixel, so a stale one only costs balance.
+        struct {
+            uint32_t width = 0, height = 0, rank = 0, world = 0, depth = 0, age = 0;
+            float org[3] = {0, 0, 0}, llc[3] = {0, 0, 0};
+            bool valid = false;
+        } made_for;
+    } order;
+
+    // ---- multi-device group (parts: empty for an ordinary scene)
+    struct Group {
+        std::vector<vk_scene *> parts;
+        // a part's own stream, its slab (on its device), the slab's landing buffer on devices[0] and the event that says it landed
+        Stream stream;
+        DeviceBuffer<uint8_t> slab;
+        DeviceBuffer<uint8_t> landing;
+        Event ev_landed;
+        Event ev_begin;                    // group: recorded on the caller's stream at the start of a frame
+        // group, VK_SCENE_RCCL_GATHER: one communicator per part (rank j = devices[j]); empty = peer copies
+        std::vector<ncclComm_t> comms;
+    } group;
+
+    // ---- vk_render_aov / vk_render_guides: their own events and output buffers, so that nothing that describes vk_render's last frame
+    // is touched
+    struct Aov {
+        Event ev0, ev1;
+        DeviceBuffer<float> buf;
+    } aov;
+
+    // ---- vk_trace_rays: the provenance tables (uploaded by the scene's first ray query), the staging buffer of the host variant (rays,
+    // then hits) and its events
+    struct Rays {
+        bool prov_ready = false;
+        DProvenance prov = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        DeviceBuffer<uint8_t> buf;
+        Event ev0, ev1;
+    } rays;
+
+    // ---- vk_denoise: the filter's scratch (two ping-pong images, the packed guides, the depth slopes), the device copies of
+    // vk_denoise's host images, its own events (before the prepare kernel, behind it, behind every level), the levels of the last timed
+    // call and the form the level kernels are launched in (vk_debug_denoise_form)
+    struct Denoise {
+        DeviceBuffer<uint8_t> buf;
+        DeviceBuffer<float> io;
+        Event ev[10];
+        uint32_t last_levels = 0;
+        int form = 0;
+    } dn;
 };
 
 namespace {
+
+// the scene that single-device work of a handle runs on: the scene itself, or devices[0]'s part of a multi-device group
+vk_scene *first_part(vk_scene *s) { return s->group.parts.empty() ? s : s->group.parts[0]; }
+const vk_scene *first_part(const vk_scene *s) { return s->group.parts.empty() ? s : s->group.parts[0]; }
 
 template <class T>
 int upload(vk_scene *s, const std::vector<T> &v, const T *&dptr) {
     dptr = nullptr;
     size_t bytes = v.size() * sizeof(T);
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
-    s->allocs.push_back(p);
-    if (bytes) HIP_TRY(hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice));
-    dptr = reinterpret_cast<const T *>(p);
-    return VK_OK;
-}
-
-// grows a device buffer owned by the scene (never shrinks); the scene's device must be current
-template <class T>
-int ensure(T *&ptr, size_t &have, size_t need) {
-    if (need <= have && ptr) return VK_OK;
-    if (ptr) HIP_TRY(hipFree(ptr));
-    ptr = nullptr; have = 0;
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, need ? need : 16));
-    ptr = reinterpret_cast<T *>(p); have = need;
+    s->allocs.emplace_back();
+    DeviceBuffer<> &b = s->allocs.back();
+    int rc = b.ensure(bytes);
+    if (rc != VK_OK) return rc;
+    if (bytes) HIP_TRY(hipMemcpy(b.get(), v.data(), bytes, hipMemcpyHostToDevice));
+    dptr = reinterpret_cast<const T *>(b.get());
     return VK_OK;
 }
 
@@ -333,8 +362,8 @@ void plan_residency(vk_scene *s, size_t hot) {
     // The near form of exact re-treeing walks a failed segment again in place: both trees in items[], i.e. global memory — unless its
     // reach spans the small spheres' whole box: then hardly a segment fails (the InOneWeekend scene: 3 in 10^5), a failed one may as well
     // requeue its whole sample, and the scene is staged in LDS like any other (7 520 against the unit form's 7 285 Msamples/s at 256 spp)
-    const bool near_needs_global = spheres_only && s->host->near_form && !s->grid_on && (s->env.near_lds >= 0 ? s->env.near_lds == 0 : !s->host->near_spans);
-    const uint32_t per_simd = spheres_only ? s->sphere_waves : (pick_variant(s) == (uint32_t)VKF_ALL_SCENE ? (uint32_t)VK_ALL_MINW
+    const bool near_needs_global = spheres_only && s->host->near_form && !s->plan.grid_on && (s->env.near_lds >= 0 ? s->env.near_lds == 0 : !s->host->near_spans);
+    const uint32_t per_simd = spheres_only ? s->plan.sphere_waves : (pick_variant(s) == (uint32_t)VKF_ALL_SCENE ? (uint32_t)VK_ALL_MINW
                                                                                                            : (uint32_t)VK_CORNELL_MINW);   // = MINW of launch_variant
     uint32_t cap = 4 * per_simd;                                             // waves per CU the variant's register budget admits
     // Workgroups hold a multiple of 4 waves that divides evenly over the CU's four SIMDs: the dispatcher deals a workgroup's waves
@@ -352,19 +381,19 @@ void plan_residency(vk_scene *s, size_t hot) {
     // Seven waves per SIMD (the sphere-only kernels need 72 VGPRs): 28 waves per CU cannot be two EQUAL workgroups — 14 waves land
     // 4+4+3+3 on the four SIMDs and the second workgroup does not fit beside the first — but they can be 16 + 12: a 1024-thread
     // workgroup (4 per SIMD) and a 768-thread one (3 per SIMD), from two concurrent launches.  Needs two LDS copies of the scene.
-    s->dual_launch = false;
+    s->plan.dual_launch = false;
     // (the near form of exact re-treeing walks a failed segment again in place: both trees in items[], i.e. global memory)
     if (spheres_only && !s->env.no_lds_scene && !near_needs_global && s->env.max_waves_per_cu == 0 && !getenv("VK_NO_DUAL_LAUNCH") &&
         2 * hot + 28 * pw <= LDS_PER_CU) {
-        s->lds_bytes = (uint32_t)hot; s->wg_threads = 768; s->wgs_per_cu = 2;      // (the single-launch shape: probe, STATS, tiny frames)
-        s->dual_launch = true;
+        s->plan.lds_bytes = (uint32_t)hot; s->plan.wg_threads = 768; s->plan.wgs_per_cu = 2;      // (the single-launch shape: probe, STATS, tiny frames)
+        s->plan.dual_launch = true;
         return;
     }
     if (best_waves >= cap && !s->env.no_lds_scene && !near_needs_global) {
-        s->lds_bytes = (uint32_t)hot; s->wg_threads = best_wg * 64; s->wgs_per_cu = best_n;
+        s->plan.lds_bytes = (uint32_t)hot; s->plan.wg_threads = best_wg * 64; s->plan.wgs_per_cu = best_n;
     } else {
         // 28 (sphere-only: seven 4-wave workgroups, 7 waves/SIMD) or 24 waves per CU
-        s->lds_bytes = 0; s->wg_threads = 256; s->wgs_per_cu = spheres_only ? 7 : per_simd;
+        s->plan.lds_bytes = 0; s->plan.wg_threads = 256; s->plan.wgs_per_cu = spheres_only ? 7 : per_simd;
     }
 }
 
@@ -400,8 +429,8 @@ int launch_variant(vk_scene *s, const KArgs &A, bool lds, dim3 grid, size_t shme
     const uint32_t role = cost ? VK_LAUNCH_PROBE : (A.list_mode == 1u ? VK_LAUNCH_REDO : (A.list_mode == 2u ? VK_LAUNCH_FALLBACK : VK_LAUNCH_MAIN));
     auto go = [&](auto kernel, bool l, int minw, bool gridf) -> int {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        hipLaunchKernelGGL(kernel, grid, dim3(s->wg_threads), shmem, st, A);
-        log_launch(s, role, F, l, minw, cost, gridf, grid.x, s->wg_threads, shmem);
+        hipLaunchKernelGGL(kernel, grid, dim3(s->plan.wg_threads), shmem, st, A);
+        log_launch(s, role, F, l, minw, cost, gridf, grid.x, s->plan.wg_threads, shmem);
         return VK_OK;
     };
     int rc;
@@ -428,20 +457,20 @@ int launch_variant(vk_scene *s, const KArgs &A, bool lds, dim3 grid, size_t shme
 template <uint32_t F, bool GRID = false>
 int launch_dual(vk_scene *s, const KArgs &A, size_t per_wave, hipStream_t st) {
     auto kernel = &render_kernel<F, true, 7, false, false, GRID>;
-    const size_t shm_a = s->lds_bytes + 16 * per_wave, shm_b = s->lds_bytes + 12 * per_wave;
+    const size_t shm_a = s->plan.lds_bytes + 16 * per_wave, shm_b = s->plan.lds_bytes + 12 * per_wave;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_a));
     // (VK_DUAL_SAME_STREAM=1, tests: both launches on ONE stream, i.e. serialised — what the self-check must notice)
-    hipStream_t st2 = s->env.dual_same_stream ? st : s->stream2;
-    HIP_TRY(hipEventRecord(s->ev_fork, st));                    // everything enqueued so far (memsets of counter and sums)
-    HIP_TRY(hipStreamWaitEvent(st2, s->ev_fork, 0));
+    hipStream_t st2 = s->env.dual_same_stream ? st : s->dual.stream2;
+    HIP_TRY(hipEventRecord(s->dual.ev_fork, st));                    // everything enqueued so far (memsets of counter and sums)
+    HIP_TRY(hipStreamWaitEvent(st2, s->dual.ev_fork, 0));
     hipLaunchKernelGGL(kernel, dim3((unsigned)s->num_cus), dim3(1024), shm_a, st, A);
     hipLaunchKernelGGL(kernel, dim3((unsigned)s->num_cus), dim3(768), shm_b, st2, A);
     HIP_TRY(hipGetLastError());
     log_launch(s, VK_LAUNCH_DUAL_1024, F, true, 7, false, GRID, (uint32_t)s->num_cus, 1024u, shm_a);
     log_launch(s, VK_LAUNCH_DUAL_768, F, true, 7, false, GRID, (uint32_t)s->num_cus, 768u, shm_b);
-    HIP_TRY(hipEventRecord(s->ev_join, st2));
-    HIP_TRY(hipStreamWaitEvent(st, s->ev_join, 0));              // the resolve kernel waits for both
-    s->dual_last = true;
+    HIP_TRY(hipEventRecord(s->dual.ev_join, st2));
+    HIP_TRY(hipStreamWaitEvent(st, s->dual.ev_join, 0));              // the resolve kernel waits for both
+    s->dual.last = true;
     return VK_OK;
 }
 
@@ -530,7 +559,7 @@ uint32_t choose_chunks(const vk_scene *s, const vk_render_params *p, const uint6
     // units of the rank's dearest tiles, so smaller ones (C2's 1/8 share: 64 -> 54.2 ms, 32 -> 53.1, 16 -> 52.9, 8 -> 53.5; ideal 50.0).
     // (seven waves per SIMD — the dual launch of sphere-only LDS scenes — like the smaller units too: 16 / 32 / 48 / 64 -> 6 805 / 6 836 /
     // 6 815 / 6 776 Msamples/s on C2 at full size)
-    uint32_t cap = (p->tile_world > 1u || s->dual_launch) ? 32u : 64u;
+    uint32_t cap = (p->tile_world > 1u || s->plan.dual_launch) ? 32u : 64u;
     // (Round 1 and the first half of round 2 cut the units of scenes bigger than an XCD's L2 down to 8 spp "because tile costs are
     // skewed by orders of magnitude": the skew was NaN rays walking the whole million-item tree — see begin_segment in vk_trace.h.
     // Without them C5 prefers the common setting: 4 / 8 / 16 / 32 / 64 spp per unit -> 564 / 574 / 579 / 583 / 585 Msamples/s.)
@@ -548,20 +577,20 @@ uint32_t choose_chunks(const vk_scene *s, const vk_render_params *p, const uint6
     return n;
 }
 
-// The verdict on a frame with a second launch (its plan has arrived in slot b of plan_host): see vk_scene::exact_resume.
+// The verdict on a frame with a second launch (its plan has arrived in slot b of plan_host): see vk_scene::Exact::resume.
 void judge_frame(vk_scene *s, int b) {
-    s->plan_pending[b] = false;
-    const uint32_t requeued = s->plan_host[4 * b + 1], lost = s->plan_host[4 * b + 2];
-    const uint64_t frame_samples = s->plan_samples[b];
+    s->exact.plan_pending[b] = false;
+    const uint32_t requeued = s->exact.plan_host[4 * b + 1], lost = s->exact.plan_host[4 * b + 2];
+    const uint64_t frame_samples = s->exact.plan_samples[b];
     const bool heavy = (uint64_t)requeued * 4u > frame_samples && frame_samples >= (1u << 20);
     if (lost != 0u || heavy) {
-        s->exact_resume = s->frame_no + s->exact_pause;
+        s->exact.resume = s->exact.frame_no + s->exact.pause;
         fprintf(stderr, "vecchio_amd: exact re-treeing %s (%u of %llu samples requeued, %u did not fit); this scene renders on the tree as "
             "handed over for the next %llu frames\n", lost ? "overflowed its queues and the frame was rendered again" : "sent over a quarter of "
-            "a frame through the second launch", requeued, (unsigned long long)frame_samples, lost, (unsigned long long)s->exact_pause);
-        s->exact_pause = std::min<uint64_t>(s->exact_pause * 2u, 4096u);
-    } else if (s->exact_pause > 32u) {
-        s->exact_pause /= 2u;           // a clean frame on the rebuilt tree: relapses are forgiven step by step
+            "a frame through the second launch", requeued, (unsigned long long)frame_samples, lost, (unsigned long long)s->exact.pause);
+        s->exact.pause = std::min<uint64_t>(s->exact.pause * 2u, 4096u);
+    } else if (s->exact.pause > 32u) {
+        s->exact.pause /= 2u;           // a clean frame on the rebuilt tree: relapses are forgiven step by step
     }
 }
 
@@ -588,64 +617,71 @@ struct AccumDesc {
     uint64_t known_tiles, known_px;   // active tiles and their in-image pixels as far as the host knows (sizing only, never a pixel)
 };
 
-// Enqueues one render of this call's tile partition into the f32 framebuffer d_out (device memory of s->device) on `st`.  With `acc`
-// (progressive rendering): one window of samples, added into acc's running sums, d_out = their running mean.
-int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params *p, float *d_out, hipStream_t st, bool want_debug,
-    vk_stats *stats, const AccumDesc *acc = nullptr) {
-    HIP_TRY(hipSetDevice(s->device));
-    s->launch_log.clear();
-    const TileGeom g(p);
-    KArgs A;
-    memset(&A, 0, sizeof(A));
-    A.S = s->dev;
-    // the verdicts that have arrived (never waits): the older slot first
+// ---- enqueue_render_f32 and its stages, in the order it runs them.  Each stage enqueues on the call's stream `st` what its name says and
+// hands what it decided to the later ones through its arguments.
+
+// the verdicts that have arrived (never waits): the older slot first
+void judge_arrived_frames(vk_scene *s) {
     for (int k = 1; k <= 2; k++) {
-        const int b = (s->plan_last + k) & 1;
-        if (s->plan_pending[b] && hipEventQuery(s->ev_plan[b]) == hipSuccess) judge_frame(s, b);
+        const int b = (s->exact.plan_last + k) & 1;
+        if (s->exact.plan_pending[b] && hipEventQuery(s->exact.ev_plan[b]) == hipSuccess) judge_frame(s, b);
     }
     (void)hipGetLastError();      // (hipErrorNotReady of a query is not an error of this call)
-    s->frame_no++;
-    bool exact = s->exact && !s->want_phase_stats && s->frame_no >= s->exact_resume;     // (the diagnostic builds have no second launch)
-    // The near form: primary rays start on the tree as handed over when the camera (its lens included) is farther than `reach` from every
-    // sphere — their walk on the rebuilt tree could not stand (vk_trace.h begin_segment).  Decided from the box around the small spheres
-    // and the surfaces of the few big ones; when in doubt: no.
-    if (s->host->near_form && !s->grid_on && (A.S.walk_start != 0u || s->exact) && s->host->n_big != 0xFFFFFFFFu) {
-        const LinearScene &H = *s->host;
-        const double reach = (double)H.reach + (double)fabsf(cam->lens_radius) * 1.5 + 1e-3 * (double)H.reach;
-        double d2 = 0.0;
-        for (int k = 0; k < 3; k++) {
-            const double o = cam->origin[k], e = o < H.small_lo[k] ? H.small_lo[k] - o : (o > H.small_hi[k] ? o - H.small_hi[k] : 0.0);
-            d2 += e * e;
-        }
-        bool far_from_all = d2 > reach * reach;
-        for (uint32_t b = 0; b < H.n_big && far_from_all; b++) {
-            double q = 0.0;
-            for (int k = 0; k < 3; k++) q += ((double)cam->origin[k] - H.big[b][k]) * ((double)cam->origin[k] - H.big[b][k]);
-            far_from_all = fabs(sqrt(q) - (double)H.big[b][3]) > reach;
-        }
-        if (A.S.walk_start != 0u) A.S.primary_ref = far_from_all ? 1u : 0u;
-        else if (far_from_all) exact = false;      // (staged in LDS there is one tree per launch: such a frame on the tree as handed over)
+}
+
+// Stage 1: takes the verdicts that have arrived; does this frame run on the rebuilt tree, with a second launch?
+bool begin_frame_exact(vk_scene *s) {
+    judge_arrived_frames(s);
+    s->exact.frame_no++;
+    return s->exact.on && !s->want_phase_stats && s->exact.frame_no >= s->exact.resume;     // (the diagnostic builds have no second launch)
+}
+
+// Stage 2, the near form: primary rays start on the tree as handed over when the camera (its lens included) is farther than `reach` from
+// every sphere — their walk on the rebuilt tree could not stand (vk_trace.h begin_segment).  Decided from the box around the small spheres
+// and the surfaces of the few big ones; when in doubt: no.  Writes view.primary_ref, or takes `exact` back.
+void near_form_primary_rays(const vk_scene *s, const vk_camera *cam, DScene &view, bool &exact) {
+    if (!(s->host->near_form && !s->plan.grid_on && (view.walk_start != 0u || s->exact.on) && s->host->n_big != 0xFFFFFFFFu)) return;
+    const LinearScene &H = *s->host;
+    const double reach = (double)H.reach + (double)fabsf(cam->lens_radius) * 1.5 + 1e-3 * (double)H.reach;
+    double d2 = 0.0;
+    for (int k = 0; k < 3; k++) {
+        const double o = cam->origin[k], e = o < H.small_lo[k] ? H.small_lo[k] - o : (o > H.small_hi[k] ? o - H.small_hi[k] : 0.0);
+        d2 += e * e;
     }
+    bool far_from_all = d2 > reach * reach;
+    for (uint32_t b = 0; b < H.n_big && far_from_all; b++) {
+        double q = 0.0;
+        for (int k = 0; k < 3; k++) q += ((double)cam->origin[k] - H.big[b][k]) * ((double)cam->origin[k] - H.big[b][k]);
+        far_from_all = fabs(sqrt(q) - (double)H.big[b][3]) > reach;
+    }
+    if (view.walk_start != 0u) view.primary_ref = far_from_all ? 1u : 0u;
+    else if (far_from_all) exact = false;      // (staged in LDS there is one tree per launch: such a frame on the tree as handed over)
+}
+
+// Stage 3: the kernel's constants and everything of KArgs that does not depend on a later stage
+int fill_render_args(vk_scene *s, const vk_camera *cam, const vk_render_params *p, const TileGeom &g, float *d_out, const AccumDesc *acc,
+    hipStream_t st, KArgs &A) {
     A.C.cam = *cam;
     A.C.width = p->width; A.C.height = p->height; A.C.spp = p->samples_per_pixel; A.C.max_depth = p->max_depth;
     A.C.seed = p->seed; A.C.integrator = p->integrator; A.C.background = p->background;
     A.C.bg[0] = p->background_color[0]; A.C.bg[1] = p->background_color[1]; A.C.bg[2] = p->background_color[2];
     A.out = d_out;
     A.tiles_x = g.tiles_x; A.tiles_y = g.tiles_y;
-    const uint32_t tiles = g.tiles;
     A.tile_rank = g.rank; A.tile_world = g.world;
     A.n_local_tiles = g.n_local;
-    const bool adapt = acc && acc->tile_n;
-    A.n_chunks = choose_chunks(s, p, adapt ? &acc->known_tiles : nullptr);
+    A.n_chunks = choose_chunks(s, p, acc && acc->tile_n ? &acc->known_tiles : nullptr);
 #ifdef VK_WAVE_TIMES
     if (getenv("VK_WAVE_TIMES")) {
-        if (!s->wave_times) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->wave_times), 3u * 1024u * 16u * sizeof(unsigned long long)));
+        int rc = s->wave_times.ensure(3u * 1024u * 16u * sizeof(unsigned long long));
+        if (rc != VK_OK) return rc;
         HIP_TRY(hipMemsetAsync(s->wave_times, 0, 3u * 1024u * 16u * sizeof(unsigned long long), st));
         A.wave_times = s->wave_times;
     }
+#else
+    (void)st;
 #endif
     A.counter = s->counter;
-    A.clamped = reinterpret_cast<unsigned long long *>(s->counter) + 1;     // bytes 8..15 of the counter block
+    A.clamped = reinterpret_cast<unsigned long long *>(s->counter.get()) + 1;     // bytes 8..15 of the counter block
     A.launch_units = s->counter + 4;                                         // bytes 16..23: units pulled by each launch of a dual launch
     A.accum_clamp = accum_clamp_for(acc ? acc->budget : p->samples_per_pixel);
     A.sample_base = acc ? acc->sample_base : 0u;
@@ -653,56 +689,44 @@ int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params
     if (s->env.shade_defer >= 1 && s->env.shade_defer <= 64) A.shade_defer = (uint32_t)s->env.shade_defer;   // diagnostics
     // scenes beyond an XCD's L2 (C5: a leaf every 6 box steps, every gather a possible L2 miss): pending sphere tests are served
     // sooner — when 3x their lanes outnumber the stepping ones (1 / 2 / 3 -> 606 / 623 / 631 Msamples/s); L2-resident scenes: 1
-    A.prim_weight = s->hot_bytes > (4u << 20) ? 3u : 1u;
+    A.prim_weight = s->plan.hot_bytes > (4u << 20) ? 3u : 1u;
     if (s->env.prim_weight >= 1 && s->env.prim_weight <= 64) A.prim_weight = (uint32_t)s->env.prim_weight;   // diagnostics
-    size_t n_pixels = (size_t)p->width * p->height;
-    if (stats) {
-        stats->samples = adapt ? acc->known_px * p->samples_per_pixel : partition_samples(p, g);
-        stats->kernel_launches = 1;
-        stats->scene_in_lds = s->lds_bytes ? 1u : 0u;
-        stats->kernel_ms = 0.0; stats->seconds = 0.0;
-    }
-    if (want_debug) {
-        size_t need = n_pixels * p->samples_per_pixel * sizeof(float4);
-        int rc = ensure(s->debug, s->debug_bytes, need);
-        if (rc != VK_OK) return rc;
-        HIP_TRY(hipMemsetAsync(s->debug, 0, need, st));
-        A.debug = s->debug;
-    }
-    HIP_TRY(hipEventRecord(s->ev0, st));
-    if (p->max_depth == 0) {
-        // ray_color returns (0,0,0) before tracing anything when depth (1) > MAX_DEPTH (main.rs:126-128): a black partition
-        HIP_TRY(hipMemsetAsync(s->counter, 0, 32, st));
-        int rc = tile_move<TM_ZERO_F32>(nullptr, d_out, p, g, st);
-        if (rc != VK_OK) return rc;
-        if (acc) HIP_TRY(hipEventRecord(acc->ev_done, st));     // (every sample is (0,0,0): the running sums stay 0, so does their mean)
-        HIP_TRY(hipEventRecord(s->ev1, st));
-        s->last_timed = true;
-        s->redo_last = false; s->dual_last = false;      // (nothing was launched: no second launch, no unit split to judge)
-        return VK_OK;
-    }
-    // Heavy-first tile order.  A launch ends when its slowest unit does, and tile costs are skewed (C2's glass tiles cost 8x
-    // the mean, units that start mid-launch finish last).  So a probe launch of a few samples per pixel times every tile
-    // (the COST build of the same kernel variant), three tiny kernels bucket-sort the tiles dearest first, and the real
-    // launch takes its units in that order (longest processing time first).  The order never changes a pixel.
-    // One rank's 1/8 share of C2: 78.1 -> 68.6 ms (ideal 64.9); whole frame 522 -> 519 ms including the probe.
-    // (whole frames on one GPU gain nothing from it any more — there is no per-unit drain — and the 1 M-sphere scene loses 12 %
-    // with its dearest tiles all in flight at once; one rank's 1/8 share of C2: 59.7 ms in raster order, 53.9 dearest first, ideal 50.0)
-    bool use_order = A.n_local_tiles >= 64 && p->samples_per_pixel >= 64 && s->env.tile_order && (g.world > 1u || s->env.tile_order_forced);
-    if (use_order) {
-        int rc = ensure(s->tile_cost, s->tile_cost_n, (size_t)tiles * sizeof(uint32_t));
-        if (rc == VK_OK) rc = ensure(s->tile_order, s->tile_order_n, (size_t)A.n_local_tiles * sizeof(uint32_t));
-        if (rc != VK_OK) return rc;
-        if (!s->order_hist) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->order_hist), ORDER_BUCKETS * sizeof(uint32_t)));
-    }
-    {   // order-independent pixel sums (vk_kernels.h to_fixed): zeroed per frame, resolved into d_out after the launch
-        int rc = ensure(s->accum, s->accum_bytes, n_pixels * 3 * sizeof(long long));
-        if (rc != VK_OK) return rc;
-        HIP_TRY(hipMemsetAsync(s->accum, 0, n_pixels * 3 * sizeof(long long), st));
-        A.accum = s->accum;
-    }
-    s->redo_last = false;
-    const bool lds_scene = s->lds_bytes != 0;
+    return VK_OK;
+}
+
+// Stage 4, max_depth == 0: ray_color returns (0,0,0) before tracing anything when depth (1) > MAX_DEPTH (main.rs:126-128): a black
+// partition, nothing launched
+int enqueue_black_frame(vk_scene *s, const vk_render_params *p, const TileGeom &g, float *d_out, hipStream_t st, const AccumDesc *acc) {
+    HIP_TRY(hipMemsetAsync(s->counter, 0, 32, st));
+    int rc = tile_move<TM_ZERO_F32>(nullptr, d_out, p, g, st);
+    if (rc != VK_OK) return rc;
+    if (acc) HIP_TRY(hipEventRecord(acc->ev_done, st));     // (every sample is (0,0,0): the running sums stay 0, so does their mean)
+    HIP_TRY(hipEventRecord(s->ev1, st));
+    s->last_timed = true;
+    s->exact.redo_last = false; s->dual.last = false;      // (nothing was launched: no second launch, no unit split to judge)
+    return VK_OK;
+}
+
+// Heavy-first tile order.  A launch ends when its slowest unit does, and tile costs are skewed (C2's glass tiles cost 8x
+// the mean, units that start mid-launch finish last).  So a probe launch of a few samples per pixel times every tile
+// (the COST build of the same kernel variant), three tiny kernels bucket-sort the tiles dearest first, and the real
+// launch takes its units in that order (longest processing time first).  The order never changes a pixel.
+// One rank's 1/8 share of C2: 78.1 -> 68.6 ms (ideal 64.9); whole frame 522 -> 519 ms including the probe.
+// (whole frames on one GPU gain nothing from it any more — there is no per-unit drain — and the 1 M-sphere scene loses 12 %
+// with its dearest tiles all in flight at once; one rank's 1/8 share of C2: 59.7 ms in raster order, 53.9 dearest first, ideal 50.0)
+// Does this frame take its tiles in that order?  If so, the order's buffers are there afterwards.
+int want_tile_order(vk_scene *s, const vk_render_params *p, const TileGeom &g, bool &use_order) {
+    use_order = g.n_local >= 64 && p->samples_per_pixel >= 64 && s->env.tile_order && (g.world > 1u || s->env.tile_order_forced);
+    if (!use_order) return VK_OK;
+    int rc = s->order.cost.ensure((size_t)g.tiles * sizeof(uint32_t));
+    if (rc == VK_OK) rc = s->order.order.ensure((size_t)g.n_local * sizeof(uint32_t));
+    if (rc == VK_OK) rc = s->order.hist.ensure(ORDER_BUCKETS * sizeof(uint32_t));
+    return rc;
+}
+
+// Stage 5: sizes and arms the queues between the two launches of exact re-treeing; takes `exact` back when there is no memory for
+// them.  Without a second launch the frame's view is the tree as handed over.
+int arm_redo_queues(vk_scene *s, uint64_t frame_samples, hipStream_t st, KArgs &A, bool &exact) {
     uint64_t per_region = 0;
     if (exact) {
         // queues for the samples the first launch drops: room for 1/32 of the partition's samples (C2 drops 0.05 %; 8 bytes each: 0.5 GB
@@ -710,191 +734,209 @@ int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params
         // (vk_scene_last_requeued_samples), vk_render then renders the frame again on the tree as handed over
         // (at most 256 MB: a frame that needs more overflows, and the fallback launch renders it on the tree as handed over)
         // (an adaptive window: the samples of its active tiles, the tree's verdict judges what was rendered)
-        s->redo_last_samples = adapt ? acc->known_px * p->samples_per_pixel : partition_samples(p, g);
-        per_region = std::min<uint64_t>(s->redo_last_samples / 32u / REDO_REGIONS + 4096u, (256ull << 20) / sizeof(uint2) / REDO_REGIONS);
+        s->exact.redo_last_samples = frame_samples;
+        per_region = std::min<uint64_t>(frame_samples / 32u / REDO_REGIONS + 4096u, (256ull << 20) / sizeof(uint2) / REDO_REGIONS);
         // (the grid form seen from far away — the 1 M-sphere scene's camera — requeues 4 % of its samples: hits reported before the ray
         // enters their leaf's box, see segment_unsafe; room for an eighth, up to 4 GB of the 288)
-        if (s->grid_on && !lds_scene) per_region = std::min<uint64_t>(s->redo_last_samples / 8u / REDO_REGIONS + 4096u, (4096ull << 20) / sizeof(uint2) / REDO_REGIONS);
+        if (s->plan.grid_on && s->plan.lds_bytes == 0) per_region = std::min<uint64_t>(frame_samples / 8u / REDO_REGIONS + 4096u, (4096ull << 20) / sizeof(uint2) / REDO_REGIONS);
         if (s->env.redo_region_cap >= 1) per_region = (uint64_t)s->env.redo_region_cap;      // tests
-    }
-    if (exact) {
         // (no memory for the queues: this frame on the tree as handed over, which needs none)
-        if (ensure(s->redo_list, s->redo_bytes, (size_t)per_region * REDO_REGIONS * sizeof(uint2)) != VK_OK) { (void)hipGetLastError(); exact = false; }
+        if (s->exact.redo_list.ensure((size_t)per_region * REDO_REGIONS * sizeof(uint2)) != VK_OK) { (void)hipGetLastError(); exact = false; }
     }
     if (exact) {
-        HIP_TRY(hipMemsetAsync(s->redo_count, 0, (REDO_REGIONS * REDO_COUNT_STRIDE + 16) * sizeof(uint32_t), st));
-        A.redo_list = s->redo_list; A.redo_count = s->redo_count; A.redo_plan = s->redo_count + REDO_REGIONS * REDO_COUNT_STRIDE;
+        HIP_TRY(hipMemsetAsync(s->exact.redo_count, 0, (REDO_REGIONS * REDO_COUNT_STRIDE + 16) * sizeof(uint32_t), st));
+        A.redo_list = s->exact.redo_list; A.redo_count = s->exact.redo_count; A.redo_plan = s->exact.redo_count + REDO_REGIONS * REDO_COUNT_STRIDE;
         A.redo_region_cap = (uint32_t)per_region;
-    } else if (s->exact) {
-        A.S = s->ref_view;      // no second launch (diagnostic builds, a scene switched off, an oversized frame): the tree as handed over
+    } else if (s->exact.on) {
+        A.S = s->exact.ref_view;      // no second launch (diagnostic builds, a scene switched off, an oversized frame): the tree as handed over
     }
-    if (s->grid_on && s->want_phase_stats && A.S.grid.nu != 0u) {
-        // (the diagnostic builds have no grid walk: the tree as handed over, which is what items[] holds for a grid scene in global memory)
-        A.S.grid.nu = 0u; A.S.walk_start = 0u; A.S.t_pad = 0.0f; A.S.gate_scale = 1.0f; A.S.tmin_gate = T_MIN; A.S.tie_rank = nullptr;
-    }
-    // LDS residency of the hot records
-    bool lds = s->lds_bytes != 0;
-    const uint32_t waves_per_wg = s->wg_threads / 64;
-    size_t shmem = (size_t)waves_per_wg * per_wave_lds_bytes(pick_variant(s));
-    if (lds) { A.lds_items = A.S.grid.nu != 0u ? s->grid_slots : A.S.n_items; A.lds_spheres = s->dev.n_spheres; A.lds_boxes = s->dev.n_boxes;
-        shmem += s->lds_bytes; }
-    // persistent grid: enough workgroups to fill the chip, never more than there are units
-    s->dual_last = false;
+    // (the diagnostic builds have no grid walk: the tree as handed over, which is what items[] holds for a grid scene in global memory)
+    if (s->plan.grid_on && s->want_phase_stats && A.S.grid.nu != 0u) A.S = handed_over_view(A.S);
+    return VK_OK;
+}
+
+// the shape of a frame's launches: LDS residency of the hot records, the persistent grid, the kernel variant
+struct LaunchShape {
+    bool lds; uint32_t waves_per_wg; size_t shmem;
+    uint64_t n_units;      // units the main launch will find, as far as the host knows
+    uint32_t grid;         // enough workgroups to fill the chip, never more than there are units
+    uint32_t F;
+};
+
+int plan_launch(const vk_scene *s, const vk_render_params *p, const AccumDesc *acc, KArgs &A, LaunchShape &L) {
+    L.lds = s->plan.lds_bytes != 0;
+    L.waves_per_wg = s->plan.wg_threads / 64;
+    L.shmem = (size_t)L.waves_per_wg * per_wave_lds_bytes(pick_variant(s));
+    if (L.lds) { A.lds_items = A.S.grid.nu != 0u ? s->plan.grid_slots : A.S.n_items; A.lds_spheres = s->dev.n_spheres; A.lds_boxes = s->dev.n_boxes;
+        L.shmem += s->plan.lds_bytes; }
     // (choose_chunks keeps it below)
     if ((uint64_t)A.n_local_tiles * A.n_chunks >= 0xFFFFFFFFull) return fail(VK_ERR_BAD_ARG, "tiles x sample chunks exceeds the 32-bit unit counter");
     // the grid and the dual launch are sized from the units an adaptive window will find, as far as the host knows
-    const uint64_t n_units = (adapt ? acc->known_tiles : (uint64_t)A.n_local_tiles) * A.n_chunks;
-    uint32_t grid = (uint32_t)s->num_cus * s->wgs_per_cu;
-    uint64_t need_wgs = (n_units + waves_per_wg - 1) / waves_per_wg;
-    if (grid > need_wgs) grid = (uint32_t)need_wgs;
-    if (grid < 1) grid = 1;
+    L.n_units = (acc && acc->tile_n ? acc->known_tiles : (uint64_t)A.n_local_tiles) * A.n_chunks;
+    L.grid = (uint32_t)s->num_cus * s->plan.wgs_per_cu;
+    uint64_t need_wgs = (L.n_units + L.waves_per_wg - 1) / L.waves_per_wg;
+    if (L.grid > need_wgs) L.grid = (uint32_t)need_wgs;
+    if (L.grid < 1) L.grid = 1;
+    L.F = pick_variant(s) | (p->integrator == VK_INTEGRATOR_PDF ? (uint32_t)VKF_INTEG_PDF : 0u);
+    return VK_OK;
+}
 
-    int rc = VK_OK;
-    uint32_t F = pick_variant(s) | (p->integrator == VK_INTEGRATOR_PDF ? (uint32_t)VKF_INTEG_PDF : 0u);
-    // (VK_ORDER_REUSE=0 probes every frame)
-    bool reuse_order = false;
-    if (use_order && !s->want_phase_stats && s->env.order_reuse) {
-        auto &o = s->order_for;
+// Stage 6: the order of want_tile_order into A.tile_order — the one kept from an earlier frame of this partition, or a probe launch and
+// the three sorting kernels
+int enqueue_tile_order(vk_scene *s, const vk_camera *cam, const vk_render_params *p, const TileGeom &g, const LaunchShape &L, hipStream_t st,
+    KArgs &A) {
+    auto &o = s->order.made_for;
+    if (s->env.order_reuse) {      // (VK_ORDER_REUSE=0 probes every frame)
         auto close3 = [](const float *a, const float *b, float scale) {
             float d = fabsf(a[0] - b[0]) + fabsf(a[1] - b[1]) + fabsf(a[2] - b[2]);
             return d <= 0.05f * scale;
         };
         const float hscale = fabsf(cam->horizontal[0]) + fabsf(cam->horizontal[1]) + fabsf(cam->horizontal[2]) +
                              fabsf(cam->vertical[0]) + fabsf(cam->vertical[1]) + fabsf(cam->vertical[2]);      // size of the view plane
-        reuse_order = o.valid && o.width == p->width && o.height == p->height && o.rank == g.rank && o.world == g.world &&
-                      o.depth == p->max_depth && o.age < 16u && close3(o.org, cam->origin, hscale) &&
-                      close3(o.llc, cam->lower_left_corner, hscale);
-        if (reuse_order) { o.age++; A.tile_order = s->tile_order; }
+        const bool reuse = o.valid && o.width == p->width && o.height == p->height && o.rank == g.rank && o.world == g.world &&
+                           o.depth == p->max_depth && o.age < 16u && close3(o.org, cam->origin, hscale) &&
+                           close3(o.llc, cam->lower_left_corner, hscale);
+        if (reuse) { o.age++; A.tile_order = s->order.order; return VK_OK; }
     }
-    if (use_order && !s->want_phase_stats && !reuse_order) {
-        KArgs B = A;                                   // the probe: the same view at 1..4 samples per pixel, one unit per tile
-        // (C2, one rank's 1/8 share: probe of 1 / 2 / 4 / 8 / 16 spp -> 68.6 / 69.0 / 69.8 / 70.5 / 73.0 ms: more samples cost more than
-        // they sort better)
-        B.C.spp = p->samples_per_pixel / 1024u; B.C.spp = B.C.spp < 1u ? 1u : (B.C.spp > 4u ? 4u : B.C.spp);
-        // diagnostics
-        if (s->env.probe_spp >= 1 && (uint32_t)s->env.probe_spp <= p->samples_per_pixel) B.C.spp = (uint32_t)s->env.probe_spp;
-        // the probe only ranks the tiles: its paths are cut at 16 segments, so that this short launch does not end on a handful of
-        // 50-segment paths (one rank's 1/8 share, efficiency against the whole frame / 8 with the cut at 50 / 16 / 8: C2 0.937 / 0.949 /
-        // 0.948, C3 0.93 / 0.95 / 0.96, C5 0.957 / 0.957 / 0.951 — deep paths are part of what makes C5's tiles dear)
-        {
-            const uint32_t cut = s->env.probe_depth >= 1 ? (uint32_t)s->env.probe_depth : 16u;
-            if (B.C.max_depth > cut) B.C.max_depth = cut;
-        }
-        B.n_chunks = 1; B.accum = nullptr; B.debug = nullptr; B.tile_order = nullptr;   // no sums: the probe only times the tiles
-        B.redo_list = nullptr;                         // ... and drops nothing
-        B.tile_cost = s->tile_cost;
-        HIP_TRY(hipMemsetAsync(s->tile_cost, 0, (size_t)tiles * sizeof(uint32_t), st));
-        HIP_TRY(hipMemsetAsync(s->counter, 0, sizeof(uint32_t), st));
-        uint32_t pgrid = (uint32_t)s->num_cus * s->wgs_per_cu, pneed = (A.n_local_tiles + waves_per_wg - 1) / waves_per_wg;
-        if (pgrid > pneed) pgrid = pneed;
-        rc = launch_by_features(s, F, B, lds, dim3(pgrid), shmem, st, true);
-        if (rc != VK_OK) return rc;
-        uint32_t nb = (A.n_local_tiles + 255u) / 256u;
-        HIP_TRY(hipMemsetAsync(s->order_hist, 0, ORDER_BUCKETS * sizeof(uint32_t), st));
-        hipLaunchKernelGGL(order_hist_kernel, dim3(nb), dim3(256), 0, st, (const uint32_t *)s->tile_cost, A.n_local_tiles, A.tile_rank,
-            A.tile_world, s->order_hist);
-        hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(1), 0, st, s->order_hist);
-        hipLaunchKernelGGL(order_scatter_kernel, dim3(nb), dim3(256), 0, st, s->tile_cost, A.n_local_tiles, A.tile_rank, A.tile_world,
-            s->order_hist, s->tile_order);
-        HIP_TRY(hipGetLastError());
-        A.tile_order = s->tile_order;
-        auto &o = s->order_for;
-        o.valid = true; o.width = p->width; o.height = p->height; o.rank = g.rank; o.world = g.world; o.depth = p->max_depth; o.age = 0;
-        for (int k = 0; k < 3; k++) { o.org[k] = cam->origin[k]; o.llc[k] = cam->lower_left_corner[k]; }
+    KArgs B = A;                                   // the probe: the same view at 1..4 samples per pixel, one unit per tile
+    // (C2, one rank's 1/8 share: probe of 1 / 2 / 4 / 8 / 16 spp -> 68.6 / 69.0 / 69.8 / 70.5 / 73.0 ms: more samples cost more than
+    // they sort better)
+    B.C.spp = p->samples_per_pixel / 1024u; B.C.spp = B.C.spp < 1u ? 1u : (B.C.spp > 4u ? 4u : B.C.spp);
+    // diagnostics
+    if (s->env.probe_spp >= 1 && (uint32_t)s->env.probe_spp <= p->samples_per_pixel) B.C.spp = (uint32_t)s->env.probe_spp;
+    // the probe only ranks the tiles: its paths are cut at 16 segments, so that this short launch does not end on a handful of
+    // 50-segment paths (one rank's 1/8 share, efficiency against the whole frame / 8 with the cut at 50 / 16 / 8: C2 0.937 / 0.949 /
+    // 0.948, C3 0.93 / 0.95 / 0.96, C5 0.957 / 0.957 / 0.951 — deep paths are part of what makes C5's tiles dear)
+    {
+        const uint32_t cut = s->env.probe_depth >= 1 ? (uint32_t)s->env.probe_depth : 16u;
+        if (B.C.max_depth > cut) B.C.max_depth = cut;
     }
-    if (adapt) {
-        // the active slots, filtered from the tile order of this window (dearest first, or raster): count, then scatter in order
-        if (g.n_local == 0) {
-            HIP_TRY(hipMemsetAsync(acc->ctl, 0, sizeof(uint32_t), st));
-        } else {
-            const uint32_t nb = (g.n_local + 1023u) / 1024u;
-            hipLaunchKernelGGL(adaptive_count_kernel, dim3(nb), dim3(1024), 0, st, A.tile_order, (const uint32_t *)acc->tile_n, g.n_local,
-                               acc->ctl + 4);
-            hipLaunchKernelGGL(adaptive_scatter_kernel, dim3(nb), dim3(1024), 0, st, A.tile_order, (const uint32_t *)acc->tile_n, g.n_local,
-                               (const uint32_t *)(acc->ctl + 4), acc->list, acc->ctl);
-            HIP_TRY(hipGetLastError());
-        }
-        A.tile_order = acc->list;
-        A.active_count = acc->ctl;
-    }
-    HIP_TRY(hipMemsetAsync(s->counter, 0, 32, st));       // work counter, this frame's clamped-sample count, per-launch unit counts
-#ifdef VK_DEBUG_LIB
-    if (s->want_phase_stats) {
-        const uint32_t FULLPDF = VKF_ALL_SCENE | VKF_INTEG_PDF;
-        const uint32_t CORNELLPDF = VKF_RECT | VKF_LIST | VKF_INSTANCE | VKF_BOX | VKF_INTEG_PDF;
-        if (F != 0u && F != FULLPDF && F != CORNELLPDF)
-            return fail(VK_ERR_UNSUPPORTED, "phase statistics are only built for the sphere-only/scatter, the Cornell-type/PDF and the full/PDF variants");
-        if (!s->phase_stats) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->phase_stats), 24 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(s->phase_stats, 0, 24 * sizeof(unsigned long long), st));
-        A.phase_stats = s->phase_stats;
-        auto go = [&](auto kernel) -> int {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-            hipLaunchKernelGGL(kernel, dim3(grid), dim3(s->wg_threads), shmem, st, A);
-            return VK_OK;
-        };
-        if (F == 0u) rc = lds ? go(&render_kernel<0u, true, 6, true>) : go(&render_kernel<0u, false, 6, true>);
-        else if (F == CORNELLPDF) rc = lds ? go(&render_kernel<CORNELLPDF, true, 6, true>) : go(&render_kernel<CORNELLPDF, false, 6, true>);
-        else rc = lds ? go(&render_kernel<FULLPDF, true, 4, true>) : go(&render_kernel<FULLPDF, false, 4, true>);
-        if (rc != VK_OK) return rc;
-        HIP_TRY(hipGetLastError());
-        F = 0xFFFFFFFFu;   // launched
-    }
-#endif
-    if (F != 0xFFFFFFFFu) {
-        // enough units for 28 waves per CU to stay busy: the dual launch; else (tiny frames) the single 2 x 768-thread shape
-        const bool dual = s->dual_launch && lds && n_units >= (uint64_t)s->num_cus * 28u * 4u && s->stream2;
-        if (dual) {
-            // seven waves per SIMD hide more of a parked lane's wait: shading deferred 5x, pending sphere tests served at 2x weight
-            // (C2 at 256 spp, (defer, weight): (4,1) 6 098, (5,1) 6 166, (5,2) 6 230, (6,2) 6 208, (8,2) 6 230, (5,3) 6 071 Msamples/s)
-            // (on the rebuilt tree of exact re-treeing, 256 spp: (4,1) 7 295, (5,2) 7 395, (6,2) 7 445, (8,2) 7 435, (6,3) 7 444)
-            if (!(s->env.shade_defer >= 1 && s->env.shade_defer <= 64)) A.shade_defer = 6u;
-            if (!(s->env.prim_weight >= 1 && s->env.prim_weight <= 64)) A.prim_weight = 2u;
-        }
-        const bool gridw = A.S.grid.nu != 0u;
-        if (dual && F == 0u) rc = gridw ? launch_dual<0u, true>(s, A, per_wave_lds_bytes(0u), st) : launch_dual<0u>(s, A, per_wave_lds_bytes(0u), st);
-        else if (dual && F == (uint32_t)VKF_INTEG_PDF) rc = launch_dual<VKF_INTEG_PDF>(s, A, per_wave_lds_bytes(0u), st);
-        else rc = launch_by_features(s, F, A, lds, dim3(grid), shmem, st, false);
-    }
+    B.n_chunks = 1; B.accum = nullptr; B.debug = nullptr; B.tile_order = nullptr;   // no sums: the probe only times the tiles
+    B.redo_list = nullptr;                         // ... and drops nothing
+    B.tile_cost = s->order.cost;
+    HIP_TRY(hipMemsetAsync(s->order.cost, 0, (size_t)g.tiles * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(s->counter, 0, sizeof(uint32_t), st));
+    uint32_t pgrid = (uint32_t)s->num_cus * s->plan.wgs_per_cu, pneed = (A.n_local_tiles + L.waves_per_wg - 1) / L.waves_per_wg;
+    if (pgrid > pneed) pgrid = pneed;
+    int rc = launch_by_features(s, L.F, B, L.lds, dim3(pgrid), L.shmem, st, true);
     if (rc != VK_OK) return rc;
-    // (an adaptive window with few active tiles is lopsided by construction: it must not strike the scene's dual launch off)
-    if (adapt) s->dual_last = false;
-    if (exact) {
-        // the second launch: the queued samples on the scene as handed over, in the single-launch shape
-        uint32_t *plan = s->redo_count + REDO_REGIONS * REDO_COUNT_STRIDE;
-        hipLaunchKernelGGL(redo_plan_kernel, dim3(1), dim3(REDO_REGIONS), 0, st, (const uint32_t *)s->redo_count, A.redo_region_cap, plan,
-            (uint32_t)s->num_cus * s->wgs_per_cu * waves_per_wg);
-        HIP_TRY(hipMemsetAsync(s->counter, 0, sizeof(uint32_t), st));      // the unit counter only: clamped samples and unit counts add up
-        KArgs B = A;
-        B.S = s->ref_view; B.list_mode = 1u; B.tile_order = nullptr; B.active_count = nullptr; B.wave_times = nullptr;
-        if (lds) B.lds_items = B.S.n_items;
-        B.shade_defer = SHADE_DEFER; B.prim_weight = s->hot_bytes > (4u << 20) ? 3u : 1u;
-        rc = launch_by_features(s, F, B, lds, dim3((uint32_t)s->num_cus * s->wgs_per_cu), shmem, st, false);
-        if (rc != VK_OK) return rc;
-        // ... and the fallback behind it: should a queue have overflowed, the sums are cleared and the partition is rendered on the tree
-        // as handed over, so that a frame is never incomplete whoever the caller is (nearly always: two launches that return at once)
-        hipLaunchKernelGGL(redo_reset_kernel, dim3(1024), dim3(256), 0, st, (const uint32_t *)plan, reinterpret_cast<unsigned long long *>(s->accum),
-            n_pixels * 3, s->counter);
-        KArgs Fb = A;
-        Fb.S = s->ref_view; Fb.list_mode = 2u; Fb.redo_list = nullptr; Fb.wave_times = nullptr;
-        if (lds) Fb.lds_items = Fb.S.n_items;
-        Fb.shade_defer = SHADE_DEFER; Fb.prim_weight = B.prim_weight;
-        rc = launch_by_features(s, F, Fb, lds, dim3(grid), shmem, st, false);
-        if (rc != VK_OK) return rc;
-        // the plan travels to the slot the previous frame did not use — unless that slot's verdict is still in flight (two frames behind and
-        // not finished: the caller runs far ahead), then this frame goes unjudged rather than overwriting it
-        const int b = s->plan_last ^ 1;
-        s->redo_last = true;
-        if (!s->plan_pending[b]) {
-            HIP_TRY(hipMemcpyAsync(s->plan_host + 4 * b, plan, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipEventRecord(s->ev_plan[b], st));
-            s->plan_pending[b] = true; s->plan_samples[b] = s->redo_last_samples; s->plan_last = b;
-            s->plan_copied = true;
-        } else s->plan_copied = false;
+    uint32_t nb = (A.n_local_tiles + 255u) / 256u;
+    HIP_TRY(hipMemsetAsync(s->order.hist, 0, ORDER_BUCKETS * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(order_hist_kernel, dim3(nb), dim3(256), 0, st, (const uint32_t *)s->order.cost, A.n_local_tiles, A.tile_rank,
+        A.tile_world, s->order.hist.get());
+    hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(1), 0, st, s->order.hist.get());
+    hipLaunchKernelGGL(order_scatter_kernel, dim3(nb), dim3(256), 0, st, s->order.cost.get(), A.n_local_tiles, A.tile_rank, A.tile_world,
+        s->order.hist.get(), s->order.order.get());
+    HIP_TRY(hipGetLastError());
+    A.tile_order = s->order.order;
+    o.valid = true; o.width = p->width; o.height = p->height; o.rank = g.rank; o.world = g.world; o.depth = p->max_depth; o.age = 0;
+    for (int k = 0; k < 3; k++) { o.org[k] = cam->origin[k]; o.llc[k] = cam->lower_left_corner[k]; }
+    return VK_OK;
+}
+
+// Stage 7, an adaptive window: the active slots, filtered from the tile order of this window (dearest first, or raster): count, then
+// scatter in order
+int enqueue_adaptive_compaction(const AccumDesc *acc, const TileGeom &g, hipStream_t st, KArgs &A) {
+    if (g.n_local == 0) {
+        HIP_TRY(hipMemsetAsync(acc->ctl, 0, sizeof(uint32_t), st));
+    } else {
+        const uint32_t nb = (g.n_local + 1023u) / 1024u;
+        hipLaunchKernelGGL(adaptive_count_kernel, dim3(nb), dim3(1024), 0, st, A.tile_order, (const uint32_t *)acc->tile_n, g.n_local,
+                           acc->ctl + 4);
+        hipLaunchKernelGGL(adaptive_scatter_kernel, dim3(nb), dim3(1024), 0, st, A.tile_order, (const uint32_t *)acc->tile_n, g.n_local,
+                           (const uint32_t *)(acc->ctl + 4), acc->list, acc->ctl);
+        HIP_TRY(hipGetLastError());
     }
-    if (adapt) {
+    A.tile_order = acc->list;
+    A.active_count = acc->ctl;
+    return VK_OK;
+}
+
+#ifdef VK_DEBUG_LIB
+// Stage 8 of vk_debug_phase_stats: the instrumented (STATS) build of the variant, in the single-launch shape
+int launch_phase_stats(vk_scene *s, const LaunchShape &L, hipStream_t st, KArgs &A) {
+    const uint32_t FULLPDF = VKF_ALL_SCENE | VKF_INTEG_PDF;
+    const uint32_t CORNELLPDF = VKF_RECT | VKF_LIST | VKF_INSTANCE | VKF_BOX | VKF_INTEG_PDF;
+    if (L.F != 0u && L.F != FULLPDF && L.F != CORNELLPDF)
+        return fail(VK_ERR_UNSUPPORTED, "phase statistics are only built for the sphere-only/scatter, the Cornell-type/PDF and the full/PDF variants");
+    int rc = s->phase_stats.ensure(24 * sizeof(unsigned long long));
+    if (rc != VK_OK) return rc;
+    HIP_TRY(hipMemsetAsync(s->phase_stats, 0, 24 * sizeof(unsigned long long), st));
+    A.phase_stats = s->phase_stats;
+    auto go = [&](auto kernel) -> int {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.shmem));
+        hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(s->plan.wg_threads), L.shmem, st, A);
+        return VK_OK;
+    };
+    if (L.F == 0u) rc = L.lds ? go(&render_kernel<0u, true, 6, true>) : go(&render_kernel<0u, false, 6, true>);
+    else if (L.F == CORNELLPDF) rc = L.lds ? go(&render_kernel<CORNELLPDF, true, 6, true>) : go(&render_kernel<CORNELLPDF, false, 6, true>);
+    else rc = L.lds ? go(&render_kernel<FULLPDF, true, 4, true>) : go(&render_kernel<FULLPDF, false, 4, true>);
+    if (rc != VK_OK) return rc;
+    HIP_TRY(hipGetLastError());
+    return VK_OK;
+}
+#endif
+
+// Stage 8: the frame's launch — with enough units for 28 waves per CU to stay busy the dual launch, else (tiny frames) the single
+// 2 x 768-thread shape
+int launch_main(vk_scene *s, const LaunchShape &L, hipStream_t st, KArgs &A) {
+    const bool dual = s->plan.dual_launch && L.lds && L.n_units >= (uint64_t)s->num_cus * 28u * 4u && s->dual.stream2;
+    if (dual) {
+        // seven waves per SIMD hide more of a parked lane's wait: shading deferred 5x, pending sphere tests served at 2x weight
+        // (C2 at 256 spp, (defer, weight): (4,1) 6 098, (5,1) 6 166, (5,2) 6 230, (6,2) 6 208, (8,2) 6 230, (5,3) 6 071 Msamples/s)
+        // (on the rebuilt tree of exact re-treeing, 256 spp: (4,1) 7 295, (5,2) 7 395, (6,2) 7 445, (8,2) 7 435, (6,3) 7 444)
+        if (!(s->env.shade_defer >= 1 && s->env.shade_defer <= 64)) A.shade_defer = 6u;
+        if (!(s->env.prim_weight >= 1 && s->env.prim_weight <= 64)) A.prim_weight = 2u;
+    }
+    const bool gridw = A.S.grid.nu != 0u;
+    if (dual && L.F == 0u) return gridw ? launch_dual<0u, true>(s, A, per_wave_lds_bytes(0u), st) : launch_dual<0u>(s, A, per_wave_lds_bytes(0u), st);
+    if (dual && L.F == (uint32_t)VKF_INTEG_PDF) return launch_dual<VKF_INTEG_PDF>(s, A, per_wave_lds_bytes(0u), st);
+    return launch_by_features(s, L.F, A, L.lds, dim3(L.grid), L.shmem, st, false);
+}
+
+// Stage 9, exact re-treeing: the second launch, the fallback launch behind it and the copy of the frame's plan to a verdict slot
+int enqueue_redo(vk_scene *s, const KArgs &A, const LaunchShape &L, size_t n_pixels, hipStream_t st) {
+    // the second launch: the queued samples on the scene as handed over, in the single-launch shape
+    uint32_t *plan = s->exact.redo_count + REDO_REGIONS * REDO_COUNT_STRIDE;
+    hipLaunchKernelGGL(redo_plan_kernel, dim3(1), dim3(REDO_REGIONS), 0, st, (const uint32_t *)s->exact.redo_count, A.redo_region_cap, plan,
+        (uint32_t)s->num_cus * s->plan.wgs_per_cu * L.waves_per_wg);
+    HIP_TRY(hipMemsetAsync(s->counter, 0, sizeof(uint32_t), st));      // the unit counter only: clamped samples and unit counts add up
+    KArgs B = A;
+    B.S = s->exact.ref_view; B.list_mode = 1u; B.tile_order = nullptr; B.active_count = nullptr; B.wave_times = nullptr;
+    if (L.lds) B.lds_items = B.S.n_items;
+    B.shade_defer = SHADE_DEFER; B.prim_weight = s->plan.hot_bytes > (4u << 20) ? 3u : 1u;
+    int rc = launch_by_features(s, L.F, B, L.lds, dim3((uint32_t)s->num_cus * s->plan.wgs_per_cu), L.shmem, st, false);
+    if (rc != VK_OK) return rc;
+    // ... and the fallback behind it: should a queue have overflowed, the sums are cleared and the partition is rendered on the tree
+    // as handed over, so that a frame is never incomplete whoever the caller is (nearly always: two launches that return at once)
+    hipLaunchKernelGGL(redo_reset_kernel, dim3(1024), dim3(256), 0, st, (const uint32_t *)plan, reinterpret_cast<unsigned long long *>(s->accum.get()),
+        n_pixels * 3, s->counter.get());
+    KArgs Fb = A;
+    Fb.S = s->exact.ref_view; Fb.list_mode = 2u; Fb.redo_list = nullptr; Fb.wave_times = nullptr;
+    if (L.lds) Fb.lds_items = Fb.S.n_items;
+    Fb.shade_defer = SHADE_DEFER; Fb.prim_weight = B.prim_weight;
+    rc = launch_by_features(s, L.F, Fb, L.lds, dim3(L.grid), L.shmem, st, false);
+    if (rc != VK_OK) return rc;
+    // the plan travels to the slot the previous frame did not use — unless that slot's verdict is still in flight (two frames behind and
+    // not finished: the caller runs far ahead), then this frame goes unjudged rather than overwriting it
+    const int b = s->exact.plan_last ^ 1;
+    s->exact.redo_last = true;
+    if (!s->exact.plan_pending[b]) {
+        HIP_TRY(hipMemcpyAsync(s->exact.plan_host + 4 * b, plan, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(s->exact.ev_plan[b], st));
+        s->exact.plan_pending[b] = true; s->exact.plan_samples[b] = s->exact.redo_last_samples; s->exact.plan_last = b;
+        s->exact.plan_copied = true;
+    } else s->exact.plan_copied = false;
+    return VK_OK;
+}
+
+// Stage 10: the frame's fixed-point sums into d_out — plainly, into a progressive handle's running sums, or as an adaptive window
+int enqueue_resolve(const KArgs &A, const vk_render_params *p, const TileGeom &g, float *d_out, const AccumDesc *acc, hipStream_t st) {
+    const size_t n_pixels = (size_t)p->width * p->height;
+    const uint32_t blocks = (uint32_t)((n_pixels + 255) / 256);
+    if (acc && acc->tile_n) {
         // adaptive: the active tiles' sums into the running sums, every pixel's mean over its tile's samples into d_out; then the judge
         // freezes the tiles that have converged and counts the others for the host (pinned copy, landed by ev_done)
-        uint32_t blocks = (uint32_t)((n_pixels + 255) / 256);
         hipLaunchKernelGGL(adaptive_resolve_kernel, dim3(blocks), dim3(256), 0, st, (const long long *)A.accum, acc->run, acc->m2, d_out,
                            p->width, p->height, p->samples_per_pixel, acc->done, A.tiles_x, A.tile_rank, A.tile_world,
                            (const uint32_t *)acc->tile_n, (const unsigned long long *)A.clamped, acc->clamped);
@@ -907,24 +949,94 @@ int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(acc->h_left, acc->ctl + 1, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipEventRecord(acc->ev_done, st));
-        if (stats) stats->kernel_launches = 2;
     } else if (acc) {
         // progressive: the window's sums into the running sums, the running mean into d_out (the window's sums stay in s->accum until
-        // here, so the fallback above re-renders this window only and earlier windows are untouched)
-        uint32_t blocks = (uint32_t)((n_pixels + 255) / 256);
+        // here, so the fallback launch re-renders this window only and earlier windows are untouched)
         hipLaunchKernelGGL(accumulate_resolve_kernel, dim3(blocks), dim3(256), 0, st, (const long long *)A.accum, acc->run, acc->m2, d_out,
                            p->width, p->height, p->samples_per_pixel, acc->done, A.tiles_x, A.tile_rank, A.tile_world,
                            (const unsigned long long *)A.clamped, acc->clamped);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(acc->ev_done, st));
-        if (stats) stats->kernel_launches = 2;
     } else {
-        uint32_t blocks = (uint32_t)((n_pixels + 255) / 256);
         hipLaunchKernelGGL(resolve_kernel, dim3(blocks), dim3(256), 0, st, (const long long *)A.accum, d_out, p->width, p->height,
                            p->samples_per_pixel, A.tiles_x, A.tile_rank, A.tile_world);
         HIP_TRY(hipGetLastError());
-        if (stats) stats->kernel_launches = 2;
     }
+    return VK_OK;
+}
+
+// Enqueues one render of this call's tile partition into the f32 framebuffer d_out (device memory of s->device) on `st`.  With `acc`
+// (progressive rendering): one window of samples, added into acc's running sums, d_out = their running mean.
+int enqueue_render_f32(vk_scene *s, const vk_camera *cam, const vk_render_params *p, float *d_out, hipStream_t st, bool want_debug,
+    vk_stats *stats, const AccumDesc *acc = nullptr) {
+    HIP_TRY(hipSetDevice(s->device));
+    s->launch_log.clear();
+    const TileGeom g(p);
+    const bool adapt = acc && acc->tile_n;
+    const size_t n_pixels = (size_t)p->width * p->height;
+    // (an adaptive window: the samples of its active tiles, as far as the host knows)
+    const uint64_t frame_samples = adapt ? acc->known_px * p->samples_per_pixel : partition_samples(p, g);
+    KArgs A;
+    memset(&A, 0, sizeof(A));
+    A.S = s->dev;
+    bool exact = begin_frame_exact(s);
+    near_form_primary_rays(s, cam, A.S, exact);
+    int rc = fill_render_args(s, cam, p, g, d_out, acc, st, A);
+    if (rc != VK_OK) return rc;
+    if (stats) {
+        stats->samples = frame_samples;
+        stats->kernel_launches = p->max_depth == 0 ? 1 : 2;      // (render + resolve)
+        stats->scene_in_lds = s->plan.lds_bytes ? 1u : 0u;
+        stats->kernel_ms = 0.0; stats->seconds = 0.0;
+    }
+    if (want_debug) {
+        size_t need = n_pixels * p->samples_per_pixel * sizeof(float4);
+        rc = s->debug.ensure(need);
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipMemsetAsync(s->debug, 0, need, st));
+        A.debug = s->debug;
+    }
+    HIP_TRY(hipEventRecord(s->ev0, st));
+    if (p->max_depth == 0) return enqueue_black_frame(s, p, g, d_out, st, acc);
+    bool use_order = false;
+    rc = want_tile_order(s, p, g, use_order);
+    if (rc != VK_OK) return rc;
+    {   // order-independent pixel sums (vk_kernels.h to_fixed): zeroed per frame, resolved into d_out after the launch
+        rc = s->accum.ensure(n_pixels * 3 * sizeof(long long));
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipMemsetAsync(s->accum, 0, n_pixels * 3 * sizeof(long long), st));
+        A.accum = s->accum;
+    }
+    s->exact.redo_last = false;
+    s->dual.last = false;
+    rc = arm_redo_queues(s, frame_samples, st, A, exact);
+    if (rc != VK_OK) return rc;
+    LaunchShape L;
+    rc = plan_launch(s, p, acc, A, L);
+    if (rc != VK_OK) return rc;
+    if (use_order && !s->want_phase_stats) {
+        rc = enqueue_tile_order(s, cam, p, g, L, st, A);
+        if (rc != VK_OK) return rc;
+    }
+    if (adapt) {
+        rc = enqueue_adaptive_compaction(acc, g, st, A);
+        if (rc != VK_OK) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(s->counter, 0, 32, st));       // work counter, this frame's clamped-sample count, per-launch unit counts
+#ifdef VK_DEBUG_LIB
+    if (s->want_phase_stats) rc = launch_phase_stats(s, L, st, A);
+    else
+#endif
+    rc = launch_main(s, L, st, A);
+    if (rc != VK_OK) return rc;
+    // (an adaptive window with few active tiles is lopsided by construction: it must not strike the scene's dual launch off)
+    if (adapt) s->dual.last = false;
+    if (exact) {
+        rc = enqueue_redo(s, A, L, n_pixels, st);
+        if (rc != VK_OK) return rc;
+    }
+    rc = enqueue_resolve(A, p, g, d_out, acc, st);
+    if (rc != VK_OK) return rc;
     HIP_TRY(hipEventRecord(s->ev1, st));
     s->last_timed = true;
     return VK_OK;
@@ -935,7 +1047,7 @@ int enqueue_render_single(vk_scene *s, const vk_camera *cam, const vk_render_par
     vk_stats *stats, const AccumDesc *acc) {
     if (p->output_format == VK_OUTPUT_F32) return enqueue_render_f32(s, cam, p, reinterpret_cast<float *>(d_out), st, want_debug, stats, acc);
     HIP_TRY(hipSetDevice(s->device));
-    int rc = ensure(s->fb, s->fb_bytes, (size_t)p->width * p->height * 3 * sizeof(float));
+    int rc = s->fb.ensure((size_t)p->width * p->height * 3 * sizeof(float));
     if (rc != VK_OK) return rc;
     rc = enqueue_render_f32(s, cam, p, s->fb, st, want_debug, stats, acc);
     if (rc != VK_OK) return rc;
@@ -948,83 +1060,83 @@ int enqueue_render_single(vk_scene *s, const vk_camera *cam, const vk_render_par
 // one descriptor per part, holding that part's running sums on its own device.
 int enqueue_render_multi(vk_scene *grp, const vk_camera *cam, const vk_render_params *p, void *d_out, hipStream_t st0, vk_stats *stats,
     const AccumDesc *acc) {
-    const uint32_t n = (uint32_t)grp->parts.size();
+    const uint32_t n = (uint32_t)grp->group.parts.size();
     const TileGeom g(p);
     const bool u8 = p->output_format == VK_OUTPUT_RGB8;
     const size_t slot_bytes = u8 ? 3 : 12;
     HIP_TRY(hipSetDevice(grp->device));
-    HIP_TRY(hipEventRecord(grp->ev_begin, st0));      // the parts start after whatever the caller's stream held before this frame
+    HIP_TRY(hipEventRecord(grp->group.ev_begin, st0));      // the parts start after whatever the caller's stream held before this frame
     uint64_t samples = 0; uint32_t launches = 0;
     std::vector<TileGeom> geoms;
     std::vector<size_t> slab_size;
     for (uint32_t j = 0; j < n; j++) {
-        vk_scene *q = grp->parts[j];
+        vk_scene *q = grp->group.parts[j];
         vk_render_params pj = *p;
         pj.tile_rank = g.rank + g.world * j; pj.tile_world = g.world * n; pj.output_format = VK_OUTPUT_F32;
         const TileGeom gj(&pj);
         geoms.push_back(gj);
         HIP_TRY(hipSetDevice(q->device));
-        HIP_TRY(hipStreamWaitEvent(q->stream, grp->ev_begin, 0));
-        int rc = ensure(q->fb, q->fb_bytes, (size_t)p->width * p->height * 3 * sizeof(float));
+        HIP_TRY(hipStreamWaitEvent(q->group.stream, grp->group.ev_begin, 0));
+        int rc = q->fb.ensure((size_t)p->width * p->height * 3 * sizeof(float));
         if (rc != VK_OK) return rc;
         vk_stats sj;
         memset(&sj, 0, sizeof(sj));
-        rc = enqueue_render_f32(q, cam, &pj, q->fb, q->stream, false, &sj, acc ? &acc[j] : nullptr);
+        rc = enqueue_render_f32(q, cam, &pj, q->fb, q->group.stream, false, &sj, acc ? &acc[j] : nullptr);
         if (rc != VK_OK) return rc;
         samples += sj.samples; launches += sj.kernel_launches;
         size_t bytes = (size_t)gj.n_local * 64u * slot_bytes;
-        rc = ensure(q->slab, q->slab_bytes, bytes);
+        rc = q->group.slab.ensure(bytes);
         if (rc != VK_OK) return rc;
-        rc = u8 ? tile_move<TM_PACK_U8>(q->fb, q->slab, &pj, gj, q->stream) : tile_move<TM_PACK_F32>(q->fb, q->slab, &pj, gj, q->stream);
+        rc = u8 ? tile_move<TM_PACK_U8>(q->fb, q->group.slab, &pj, gj, q->group.stream) : tile_move<TM_PACK_F32>(q->fb, q->group.slab, &pj, gj, q->group.stream);
         if (rc != VK_OK) return rc;
-        if (bytes > q->landing_bytes) {                // the landing buffer lives on devices[0]
+        if (bytes > q->group.landing.bytes()) {                // the landing buffer lives on devices[0]
             HIP_TRY(hipSetDevice(grp->device));
-            rc = ensure(q->landing, q->landing_bytes, bytes);
+            rc = q->group.landing.ensure(bytes);
             if (rc != VK_OK) return rc;
             HIP_TRY(hipSetDevice(q->device));
         }
         slab_size.push_back(bytes);
-        if (grp->comms.empty()) {
-            if (bytes) HIP_TRY(hipMemcpyPeerAsync(q->landing, grp->device, q->slab, q->device, bytes, q->stream));
-            HIP_TRY(hipEventRecord(q->ev_landed, q->stream));
+        if (grp->group.comms.empty()) {
+            if (bytes) HIP_TRY(hipMemcpyPeerAsync(q->group.landing, grp->device, q->group.slab, q->device, bytes, q->group.stream));
+            HIP_TRY(hipEventRecord(q->group.ev_landed, q->group.stream));
         }
     }
-    if (!grp->comms.empty()) {
+    if (!grp->group.comms.empty()) {
         // The same exchange as ONE RCCL group: part j sends its slab on its own stream (behind its render and pack), devices[0] receives
         // the slabs on the group's receive stream, which waits for nothing but the start of the frame (the previous frame's unpack
         // kernels have read the landing buffers by then) — so the transfers overlap devices[0]'s own render.  ncclSend / ncclRecv pairs
         // inside one ncclGroupStart / ncclGroupEnd progress together; the receives complete in that stream's order, so ONE event says
         // that every slab has landed.  Part 0's slab is on devices[0] already and is unpacked where it lies.
         const RcclApi &R = rccl_api();
-        vk_scene *q0 = grp->parts[0];
+        vk_scene *q0 = grp->group.parts[0];
         HIP_TRY(hipSetDevice(q0->device));
-        HIP_TRY(hipEventRecord(q0->ev_landed, q0->stream));
-        HIP_TRY(hipStreamWaitEvent(grp->stream, grp->ev_begin, 0));
+        HIP_TRY(hipEventRecord(q0->group.ev_landed, q0->group.stream));
+        HIP_TRY(hipStreamWaitEvent(grp->group.stream, grp->group.ev_begin, 0));
         RCCL_TRY(R.GroupStart());
         for (uint32_t j = 1; j < n; j++) {
-            vk_scene *q = grp->parts[j];
+            vk_scene *q = grp->group.parts[j];
             if (!slab_size[j]) continue;
-            RCCL_TRY(R.Send(q->slab, slab_size[j], ncclUint8, 0, grp->comms[j], q->stream));
-            RCCL_TRY(R.Recv(q->landing, slab_size[j], ncclUint8, (int)j, grp->comms[0], grp->stream));
+            RCCL_TRY(R.Send(q->group.slab, slab_size[j], ncclUint8, 0, grp->group.comms[j], q->group.stream));
+            RCCL_TRY(R.Recv(q->group.landing, slab_size[j], ncclUint8, (int)j, grp->group.comms[0], grp->group.stream));
         }
         RCCL_TRY(R.GroupEnd());
         HIP_TRY(hipSetDevice(grp->device));
-        HIP_TRY(hipEventRecord(grp->ev_landed, grp->stream));
+        HIP_TRY(hipEventRecord(grp->group.ev_landed, grp->group.stream));
     }
     HIP_TRY(hipSetDevice(grp->device));
     for (uint32_t j = 0; j < n; j++) {
-        vk_scene *q = grp->parts[j];
+        vk_scene *q = grp->group.parts[j];
         vk_render_params pj = *p;
         pj.tile_rank = geoms[j].rank; pj.tile_world = geoms[j].world;
-        const bool rccl = !grp->comms.empty();
-        HIP_TRY(hipStreamWaitEvent(st0, (rccl && j != 0u ? grp : q)->ev_landed, 0));
-        const void *from = rccl && j == 0u ? q->slab : q->landing;
+        const bool rccl = !grp->group.comms.empty();
+        HIP_TRY(hipStreamWaitEvent(st0, (rccl && j != 0u ? grp : q)->group.ev_landed, 0));
+        const void *from = rccl && j == 0u ? q->group.slab.get() : q->group.landing.get();
         int rc = u8 ? tile_move<TM_UNPACK_U8>(from, d_out, &pj, geoms[j], st0) : tile_move<TM_UNPACK_F32>(from, d_out, &pj, geoms[j], st0);
         if (rc != VK_OK) return rc;
     }
     grp->last_timed = true;
     if (stats) {
-        stats->samples = samples; stats->kernel_launches = launches; stats->scene_in_lds = grp->parts[0]->lds_bytes ? 1u : 0u;
+        stats->samples = samples; stats->kernel_launches = launches; stats->scene_in_lds = grp->group.parts[0]->plan.lds_bytes ? 1u : 0u;
         stats->kernel_ms = 0.0; stats->seconds = 0.0;
     }
     return VK_OK;
@@ -1034,32 +1146,18 @@ int enqueue_render(vk_scene *s, const vk_camera *cam, const vk_render_params *p,
     vk_stats *stats, const AccumDesc *acc = nullptr) {
     int rc = check_render_args(s, cam, p);
     if (rc != VK_OK) return rc;
-    if (!s->parts.empty()) {
+    if (!s->group.parts.empty()) {
         if (want_debug) return fail(VK_ERR_UNSUPPORTED, "per-sample debug output is single-device only");
         return enqueue_render_multi(s, cam, p, d_out, st, stats, acc);
     }
     return enqueue_render_single(s, cam, p, d_out, st, want_debug, stats, acc);
 }
 
+// (the communicators before the parts whose streams they use; every device resource goes with its owner: vk_resources.h)
 void destroy_one(vk_scene *s) {
     if (!s) return;
-    for (ncclComm_t c : s->comms) if (c) (void)rccl_api().CommDestroy(c);
-    for (vk_scene *q : s->parts) destroy_one(q);
-    (void)hipSetDevice(s->device);
-    for (void *p : s->allocs) (void)hipFree(p);
-    for (void *p : {(void *)s->counter, (void *)s->fb, (void *)s->fb8, (void *)s->accum, (void *)s->debug, (void *)s->phase_stats,
-        (void *)s->tile_cost,
-                    (void *)s->tile_order, (void *)s->order_hist, (void *)s->slab, (void *)s->redo_list, (void *)s->redo_count,
-                    (void *)s->aov_buf, (void *)s->dn_buf, (void *)s->dn_io, (void *)s->ray_buf})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : s->dn_ev) if (e) (void)hipEventDestroy(e);
-    if (s->plan_host) (void)hipHostFree(s->plan_host);
-    if (s->landing) { (void)hipSetDevice(s->landing_device); (void)hipFree(s->landing); (void)hipSetDevice(s->device); }
-    for (hipEvent_t e : {s->ev0, s->ev1, s->ev_landed, s->ev_begin, s->ev_fork, s->ev_join, s->ev_plan[0], s->ev_plan[1], s->aov_ev0,
-                         s->aov_ev1, s->ray_ev0, s->ray_ev1})
-        if (e) (void)hipEventDestroy(e);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    if (s->stream2) (void)hipStreamDestroy(s->stream2);
+    for (ncclComm_t c : s->group.comms) if (c) (void)rccl_api().CommDestroy(c);
+    for (vk_scene *q : s->group.parts) destroy_one(q);
     delete s;
 }
 
@@ -1102,12 +1200,13 @@ int create_on_device(const std::shared_ptr<const LinearScene> &host, int device,
     // the grid form (DGrid): the first launch stages the table [cells | refs] instead of a tree, the second one the tree as handed over
     bool grid = H.grid.nu != 0u && rebuilt && !s->env.no_grid;
     const size_t grid_table_bytes = grid ? ((H.grid_cells.size() + H.grid_refs.size()) * sizeof(uint32_t) + 31u) / 32u * 32u : 0u;
-    // (the probe and the diagnostic builds walk the rebuilt TREE, which therefore counts too where the scene is staged in LDS)
+    // (the second launch and the diagnostic builds stage the tree as handed over, which therefore counts too where the scene is staged
+    // in LDS; the probe of a grid view walks the grid like the frame's launch: launch_variant sends its COST launches to the GRID kernel)
     if (grid) hot = std::max(grid_table_bytes, std::max(H.ref_items.size(), H.items.size()) * sizeof(DItem)) + H.spheres.size() * sizeof(DSphere);
-    s->grid_on = grid;
-    s->hot_bytes = hot;
+    s->plan.grid_on = grid;
+    s->plan.hot_bytes = hot;
     plan_residency(s.get(), hot);
-    if (grid && s->lds_bytes == 0 && !s->env.grid_global) {
+    if (grid && s->plan.lds_bytes == 0 && !s->env.grid_global) {
         // The grid form is for scenes staged in LDS.  From global memory every visited cell is three dependent cache misses (cell ->
         // references -> sphere) once the tables outgrow an XCD's L2, where a tree's top levels stay hot; and a large layer seen from far
         // away needs wide bands of cells around its primary rays (the dilation grows with the distance from the origin: 1.4 per 1 000).
@@ -1115,7 +1214,7 @@ int create_on_device(const std::shared_ptr<const LinearScene> &host, int device,
         // 1 400, a win while everything fits L2: profiles/r05/experiments/README.md).
         grid = false;
         hot = std::max(H.items.size(), H.ref_items.size()) * sizeof(DItem) + H.spheres.size() * sizeof(DSphere) + H.boxes.size() * sizeof(DBox);
-        s->grid_on = false; s->hot_bytes = hot;
+        s->plan.grid_on = false; s->plan.hot_bytes = hot;
         plan_residency(s.get(), hot);
     }
     D.gate_scale = 1.0f; D.tmin_gate = T_MIN;
@@ -1137,22 +1236,22 @@ int create_on_device(const std::shared_ptr<const LinearScene> &host, int device,
             if (rc != VK_OK) return rc;
             D.grid_refs = D.grid_cells + H.grid_cells.size();
             D.grid = H.grid;
-            s->grid_slots = (uint32_t)(grid_table_bytes / 32u);
+            s->plan.grid_slots = (uint32_t)(grid_table_bytes / 32u);
         }
         if (!H.unit_item.empty() && H.proven) { rc = upload(s.get(), H.unit_item, D.unit_item); if (rc != VK_OK) return rc; }
-        if (grid && s->lds_bytes == 0) {
+        if (grid && s->plan.lds_bytes == 0) {
             // from global memory: the first launch reads the table and the spheres only; the tree as handed over serves the second one
             // (and the diagnostic builds)
             UP(ref_items, ref_items);
             D.items = D.ref_items; D.n_ref_items = hv.n_ref_items; D.n_items = D.n_ref_items; D.n_world_items = D.n_ref_items;
             D.unit_tree = D.ref_items;
-            s->exact = true;
+            s->exact.on = true;
         } else
-        if (s->lds_bytes != 0) {
+        if (s->plan.lds_bytes != 0) {
             UP(items, items); UP(ref_items, ref_items);
             D.n_ref_items = hv.n_ref_items; D.n_items = (uint32_t)H.items.size(); D.n_world_items = H.world_items;
             D.unit_tree = D.ref_items;
-            s->exact = true;
+            s->exact.on = true;
         } else {
             uint32_t walk_start = 0;
             const std::vector<DItem> both = H.combined_items(walk_start);
@@ -1162,7 +1261,7 @@ int create_on_device(const std::shared_ptr<const LinearScene> &host, int device,
             D.unit_tree = D.items;       // (the tree as handed over comes first, item for item)
         }
     } else if (!H.ref_items.empty()) {
-        UP(ref_items, items);        // (the tree as handed over, as s->ref_view has it)
+        UP(ref_items, items);        // (the tree as handed over, as s->exact.ref_view has it)
         D.n_items = (uint32_t)H.ref_items.size(); D.n_world_items = D.n_items;
     } else {
         UP(items, items);
@@ -1182,30 +1281,27 @@ int create_on_device(const std::shared_ptr<const LinearScene> &host, int device,
         D.noise_perlin[k] = H.noise_perlin[k]; }
     D.n_spheres = (uint32_t)H.spheres.size();
     D.n_lights = (uint32_t)H.lights.size(); D.features = H.features; D.n_boxes = (uint32_t)H.boxes.size();
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->counter), 256));
-    HIP_TRY(hipEventCreate(&s->ev0));
-    HIP_TRY(hipEventCreate(&s->ev1));
+#define MAKE(expr) do { rc = (expr); if (rc != VK_OK) return rc; } while (0)
+    MAKE(s->counter.ensure(256));
+    MAKE(s->ev0.create());
+    MAKE(s->ev1.create());
     if (own_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_landed, hipEventDisableTiming));
+        MAKE(s->group.stream.create());
+        MAKE(s->group.ev_landed.create(hipEventDisableTiming));
     }
-    if (s->exact) {
-        // the scene as handed over (tests/emu/emu.cpp reference_view is the same thing on the host)
-        s->ref_view = D;
-        s->ref_view.items = D.ref_items; s->ref_view.n_items = D.n_ref_items; s->ref_view.n_world_items = D.n_ref_items;
-        s->ref_view.ref_items = nullptr; s->ref_view.n_ref_items = 0; s->ref_view.t_pad = 0.0f; s->ref_view.gate_scale = 1.0f;
-        s->ref_view.tmin_gate = T_MIN; s->ref_view.tie_rank = nullptr; s->ref_view.grid.nu = 0u;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->redo_count), (REDO_REGIONS * REDO_COUNT_STRIDE + 16) * sizeof(uint32_t)));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&s->plan_host), 8 * sizeof(uint32_t), hipHostMallocDefault));
-        memset(s->plan_host, 0, 8 * sizeof(uint32_t));
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_plan[0], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_plan[1], hipEventDisableTiming));
+    if (s->exact.on) {
+        s->exact.ref_view = handed_over_view(D);      // the second launch's scene
+        MAKE(s->exact.redo_count.ensure((REDO_REGIONS * REDO_COUNT_STRIDE + 16) * sizeof(uint32_t)));
+        HIP_TRY(s->exact.plan_host.alloc(8 * sizeof(uint32_t)));
+        MAKE(s->exact.ev_plan[0].create(hipEventDisableTiming));
+        MAKE(s->exact.ev_plan[1].create(hipEventDisableTiming));
     }
-    if (s->dual_launch) {
-        HIP_TRY(hipStreamCreateWithFlags(&s->stream2, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
+    if (s->plan.dual_launch) {
+        MAKE(s->dual.stream2.create());
+        MAKE(s->dual.ev_fork.create(hipEventDisableTiming));
+        MAKE(s->dual.ev_join.create(hipEventDisableTiming));
     }
+#undef MAKE
     out = std::move(s);
     return VK_OK;
 }
@@ -1292,7 +1388,6 @@ int vk_scene_create_multi(const vk_scene_desc *desc, const int *devices, int n_d
             ScenePtr part;
             rc = create_on_device(host, devices[j], true, part);
             if (rc != VK_OK) return rc;
-            part->landing_device = devices[0];
             if (devices[j] != devices[0]) {          // let devices[0] and this device address each other's memory (xGMI peer copies)
                 int can = 0;
                 HIP_TRY(hipDeviceCanAccessPeer(&can, devices[j], devices[0]));
@@ -1307,7 +1402,7 @@ int vk_scene_create_multi(const vk_scene_desc *desc, const int *devices, int n_d
                     (void)hipGetLastError();
                 }
             }
-            grp->parts.push_back(part.release());
+            grp->group.parts.push_back(part.release());
         }
         const bool want_rccl = (desc->flags & VK_SCENE_RCCL_GATHER) != 0u || (getenv("VK_MULTI_GATHER") && !strcmp(getenv("VK_MULTI_GATHER"), "rccl"));
         if (want_rccl) {
@@ -1322,23 +1417,23 @@ int vk_scene_create_multi(const vk_scene_desc *desc, const int *devices, int n_d
             else if (!distinct) fprintf(stderr, "vecchio_amd: VK_SCENE_RCCL_GATHER: a device is listed more than once (one communicator rank per "
                 "device); the tile slabs travel by peer copies\n");
             else {
-                grp->comms.assign((size_t)n_devices, nullptr);
-                ncclResult_t r = R.CommInitAll(grp->comms.data(), n_devices, devices);
+                grp->group.comms.assign((size_t)n_devices, nullptr);
+                ncclResult_t r = R.CommInitAll(grp->group.comms.data(), n_devices, devices);
                 if (r != ncclSuccess) {
                     fprintf(stderr, "vecchio_amd: ncclCommInitAll over %d devices failed (%s); the tile slabs travel by peer copies\n", n_devices,
                         R.GetErrorString(r));
-                    grp->comms.clear();
+                    grp->group.comms.clear();
                 }
             }
-            if (!grp->comms.empty()) {       // the receive stream of devices[0] and the event behind the frame's last receive
+            if (!grp->group.comms.empty()) {       // the receive stream of devices[0] and the event behind the frame's last receive
                 HIP_TRY(hipSetDevice(devices[0]));
-                HIP_TRY(hipStreamCreateWithFlags(&grp->stream, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&grp->ev_landed, hipEventDisableTiming));
+                if ((rc = grp->group.stream.create()) != VK_OK) return rc;
+                if ((rc = grp->group.ev_landed.create(hipEventDisableTiming)) != VK_OK) return rc;
             }
         }
         HIP_TRY(hipSetDevice(devices[0]));
-        HIP_TRY(hipEventCreateWithFlags(&grp->ev_begin, hipEventDisableTiming));
-        grp->lds_bytes = grp->parts[0]->lds_bytes; grp->hot_bytes = grp->parts[0]->hot_bytes;
+        if ((rc = grp->group.ev_begin.create(hipEventDisableTiming)) != VK_OK) return rc;
+        grp->plan.lds_bytes = grp->group.parts[0]->plan.lds_bytes; grp->plan.hot_bytes = grp->group.parts[0]->plan.hot_bytes;
         *out = grp.release();
         return VK_OK;
     });
@@ -1349,7 +1444,7 @@ void vk_scene_destroy(vk_scene *s) { destroy_one(s); }
 int vk_scene_get_info(const vk_scene *s, vk_scene_info *out) {
     if (!s || !out) return fail(VK_ERR_BAD_ARG, "null argument");
     const LinearScene &H = *s->host;
-    const vk_scene *one = s->parts.empty() ? s : s->parts[0];
+    const vk_scene *one = first_part(s);
     out->n_items = (uint32_t)H.items.size();
     out->n_prims = H.n_prims;
     out->n_instances = (uint32_t)H.instances.size();
@@ -1359,16 +1454,16 @@ int vk_scene_get_info(const vk_scene *s, vk_scene_info *out) {
          H.media.size() * sizeof(DMedium) + H.instances.size() * sizeof(DInstance) + H.materials.size() * sizeof(DMaterial) +
          H.textures.size() * sizeof(DTexture) + H.image_bytes.size() + H.perlins.size() * sizeof(DPerlin);
     out->device_bytes = b;
-    out->lds_bytes = one->lds_bytes;
+    out->lds_bytes = one->plan.lds_bytes;
     out->features = pick_variant(one);
     const bool rebuilt = !H.ref_items.empty() && pick_variant(one) == 0u;      // (see create_on_device)
-    out->tree = rebuilt ? (one->grid_on ? VK_TREE_REBUILT_GRID : H.near_form ? VK_TREE_REBUILT_NEAR : (H.proven ? VK_TREE_REBUILT_PROVEN : VK_TREE_REBUILT_EMPIRICAL))
+    out->tree = rebuilt ? (one->plan.grid_on ? VK_TREE_REBUILT_GRID : H.near_form ? VK_TREE_REBUILT_NEAR : (H.proven ? VK_TREE_REBUILT_PROVEN : VK_TREE_REBUILT_EMPIRICAL))
                                      : (!H.tie_rank.empty() && H.ref_items.empty() ? VK_TREE_REBUILT_FAST : VK_TREE_HANDED_OVER);
-    out->gather = s->parts.empty() ? VK_GATHER_NONE : (s->comms.empty() ? VK_GATHER_PEER_COPY : VK_GATHER_RCCL);
+    out->gather = s->group.parts.empty() ? VK_GATHER_NONE : (s->group.comms.empty() ? VK_GATHER_PEER_COPY : VK_GATHER_RCCL);
     out->tree_suspended_frames = 0;
-    for (const vk_scene *q : (s->parts.empty() ? std::vector<vk_scene *>{const_cast<vk_scene *>(s)} : s->parts))
-        if (q->exact_resume > q->frame_no + 1u) out->tree_suspended_frames = std::max<uint32_t>(out->tree_suspended_frames,
-            (uint32_t)(q->exact_resume - q->frame_no - 1u));
+    for (const vk_scene *q : (s->group.parts.empty() ? std::vector<vk_scene *>{const_cast<vk_scene *>(s)} : s->group.parts))
+        if (q->exact.resume > q->exact.frame_no + 1u) out->tree_suspended_frames = std::max<uint32_t>(out->tree_suspended_frames,
+            (uint32_t)(q->exact.resume - q->exact.frame_no - 1u));
     return VK_OK;
 }
 
@@ -1383,9 +1478,9 @@ int vk_render_device(vk_scene *scene, const vk_camera *cam, const vk_render_para
 // this scene; synchronises on their end event.  Multi-device: the slowest part.
 int vk_scene_part_info(vk_scene *s, int part, vk_part_info *out) {
     if (!s || !out) return fail(VK_ERR_BAD_ARG, "null argument");
-    const int n = s->parts.empty() ? 1 : (int)s->parts.size();
+    const int n = s->group.parts.empty() ? 1 : (int)s->group.parts.size();
     if (part < 0 || part >= n) return fail(VK_ERR_BAD_ARG, "part index out of range");
-    vk_scene *q = s->parts.empty() ? s : s->parts[(size_t)part];
+    vk_scene *q = s->group.parts.empty() ? s : s->group.parts[(size_t)part];
     memset(out, 0, sizeof(*out));
     out->n_parts = (uint32_t)n;
     out->device = q->device;
@@ -1393,7 +1488,7 @@ int vk_scene_part_info(vk_scene *s, int part, vk_part_info *out) {
     HIP_TRY(hipGetDeviceProperties(&pr, q->device));
     snprintf(out->name, sizeof(out->name), "%s", pr.name);
     if (hipDeviceGetPCIBusId(out->pci_bus_id, (int)sizeof(out->pci_bus_id), q->device) != hipSuccess) { (void)hipGetLastError(); out->pci_bus_id[0] = 0; }
-    const int landing = s->parts.empty() ? q->device : s->device;
+    const int landing = s->group.parts.empty() ? q->device : s->device;
     int can = 1;
     if (q->device != landing) HIP_TRY(hipDeviceCanAccessPeer(&can, q->device, landing));
     out->can_access_landing_device = (uint32_t)can;
@@ -1410,9 +1505,9 @@ int vk_scene_part_info(vk_scene *s, int part, vk_part_info *out) {
 int vk_scene_last_kernel_ms(vk_scene *s, double *ms_out) {
     if (!s || !ms_out) return fail(VK_ERR_BAD_ARG, "null argument");
     if (!s->last_timed) return fail(VK_ERR_BAD_ARG, "no render enqueued yet");
-    if (!s->parts.empty()) {
+    if (!s->group.parts.empty()) {
         double worst = 0.0;
-        for (vk_scene *q : s->parts) {
+        for (vk_scene *q : s->group.parts) {
             double ms = 0.0;
             int rc = vk_scene_last_kernel_ms(q, &ms);
             if (rc != VK_OK) return rc;
@@ -1423,7 +1518,7 @@ int vk_scene_last_kernel_ms(vk_scene *s, double *ms_out) {
     }
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipEventSynchronize(s->ev1));
-    if (s->wave_times && s->parts.empty()) {      // diagnostics: when the waves of the last render's FIRST launch started, pulled their last unit and ended
+    if (s->wave_times && s->group.parts.empty()) {      // diagnostics: when the waves of the last render's FIRST launch started, pulled their last unit and ended
         std::vector<unsigned long long> w(3u * 1024u * 16u);
         HIP_TRY(hipMemcpy(w.data(), s->wave_times, w.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         unsigned long long t0 = ~0ull, t1 = 0; std::vector<double> ends, lasts;
@@ -1439,23 +1534,23 @@ int vk_scene_last_kernel_ms(vk_scene *s, double *ms_out) {
     float ms = 0.0f;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     *ms_out = (double)ms;
-    if (s->dual_last && s->dual_launch) {        // did the two launches of the last frame share the work?  (see vk_scene::dual_strikes)
+    if (s->dual.last && s->plan.dual_launch) {        // did the two launches of the last frame share the work?  (see vk_scene::Dual::strikes)
         uint32_t u[2] = {0u, 0u};
         if (hipMemcpy(u, s->counter + 4, sizeof(u), hipMemcpyDeviceToHost) == hipSuccess && u[0] + u[1] > 0u) {
             const double share = (double)u[1] / (double)(u[0] + u[1]);       // ~12 / 28 when both run side by side
             const bool lopsided = share < 0.10 || share > 0.90;
-            s->dual_strikes = lopsided ? s->dual_strikes + 1 : 0;
+            s->dual.strikes = lopsided ? s->dual.strikes + 1 : 0;
             if (s->env.dual_debug)
                 fprintf(stderr, "vecchio_amd: dual launch: 1024-thread launch %u units, 768-thread launch %u units (%.2f)\n", u[0], u[1],
                     share);
-            if (s->dual_strikes >= 2) {
-                s->dual_launch = false;
+            if (s->dual.strikes >= 2) {
+                s->plan.dual_launch = false;
                 fprintf(stderr, "vecchio_amd: the two launches of the 7-waves-per-SIMD shape do not run side by side on this runtime "
                                 "(unit split %u / %u); using the single-launch shape from now on\n", u[0], u[1]);
             }
         }
         (void)hipGetLastError();
-        s->dual_last = false;
+        s->dual.last = false;
     }
     return VK_OK;
 }
@@ -1465,8 +1560,8 @@ int vk_scene_last_clamped_samples(vk_scene *s, uint64_t *out) {
     if (!s || !out) return fail(VK_ERR_BAD_ARG, "null argument");
     if (!s->last_timed) return fail(VK_ERR_BAD_ARG, "no render enqueued yet");
     *out = 0;
-    if (!s->parts.empty()) {
-        for (vk_scene *q : s->parts) {
+    if (!s->group.parts.empty()) {
+        for (vk_scene *q : s->group.parts) {
             uint64_t v = 0;
             int rc = vk_scene_last_clamped_samples(q, &v);
             if (rc != VK_OK) return rc;
@@ -1477,7 +1572,7 @@ int vk_scene_last_clamped_samples(vk_scene *s, uint64_t *out) {
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipEventSynchronize(s->ev1));
     unsigned long long v = 0;
-    HIP_TRY(hipMemcpy(&v, reinterpret_cast<unsigned long long *>(s->counter) + 1, sizeof(v), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&v, reinterpret_cast<unsigned long long *>(s->counter.get()) + 1, sizeof(v), hipMemcpyDeviceToHost));
     *out = v;
     return VK_OK;
 }
@@ -1489,9 +1584,9 @@ int vk_scene_last_requeued_samples(vk_scene *s, uint64_t *out) {
     if (!s || !out) return fail(VK_ERR_BAD_ARG, "null argument");
     if (!s->last_timed) return fail(VK_ERR_BAD_ARG, "no render enqueued yet");
     *out = 0;
-    if (!s->parts.empty()) {
+    if (!s->group.parts.empty()) {
         int worst = VK_OK;
-        for (vk_scene *q : s->parts) {
+        for (vk_scene *q : s->group.parts) {
             uint64_t v = 0;
             int rc = vk_scene_last_requeued_samples(q, &v);
             if (rc != VK_OK) worst = rc;
@@ -1499,22 +1594,18 @@ int vk_scene_last_requeued_samples(vk_scene *s, uint64_t *out) {
         }
         return worst;
     }
-    if (!s->redo_last) return VK_OK;
+    if (!s->exact.redo_last) return VK_OK;
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipEventSynchronize(s->ev1));
-    if (!s->plan_copied) {      // (the caller ran more than two frames ahead: this frame's plan was not copied; read it now)
+    if (!s->exact.plan_copied) {      // (the caller ran more than two frames ahead: this frame's plan was not copied; read it now)
         uint32_t plan[4];
-        HIP_TRY(hipMemcpy(plan, s->redo_count + REDO_REGIONS * REDO_COUNT_STRIDE, sizeof(plan), hipMemcpyDeviceToHost));
-        *out = plan[2] != 0u ? s->redo_last_samples : plan[1];
+        HIP_TRY(hipMemcpy(plan, s->exact.redo_count + REDO_REGIONS * REDO_COUNT_STRIDE, sizeof(plan), hipMemcpyDeviceToHost));
+        *out = plan[2] != 0u ? s->exact.redo_last_samples : plan[1];
         return VK_OK;
     }
-    const int b = s->plan_last;
-    *out = s->plan_host[4 * b + 2] != 0u ? s->redo_last_samples : s->plan_host[4 * b + 1];
-    for (int k = 1; k <= 2; k++) {
-        const int c = (b + k) & 1;
-        if (s->plan_pending[c] && hipEventQuery(s->ev_plan[c]) == hipSuccess) judge_frame(s, c);
-    }
-    (void)hipGetLastError();
+    const int b = s->exact.plan_last;
+    *out = s->exact.plan_host[4 * b + 2] != 0u ? s->exact.redo_last_samples : s->exact.plan_host[4 * b + 1];
+    judge_arrived_frames(s);
     return VK_OK;
 }
 
@@ -1530,8 +1621,8 @@ static int render_host(vk_scene *scene, const vk_camera *cam, const vk_render_pa
     size_t bytes = n_pixels * 3 * (u8 ? 1 : sizeof(float));
     // a multi-device group scatters into the image on devices[0]; a single device renders f32 into fb and converts into fb8
     void *d_img;
-    if (u8) { rc = ensure(scene->fb8, scene->fb8_bytes, bytes); d_img = scene->fb8; }
-    else { rc = ensure(scene->fb, scene->fb_bytes, bytes); d_img = scene->fb; }
+    if (u8) { rc = scene->fb8.ensure(bytes); d_img = scene->fb8; }
+    else { rc = scene->fb.ensure(bytes); d_img = scene->fb; }
     if (rc != VK_OK) return rc;
     vk_stats st;
     double ms = 0.0;
@@ -1541,7 +1632,7 @@ static int render_host(vk_scene *scene, const vk_camera *cam, const vk_render_pa
         if (rc != VK_OK) return rc;
         HIP_TRY(hipStreamSynchronize(nullptr));
         uint64_t requeued = 0;
-        rc = vk_scene_last_requeued_samples(scene, &requeued);      // (judges the frame: see vk_scene::exact_resume)
+        rc = vk_scene_last_requeued_samples(scene, &requeued);      // (judges the frame: see vk_scene::Exact::resume)
         if (rc != VK_OK) return rc;
     }
     rc = vk_scene_last_kernel_ms(scene, &ms);
@@ -1592,7 +1683,7 @@ int vk_debug_render_samples(vk_scene *scene, const vk_camera *cam, const vk_rend
 int vk_debug_last_launches(vk_scene *scene, vk_debug_launch *out, uint32_t cap, uint32_t *n) {
     if (!scene || !n || (cap && !out)) return fail(VK_ERR_BAD_ARG, "null argument");
     std::vector<vk_debug_launch> all;
-    for (const vk_scene *q : (scene->parts.empty() ? std::vector<vk_scene *>{scene} : scene->parts))
+    for (const vk_scene *q : (scene->group.parts.empty() ? std::vector<vk_scene *>{scene} : scene->group.parts))
         all.insert(all.end(), q->launch_log.begin(), q->launch_log.end());
     *n = (uint32_t)all.size();
     for (uint32_t k = 0; k < cap && k < *n; k++) out[k] = all[k];
@@ -1607,19 +1698,11 @@ int vk_debug_last_launches(vk_scene *scene, vk_debug_launch *out, uint32_t cap, 
 namespace {
 
 // The tree the first-hit walk runs on: the tree as handed over.  Where the scene has a second launch (exact re-treeing staged in LDS, or
-// the grid form) that is s->ref_view, the REDO launch's view; where both trees share items[] (exact re-treeing from global memory) it is
+// the grid form) that is s->exact.ref_view, the REDO launch's view; where both trees share items[] (exact re-treeing from global memory) it is
 // their first part, whose exits lead past the rebuilt tree (vk_linearize.cpp combined_items) — the in-place redo walk's tree.  Anywhere
 // else the scene holds one tree: the one handed over, or under VK_SCENE_FAST_ACCEL the rebuilt one (with its tie table), which is then
 // also what vk_render walks — such a scene has no copy of the tree as handed over on the device.
-DScene aov_view(const vk_scene *s) {
-    if (s->exact) return s->ref_view;
-    DScene v = s->dev;
-    if (v.walk_start != 0u) {
-        v.walk_start = 0u; v.primary_ref = 0u; v.t_pad = 0.0f; v.gate_scale = 1.0f; v.tmin_gate = T_MIN; v.tie_rank = nullptr;
-        v.ref_items = nullptr; v.n_ref_items = 0u;
-    }
-    return v;
-}
+DScene aov_view(const vk_scene *s) { return s->exact.on ? s->exact.ref_view : handed_over_view(s->dev); }
 
 // n_bufs: 4 (vk_render_aov) or 5 (vk_render_guides: bounces too)
 int check_aov_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p, uint32_t first_sample, const void *const *bufs,
@@ -1645,7 +1728,7 @@ int enqueue_aov(vk_scene *q, const vk_camera *cam, const vk_render_params *p, ui
     AovArgs A;
     memset(&A, 0, sizeof(A));
     A.S = aov_view(q);
-    if (A.S.grid.nu != 0u || A.S.t_pad != 0.0f || A.S.walk_start != 0u || A.S.gate_scale != 1.0f || A.S.primary_ref != 0u)
+    if (!is_plain_tree_view(A.S))
         return fail(VK_ERR_BAD_ARG, "internal error: the first-hit walk needs a tree view without the rebuilt forms' gates");
     A.C.cam = *cam;
     A.C.width = p->width; A.C.height = p->height; A.C.spp = p->samples_per_pixel; A.C.max_depth = 0u;
@@ -1654,9 +1737,10 @@ int enqueue_aov(vk_scene *q, const vk_camera *cam, const vk_render_params *p, ui
     A.albedo = d[0]; A.normal = d[1]; A.depth = d[2]; A.coverage = d[3];
     A.first_sample = first_sample; A.tiles_x = g.tiles_x; A.tile_rank = g.rank; A.tile_world = g.world; A.n_local = g.n_local;
     if (timed) {
-        if (!q->aov_ev0) HIP_TRY(hipEventCreate(&q->aov_ev0));
-        if (!q->aov_ev1) HIP_TRY(hipEventCreate(&q->aov_ev1));
-        HIP_TRY(hipEventRecord(q->aov_ev0, st));
+        int rc = q->aov.ev0.create();
+        if (rc == VK_OK) rc = q->aov.ev1.create();
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipEventRecord(q->aov.ev0, st));
     }
     if (g.n_local != 0u) {
         const dim3 grid((g.n_local + AOV_BLOCK / 64 - 1) / (AOV_BLOCK / 64));
@@ -1670,7 +1754,7 @@ int enqueue_aov(vk_scene *q, const vk_camera *cam, const vk_render_params *p, ui
         else hipLaunchKernelGGL(aov_kernel<(uint32_t)VKF_ALL_SCENE>, grid, dim3(AOV_BLOCK), 0, st, A);
         HIP_TRY(hipGetLastError());
     }
-    if (timed) HIP_TRY(hipEventRecord(q->aov_ev1, st));
+    if (timed) HIP_TRY(hipEventRecord(q->aov.ev1, st));
     return VK_OK;
 }
 
@@ -1681,39 +1765,66 @@ void aov_stats(const vk_render_params *p, vk_stats *st) {
     st->kernel_launches = g.n_local != 0u ? 1u : 0u;
 }
 
+// ---- the host-pointer calls (vk_render_aov, vk_render_guides, vk_denoise, vk_temporal_accumulate): the call's images side by side in ONE
+// staging buffer of the handle, uploads, a timed launch between two events, downloads, vk_stats.
+struct StagedImages {
+    float *dev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // image k's slice; null for a null image
+    // Lays the non-null images host[0, n) (comps[k] floats per pixel) out in `buf`, grown as needed, and uploads those whose bit is set
+    // in `mask`.  The buffer's device must be current.
+    int upload(DeviceBuffer<float> &buf, float *const *host, const uint32_t *comps, int n, size_t n_pixels, uint32_t mask) {
+        host_ = host; comps_ = comps; n_ = n; n_pixels_ = n_pixels;
+        size_t floats = 0;
+        for (int k = 0; k < n; k++) if (host[k]) floats += n_pixels * comps[k];
+        int rc = buf.ensure(floats * sizeof(float));
+        if (rc != VK_OK) return rc;
+        size_t at = 0;
+        for (int k = 0; k < n; k++) {
+            if (!host[k]) continue;
+            dev[k] = buf + at; at += n_pixels * comps[k];
+            if (mask >> k & 1u) HIP_TRY(hipMemcpy(dev[k], host[k], n_pixels * comps[k] * sizeof(float), hipMemcpyHostToDevice));
+        }
+        return VK_OK;
+    }
+    // the images whose bit is set in `mask`, back into the caller's memory (waits for the launch: the copies are synchronous)
+    int download(uint32_t mask) const {
+        for (int k = 0; k < n_; k++)
+            if (host_[k] && (mask >> k & 1u)) HIP_TRY(hipMemcpy(host_[k], dev[k], n_pixels_ * comps_[k] * sizeof(float), hipMemcpyDeviceToHost));
+        return VK_OK;
+    }
+
+private:
+    float *const *host_ = nullptr; const uint32_t *comps_ = nullptr; int n_ = 0; size_t n_pixels_ = 0;
+};
+
+// ends a timed host-pointer call: waits for its closing event and writes the two times into the caller's stats (whose counts are filled)
+int end_timed_call(hipEvent_t ev0, hipEvent_t ev1, std::chrono::steady_clock::time_point t0, vk_stats *stats_out) {
+    HIP_TRY(hipEventSynchronize(ev1));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    if (stats_out) {
+        stats_out->kernel_ms = (double)ms;
+        stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return VK_OK;
+}
+
 // The host-pointer call of vk_render_aov (n_bufs 4, gp null) and vk_render_guides (n_bufs 5): the wanted buffers staged side by side in the
 // scene's own device buffer, one timed launch, the copies back.  The arguments have been checked.
 int render_aov_host(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample, float *const host[5],
     int n_bufs, const vk_guide_params *gp, vk_stats *stats_out) {
     const auto t0 = std::chrono::steady_clock::now();
-    vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+    vk_scene *q = first_part(scene);
     HIP_TRY(hipSetDevice(q->device));
-    const size_t n_pixels = (size_t)params->width * params->height;
-    size_t floats = 0;
-    for (int k = 0; k < n_bufs; k++) if (host[k]) floats += n_pixels * AOV_COMPONENTS[k];
-    int rc = ensure(q->aov_buf, q->aov_bytes, floats * sizeof(float));
-    if (rc != VK_OK) return rc;
-    float *dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t at = 0;
-    for (int k = 0; k < n_bufs; k++) if (host[k]) { dev[k] = q->aov_buf + at; at += n_pixels * AOV_COMPONENTS[k]; }
     // a partition: the caller's pixels outside it must come back untouched
     const bool partial = (params->tile_world ? params->tile_world : 1u) > 1u;
-    if (partial)
-        for (int k = 0; k < n_bufs; k++)
-            if (host[k]) HIP_TRY(hipMemcpy(dev[k], host[k], n_pixels * AOV_COMPONENTS[k] * sizeof(float), hipMemcpyHostToDevice));
-    rc = enqueue_aov(q, cam, params, first_sample, dev, nullptr, true, gp, dev[4]);
+    StagedImages im;
+    int rc = im.upload(q->aov.buf, host, AOV_COMPONENTS, n_bufs, (size_t)params->width * params->height, partial ? ~0u : 0u);
     if (rc != VK_OK) return rc;
-    HIP_TRY(hipEventSynchronize(q->aov_ev1));
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, q->aov_ev0, q->aov_ev1));
-    for (int k = 0; k < n_bufs; k++)
-        if (host[k]) HIP_TRY(hipMemcpy(host[k], dev[k], n_pixels * AOV_COMPONENTS[k] * sizeof(float), hipMemcpyDeviceToHost));
-    if (stats_out) {
-        aov_stats(params, stats_out);
-        stats_out->kernel_ms = (double)ms;
-        stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return VK_OK;
+    rc = enqueue_aov(q, cam, params, first_sample, im.dev, nullptr, true, gp, im.dev[4]);
+    if (rc != VK_OK) return rc;
+    if ((rc = im.download(~0u)) != VK_OK) return rc;
+    if (stats_out) aov_stats(params, stats_out);
+    return end_timed_call(q->aov.ev0, q->aov.ev1, t0, stats_out);
 }
 
 // vk_render_guides' own checks, made first (they need no scene), then the first-hit checks with five buffers
@@ -1748,7 +1859,7 @@ int vk_render_aov_device(vk_scene *scene, const vk_camera *cam, const vk_render_
                          static_cast<float *>(d_coverage)};
         int rc = check_aov_args(scene, cam, params, first_sample, reinterpret_cast<const void *const *>(dev), 4);
         if (rc != VK_OK) return rc;
-        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        vk_scene *q = first_part(scene);
         rc = enqueue_aov(q, cam, params, first_sample, dev, reinterpret_cast<hipStream_t>(hip_stream), false);
         if (rc != VK_OK) return rc;
         if (stats_out) aov_stats(params, stats_out);
@@ -1785,7 +1896,7 @@ int vk_render_guides_device(vk_scene *scene, const vk_camera *cam, const vk_rend
                          static_cast<float *>(d_coverage), static_cast<float *>(d_bounces)};
         int rc = check_guide_args(scene, cam, params, first_sample, gp, reinterpret_cast<const void *const *>(dev));
         if (rc != VK_OK) return rc;
-        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        vk_scene *q = first_part(scene);
         rc = enqueue_aov(q, cam, params, first_sample, dev, reinterpret_cast<hipStream_t>(hip_stream), false, gp, dev[4]);
         if (rc != VK_OK) return rc;
         if (stats_out) aov_stats(params, stats_out);
@@ -1812,15 +1923,15 @@ int check_trace_args(vk_scene *scene, const vk_trace_params *tp, const void *ray
 
 // the provenance tables, on the device with the scene's first ray query (freed with the scene's other uploads)
 int ensure_provenance(vk_scene *q) {
-    if (q->prov_ready) return VK_OK;
+    if (q->rays.prov_ready) return VK_OK;
     const LinearScene &H = *q->host;
     int rc;
-    if ((rc = upload(q, H.src_sphere, q->prov.sphere)) != VK_OK) return rc;
-    if ((rc = upload(q, H.src_moving, q->prov.moving)) != VK_OK) return rc;
-    if ((rc = upload(q, H.src_rect, q->prov.rect)) != VK_OK) return rc;
-    if ((rc = upload(q, H.src_box_face, q->prov.box_face)) != VK_OK) return rc;
-    if ((rc = upload(q, H.src_medium, q->prov.medium)) != VK_OK) return rc;
-    q->prov_ready = true;
+    if ((rc = upload(q, H.src_sphere, q->rays.prov.sphere)) != VK_OK) return rc;
+    if ((rc = upload(q, H.src_moving, q->rays.prov.moving)) != VK_OK) return rc;
+    if ((rc = upload(q, H.src_rect, q->rays.prov.rect)) != VK_OK) return rc;
+    if ((rc = upload(q, H.src_box_face, q->rays.prov.box_face)) != VK_OK) return rc;
+    if ((rc = upload(q, H.src_medium, q->rays.prov.medium)) != VK_OK) return rc;
+    q->rays.prov_ready = true;
     return VK_OK;
 }
 
@@ -1829,9 +1940,9 @@ int enqueue_trace(vk_scene *q, const vk_trace_params *tp, uint64_t first_index, 
     TraceArgs A;
     memset(&A, 0, sizeof(A));
     A.S = aov_view(q);
-    if (A.S.grid.nu != 0u || A.S.t_pad != 0.0f || A.S.walk_start != 0u || A.S.gate_scale != 1.0f || A.S.primary_ref != 0u)
+    if (!is_plain_tree_view(A.S))
         return fail(VK_ERR_BAD_ARG, "internal error: a ray query needs a tree view without the rebuilt forms' gates");
-    A.P = q->prov;
+    A.P = q->rays.prov;
     A.rays = static_cast<const float4 *>(d_rays); A.hits = static_cast<uint4 *>(d_hits);
     A.seed = tp->seed; A.first_index = first_index; A.n_rays = n;
     const dim3 grid((uint32_t)((n + AOV_BLOCK - 1) / AOV_BLOCK));
@@ -1853,26 +1964,25 @@ int vk_trace_rays(vk_scene *scene, const vk_trace_params *params, const vk_ray *
         if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
         if (n_rays == 0u) return VK_OK;
         const auto t0 = std::chrono::steady_clock::now();
-        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        vk_scene *q = first_part(scene);
         HIP_TRY(hipSetDevice(q->device));
         if ((rc = ensure_provenance(q)) != VK_OK) return rc;
         const uint64_t cap = n_rays < RAY_CHUNK ? n_rays : RAY_CHUNK;
-        if ((rc = ensure(q->ray_buf, q->ray_bytes, (size_t)cap * (sizeof(vk_ray) + sizeof(vk_hit)))) != VK_OK) return rc;
-        if (!q->ray_ev0) HIP_TRY(hipEventCreate(&q->ray_ev0));
-        if (!q->ray_ev1) HIP_TRY(hipEventCreate(&q->ray_ev1));
+        if ((rc = q->rays.buf.ensure((size_t)cap * (sizeof(vk_ray) + sizeof(vk_hit)))) != VK_OK) return rc;
+        if ((rc = q->rays.ev0.create()) != VK_OK || (rc = q->rays.ev1.create()) != VK_OK) return rc;
         // (the buffer may be larger than this call needs: the hits start behind THIS call's rays)
-        uint8_t *d_rays = q->ray_buf, *d_hits = q->ray_buf + (size_t)cap * sizeof(vk_ray);
+        uint8_t *d_rays = q->rays.buf, *d_hits = d_rays + (size_t)cap * sizeof(vk_ray);
         double ms_sum = 0.0;
         uint64_t launches = 0;
         for (uint64_t at = 0; at < n_rays; at += cap) {
             const uint64_t n = n_rays - at < cap ? n_rays - at : cap;
             HIP_TRY(hipMemcpy(d_rays, rays + at, (size_t)n * sizeof(vk_ray), hipMemcpyHostToDevice));
-            HIP_TRY(hipEventRecord(q->ray_ev0, nullptr));
+            HIP_TRY(hipEventRecord(q->rays.ev0, nullptr));
             if ((rc = enqueue_trace(q, params, params->first_index + at, d_rays, n, d_hits, nullptr)) != VK_OK) return rc;
-            HIP_TRY(hipEventRecord(q->ray_ev1, nullptr));
-            HIP_TRY(hipEventSynchronize(q->ray_ev1));
+            HIP_TRY(hipEventRecord(q->rays.ev1, nullptr));
+            HIP_TRY(hipEventSynchronize(q->rays.ev1));
             float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, q->ray_ev0, q->ray_ev1));
+            HIP_TRY(hipEventElapsedTime(&ms, q->rays.ev0, q->rays.ev1));
             ms_sum += (double)ms; launches++;
             HIP_TRY(hipMemcpy(hits + at, d_hits, (size_t)n * sizeof(vk_hit), hipMemcpyDeviceToHost));
         }
@@ -1891,7 +2001,7 @@ int vk_trace_rays_device(vk_scene *scene, const vk_trace_params *params, const v
         if (rc != VK_OK) return rc;
         if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
         if (n_rays == 0u) return VK_OK;
-        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        vk_scene *q = first_part(scene);
         HIP_TRY(hipSetDevice(q->device));
         if ((rc = ensure_provenance(q)) != VK_OK) return rc;
         if ((rc = enqueue_trace(q, params, params->first_index, d_rays, n_rays, d_hits, reinterpret_cast<hipStream_t>(hip_stream))) != VK_OK)
@@ -1938,32 +2048,32 @@ int check_denoise_args(vk_scene *scene, const vk_denoise_params *dp, const void 
 int enqueue_denoise(vk_scene *q, const vk_denoise_params *dp, const float *const d[6], hipStream_t st, bool timed) {
     HIP_TRY(hipSetDevice(q->device));
     const size_t n = (size_t)dp->width * dp->height;
-    int rc = ensure(q->dn_buf, q->dn_bytes, n * (3 * sizeof(float4) + sizeof(float2)));
+    int rc = q->dn.buf.ensure(n * (3 * sizeof(float4) + sizeof(float2)));
     if (rc != VK_OK) return rc;
-    float4 *P[2] = {reinterpret_cast<float4 *>(q->dn_buf), reinterpret_cast<float4 *>(q->dn_buf) + n};
+    float4 *P[2] = {reinterpret_cast<float4 *>(q->dn.buf.get()), reinterpret_cast<float4 *>(q->dn.buf.get()) + n};
     DnArgs A;
     memset(&A, 0, sizeof(A));
-    A.G = reinterpret_cast<float4 *>(q->dn_buf) + 2 * n;
-    A.S = reinterpret_cast<float2 *>(reinterpret_cast<float4 *>(q->dn_buf) + 3 * n);
+    A.G = reinterpret_cast<float4 *>(q->dn.buf.get()) + 2 * n;
+    A.S = reinterpret_cast<float2 *>(reinterpret_cast<float4 *>(q->dn.buf.get()) + 3 * n);
     A.color = d[0]; A.stderr3 = d[1]; A.albedo = d[2]; A.normal = d[3]; A.depth = d[4]; A.out = const_cast<float *>(d[5]);
     A.width = dp->width; A.height = dp->height; A.normal_squarings = dp->normal_squarings;
     A.sigma_l = dp->sigma_l; A.sigma_z = dp->sigma_z; A.albedo_floor = dp->albedo_floor;
     const uint32_t guides = (d[1] ? DN_HAS_STDERR : 0u) | (d[2] ? DN_HAS_ALBEDO : 0u) | (d[3] ? DN_HAS_NORMAL : 0u) | (d[4] ? DN_HAS_DEPTH : 0u);
     if (timed) {
-        for (uint32_t k = 0; k < dp->levels + 2u; k++) if (!q->dn_ev[k]) HIP_TRY(hipEventCreate(&q->dn_ev[k]));
-        HIP_TRY(hipEventRecord(q->dn_ev[0], st));
+        for (uint32_t k = 0; k < dp->levels + 2u; k++) if ((rc = q->dn.ev[k].create()) != VK_OK) return rc;
+        HIP_TRY(hipEventRecord(q->dn.ev[0], st));
     }
     const dim3 grid((dp->width + DN_SX - 1) / DN_SX, (dp->height + DN_R - 1) / DN_R);
     A.flags = guides; A.Pout = P[0]; A.s = 1;
     hipLaunchKernelGGL(denoise_prepare_kernel, grid, dim3(DN_BLOCK), 0, st, A);
     HIP_TRY(hipGetLastError());
-    if (timed) HIP_TRY(hipEventRecord(q->dn_ev[1], st));
+    if (timed) HIP_TRY(hipEventRecord(q->dn.ev[1], st));
     for (uint32_t i = 0; i < dp->levels; i++) {
         A.s = 1 << i;
         A.Pin = P[i & 1u]; A.Pout = P[(i & 1u) ^ 1u];
         A.flags = guides | (i + 1u == dp->levels ? DN_LAST : 0u);
-        const bool staged = q->dn_form == VK_DENOISE_FORM_PLAIN ? false
-            : A.s <= (q->dn_form == VK_DENOISE_FORM_STAGED ? DN_STAGED_MAX_S : DN_STAGED_AUTO_MAX_S);
+        const bool staged = q->dn.form == VK_DENOISE_FORM_PLAIN ? false
+            : A.s <= (q->dn.form == VK_DENOISE_FORM_STAGED ? DN_STAGED_MAX_S : DN_STAGED_AUTO_MAX_S);
         if (staged) {
             // one workgroup per DN_SX columns and DN_R rows of one residue class of y mod s
             const uint32_t per_class = ((dp->height + (uint32_t)A.s - 1u) / (uint32_t)A.s + DN_R - 1) / DN_R;
@@ -1973,9 +2083,9 @@ int enqueue_denoise(vk_scene *q, const vk_denoise_params *dp, const float *const
             hipLaunchKernelGGL(denoise_level_plain_kernel, grid, dim3(DN_BLOCK), 0, st, A);
         }
         HIP_TRY(hipGetLastError());
-        if (timed) HIP_TRY(hipEventRecord(q->dn_ev[2 + i], st));
+        if (timed) HIP_TRY(hipEventRecord(q->dn.ev[2 + i], st));
     }
-    if (timed) q->dn_last_levels = dp->levels;
+    if (timed) q->dn.last_levels = dp->levels;
     return VK_OK;
 }
 
@@ -1995,39 +2105,24 @@ int vk_denoise_default_params(uint32_t width, uint32_t height, vk_denoise_params
 int vk_denoise(vk_scene *scene, const vk_denoise_params *dp, const float *color, const float *stderr3, const float *albedo,
     const float *normal, const float *depth, float *out, vk_stats *stats_out) {
     return guarded([&]() -> int {
-        const float *host[6] = {color, stderr3, albedo, normal, depth, out};
+        float *const host[6] = {const_cast<float *>(color), const_cast<float *>(stderr3), const_cast<float *>(albedo),
+                                const_cast<float *>(normal), const_cast<float *>(depth), out};
         int rc = check_denoise_args(scene, dp, reinterpret_cast<const void *const *>(host));
         if (rc != VK_OK) return rc;
         const auto t0 = std::chrono::steady_clock::now();
-        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        vk_scene *q = first_part(scene);
         HIP_TRY(hipSetDevice(q->device));
         const size_t n = (size_t)dp->width * dp->height;
-        size_t floats = 0;
-        for (int k = 0; k < 6; k++) if (host[k]) floats += n * DN_COMPONENTS[k];
-        rc = ensure(q->dn_io, q->dn_io_bytes, floats * sizeof(float));
-        if (rc != VK_OK) return rc;
-        const float *dev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        size_t at = 0;
-        for (int k = 0; k < 6; k++) {
-            if (!host[k]) continue;
-            dev[k] = q->dn_io + at;
-            if (k < 5) HIP_TRY(hipMemcpy(q->dn_io + at, host[k], n * DN_COMPONENTS[k] * sizeof(float), hipMemcpyHostToDevice));
-            at += n * DN_COMPONENTS[k];
-        }
-        rc = enqueue_denoise(q, dp, dev, nullptr, true);
-        if (rc != VK_OK) return rc;
-        HIP_TRY(hipEventSynchronize(q->dn_ev[1 + dp->levels]));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, q->dn_ev[0], q->dn_ev[1 + dp->levels]));
-        HIP_TRY(hipMemcpy(out, dev[5], n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        StagedImages im;
+        if ((rc = im.upload(q->dn.io, host, DN_COMPONENTS, 6, n, 0x1Fu)) != VK_OK) return rc;      // (every image but out)
+        if ((rc = enqueue_denoise(q, dp, im.dev, nullptr, true)) != VK_OK) return rc;
+        if ((rc = im.download(1u << 5)) != VK_OK) return rc;
         if (stats_out) {
             memset(stats_out, 0, sizeof(*stats_out));
             stats_out->samples = n;
-            stats_out->kernel_ms = (double)ms;
             stats_out->kernel_launches = 1u + dp->levels;
-            stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
-        return VK_OK;
+        return end_timed_call(q->dn.ev[0], q->dn.ev[1 + dp->levels], t0, stats_out);
     });
 }
 
@@ -2038,7 +2133,7 @@ int vk_denoise_device(vk_scene *scene, const vk_denoise_params *dp, const void *
                                static_cast<const float *>(d_normal), static_cast<const float *>(d_depth), static_cast<const float *>(d_out)};
         int rc = check_denoise_args(scene, dp, reinterpret_cast<const void *const *>(dev));
         if (rc != VK_OK) return rc;
-        vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
+        vk_scene *q = first_part(scene);
         return enqueue_denoise(q, dp, dev, reinterpret_cast<hipStream_t>(hip_stream), false);
     });
 }
@@ -2046,20 +2141,20 @@ int vk_denoise_device(vk_scene *scene, const vk_denoise_params *dp, const void *
 int vk_debug_denoise_form(vk_scene *scene, int form) {
     if (!scene) return fail(VK_ERR_BAD_ARG, "null scene");
     if (form < VK_DENOISE_FORM_AUTO || form > VK_DENOISE_FORM_STAGED) return fail(VK_ERR_BAD_ARG, "unknown denoise form");
-    (scene->parts.empty() ? scene : scene->parts[0])->dn_form = form;
+    first_part(scene)->dn.form = form;
     return VK_OK;
 }
 
 int vk_debug_denoise_last_ms(vk_scene *scene, double ms_out[9]) {
     if (!scene || !ms_out) return fail(VK_ERR_BAD_ARG, "null argument");
-    vk_scene *q = scene->parts.empty() ? scene : scene->parts[0];
-    if (q->dn_last_levels == 0u) return fail(VK_ERR_BAD_ARG, "no vk_denoise on this scene yet");
+    vk_scene *q = first_part(scene);
+    if (q->dn.last_levels == 0u) return fail(VK_ERR_BAD_ARG, "no vk_denoise on this scene yet");
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(q->device));
-        HIP_TRY(hipEventSynchronize(q->dn_ev[1 + q->dn_last_levels]));
+        HIP_TRY(hipEventSynchronize(q->dn.ev[1 + q->dn.last_levels]));
         for (uint32_t k = 0; k < 9u; k++) {
             float ms = 0.0f;
-            if (k <= q->dn_last_levels) HIP_TRY(hipEventElapsedTime(&ms, q->dn_ev[k], q->dn_ev[k + 1]));
+            if (k <= q->dn.last_levels) HIP_TRY(hipEventElapsedTime(&ms, q->dn.ev[k], q->dn.ev[k + 1]));
             ms_out[k] = (double)ms;
         }
         return VK_OK;
@@ -2074,10 +2169,10 @@ int vk_debug_denoise_last_ms(vk_scene *scene, double ms_out[9]) {
 struct vk_temporal {
     int device = 0;
     vk_temporal_params tp{};
-    float4 *hist = nullptr;                         // two histories of three planes of width*height float4 each
-    unsigned long long *count = nullptr;            // pixels_with_history of the last frame
-    float *io = nullptr; size_t io_bytes = 0;       // vk_temporal_accumulate's images on the device
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;        // around the last frame's kernel (ev1: what vk_temporal_get_info waits for)
+    DeviceBuffer<float4> hist;                      // two histories of three planes of width*height float4 each
+    DeviceBuffer<unsigned long long> count;         // pixels_with_history of the last frame
+    DeviceBuffer<float> io;                         // vk_temporal_accumulate's images on the device
+    Event ev0, ev1;                                 // around the last frame's kernel (ev1: what vk_temporal_get_info waits for)
     uint32_t frames = 0;                            // since create or reset
     uint32_t cur = 0;                               // the history the last frame wrote
     vk_camera prev{};                               // the last frame's camera
@@ -2153,8 +2248,6 @@ int enqueue_temporal(vk_temporal *t, const vk_camera *cam, const float *const d[
 void temporal_free(vk_temporal *t) {
     (void)hipSetDevice(t->device);
     if (t->ev1) (void)hipEventSynchronize(t->ev1);
-    for (void *p : {(void *)t->hist, (void *)t->count, (void *)t->io}) if (p) (void)hipFree(p);
-    for (hipEvent_t e : {t->ev0, t->ev1}) if (e) (void)hipEventDestroy(e);
     delete t;
 }
 
@@ -2176,23 +2269,20 @@ int vk_temporal_create(vk_scene *scene, const vk_temporal_params *tp, vk_tempora
     if (rc != VK_OK) return rc;
     if (!scene) return fail(VK_ERR_BAD_ARG, "null scene");
     return guarded([&]() -> int {
-        vk_temporal *t = new vk_temporal();
-        t->device = (scene->parts.empty() ? scene : scene->parts[0])->device;
+        std::unique_ptr<vk_temporal, void (*)(vk_temporal *)> t(new vk_temporal(), temporal_free);
+        t->device = first_part(scene)->device;
         t->tp = *tp;
         const size_t n = (size_t)tp->width * tp->height;
-        int e = VK_OK;
-        auto tryhip = [&](hipError_t r, const char *what) {
-            if (e == VK_OK && r != hipSuccess) e = fail(r == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string(what) + ": " +
-                hipGetErrorString(r));
-        };
-        tryhip(hipSetDevice(t->device), "hipSetDevice");
-        if (e == VK_OK) tryhip(hipMalloc(reinterpret_cast<void **>(&t->hist), 6 * n * sizeof(float4)), "hipMalloc (history)");
-        if (e == VK_OK) tryhip(hipMalloc(reinterpret_cast<void **>(&t->count), sizeof(unsigned long long)), "hipMalloc");
-        if (e == VK_OK) tryhip(hipMemset(t->count, 0, sizeof(unsigned long long)), "hipMemset");
-        if (e == VK_OK) tryhip(hipEventCreate(&t->ev0), "hipEventCreate");
-        if (e == VK_OK) tryhip(hipEventCreate(&t->ev1), "hipEventCreate");
-        if (e != VK_OK) { temporal_free(t); return e; }
-        *out = t;
+        HIP_TRY(hipSetDevice(t->device));
+        hipError_t e;      // (out of device memory has a code of its own)
+        if ((e = t->hist.alloc(6 * n * sizeof(float4))) != hipSuccess) return fail(e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP,
+            std::string("hipMalloc (history): ") + hipGetErrorString(e));
+        if ((e = t->count.alloc(sizeof(unsigned long long))) != hipSuccess) return fail(e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP,
+            std::string("hipMalloc: ") + hipGetErrorString(e));
+        int rc;
+        HIP_TRY(hipMemset(t->count, 0, sizeof(unsigned long long)));
+        if ((rc = t->ev0.create()) != VK_OK || (rc = t->ev1.create()) != VK_OK) return rc;
+        *out = t.release();
         return VK_OK;
     });
 }
@@ -2207,33 +2297,16 @@ int vk_temporal_accumulate(vk_temporal *t, const vk_camera *cam, const float *co
         const auto t0 = std::chrono::steady_clock::now();
         HIP_TRY(hipSetDevice(t->device));
         const size_t n = (size_t)t->tp.width * t->tp.height;
-        size_t floats = 0;
-        for (int k = 0; k < 8; k++) if (host[k]) floats += n * TA_COMPONENTS[k];
-        rc = ensure(t->io, t->io_bytes, floats * sizeof(float));
-        if (rc != VK_OK) return rc;
-        const float *dev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        size_t at = 0;
-        for (int k = 0; k < 8; k++) {
-            if (!host[k]) continue;
-            dev[k] = t->io + at;
-            if (k < 5) HIP_TRY(hipMemcpy(t->io + at, host[k], n * TA_COMPONENTS[k] * sizeof(float), hipMemcpyHostToDevice));
-            at += n * TA_COMPONENTS[k];
-        }
-        rc = enqueue_temporal(t, cam, dev, nullptr, true);
-        if (rc != VK_OK) return rc;
-        HIP_TRY(hipEventSynchronize(t->ev1));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, t->ev0, t->ev1));
-        for (int k = 5; k < 8; k++)
-            if (host[k]) HIP_TRY(hipMemcpy(host[k], dev[k], n * TA_COMPONENTS[k] * sizeof(float), hipMemcpyDeviceToHost));
+        StagedImages im;
+        if ((rc = im.upload(t->io, host, TA_COMPONENTS, 8, n, 0x1Fu)) != VK_OK) return rc;      // (the inputs)
+        if ((rc = enqueue_temporal(t, cam, im.dev, nullptr, true)) != VK_OK) return rc;
+        if ((rc = im.download(0xE0u)) != VK_OK) return rc;                                      // (the three outputs)
         if (stats_out) {
             memset(stats_out, 0, sizeof(*stats_out));
             stats_out->samples = n;
-            stats_out->kernel_ms = (double)ms;
             stats_out->kernel_launches = 1u;
-            stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
-        return VK_OK;
+        return end_timed_call(t->ev0, t->ev1, t0, stats_out);
     });
 }
 
@@ -2288,15 +2361,16 @@ struct vk_progress {
     vk_adaptive_params ap;
     struct Part {                  // one per device part (the scene itself for a one-device scene)
         int device = 0;
-        long long *run = nullptr;
-        double *m2 = nullptr;
-        unsigned long long *clamped = nullptr;
-        hipEvent_t ev = nullptr;
+        DeviceBuffer<long long> run;
+        DeviceBuffer<double> m2;
+        DeviceBuffer<unsigned long long> clamped;
+        Event ev;
         // the part's share of the partition: tiles rank + world * i, i < n_local (in_px: their in-image pixels)
         uint32_t rank = 0, world = 1, n_local = 0;
         uint64_t in_px = 0;
         // adaptive (allocated by vk_progress_set_adaptive): see AccumDesc
-        uint32_t *tile_n = nullptr, *tile_k = nullptr, *list = nullptr, *ctl = nullptr, *h_left = nullptr;
+        DeviceBuffer<uint32_t> tile_n, tile_k, list, ctl;
+        PinnedBuffer<uint32_t> h_left;
     };
     std::vector<Part> parts;
     size_t n_words = 0;            // width*height*3
@@ -2304,13 +2378,19 @@ struct vk_progress {
 
 namespace {
 
+// an allocation of a progressive handle: any failure counts as out of memory (the sticky error cleared)
+template <class T>
+bool device_alloc(DeviceBuffer<T> &b, size_t bytes) {
+    if (b.alloc(bytes) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+// (waits for each part's last step before the part's sums go)
 void progress_free(vk_progress *pr) {
     for (auto &q : pr->parts) {
         (void)hipSetDevice(q.device);
-        if (q.ev) { (void)hipEventSynchronize(q.ev); (void)hipEventDestroy(q.ev); }
-        for (void *p : {(void *)q.run, (void *)q.m2, (void *)q.clamped, (void *)q.tile_n, (void *)q.tile_k, (void *)q.list, (void *)q.ctl})
-            if (p) (void)hipFree(p);
-        if (q.h_left) (void)hipHostFree(q.h_left);
+        if (q.ev) (void)hipEventSynchronize(q.ev);
     }
     (void)hipGetLastError();
     delete pr;
@@ -2427,16 +2507,17 @@ int vk_progress_create(vk_scene *scene, const vk_camera *cam, const vk_render_pa
     int rc = check_render_args(scene, cam, params);
     if (rc != VK_OK) return rc;
     return guarded([&]() -> int {
-        vk_progress *pr = new vk_progress;
+        std::unique_ptr<vk_progress, void (*)(vk_progress *)> pr(new vk_progress, progress_free);
         pr->scene = scene; pr->cam = *cam; pr->params = *params; pr->flags = flags;
         memset(&pr->ap, 0, sizeof(pr->ap));
         pr->n_words = (size_t)params->width * params->height * 3;
-        std::vector<vk_scene *> parts = scene->parts;
+        std::vector<vk_scene *> parts = scene->group.parts;
         if (parts.empty()) parts.push_back(scene);
         const TileGeom g(params);
         for (size_t j = 0; j < parts.size(); j++) {
             vk_scene *q = parts[j];
-            vk_progress::Part P;
+            pr->parts.emplace_back();
+            auto &P = pr->parts.back();
             P.device = q->device;
             // (enqueue_render_multi's split: part j of n renders tiles R + W (j + n i))
             vk_render_params pj = *params;
@@ -2445,22 +2526,14 @@ int vk_progress_create(vk_scene *scene, const vk_camera *cam, const vk_render_pa
             P.rank = gj.rank; P.world = gj.world; P.n_local = gj.n_local;
             pj.samples_per_pixel = 1;
             P.in_px = gj.n_local ? partition_samples(&pj, gj) : 0u;
-            pr->parts.push_back(P);
-            auto &R = pr->parts.back();
-            int e = VK_OK;
-            auto alloc = [&](void **ptr, size_t bytes) {
-                if (e == VK_OK && hipMalloc(ptr, bytes) != hipSuccess) { (void)hipGetLastError(); e = fail(VK_ERR_OOM, "out of device memory"); }
-            };
-            if (hipSetDevice(q->device) != hipSuccess) e = fail(VK_ERR_HIP, "hipSetDevice failed");
-            alloc(reinterpret_cast<void **>(&R.run), pr->n_words * sizeof(long long));
-            if (flags & VK_PROGRESS_STDERR) alloc(reinterpret_cast<void **>(&R.m2), pr->n_words * sizeof(double));
-            alloc(reinterpret_cast<void **>(&R.clamped), sizeof(unsigned long long));
-            if (e == VK_OK && hipEventCreateWithFlags(&R.ev, hipEventDisableTiming) != hipSuccess) e = fail(VK_ERR_HIP, "hipEventCreate failed");
-            if (e != VK_OK) { progress_free(pr); return e; }
+            if (hipSetDevice(q->device) != hipSuccess) return fail(VK_ERR_HIP, "hipSetDevice failed");
+            if (!device_alloc(P.run, pr->n_words * sizeof(long long)) || ((flags & VK_PROGRESS_STDERR) && !device_alloc(P.m2, pr->n_words * sizeof(double))) ||
+                !device_alloc(P.clamped, sizeof(unsigned long long))) return fail(VK_ERR_OOM, "out of device memory");
+            if (P.ev.create(hipEventDisableTiming) != VK_OK) return fail(VK_ERR_HIP, "hipEventCreate failed");
         }
-        int z = progress_zero(pr);
-        if (z != VK_OK) { progress_free(pr); return z; }
-        *out = pr;
+        int z = progress_zero(pr.get());
+        if (z != VK_OK) return z;
+        *out = pr.release();
         return VK_OK;
     });
 }
@@ -2480,24 +2553,12 @@ int vk_progress_set_adaptive(vk_progress *pr, const vk_adaptive_params *ap) {
             HIP_TRY(hipSetDevice(q.device));
             const size_t words = (size_t)q.n_local + 1u;
             int e = VK_OK;
-            auto alloc = [&](void **ptr, size_t bytes) {
-                if (e == VK_OK && hipMalloc(ptr, bytes) != hipSuccess) { (void)hipGetLastError(); e = fail(VK_ERR_OOM, "out of device memory"); }
-            };
-            alloc(reinterpret_cast<void **>(&q.tile_n), words * sizeof(uint32_t));
-            alloc(reinterpret_cast<void **>(&q.tile_k), words * sizeof(uint32_t));
-            alloc(reinterpret_cast<void **>(&q.list), words * sizeof(uint32_t));
-            alloc(reinterpret_cast<void **>(&q.ctl), (4u + (q.n_local + 1023u) / 1024u) * sizeof(uint32_t));
-            if (e == VK_OK && hipHostMalloc(reinterpret_cast<void **>(&q.h_left), 4 * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError(); e = fail(VK_ERR_OOM, "out of pinned host memory");
-            }
+            if (!device_alloc(q.tile_n, words * sizeof(uint32_t)) || !device_alloc(q.tile_k, words * sizeof(uint32_t)) ||
+                !device_alloc(q.list, words * sizeof(uint32_t)) || !device_alloc(q.ctl, (4u + (q.n_local + 1023u) / 1024u) * sizeof(uint32_t)))
+                e = fail(VK_ERR_OOM, "out of device memory");
+            else if (q.h_left.alloc(4 * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); e = fail(VK_ERR_OOM, "out of pinned host memory"); }
             if (e != VK_OK) {      // (the handle as it was: non-adaptive, nothing of this call kept)
-                for (auto &u : pr->parts) {
-                    (void)hipSetDevice(u.device);
-                    for (uint32_t **p : {&u.tile_n, &u.tile_k, &u.list, &u.ctl}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-                    if (u.h_left) (void)hipHostFree(u.h_left);
-                    u.h_left = nullptr;
-                }
-                (void)hipGetLastError();
+                for (auto &u : pr->parts) { u.tile_n.reset(); u.tile_k.reset(); u.list.reset(); u.ctl.reset(); u.h_left.reset(); }
                 return e;
             }
         }
@@ -2742,11 +2803,11 @@ int vk_debug_phase_stats(vk_scene *scene, const vk_camera *cam, const vk_render_
     if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
     int rc = check_render_args(scene, cam, params);
     if (rc != VK_OK) return rc;
-    if (!scene->parts.empty() || params->output_format != VK_OUTPUT_F32) return fail(VK_ERR_UNSUPPORTED,
+    if (!scene->group.parts.empty() || params->output_format != VK_OUTPUT_F32) return fail(VK_ERR_UNSUPPORTED,
         "phase statistics: single device, VK_OUTPUT_F32");
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(scene->device));
-        int rc2 = ensure(scene->fb, scene->fb_bytes, (size_t)params->width * params->height * 3 * sizeof(float));
+        int rc2 = scene->fb.ensure((size_t)params->width * params->height * 3 * sizeof(float));
         if (rc2 != VK_OK) return rc2;
         scene->want_phase_stats = true;
         rc2 = enqueue_render(scene, cam, params, scene->fb, nullptr, false, nullptr);
@@ -2775,6 +2836,13 @@ int vk_debug_math(int device, int op, const float *a, const float *b, float *out
         (const float *)db.p, dout.p, n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, dout.p, n * 4, hipMemcpyDeviceToHost));
+    return VK_OK;
+}
+
+// test hook: the live device buffers, pinned buffers, events and streams of this library's handles (vk_resources.h)
+int vk_debug_live_objects(uint64_t out[4]) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    for (int k = 0; k < 4; k++) out[k] = vkr::g_live[k].load();
     return VK_OK;
 }
 

@@ -180,5 +180,25 @@ struct DProvenance { const uint32_t *sphere, *moving, *rect, *box_face, *medium;
 inline void use_grid(DScene &s) { s.trust_r0sq = __builtin_inff(); s.reach = 0.0f; s.primary_ref = 0u; }
 inline void drop_grid(DScene &s) { s.grid.nu = 0u; s.grid.nv = 0u; }
 
+// The tree AS HANDED OVER of a scene, whatever rebuilt form `s` walks: ref_items in items[] where the scene keeps that tree apart (exact
+// re-treeing staged in LDS, the grid form), the first part of items[] where both trees share it (walk_start != 0: that part's exits lead
+// past the rebuilt tree, vk_linearize.cpp combined_items) — and none of the rebuilt forms' gates, tie table or grid.  This is the view of
+// the second launch of exact re-treeing, of the diagnostic builds, of the first-hit walks and ray queries, and what the emulator renders
+// a dropped sample on.  A scene that holds ONE tree (walk_start == 0, no ref_items, no grid) is returned as it is, tie table included:
+// the tree handed over, or under VK_SCENE_FAST_ACCEL the rebuilt one, which is then the only tree there is.
+constexpr float HANDED_OVER_T_MIN = 0.001f;      // T_MIN of vk_trace.h (main.rs:130)
+inline DScene handed_over_view(const DScene &s) {
+    DScene v = s;
+    if (s.ref_items) { v.items = s.ref_items; v.n_items = s.n_ref_items; v.n_world_items = s.n_ref_items; }
+    else if (s.walk_start == 0u && s.grid.nu == 0u) return v;
+    v.walk_start = 0u; v.primary_ref = 0u; v.t_pad = 0.0f; v.gate_scale = 1.0f; v.tmin_gate = HANDED_OVER_T_MIN; v.tie_rank = nullptr;
+    v.grid.nu = 0u; v.ref_items = nullptr; v.n_ref_items = 0u;
+    return v;
+}
+// a view on which a walk meets no gate of a rebuilt form (what the first-hit walks and the ray queries ask of theirs)
+inline bool is_plain_tree_view(const DScene &s) {
+    return s.grid.nu == 0u && s.t_pad == 0.0f && s.walk_start == 0u && s.gate_scale == 1.0f && s.primary_ref == 0u;
+}
+
 }  // namespace vkd
 #endif

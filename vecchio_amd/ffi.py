@@ -405,6 +405,8 @@ def load_debug_lib():
     lib.vk_debug_phase_stats.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(C.c_uint64 * 24)]
     lib.vk_debug_math.restype = C.c_int
     lib.vk_debug_math.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.vk_debug_live_objects.restype = C.c_int
+    lib.vk_debug_live_objects.argtypes = [C.POINTER(C.c_uint64 * 4)]
     _dbg = lib
     return lib
 
