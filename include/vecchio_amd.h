@@ -126,6 +126,12 @@ enum {
     VK_MAT_ISOTROPIC = 4,    /* material.rs:436-465  texture */
     VK_MAT_SPEC_DIFFUSE = 5  /* material.rs:467-488  a = specular material, b = diffuse material, param = pct */
 };
+/* A SpecDiffuse may have any material as a child, another SpecDiffuse included (Arc<MaterialSS>).  The device resolves at most
+ * VK_MAX_SPEC_DIFFUSE_DEPTH SpecDiffuses on a path from a material to a leaf, counted along the deeper of the two children (the draw
+ * loop and the scattering_pdf loop of shade_core and the stack of aov_albedo, vk_trace.h, hold that many).  Scene creation returns
+ * VK_ERR_UNSUPPORTED, with the limit in the message, for a deeper acyclic graph, and VK_ERR_BAD_ARG ("cyclic") for a SpecDiffuse that
+ * reaches itself through a or b. */
+#define VK_MAX_SPEC_DIFFUSE_DEPTH 8u
 typedef struct vk_material {
     uint32_t kind;
     uint32_t texture;
@@ -139,6 +145,11 @@ enum {
     VK_TEX_IMAGE = 2,   /* material.rs:261-304 a = image index  */
     VK_TEX_NOISE = 3    /* material.rs:416-434 a = perlin index, scale */
 };
+/* A checker may have any texture as a child, another checker included (Arc<TextureSS>).  The device resolves at most
+ * VK_MAX_CHECKER_DEPTH checkers on a path from a texture to a leaf, counted along the deeper of the two children (texture_value,
+ * vk_trace.h, walks 16 records: 15 checkers and the leaf).  Scene creation returns VK_ERR_UNSUPPORTED, with the limit in the message,
+ * for a deeper acyclic graph, and VK_ERR_BAD_ARG ("cyclic") for a checker that reaches itself through a or b. */
+#define VK_MAX_CHECKER_DEPTH 15u
 typedef struct vk_texture {
     uint32_t kind;
     float color[3];
@@ -157,6 +168,7 @@ typedef struct vk_perlin {     /* material.rs:306-311 */
 } vk_perlin;
 
 /* ---- the flattened scene ------------------------------------------------------------ */
+/* An array pointer that is NULL while its count is not 0 is refused with VK_ERR_BAD_ARG (each record array and lights). */
 typedef struct vk_scene_desc {
     uint32_t abi_version;      /* VK_ABI_VERSION (6 is accepted too: the description has not changed since) */
     uint32_t n_bvh;            const vk_bvh_node *bvh;

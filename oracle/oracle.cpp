@@ -21,6 +21,7 @@
 // counter-based stream (vk_math.h); draw ORDER and COUNT are the reference's.
 #include "oracle.h"
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstring>
@@ -900,10 +901,53 @@ struct Scene {
         return out;
     }
 
+    // The records below are wired up with raw pointers and evaluated by recursion (Checker::value, SpecDiffuse::scatter_with_pdf): a
+    // checker or a SpecDiffuse that reaches itself would never return.  The library refuses such a graph, and one nested deeper than
+    // VK_MAX_CHECKER_DEPTH / VK_MAX_SPEC_DIFFUSE_DEPTH (include/vecchio_amd.h); so does the loader.  `kids(i, out)` gives the two
+    // children of record i when it is a checker / SpecDiffuse (indices already range-checked) and false for a leaf.
+    template <class Kids>
+    bool check_nesting(uint32_t n, Kids kids, uint32_t limit, const char *what) {
+        std::vector<int> depth(n, -1);                 // -1 unknown, -2 being worked out, >= 0 known
+        std::vector<std::pair<uint32_t, int>> st;      // (record, children already pushed?)
+        for (uint32_t root = 0; root < n; root++) {
+            if (depth[root] >= 0) continue;
+            st.emplace_back(root, 0);
+            while (!st.empty()) {
+                const uint32_t i = st.back().first;
+                uint32_t c[2];
+                if (depth[i] >= 0) { st.pop_back(); continue; }          // (pushed by two parents: worked out by the first)
+                if (!kids(i, c)) { depth[i] = 0; st.pop_back(); continue; }
+                if (st.back().second == 0) {
+                    st.back().second = 1; depth[i] = -2;
+                    for (uint32_t k : c) {
+                        if (depth[k] == -2) return fail(std::string(what) + " graph is cyclic");
+                        if (depth[k] == -1) st.emplace_back(k, 0);
+                    }
+                    continue;
+                }
+                depth[i] = 1 + std::max(depth[c[0]], depth[c[1]]);      // (both children are worked out by now)
+                if ((uint32_t)depth[i] > limit)
+                    return fail(std::string(what) + " nesting of " + std::to_string(depth[i]) + " is over the limit of " +
+                                std::to_string(limit));
+                st.pop_back();
+            }
+        }
+        return true;
+    }
+
     bool build(const vk_scene_desc *desc, bool textures_only = false) {
         d = desc;
         if (!desc) return fail("null scene desc");
         if (desc->abi_version != VK_ABI_VERSION) return fail("abi version mismatch");
+        {
+            const std::pair<uint32_t, const void *> arrays[] = {
+                {desc->n_bvh, desc->bvh}, {desc->n_spheres, desc->spheres}, {desc->n_moving_spheres, desc->moving_spheres},
+                {desc->n_rects, desc->rects}, {desc->n_lists, desc->lists}, {desc->n_list_items, desc->list_items},
+                {desc->n_media, desc->media}, {desc->n_translates, desc->translates}, {desc->n_rotates, desc->rotates},
+                {desc->n_materials, desc->materials}, {desc->n_textures, desc->textures}, {desc->n_images, desc->images},
+                {desc->n_perlins, desc->perlins}, {desc->n_lights, desc->lights}};
+            for (const auto &a : arrays) if (a.first != 0u && !a.second) return fail("null array with a non-zero count");
+        }
         // textures (children must have smaller... any index; two passes)
         textures.resize(desc->n_textures);
         for (uint32_t i = 0; i < desc->n_textures; i++) {
@@ -941,6 +985,10 @@ struct Scene {
                 c->odd = textures[t.a].get(); c->even = textures[t.b].get();
             }
         }
+        if (!check_nesting(desc->n_textures, [&](uint32_t i, uint32_t *c) {
+                const vk_texture &t = desc->textures[i];
+                c[0] = t.a; c[1] = t.b;
+                return t.kind == VK_TEX_CHECKER; }, VK_MAX_CHECKER_DEPTH, "checker")) return false;
         if (textures_only) return true;      // (oracle_texture_values)
         materials.resize(desc->n_materials);
         for (uint32_t i = 0; i < desc->n_materials; i++) {
@@ -967,6 +1015,10 @@ struct Scene {
                 p->specular = materials[m.a].get(); p->diffuse = materials[m.b].get();
             }
         }
+        if (!check_nesting(desc->n_materials, [&](uint32_t i, uint32_t *c) {
+                const vk_material &m = desc->materials[i];
+                c[0] = m.a; c[1] = m.b;
+                return m.kind == VK_MAT_SPEC_DIFFUSE; }, VK_MAX_SPEC_DIFFUSE_DEPTH, "SpecDiffuse")) return false;
         world = build_ref(desc->world, 0);
         if (!world) return false;
         lights = std::make_shared<HittableList>();

@@ -1240,6 +1240,68 @@ struct Builder {
         return true;
     }
 
+    // Longest chain of inner records (checkers below a texture, SpecDiffuses below a material) starting at every record: 0 for a leaf,
+    // 1 + the deeper child for an inner record.  Iterative (a chain may be as long as the array); false when the graph has a cycle.
+    // The children's indices are in range (checked by the caller).
+    template <class Inner, class Child>
+    static bool chain_depths(uint32_t n, Inner inner, Child child, std::vector<uint32_t> &depth) {
+        depth.assign(n, 0u);
+        std::vector<uint8_t> state(n, 0);                      // 0 not seen, 1 on the path, 2 done
+        struct Fr { uint32_t node; int stage; };
+        std::vector<Fr> st;
+        for (uint32_t root = 0; root < n; root++) {
+            if (state[root] || !inner(root)) continue;
+            st.push_back(Fr{root, 0}); state[root] = 1;
+            while (!st.empty()) {
+                Fr &fr = st.back();
+                if (fr.stage == 2) {
+                    const uint32_t a = child(fr.node, 0), b = child(fr.node, 1);
+                    depth[fr.node] = 1u + (depth[a] > depth[b] ? depth[a] : depth[b]);
+                    state[fr.node] = 2; st.pop_back();
+                    continue;
+                }
+                const uint32_t c = child(fr.node, fr.stage);
+                fr.stage += 1;
+                if (!inner(c) || state[c] == 2) continue;
+                if (state[c] == 1) return false;
+                state[c] = 1; st.push_back(Fr{c, 0});          // (fr is invalid after this)
+            }
+        }
+        return true;
+    }
+
+    // What vk_trace.h can resolve (include/vecchio_amd.h, vk_texture / vk_material): texture_value spends one of its 16 iterations per
+    // checker and one on the leaf; shade_core's two loops and aov_albedo's stack hold 8 SpecDiffuse levels.  Past those the kernel would
+    // end the walk silently with a black texture / a wrong material, so deeper (or cyclic) graphs are refused here.
+    bool graph_limits() {
+        std::vector<uint32_t> depth;
+        if (!chain_depths(d->n_textures, [&](uint32_t i) { return d->textures[i].kind == VK_TEX_CHECKER; },
+                [&](uint32_t i, int k) { return k == 0 ? d->textures[i].a : d->textures[i].b; }, depth))
+            return fail(VK_ERR_BAD_ARG, "checker textures are cyclic");
+        for (uint32_t i = 0; i < d->n_textures; i++)
+            if (depth[i] > VK_MAX_CHECKER_DEPTH) return fail(VK_ERR_UNSUPPORTED, "device path: texture " + std::to_string(i) + " has " +
+                std::to_string(depth[i]) + " nested checkers, the limit is " + std::to_string(VK_MAX_CHECKER_DEPTH));
+        if (!chain_depths(d->n_materials, [&](uint32_t i) { return d->materials[i].kind == VK_MAT_SPEC_DIFFUSE; },
+                [&](uint32_t i, int k) { return k == 0 ? d->materials[i].a : d->materials[i].b; }, depth))
+            return fail(VK_ERR_BAD_ARG, "SpecDiffuse materials are cyclic");
+        for (uint32_t i = 0; i < d->n_materials; i++)
+            if (depth[i] > VK_MAX_SPEC_DIFFUSE_DEPTH) return fail(VK_ERR_UNSUPPORTED, "device path: material " + std::to_string(i) + " has " +
+                std::to_string(depth[i]) + " nested SpecDiffuses, the limit is " + std::to_string(VK_MAX_SPEC_DIFFUSE_DEPTH));
+        return true;
+    }
+
+    bool null_arrays() {
+        const struct { const char *name; uint32_t n; const void *p; } arrays[] = {
+            {"bvh", d->n_bvh, d->bvh}, {"spheres", d->n_spheres, d->spheres}, {"moving_spheres", d->n_moving_spheres, d->moving_spheres},
+            {"rects", d->n_rects, d->rects}, {"lists", d->n_lists, d->lists}, {"list_items", d->n_list_items, d->list_items},
+            {"media", d->n_media, d->media}, {"translates", d->n_translates, d->translates}, {"rotates", d->n_rotates, d->rotates},
+            {"materials", d->n_materials, d->materials}, {"textures", d->n_textures, d->textures}, {"images", d->n_images, d->images},
+            {"perlins", d->n_perlins, d->perlins}, {"lights", d->n_lights, d->lights}};
+        for (const auto &a : arrays)
+            if (a.n != 0u && !a.p) return fail(VK_ERR_BAD_ARG, std::string("null array with a non-zero count: ") + a.name);
+        return true;
+    }
+
     bool materials_and_textures() {
         for (uint32_t i = 0; i < d->n_textures; i++) {
             const vk_texture &t = d->textures[i];
@@ -1292,13 +1354,14 @@ struct Builder {
             } else if (m.kind != VK_MAT_DIELECTRIC) return fail(VK_ERR_BAD_ARG, "unknown material kind");
             L.materials.push_back(o);
         }
-        return true;
+        return graph_limits();
     }
 
     bool run() {
         if (!d) return fail(VK_ERR_BAD_ARG, "null scene description");
         // (ABI 7 left vk_scene_desc as ABI 6 had it)
         if (d->abi_version != VK_ABI_VERSION && d->abi_version != 6u) return fail(VK_ERR_BAD_ARG, "abi version mismatch");
+        if (!null_arrays()) return false;
         L.tie_base_rect = d->n_spheres; L.tie_base_box = d->n_spheres + d->n_rects;
         L.tie_base_list = d->n_spheres + d->n_rects + d->n_lists;
         if (!materials_and_textures()) return false;

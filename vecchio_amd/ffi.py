@@ -22,6 +22,7 @@ VK_REF_INDEX_MASK = 0x07FFFFFF
 (VK_MAT_LAMBERTIAN, VK_MAT_METAL, VK_MAT_DIELECTRIC, VK_MAT_DIFFUSE_LIGHT, VK_MAT_ISOTROPIC,
  VK_MAT_SPEC_DIFFUSE) = range(6)
 VK_TEX_SOLID, VK_TEX_CHECKER, VK_TEX_IMAGE, VK_TEX_NOISE = range(4)
+VK_MAX_CHECKER_DEPTH, VK_MAX_SPEC_DIFFUSE_DEPTH = 15, 8      # deepest nesting the device resolves (include/vecchio_amd.h)
 VK_INTEGRATOR_PDF, VK_INTEGRATOR_SCATTER = 0, 1
 VK_BACKGROUND_SOLID, VK_BACKGROUND_SKY = 0, 1
 VK_OUTPUT_F32, VK_OUTPUT_RGB8 = 0, 1
