@@ -628,6 +628,31 @@ int vk_trace_rays(vk_scene *scene, const vk_trace_params *params, const vk_ray *
 int vk_trace_rays_device(vk_scene *scene, const vk_trace_params *params, const void *d_rays, uint64_t n_rays, void *d_hits,
                          void *hip_stream, vk_stats *stats_out);
 
+/* ---- occlusion queries: any-hit for caller-supplied rays (additive symbols of ABI 7) --------------------------------------------------
+ * replaces: world.hit(&ray, 0.001, tmax).is_some(), for the shadow and visibility rays of the ray queries' users.
+ *   occluded[i] = 1 if BVHNode::hit(&Ray{origin, direction, time}, 0.001, tmax) returns Some, else 0.
+ *   THE CONTRACT: occluded[i] equals hits[i].hit of vk_trace_rays called with the same scene, params and rays, bit for bit, for every
+ *     ray, media included.  (BVHNode::hit only ever replaces an accepted hit with a closer one, so Some is decided at the first
+ *     acceptance; the walk stops there, after the same steps and — in a ConstantMedium — the same draws of the same stream.)
+ *   Everything else is vk_trace_rays' rule: tmin is VK_RAY_TMIN; a tmax that is a NaN or <= VK_RAY_TMIN gives 0 without a walk; with
+ *     nothing accepted a Rect at exactly tmax counts and a Sphere, a MovingSphere or a Boxy does not; non-finite rays are the
+ *     reference's (a NaN ray that "hits" a Rect with a NaN t is occluded = 1); the tree view; the stream of ray i,
+ *     rng_for_sample(seed + 0x9E3779B97F4A7C15 * (first_index + i), 0, 0); the scene-state rules (the scene's one render in flight,
+ *     nothing of vk_render's last frame, no vk_progress or vk_temporal handle touched); devices[0] of a multi-device scene.
+ *   Segment visibility between two points a and b is the ray origin = a, direction = b - a, tmax = 1: it needs no further call.
+ *   Arguments: VK_ERR_BAD_ARG with nothing enqueued and the outputs untouched for a null scene or params, null rays or occluded with
+ *     n_rays > 0, flags != 0, n_rays > 2^32.  n_rays == 0: VK_OK, nothing done (stats_out zeroed).  Bytes beyond occluded[n_rays - 1]
+ *     are never written.
+ *   stats_out: samples = n_rays, kernel_ms (vk_trace_occluded only: summed over its chunks), kernel_launches.
+ *   vk_trace_occluded stages rays and bytes through the ray queries' scratch of the scene handle, at most 2^20 rays at a time (longer
+ *     batches run in chunks, which first_index makes invisible).  No tables are uploaded: the call names no object.               */
+int vk_trace_occluded(vk_scene *scene, const vk_trace_params *params, const vk_ray *rays, uint64_t n_rays, uint8_t *occluded,
+                      vk_stats *stats_out);
+/* device buffers on the scene's device (devices[0] of a multi-device scene): d_rays 16-byte aligned, d_occluded (n_rays bytes) of any
+ * alignment; enqueued on hip_stream, no host wait */
+int vk_trace_occluded_device(vk_scene *scene, const vk_trace_params *params, const void *d_rays, uint64_t n_rays, void *d_occluded,
+                             void *hip_stream, vk_stats *stats_out);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

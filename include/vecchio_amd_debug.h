@@ -72,6 +72,12 @@ int vk_debug_math(int device, int op, const float *a, const float *b, float *out
 /* libvecchio_amd_debug.so only: how many device resources the library's handles (scenes, progressive and temporal handles) own right
  * now: out[0] device buffers, [1] pinned host buffers, [2] events, [3] streams.  Back at its earlier value once a handle is destroyed. */
 int vk_debug_live_objects(uint64_t out[4]);
+/* vk_trace_occluded_device through a named form of occlusion_kernel (vk_kernels.h).  refill = 0: one ray per lane (the A/B partner of
+ * the refill form; k and t are ignored).  refill != 0: the refill form with 64 * k rays per wave (k in 1..4096) that goes back to the
+ * claim once t lanes are idle (t in 1..64).  The bytes are the same for every choice.  libvecchio_amd_debug.so holds both forms;
+ * libvecchio_amd.so holds the form vk_trace_occluded launches and answers VK_ERR_UNSUPPORTED for the other one. */
+int vk_debug_trace_occluded_device(vk_scene *scene, const vk_trace_params *params, const void *d_rays, uint64_t n_rays, void *d_occluded,
+                                   void *hip_stream, int refill, uint32_t k, uint32_t t);
 
 #ifdef __cplusplus
 }

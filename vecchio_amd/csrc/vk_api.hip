@@ -2013,6 +2013,123 @@ int vk_trace_rays_device(vk_scene *scene, const vk_trace_params *params, const v
 
 }  // extern "C"
 
+// ---- occlusion queries (vk_trace_occluded): occlusion_kernel on the ray queries' tree view, device, staging buffer and events — rays,
+// then one byte per ray behind them.  No provenance: the call names no object.
+namespace {
+
+int check_occlusion_args(vk_scene *scene, const vk_trace_params *tp, const void *rays, uint64_t n_rays, const void *occluded) {
+    if (!scene || !tp) return fail(VK_ERR_BAD_ARG, "null argument (scene or trace parameters)");
+    if (tp->flags != 0u) return fail(VK_ERR_BAD_ARG, "trace flags must be 0");
+    if (n_rays > (1ull << 32)) return fail(VK_ERR_BAD_ARG, "n_rays exceeds 2^32");
+    if (n_rays != 0u && (!rays || !occluded)) return fail(VK_ERR_BAD_ARG, "null rays or occluded with n_rays > 0");
+    return VK_OK;
+}
+
+template <bool REFILL>
+void launch_occlusion(uint32_t features, const OcclusionArgs &A, hipStream_t st) {
+    // one ray per lane, or one block of 64 * k rays per wave
+    const uint64_t per_group = REFILL ? 64ull * A.k * (AOV_BLOCK / 64) : (uint64_t)AOV_BLOCK;
+    const dim3 grid((uint32_t)((A.n_rays + per_group - 1) / per_group));
+    // as enqueue_trace chooses
+    if (features == 0u) hipLaunchKernelGGL((occlusion_kernel<0u, REFILL>), grid, dim3(AOV_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL((occlusion_kernel<(uint32_t)VKF_ALL_SCENE, REFILL>), grid, dim3(AOV_BLOCK), 0, st, A);
+}
+
+// one launch for rays [0, n) of d_rays, whose first ray is ray `first_index` of the caller's batch
+int enqueue_occlusion(vk_scene *q, const vk_trace_params *tp, uint64_t first_index, const void *d_rays, uint64_t n, void *d_occluded,
+    hipStream_t st, bool refill = OCC_PRODUCTION_REFILL, uint32_t k = OCC_K, uint32_t t = OCC_T) {
+    OcclusionArgs A;
+    memset(&A, 0, sizeof(A));
+    A.S = aov_view(q);
+    if (!is_plain_tree_view(A.S))
+        return fail(VK_ERR_BAD_ARG, "internal error: an occlusion query needs a tree view without the rebuilt forms' gates");
+    A.rays = static_cast<const float4 *>(d_rays); A.occluded = static_cast<uint8_t *>(d_occluded);
+    A.seed = tp->seed; A.first_index = first_index; A.n_rays = n;
+    A.k = k; A.t = t;
+#ifdef VK_DEBUG_LIB      // both forms (vk_debug_trace_occluded_device); the product library holds the production form only
+    if (refill) launch_occlusion<true>(q->host->features, A, st); else launch_occlusion<false>(q->host->features, A, st);
+#else
+    if (refill != OCC_PRODUCTION_REFILL) return fail(VK_ERR_UNSUPPORTED, "this form of the occlusion kernel is in the debug library only");
+    launch_occlusion<OCC_PRODUCTION_REFILL>(q->host->features, A, st);
+#endif
+    HIP_TRY(hipGetLastError());
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_trace_occluded(vk_scene *scene, const vk_trace_params *params, const vk_ray *rays, uint64_t n_rays, uint8_t *occluded,
+    vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        int rc = check_occlusion_args(scene, params, rays, n_rays, occluded);
+        if (rc != VK_OK) return rc;
+        if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
+        if (n_rays == 0u) return VK_OK;
+        const auto t0 = std::chrono::steady_clock::now();
+        vk_scene *q = first_part(scene);
+        HIP_TRY(hipSetDevice(q->device));
+        const uint64_t cap = n_rays < RAY_CHUNK ? n_rays : RAY_CHUNK;
+        if ((rc = q->rays.buf.ensure((size_t)cap * (sizeof(vk_ray) + 1u))) != VK_OK) return rc;
+        if ((rc = q->rays.ev0.create()) != VK_OK || (rc = q->rays.ev1.create()) != VK_OK) return rc;
+        uint8_t *d_rays = q->rays.buf, *d_occluded = d_rays + (size_t)cap * sizeof(vk_ray);
+        double ms_sum = 0.0;
+        uint64_t launches = 0;
+        for (uint64_t at = 0; at < n_rays; at += cap) {
+            const uint64_t n = n_rays - at < cap ? n_rays - at : cap;
+            HIP_TRY(hipMemcpy(d_rays, rays + at, (size_t)n * sizeof(vk_ray), hipMemcpyHostToDevice));
+            HIP_TRY(hipEventRecord(q->rays.ev0, nullptr));
+            if ((rc = enqueue_occlusion(q, params, params->first_index + at, d_rays, n, d_occluded, nullptr)) != VK_OK) return rc;
+            HIP_TRY(hipEventRecord(q->rays.ev1, nullptr));
+            HIP_TRY(hipEventSynchronize(q->rays.ev1));
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, q->rays.ev0, q->rays.ev1));
+            ms_sum += (double)ms; launches++;
+            HIP_TRY(hipMemcpy(occluded + at, d_occluded, (size_t)n, hipMemcpyDeviceToHost));
+        }
+        if (stats_out) {
+            stats_out->samples = n_rays; stats_out->kernel_ms = ms_sum; stats_out->kernel_launches = (uint32_t)launches;
+            stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return VK_OK;
+    });
+}
+
+int vk_trace_occluded_device(vk_scene *scene, const vk_trace_params *params, const void *d_rays, uint64_t n_rays, void *d_occluded,
+    void *hip_stream, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        int rc = check_occlusion_args(scene, params, d_rays, n_rays, d_occluded);
+        if (rc != VK_OK) return rc;
+        if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
+        if (n_rays == 0u) return VK_OK;
+        vk_scene *q = first_part(scene);
+        HIP_TRY(hipSetDevice(q->device));
+        if ((rc = enqueue_occlusion(q, params, params->first_index, d_rays, n_rays, d_occluded, reinterpret_cast<hipStream_t>(hip_stream))) != VK_OK)
+            return rc;
+        if (stats_out) { stats_out->samples = n_rays; stats_out->kernel_launches = 1u; }
+        return VK_OK;
+    });
+}
+
+// test and report hook: vk_trace_occluded_device through the named form of the kernel (vecchio_amd_debug.h; the product library holds
+// the production form only and refuses the other one)
+int vk_debug_trace_occluded_device(vk_scene *scene, const vk_trace_params *params, const void *d_rays, uint64_t n_rays, void *d_occluded,
+    void *hip_stream, int refill, uint32_t k, uint32_t t) {
+    return guarded([&]() -> int {
+        int rc = check_occlusion_args(scene, params, d_rays, n_rays, d_occluded);
+        if (rc != VK_OK) return rc;
+        if (refill != 0 && (k < 1u || k > 4096u || t < 1u || t > 64u)) return fail(VK_ERR_BAD_ARG, "k must be in 1..4096 and t in 1..64");
+        if (n_rays == 0u) return VK_OK;
+        vk_scene *q = first_part(scene);
+        HIP_TRY(hipSetDevice(q->device));
+        return enqueue_occlusion(q, params, params->first_index, d_rays, n_rays, d_occluded, reinterpret_cast<hipStream_t>(hip_stream),
+                                 refill != 0, k, t);
+    });
+}
+
+}  // extern "C"
+
 // ---- the denoiser (vk_denoise): denoise_prepare_kernel, then one level kernel per pass (vk_kernels.h), on the scene's device (devices[0]
 // of a multi-device scene), on scratch and events of its own: nothing that describes vk_render's last frame is read or written.
 namespace {

@@ -1269,6 +1269,79 @@ __global__ __launch_bounds__(AOV_BLOCK) void trace_rays_kernel(TraceArgs A) {
     out[3] = make_uint4(w[12], w[13], w[14], w[15]);
 }
 
+// ---- occlusion queries (vk_trace_occluded): vk_trace.h occluded_ray for rays read from memory, one byte per ray.  Any-hit walks are
+// ragged — a ray that starts inside a box it hits ends in a few steps, a miss walks its whole candidate set — and with one ray per lane a
+// wave costs its slowest ray.  REFILL: a wave owns rays [wave * 64 * k, (wave + 1) * 64 * k) and hands them to its lanes as they fall
+// idle: the idle lanes' ballot, each one's rank in it (mbcnt), a wave-uniform cursor advanced by the popcount — plain C++, the cursor in
+// a scalar register because every operand is uniform.  The wave then steps its walking lanes and comes back to the claim once `t` lanes
+// are idle and rays remain.  A lane loads its ray as two 16-byte loads and stores its byte at the ray's own index.  No LDS, no atomics:
+// ray i's byte depends on (scene, ray i, seed, first_index + i) alone, so which lane walked it when cannot show.  !REFILL: one ray per
+// lane, trace_rays_kernel's shape (the A/B partner).  k and t are launch arguments so that tools/occlusion_report.py can sweep them;
+// OCC_K and OCC_T are the defaults.
+struct OcclusionArgs {
+    DScene S;                // a tree view (vk_api.hip aov_view)
+    const float4 *rays;      // vk_ray[n_rays]
+    uint8_t *occluded;       // [n_rays]
+    uint64_t seed, first_index, n_rays;
+    uint32_t k, t;           // REFILL only: rays per lane of a wave's block (>= 1), idle lanes that send the wave back to the claim (1..64)
+};
+constexpr uint32_t OCC_K = 8u, OCC_T = 16u;
+// The form vk_trace_occluded launches (the other one: the debug library only).  One ray per lane: on the MI355X the refill form was slower
+// on every batch of tools/occlusion_report.py, at every (k, t) swept (Occlusion queries: a wave that owns 64 * k rays leaves
+// the machine k times fewer waves to hide the walk's memory latency with, which costs more than the idle lanes it fills).
+constexpr bool OCC_PRODUCTION_REFILL = false;
+template <uint32_t F, bool REFILL>
+__global__ __launch_bounds__(AOV_BLOCK) void occlusion_kernel(OcclusionArgs A) {
+    const GlobalMem M{A.S.items, A.S.spheres, A.S.sphere_mat, A.S.boxes};
+    if constexpr (!REFILL) {
+        const uint64_t i = (uint64_t)blockIdx.x * AOV_BLOCK + threadIdx.x;
+        if (i >= A.n_rays) return;
+        const float4 r0 = A.rays[i * 2u], r1 = A.rays[i * 2u + 1u];
+        Lane L;
+        A.occluded[i] = occluded_ray<F, GlobalMem>(L, A.S, M, v3(r0.x, r0.y, r0.z), v3(r1.x, r1.y, r1.z), r1.w, r0.w,
+                                                   ray_seed(A.seed, A.first_index + i)) ? 1u : 0u;
+    } else {
+        // wave-uniform: the block's first ray, its length, how many of its rays have been handed out
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (AOV_BLOCK / 64) + (threadIdx.x >> 6));
+        const uint64_t per_wave = 64ull * A.k, first = (uint64_t)wave * per_wave;
+        if (first >= A.n_rays) return;
+        const uint32_t count = (uint32_t)(A.n_rays - first < per_wave ? A.n_rays - first : per_wave);
+        uint32_t next = 0u;
+        // (the block's own base pointers and seed: ray_seed(seed, first_index + first + m) = ray_seed(wseed, m) in wrapping u64)
+        const float4 *wrays = A.rays + first * 2u;
+        uint8_t *wout = A.occluded + first;
+        const uint64_t wseed = ray_seed(A.seed, A.first_index + first);
+        // A lane is idle when its Lane has nothing left to ask (occlusion_walking is false): at the start, after its ray's byte is stored.
+        Lane L;
+        L.i = 0u; L.end = 0u; L.pend = 0u; L.cur_inst = -1; L.cell = GRID_DONE; L.best_prim = 0u;
+        uint32_t mine = 0u;          // the ray this lane walks, counted from `first`
+        for (;;) {
+            const bool idle_lane = !occlusion_walking(L);
+            const unsigned long long idle = __ballot(idle_lane);
+            if (next < count && (uint32_t)__popcll(idle) >= A.t) {
+                // the claim: the idle lanes take rays first + next, first + next + 1, ... in lane order
+                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
+                if (idle_lane && next + rank < count) {
+                    mine = next + rank;
+                    const float4 r0 = wrays[mine * 2u], r1 = wrays[mine * 2u + 1u];
+                    const bool begun = occlusion_begin<F, GlobalMem>(L, A.S, v3(r0.x, r0.y, r0.z), v3(r1.x, r1.y, r1.z), r1.w, r0.w,
+                                                                     ray_seed(wseed, mine));
+                    // decided without a step (the tmax guard left L idle as it was; an empty world, a dead ray): not occluded
+                    if (!begun || !occlusion_walking(L)) wout[mine] = 0u;
+                }
+                const uint32_t taken = (uint32_t)__popcll(idle);
+                next = count - next < taken ? count : next + taken;
+            } else if (idle == ~0ull) {
+                break;               // nothing walks and nothing is left (every wave of a launch is a full one)
+            }
+            if (occlusion_walking(L)) {
+                traverse_step<F, GlobalMem>(L, A.S, M);
+                if (!occlusion_walking(L)) wout[mine] = L.best_prim != 0u ? 1u : 0u;
+            }
+        }
+    }
+}
+
 // ---- tile slabs: the pixels of one tile partition (tiles t = rank + i*world, i = 0..n_local) packed tile by tile,
 // 64 pixel slots per tile, 3 components per slot.  A multi-device scene moves one slab per device to devices[0]
 // (the path's only exchange) and de-interleaves it there; RGB8 output packs bytes (to_color fused: 4x less traffic).

@@ -1675,5 +1675,28 @@ VK_HD void hit_words(const RayHit &H, uint32_t w[16]) {
     w[12] = H.object; w[13] = H.medium; w[14] = 0u; w[15] = 0u;
 }
 
+// ------------------------------------------------------------------ occlusion queries (vk_trace_occluded, include/vecchio_amd.h)
+// world.hit(&Ray{o, d, time}, T_MIN, tmax).is_some(): trace_ray's tmax guard, stream and begin_segment, then the same steps only while
+// nothing has been accepted.  An acceptance is final for the question asked — the walk only ever replaces an accepted hit with a closer
+// one, best_prim never returns to 0 — and until the first one L.T is still tmax, so every step taken is trace_ray's step on trace_ray's
+// state: the answer is trace_ray's H.hit bit for bit.  A step may leave the leaf's right object queued in pend (prim_step tests the left
+// one first) or, in the sphere-only form, test both: neither matters, only existence is asked.  No record, no u/v, no provenance.
+// occlusion_begin: false = decided without a walk (not occluded)
+template <uint32_t F, class Mem>
+VK_HD bool occlusion_begin(Lane &L, const DScene &S, V3 o, V3 d, float time, float tmax, uint64_t rseed) {
+    if (!(tmax > T_MIN)) return false;
+    L.depth = 0u; L.pixel = 0u; L.sample = 0u;
+    if (F & VKF_MEDIUM) L.rng = vk::rng_for_sample(rseed, 0u, 0u);
+    begin_segment<Mem::ISHIFT, fused_box<F, Mem>(), spheres_only<F>()>(L, S, o, d, time, false, tmax);
+    return true;
+}
+VK_HD bool occlusion_walking(const Lane &L) { return L.best_prim == 0u && traversing(L); }
+template <uint32_t F, class Mem>
+VK_HD bool occluded_ray(Lane &L, const DScene &S, const Mem &M, V3 o, V3 d, float time, float tmax, uint64_t rseed) {
+    if (!occlusion_begin<F, Mem>(L, S, o, d, time, tmax, rseed)) return false;
+    while (occlusion_walking(L)) traverse_step<F, Mem>(L, S, M);
+    return L.best_prim != 0u;
+}
+
 }  // namespace vkd
 #endif

@@ -272,7 +272,7 @@ DEVICE_SYMBOLS = [
     "vk_progress_get_info", "vk_progress_destroy", "vk_progress_set_adaptive", "vk_progress_tile_samples",
     "vk_render_aov", "vk_render_aov_device",
     "vk_guide_default_params", "vk_render_guides", "vk_render_guides_device",
-    "vk_trace_rays", "vk_trace_rays_device",
+    "vk_trace_rays", "vk_trace_rays_device", "vk_trace_occluded", "vk_trace_occluded_device",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -353,6 +353,11 @@ def _bind(lib):
     lib.vk_trace_rays_device.restype = C.c_int
     lib.vk_trace_rays_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                          C.POINTER(Stats)]
+    lib.vk_trace_occluded.restype = C.c_int
+    lib.vk_trace_occluded.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_trace_occluded_device.restype = C.c_int
+    lib.vk_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                             C.POINTER(Stats)]
     lib.vk_denoise_default_params.restype = C.c_int
     lib.vk_denoise_default_params.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams)]
     lib.vk_denoise.restype = C.c_int
@@ -384,6 +389,9 @@ def _bind(lib):
     lib.vk_debug_last_launches.argtypes = [C.c_void_p, C.POINTER(DebugLaunch), C.c_uint32, C.POINTER(C.c_uint32)]
     lib.vk_debug_progress_moments.restype = C.c_int
     lib.vk_debug_progress_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_debug_trace_occluded_device.restype = C.c_int
+    lib.vk_debug_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                   C.c_int, C.c_uint32, C.c_uint32]
 
 
 _dbg = None

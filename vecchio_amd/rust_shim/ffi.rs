@@ -159,6 +159,11 @@ extern "C" {
                          stats_out: *mut vk_stats) -> c_int;
     pub fn vk_trace_rays_device(scene: *mut vk_scene, params: *const vk_trace_params, d_rays: *const c_void, n_rays: u64,
                                 d_hits: *mut c_void, hip_stream: *mut c_void, stats_out: *mut vk_stats) -> c_int;
+    // occlusion queries (additive symbols of ABI 7): occluded[i] = hits[i].hit of vk_trace_rays on the same arguments, one byte per ray
+    pub fn vk_trace_occluded(scene: *mut vk_scene, params: *const vk_trace_params, rays: *const vk_ray, n_rays: u64, occluded: *mut u8,
+                             stats_out: *mut vk_stats) -> c_int;
+    pub fn vk_trace_occluded_device(scene: *mut vk_scene, params: *const vk_trace_params, d_rays: *const c_void, n_rays: u64,
+                                    d_occluded: *mut c_void, hip_stream: *mut c_void, stats_out: *mut vk_stats) -> c_int;
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

@@ -182,6 +182,40 @@ class DeviceScene:
                                                  C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
         return (out, stats) if return_stats else out
 
+    def trace_occluded(self, rays, seed=0, first_index=0, out=None, stream=None, return_stats=False):
+        """Is anything between tmin and tmax of each caller-supplied ray (vk_trace_occluded): a uint8 array, occluded[i] == the `hit`
+        field trace_rays() returns for rays[i].  rays as for trace_rays(): a RAY_DTYPE array, or a device tensor ((n, 8) float32 on this
+        scene's device), which goes through vk_trace_occluded_device on `stream` without a host wait and returns an (n,) uint8 tensor
+        (or writes into `out`).  Visibility of the segment from a to b: origin a, direction b - a, tmax 1."""
+        tp = ffi.TraceParams(seed & 0xFFFFFFFFFFFFFFFF, first_index, 0, 0)
+        stats = ffi.Stats()
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8 != 0:
+                raise ValueError("device rays must be a contiguous float32 tensor of 8 floats per ray")
+            n = rays.numel() // 8
+            if out is None:
+                out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
+            if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != n:
+                raise ValueError("device occlusion bytes must be a contiguous uint8 tensor of one byte per ray")
+            check(self._lib, self._lib.vk_trace_occluded_device(self._h, C.byref(tp), C.c_void_p(rays.data_ptr() if n else None), n,
+                                                                C.c_void_p(out.data_ptr() if n else None), C.c_void_p(stream or 0),
+                                                                C.byref(stats)))
+            return (out, stats) if return_stats else out
+        rays = np.ascontiguousarray(rays)
+        if rays.dtype != RAY_DTYPE:
+            if rays.nbytes % 32 != 0 or rays.dtype.itemsize not in (4, 32):
+                raise ValueError("rays must be a RAY_DTYPE array (or float32 data of 8 floats per ray)")
+            rays = rays.reshape(-1).view(RAY_DTYPE)
+        rays = rays.reshape(-1)
+        if out is None:
+            out = np.zeros(rays.shape[0], np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.shape == rays.shape
+        n = rays.shape[0]
+        check(self._lib, self._lib.vk_trace_occluded(self._h, C.byref(tp), C.c_void_p(rays.ctypes.data if n else None), n,
+                                                     C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
+        return (out, stats) if return_stats else out
+
     GUIDE_CHANNELS = AOV_CHANNELS + ("bounces",)
 
     def guide_params(self, **overrides):
