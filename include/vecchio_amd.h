@@ -305,7 +305,20 @@ int vk_gather_backends(void);
  * (RotatingCamera, scene.rs:65-91).  The handle also owns per-launch scratch (work counter,
  * chunk partials, tile order): AT MOST ONE render may be in flight per vk_scene — calls on one
  * scene must be made from one thread at a time and be stream-ordered (the reference's frame loop,
- * main.rs:176, is exactly that); concurrent frames need one vk_scene each.                */
+ * main.rs:176, is exactly that); concurrent frames need one vk_scene each.
+ * STREAM-ORDERED, for the entry points that take a `hip_stream` (the *_device calls), means two things:
+ *   - Successive *_device calls on one scene (and on its vk_progress / vk_temporal handles) are ordered by the caller's stream(s): a
+ *     call's work starts after everything enqueued on its hip_stream before the call, and whatever is enqueued on that stream once the
+ *     call has returned starts after that work; the library's own streams fork from and join back into hip_stream.  Calls on ONE stream
+ *     need nothing else; a caller that moves to another stream orders the two itself (an event), as for any work on its buffers.
+ *   - Arguments passed by pointer to host structs (camera, render / guide / trace / denoise params) are consumed before the call
+ *     returns: the caller may overwrite or free them at once.  Device buffers are read and written in stream order.
+ * What is NOT promised: a blocking host-pointer call (vk_render, vk_progress_step, vk_render_aov, vk_trace_rays, vk_denoise,
+ * vk_temporal_accumulate, ...) works on the NULL stream and does not wait for a *_device call still in flight on the same scene.  The
+ * NULL stream waits for blocking streams only: after *_device calls on a non-blocking stream (hipStreamNonBlocking; PyTorch's streams
+ * are) the caller synchronises that stream before the blocking call.  The calls documented as waiting (vk_scene_last_*,
+ * vk_progress_get_info, vk_progress_stderr_device, vk_temporal_get_info, ...) wait for the scene's or the handle's last enqueued work.
+ * tests/test_gpu_stream_order.py holds every *_device entry point to the two promises on a non-blocking stream of the caller's.      */
 int vk_scene_create(const vk_scene_desc *desc, int device, vk_scene **out);
 /* same, uploaded to EVERY device in devices[0..n_devices) ("uploads to every participating
  * GPU").  vk_render / vk_render_device on such a scene deal this call's 8x8 tiles round-robin over the
