@@ -666,6 +666,51 @@ int vk_trace_occluded(vk_scene *scene, const vk_trace_params *params, const vk_r
 int vk_trace_occluded_device(vk_scene *scene, const vk_trace_params *params, const void *d_rays, uint64_t n_rays, void *d_occluded,
                              void *hip_stream, vk_stats *stats_out);
 
+/* ---- radiance queries: path-traced colour for caller-supplied rays (additive symbols of ABI 7) ---------------------------------------
+ * replaces: ray_color(&ray, &background, &world, &lights, 1) of main.rs:123-153 (ray_color_scatter for VK_INTEGRATOR_SCATTER), for rays
+ * the CALLER supplies: a panorama or environment-map bake, a fisheye or orthographic camera, a lightmap texel, an irradiance probe, a
+ * camera model of the caller's own.  rgb_out[i] is the mean of samples_per_ray samples of ray i.
+ *   Sample s of ray i, s in [first_sample, first_sample + samples_per_ray), is ray_color(&Ray{origin, direction, time}, depth 1) with the
+ *     scene's lights, the given background and max_depth, everything f32 and unfused in the reference's order: exactly what vk_render
+ *     computes for a sample once it has its primary ray.  Its stream is rng_for_sample(seed + 0x9E3779B97F4A7C15 * (first_index + i), 0,
+ *     s), in wrapping u64, taken from its beginning.  The ray is the same for every sample: a caller who wants jitter (antialiasing, a
+ *     lens, motion blur) supplies one ray per jittered sample.
+ *   tmax replaces infinity in the FIRST world.hit only, by vk_trace_rays' rules: a tmax that is a NaN or <= VK_RAY_TMIN misses without
+ *     a walk, and the path sees the background; with nothing accepted a Rect at exactly tmax is accepted and a Sphere, a MovingSphere
+ *     or a Boxy is not.  Later segments use infinity.  Hence: the first segment of sample 0 is, media draws included, exactly what
+ *     vk_trace_rays reports for the same seed, first_index and ray.
+ *   Tree view.  The one vk_trace_rays walks: the tree as handed over, or under VK_SCENE_FAST_ACCEL the rebuilt one.
+ *   Aggregation is vk_render's: a sample with a non-finite component adds nothing but counts in n (main.rs:192-194); sums are 64-bit
+ *     fixed point with 2^-26 resolution; a component beyond +-min(1e10, 1.3e11 / samples_per_ray) is clamped to that and the sample
+ *     counted in stats_out->clamped_samples; rgb_out[i] = sum / samples_per_ray.  The result is ONE value per (scene, params, ray,
+ *     index): it does not depend on the launch shape, on the order of the rays or on how a batch is cut into pieces whose first_index
+ *     continue each other.
+ *   max_depth = 0: every sample is (0,0,0), as for vk_render.
+ *   Arguments: VK_ERR_BAD_ARG with nothing enqueued and the outputs untouched for a null scene or params, null rays or rgb_out with
+ *     n_rays > 0, flags != 0, samples_per_ray outside 1..2^26, first_sample + samples_per_ray > 2^32 - 1, an unknown integrator or
+ *     background, n_rays > 2^32.  VK_ERR_UNSUPPORTED where vk_render answers it (the PDF integrator without lights, the scatter
+ *     integrator with a SpecDiffuse).  n_rays == 0: VK_OK, nothing done (stats_out zeroed).
+ *   Scene state: vk_trace_rays' rules.  The call is the scene's one render in flight; it touches nothing that describes vk_render's last
+ *     frame and no vk_progress or vk_temporal handle.  A multi-device scene runs the call on devices[0].  Rays and colours are staged
+ *     through the ray queries' scratch of the scene handle, at most 2^20 rays at a time (longer batches run in chunks, which first_index
+ *     makes invisible).  stats_out: samples = n_rays * samples_per_ray, kernel_ms (summed over the chunks), kernel_launches (one per
+ *     chunk), clamped_samples.
+ *   There is no device-pointer variant yet.                                                                                         */
+typedef struct vk_radiance_params {
+    uint64_t seed;
+    uint64_t first_index;        /* index of rays[0] in the caller's batch */
+    uint32_t samples_per_ray;    /* 1..2^26 */
+    uint32_t first_sample;       /* first_sample + samples_per_ray <= 2^32 - 1 */
+    uint32_t max_depth;          /* as vk_render_params.max_depth (0: every sample (0,0,0)) */
+    uint32_t integrator;         /* VK_INTEGRATOR_* */
+    uint32_t background;         /* VK_BACKGROUND_* */
+    float background_color[3];
+    uint32_t flags;              /* 0 */
+    uint32_t _pad;
+} vk_radiance_params;
+int vk_trace_radiance(vk_scene *scene, const vk_radiance_params *params, const vk_ray *rays, uint64_t n_rays,
+                      float *rgb_out /* n_rays * 3 */, vk_stats *stats_out);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

@@ -78,6 +78,14 @@ int vk_debug_live_objects(uint64_t out[4]);
  * libvecchio_amd.so holds the form vk_trace_occluded launches and answers VK_ERR_UNSUPPORTED for the other one. */
 int vk_debug_trace_occluded_device(vk_scene *scene, const vk_trace_params *params, const void *d_rays, uint64_t n_rays, void *d_occluded,
                                    void *hip_stream, int refill, uint32_t k, uint32_t t);
+/* as vk_trace_radiance, returning every sample: samples_out[(i * samples_per_ray + k) * 4 + 0..2] = the radiance before the finite
+ * filter, [+3] = the stream's counter at the sample's end (bit pattern); k = s - first_sample.  keys NULL: the public rule.  keys[i]
+ * given: sample k of ray i uses rng_for_sample(keys[i].seed, keys[i].pixel, keys[i].sample + k) with its counter set to keys[i].ctr
+ * before the first draw — a sample of vk_render is "the camera's draws, then ray_color on the same stream", so the query can resume
+ * that stream right behind the camera's draws and be compared with the oracle sample by sample.  In both libraries. */
+typedef struct vk_debug_stream_key { uint64_t seed; uint32_t pixel, sample, ctr, _pad; } vk_debug_stream_key;
+int vk_debug_trace_radiance_samples(vk_scene *scene, const vk_radiance_params *params, const vk_ray *rays, uint64_t n_rays,
+                                    const vk_debug_stream_key *keys, float *samples_out, vk_stats *stats_out);
 
 #ifdef __cplusplus
 }

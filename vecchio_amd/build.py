@@ -196,10 +196,10 @@ def build_emu(force=False):
     edir = os.path.join(ROOT, "tests", "emu")
     out = os.path.join(edir, "_build", "libemu.so")
     srcs = [os.path.join(edir, "emu.cpp"), os.path.join(edir, "emu_guides.cpp"), os.path.join(edir, "emu_rays.cpp"),
-            os.path.join(edir, "emu_occlusion.cpp"),
+            os.path.join(edir, "emu_occlusion.cpp"), os.path.join(edir, "emu_radiance.cpp"),
             os.path.join(CSRC, "vk_linearize.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h")] + \
-        [os.path.join(ROOT, "include", "vecchio_amd.h")]
+        [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
     if force or _newer(out, deps, CXXFLAGS):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         _run([CXX] + CXXFLAGS + ["-shared", "-o", out] + srcs + ["-lpthread"])

@@ -2130,6 +2130,186 @@ int vk_debug_trace_occluded_device(vk_scene *scene, const vk_trace_params *param
 
 }  // extern "C"
 
+// ---- radiance queries (vk_trace_radiance): radiance_kernel on the ray queries' tree view, device, staging buffer and events.  The
+// scratch of one chunk: [unit counter, clamped count: 32 bytes][rays][fixed-point sums][means] — or, for the per-sample hook,
+// [32 bytes][rays][samples][keys].  enqueue_radiance takes device pointers and a stream, so that a device-pointer variant is a wrapper.
+namespace {
+
+static_assert(sizeof(RadianceKey) == sizeof(vk_debug_stream_key) && sizeof(RadianceKey) == 24, "vk_debug_stream_key is what the kernel reads");
+constexpr size_t RAD_HEAD = 32;                  // bytes ahead of the rays: unit counter (u32), pad, clamped samples (u64), pad
+constexpr uint64_t RAD_HOOK_SAMPLES = 1ull << 22;    // samples per launch of the per-sample hook (64 MiB of them)
+
+int check_radiance_args(vk_scene *scene, const vk_radiance_params *rp, const void *rays, uint64_t n_rays, const void *out) {
+    if (!scene || !rp) return fail(VK_ERR_BAD_ARG, "null argument (scene or radiance parameters)");
+    if (rp->flags != 0u) return fail(VK_ERR_BAD_ARG, "radiance flags must be 0");
+    if (n_rays > (1ull << 32)) return fail(VK_ERR_BAD_ARG, "n_rays exceeds 2^32");
+    if (n_rays != 0u && (!rays || !out)) return fail(VK_ERR_BAD_ARG, "null rays or output with n_rays > 0");
+    if (rp->samples_per_ray == 0u || rp->samples_per_ray > (1u << 26)) return fail(VK_ERR_BAD_ARG, "samples_per_ray must be in 1..2^26");
+    if ((uint64_t)rp->first_sample + rp->samples_per_ray > 0xFFFFFFFFull) return fail(VK_ERR_BAD_ARG,
+        "first_sample + samples_per_ray exceeds 2^32 - 1");
+    if (rp->integrator > VK_INTEGRATOR_SCATTER || rp->background > VK_BACKGROUND_SKY) return fail(VK_ERR_BAD_ARG, "bad integrator/background");
+    return VK_OK;
+}
+
+template <uint32_t F>
+int launch_radiance(const RadianceArgs &A, dim3 grid, hipStream_t st) {
+    // Six waves per SIMD (80 VGPRs), as render_kernel's variants — except the everything-variants: render_kernel calls their SHADE + REFILL
+    // phase out of line to hold them there (shade_refill_call); this kernel keeps its phase inline, where 80 registers cost them ~500
+    // scratch instructions, so they are built for four (128 VGPRs)
+    constexpr int MINW = (F & VKF_ALL_SCENE) == VKF_ALL_SCENE ? 4 : 6;
+    auto kernel = &radiance_kernel<F, MINW>;
+    const size_t shmem = (size_t)(RAD_BLOCK / 64) * wave_block_floats<F>() * sizeof(float);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipLaunchKernelGGL(kernel, grid, dim3(RAD_BLOCK), shmem, st, A);
+    HIP_TRY(hipGetLastError());
+    return VK_OK;
+}
+
+// one launch for rays [0, n) of d_rays, whose first ray is ray `first_index` of the caller's batch: means into d_rgb through d_accum, or
+// (d_samples != null) every sample into d_samples.  d_head: RAD_HEAD bytes (cleared here).
+int enqueue_radiance(vk_scene *q, const vk_radiance_params *rp, uint64_t first_index, const void *d_rays, const void *d_keys, uint32_t n,
+    uint8_t *d_head, long long *d_accum, float *d_rgb, float *d_samples, hipStream_t st) {
+    RadianceArgs A;
+    memset(&A, 0, sizeof(A));
+    A.S = aov_view(q);
+    if (!is_plain_tree_view(A.S))
+        return fail(VK_ERR_BAD_ARG, "internal error: a radiance query needs a tree view without the rebuilt forms' gates");
+    A.C.spp = rp->samples_per_ray; A.C.max_depth = rp->max_depth; A.C.seed = rp->seed;
+    A.C.integrator = rp->integrator; A.C.background = rp->background;
+    A.C.bg[0] = rp->background_color[0]; A.C.bg[1] = rp->background_color[1]; A.C.bg[2] = rp->background_color[2];
+    A.rays = static_cast<const float4 *>(d_rays); A.keys = static_cast<const RadianceKey *>(d_keys);
+    A.accum = d_samples ? nullptr : d_accum; A.samples = reinterpret_cast<float4 *>(d_samples);
+    A.counter = reinterpret_cast<uint32_t *>(d_head); A.clamped = reinterpret_cast<unsigned long long *>(d_head + 8);
+    A.accum_clamp = accum_clamp_for(rp->samples_per_ray);
+    A.first_index = first_index; A.n_rays = n; A.first_sample = rp->first_sample;
+    A.shade_defer = SHADE_DEFER; A.prim_weight = q->plan.hot_bytes > (4u << 20) ? 3u : 1u;
+    // Units: (64 rays, a chunk of samples).  Enough of them to keep every wave of the launch busy four times over where the samples
+    // allow it, at least four samples to a chunk; a chunk stays below 2^16 samples (the kernel counts 64 x that in 32 bits).  Any choice
+    // gives the same sums.
+    const uint32_t spp = rp->samples_per_ray, n_blocks = (n + 63u) / 64u;
+    const uint32_t waves = (uint32_t)q->num_cus * 24u;
+    uint32_t n_chunks = (4u * waves + n_blocks - 1u) / n_blocks;
+    const uint32_t hi = spp / 4u > 4096u ? 4096u : (spp / 4u ? spp / 4u : 1u), lo = (spp + 65535u) / 65536u;
+    if (n_chunks > hi) n_chunks = hi;
+    if (n_chunks < lo) n_chunks = lo;
+    A.n_chunks = n_chunks;
+    const uint64_t units = (uint64_t)n_blocks * n_chunks;        // <= 2^14 * 2^12 for the host calls' chunks of 2^20 rays
+    if (units >= (1ull << 31)) return fail(VK_ERR_BAD_ARG, "internal error: too many work units in one radiance launch");
+    const uint64_t groups = (units + (RAD_BLOCK / 64) - 1) / (RAD_BLOCK / 64), full = (uint64_t)q->num_cus * 6u;   // (24 waves per CU)
+    const dim3 grid((uint32_t)(groups < full ? groups : full));
+    HIP_TRY(hipMemsetAsync(d_head, 0, RAD_HEAD, st));
+    if (A.accum) HIP_TRY(hipMemsetAsync(d_accum, 0, (size_t)n * 3u * sizeof(long long), st));
+    const uint32_t F = pick_variant(q) | (rp->integrator == VK_INTEGRATOR_PDF ? (uint32_t)VKF_INTEG_PDF : 0u);
+    const uint32_t F_CORNELL = VKF_RECT | VKF_LIST | VKF_INSTANCE | VKF_BOX;
+    int rc;
+    switch (F) {      // as launch_by_features chooses
+        case 0u: rc = launch_radiance<0u>(A, grid, st); break;
+        case VKF_INTEG_PDF: rc = launch_radiance<VKF_INTEG_PDF>(A, grid, st); break;
+        case F_CORNELL: rc = launch_radiance<F_CORNELL>(A, grid, st); break;
+        case F_CORNELL | VKF_INTEG_PDF: rc = launch_radiance<(F_CORNELL | VKF_INTEG_PDF)>(A, grid, st); break;
+        case VKF_ALL_SCENE: rc = launch_radiance<VKF_ALL_SCENE>(A, grid, st); break;
+        default: rc = launch_radiance<(VKF_ALL_SCENE | VKF_INTEG_PDF)>(A, grid, st); break;
+    }
+    if (rc != VK_OK) return rc;
+    if (A.accum) {
+        const uint32_t nv = n * 3u;
+        hipLaunchKernelGGL(radiance_resolve_kernel, dim3((nv + 255u) / 256u), dim3(256), 0, st, d_accum, d_rgb, nv, spp);
+        HIP_TRY(hipGetLastError());
+    }
+    return VK_OK;
+}
+
+// the host call behind vk_trace_radiance (keys == null, samples_out == null) and its per-sample hook
+int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *rays, uint64_t n_rays, const vk_debug_stream_key *keys,
+    float *rgb_out, float *samples_out, vk_stats *stats_out) {
+    int rc = check_radiance_args(scene, rp, rays, n_rays, samples_out ? samples_out : rgb_out);
+    if (rc != VK_OK) return rc;
+    if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
+    if (n_rays == 0u) return VK_OK;
+    {   // what vk_render refuses of a scene (check_render_args); the handle is read from here on
+        const LinearScene &H = *scene->host;
+        if (rp->integrator == VK_INTEGRATOR_PDF && H.lights.empty())
+            return fail(VK_ERR_UNSUPPORTED, "PDF integrator with an empty lights list (Vec::random unwraps None, hittable.rs:431)");
+        if (rp->integrator == VK_INTEGRATOR_SCATTER && (H.features & VKF_SPEC_DIFFUSE))
+            return fail(VK_ERR_UNSUPPORTED, "SpecDiffuse has no Material::scatter (default impl unwraps a None specular ray, material.rs:21-28)");
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t spp = rp->samples_per_ray;
+    if (rp->max_depth == 0u) {        // every sample is (0,0,0) (main.rs:126-128) and draws nothing
+        if (samples_out) {
+            for (uint64_t i = 0; i < n_rays; i++) for (uint32_t k = 0; k < spp; k++) {
+                float *o = samples_out + (i * spp + k) * 4u;
+                const uint32_t ctr = keys ? keys[i].ctr : 0u;
+                o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f; memcpy(o + 3, &ctr, 4);
+            }
+        } else {
+            memset(rgb_out, 0, (size_t)n_rays * 3u * sizeof(float));
+        }
+        if (stats_out) stats_out->samples = n_rays * spp;
+        return VK_OK;
+    }
+    vk_scene *q = first_part(scene);
+    HIP_TRY(hipSetDevice(q->device));
+    uint64_t cap = n_rays < RAY_CHUNK ? n_rays : RAY_CHUNK;
+    if (samples_out) { const uint64_t c = RAD_HOOK_SAMPLES / spp ? RAD_HOOK_SAMPLES / spp : 1u; if (cap > c) cap = c; }
+    const size_t per_ray = samples_out ? sizeof(vk_ray) + (size_t)spp * 16u + sizeof(vk_debug_stream_key)
+                                       : sizeof(vk_ray) + 3u * sizeof(long long) + 3u * sizeof(float);
+    if ((rc = q->rays.buf.ensure(RAD_HEAD + (size_t)cap * per_ray)) != VK_OK) return rc;
+    if ((rc = q->rays.ev0.create()) != VK_OK || (rc = q->rays.ev1.create()) != VK_OK) return rc;
+    uint8_t *d_head = q->rays.buf, *d_rays = d_head + RAD_HEAD, *d_second = d_rays + (size_t)cap * sizeof(vk_ray);
+    // (means: sums, then means; hook: samples, then keys)
+    uint8_t *d_third = d_second + (size_t)cap * (samples_out ? (size_t)spp * 16u : 3u * sizeof(long long));
+    double ms_sum = 0.0;
+    uint64_t launches = 0, clamped = 0;
+    for (uint64_t at = 0; at < n_rays; at += cap) {
+        const uint64_t n = n_rays - at < cap ? n_rays - at : cap;
+        HIP_TRY(hipMemcpy(d_rays, rays + at, (size_t)n * sizeof(vk_ray), hipMemcpyHostToDevice));
+        if (samples_out && keys) HIP_TRY(hipMemcpy(d_third, keys + at, (size_t)n * sizeof(vk_debug_stream_key), hipMemcpyHostToDevice));
+        HIP_TRY(hipEventRecord(q->rays.ev0, nullptr));
+        if (samples_out) rc = enqueue_radiance(q, rp, rp->first_index + at, d_rays, keys ? d_third : nullptr, (uint32_t)n, d_head, nullptr,
+                                               nullptr, reinterpret_cast<float *>(d_second), nullptr);
+        else rc = enqueue_radiance(q, rp, rp->first_index + at, d_rays, nullptr, (uint32_t)n, d_head, reinterpret_cast<long long *>(d_second),
+                                   reinterpret_cast<float *>(d_third), nullptr, nullptr);
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipEventRecord(q->rays.ev1, nullptr));
+        HIP_TRY(hipEventSynchronize(q->rays.ev1));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, q->rays.ev0, q->rays.ev1));
+        ms_sum += (double)ms; launches++;
+        if (samples_out) HIP_TRY(hipMemcpy(samples_out + at * spp * 4u, d_second, (size_t)n * spp * 16u, hipMemcpyDeviceToHost));
+        else HIP_TRY(hipMemcpy(rgb_out + at * 3u, d_third, (size_t)n * 3u * sizeof(float), hipMemcpyDeviceToHost));
+        unsigned long long c = 0;
+        HIP_TRY(hipMemcpy(&c, d_head + 8, sizeof(c), hipMemcpyDeviceToHost));
+        clamped += c;
+    }
+    if (stats_out) {
+        stats_out->samples = n_rays * spp; stats_out->kernel_ms = ms_sum; stats_out->kernel_launches = (uint32_t)launches;
+        stats_out->clamped_samples = clamped;
+        stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_trace_radiance(vk_scene *scene, const vk_radiance_params *params, const vk_ray *rays, uint64_t n_rays, float *rgb_out,
+    vk_stats *stats_out) {
+    return guarded([&]() -> int { return radiance_host(scene, params, rays, n_rays, nullptr, rgb_out, nullptr, stats_out); });
+}
+
+// test hook (vecchio_amd_debug.h): every sample of the query, optionally on streams resumed from keys
+int vk_debug_trace_radiance_samples(vk_scene *scene, const vk_radiance_params *params, const vk_ray *rays, uint64_t n_rays,
+    const vk_debug_stream_key *keys, float *samples_out, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        if (n_rays != 0u && !samples_out) return fail(VK_ERR_BAD_ARG, "null samples buffer");
+        return radiance_host(scene, params, rays, n_rays, keys, nullptr, samples_out, stats_out);
+    });
+}
+
+}  // extern "C"
+
 // ---- the denoiser (vk_denoise): denoise_prepare_kernel, then one level kernel per pass (vk_kernels.h), on the scene's device (devices[0]
 // of a multi-device scene), on scratch and events of its own: nothing that describes vk_render's last frame is read or written.
 namespace {

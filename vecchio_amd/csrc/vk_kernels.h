@@ -1703,6 +1703,275 @@ __global__ __launch_bounds__(DN_BLOCK) void temporal_accumulate_kernel(TaArgs A)
     if ((threadIdx.x & 63u) == 0u && m != 0ull) atomicAdd(A.count, (unsigned long long)__popcll(m));
 }
 
+// ---- radiance queries (vk_trace_radiance): ray_color for rays read from memory.  render_kernel's shape — a persistent kernel, the
+// wave-level phase scheduler (BOX / PRIM / SHADE + REFILL), idle lanes refilled by ballot + prefix popcount, cold path state parked in
+// the wave's LDS block, finished samples summed in 64-bit fixed point — around a different REFILL: a work unit is (64 consecutive rays,
+// a chunk of samples), item k of it is ray slot k & 63, sample s0 + (k >> 6).  A refilled lane loads its vk_ray as two 16-byte loads,
+// seeds its stream from the ray's index (or from keys[i], the test hook) and starts its first segment with the ray's tmax as the
+// closest distance so far.  A unit's sums collect in the wave's 64 x 3 LDS accumulators and reach the launch's sums (accum, one triple
+// per ray) when the wave pulls its next unit; radiance_resolve_kernel divides.  With `samples` set every sample's 16 bytes are stored
+// instead (the per-sample hook).  The scene is walked from global memory on the ray queries' tree view (vk_api.hip aov_view): no
+// rebuilt form, no requeue, no probe build; a new kernel, so that no instance of render_kernel changes.
+struct RadianceKey { uint64_t seed; uint32_t pixel, sample, ctr, _pad; };      // vk_debug_stream_key (vecchio_amd_debug.h)
+struct RadianceArgs {
+    DScene S;                // a tree view (vk_api.hip aov_view)
+    RenderConsts C;          // seed, spp = samples_per_ray, max_depth, integrator, background; no camera, no image size
+    const float4 *rays;      // vk_ray[n_rays]
+    const RadianceKey *keys; // [n_rays] or null = the public rule
+    long long *accum;        // [n_rays * 3] fixed-point sums, or null (the per-sample hook)
+    float4 *samples;         // [n_rays * spp] (rgb, final counter) or null
+    uint32_t *counter;       // work-unit counter
+    unsigned long long *clamped;
+    float accum_clamp;
+    uint64_t first_index;
+    uint32_t n_rays, first_sample, n_chunks, shade_defer, prim_weight;
+};
+typedef const __attribute__((address_space(4))) RadianceArgs *RArgsC;
+__device__ __forceinline__ RArgsC rargs_fresh() {       // (see kargs_fresh)
+    RArgsC p = (RArgsC)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+#define RARG(p, field) (*(const decltype(RadianceArgs::field) *)&((p)->field))
+constexpr int RAD_BLOCK = 256;       // 4 waves per workgroup
+enum : int { RS_BLOCK = 0, RS_S0 = 1, RS_TOTAL = 2, RS_NEXT = 3 };      // the wave state: the unit being handed out (cf. WS_*)
+
+// adds the wave's LDS sums of ray block `blk` (lane = ray slot) to the launch's accumulators and clears them
+__device__ __forceinline__ void flush_ray_sums(unsigned long long *sums, long long *accum, uint32_t blk, uint32_t lane, uint32_t n_rays) {
+    const uint32_t r = blk * 64u + lane;
+    if (!accum || blk == 0xFFFFFFFFu || r >= n_rays) return;
+    unsigned long long *a = reinterpret_cast<unsigned long long *>(accum) + (size_t)r * 3;
+    for (int c = 0; c < 3; c++) {
+        unsigned long long v = sums[lane * 3 + c];
+        if (v) { atomicAdd(a + c, v); sums[lane * 3 + c] = 0ull; }
+    }
+}
+
+// the SHADE + REFILL phase (cf. shade_refill_body).  Leaves `fresh` lanes with a new ray parked in L.wo / L.wd / L.time; t0 / walk are
+// what its first segment starts with (radiance_start_core; +inf / true for a path that continues).
+template <uint32_t F>
+__device__ __forceinline__ void radiance_phase(Lane &L, bool is_shade, bool &active, bool &need, bool &fresh, bool &touched, float &t0,
+                                               bool &walk, RArgsC P, float *cold, unsigned long long *sums, uint32_t *wstate, uint32_t lane) {
+    RenderConsts C = RARG(P, C);
+    DScene S = RARG(P, S);
+    GlobalMem M = make_mem<F, false>(S, 0u);
+    fresh = false; t0 = INFINITY; walk = true;
+    const PreTurb pre_turb = cooperative_turb<F, GlobalMem>(L, S, M, is_shade, lane);
+    touched = is_shade;
+    if (is_shade) {
+        cold_load_path<F>(cold, lane, L);
+        V3 no, nd; float nt;
+        bool cont = shade_core<F, GlobalMem>(L, S, M, C, no, nd, nt, pre_turb, no_pre_ball());
+        if (cont) { L.wo = no; L.wd = nd; L.time = nt; fresh = true; }
+        else {
+            const uint32_t r = __float_as_uint(cold[CF_XY * 64 + lane]);       // the ray, counted from the launch's first
+            float4 *dbg = RARG(P, samples);
+            if (dbg) dbg[(size_t)r * C.spp + (__float_as_uint(cold[CF_SAMPLE * 64 + lane]) - RARG(P, first_sample))] =
+                make_float4(L.acc.x, L.acc.y, L.acc.z, __uint_as_float(L.rng.ctr));
+            long long *acc = RARG(P, accum);
+            if (acc && isfinite(L.acc.x) && isfinite(L.acc.y) && isfinite(L.acc.z)) {   // main.rs:192-194; c += color (main.rs:193)
+                const float clampv = RARG(P, accum_clamp);
+                const float big = fmaxf(fmaxf(fabsf(L.acc.x), fabsf(L.acc.y)), fabsf(L.acc.z));
+                unsigned long long fx, fy, fz;
+                if (big <= ACCUM_SMALL) {
+                    fx = (unsigned long long)to_fixed_small(L.acc.x); fy = (unsigned long long)to_fixed_small(L.acc.y);
+                    fz = (unsigned long long)to_fixed_small(L.acc.z);
+                } else {
+                    if (big > clampv) atomicAdd(RARG(P, clamped), 1ull);     // (rare)
+                    fx = (unsigned long long)to_fixed(L.acc.x, clampv); fy = (unsigned long long)to_fixed(L.acc.y, clampv);
+                    fz = (unsigned long long)to_fixed(L.acc.z, clampv);
+                }
+                // a sample of the block the wave is handing out lands in the wave's LDS sums; a straggler of an earlier unit goes to
+                // the launch's sums directly
+                if ((r >> 6) == __builtin_amdgcn_readfirstlane(wstate[RS_BLOCK])) {
+                    unsigned long long *t = sums + (r & 63u) * 3u;
+                    atomicAdd(t + 0, fx); atomicAdd(t + 1, fy); atomicAdd(t + 2, fz);
+                } else {
+                    unsigned long long *a = reinterpret_cast<unsigned long long *>(acc) + (size_t)r * 3;
+                    atomicAdd(a + 0, fx); atomicAdd(a + 1, fy); atomicAdd(a + 2, fz);
+                }
+            }
+            active = false;
+            need = true;
+        }
+    }
+    // ---- hand out (ray, sample) items of the wave's current unit to the lanes without a path; pull the next unit when it is used up
+    for (;;) {
+        unsigned long long need_mask = __builtin_amdgcn_ballot_w64(need);
+        if (!need_mask) break;
+        uint4 ws = *reinterpret_cast<const uint4 *>(wstate);
+        uint32_t blk = __builtin_amdgcn_readfirstlane(ws.x), s0 = __builtin_amdgcn_readfirstlane(ws.y);
+        uint32_t total = __builtin_amdgcn_readfirstlane(ws.z), next = __builtin_amdgcn_readfirstlane(ws.w);
+        const uint32_t n_rays = RARG(P, n_rays);
+        if (next >= total) {
+            uint32_t unit = 0;
+            if (lane == 0) unit = atomicAdd(RARG(P, counter), 1u);
+            unit = __builtin_amdgcn_readfirstlane(unit);
+            const uint32_t n_chunks = RARG(P, n_chunks);
+            // (the host keeps blocks x chunks below 2^31 and a chunk below 2^20 samples)
+            if (unit >= ((n_rays + 63u) >> 6) * n_chunks) { need = false; break; }
+            flush_ray_sums(sums, RARG(P, accum), blk, lane, n_rays);          // the finished unit's sums so far
+            const uint32_t chunk = unit % n_chunks;
+            blk = unit / n_chunks;
+            s0 = (uint32_t)(((uint64_t)C.spp * chunk) / n_chunks);
+            const uint32_t s1 = (uint32_t)(((uint64_t)C.spp * (chunk + 1)) / n_chunks);
+            next = 0u; total = 64u * (s1 - s0);
+            s0 += RARG(P, first_sample);
+            if (lane == 0) { wstate[RS_BLOCK] = blk; wstate[RS_S0] = s0; wstate[RS_TOTAL] = total; }
+        }
+        const uint32_t k = next + (uint32_t)__popcll(need_mask & ((1ull << lane) - 1ull));
+        if (need && k < total) {
+            const uint32_t r = blk * 64u + (k & 63u), smp = s0 + (k >> 6);
+            if (r < n_rays) {                  // slots behind the batch's last ray are skipped: the lane asks again
+                cold[CF_XY * 64 + lane] = __uint_as_float(r);
+                cold[CF_SAMPLE * 64 + lane] = __uint_as_float(smp);
+                const float4 *rays = RARG(P, rays);
+                const float4 r0 = rays[(size_t)r * 2u], r1 = rays[(size_t)r * 2u + 1u];
+                const RadianceKey *keys = RARG(P, keys);
+                Rng g;
+                if (keys) {
+                    const RadianceKey kk = keys[r];
+                    g = vk::rng_for_sample(kk.seed, kk.pixel, kk.sample + (smp - RARG(P, first_sample)));
+                    g.ctr = kk.ctr;
+                } else {
+                    g = radiance_rng(C.seed, RARG(P, first_index) + r, smp);
+                }
+                radiance_start_core(L, g, r0.w, t0, walk);
+                L.wo = v3(r0.x, r0.y, r0.z); L.wd = v3(r1.x, r1.y, r1.z); L.time = r1.w;
+                fresh = true;
+                active = true;
+                need = false;
+                touched = true;
+            }
+        }
+        const uint32_t taken = (uint32_t)__popcll(need_mask);
+        if (lane == 0) wstate[RS_NEXT] = next + taken < total ? next + taken : total;
+    }
+}
+
+template <uint32_t F, int MINW>
+__global__ __launch_bounds__(RAD_BLOCK, MINW) void radiance_kernel(RadianceArgs A_byval) {
+    (void)A_byval;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    using Mem = GlobalMem;
+    // ---- LDS layout: per wave [cold lane state | block sums: 64 x 3 x u64 | wave state]
+    float *cold = reinterpret_cast<float *>(smem) + wave * wave_block_floats<F>();
+    unsigned long long *sums = reinterpret_cast<unsigned long long *>(cold + 64 * ncold<F>());
+    uint32_t *wstate = reinterpret_cast<uint32_t *>(cold + 64 * ncold<F>() + 64 * 3 * 2);
+    // the wave has no unit yet: the first SHADE + REFILL phase pulls one
+    sums[lane * 3 + 0] = 0ull; sums[lane * 3 + 1] = 0ull; sums[lane * 3 + 2] = 0ull;
+    if (lane == 0) { wstate[RS_BLOCK] = 0xFFFFFFFFu; wstate[RS_NEXT] = 0u; wstate[RS_TOTAL] = 0u; }
+
+    Lane L;
+    __builtin_memset(&L, 0, sizeof(L));
+    L.cur_inst = -1; L.cell = GRID_DONE;
+    bool need = true;          // lane has no path and wants an item (false once the launch's units are all handed out)
+    bool active = false;       // lane holds a live path
+    uint32_t shade_defer, prim_weight;
+    { RArgsC U = rargs_fresh(); shade_defer = RARG(U, shade_defer); prim_weight = RARG(U, prim_weight); }
+    unsigned long long m_act = 0ull, m_need = ~0ull;
+    // the scheduler of render_kernel (which see): the wave runs the code of the most populated state with the lanes in it
+    for (;;) {
+        const bool HAS_HEAVY = (F & (VKF_LIST | VKF_MEDIUM | VKF_INSTANCE | VKF_BOX)) != 0;
+        const unsigned long long m_pend0 = __builtin_amdgcn_uicmp(L.pend, 0u, 33 /* ne */) & m_act;
+        unsigned long long m_trav = __builtin_amdgcn_uicmp(L.i, L.end, 36 /* ult */);
+        if (F & VKF_INSTANCE) m_trav |= __builtin_amdgcn_sicmp(L.cur_inst, 0, 39 /* sge */);
+        const unsigned long long m_heavy = HAS_HEAVY ? (heavy_mask<F>(L.pend) & m_pend0) : 0ull;
+        const unsigned long long m_light = m_pend0 & ~m_heavy;
+        const unsigned long long m_shade = m_act & ~m_pend0 & ~m_trav;
+        const uint32_t n_box = (uint32_t)__builtin_popcountll(m_act & ~m_pend0 & m_trav);
+        const uint32_t n_heavy = (uint32_t)__builtin_popcountll(m_heavy), n_light = (uint32_t)__builtin_popcountll(m_light);
+        const uint32_t n_prim = n_heavy > n_light ? n_heavy : n_light;
+        const uint32_t n_sn = (uint32_t)__builtin_popcountll(m_shade | m_need);
+        if ((n_box | n_prim | n_sn) == 0) break;
+        if (n_box >= n_prim * prim_weight && n_box * shade_defer >= n_sn) {
+            // ---- BOX: UNROLL steps under a shrinking EXEC mask per exit test, while box lanes are the plurality
+            RArgsC P = rargs_fresh();
+            DScene S = RARG(P, S);
+            Mem M = make_mem<F, false>(S, 0u);
+            const uint32_t live = n_box + n_heavy + n_light + n_sn;
+            constexpr bool SPHERES = (F & ~(uint32_t)VKF_INTEG_PDF) == 0u;
+            constexpr int UNROLL = ((F & VKF_ALL_SCENE) == VKF_ALL_SCENE) ? BOX_UNROLL + 1 : (SPHERES ? VK_GLOBAL_SPHERE_UNROLL : VK_CORNELL_UNROLL);
+            unsigned long long m_pend, m_lt, m_inst = 0ull;
+            auto masks = [&]() {
+                m_pend = __builtin_amdgcn_uicmp(L.pend, 0u, 33 /* ne */);
+                m_lt = __builtin_amdgcn_uicmp(L.i, range_end<F, Mem>(L, S), 36 /* ult */);
+                if (F & VKF_INSTANCE) m_inst = __builtin_amdgcn_sicmp(L.cur_inst, 0, 39 /* sge */);
+            };
+            masks();
+            for (;;) {
+                if (F & VKF_INSTANCE) {     // end of an instance's item range: back to the parent space (rare)
+                    const unsigned long long m_leave = m_act & ~m_pend & ~m_lt & m_inst;
+                    if (m_leave != 0ull) {
+                        if (__builtin_amdgcn_inverse_ballot_w64(m_leave)) { cold_load_world_ray<F>(cold, lane, L);
+                            leave_instance<F, Mem>(L, S); }
+                        masks();
+                    }
+                }
+                const bool go = __builtin_amdgcn_inverse_ballot_w64(m_act & ~m_pend & m_lt);
+                box_steps<F, Mem, UNROLL>(L, S, M, go);
+                masks();
+                const unsigned long long m_prim = m_pend & m_act, m_box = (m_lt | m_inst) & ~m_pend & m_act;
+                const uint32_t nb = (uint32_t)__builtin_popcountll(m_box), np = (uint32_t)__builtin_popcountll(m_prim);
+                const uint32_t ns = live - nb - np;
+                const int keep1 = (int)nb - (int)(np * prim_weight > 1u ? np * prim_weight : 1u), keep2 = (int)(nb * shade_defer) - (int)ns;
+                if ((keep1 | keep2) < 0) {
+                    // a LIGHT primitive test runs right here and the loop keeps stepping (see render_kernel)
+                    const unsigned long long m_lt2 = HAS_HEAVY ? (m_prim & ~heavy_mask<F>(L.pend)) : m_prim;
+                    const uint32_t nl = (uint32_t)__builtin_popcountll(m_lt2);
+                    if ((((int)nl - 1) | ((int)(2u * nl) - (int)np) | ((int)(nl * shade_defer) - (int)ns)) >= 0) {
+                        if (__builtin_amdgcn_inverse_ballot_w64(m_lt2)) prim_step<F, Mem>(L, S, M);
+                        masks();
+                        continue;
+                    }
+                    break;
+                }
+            }
+        } else if (n_prim * shade_defer >= n_sn) {
+            // ---- PRIM: intersect / enter the pending object
+            RArgsC P = rargs_fresh();
+            DScene S = RARG(P, S);
+            Mem M = make_mem<F, false>(S, 0u);
+            if (__builtin_amdgcn_inverse_ballot_w64(n_heavy > n_light ? m_heavy : m_light)) {
+                if (F & VKF_MEDIUM) {    // ConstantMedium::hit draws inside traversal (hittable.rs:473)
+                    L.rng.key = (uint64_t)__float_as_uint(cold[CF_KEY * 64 + lane]) |
+                                ((uint64_t)__float_as_uint(cold[(CF_KEY + 1) * 64 + lane]) << 32);
+                    L.rng.ctr = __float_as_uint(cold[CF_CTR * 64 + lane]);
+                }
+                prim_step<F, Mem>(L, S, M);
+                if (F & VKF_MEDIUM) cold[CF_CTR * 64 + lane] = __uint_as_float(L.rng.ctr);
+            }
+        } else {
+            // ---- SHADE + REFILL; one begin_segment for both kinds of new ray
+            const bool is_shade = __builtin_amdgcn_inverse_ballot_w64(m_shade);
+            bool touched = false, fresh = false, walk = true;
+            float t0 = INFINITY;
+            radiance_phase<F>(L, is_shade, active, need, fresh, touched, t0, walk, rargs_fresh(), cold, sums, wstate, lane);
+            if (fresh) {
+                RArgsC P = rargs_fresh();
+                DScene S = RARG(P, S);
+                begin_segment<Mem::ISHIFT, fused_box<F, Mem>(), spheres_only<F>()>(L, S, L.wo, L.wd, L.time, false, t0);
+                if (!walk) radiance_skip_walk(L);
+            }
+            if (active && touched) cold_store_path<F>(cold, lane, L);
+            m_act = __builtin_amdgcn_ballot_w64(active); m_need = __builtin_amdgcn_ballot_w64(need);
+        }
+    }
+    {   // the last unit's sums
+        RArgsC P = rargs_fresh();
+        flush_ray_sums(sums, RARG(P, accum), __builtin_amdgcn_readfirstlane(wstate[RS_BLOCK]), lane, RARG(P, n_rays));
+    }
+}
+
+// ray mean = fixed-point sum / samples_per_ray (resolve_kernel's arithmetic)
+__global__ void radiance_resolve_kernel(const long long *accum, float *out, uint32_t n_values, uint32_t spp) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_values) return;
+    const float inv_scale = 1.0f / ACCUM_SCALE;
+    out[i] = ((float)accum[i] * inv_scale) / (float)spp;
+}
+
 #ifdef VK_DEBUG_LIB
 // device math probe (tests: GPU transcendental/draw functions are bit-identical to the host's)
 __global__ void math_probe_kernel(int op, const float *a, const float *b, float *out, size_t n) {

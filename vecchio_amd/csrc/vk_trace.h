@@ -1698,5 +1698,36 @@ VK_HD bool occluded_ray(Lane &L, const DScene &S, const Mem &M, V3 o, V3 d, floa
     return L.best_prim != 0u;
 }
 
+// ------------------------------------------------------------------ radiance queries (vk_trace_radiance, include/vecchio_amd.h)
+// ray_color(&Ray{o, d, time}, depth 1) on the stream `rng` (taken where it stands) for a ray the caller supplies: start_sample_core's
+// path state without its camera.  The new ray is returned parked in L.wo / L.wd / L.time, as start_sample_core's callers expect it;
+// `t0` is the closest-so-far distance its first segment starts with (trace_ray's tmax) and `walk` says whether that segment is walked at
+// all: a tmax that is a NaN or <= T_MIN misses without a walk, and the path sees the background (radiance_skip_walk).
+VK_HD void radiance_start_core(Lane &L, const Rng &rng, float tmax, float &t0, bool &walk) {
+    L.pixel = 0u; L.sample = 0u;
+    L.rng = rng;
+    L.thr = v3s(1.0f); L.acc = v3s(0.0f); L.depth = 1;
+    walk = tmax > T_MIN;
+    t0 = walk ? tmax : INFINITY;
+}
+// after begin_segment: nothing left to ask, nothing accepted (shade_core then takes the miss branch on L.wd)
+VK_HD void radiance_skip_walk(Lane &L) { L.i = L.end; L.pend = 0u; L.pend2 = 0u; L.cur_inst = -1; L.cell = GRID_DONE; L.best_prim = 0u; }
+// the stream of sample s of ray `index` of a batch (the public rule)
+VK_HD Rng radiance_rng(uint64_t seed, uint64_t index, uint32_t s) { return vk::rng_for_sample(ray_seed(seed, index), 0u, s); }
+// one whole sample inside the lane (the host emulator; the device kernel runs the same pieces under its phase scheduler).  S must be a
+// tree view (no grid, no rebuilt-form gates).  Returns the radiance before the finite filter; the stream's final counter is L.rng.ctr.
+template <uint32_t F, class Mem>
+VK_HD V3 radiance_sample(Lane &L, const DScene &S, const Mem &M, const RenderConsts &C, V3 o, V3 d, float time, float tmax, const Rng &rng) {
+    float t0; bool walk;
+    radiance_start_core(L, rng, tmax, t0, walk);
+    begin_segment<Mem::ISHIFT, fused_box<F, Mem>(), spheres_only<F>()>(L, S, o, d, time, false, t0);
+    if (!walk) radiance_skip_walk(L);
+    for (;;) {
+        while (traversing(L)) traverse_step<F, Mem>(L, S, M);
+        if (!shade<F, Mem>(L, S, M, C)) break;
+    }
+    return L.acc;
+}
+
 }  // namespace vkd
 #endif

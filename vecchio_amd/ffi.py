@@ -177,6 +177,18 @@ class TraceParams(C.Structure):
 VK_RAY_TMIN = 0.001
 
 
+class RadianceParams(C.Structure):
+    """vk_radiance_params (vk_trace_radiance)"""
+    _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64), ("samples_per_ray", C.c_uint32), ("first_sample", C.c_uint32),
+                ("max_depth", C.c_uint32), ("integrator", C.c_uint32), ("background", C.c_uint32), ("background_color", F3),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class DebugStreamKey(C.Structure):
+    """vk_debug_stream_key of include/vecchio_amd_debug.h (vk_debug_trace_radiance_samples)"""
+    _fields_ = [("seed", C.c_uint64), ("pixel", C.c_uint32), ("sample", C.c_uint32), ("ctr", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class GuideParams(C.Structure):
     """vk_guide_params (vk_render_guides)"""
     _fields_ = [("max_bounces", C.c_uint32), ("fuzz_max", C.c_float), ("flags", C.c_uint32)]
@@ -273,6 +285,7 @@ DEVICE_SYMBOLS = [
     "vk_render_aov", "vk_render_aov_device",
     "vk_guide_default_params", "vk_render_guides", "vk_render_guides_device",
     "vk_trace_rays", "vk_trace_rays_device", "vk_trace_occluded", "vk_trace_occluded_device",
+    "vk_trace_radiance",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -355,6 +368,8 @@ def _bind(lib):
                                          C.POINTER(Stats)]
     lib.vk_trace_occluded.restype = C.c_int
     lib.vk_trace_occluded.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_trace_radiance.restype = C.c_int
+    lib.vk_trace_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
     lib.vk_trace_occluded_device.restype = C.c_int
     lib.vk_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                              C.POINTER(Stats)]
@@ -389,6 +404,9 @@ def _bind(lib):
     lib.vk_debug_last_launches.argtypes = [C.c_void_p, C.POINTER(DebugLaunch), C.c_uint32, C.POINTER(C.c_uint32)]
     lib.vk_debug_progress_moments.restype = C.c_int
     lib.vk_debug_progress_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_debug_trace_radiance_samples.restype = C.c_int
+    lib.vk_debug_trace_radiance_samples.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(Stats)]
     lib.vk_debug_trace_occluded_device.restype = C.c_int
     lib.vk_debug_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_uint32, C.c_uint32]

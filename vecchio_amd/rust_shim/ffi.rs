@@ -105,6 +105,9 @@ pub struct vk_hit { pub p: [f32; 3], pub t: f32, pub normal: [f32; 3], pub u: f3
 pub struct vk_trace_params { pub seed: u64, pub first_index: u64, pub flags: u32, pub _pad: u32 }
 
 #[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_radiance_params { pub seed: u64, pub first_index: u64, pub samples_per_ray: u32, pub first_sample: u32, pub max_depth: u32, pub integrator: u32, pub background: u32, pub background_color: [f32; 3], pub flags: u32, pub _pad: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_temporal_params { pub width: u32, pub height: u32, pub max_history: u32, pub depth_tol: f32, pub normal_cos_min: f32, pub albedo_floor: f32, pub flags: u32 }
 
 #[repr(C)] #[derive(Copy, Clone, Default)]
@@ -164,6 +167,9 @@ extern "C" {
                              stats_out: *mut vk_stats) -> c_int;
     pub fn vk_trace_occluded_device(scene: *mut vk_scene, params: *const vk_trace_params, d_rays: *const c_void, n_rays: u64,
                                     d_occluded: *mut c_void, hip_stream: *mut c_void, stats_out: *mut vk_stats) -> c_int;
+    // radiance queries (additive symbols of ABI 7): rgb_out[i] = the mean of samples_per_ray samples of ray_color(rays[i]), 3 floats per ray
+    pub fn vk_trace_radiance(scene: *mut vk_scene, params: *const vk_radiance_params, rays: *const vk_ray, n_rays: u64, rgb_out: *mut f32,
+                             stats_out: *mut vk_stats) -> c_int;
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

@@ -68,6 +68,8 @@ class HostScene:
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmax", "<f4"), ("direction", "<f4", 3), ("time", "<f4")])
 HIT_DTYPE = np.dtype([("p", "<f4", 3), ("t", "<f4"), ("normal", "<f4", 3), ("u", "<f4"), ("v", "<f4"), ("hit", "<u4"), ("front", "<u4"),
                       ("material", "<u4"), ("object", "<u4"), ("medium", "<u4"), ("_pad", "<u4", 2)])
+KEY_DTYPE = np.dtype([("seed", "<u8"), ("pixel", "<u4"), ("sample", "<u4"), ("ctr", "<u4"), ("_pad", "<u4")])   # vk_debug_stream_key
+assert KEY_DTYPE.itemsize == C.sizeof(ffi.DebugStreamKey) == 24
 assert RAY_DTYPE.itemsize == C.sizeof(ffi.Ray) == 32 and HIT_DTYPE.itemsize == C.sizeof(ffi.Hit) == 64
 
 
@@ -214,6 +216,56 @@ class DeviceScene:
         n = rays.shape[0]
         check(self._lib, self._lib.vk_trace_occluded(self._h, C.byref(tp), C.c_void_p(rays.ctypes.data if n else None), n,
                                                      C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
+        return (out, stats) if return_stats else out
+
+    @staticmethod
+    def _host_rays(rays):
+        rays = np.ascontiguousarray(rays)
+        if rays.dtype != RAY_DTYPE:
+            if rays.nbytes % 32 != 0 or rays.dtype.itemsize not in (4, 32):
+                raise ValueError("rays must be a RAY_DTYPE array (or float32 data of 8 floats per ray)")
+            rays = rays.reshape(-1).view(RAY_DTYPE)
+        return rays.reshape(-1)
+
+    @staticmethod
+    def radiance_params(seed=0, first_index=0, samples_per_ray=1, first_sample=0, max_depth=50, integrator=ffi.VK_INTEGRATOR_PDF,
+                        background=ffi.VK_BACKGROUND_SOLID, background_color=(0.0, 0.0, 0.0)):
+        """A vk_radiance_params (ffi.RadianceParams)."""
+        return ffi.RadianceParams(seed & 0xFFFFFFFFFFFFFFFF, first_index, samples_per_ray, first_sample, max_depth, integrator, background,
+                                  ffi.F3(*background_color), 0, 0)
+
+    def trace_radiance(self, rays, seed=0, first_index=0, samples_per_ray=1, first_sample=0, max_depth=50,
+                       integrator=ffi.VK_INTEGRATOR_PDF, background=ffi.VK_BACKGROUND_SOLID, background_color=(0.0, 0.0, 0.0), out=None,
+                       return_stats=False):
+        """Path-traced colour arriving along caller-supplied rays (vk_trace_radiance): an (n, 3) float32 array, out[i] the mean of
+        samples first_sample .. first_sample + samples_per_ray - 1 of rays[i], each ray_color(rays[i]) on its own stream.  rays as for
+        trace_rays(): a RAY_DTYPE array (host memory; the call has no device-pointer variant yet)."""
+        rp = self.radiance_params(seed, first_index, samples_per_ray, first_sample, max_depth, integrator, background, background_color)
+        stats = ffi.Stats()
+        rays = self._host_rays(rays)
+        n = rays.shape[0]
+        if out is None:
+            out = np.zeros((n, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (n, 3)
+        check(self._lib, self._lib.vk_trace_radiance(self._h, C.byref(rp), C.c_void_p(rays.ctypes.data if n else None), n,
+                                                     C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
+        return (out, stats) if return_stats else out
+
+    def debug_radiance_samples(self, rays, keys=None, return_stats=False, **params):
+        """Every sample of trace_radiance() (vk_debug_trace_radiance_samples, a test hook): an (n, samples_per_ray, 4) float32 array,
+        [..., :3] the radiance before the finite filter, [..., 3] the stream's final counter (bit pattern).  keys: None, or one
+        (seed, pixel, sample, ctr) per ray as a KEY_DTYPE array, whose streams the samples resume.  params: radiance_params()'s keywords."""
+        rp = self.radiance_params(**params)
+        stats = ffi.Stats()
+        rays = self._host_rays(rays)
+        n = rays.shape[0]
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, KEY_DTYPE).reshape(-1)
+            assert keys.shape[0] == n
+        out = np.zeros((n, rp.samples_per_ray, 4), np.float32)
+        check(self._lib, self._lib.vk_debug_trace_radiance_samples(self._h, C.byref(rp), C.c_void_p(rays.ctypes.data if n else None), n,
+                                                                   C.c_void_p(keys.ctypes.data if keys is not None and n else None),
+                                                                   C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
         return (out, stats) if return_stats else out
 
     GUIDE_CHANNELS = AOV_CHANNELS + ("bounces",)
