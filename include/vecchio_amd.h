@@ -711,6 +711,39 @@ typedef struct vk_radiance_params {
 int vk_trace_radiance(vk_scene *scene, const vk_radiance_params *params, const vk_ray *rays, uint64_t n_rays,
                       float *rgb_out /* n_rays * 3 */, vk_stats *stats_out);
 
+/* ---- irradiance queries: cosine-weighted radiance at caller-supplied points (additive symbols of ABI 7) ------------------------------
+ * replaces: CosinePDF::new(n).generate() (util.rs:126-130, 144-146) followed by ray_color, for surface points the CALLER supplies: a
+ * lightmap texel, an irradiance probe, an ambient term.  rgb_out[i] is the mean radiance arriving at point i over cosine-weighted
+ * directions of the hemisphere around its normal.  The directions are drawn on the device from each sample's own stream: the caller
+ * uploads 32 bytes per point, not per sample, and keeps sample windows and the one-value guarantee of vk_trace_radiance.
+ *   A point is a vk_ray read as: origin = the position p; direction = the surface normal n, of any non-zero length (the hemisphere is
+ *     the one around n as given: the call is one-sided); time = the time of every ray from the point; tmax cuts the first segment only,
+ *     by vk_trace_radiance's rule (a finite tmax gives a range-limited gather: what lies beyond it is the background).
+ *   Sample s of point i, s in [first_sample, first_sample + samples_per_ray), everything f32 and unfused in the reference's order:
+ *     g = rng_for_sample(seed + 0x9E3779B97F4A7C15 * (first_index + i), 0, s), in wrapping u64, taken from its beginning;
+ *     local = random_cosine_direction(g) (util.rs:52-63: two gen_f32 draws, so the stream's counter stands at 2);
+ *     d = ONB::new_from_w(n).local(local) (util.rs:95-110), not normalised afterwards;
+ *     the sample is ray_color(&Ray{p, d, time}, depth 1) CONTINUING the stream g (ray_color_scatter for VK_INTEGRATOR_SCATTER), tmax
+ *     the closest-so-far distance of its first world.hit.  Everything behind that is vk_trace_radiance's rule word for word: the tree
+ *     view, VK_RAY_TMIN, media draws from the sample's stream.  max_depth = 0: every sample is (0,0,0) and nothing is drawn.
+ *   Aggregation is vk_trace_radiance's: a sample with a non-finite component adds nothing but counts in n; sums are 64-bit fixed point
+ *     with 2^-26 resolution; a component beyond +-min(1e10, 1.3e11 / samples_per_ray) is clamped to that and the sample counted in
+ *     stats_out->clamped_samples; rgb_out[i] = sum / samples_per_ray.  The result is ONE value per (scene, params, point, index): it
+ *     does not depend on the launch shape, on the order of the points or on how a batch is cut into pieces whose first_index continue
+ *     each other.
+ *   What the value is.  The plain mean of the samples' radiance.  The directions' density cos / pi cancels the cosine of the irradiance
+ *     integral, so the irradiance is E = pi * rgb_out[i], and a Lambertian texel of albedo a radiates a * rgb_out[i].  The library does
+ *     not multiply by pi: the result stays the exact fixed-point mean.
+ *   Degenerate normals get no special case.  ONB::new_from_w of a zero or non-finite normal has NaN axes; the ray is then non-finite and
+ *     follows vk_trace_rays' rule for non-finite rays.  In a world of spheres only such a point sees the background along a NaN
+ *     direction: VK_BACKGROUND_SOLID gives background_color exactly, VK_BACKGROUND_SKY gives NaN samples, which are dropped, so the
+ *     result is (0,0,0).
+ *   Arguments, VK_ERR_UNSUPPORTED, n_points == 0, scene state, multi-device scenes, staging (at most 2^20 points at a time through the
+ *     ray queries' scratch) and stats_out (samples = n_points * samples_per_ray) are vk_trace_radiance's, with the same messages.
+ *   There is no device-pointer variant yet.                                                                                         */
+int vk_trace_irradiance(vk_scene *scene, const vk_radiance_params *params, const vk_ray *points, uint64_t n_points,
+                        float *rgb_out /* n_points * 3 */, vk_stats *stats_out);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

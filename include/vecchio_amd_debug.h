@@ -86,6 +86,12 @@ int vk_debug_trace_occluded_device(vk_scene *scene, const vk_trace_params *param
 typedef struct vk_debug_stream_key { uint64_t seed; uint32_t pixel, sample, ctr, _pad; } vk_debug_stream_key;
 int vk_debug_trace_radiance_samples(vk_scene *scene, const vk_radiance_params *params, const vk_ray *rays, uint64_t n_rays,
                                     const vk_debug_stream_key *keys, float *samples_out, vk_stats *stats_out);
+/* as vk_trace_irradiance, returning every sample: samples_out[(i * samples_per_ray + k) * 4 + 0..3] as above (the counter includes the
+ * direction's two draws) and, with dirs_out given, dirs_out[(i * samples_per_ray + k) * 4 + 0..2] = the direction drawn for the sample,
+ * [+3] = 0.  There are no keys: the public stream rule is the only one.  max_depth = 0: both are zeros.  In both libraries. */
+int vk_debug_trace_irradiance_samples(vk_scene *scene, const vk_radiance_params *params, const vk_ray *points, uint64_t n_points,
+                                      float *samples_out /* n * spp * 4 */, float *dirs_out /* n * spp * 4, may be NULL */,
+                                      vk_stats *stats_out);
 
 #ifdef __cplusplus
 }

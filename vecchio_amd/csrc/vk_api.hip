@@ -2133,6 +2133,8 @@ int vk_debug_trace_occluded_device(vk_scene *scene, const vk_trace_params *param
 // ---- radiance queries (vk_trace_radiance): radiance_kernel on the ray queries' tree view, device, staging buffer and events.  The
 // scratch of one chunk: [unit counter, clamped count: 32 bytes][rays][fixed-point sums][means] — or, for the per-sample hook,
 // [32 bytes][rays][samples][keys].  enqueue_radiance takes device pointers and a stream, so that a device-pointer variant is a wrapper.
+// Irradiance queries (vk_trace_irradiance) are the same calls with `gather` set: gather_kernel instead of radiance_kernel, the rays read
+// as (point, normal) records, no keys, and in the hook's scratch the drawn directions where the keys would be.
 namespace {
 
 static_assert(sizeof(RadianceKey) == sizeof(vk_debug_stream_key) && sizeof(RadianceKey) == 24, "vk_debug_stream_key is what the kernel reads");
@@ -2151,13 +2153,14 @@ int check_radiance_args(vk_scene *scene, const vk_radiance_params *rp, const voi
     return VK_OK;
 }
 
-template <uint32_t F>
+template <uint32_t F, bool GATHER>
 int launch_radiance(const RadianceArgs &A, dim3 grid, hipStream_t st) {
     // Six waves per SIMD (80 VGPRs), as render_kernel's variants — except the everything-variants: render_kernel calls their SHADE + REFILL
     // phase out of line to hold them there (shade_refill_call); this kernel keeps its phase inline, where 80 registers cost them ~500
     // scratch instructions, so they are built for four (128 VGPRs)
     constexpr int MINW = (F & VKF_ALL_SCENE) == VKF_ALL_SCENE ? 4 : 6;
-    auto kernel = &radiance_kernel<F, MINW>;
+    // (gather_kernel: the same rule; DESIGN.md "Irradiance queries" has its instances' numbers)
+    auto kernel = GATHER ? &gather_kernel<F, MINW> : &radiance_kernel<F, MINW>;
     const size_t shmem = (size_t)(RAD_BLOCK / 64) * wave_block_floats<F>() * sizeof(float);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     hipLaunchKernelGGL(kernel, grid, dim3(RAD_BLOCK), shmem, st, A);
@@ -2165,10 +2168,16 @@ int launch_radiance(const RadianceArgs &A, dim3 grid, hipStream_t st) {
     return VK_OK;
 }
 
+template <uint32_t F>
+int launch_query(bool gather, const RadianceArgs &A, dim3 grid, hipStream_t st) {
+    return gather ? launch_radiance<F, true>(A, grid, st) : launch_radiance<F, false>(A, grid, st);
+}
+
 // one launch for rays [0, n) of d_rays, whose first ray is ray `first_index` of the caller's batch: means into d_rgb through d_accum, or
-// (d_samples != null) every sample into d_samples.  d_head: RAD_HEAD bytes (cleared here).
+// (d_samples != null) every sample into d_samples.  d_head: RAD_HEAD bytes (cleared here).  gather: d_rays holds points, gather_kernel
+// runs, and with d_samples every sample's direction goes to d_dirs where that is given.
 int enqueue_radiance(vk_scene *q, const vk_radiance_params *rp, uint64_t first_index, const void *d_rays, const void *d_keys, uint32_t n,
-    uint8_t *d_head, long long *d_accum, float *d_rgb, float *d_samples, hipStream_t st) {
+    uint8_t *d_head, long long *d_accum, float *d_rgb, float *d_samples, hipStream_t st, bool gather = false, float *d_dirs = nullptr) {
     RadianceArgs A;
     memset(&A, 0, sizeof(A));
     A.S = aov_view(q);
@@ -2179,6 +2188,7 @@ int enqueue_radiance(vk_scene *q, const vk_radiance_params *rp, uint64_t first_i
     A.C.bg[0] = rp->background_color[0]; A.C.bg[1] = rp->background_color[1]; A.C.bg[2] = rp->background_color[2];
     A.rays = static_cast<const float4 *>(d_rays); A.keys = static_cast<const RadianceKey *>(d_keys);
     A.accum = d_samples ? nullptr : d_accum; A.samples = reinterpret_cast<float4 *>(d_samples);
+    A.dirs = gather && d_samples ? reinterpret_cast<float4 *>(d_dirs) : nullptr;
     A.counter = reinterpret_cast<uint32_t *>(d_head); A.clamped = reinterpret_cast<unsigned long long *>(d_head + 8);
     A.accum_clamp = accum_clamp_for(rp->samples_per_ray);
     A.first_index = first_index; A.n_rays = n; A.first_sample = rp->first_sample;
@@ -2203,12 +2213,12 @@ int enqueue_radiance(vk_scene *q, const vk_radiance_params *rp, uint64_t first_i
     const uint32_t F_CORNELL = VKF_RECT | VKF_LIST | VKF_INSTANCE | VKF_BOX;
     int rc;
     switch (F) {      // as launch_by_features chooses
-        case 0u: rc = launch_radiance<0u>(A, grid, st); break;
-        case VKF_INTEG_PDF: rc = launch_radiance<VKF_INTEG_PDF>(A, grid, st); break;
-        case F_CORNELL: rc = launch_radiance<F_CORNELL>(A, grid, st); break;
-        case F_CORNELL | VKF_INTEG_PDF: rc = launch_radiance<(F_CORNELL | VKF_INTEG_PDF)>(A, grid, st); break;
-        case VKF_ALL_SCENE: rc = launch_radiance<VKF_ALL_SCENE>(A, grid, st); break;
-        default: rc = launch_radiance<(VKF_ALL_SCENE | VKF_INTEG_PDF)>(A, grid, st); break;
+        case 0u: rc = launch_query<0u>(gather, A, grid, st); break;
+        case VKF_INTEG_PDF: rc = launch_query<VKF_INTEG_PDF>(gather, A, grid, st); break;
+        case F_CORNELL: rc = launch_query<F_CORNELL>(gather, A, grid, st); break;
+        case F_CORNELL | VKF_INTEG_PDF: rc = launch_query<(F_CORNELL | VKF_INTEG_PDF)>(gather, A, grid, st); break;
+        case VKF_ALL_SCENE: rc = launch_query<VKF_ALL_SCENE>(gather, A, grid, st); break;
+        default: rc = launch_query<(VKF_ALL_SCENE | VKF_INTEG_PDF)>(gather, A, grid, st); break;
     }
     if (rc != VK_OK) return rc;
     if (A.accum) {
@@ -2219,9 +2229,10 @@ int enqueue_radiance(vk_scene *q, const vk_radiance_params *rp, uint64_t first_i
     return VK_OK;
 }
 
-// the host call behind vk_trace_radiance (keys == null, samples_out == null) and its per-sample hook
+// the host call behind vk_trace_radiance (keys == null, samples_out == null) and its per-sample hook; with `gather` the one behind
+// vk_trace_irradiance and its hook (rays = the points, keys == null; dirs_out: the hook's directions, or null)
 int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *rays, uint64_t n_rays, const vk_debug_stream_key *keys,
-    float *rgb_out, float *samples_out, vk_stats *stats_out) {
+    float *rgb_out, float *samples_out, vk_stats *stats_out, bool gather = false, float *dirs_out = nullptr) {
     int rc = check_radiance_args(scene, rp, rays, n_rays, samples_out ? samples_out : rgb_out);
     if (rc != VK_OK) return rc;
     if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
@@ -2242,6 +2253,7 @@ int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *r
                 const uint32_t ctr = keys ? keys[i].ctr : 0u;
                 o[0] = 0.0f; o[1] = 0.0f; o[2] = 0.0f; memcpy(o + 3, &ctr, 4);
             }
+            if (dirs_out) memset(dirs_out, 0, (size_t)n_rays * spp * 16u);          // (no direction is drawn either)
         } else {
             memset(rgb_out, 0, (size_t)n_rays * 3u * sizeof(float));
         }
@@ -2252,12 +2264,12 @@ int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *r
     HIP_TRY(hipSetDevice(q->device));
     uint64_t cap = n_rays < RAY_CHUNK ? n_rays : RAY_CHUNK;
     if (samples_out) { const uint64_t c = RAD_HOOK_SAMPLES / spp ? RAD_HOOK_SAMPLES / spp : 1u; if (cap > c) cap = c; }
-    const size_t per_ray = samples_out ? sizeof(vk_ray) + (size_t)spp * 16u + sizeof(vk_debug_stream_key)
+    const size_t per_ray = samples_out ? sizeof(vk_ray) + (size_t)spp * 16u + (dirs_out ? (size_t)spp * 16u : sizeof(vk_debug_stream_key))
                                        : sizeof(vk_ray) + 3u * sizeof(long long) + 3u * sizeof(float);
     if ((rc = q->rays.buf.ensure(RAD_HEAD + (size_t)cap * per_ray)) != VK_OK) return rc;
     if ((rc = q->rays.ev0.create()) != VK_OK || (rc = q->rays.ev1.create()) != VK_OK) return rc;
     uint8_t *d_head = q->rays.buf, *d_rays = d_head + RAD_HEAD, *d_second = d_rays + (size_t)cap * sizeof(vk_ray);
-    // (means: sums, then means; hook: samples, then keys)
+    // (means: sums, then means; hook: samples, then keys or directions)
     uint8_t *d_third = d_second + (size_t)cap * (samples_out ? (size_t)spp * 16u : 3u * sizeof(long long));
     double ms_sum = 0.0;
     uint64_t launches = 0, clamped = 0;
@@ -2267,9 +2279,10 @@ int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *r
         if (samples_out && keys) HIP_TRY(hipMemcpy(d_third, keys + at, (size_t)n * sizeof(vk_debug_stream_key), hipMemcpyHostToDevice));
         HIP_TRY(hipEventRecord(q->rays.ev0, nullptr));
         if (samples_out) rc = enqueue_radiance(q, rp, rp->first_index + at, d_rays, keys ? d_third : nullptr, (uint32_t)n, d_head, nullptr,
-                                               nullptr, reinterpret_cast<float *>(d_second), nullptr);
+                                               nullptr, reinterpret_cast<float *>(d_second), nullptr, gather,
+                                               dirs_out ? reinterpret_cast<float *>(d_third) : nullptr);
         else rc = enqueue_radiance(q, rp, rp->first_index + at, d_rays, nullptr, (uint32_t)n, d_head, reinterpret_cast<long long *>(d_second),
-                                   reinterpret_cast<float *>(d_third), nullptr, nullptr);
+                                   reinterpret_cast<float *>(d_third), nullptr, nullptr, gather);
         if (rc != VK_OK) return rc;
         HIP_TRY(hipEventRecord(q->rays.ev1, nullptr));
         HIP_TRY(hipEventSynchronize(q->rays.ev1));
@@ -2278,6 +2291,7 @@ int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *r
         ms_sum += (double)ms; launches++;
         if (samples_out) HIP_TRY(hipMemcpy(samples_out + at * spp * 4u, d_second, (size_t)n * spp * 16u, hipMemcpyDeviceToHost));
         else HIP_TRY(hipMemcpy(rgb_out + at * 3u, d_third, (size_t)n * 3u * sizeof(float), hipMemcpyDeviceToHost));
+        if (samples_out && dirs_out) HIP_TRY(hipMemcpy(dirs_out + at * spp * 4u, d_third, (size_t)n * spp * 16u, hipMemcpyDeviceToHost));
         unsigned long long c = 0;
         HIP_TRY(hipMemcpy(&c, d_head + 8, sizeof(c), hipMemcpyDeviceToHost));
         clamped += c;
@@ -2305,6 +2319,20 @@ int vk_debug_trace_radiance_samples(vk_scene *scene, const vk_radiance_params *p
     return guarded([&]() -> int {
         if (n_rays != 0u && !samples_out) return fail(VK_ERR_BAD_ARG, "null samples buffer");
         return radiance_host(scene, params, rays, n_rays, keys, nullptr, samples_out, stats_out);
+    });
+}
+
+int vk_trace_irradiance(vk_scene *scene, const vk_radiance_params *params, const vk_ray *points, uint64_t n_points, float *rgb_out,
+    vk_stats *stats_out) {
+    return guarded([&]() -> int { return radiance_host(scene, params, points, n_points, nullptr, rgb_out, nullptr, stats_out, true); });
+}
+
+// test hook (vecchio_amd_debug.h): every sample of the query and, where asked for, the direction drawn for it
+int vk_debug_trace_irradiance_samples(vk_scene *scene, const vk_radiance_params *params, const vk_ray *points, uint64_t n_points,
+    float *samples_out, float *dirs_out, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        if (n_points != 0u && !samples_out) return fail(VK_ERR_BAD_ARG, "null samples buffer");
+        return radiance_host(scene, params, points, n_points, nullptr, nullptr, samples_out, stats_out, true, dirs_out);
     });
 }
 

@@ -1725,6 +1725,8 @@ struct RadianceArgs {
     float accum_clamp;
     uint64_t first_index;
     uint32_t n_rays, first_sample, n_chunks, shade_defer, prim_weight;
+    float4 *dirs;            // gather_kernel's per-sample hook: [n_rays * spp] (the drawn direction, 0) or null.  Last, so that every
+                             // other field keeps the offset radiance_kernel was built with
 };
 typedef const __attribute__((address_space(4))) RadianceArgs *RArgsC;
 __device__ __forceinline__ RArgsC rargs_fresh() {       // (see kargs_fresh)
@@ -1748,8 +1750,10 @@ __device__ __forceinline__ void flush_ray_sums(unsigned long long *sums, long lo
 }
 
 // the SHADE + REFILL phase (cf. shade_refill_body).  Leaves `fresh` lanes with a new ray parked in L.wo / L.wd / L.time; t0 / walk are
-// what its first segment starts with (radiance_start_core; +inf / true for a path that continues).
-template <uint32_t F>
+// what its first segment starts with (radiance_start_core; +inf / true for a path that continues).  GATHER (gather_kernel,
+// vk_trace_irradiance): the record read is a point — origin p, direction the normal n — and the ray is made here: the lane draws
+// irradiance_direction from the sample's stream, parks (p, d, time) and hands radiance_start_core the stream behind the draw.
+template <uint32_t F, bool GATHER = false>
 __device__ __forceinline__ void radiance_phase(Lane &L, bool is_shade, bool &active, bool &need, bool &fresh, bool &touched, float &t0,
                                                bool &walk, RArgsC P, float *cold, unsigned long long *sums, uint32_t *wstate, uint32_t lane) {
     RenderConsts C = RARG(P, C);
@@ -1836,8 +1840,14 @@ __device__ __forceinline__ void radiance_phase(Lane &L, bool is_shade, bool &act
                 } else {
                     g = radiance_rng(C.seed, RARG(P, first_index) + r, smp);
                 }
+                V3 dir = v3(r1.x, r1.y, r1.z);
+                if (GATHER) {
+                    dir = irradiance_direction(g, dir);
+                    float4 *dd = RARG(P, dirs);
+                    if (dd) dd[(size_t)r * C.spp + (smp - RARG(P, first_sample))] = make_float4(dir.x, dir.y, dir.z, 0.0f);
+                }
                 radiance_start_core(L, g, r0.w, t0, walk);
-                L.wo = v3(r0.x, r0.y, r0.z); L.wd = v3(r1.x, r1.y, r1.z); L.time = r1.w;
+                L.wo = v3(r0.x, r0.y, r0.z); L.wd = dir; L.time = r1.w;
                 fresh = true;
                 active = true;
                 need = false;
@@ -1849,9 +1859,9 @@ __device__ __forceinline__ void radiance_phase(Lane &L, bool is_shade, bool &act
     }
 }
 
-template <uint32_t F, int MINW>
-__global__ __launch_bounds__(RAD_BLOCK, MINW) void radiance_kernel(RadianceArgs A_byval) {
-    (void)A_byval;
+// the persistent loop of both query kernels (radiance_kernel, gather_kernel): they differ in the refill's ray-making step only
+template <uint32_t F, bool GATHER>
+__device__ __forceinline__ void path_query_waves() {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     using Mem = GlobalMem;
@@ -1947,7 +1957,7 @@ __global__ __launch_bounds__(RAD_BLOCK, MINW) void radiance_kernel(RadianceArgs 
             const bool is_shade = __builtin_amdgcn_inverse_ballot_w64(m_shade);
             bool touched = false, fresh = false, walk = true;
             float t0 = INFINITY;
-            radiance_phase<F>(L, is_shade, active, need, fresh, touched, t0, walk, rargs_fresh(), cold, sums, wstate, lane);
+            radiance_phase<F, GATHER>(L, is_shade, active, need, fresh, touched, t0, walk, rargs_fresh(), cold, sums, wstate, lane);
             if (fresh) {
                 RArgsC P = rargs_fresh();
                 DScene S = RARG(P, S);
@@ -1962,6 +1972,21 @@ __global__ __launch_bounds__(RAD_BLOCK, MINW) void radiance_kernel(RadianceArgs 
         RArgsC P = rargs_fresh();
         flush_ray_sums(sums, RARG(P, accum), __builtin_amdgcn_readfirstlane(wstate[RS_BLOCK]), lane, RARG(P, n_rays));
     }
+}
+
+template <uint32_t F, int MINW>
+__global__ __launch_bounds__(RAD_BLOCK, MINW) void radiance_kernel(RadianceArgs A_byval) {
+    (void)A_byval;
+    path_query_waves<F, false>();
+}
+
+// ---- irradiance queries (vk_trace_irradiance): radiance_kernel around a refill that reads (point, normal) records and draws each
+// sample's cosine-weighted direction on the device (radiance_phase<F, true>).  No per-path state is added: the normal is read again at
+// every refill, as the ray is.  The arguments are radiance_kernel's (rays = the points, keys = null).
+template <uint32_t F, int MINW>
+__global__ __launch_bounds__(RAD_BLOCK, MINW) void gather_kernel(RadianceArgs A_byval) {
+    (void)A_byval;
+    path_query_waves<F, true>();
 }
 
 // ray mean = fixed-point sum / samples_per_ray (resolve_kernel's arithmetic)

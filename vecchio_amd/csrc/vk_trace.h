@@ -1729,5 +1729,22 @@ VK_HD V3 radiance_sample(Lane &L, const DScene &S, const Mem &M, const RenderCon
     return L.acc;
 }
 
+// ------------------------------------------------------------------ irradiance queries (vk_trace_irradiance, include/vecchio_amd.h)
+// CosinePDF::new(n).generate() (util.rs:126-130, 144-146) on the stream `g`: the direction shade_core draws for a Lambertian hit's cosine half.
+// Two gen_f32 draws; not normalised; a zero or non-finite normal gives NaN axes and a NaN direction.
+VK_HD V3 irradiance_direction(Rng &g, V3 n) {
+    Onb uvw = onb_from_w(n);
+    return onb_local(uvw, random_cosine_direction(g));
+}
+// one whole sample at the point p with the normal n inside the lane (the host emulator; cf. radiance_sample): the direction from the
+// sample's stream, then radiance_sample on the stream where the draw left it.  `d` returns the direction.
+template <uint32_t F, class Mem>
+VK_HD V3 irradiance_sample(Lane &L, const DScene &S, const Mem &M, const RenderConsts &C, V3 p, V3 n, float time, float tmax, const Rng &rng,
+                           V3 &d) {
+    Rng g = rng;
+    d = irradiance_direction(g, n);
+    return radiance_sample<F, Mem>(L, S, M, C, p, d, time, tmax, g);
+}
+
 }  // namespace vkd
 #endif

@@ -285,7 +285,7 @@ DEVICE_SYMBOLS = [
     "vk_render_aov", "vk_render_aov_device",
     "vk_guide_default_params", "vk_render_guides", "vk_render_guides_device",
     "vk_trace_rays", "vk_trace_rays_device", "vk_trace_occluded", "vk_trace_occluded_device",
-    "vk_trace_radiance",
+    "vk_trace_radiance", "vk_trace_irradiance",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -370,6 +370,8 @@ def _bind(lib):
     lib.vk_trace_occluded.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
     lib.vk_trace_radiance.restype = C.c_int
     lib.vk_trace_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_trace_irradiance.restype = C.c_int
+    lib.vk_trace_irradiance.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
     lib.vk_trace_occluded_device.restype = C.c_int
     lib.vk_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                              C.POINTER(Stats)]
@@ -407,6 +409,9 @@ def _bind(lib):
     lib.vk_debug_trace_radiance_samples.restype = C.c_int
     lib.vk_debug_trace_radiance_samples.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                     C.POINTER(Stats)]
+    lib.vk_debug_trace_irradiance_samples.restype = C.c_int
+    lib.vk_debug_trace_irradiance_samples.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(Stats)]
     lib.vk_debug_trace_occluded_device.restype = C.c_int
     lib.vk_debug_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_uint32, C.c_uint32]

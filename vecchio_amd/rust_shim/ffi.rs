@@ -170,6 +170,10 @@ extern "C" {
     // radiance queries (additive symbols of ABI 7): rgb_out[i] = the mean of samples_per_ray samples of ray_color(rays[i]), 3 floats per ray
     pub fn vk_trace_radiance(scene: *mut vk_scene, params: *const vk_radiance_params, rays: *const vk_ray, n_rays: u64, rgb_out: *mut f32,
                              stats_out: *mut vk_stats) -> c_int;
+    // irradiance queries (additive symbols of ABI 7): a point is a vk_ray whose origin is the position and whose direction is the surface
+    // normal; rgb_out[i] = the mean radiance over samples_per_ray cosine-weighted directions drawn on the device (irradiance = pi * that)
+    pub fn vk_trace_irradiance(scene: *mut vk_scene, params: *const vk_radiance_params, points: *const vk_ray, n_points: u64,
+                               rgb_out: *mut f32, stats_out: *mut vk_stats) -> c_int;
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

@@ -84,6 +84,22 @@ def make_rays(origin, direction, time=0.0, tmax=np.inf):
     return rays
 
 
+def make_points(p, normal, time=0.0, tmax=np.inf):
+    """Points for DeviceScene.trace_irradiance(): a RAY_DTYPE array whose origin is the position and whose direction is the surface
+    normal (of any non-zero length), from positions and normals (n, 3) and per-point or scalar times and tmax."""
+    return make_rays(p, normal, time, tmax)
+
+
+def points_from_hits(hits, time=0.0):
+    """Points for DeviceScene.trace_irradiance() from trace_rays()' HIT_DTYPE records: the hit point with the normal that faces the ray
+    that found it (vk_hit.normal is face-oriented already).  Misses and hits inside a medium (whose normal is arbitrary) are skipped;
+    returns (points, index) with index[k] the record points[k] came from.  time: scalar, or one value per record."""
+    hits = np.asarray(hits).reshape(-1)
+    index = np.flatnonzero((hits["hit"] == 1) & (hits["medium"] == 0))
+    time = np.broadcast_to(np.asarray(time, np.float32), hits.shape)[index]
+    return make_points(hits["p"][index], hits["normal"][index], time), index
+
+
 def check(lib, status):
     if status != ffi.VK_OK:
         raise RuntimeError(f"vecchio_amd status {status}: {lib.vk_last_error().decode()}")
@@ -267,6 +283,39 @@ class DeviceScene:
                                                                    C.c_void_p(keys.ctypes.data if keys is not None and n else None),
                                                                    C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
         return (out, stats) if return_stats else out
+
+    def trace_irradiance(self, points, seed=0, first_index=0, samples_per_ray=1, first_sample=0, max_depth=50,
+                         integrator=ffi.VK_INTEGRATOR_PDF, background=ffi.VK_BACKGROUND_SOLID, background_color=(0.0, 0.0, 0.0), out=None,
+                         return_stats=False):
+        """Cosine-weighted mean radiance arriving at caller-supplied surface points (vk_trace_irradiance): an (n, 3) float32 array,
+        out[i] the mean of samples first_sample .. first_sample + samples_per_ray - 1 of points[i], each a direction drawn on the device
+        around the point's normal and ray_color along it on the same stream.  Irradiance is pi * out; a Lambertian texel of albedo a
+        radiates a * out.  points: make_points() / points_from_hits() (host memory; the call has no device-pointer variant yet)."""
+        rp = self.radiance_params(seed, first_index, samples_per_ray, first_sample, max_depth, integrator, background, background_color)
+        stats = ffi.Stats()
+        points = self._host_rays(points)
+        n = points.shape[0]
+        if out is None:
+            out = np.zeros((n, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (n, 3)
+        check(self._lib, self._lib.vk_trace_irradiance(self._h, C.byref(rp), C.c_void_p(points.ctypes.data if n else None), n,
+                                                       C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
+        return (out, stats) if return_stats else out
+
+    def debug_irradiance_samples(self, points, return_stats=False, **params):
+        """Every sample of trace_irradiance() (vk_debug_trace_irradiance_samples, a test hook): (samples, dirs), both
+        (n, samples_per_ray, 4) float32 — samples[..., :3] the radiance before the finite filter, samples[..., 3] the stream's final
+        counter (bit pattern), dirs[..., :3] the direction drawn for the sample.  params: radiance_params()'s keywords."""
+        rp = self.radiance_params(**params)
+        stats = ffi.Stats()
+        points = self._host_rays(points)
+        n = points.shape[0]
+        samples = np.zeros((n, rp.samples_per_ray, 4), np.float32)
+        dirs = np.zeros((n, rp.samples_per_ray, 4), np.float32)
+        check(self._lib, self._lib.vk_debug_trace_irradiance_samples(self._h, C.byref(rp), C.c_void_p(points.ctypes.data if n else None), n,
+                                                                     C.c_void_p(samples.ctypes.data if n else None),
+                                                                     C.c_void_p(dirs.ctypes.data if n else None), C.byref(stats)))
+        return (samples, dirs, stats) if return_stats else (samples, dirs)
 
     GUIDE_CHANNELS = AOV_CHANNELS + ("bounces",)
 
