@@ -3,15 +3,7 @@
 // * 4 + 0..2] = the radiance of sample first_sample + k of points[i] before the finite filter, [+3] = the stream's final counter;
 // dirs[(i * samples_per_ray + k) * 4 + 0..2] = the direction drawn for it, [+3] = 0.  max_depth = 0: nothing is drawn, both are zeros.
 // Built into tests/emu's library only.
-#include <cmath>
-#include <cstring>
-#include <string>
-
-#include "../../include/vecchio_amd_debug.h"
-#include "../../vecchio_amd/csrc/vk_linearize.h"
-#include "../../vecchio_amd/csrc/vk_trace.h"
-
-using namespace vkd;
+#include "emu_query.h"
 
 static thread_local std::string g_irr_err;
 
@@ -47,30 +39,12 @@ const char *emu_irradiance_last_error() { return g_irr_err.c_str(); }
 int emu_irradiance(const vk_scene_desc *desc, const vk_radiance_params *rp, const vk_ray *points, uint64_t n, float *samples, float *dirs,
     uint32_t *features_out) {
     if (!rp || (n != 0u && (!points || !samples))) { g_irr_err = "null params, points or samples"; return VK_ERR_BAD_ARG; }
-    LinearScene LS;
-    LinearizeOptions opt;
-    opt.retree = (desc && (desc->flags & VK_SCENE_FAST_ACCEL)) ? 1 : 0;
-    int st = linearize(desc, LS, g_irr_err, opt);
-    if (st != VK_OK) return st;
-    DScene S = LS.host_view();
-    if (!is_plain_tree_view(S)) {
-        g_irr_err = "the tree view came with a rebuilt form's gates"; return VK_ERR_BAD_ARG; }
-    const GlobalMem M{S.items, S.spheres, S.sphere_mat, S.boxes};
-    RenderConsts C;
-    memset(&C, 0, sizeof(C));
-    C.spp = rp->samples_per_ray; C.max_depth = rp->max_depth; C.seed = rp->seed;
-    C.integrator = rp->integrator; C.background = rp->background;
-    C.bg[0] = rp->background_color[0]; C.bg[1] = rp->background_color[1]; C.bg[2] = rp->background_color[2];
-    if (features_out) *features_out = LS.features;
-    const bool pdf = rp->integrator == VK_INTEGRATOR_PDF;
-    if (LS.features == 0u) {
-        if (pdf) irradiance_run<(uint32_t)VKF_INTEG_PDF>(S, M, C, rp, points, n, samples, dirs);
-        else irradiance_run<0u>(S, M, C, rp, points, n, samples, dirs);
-    } else {
-        if (pdf) irradiance_run<(uint32_t)(VKF_ALL_SCENE | VKF_INTEG_PDF)>(S, M, C, rp, points, n, samples, dirs);
-        else irradiance_run<(uint32_t)VKF_ALL_SCENE>(S, M, C, rp, points, n, samples, dirs);
-    }
-    return VK_OK;
+    return with_query_scene(desc, g_irr_err, [&](const LinearScene &LS, const DScene &S, const GlobalMem &M) {
+        if (features_out) *features_out = LS.features;
+        with_radiance_features(LS.features, rp, [&](auto f) {
+            irradiance_run<decltype(f)::value>(S, M, radiance_consts(rp), rp, points, n, samples, dirs);
+        });
+    });
 }
 
 }  // extern "C"

@@ -1,14 +1,7 @@
 // emu_occlusion.cpp — TEST TOOL: occlusion queries (vk_trace_occluded) on the host: vk_trace.h occluded_ray over a batch, on the tree view,
 // with the lineariser and the choice of F exactly as emu_rays.cpp has them.  occluded[i] answers rays[i], which is ray first_index + i
 // of the caller's batch.  Built into tests/emu's library only.
-#include <cmath>
-#include <cstring>
-#include <string>
-
-#include "../../vecchio_amd/csrc/vk_linearize.h"
-#include "../../vecchio_amd/csrc/vk_trace.h"
-
-using namespace vkd;
+#include "emu_query.h"
 
 static thread_local std::string g_occ_err;
 
@@ -31,19 +24,10 @@ const char *emu_occlusion_last_error() { return g_occ_err.c_str(); }
 int emu_occlusion(const vk_scene_desc *desc, uint64_t seed, uint64_t first_index, const vk_ray *rays, uint64_t n, uint8_t *occluded,
     uint32_t *features_out) {
     if (n != 0u && (!rays || !occluded)) { g_occ_err = "null rays or occluded"; return VK_ERR_BAD_ARG; }
-    LinearScene LS;
-    LinearizeOptions opt;
-    opt.retree = (desc && (desc->flags & VK_SCENE_FAST_ACCEL)) ? 1 : 0;
-    int st = linearize(desc, LS, g_occ_err, opt);
-    if (st != VK_OK) return st;
-    DScene S = LS.host_view();
-    if (!is_plain_tree_view(S)) {
-        g_occ_err = "the tree view came with a rebuilt form's gates"; return VK_ERR_BAD_ARG; }
-    const GlobalMem M{S.items, S.spheres, S.sphere_mat, S.boxes};
-    if (features_out) *features_out = LS.features;
-    if (LS.features == 0u) occlusion_run<0u>(S, M, seed, first_index, rays, n, occluded);
-    else occlusion_run<(uint32_t)VKF_ALL_SCENE>(S, M, seed, first_index, rays, n, occluded);
-    return VK_OK;
+    return with_query_scene(desc, g_occ_err, [&](const LinearScene &LS, const DScene &S, const GlobalMem &M) {
+        if (features_out) *features_out = LS.features;
+        with_features(LS.features, [&](auto f) { occlusion_run<decltype(f)::value>(S, M, seed, first_index, rays, n, occluded); });
+    });
 }
 
 }  // extern "C"

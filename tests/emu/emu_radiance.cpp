@@ -2,15 +2,7 @@
 // aov_view promises (the tree as handed over; under VK_SCENE_FAST_ACCEL the rebuilt tree with its tie table), F chosen as the launcher
 // chooses it.  samples[(i * samples_per_ray + k) * 4 + 0..2] = the radiance of sample first_sample + k of rays[i] before the finite
 // filter, [+3] = the stream's final counter; keys as vk_debug_trace_radiance_samples takes them.  Built into tests/emu's library only.
-#include <cmath>
-#include <cstring>
-#include <string>
-
-#include "../../include/vecchio_amd_debug.h"
-#include "../../vecchio_amd/csrc/vk_linearize.h"
-#include "../../vecchio_amd/csrc/vk_trace.h"
-
-using namespace vkd;
+#include "emu_query.h"
 
 static thread_local std::string g_rad_err;
 
@@ -44,30 +36,12 @@ const char *emu_radiance_last_error() { return g_rad_err.c_str(); }
 int emu_radiance(const vk_scene_desc *desc, const vk_radiance_params *rp, const vk_ray *rays, uint64_t n, const vk_debug_stream_key *keys,
     float *samples, uint32_t *features_out) {
     if (!rp || (n != 0u && (!rays || !samples))) { g_rad_err = "null params, rays or samples"; return VK_ERR_BAD_ARG; }
-    LinearScene LS;
-    LinearizeOptions opt;
-    opt.retree = (desc && (desc->flags & VK_SCENE_FAST_ACCEL)) ? 1 : 0;
-    int st = linearize(desc, LS, g_rad_err, opt);
-    if (st != VK_OK) return st;
-    DScene S = LS.host_view();
-    if (!is_plain_tree_view(S)) {
-        g_rad_err = "the tree view came with a rebuilt form's gates"; return VK_ERR_BAD_ARG; }
-    const GlobalMem M{S.items, S.spheres, S.sphere_mat, S.boxes};
-    RenderConsts C;
-    memset(&C, 0, sizeof(C));
-    C.spp = rp->samples_per_ray; C.max_depth = rp->max_depth; C.seed = rp->seed;
-    C.integrator = rp->integrator; C.background = rp->background;
-    C.bg[0] = rp->background_color[0]; C.bg[1] = rp->background_color[1]; C.bg[2] = rp->background_color[2];
-    if (features_out) *features_out = LS.features;
-    const bool pdf = rp->integrator == VK_INTEGRATOR_PDF;
-    if (LS.features == 0u) {
-        if (pdf) radiance_run<(uint32_t)VKF_INTEG_PDF>(S, M, C, rp, rays, n, keys, samples);
-        else radiance_run<0u>(S, M, C, rp, rays, n, keys, samples);
-    } else {
-        if (pdf) radiance_run<(uint32_t)(VKF_ALL_SCENE | VKF_INTEG_PDF)>(S, M, C, rp, rays, n, keys, samples);
-        else radiance_run<(uint32_t)VKF_ALL_SCENE>(S, M, C, rp, rays, n, keys, samples);
-    }
-    return VK_OK;
+    return with_query_scene(desc, g_rad_err, [&](const LinearScene &LS, const DScene &S, const GlobalMem &M) {
+        if (features_out) *features_out = LS.features;
+        with_radiance_features(LS.features, rp, [&](auto f) {
+            radiance_run<decltype(f)::value>(S, M, radiance_consts(rp), rp, rays, n, keys, samples);
+        });
+    });
 }
 
 }  // extern "C"

@@ -2,14 +2,7 @@
 // (the tree as handed over; under VK_SCENE_FAST_ACCEL the rebuilt tree with its tie table), F chosen as the launcher chooses it, the
 // provenance tables the lineariser filled.  hits[i] answers rays[i], which is ray first_index + i of the caller's batch.  Built into
 // tests/emu's library only.
-#include <cmath>
-#include <cstring>
-#include <string>
-
-#include "../../vecchio_amd/csrc/vk_linearize.h"
-#include "../../vecchio_amd/csrc/vk_trace.h"
-
-using namespace vkd;
+#include "emu_query.h"
 
 static thread_local std::string g_rays_err;
 
@@ -36,20 +29,11 @@ const char *emu_rays_last_error() { return g_rays_err.c_str(); }
 int emu_rays(const vk_scene_desc *desc, uint64_t seed, uint64_t first_index, const vk_ray *rays, uint64_t n, vk_hit *hits,
     uint32_t *features_out) {
     if (n != 0u && (!rays || !hits)) { g_rays_err = "null rays or hits"; return VK_ERR_BAD_ARG; }
-    LinearScene LS;
-    LinearizeOptions opt;
-    opt.retree = (desc && (desc->flags & VK_SCENE_FAST_ACCEL)) ? 1 : 0;
-    int st = linearize(desc, LS, g_rays_err, opt);
-    if (st != VK_OK) return st;
-    DScene S = LS.host_view();
-    if (!is_plain_tree_view(S)) {
-        g_rays_err = "the tree view came with a rebuilt form's gates"; return VK_ERR_BAD_ARG; }
-    const GlobalMem M{S.items, S.spheres, S.sphere_mat, S.boxes};
-    const DProvenance P = LS.host_provenance();
-    if (features_out) *features_out = LS.features;
-    if (LS.features == 0u) rays_run<0u>(S, M, P, seed, first_index, rays, n, hits);
-    else rays_run<(uint32_t)VKF_ALL_SCENE>(S, M, P, seed, first_index, rays, n, hits);
-    return VK_OK;
+    return with_query_scene(desc, g_rays_err, [&](const LinearScene &LS, const DScene &S, const GlobalMem &M) {
+        const DProvenance P = LS.host_provenance();
+        if (features_out) *features_out = LS.features;
+        with_features(LS.features, [&](auto f) { rays_run<decltype(f)::value>(S, M, P, seed, first_index, rays, n, hits); });
+    });
 }
 
 }  // extern "C"

@@ -147,6 +147,15 @@ def test_the_host_call_works_in_chunks(device, host_scenes):
         tail = ds.trace_irradiance(pts[-64:], **dict(kw, first_index=2 ** 40 + n - 64))
         np.testing.assert_array_equal(bits(got[-64:]), bits(tail))
         assert (got[:4096] != got[4096:8192]).any()       # the same point at another index draws from another stream
+        # the per-sample hook stages 2^22 samples at a time: at 2^21 samples per point three points are two launches (2 + 1), and each
+        # point's samples and directions are what a call for that point alone returns
+        kw = kwargs(hs, first_index=2 ** 40, max_depth=2, samples_per_ray=1 << 21)
+        samples, dirs, st = ds.debug_irradiance_samples(pts[:3], return_stats=True, **kw)
+        assert st.kernel_launches == 2 and st.samples == 3 << 21
+        for i in range(3):
+            s1, d1 = ds.debug_irradiance_samples(pts[i:i + 1], **dict(kw, first_index=2 ** 40 + i))
+            np.testing.assert_array_equal(bits(samples[i]), bits(s1[0]), err_msg=f"point {i}")
+            np.testing.assert_array_equal(bits(dirs[i]), bits(d1[0]), err_msg=f"point {i}")
     finally:
         ds.close()
 

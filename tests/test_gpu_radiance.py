@@ -250,6 +250,18 @@ def test_the_host_call_works_in_chunks(device, host_scenes):
         tail = ds.trace_radiance(rays[-64:], **dict(kw, first_index=2 ** 40 + n - 64))
         np.testing.assert_array_equal(bits(got[-64:]), bits(tail))
         assert (got[:4096] != got[4096:8192]).any()       # the same ray at another index draws from another stream
+        # the per-sample hook stages 2^22 samples at a time: at 2^21 samples per ray three rays are two launches (2 + 1), and each ray's
+        # samples — on its own key's stream, or by the public rule at its own index — are what a call for that ray alone returns
+        from vecchio_amd.scene import KEY_DTYPE
+        keys = np.zeros(3, KEY_DTYPE)
+        keys["seed"], keys["pixel"], keys["sample"], keys["ctr"] = 5, (11, 22, 33), (1, 2, 3), (0, 4, 8)
+        kw = kwargs(hs, first_index=2 ** 40, max_depth=2, samples_per_ray=1 << 21)
+        for k in (keys, None):
+            got, st = ds.debug_radiance_samples(rays[:3], k, return_stats=True, **kw)
+            assert st.kernel_launches == 2 and st.samples == 3 << 21
+            for i in range(3):
+                one = ds.debug_radiance_samples(rays[i:i + 1], None if k is None else k[i:i + 1], **dict(kw, first_index=2 ** 40 + i))
+                np.testing.assert_array_equal(bits(got[i]), bits(one[0]), err_msg=f"ray {i}")
     finally:
         ds.close()
 

@@ -198,7 +198,9 @@ def build_emu(force=False):
     srcs = [os.path.join(edir, "emu.cpp"), os.path.join(edir, "emu_guides.cpp"), os.path.join(edir, "emu_rays.cpp"),
             os.path.join(edir, "emu_occlusion.cpp"), os.path.join(edir, "emu_radiance.cpp"),
             os.path.join(edir, "emu_irradiance.cpp"), os.path.join(CSRC, "vk_linearize.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h")] + \
+    # (the tool's own headers: whichever are there)
+    deps = srcs + sorted(os.path.join(edir, f) for f in os.listdir(edir) if f.endswith(".h")) + \
+        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
     if force or _newer(out, deps, CXXFLAGS):
         os.makedirs(os.path.dirname(out), exist_ok=True)

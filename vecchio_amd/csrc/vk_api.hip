@@ -44,6 +44,7 @@
 #include <memory>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vecchio_amd.h"
@@ -328,13 +329,36 @@ int upload(vk_scene *s, const std::vector<T> &v, const T *&dptr) {
     return VK_OK;
 }
 
+constexpr uint32_t F_CORNELL = VKF_RECT | VKF_LIST | VKF_INSTANCE | VKF_BOX;
+
 uint32_t pick_variant(const vk_scene *s) {
     const uint32_t features = s->host->features;
-    const uint32_t F_CORNELL = VKF_RECT | VKF_LIST | VKF_INSTANCE | VKF_BOX;
     if (s->env.force_full_variant) return VKF_ALL_SCENE;   // diagnostics: cost of the general kernel
     if (features == 0) return 0u;
     if ((features & ~F_CORNELL) == 0) return F_CORNELL;
     return VKF_ALL_SCENE;
+}
+
+// ---- the two choices of a kernel instance, each made in ONE place.  fn is a generic callable; it is handed the chosen feature set as a
+// std::integral_constant<uint32_t, F> and what it returns is returned.
+// The six variants of the path-tracing kernels (render_kernel, radiance_kernel, gather_kernel): F = pick_variant() | the integrator's bit.
+template <class Fn>
+auto with_variant(uint32_t F, Fn &&fn) {
+    switch (F) {
+        case 0u: return fn(std::integral_constant<uint32_t, 0u>{});
+        case VKF_INTEG_PDF: return fn(std::integral_constant<uint32_t, (uint32_t)VKF_INTEG_PDF>{});
+        case F_CORNELL: return fn(std::integral_constant<uint32_t, F_CORNELL>{});
+        case F_CORNELL | VKF_INTEG_PDF: return fn(std::integral_constant<uint32_t, (F_CORNELL | VKF_INTEG_PDF)>{});
+        case VKF_ALL_SCENE: return fn(std::integral_constant<uint32_t, (uint32_t)VKF_ALL_SCENE>{});
+        default: return fn(std::integral_constant<uint32_t, (uint32_t)(VKF_ALL_SCENE | VKF_INTEG_PDF)>{});
+    }
+}
+// The two instances of the single-walk kernels (first-hit buffers, guides, ray and occlusion queries): a sphere-only world takes the fused
+// sphere path (C2), anything else the everything-variant.
+template <class Fn>
+auto with_walk_variant(uint32_t scene_features, Fn &&fn) {
+    if (scene_features == 0u) return fn(std::integral_constant<uint32_t, 0u>{});
+    return fn(std::integral_constant<uint32_t, (uint32_t)VKF_ALL_SCENE>{});
 }
 
 size_t per_wave_lds_bytes(uint32_t F) {   // cold lane state of one wave + its tile's fixed-point sums (64 x 3 x 8 B) + its unit state
@@ -476,15 +500,17 @@ int launch_dual(vk_scene *s, const KArgs &A, size_t per_wave, hipStream_t st) {
 
 // cost = the probe build of the variant (per-tile times into A.tile_cost)
 int launch_by_features(vk_scene *s, uint32_t F, const KArgs &A, bool lds, dim3 grid, size_t shmem, hipStream_t st, bool cost) {
-    const uint32_t F_CORNELL = VKF_RECT | VKF_LIST | VKF_INSTANCE | VKF_BOX;
-    switch (F) {
-        case 0u: return launch_variant<0u>(s, A, lds, grid, shmem, st, cost);
-        case VKF_INTEG_PDF: return launch_variant<VKF_INTEG_PDF>(s, A, lds, grid, shmem, st, cost);
-        case F_CORNELL: return launch_variant<F_CORNELL>(s, A, lds, grid, shmem, st, cost);
-        case F_CORNELL | VKF_INTEG_PDF: return launch_variant<(F_CORNELL | VKF_INTEG_PDF)>(s, A, lds, grid, shmem, st, cost);
-        case VKF_ALL_SCENE: return launch_variant<VKF_ALL_SCENE>(s, A, lds, grid, shmem, st, cost);
-        default: return launch_variant<(VKF_ALL_SCENE | VKF_INTEG_PDF)>(s, A, lds, grid, shmem, st, cost);
-    }
+    return with_variant(F, [&](auto f) { return launch_variant<decltype(f)::value>(s, A, lds, grid, shmem, st, cost); });
+}
+
+// what vk_render and the radiance queries refuse of a scene under an integrator
+int check_integrator_for_scene(const LinearScene &H, uint32_t integrator) {
+    if (integrator == VK_INTEGRATOR_PDF && H.lights.empty())
+        return fail(VK_ERR_UNSUPPORTED, "PDF integrator with an empty lights list (Vec::random unwraps None, hittable.rs:431)");
+    if (integrator == VK_INTEGRATOR_SCATTER && (H.features & VKF_SPEC_DIFFUSE))
+        return fail(VK_ERR_UNSUPPORTED,
+            "SpecDiffuse has no Material::scatter (default impl unwraps a None specular ray, material.rs:21-28)");
+    return VK_OK;
 }
 
 // the checks of every call that takes a camera and render parameters (vk_render, vk_progress_create, vk_render_aov)
@@ -507,13 +533,7 @@ int check_call_args(vk_scene *scene, const vk_camera *cam, const vk_render_param
 int check_render_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p) {
     int rc = check_call_args(scene, cam, p);
     if (rc != VK_OK) return rc;
-    const LinearScene &H = *scene->host;
-    if (p->integrator == VK_INTEGRATOR_PDF && H.lights.empty())
-        return fail(VK_ERR_UNSUPPORTED, "PDF integrator with an empty lights list (Vec::random unwraps None, hittable.rs:431)");
-    if (p->integrator == VK_INTEGRATOR_SCATTER && (H.features & VKF_SPEC_DIFFUSE))
-        return fail(VK_ERR_UNSUPPORTED,
-            "SpecDiffuse has no Material::scatter (default impl unwraps a None specular ray, material.rs:21-28)");
-    return VK_OK;
+    return check_integrator_for_scene(*scene->host, p->integrator);
 }
 
 struct TileGeom {      // the tile partition of one call
@@ -1704,6 +1724,14 @@ namespace {
 // also what vk_render walks — such a scene has no copy of the tree as handed over on the device.
 DScene aov_view(const vk_scene *s) { return s->exact.on ? s->exact.ref_view : handed_over_view(s->dev); }
 
+// aov_view for a launcher: none of these kernels knows the rebuilt forms' gates.  what: the walk that asks, as the refusal names it.
+int query_view(const vk_scene *q, const char *what, DScene *S) {
+    *S = aov_view(q);
+    if (!is_plain_tree_view(*S))
+        return fail(VK_ERR_BAD_ARG, std::string("internal error: ") + what + " needs a tree view without the rebuilt forms' gates");
+    return VK_OK;
+}
+
 // n_bufs: 4 (vk_render_aov) or 5 (vk_render_guides: bounces too)
 int check_aov_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p, uint32_t first_sample, const void *const *bufs,
     int n_bufs) {
@@ -1727,9 +1755,8 @@ int enqueue_aov(vk_scene *q, const vk_camera *cam, const vk_render_params *p, ui
     const TileGeom g(p);
     AovArgs A;
     memset(&A, 0, sizeof(A));
-    A.S = aov_view(q);
-    if (!is_plain_tree_view(A.S))
-        return fail(VK_ERR_BAD_ARG, "internal error: the first-hit walk needs a tree view without the rebuilt forms' gates");
+    int rc = query_view(q, "the first-hit walk", &A.S);
+    if (rc != VK_OK) return rc;
     A.C.cam = *cam;
     A.C.width = p->width; A.C.height = p->height; A.C.spp = p->samples_per_pixel; A.C.max_depth = 0u;
     A.C.seed = p->seed; A.C.integrator = p->integrator; A.C.background = p->background;
@@ -1737,21 +1764,24 @@ int enqueue_aov(vk_scene *q, const vk_camera *cam, const vk_render_params *p, ui
     A.albedo = d[0]; A.normal = d[1]; A.depth = d[2]; A.coverage = d[3];
     A.first_sample = first_sample; A.tiles_x = g.tiles_x; A.tile_rank = g.rank; A.tile_world = g.world; A.n_local = g.n_local;
     if (timed) {
-        int rc = q->aov.ev0.create();
+        rc = q->aov.ev0.create();
         if (rc == VK_OK) rc = q->aov.ev1.create();
         if (rc != VK_OK) return rc;
         HIP_TRY(hipEventRecord(q->aov.ev0, st));
     }
     if (g.n_local != 0u) {
         const dim3 grid((g.n_local + AOV_BLOCK / 64 - 1) / (AOV_BLOCK / 64));
-        // a sphere-only world: the fused sphere path (C2); anything else: the everything-variant
         if (gp) {
             GuideArgs G;
             G.A = A; G.bounces = d_bounces; G.max_bounces = gp->max_bounces; G.fuzz_max = gp->fuzz_max;
-            if (q->host->features == 0u) hipLaunchKernelGGL(specular_guides_kernel<0u>, grid, dim3(AOV_BLOCK), 0, st, G);
-            else hipLaunchKernelGGL(specular_guides_kernel<(uint32_t)VKF_ALL_SCENE>, grid, dim3(AOV_BLOCK), 0, st, G);
-        } else if (q->host->features == 0u) hipLaunchKernelGGL(aov_kernel<0u>, grid, dim3(AOV_BLOCK), 0, st, A);
-        else hipLaunchKernelGGL(aov_kernel<(uint32_t)VKF_ALL_SCENE>, grid, dim3(AOV_BLOCK), 0, st, A);
+            with_walk_variant(q->host->features, [&](auto f) {
+                hipLaunchKernelGGL(specular_guides_kernel<decltype(f)::value>, grid, dim3(AOV_BLOCK), 0, st, G);
+            });
+        } else {
+            with_walk_variant(q->host->features, [&](auto f) {
+                hipLaunchKernelGGL(aov_kernel<decltype(f)::value>, grid, dim3(AOV_BLOCK), 0, st, A);
+            });
+        }
         HIP_TRY(hipGetLastError());
     }
     if (timed) HIP_TRY(hipEventRecord(q->aov.ev1, st));
@@ -1906,19 +1936,96 @@ int vk_render_guides_device(vk_scene *scene, const vk_camera *cam, const vk_rend
 
 }  // extern "C"
 
-// ---- ray queries (vk_trace_rays): trace_rays_kernel on the tree view of the first-hit buffers (aov_view), on the scene's device
-// (devices[0] of a multi-device scene), with events and a staging buffer of its own: nothing that describes vk_render's last frame is
-// read or written.
+// ---- ray-batch queries (vk_trace_rays, vk_trace_occluded, vk_trace_radiance, vk_trace_irradiance and their hooks): one kernel per
+// family on the tree view of the first-hit buffers (query_view), on the scene's device (devices[0] of a multi-device scene), with events
+// and a staging buffer of their own: nothing that describes vk_render's last frame is read or written.  What the families share is
+// here: the argument checks of a batch (check_batch_args) and the host-pointer calls' chunked loop (run_batch).  A family adds its
+// checks, its enqueue_* — device pointers and a stream, so that a device-pointer variant is a wrapper — and a BatchLayout.
 namespace {
 
-constexpr uint64_t RAY_CHUNK = 1ull << 20;      // rays staged at a time by the host variant (96 MiB of scratch)
+constexpr uint64_t RAY_CHUNK = 1ull << 20;      // rays staged at a time by the host variants (96 MiB of scratch for vk_trace_rays)
 
-int check_trace_args(vk_scene *scene, const vk_trace_params *tp, const void *rays, uint64_t n_rays, const void *hits) {
-    if (!scene || !tp) return fail(VK_ERR_BAD_ARG, "null argument (scene or trace parameters)");
-    if (tp->flags != 0u) return fail(VK_ERR_BAD_ARG, "trace flags must be 0");
-    if (n_rays > (1ull << 32)) return fail(VK_ERR_BAD_ARG, "n_rays exceeds 2^32");
-    if (n_rays != 0u && (!rays || !hits)) return fail(VK_ERR_BAD_ARG, "null rays or hits with n_rays > 0");
+// The checks every batch call makes first.  what: the family's nouns for its parameter block ("trace") and its output ("hits").
+struct BatchNouns { const char *params, *out; };
+int check_batch_args(const vk_scene *scene, const void *params, uint32_t flags, uint64_t n, const void *in, const void *out,
+    const BatchNouns &what) {
+    if (!scene || !params) return fail(VK_ERR_BAD_ARG, std::string("null argument (scene or ") + what.params + " parameters)");
+    if (flags != 0u) return fail(VK_ERR_BAD_ARG, std::string(what.params) + " flags must be 0");
+    if (n > (1ull << 32)) return fail(VK_ERR_BAD_ARG, "n_rays exceeds 2^32");
+    if (n != 0u && (!in || !out)) return fail(VK_ERR_BAD_ARG, std::string("null rays or ") + what.out + " with n_rays > 0");
     return VK_OK;
+}
+
+// One chunk's scratch in the scene's staging buffer: [head bytes][stream 0][stream 1]..., stream k holding `bytes` per ray for the `cap`
+// rays of a chunk (the buffer may be larger than a call needs: every stream starts behind THIS call's earlier ones).  A stream with
+// `in` is uploaded ahead of a chunk's launch, one with `out` downloaded behind it; one with neither is the kernels' own.
+struct BatchStream {
+    size_t bytes;
+    const void *in;
+    void *out;
+};
+struct BatchLayout {
+    size_t head = 0;               // bytes ahead of the streams, cleared by the family's enqueue
+    uint64_t cap = RAY_CHUNK;      // rays per chunk, at most
+    int n_streams = 0;
+    BatchStream stream[4] = {};
+    size_t clamped_at = 0;         // != 0: a u64 at this offset of the head, read back per chunk and summed into vk_stats.clamped_samples
+    uint64_t samples_per_ray = 1;  // vk_stats.samples = rays x this
+};
+
+// The host-pointer call of every family, its arguments checked and its device current: rays [0, n_rays) in chunks of L.cap through the
+// staging buffer, each chunk uploaded, enqueued on the null stream between the scene's two ray-query events — enqueue(first_index,
+// n, d_head, d_stream, stream) — waited for, timed and downloaded; then the stats.
+template <class Enqueue>
+int run_batch(vk_scene *q, BatchLayout L, uint64_t n_rays, uint64_t first_index, std::chrono::steady_clock::time_point t0,
+    vk_stats *stats_out, Enqueue &&enqueue) {
+    int rc;
+    const uint64_t cap = n_rays < L.cap ? n_rays : L.cap;
+    size_t per_ray = 0;
+    for (int k = 0; k < L.n_streams; k++) per_ray += L.stream[k].bytes;
+    if ((rc = q->rays.buf.ensure(L.head + (size_t)cap * per_ray)) != VK_OK) return rc;
+    if ((rc = q->rays.ev0.create()) != VK_OK || (rc = q->rays.ev1.create()) != VK_OK) return rc;
+    uint8_t *d_head = q->rays.buf, *d[4] = {nullptr, nullptr, nullptr, nullptr};
+    {
+        uint8_t *at = d_head + L.head;
+        for (int k = 0; k < L.n_streams; k++) { d[k] = at; at += (size_t)cap * L.stream[k].bytes; }
+    }
+    double ms_sum = 0.0;
+    uint64_t launches = 0, clamped = 0;
+    for (uint64_t at = 0; at < n_rays; at += cap) {
+        const uint64_t n = n_rays - at < cap ? n_rays - at : cap;
+        for (int k = 0; k < L.n_streams; k++) {
+            const BatchStream &s = L.stream[k];
+            if (s.in) HIP_TRY(hipMemcpy(d[k], static_cast<const uint8_t *>(s.in) + at * s.bytes, (size_t)n * s.bytes, hipMemcpyHostToDevice));
+        }
+        HIP_TRY(hipEventRecord(q->rays.ev0, nullptr));
+        if ((rc = enqueue(first_index + at, n, d_head, d, (hipStream_t) nullptr)) != VK_OK) return rc;
+        HIP_TRY(hipEventRecord(q->rays.ev1, nullptr));
+        HIP_TRY(hipEventSynchronize(q->rays.ev1));
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, q->rays.ev0, q->rays.ev1));
+        ms_sum += (double)ms; launches++;
+        for (int k = 0; k < L.n_streams; k++) {
+            const BatchStream &s = L.stream[k];
+            if (s.out) HIP_TRY(hipMemcpy(static_cast<uint8_t *>(s.out) + at * s.bytes, d[k], (size_t)n * s.bytes, hipMemcpyDeviceToHost));
+        }
+        if (L.clamped_at) {
+            unsigned long long c = 0;
+            HIP_TRY(hipMemcpy(&c, d_head + L.clamped_at, sizeof(c), hipMemcpyDeviceToHost));
+            clamped += c;
+        }
+    }
+    if (stats_out) {
+        stats_out->samples = n_rays * L.samples_per_ray; stats_out->kernel_ms = ms_sum; stats_out->kernel_launches = (uint32_t)launches;
+        stats_out->clamped_samples = clamped;
+        stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return VK_OK;
+}
+
+// ---- closest hits (vk_trace_rays): trace_rays_kernel; the staging buffer holds rays, then hits
+int check_trace_args(vk_scene *scene, const vk_trace_params *tp, const void *rays, uint64_t n_rays, const void *hits) {
+    return check_batch_args(scene, tp, tp ? tp->flags : 0u, n_rays, rays, hits, {"trace", "hits"});
 }
 
 // the provenance tables, on the device with the scene's first ray query (freed with the scene's other uploads)
@@ -1939,16 +2046,15 @@ int ensure_provenance(vk_scene *q) {
 int enqueue_trace(vk_scene *q, const vk_trace_params *tp, uint64_t first_index, const void *d_rays, uint64_t n, void *d_hits, hipStream_t st) {
     TraceArgs A;
     memset(&A, 0, sizeof(A));
-    A.S = aov_view(q);
-    if (!is_plain_tree_view(A.S))
-        return fail(VK_ERR_BAD_ARG, "internal error: a ray query needs a tree view without the rebuilt forms' gates");
+    int rc = query_view(q, "a ray query", &A.S);
+    if (rc != VK_OK) return rc;
     A.P = q->rays.prov;
     A.rays = static_cast<const float4 *>(d_rays); A.hits = static_cast<uint4 *>(d_hits);
     A.seed = tp->seed; A.first_index = first_index; A.n_rays = n;
     const dim3 grid((uint32_t)((n + AOV_BLOCK - 1) / AOV_BLOCK));
-    // as enqueue_aov chooses: a sphere-only world the fused sphere path, anything else the everything-variant
-    if (q->host->features == 0u) hipLaunchKernelGGL(trace_rays_kernel<0u>, grid, dim3(AOV_BLOCK), 0, st, A);
-    else hipLaunchKernelGGL(trace_rays_kernel<(uint32_t)VKF_ALL_SCENE>, grid, dim3(AOV_BLOCK), 0, st, A);
+    with_walk_variant(q->host->features, [&](auto f) {
+        hipLaunchKernelGGL(trace_rays_kernel<decltype(f)::value>, grid, dim3(AOV_BLOCK), 0, st, A);
+    });
     HIP_TRY(hipGetLastError());
     return VK_OK;
 }
@@ -1967,30 +2073,12 @@ int vk_trace_rays(vk_scene *scene, const vk_trace_params *params, const vk_ray *
         vk_scene *q = first_part(scene);
         HIP_TRY(hipSetDevice(q->device));
         if ((rc = ensure_provenance(q)) != VK_OK) return rc;
-        const uint64_t cap = n_rays < RAY_CHUNK ? n_rays : RAY_CHUNK;
-        if ((rc = q->rays.buf.ensure((size_t)cap * (sizeof(vk_ray) + sizeof(vk_hit)))) != VK_OK) return rc;
-        if ((rc = q->rays.ev0.create()) != VK_OK || (rc = q->rays.ev1.create()) != VK_OK) return rc;
-        // (the buffer may be larger than this call needs: the hits start behind THIS call's rays)
-        uint8_t *d_rays = q->rays.buf, *d_hits = d_rays + (size_t)cap * sizeof(vk_ray);
-        double ms_sum = 0.0;
-        uint64_t launches = 0;
-        for (uint64_t at = 0; at < n_rays; at += cap) {
-            const uint64_t n = n_rays - at < cap ? n_rays - at : cap;
-            HIP_TRY(hipMemcpy(d_rays, rays + at, (size_t)n * sizeof(vk_ray), hipMemcpyHostToDevice));
-            HIP_TRY(hipEventRecord(q->rays.ev0, nullptr));
-            if ((rc = enqueue_trace(q, params, params->first_index + at, d_rays, n, d_hits, nullptr)) != VK_OK) return rc;
-            HIP_TRY(hipEventRecord(q->rays.ev1, nullptr));
-            HIP_TRY(hipEventSynchronize(q->rays.ev1));
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, q->rays.ev0, q->rays.ev1));
-            ms_sum += (double)ms; launches++;
-            HIP_TRY(hipMemcpy(hits + at, d_hits, (size_t)n * sizeof(vk_hit), hipMemcpyDeviceToHost));
-        }
-        if (stats_out) {
-            stats_out->samples = n_rays; stats_out->kernel_ms = ms_sum; stats_out->kernel_launches = (uint32_t)launches;
-            stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
-        return VK_OK;
+        BatchLayout L;
+        L.n_streams = 2; L.stream[0] = {sizeof(vk_ray), rays, nullptr}; L.stream[1] = {sizeof(vk_hit), nullptr, hits};
+        return run_batch(q, L, n_rays, params->first_index, t0, stats_out,
+            [&](uint64_t first_index, uint64_t n, uint8_t *, uint8_t *const d[4], hipStream_t st) {
+                return enqueue_trace(q, params, first_index, d[0], n, d[1], st);
+            });
     });
 }
 
@@ -2013,16 +2101,12 @@ int vk_trace_rays_device(vk_scene *scene, const vk_trace_params *params, const v
 
 }  // extern "C"
 
-// ---- occlusion queries (vk_trace_occluded): occlusion_kernel on the ray queries' tree view, device, staging buffer and events — rays,
-// then one byte per ray behind them.  No provenance: the call names no object.
+// ---- occlusion queries (vk_trace_occluded): occlusion_kernel; the staging buffer holds rays, then one byte per ray.  No provenance: the
+// call names no object.
 namespace {
 
 int check_occlusion_args(vk_scene *scene, const vk_trace_params *tp, const void *rays, uint64_t n_rays, const void *occluded) {
-    if (!scene || !tp) return fail(VK_ERR_BAD_ARG, "null argument (scene or trace parameters)");
-    if (tp->flags != 0u) return fail(VK_ERR_BAD_ARG, "trace flags must be 0");
-    if (n_rays > (1ull << 32)) return fail(VK_ERR_BAD_ARG, "n_rays exceeds 2^32");
-    if (n_rays != 0u && (!rays || !occluded)) return fail(VK_ERR_BAD_ARG, "null rays or occluded with n_rays > 0");
-    return VK_OK;
+    return check_batch_args(scene, tp, tp ? tp->flags : 0u, n_rays, rays, occluded, {"trace", "occluded"});
 }
 
 template <bool REFILL>
@@ -2030,9 +2114,9 @@ void launch_occlusion(uint32_t features, const OcclusionArgs &A, hipStream_t st)
     // one ray per lane, or one block of 64 * k rays per wave
     const uint64_t per_group = REFILL ? 64ull * A.k * (AOV_BLOCK / 64) : (uint64_t)AOV_BLOCK;
     const dim3 grid((uint32_t)((A.n_rays + per_group - 1) / per_group));
-    // as enqueue_trace chooses
-    if (features == 0u) hipLaunchKernelGGL((occlusion_kernel<0u, REFILL>), grid, dim3(AOV_BLOCK), 0, st, A);
-    else hipLaunchKernelGGL((occlusion_kernel<(uint32_t)VKF_ALL_SCENE, REFILL>), grid, dim3(AOV_BLOCK), 0, st, A);
+    with_walk_variant(features, [&](auto f) {
+        hipLaunchKernelGGL((occlusion_kernel<decltype(f)::value, REFILL>), grid, dim3(AOV_BLOCK), 0, st, A);
+    });
 }
 
 // one launch for rays [0, n) of d_rays, whose first ray is ray `first_index` of the caller's batch
@@ -2040,9 +2124,8 @@ int enqueue_occlusion(vk_scene *q, const vk_trace_params *tp, uint64_t first_ind
     hipStream_t st, bool refill = OCC_PRODUCTION_REFILL, uint32_t k = OCC_K, uint32_t t = OCC_T) {
     OcclusionArgs A;
     memset(&A, 0, sizeof(A));
-    A.S = aov_view(q);
-    if (!is_plain_tree_view(A.S))
-        return fail(VK_ERR_BAD_ARG, "internal error: an occlusion query needs a tree view without the rebuilt forms' gates");
+    int rc = query_view(q, "an occlusion query", &A.S);
+    if (rc != VK_OK) return rc;
     A.rays = static_cast<const float4 *>(d_rays); A.occluded = static_cast<uint8_t *>(d_occluded);
     A.seed = tp->seed; A.first_index = first_index; A.n_rays = n;
     A.k = k; A.t = t;
@@ -2070,29 +2153,12 @@ int vk_trace_occluded(vk_scene *scene, const vk_trace_params *params, const vk_r
         const auto t0 = std::chrono::steady_clock::now();
         vk_scene *q = first_part(scene);
         HIP_TRY(hipSetDevice(q->device));
-        const uint64_t cap = n_rays < RAY_CHUNK ? n_rays : RAY_CHUNK;
-        if ((rc = q->rays.buf.ensure((size_t)cap * (sizeof(vk_ray) + 1u))) != VK_OK) return rc;
-        if ((rc = q->rays.ev0.create()) != VK_OK || (rc = q->rays.ev1.create()) != VK_OK) return rc;
-        uint8_t *d_rays = q->rays.buf, *d_occluded = d_rays + (size_t)cap * sizeof(vk_ray);
-        double ms_sum = 0.0;
-        uint64_t launches = 0;
-        for (uint64_t at = 0; at < n_rays; at += cap) {
-            const uint64_t n = n_rays - at < cap ? n_rays - at : cap;
-            HIP_TRY(hipMemcpy(d_rays, rays + at, (size_t)n * sizeof(vk_ray), hipMemcpyHostToDevice));
-            HIP_TRY(hipEventRecord(q->rays.ev0, nullptr));
-            if ((rc = enqueue_occlusion(q, params, params->first_index + at, d_rays, n, d_occluded, nullptr)) != VK_OK) return rc;
-            HIP_TRY(hipEventRecord(q->rays.ev1, nullptr));
-            HIP_TRY(hipEventSynchronize(q->rays.ev1));
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, q->rays.ev0, q->rays.ev1));
-            ms_sum += (double)ms; launches++;
-            HIP_TRY(hipMemcpy(occluded + at, d_occluded, (size_t)n, hipMemcpyDeviceToHost));
-        }
-        if (stats_out) {
-            stats_out->samples = n_rays; stats_out->kernel_ms = ms_sum; stats_out->kernel_launches = (uint32_t)launches;
-            stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
-        return VK_OK;
+        BatchLayout L;
+        L.n_streams = 2; L.stream[0] = {sizeof(vk_ray), rays, nullptr}; L.stream[1] = {1u, nullptr, occluded};
+        return run_batch(q, L, n_rays, params->first_index, t0, stats_out,
+            [&](uint64_t first_index, uint64_t n, uint8_t *, uint8_t *const d[4], hipStream_t st) {
+                return enqueue_occlusion(q, params, first_index, d[0], n, d[1], st);
+            });
     });
 }
 
@@ -2130,9 +2196,8 @@ int vk_debug_trace_occluded_device(vk_scene *scene, const vk_trace_params *param
 
 }  // extern "C"
 
-// ---- radiance queries (vk_trace_radiance): radiance_kernel on the ray queries' tree view, device, staging buffer and events.  The
-// scratch of one chunk: [unit counter, clamped count: 32 bytes][rays][fixed-point sums][means] — or, for the per-sample hook,
-// [32 bytes][rays][samples][keys].  enqueue_radiance takes device pointers and a stream, so that a device-pointer variant is a wrapper.
+// ---- radiance queries (vk_trace_radiance): radiance_kernel.  The scratch of one chunk: [unit counter, clamped count: 32 bytes][rays]
+// [fixed-point sums][means] — or, for the per-sample hook, [32 bytes][rays][samples][keys].
 // Irradiance queries (vk_trace_irradiance) are the same calls with `gather` set: gather_kernel instead of radiance_kernel, the rays read
 // as (point, normal) records, no keys, and in the hook's scratch the drawn directions where the keys would be.
 namespace {
@@ -2142,10 +2207,8 @@ constexpr size_t RAD_HEAD = 32;                  // bytes ahead of the rays: uni
 constexpr uint64_t RAD_HOOK_SAMPLES = 1ull << 22;    // samples per launch of the per-sample hook (64 MiB of them)
 
 int check_radiance_args(vk_scene *scene, const vk_radiance_params *rp, const void *rays, uint64_t n_rays, const void *out) {
-    if (!scene || !rp) return fail(VK_ERR_BAD_ARG, "null argument (scene or radiance parameters)");
-    if (rp->flags != 0u) return fail(VK_ERR_BAD_ARG, "radiance flags must be 0");
-    if (n_rays > (1ull << 32)) return fail(VK_ERR_BAD_ARG, "n_rays exceeds 2^32");
-    if (n_rays != 0u && (!rays || !out)) return fail(VK_ERR_BAD_ARG, "null rays or output with n_rays > 0");
+    int rc = check_batch_args(scene, rp, rp ? rp->flags : 0u, n_rays, rays, out, {"radiance", "output"});
+    if (rc != VK_OK) return rc;
     if (rp->samples_per_ray == 0u || rp->samples_per_ray > (1u << 26)) return fail(VK_ERR_BAD_ARG, "samples_per_ray must be in 1..2^26");
     if ((uint64_t)rp->first_sample + rp->samples_per_ray > 0xFFFFFFFFull) return fail(VK_ERR_BAD_ARG,
         "first_sample + samples_per_ray exceeds 2^32 - 1");
@@ -2168,11 +2231,6 @@ int launch_radiance(const RadianceArgs &A, dim3 grid, hipStream_t st) {
     return VK_OK;
 }
 
-template <uint32_t F>
-int launch_query(bool gather, const RadianceArgs &A, dim3 grid, hipStream_t st) {
-    return gather ? launch_radiance<F, true>(A, grid, st) : launch_radiance<F, false>(A, grid, st);
-}
-
 // one launch for rays [0, n) of d_rays, whose first ray is ray `first_index` of the caller's batch: means into d_rgb through d_accum, or
 // (d_samples != null) every sample into d_samples.  d_head: RAD_HEAD bytes (cleared here).  gather: d_rays holds points, gather_kernel
 // runs, and with d_samples every sample's direction goes to d_dirs where that is given.
@@ -2180,9 +2238,8 @@ int enqueue_radiance(vk_scene *q, const vk_radiance_params *rp, uint64_t first_i
     uint8_t *d_head, long long *d_accum, float *d_rgb, float *d_samples, hipStream_t st, bool gather = false, float *d_dirs = nullptr) {
     RadianceArgs A;
     memset(&A, 0, sizeof(A));
-    A.S = aov_view(q);
-    if (!is_plain_tree_view(A.S))
-        return fail(VK_ERR_BAD_ARG, "internal error: a radiance query needs a tree view without the rebuilt forms' gates");
+    int rc = query_view(q, "a radiance query", &A.S);
+    if (rc != VK_OK) return rc;
     A.C.spp = rp->samples_per_ray; A.C.max_depth = rp->max_depth; A.C.seed = rp->seed;
     A.C.integrator = rp->integrator; A.C.background = rp->background;
     A.C.bg[0] = rp->background_color[0]; A.C.bg[1] = rp->background_color[1]; A.C.bg[2] = rp->background_color[2];
@@ -2210,16 +2267,10 @@ int enqueue_radiance(vk_scene *q, const vk_radiance_params *rp, uint64_t first_i
     HIP_TRY(hipMemsetAsync(d_head, 0, RAD_HEAD, st));
     if (A.accum) HIP_TRY(hipMemsetAsync(d_accum, 0, (size_t)n * 3u * sizeof(long long), st));
     const uint32_t F = pick_variant(q) | (rp->integrator == VK_INTEGRATOR_PDF ? (uint32_t)VKF_INTEG_PDF : 0u);
-    const uint32_t F_CORNELL = VKF_RECT | VKF_LIST | VKF_INSTANCE | VKF_BOX;
-    int rc;
-    switch (F) {      // as launch_by_features chooses
-        case 0u: rc = launch_query<0u>(gather, A, grid, st); break;
-        case VKF_INTEG_PDF: rc = launch_query<VKF_INTEG_PDF>(gather, A, grid, st); break;
-        case F_CORNELL: rc = launch_query<F_CORNELL>(gather, A, grid, st); break;
-        case F_CORNELL | VKF_INTEG_PDF: rc = launch_query<(F_CORNELL | VKF_INTEG_PDF)>(gather, A, grid, st); break;
-        case VKF_ALL_SCENE: rc = launch_query<VKF_ALL_SCENE>(gather, A, grid, st); break;
-        default: rc = launch_query<(VKF_ALL_SCENE | VKF_INTEG_PDF)>(gather, A, grid, st); break;
-    }
+    rc = with_variant(F, [&](auto f) {
+        constexpr uint32_t FV = decltype(f)::value;
+        return gather ? launch_radiance<FV, true>(A, grid, st) : launch_radiance<FV, false>(A, grid, st);
+    });
     if (rc != VK_OK) return rc;
     if (A.accum) {
         const uint32_t nv = n * 3u;
@@ -2237,13 +2288,8 @@ int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *r
     if (rc != VK_OK) return rc;
     if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
     if (n_rays == 0u) return VK_OK;
-    {   // what vk_render refuses of a scene (check_render_args); the handle is read from here on
-        const LinearScene &H = *scene->host;
-        if (rp->integrator == VK_INTEGRATOR_PDF && H.lights.empty())
-            return fail(VK_ERR_UNSUPPORTED, "PDF integrator with an empty lights list (Vec::random unwraps None, hittable.rs:431)");
-        if (rp->integrator == VK_INTEGRATOR_SCATTER && (H.features & VKF_SPEC_DIFFUSE))
-            return fail(VK_ERR_UNSUPPORTED, "SpecDiffuse has no Material::scatter (default impl unwraps a None specular ray, material.rs:21-28)");
-    }
+    // (the handle is read from here on)
+    if ((rc = check_integrator_for_scene(*scene->host, rp->integrator)) != VK_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t spp = rp->samples_per_ray;
     if (rp->max_depth == 0u) {        // every sample is (0,0,0) (main.rs:126-128) and draws nothing
@@ -2262,46 +2308,27 @@ int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *r
     }
     vk_scene *q = first_part(scene);
     HIP_TRY(hipSetDevice(q->device));
-    uint64_t cap = n_rays < RAY_CHUNK ? n_rays : RAY_CHUNK;
-    if (samples_out) { const uint64_t c = RAD_HOOK_SAMPLES / spp ? RAD_HOOK_SAMPLES / spp : 1u; if (cap > c) cap = c; }
-    const size_t per_ray = samples_out ? sizeof(vk_ray) + (size_t)spp * 16u + (dirs_out ? (size_t)spp * 16u : sizeof(vk_debug_stream_key))
-                                       : sizeof(vk_ray) + 3u * sizeof(long long) + 3u * sizeof(float);
-    if ((rc = q->rays.buf.ensure(RAD_HEAD + (size_t)cap * per_ray)) != VK_OK) return rc;
-    if ((rc = q->rays.ev0.create()) != VK_OK || (rc = q->rays.ev1.create()) != VK_OK) return rc;
-    uint8_t *d_head = q->rays.buf, *d_rays = d_head + RAD_HEAD, *d_second = d_rays + (size_t)cap * sizeof(vk_ray);
-    // (means: sums, then means; hook: samples, then keys or directions)
-    uint8_t *d_third = d_second + (size_t)cap * (samples_out ? (size_t)spp * 16u : 3u * sizeof(long long));
-    double ms_sum = 0.0;
-    uint64_t launches = 0, clamped = 0;
-    for (uint64_t at = 0; at < n_rays; at += cap) {
-        const uint64_t n = n_rays - at < cap ? n_rays - at : cap;
-        HIP_TRY(hipMemcpy(d_rays, rays + at, (size_t)n * sizeof(vk_ray), hipMemcpyHostToDevice));
-        if (samples_out && keys) HIP_TRY(hipMemcpy(d_third, keys + at, (size_t)n * sizeof(vk_debug_stream_key), hipMemcpyHostToDevice));
-        HIP_TRY(hipEventRecord(q->rays.ev0, nullptr));
-        if (samples_out) rc = enqueue_radiance(q, rp, rp->first_index + at, d_rays, keys ? d_third : nullptr, (uint32_t)n, d_head, nullptr,
-                                               nullptr, reinterpret_cast<float *>(d_second), nullptr, gather,
-                                               dirs_out ? reinterpret_cast<float *>(d_third) : nullptr);
-        else rc = enqueue_radiance(q, rp, rp->first_index + at, d_rays, nullptr, (uint32_t)n, d_head, reinterpret_cast<long long *>(d_second),
-                                   reinterpret_cast<float *>(d_third), nullptr, nullptr, gather);
-        if (rc != VK_OK) return rc;
-        HIP_TRY(hipEventRecord(q->rays.ev1, nullptr));
-        HIP_TRY(hipEventSynchronize(q->rays.ev1));
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, q->rays.ev0, q->rays.ev1));
-        ms_sum += (double)ms; launches++;
-        if (samples_out) HIP_TRY(hipMemcpy(samples_out + at * spp * 4u, d_second, (size_t)n * spp * 16u, hipMemcpyDeviceToHost));
-        else HIP_TRY(hipMemcpy(rgb_out + at * 3u, d_third, (size_t)n * 3u * sizeof(float), hipMemcpyDeviceToHost));
-        if (samples_out && dirs_out) HIP_TRY(hipMemcpy(dirs_out + at * spp * 4u, d_third, (size_t)n * spp * 16u, hipMemcpyDeviceToHost));
-        unsigned long long c = 0;
-        HIP_TRY(hipMemcpy(&c, d_head + 8, sizeof(c), hipMemcpyDeviceToHost));
-        clamped += c;
+    BatchLayout L;
+    L.head = RAD_HEAD; L.clamped_at = 8; L.samples_per_ray = spp; L.n_streams = 3;
+    L.stream[0] = {sizeof(vk_ray), rays, nullptr};
+    if (samples_out) {      // the hook: samples, then keys (uploaded where given) or the directions
+        const uint64_t c = RAD_HOOK_SAMPLES / spp ? RAD_HOOK_SAMPLES / spp : 1u;
+        if (L.cap > c) L.cap = c;
+        L.stream[1] = {(size_t)spp * 16u, nullptr, samples_out};
+        if (dirs_out) L.stream[2] = {(size_t)spp * 16u, nullptr, dirs_out};
+        else L.stream[2] = {sizeof(vk_debug_stream_key), keys, nullptr};
+    } else {                // means: the fixed-point sums, then the means
+        L.stream[1] = {3u * sizeof(long long), nullptr, nullptr};
+        L.stream[2] = {3u * sizeof(float), nullptr, rgb_out};
     }
-    if (stats_out) {
-        stats_out->samples = n_rays * spp; stats_out->kernel_ms = ms_sum; stats_out->kernel_launches = (uint32_t)launches;
-        stats_out->clamped_samples = clamped;
-        stats_out->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    }
-    return VK_OK;
+    return run_batch(q, L, n_rays, rp->first_index, t0, stats_out,
+        [&](uint64_t first_index, uint64_t n, uint8_t *d_head, uint8_t *const d[4], hipStream_t st) {
+            if (samples_out) return enqueue_radiance(q, rp, first_index, d[0], keys ? d[2] : nullptr, (uint32_t)n, d_head, nullptr, nullptr,
+                                                     reinterpret_cast<float *>(d[1]), st, gather,
+                                                     dirs_out ? reinterpret_cast<float *>(d[2]) : nullptr);
+            return enqueue_radiance(q, rp, first_index, d[0], nullptr, (uint32_t)n, d_head, reinterpret_cast<long long *>(d[1]),
+                                    reinterpret_cast<float *>(d[2]), nullptr, st, gather);
+        });
 }
 
 }  // namespace

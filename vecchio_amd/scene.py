@@ -171,40 +171,20 @@ class DeviceScene:
         ray that views as one; returns a HIT_DTYPE array, hits[i] answering rays[i].  Device tensors (objects with data_ptr(): a
         (n, 8) float32 tensor of rays on this scene's device) go through vk_trace_rays_device on `stream` without a host wait and
         return an (n, 16) int32 tensor — view it as HIT_DTYPE after copying it to the host — or write into `out`."""
-        tp = ffi.TraceParams(seed & 0xFFFFFFFFFFFFFFFF, first_index, 0, 0)
-        stats = ffi.Stats()
-        if hasattr(rays, "data_ptr"):
-            import torch
-            if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8 != 0:
-                raise ValueError("device rays must be a contiguous float32 tensor of 8 floats per ray")
-            n = rays.numel() // 8
-            if out is None:
-                out = torch.empty((n, 16), dtype=torch.int32, device=rays.device)
-            if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != n * 16:
-                raise ValueError("device hits must be a contiguous int32 tensor of 16 words per ray")
-            check(self._lib, self._lib.vk_trace_rays_device(self._h, C.byref(tp), C.c_void_p(rays.data_ptr() if n else None), n,
-                                                            C.c_void_p(out.data_ptr() if n else None), C.c_void_p(stream or 0),
-                                                            C.byref(stats)))
-            return (out, stats) if return_stats else out
-        rays = np.ascontiguousarray(rays)
-        if rays.dtype != RAY_DTYPE:
-            if rays.nbytes % 32 != 0 or rays.dtype.itemsize not in (4, 32):
-                raise ValueError("rays must be a RAY_DTYPE array (or float32 data of 8 floats per ray)")
-            rays = rays.reshape(-1).view(RAY_DTYPE)
-        rays = rays.reshape(-1)
-        if out is None:
-            out = np.zeros(rays.shape[0], HIT_DTYPE)
-        assert out.dtype == HIT_DTYPE and out.flags.c_contiguous and out.shape == rays.shape
-        n = rays.shape[0]
-        check(self._lib, self._lib.vk_trace_rays(self._h, C.byref(tp), C.c_void_p(rays.ctypes.data if n else None), n,
-                                                 C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
-        return (out, stats) if return_stats else out
+        return self._trace_walk("vk_trace_rays", rays, seed, first_index, out, stream, return_stats, HIT_DTYPE, "int32", 16,
+                                "device hits must be a contiguous int32 tensor of 16 words per ray")
 
     def trace_occluded(self, rays, seed=0, first_index=0, out=None, stream=None, return_stats=False):
         """Is anything between tmin and tmax of each caller-supplied ray (vk_trace_occluded): a uint8 array, occluded[i] == the `hit`
         field trace_rays() returns for rays[i].  rays as for trace_rays(): a RAY_DTYPE array, or a device tensor ((n, 8) float32 on this
         scene's device), which goes through vk_trace_occluded_device on `stream` without a host wait and returns an (n,) uint8 tensor
         (or writes into `out`).  Visibility of the segment from a to b: origin a, direction b - a, tmax 1."""
+        return self._trace_walk("vk_trace_occluded", rays, seed, first_index, out, stream, return_stats, np.uint8, "uint8", 1,
+                                "device occlusion bytes must be a contiguous uint8 tensor of one byte per ray")
+
+    def _trace_walk(self, call, rays, seed, first_index, out, stream, return_stats, host_dtype, dev_dtype, dev_words, dev_out_error):
+        """trace_rays() / trace_occluded(): the host call `call` for a numpy batch (one host_dtype record per ray), `call`_device on
+        `stream` for a device tensor (dev_words elements of torch dtype dev_dtype per ray)"""
         tp = ffi.TraceParams(seed & 0xFFFFFFFFFFFFFFFF, first_index, 0, 0)
         stats = ffi.Stats()
         if hasattr(rays, "data_ptr"):
@@ -212,27 +192,28 @@ class DeviceScene:
             if rays.dtype != torch.float32 or not rays.is_contiguous() or rays.numel() % 8 != 0:
                 raise ValueError("device rays must be a contiguous float32 tensor of 8 floats per ray")
             n = rays.numel() // 8
+            dev_dtype = getattr(torch, dev_dtype)
             if out is None:
-                out = torch.empty((n,), dtype=torch.uint8, device=rays.device)
-            if out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != n:
-                raise ValueError("device occlusion bytes must be a contiguous uint8 tensor of one byte per ray")
-            check(self._lib, self._lib.vk_trace_occluded_device(self._h, C.byref(tp), C.c_void_p(rays.data_ptr() if n else None), n,
-                                                                C.c_void_p(out.data_ptr() if n else None), C.c_void_p(stream or 0),
-                                                                C.byref(stats)))
+                out = torch.empty((n, dev_words) if dev_words > 1 else (n,), dtype=dev_dtype, device=rays.device)
+            if out.dtype != dev_dtype or not out.is_contiguous() or out.numel() != n * dev_words:
+                raise ValueError(dev_out_error)
+            check(self._lib, getattr(self._lib, call + "_device")(self._h, C.byref(tp), C.c_void_p(rays.data_ptr() if n else None), n,
+                                                                  C.c_void_p(out.data_ptr() if n else None), C.c_void_p(stream or 0),
+                                                                  C.byref(stats)))
             return (out, stats) if return_stats else out
-        rays = np.ascontiguousarray(rays)
-        if rays.dtype != RAY_DTYPE:
-            if rays.nbytes % 32 != 0 or rays.dtype.itemsize not in (4, 32):
-                raise ValueError("rays must be a RAY_DTYPE array (or float32 data of 8 floats per ray)")
-            rays = rays.reshape(-1).view(RAY_DTYPE)
-        rays = rays.reshape(-1)
+        rays = self._host_rays(rays)
         if out is None:
-            out = np.zeros(rays.shape[0], np.uint8)
-        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.shape == rays.shape
-        n = rays.shape[0]
-        check(self._lib, self._lib.vk_trace_occluded(self._h, C.byref(tp), C.c_void_p(rays.ctypes.data if n else None), n,
-                                                     C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
+            out = np.zeros(rays.shape[0], host_dtype)
+        assert out.dtype == host_dtype and out.flags.c_contiguous and out.shape == rays.shape
+        self._host_batch(call, tp, stats, rays, out)
         return (out, stats) if return_stats else out
+
+    def _host_batch(self, call, params, stats, rays, *arrays):
+        """the host-pointer call `call` for the n rays of `rays` with the further per-ray arrays (None = a null pointer); with n == 0
+        every pointer is null"""
+        n = rays.shape[0]
+        ptrs = [C.c_void_p(a.ctypes.data if a is not None and n else None) for a in (rays,) + arrays]
+        check(self._lib, getattr(self._lib, call)(self._h, C.byref(params), ptrs[0], n, *ptrs[1:], C.byref(stats)))
 
     @staticmethod
     def _host_rays(rays):
@@ -263,8 +244,7 @@ class DeviceScene:
         if out is None:
             out = np.zeros((n, 3), np.float32)
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (n, 3)
-        check(self._lib, self._lib.vk_trace_radiance(self._h, C.byref(rp), C.c_void_p(rays.ctypes.data if n else None), n,
-                                                     C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
+        self._host_batch("vk_trace_radiance", rp, stats, rays, out)
         return (out, stats) if return_stats else out
 
     def debug_radiance_samples(self, rays, keys=None, return_stats=False, **params):
@@ -279,9 +259,7 @@ class DeviceScene:
             keys = np.ascontiguousarray(keys, KEY_DTYPE).reshape(-1)
             assert keys.shape[0] == n
         out = np.zeros((n, rp.samples_per_ray, 4), np.float32)
-        check(self._lib, self._lib.vk_debug_trace_radiance_samples(self._h, C.byref(rp), C.c_void_p(rays.ctypes.data if n else None), n,
-                                                                   C.c_void_p(keys.ctypes.data if keys is not None and n else None),
-                                                                   C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
+        self._host_batch("vk_debug_trace_radiance_samples", rp, stats, rays, keys, out)
         return (out, stats) if return_stats else out
 
     def trace_irradiance(self, points, seed=0, first_index=0, samples_per_ray=1, first_sample=0, max_depth=50,
@@ -298,8 +276,7 @@ class DeviceScene:
         if out is None:
             out = np.zeros((n, 3), np.float32)
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (n, 3)
-        check(self._lib, self._lib.vk_trace_irradiance(self._h, C.byref(rp), C.c_void_p(points.ctypes.data if n else None), n,
-                                                       C.c_void_p(out.ctypes.data if n else None), C.byref(stats)))
+        self._host_batch("vk_trace_irradiance", rp, stats, points, out)
         return (out, stats) if return_stats else out
 
     def debug_irradiance_samples(self, points, return_stats=False, **params):
@@ -312,9 +289,7 @@ class DeviceScene:
         n = points.shape[0]
         samples = np.zeros((n, rp.samples_per_ray, 4), np.float32)
         dirs = np.zeros((n, rp.samples_per_ray, 4), np.float32)
-        check(self._lib, self._lib.vk_debug_trace_irradiance_samples(self._h, C.byref(rp), C.c_void_p(points.ctypes.data if n else None), n,
-                                                                     C.c_void_p(samples.ctypes.data if n else None),
-                                                                     C.c_void_p(dirs.ctypes.data if n else None), C.byref(stats)))
+        self._host_batch("vk_debug_trace_irradiance_samples", rp, stats, points, samples, dirs)
         return (samples, dirs, stats) if return_stats else (samples, dirs)
 
     GUIDE_CHANNELS = AOV_CHANNELS + ("bounces",)
