@@ -744,6 +744,52 @@ int vk_trace_radiance(vk_scene *scene, const vk_radiance_params *params, const v
 int vk_trace_irradiance(vk_scene *scene, const vk_radiance_params *params, const vk_ray *points, uint64_t n_points,
                         float *rgb_out /* n_points * 3 */, vk_stats *stats_out);
 
+/* ---- probe queries: spherical-harmonic radiance at caller-supplied points (additive symbols of ABI 7) -------------------------------
+ * replaces: random_in_unit_sphere().unit_vector() (util.rs:31-39) followed by ray_color, for points the CALLER supplies that have no
+ * normal: a light probe of an irradiance volume, the lighting of a moving object.  sh_out holds, per probe, the mean over uniformly
+ * distributed directions of the incoming radiance times each of the nine real spherical-harmonic basis functions of bands 0..2, per
+ * colour channel: 27 floats, from which vk_probe_eval answers for ANY normal afterwards.  The directions are drawn on the device from
+ * each sample's own stream: the caller uploads 32 bytes per probe and downloads 108.
+ *   A probe is a vk_ray read as: origin = the position p; direction is NOT READ (any bytes, NaN included, give the same result);
+ *     time = the time of every ray from the probe; tmax cuts the first segment only, by vk_trace_radiance's rule: a tmax that is a NaN
+ *     or <= VK_RAY_TMIN misses without a walk, and the sample is the background along its direction.
+ *   Sample s of probe i, s in [first_sample, first_sample + samples_per_ray), everything f32 and unfused in the reference's order:
+ *     g = rng_for_sample(seed + 0x9E3779B97F4A7C15 * (first_index + i), 0, s), in wrapping u64, taken from its beginning;
+ *     b = random_in_unit_sphere(g) (util.rs:31-39: x, y, z = three gen_range(-1, 1) draws in this order, again while
+ *       (x*x + y*y) + z*z >= 1, so the stream's counter stands at 3 * tries);
+ *     u = b.unit_vector() = (b.x / l, b.y / l, b.z / l) with l = sqrtf((b.x*b.x + b.y*b.y) + b.z*b.z);
+ *     the sample is L = ray_color(&Ray{p, u, time}, depth 1) CONTINUING the stream g (ray_color_scatter for VK_INTEGRATOR_SCATTER), tmax
+ *     the closest-so-far distance of its first world.hit.  Everything behind that is vk_trace_radiance's rule word for word: the tree
+ *     view, VK_RAY_TMIN, media draws from the sample's stream.  max_depth = 0: every sample is (0,0,0) and nothing is drawn.
+ *   Basis.  With (x, y, z) = u, in f32 in exactly this form:
+ *     Y0 = 0.282095f              Y1 = 0.488603f*y            Y2 = 0.488603f*z
+ *     Y3 = 0.488603f*x            Y4 = 1.092548f*(x*y)        Y5 = 1.092548f*(y*z)
+ *     Y6 = 0.315392f*(3.0f*(z*z) - 1.0f)                      Y7 = 1.092548f*(x*z)        Y8 = 0.546274f*(x*x - y*y)
+ *   Aggregation.  The contribution of a sample to coefficient k, channel c is the f32 product Y_k * L_c.  A sample with a non-finite
+ *     component of L or of u adds to none of the 27 sums but counts in n = samples_per_ray (a zero b gets no special case: its NaN
+ *     direction drops the sample).  Sums are 64-bit fixed point with 2^-26 resolution: each product is clamped to
+ *     +-min(1e10, 1.3e11 / samples_per_ray), multiplied by 2^26 and truncated toward zero; a sample with at least one clamped product
+ *     counts once in stats_out->clamped_samples.  sh_out[(i * 9 + k) * 3 + c] = (float)sum * 2^-26 / (float)samples_per_ray, each step
+ *     in f32.  The result is ONE value per (scene, params, probe, index): it does not depend on the launch shape, on the order of the
+ *     probes, on how a batch is cut into pieces whose first_index continue each other, or on how the samples are split over launches
+ *     (the fixed-point sums of two sample windows add).
+ *   What the value is.  The plain mean of Y_k(u) * L(u) over the sphere's uniform density 1 / 4pi.  The spherical-harmonic coefficient
+ *     of the radiance is therefore 4pi * sh_out.  The library does not multiply by 4pi: the result stays the exact fixed-point mean, and
+ *     vk_probe_eval's weights contain the factor.
+ *   Arguments, VK_ERR_UNSUPPORTED, n_probes == 0, scene state, multi-device scenes, staging (at most 2^20 probes at a time through the
+ *     ray queries' scratch) and stats_out (samples = n_probes * samples_per_ray) are vk_trace_radiance's, with the same messages.
+ *   There is no device-pointer variant yet.                                                                                         */
+#define VK_PROBE_COEFFS 9u
+int vk_trace_probes(vk_scene *scene, const vk_radiance_params *params, const vk_ray *probes, uint64_t n_probes,
+                    float *sh_out /* n_probes * 9 * 3 */, vk_stats *stats_out);
+/* Evaluates a probe for the direction n (of any non-zero length; normalised here).  Touches no device and no handle.
+ *   rgb[c] = sum_k w_l(k) * sh27[k * 3 + c] * Y_k(unit(n)), l(k) the band of k (0; 1..3; 4..8), computed in double and rounded once.
+ *   mode 0: the radiance arriving along n, band-limited: w = 4pi for every k.
+ *   mode 1: irradiance / pi for a surface of normal n — the quantity vk_trace_irradiance's rgb_out estimates — by the cosine lobe's
+ *     band weights: w_0 = 4pi, w_1 = 8pi/3, w_2 = pi.
+ *   VK_ERR_BAD_ARG for a null pointer or another mode; rgb is then untouched.  A zero or non-finite n gives NaN.                    */
+int vk_probe_eval(const float *sh27, const float n[3], uint32_t mode, float rgb[3]);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

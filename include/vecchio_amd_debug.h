@@ -92,6 +92,13 @@ int vk_debug_trace_radiance_samples(vk_scene *scene, const vk_radiance_params *p
 int vk_debug_trace_irradiance_samples(vk_scene *scene, const vk_radiance_params *params, const vk_ray *points, uint64_t n_points,
                                       float *samples_out /* n * spp * 4 */, float *dirs_out /* n * spp * 4, may be NULL */,
                                       vk_stats *stats_out);
+/* as vk_trace_probes, returning every sample: samples_out[(i * samples_per_ray + k) * 4 + 0..2] = the radiance L before the finite
+ * filter, [+3] = the stream's counter at the sample's end (it includes the direction's 3 * tries draws) and, with dirs_out given,
+ * dirs_out[(i * samples_per_ray + k) * 4 + 0..2] = the unit direction u drawn for the sample, [+3] = 0.  There are no keys: the public
+ * stream rule is the only one.  max_depth = 0: both are zeros.  In both libraries. */
+int vk_debug_trace_probe_samples(vk_scene *scene, const vk_radiance_params *params, const vk_ray *probes, uint64_t n_probes,
+                                 float *samples_out /* n * spp * 4 */, float *dirs_out /* n * spp * 4, may be NULL */,
+                                 vk_stats *stats_out);
 
 #ifdef __cplusplus
 }

@@ -1936,7 +1936,7 @@ int vk_render_guides_device(vk_scene *scene, const vk_camera *cam, const vk_rend
 
 }  // extern "C"
 
-// ---- ray-batch queries (vk_trace_rays, vk_trace_occluded, vk_trace_radiance, vk_trace_irradiance and their hooks): one kernel per
+// ---- ray-batch queries (vk_trace_rays, vk_trace_occluded, vk_trace_radiance, vk_trace_irradiance, vk_trace_probes and their hooks): one kernel per
 // family on the tree view of the first-hit buffers (query_view), on the scene's device (devices[0] of a multi-device scene), with events
 // and a staging buffer of their own: nothing that describes vk_render's last frame is read or written.  What the families share is
 // here: the argument checks of a batch (check_batch_args) and the host-pointer calls' chunked loop (run_batch).  A family adds its
@@ -2200,6 +2200,8 @@ int vk_debug_trace_occluded_device(vk_scene *scene, const vk_trace_params *param
 // [fixed-point sums][means] — or, for the per-sample hook, [32 bytes][rays][samples][keys].
 // Irradiance queries (vk_trace_irradiance) are the same calls with `gather` set: gather_kernel instead of radiance_kernel, the rays read
 // as (point, normal) records, no keys, and in the hook's scratch the drawn directions where the keys would be.
+// Probe queries (vk_trace_probes) are the same calls with mode QM_PROBE: probe_kernel, the rays read as probes (the direction not read),
+// 27 fixed-point sums and 27 means a probe instead of 3, and the hook's scratch as the irradiance hook's.
 namespace {
 
 static_assert(sizeof(RadianceKey) == sizeof(vk_debug_stream_key) && sizeof(RadianceKey) == 24, "vk_debug_stream_key is what the kernel reads");
@@ -2216,15 +2218,15 @@ int check_radiance_args(vk_scene *scene, const vk_radiance_params *rp, const voi
     return VK_OK;
 }
 
-template <uint32_t F, bool GATHER>
+template <uint32_t F, int MODE>
 int launch_radiance(const RadianceArgs &A, dim3 grid, hipStream_t st) {
     // Six waves per SIMD (80 VGPRs), as render_kernel's variants — except the everything-variants: render_kernel calls their SHADE + REFILL
     // phase out of line to hold them there (shade_refill_call); this kernel keeps its phase inline, where 80 registers cost them ~500
     // scratch instructions, so they are built for four (128 VGPRs)
     constexpr int MINW = (F & VKF_ALL_SCENE) == VKF_ALL_SCENE ? 4 : 6;
-    // (gather_kernel: the same rule; DESIGN.md "Irradiance queries" has its instances' numbers)
-    auto kernel = GATHER ? &gather_kernel<F, MINW> : &radiance_kernel<F, MINW>;
-    const size_t shmem = (size_t)(RAD_BLOCK / 64) * wave_block_floats<F>() * sizeof(float);
+    // (gather_kernel, probe_kernel: the same rule; DESIGN.md "Irradiance queries" and "Probe queries" have their instances' numbers)
+    auto kernel = MODE == QM_PROBE ? &probe_kernel<F, MINW> : (MODE == QM_GATHER ? &gather_kernel<F, MINW> : &radiance_kernel<F, MINW>);
+    const size_t shmem = (size_t)(RAD_BLOCK / 64) * query_block_floats<F, MODE>() * sizeof(float);
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     hipLaunchKernelGGL(kernel, grid, dim3(RAD_BLOCK), shmem, st, A);
     HIP_TRY(hipGetLastError());
@@ -2232,10 +2234,11 @@ int launch_radiance(const RadianceArgs &A, dim3 grid, hipStream_t st) {
 }
 
 // one launch for rays [0, n) of d_rays, whose first ray is ray `first_index` of the caller's batch: means into d_rgb through d_accum, or
-// (d_samples != null) every sample into d_samples.  d_head: RAD_HEAD bytes (cleared here).  gather: d_rays holds points, gather_kernel
-// runs, and with d_samples every sample's direction goes to d_dirs where that is given.
+// (d_samples != null) every sample into d_samples.  d_head: RAD_HEAD bytes (cleared here).  QM_GATHER: d_rays holds points, gather_kernel
+// runs, and with d_samples every sample's direction goes to d_dirs where that is given.  QM_PROBE: d_rays holds probes, probe_kernel
+// runs, d_accum and d_rgb hold 27 values a probe, d_dirs as for QM_GATHER.
 int enqueue_radiance(vk_scene *q, const vk_radiance_params *rp, uint64_t first_index, const void *d_rays, const void *d_keys, uint32_t n,
-    uint8_t *d_head, long long *d_accum, float *d_rgb, float *d_samples, hipStream_t st, bool gather = false, float *d_dirs = nullptr) {
+    uint8_t *d_head, long long *d_accum, float *d_rgb, float *d_samples, hipStream_t st, int mode = QM_RAY, float *d_dirs = nullptr) {
     RadianceArgs A;
     memset(&A, 0, sizeof(A));
     int rc = query_view(q, "a radiance query", &A.S);
@@ -2245,45 +2248,48 @@ int enqueue_radiance(vk_scene *q, const vk_radiance_params *rp, uint64_t first_i
     A.C.bg[0] = rp->background_color[0]; A.C.bg[1] = rp->background_color[1]; A.C.bg[2] = rp->background_color[2];
     A.rays = static_cast<const float4 *>(d_rays); A.keys = static_cast<const RadianceKey *>(d_keys);
     A.accum = d_samples ? nullptr : d_accum; A.samples = reinterpret_cast<float4 *>(d_samples);
-    A.dirs = gather && d_samples ? reinterpret_cast<float4 *>(d_dirs) : nullptr;
+    A.dirs = mode != QM_RAY && d_samples ? reinterpret_cast<float4 *>(d_dirs) : nullptr;
     A.counter = reinterpret_cast<uint32_t *>(d_head); A.clamped = reinterpret_cast<unsigned long long *>(d_head + 8);
     A.accum_clamp = accum_clamp_for(rp->samples_per_ray);
     A.first_index = first_index; A.n_rays = n; A.first_sample = rp->first_sample;
     A.shade_defer = SHADE_DEFER; A.prim_weight = q->plan.hot_bytes > (4u << 20) ? 3u : 1u;
-    // Units: (64 rays, a chunk of samples).  Enough of them to keep every wave of the launch busy four times over where the samples
+    // Units: (64 rays, a chunk of samples) — probe_kernel: (8 probes, a chunk of samples).  Enough of them to keep every wave of the launch busy four times over where the samples
     // allow it, at least four samples to a chunk; a chunk stays below 2^16 samples (the kernel counts 64 x that in 32 bits).  Any choice
     // gives the same sums.
-    const uint32_t spp = rp->samples_per_ray, n_blocks = (n + 63u) / 64u;
+    const uint32_t slots = mode == QM_PROBE ? PROBE_SLOTS : 64u, values = mode == QM_PROBE ? PROBE_VALUES : 3u;
+    const uint32_t spp = rp->samples_per_ray, n_blocks = (n + slots - 1u) / slots;
     const uint32_t waves = (uint32_t)q->num_cus * 24u;
     uint32_t n_chunks = (4u * waves + n_blocks - 1u) / n_blocks;
     const uint32_t hi = spp / 4u > 4096u ? 4096u : (spp / 4u ? spp / 4u : 1u), lo = (spp + 65535u) / 65536u;
     if (n_chunks > hi) n_chunks = hi;
     if (n_chunks < lo) n_chunks = lo;
     A.n_chunks = n_chunks;
-    const uint64_t units = (uint64_t)n_blocks * n_chunks;        // <= 2^14 * 2^12 for the host calls' chunks of 2^20 rays
+    const uint64_t units = (uint64_t)n_blocks * n_chunks;        // <= 2^14 * 2^12 (probes: 2^17 * 2^12) for the host calls' chunks of 2^20 rays
     if (units >= (1ull << 31)) return fail(VK_ERR_BAD_ARG, "internal error: too many work units in one radiance launch");
     const uint64_t groups = (units + (RAD_BLOCK / 64) - 1) / (RAD_BLOCK / 64), full = (uint64_t)q->num_cus * 6u;   // (24 waves per CU)
     const dim3 grid((uint32_t)(groups < full ? groups : full));
     HIP_TRY(hipMemsetAsync(d_head, 0, RAD_HEAD, st));
-    if (A.accum) HIP_TRY(hipMemsetAsync(d_accum, 0, (size_t)n * 3u * sizeof(long long), st));
+    if (A.accum) HIP_TRY(hipMemsetAsync(d_accum, 0, (size_t)n * values * sizeof(long long), st));
     const uint32_t F = pick_variant(q) | (rp->integrator == VK_INTEGRATOR_PDF ? (uint32_t)VKF_INTEG_PDF : 0u);
     rc = with_variant(F, [&](auto f) {
         constexpr uint32_t FV = decltype(f)::value;
-        return gather ? launch_radiance<FV, true>(A, grid, st) : launch_radiance<FV, false>(A, grid, st);
+        return mode == QM_PROBE ? launch_radiance<FV, QM_PROBE>(A, grid, st)
+             : (mode == QM_GATHER ? launch_radiance<FV, QM_GATHER>(A, grid, st) : launch_radiance<FV, QM_RAY>(A, grid, st));
     });
     if (rc != VK_OK) return rc;
     if (A.accum) {
-        const uint32_t nv = n * 3u;
+        const uint32_t nv = n * values;          // (n <= 2^20 from the host calls)
         hipLaunchKernelGGL(radiance_resolve_kernel, dim3((nv + 255u) / 256u), dim3(256), 0, st, d_accum, d_rgb, nv, spp);
         HIP_TRY(hipGetLastError());
     }
     return VK_OK;
 }
 
-// the host call behind vk_trace_radiance (keys == null, samples_out == null) and its per-sample hook; with `gather` the one behind
-// vk_trace_irradiance and its hook (rays = the points, keys == null; dirs_out: the hook's directions, or null)
+// the host call behind vk_trace_radiance (keys == null, samples_out == null) and its per-sample hook; with QM_GATHER the one behind
+// vk_trace_irradiance and its hook (rays = the points, keys == null; dirs_out: the hook's directions, or null); with QM_PROBE the one
+// behind vk_trace_probes and its hook (rays = the probes, rgb_out = sh_out: 27 floats a probe)
 int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *rays, uint64_t n_rays, const vk_debug_stream_key *keys,
-    float *rgb_out, float *samples_out, vk_stats *stats_out, bool gather = false, float *dirs_out = nullptr) {
+    float *rgb_out, float *samples_out, vk_stats *stats_out, int mode = QM_RAY, float *dirs_out = nullptr) {
     int rc = check_radiance_args(scene, rp, rays, n_rays, samples_out ? samples_out : rgb_out);
     if (rc != VK_OK) return rc;
     if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
@@ -2292,6 +2298,7 @@ int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *r
     if ((rc = check_integrator_for_scene(*scene->host, rp->integrator)) != VK_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t spp = rp->samples_per_ray;
+    const size_t values = mode == QM_PROBE ? PROBE_VALUES : 3u;      // per ray: fixed-point sums, and means
     if (rp->max_depth == 0u) {        // every sample is (0,0,0) (main.rs:126-128) and draws nothing
         if (samples_out) {
             for (uint64_t i = 0; i < n_rays; i++) for (uint32_t k = 0; k < spp; k++) {
@@ -2301,7 +2308,7 @@ int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *r
             }
             if (dirs_out) memset(dirs_out, 0, (size_t)n_rays * spp * 16u);          // (no direction is drawn either)
         } else {
-            memset(rgb_out, 0, (size_t)n_rays * 3u * sizeof(float));
+            memset(rgb_out, 0, (size_t)n_rays * values * sizeof(float));
         }
         if (stats_out) stats_out->samples = n_rays * spp;
         return VK_OK;
@@ -2318,16 +2325,16 @@ int radiance_host(vk_scene *scene, const vk_radiance_params *rp, const vk_ray *r
         if (dirs_out) L.stream[2] = {(size_t)spp * 16u, nullptr, dirs_out};
         else L.stream[2] = {sizeof(vk_debug_stream_key), keys, nullptr};
     } else {                // means: the fixed-point sums, then the means
-        L.stream[1] = {3u * sizeof(long long), nullptr, nullptr};
-        L.stream[2] = {3u * sizeof(float), nullptr, rgb_out};
+        L.stream[1] = {values * sizeof(long long), nullptr, nullptr};
+        L.stream[2] = {values * sizeof(float), nullptr, rgb_out};
     }
     return run_batch(q, L, n_rays, rp->first_index, t0, stats_out,
         [&](uint64_t first_index, uint64_t n, uint8_t *d_head, uint8_t *const d[4], hipStream_t st) {
             if (samples_out) return enqueue_radiance(q, rp, first_index, d[0], keys ? d[2] : nullptr, (uint32_t)n, d_head, nullptr, nullptr,
-                                                     reinterpret_cast<float *>(d[1]), st, gather,
+                                                     reinterpret_cast<float *>(d[1]), st, mode,
                                                      dirs_out ? reinterpret_cast<float *>(d[2]) : nullptr);
             return enqueue_radiance(q, rp, first_index, d[0], nullptr, (uint32_t)n, d_head, reinterpret_cast<long long *>(d[1]),
-                                    reinterpret_cast<float *>(d[2]), nullptr, st, gather);
+                                    reinterpret_cast<float *>(d[2]), nullptr, st, mode);
         });
 }
 
@@ -2351,7 +2358,7 @@ int vk_debug_trace_radiance_samples(vk_scene *scene, const vk_radiance_params *p
 
 int vk_trace_irradiance(vk_scene *scene, const vk_radiance_params *params, const vk_ray *points, uint64_t n_points, float *rgb_out,
     vk_stats *stats_out) {
-    return guarded([&]() -> int { return radiance_host(scene, params, points, n_points, nullptr, rgb_out, nullptr, stats_out, true); });
+    return guarded([&]() -> int { return radiance_host(scene, params, points, n_points, nullptr, rgb_out, nullptr, stats_out, QM_GATHER); });
 }
 
 // test hook (vecchio_amd_debug.h): every sample of the query and, where asked for, the direction drawn for it
@@ -2359,7 +2366,43 @@ int vk_debug_trace_irradiance_samples(vk_scene *scene, const vk_radiance_params 
     float *samples_out, float *dirs_out, vk_stats *stats_out) {
     return guarded([&]() -> int {
         if (n_points != 0u && !samples_out) return fail(VK_ERR_BAD_ARG, "null samples buffer");
-        return radiance_host(scene, params, points, n_points, nullptr, nullptr, samples_out, stats_out, true, dirs_out);
+        return radiance_host(scene, params, points, n_points, nullptr, nullptr, samples_out, stats_out, QM_GATHER, dirs_out);
+    });
+}
+
+int vk_trace_probes(vk_scene *scene, const vk_radiance_params *params, const vk_ray *probes, uint64_t n_probes, float *sh_out,
+    vk_stats *stats_out) {
+    return guarded([&]() -> int { return radiance_host(scene, params, probes, n_probes, nullptr, sh_out, nullptr, stats_out, QM_PROBE); });
+}
+
+// test hook (vecchio_amd_debug.h): every sample of the query and, where asked for, the direction drawn for it
+int vk_debug_trace_probe_samples(vk_scene *scene, const vk_radiance_params *params, const vk_ray *probes, uint64_t n_probes,
+    float *samples_out, float *dirs_out, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        if (n_probes != 0u && !samples_out) return fail(VK_ERR_BAD_ARG, "null samples buffer");
+        return radiance_host(scene, params, probes, n_probes, nullptr, nullptr, samples_out, stats_out, QM_PROBE, dirs_out);
+    });
+}
+
+// rgb[c] = sum_k w_l(k) * sh[k * 3 + c] * Y_k(unit(n)) in double, rounded once (plain host code: no device, no handle)
+int vk_probe_eval(const float *sh27, const float n[3], uint32_t mode, float rgb[3]) {
+    return guarded([&]() -> int {
+        if (!sh27 || !n || !rgb) return fail(VK_ERR_BAD_ARG, "null argument (sh27, n or rgb)");
+        if (mode > 1u) return fail(VK_ERR_BAD_ARG, "mode must be 0 (radiance) or 1 (irradiance / pi)");
+        const double len = std::sqrt((double)n[0] * n[0] + (double)n[1] * n[1] + (double)n[2] * n[2]);
+        const double x = n[0] / len, y = n[1] / len, z = n[2] / len;
+        const double Y[9] = {0.282095, 0.488603 * y, 0.488603 * z, 0.488603 * x, 1.092548 * (x * y), 1.092548 * (y * z),
+                             0.315392 * (3.0 * (z * z) - 1.0), 1.092548 * (x * z), 0.546274 * (x * x - y * y)};
+        const double pi = 3.14159265358979323846;
+        for (int c = 0; c < 3; c++) {
+            double v = 0.0;
+            for (int k = 0; k < 9; k++) {
+                const double w = mode == 0u ? 4.0 * pi : (k == 0 ? 4.0 * pi : (k < 4 ? 8.0 * pi / 3.0 : pi));
+                v += w * (double)sh27[k * 3 + c] * Y[k];
+            }
+            rgb[c] = (float)v;
+        }
+        return VK_OK;
     });
 }
 

@@ -1749,11 +1749,71 @@ __device__ __forceinline__ void flush_ray_sums(unsigned long long *sums, long lo
     }
 }
 
+// the three path queries: what the refill reads a record as (radiance_phase)
+enum : int { QM_RAY = 0, QM_GATHER = 1, QM_PROBE = 2 };
+// probe_kernel's work unit is (8 consecutive probes, a chunk of samples): 27 sums a probe, 8 x 27 x u64 = 1 728 bytes of LDS a wave
+constexpr uint32_t PROBE_SLOTS = 8u, PROBE_VALUES = 27u;
+template <int MODE> constexpr uint32_t query_sum_floats() { return MODE == QM_PROBE ? PROBE_SLOTS * PROBE_VALUES * 2u : 64u * 3u * 2u; }
+// per-wave LDS block of a path-query kernel: wave_block_floats with the kernel's own sums
+template <uint32_t F, int MODE> constexpr uint32_t query_block_floats() {
+    return 64u * (uint32_t)ncold<F>() + query_sum_floats<MODE>() + (uint32_t)WAVE_STATE_WORDS; }
+
+// adds the wave's LDS sums of probe block `blk` (8 probes x 27 values, contiguous as the launch's are) to the launch's accumulators and
+// clears them: 216 values over the 64 lanes
+__device__ __forceinline__ void flush_probe_sums(unsigned long long *sums, long long *accum, uint32_t blk, uint32_t lane, uint32_t n_probes) {
+    if (!accum || blk == 0xFFFFFFFFu) return;
+    unsigned long long *a = reinterpret_cast<unsigned long long *>(accum) + (size_t)blk * (PROBE_SLOTS * PROBE_VALUES);
+    for (uint32_t j = lane; j < PROBE_SLOTS * PROBE_VALUES; j += 64u) {
+        if (blk * PROBE_SLOTS + j / PROBE_VALUES >= n_probes) break;          // slots behind the batch's last probe
+        unsigned long long v = sums[j];
+        if (v) { atomicAdd(a + j, v); sums[j] = 0ull; }
+    }
+}
+
+// a finished, finite sample `rgb` of probe r (counted from the launch's first), sample index smp: the direction drawn again from the
+// stream's beginning, the nine basis values, and the 27 products in fixed point — converted and clamped as a radiance component is, the
+// sample counted once if a product was clamped — into the wave's LDS sums (the block being handed out) or the launch's (a straggler).
+// A non-finite direction (random_in_unit_sphere gave zero) drops the sample.
+__device__ __forceinline__ void probe_accumulate(RArgsC P, const RenderConsts &C, long long *acc, unsigned long long *sums,
+                                                 const uint32_t *wstate, uint32_t r, uint32_t smp, V3 rgb) {
+    Rng g = radiance_rng(C.seed, RARG(P, first_index) + r, smp);
+    const V3 u = probe_direction(g);
+    if (!(isfinite(u.x) && isfinite(u.y) && isfinite(u.z))) return;
+    float Y[9];
+    sh9(u, Y);
+    const float clampv = RARG(P, accum_clamp);
+    const float rgbv[3] = {rgb.x, rgb.y, rgb.z};
+    float big = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) big = fmaxf(big, fabsf(Y[k] * rgbv[c]));
+    }
+    const bool small = big <= ACCUM_SMALL;
+    if (!small && big > clampv) atomicAdd(RARG(P, clamped), 1ull);     // (rare)
+    auto add = [&](unsigned long long *t) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const float v = Y[k] * rgbv[c];
+                const unsigned long long f = (unsigned long long)(small ? to_fixed_small(v) : to_fixed(v, clampv));
+                if (f) atomicAdd(t + (k * 3 + c), f);
+            }
+        }
+    };
+    if ((r / PROBE_SLOTS) == __builtin_amdgcn_readfirstlane(wstate[RS_BLOCK])) add(sums + (r % PROBE_SLOTS) * PROBE_VALUES);
+    else add(reinterpret_cast<unsigned long long *>(acc) + (size_t)r * PROBE_VALUES);
+}
+
 // the SHADE + REFILL phase (cf. shade_refill_body).  Leaves `fresh` lanes with a new ray parked in L.wo / L.wd / L.time; t0 / walk are
-// what its first segment starts with (radiance_start_core; +inf / true for a path that continues).  GATHER (gather_kernel,
+// what its first segment starts with (radiance_start_core; +inf / true for a path that continues).  QM_GATHER (gather_kernel,
 // vk_trace_irradiance): the record read is a point — origin p, direction the normal n — and the ray is made here: the lane draws
-// irradiance_direction from the sample's stream, parks (p, d, time) and hands radiance_start_core the stream behind the draw.
-template <uint32_t F, bool GATHER = false>
+// irradiance_direction from the sample's stream, parks (p, d, time) and hands radiance_start_core the stream behind the draw.  QM_PROBE
+// (probe_kernel, vk_trace_probes): the record is a probe — origin p, direction not read — and the lane draws probe_direction; a finished
+// sample draws it AGAIN from the stream's beginning (no path state holds it) and adds its 27 products sh9 x rgb (probe_accumulate).
+// SLOTS: the records of a work unit, 64 (lane = slot at the flush) or, for the probes' 27 sums a record, 8.
+template <uint32_t F, int MODE = QM_RAY, uint32_t SLOTS = 64u>
 __device__ __forceinline__ void radiance_phase(Lane &L, bool is_shade, bool &active, bool &need, bool &fresh, bool &touched, float &t0,
                                                bool &walk, RArgsC P, float *cold, unsigned long long *sums, uint32_t *wstate, uint32_t lane) {
     RenderConsts C = RARG(P, C);
@@ -1773,6 +1833,10 @@ __device__ __forceinline__ void radiance_phase(Lane &L, bool is_shade, bool &act
             if (dbg) dbg[(size_t)r * C.spp + (__float_as_uint(cold[CF_SAMPLE * 64 + lane]) - RARG(P, first_sample))] =
                 make_float4(L.acc.x, L.acc.y, L.acc.z, __uint_as_float(L.rng.ctr));
             long long *acc = RARG(P, accum);
+            if (MODE == QM_PROBE) {
+                if (acc && isfinite(L.acc.x) && isfinite(L.acc.y) && isfinite(L.acc.z))
+                    probe_accumulate(P, C, acc, sums, wstate, r, __float_as_uint(cold[CF_SAMPLE * 64 + lane]), L.acc);
+            } else
             if (acc && isfinite(L.acc.x) && isfinite(L.acc.y) && isfinite(L.acc.z)) {   // main.rs:192-194; c += color (main.rs:193)
                 const float clampv = RARG(P, accum_clamp);
                 const float big = fmaxf(fmaxf(fabsf(L.acc.x), fabsf(L.acc.y)), fabsf(L.acc.z));
@@ -1813,19 +1877,21 @@ __device__ __forceinline__ void radiance_phase(Lane &L, bool is_shade, bool &act
             unit = __builtin_amdgcn_readfirstlane(unit);
             const uint32_t n_chunks = RARG(P, n_chunks);
             // (the host keeps blocks x chunks below 2^31 and a chunk below 2^20 samples)
-            if (unit >= ((n_rays + 63u) >> 6) * n_chunks) { need = false; break; }
-            flush_ray_sums(sums, RARG(P, accum), blk, lane, n_rays);          // the finished unit's sums so far
+            if (unit >= ((n_rays + (SLOTS - 1u)) / SLOTS) * n_chunks) { need = false; break; }
+            // the finished unit's sums so far
+            if (MODE == QM_PROBE) flush_probe_sums(sums, RARG(P, accum), blk, lane, n_rays);
+            else flush_ray_sums(sums, RARG(P, accum), blk, lane, n_rays);
             const uint32_t chunk = unit % n_chunks;
             blk = unit / n_chunks;
             s0 = (uint32_t)(((uint64_t)C.spp * chunk) / n_chunks);
             const uint32_t s1 = (uint32_t)(((uint64_t)C.spp * (chunk + 1)) / n_chunks);
-            next = 0u; total = 64u * (s1 - s0);
+            next = 0u; total = SLOTS * (s1 - s0);
             s0 += RARG(P, first_sample);
             if (lane == 0) { wstate[RS_BLOCK] = blk; wstate[RS_S0] = s0; wstate[RS_TOTAL] = total; }
         }
         const uint32_t k = next + (uint32_t)__popcll(need_mask & ((1ull << lane) - 1ull));
         if (need && k < total) {
-            const uint32_t r = blk * 64u + (k & 63u), smp = s0 + (k >> 6);
+            const uint32_t r = blk * SLOTS + (k % SLOTS), smp = s0 + k / SLOTS;
             if (r < n_rays) {                  // slots behind the batch's last ray are skipped: the lane asks again
                 cold[CF_XY * 64 + lane] = __uint_as_float(r);
                 cold[CF_SAMPLE * 64 + lane] = __uint_as_float(smp);
@@ -1841,8 +1907,8 @@ __device__ __forceinline__ void radiance_phase(Lane &L, bool is_shade, bool &act
                     g = radiance_rng(C.seed, RARG(P, first_index) + r, smp);
                 }
                 V3 dir = v3(r1.x, r1.y, r1.z);
-                if (GATHER) {
-                    dir = irradiance_direction(g, dir);
+                if (MODE != QM_RAY) {
+                    dir = MODE == QM_PROBE ? probe_direction(g) : irradiance_direction(g, dir);
                     float4 *dd = RARG(P, dirs);
                     if (dd) dd[(size_t)r * C.spp + (smp - RARG(P, first_sample))] = make_float4(dir.x, dir.y, dir.z, 0.0f);
                 }
@@ -1859,18 +1925,21 @@ __device__ __forceinline__ void radiance_phase(Lane &L, bool is_shade, bool &act
     }
 }
 
-// the persistent loop of both query kernels (radiance_kernel, gather_kernel): they differ in the refill's ray-making step only
-template <uint32_t F, bool GATHER>
+// the persistent loop of the three path-query kernels (radiance_kernel, gather_kernel, probe_kernel): they differ in the refill's
+// ray-making step and, probe_kernel, in what a finished sample adds: 27 sums for each of a unit's 8 probes instead of 3 for each of 64 rays
+template <uint32_t F, int MODE>
 __device__ __forceinline__ void path_query_waves() {
+    constexpr uint32_t SLOTS = MODE == QM_PROBE ? PROBE_SLOTS : 64u;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     using Mem = GlobalMem;
-    // ---- LDS layout: per wave [cold lane state | block sums: 64 x 3 x u64 | wave state]
-    float *cold = reinterpret_cast<float *>(smem) + wave * wave_block_floats<F>();
+    // ---- LDS layout: per wave [cold lane state | block sums: 64 x 3 x u64 (probe_kernel: 8 x 27 x u64) | wave state]
+    float *cold = reinterpret_cast<float *>(smem) + wave * query_block_floats<F, MODE>();
     unsigned long long *sums = reinterpret_cast<unsigned long long *>(cold + 64 * ncold<F>());
-    uint32_t *wstate = reinterpret_cast<uint32_t *>(cold + 64 * ncold<F>() + 64 * 3 * 2);
+    uint32_t *wstate = reinterpret_cast<uint32_t *>(cold + 64 * ncold<F>() + query_sum_floats<MODE>());
     // the wave has no unit yet: the first SHADE + REFILL phase pulls one
-    sums[lane * 3 + 0] = 0ull; sums[lane * 3 + 1] = 0ull; sums[lane * 3 + 2] = 0ull;
+    if (MODE == QM_PROBE) { for (uint32_t j = lane; j < PROBE_SLOTS * PROBE_VALUES; j += 64u) sums[j] = 0ull; }
+    else { sums[lane * 3 + 0] = 0ull; sums[lane * 3 + 1] = 0ull; sums[lane * 3 + 2] = 0ull; }
     if (lane == 0) { wstate[RS_BLOCK] = 0xFFFFFFFFu; wstate[RS_NEXT] = 0u; wstate[RS_TOTAL] = 0u; }
 
     Lane L;
@@ -1957,7 +2026,7 @@ __device__ __forceinline__ void path_query_waves() {
             const bool is_shade = __builtin_amdgcn_inverse_ballot_w64(m_shade);
             bool touched = false, fresh = false, walk = true;
             float t0 = INFINITY;
-            radiance_phase<F, GATHER>(L, is_shade, active, need, fresh, touched, t0, walk, rargs_fresh(), cold, sums, wstate, lane);
+            radiance_phase<F, MODE, SLOTS>(L, is_shade, active, need, fresh, touched, t0, walk, rargs_fresh(), cold, sums, wstate, lane);
             if (fresh) {
                 RArgsC P = rargs_fresh();
                 DScene S = RARG(P, S);
@@ -1970,14 +2039,15 @@ __device__ __forceinline__ void path_query_waves() {
     }
     {   // the last unit's sums
         RArgsC P = rargs_fresh();
-        flush_ray_sums(sums, RARG(P, accum), __builtin_amdgcn_readfirstlane(wstate[RS_BLOCK]), lane, RARG(P, n_rays));
+        if (MODE == QM_PROBE) flush_probe_sums(sums, RARG(P, accum), __builtin_amdgcn_readfirstlane(wstate[RS_BLOCK]), lane, RARG(P, n_rays));
+        else flush_ray_sums(sums, RARG(P, accum), __builtin_amdgcn_readfirstlane(wstate[RS_BLOCK]), lane, RARG(P, n_rays));
     }
 }
 
 template <uint32_t F, int MINW>
 __global__ __launch_bounds__(RAD_BLOCK, MINW) void radiance_kernel(RadianceArgs A_byval) {
     (void)A_byval;
-    path_query_waves<F, false>();
+    path_query_waves<F, QM_RAY>();
 }
 
 // ---- irradiance queries (vk_trace_irradiance): radiance_kernel around a refill that reads (point, normal) records and draws each
@@ -1986,7 +2056,17 @@ __global__ __launch_bounds__(RAD_BLOCK, MINW) void radiance_kernel(RadianceArgs 
 template <uint32_t F, int MINW>
 __global__ __launch_bounds__(RAD_BLOCK, MINW) void gather_kernel(RadianceArgs A_byval) {
     (void)A_byval;
-    path_query_waves<F, true>();
+    path_query_waves<F, QM_GATHER>();
+}
+
+// ---- probe queries (vk_trace_probes): radiance_kernel around a refill that draws each sample's uniform direction on the device
+// (radiance_phase<F, QM_PROBE, 8>) and a finish that projects the sample onto nine spherical-harmonic basis functions.  No per-path state
+// is added: the finish draws the direction again from the sample's (index, sample).  The arguments are radiance_kernel's (rays = the
+// probes, keys = null, accum = 27 sums a probe).
+template <uint32_t F, int MINW>
+__global__ __launch_bounds__(RAD_BLOCK, MINW) void probe_kernel(RadianceArgs A_byval) {
+    (void)A_byval;
+    path_query_waves<F, QM_PROBE>();
 }
 
 // ray mean = fixed-point sum / samples_per_ray (resolve_kernel's arithmetic)

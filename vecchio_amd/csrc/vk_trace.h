@@ -1746,5 +1746,31 @@ VK_HD V3 irradiance_sample(Lane &L, const DScene &S, const Mem &M, const RenderC
     return radiance_sample<F, Mem>(L, S, M, C, p, d, time, tmax, g);
 }
 
+// ------------------------------------------------------------------ probe queries (vk_trace_probes, include/vecchio_amd.h)
+// random_in_unit_sphere(g).unit_vector() (util.rs:31-39, vec3.rs): a uniform direction on the stream `g`.  Three gen_range(-1, 1) draws
+// per try; a zero point (probability about zero) gives a NaN direction.
+VK_HD V3 probe_direction(Rng &g) { return unit(random_in_unit_sphere(g)); }
+// the nine real spherical-harmonic basis functions of bands 0..2 at the unit vector u, in the header's form and order
+VK_HD void sh9(V3 u, float Y[9]) {
+    const float x = u.x, y = u.y, z = u.z;
+    Y[0] = 0.282095f;
+    Y[1] = 0.488603f * y;
+    Y[2] = 0.488603f * z;
+    Y[3] = 0.488603f * x;
+    Y[4] = 1.092548f * (x * y);
+    Y[5] = 1.092548f * (y * z);
+    Y[6] = 0.315392f * (3.0f * (z * z) - 1.0f);
+    Y[7] = 1.092548f * (x * z);
+    Y[8] = 0.546274f * (x * x - y * y);
+}
+// one whole sample of the probe at p inside the lane (the host emulator; cf. irradiance_sample): the direction from the sample's
+// stream, then radiance_sample on the stream where the draws left it.  `u` returns the direction.
+template <uint32_t F, class Mem>
+VK_HD V3 probe_sample(Lane &L, const DScene &S, const Mem &M, const RenderConsts &C, V3 p, float time, float tmax, const Rng &rng, V3 &u) {
+    Rng g = rng;
+    u = probe_direction(g);
+    return radiance_sample<F, Mem>(L, S, M, C, p, u, time, tmax, g);
+}
+
 }  // namespace vkd
 #endif

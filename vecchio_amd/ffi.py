@@ -12,6 +12,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 ASSETS_DIR = os.path.join(os.path.dirname(_HERE), "tests", "golden", "assets")
 
 VK_ABI_VERSION = 7
+VK_PROBE_COEFFS = 9
 VK_OK, VK_ERR_BAD_ARG, VK_ERR_UNSUPPORTED, VK_ERR_HIP, VK_ERR_NO_DEVICE, VK_ERR_OOM = range(6)
 
 (VK_KIND_NONE, VK_KIND_BVH, VK_KIND_SPHERE, VK_KIND_MOVING_SPHERE, VK_KIND_RECT, VK_KIND_LIST,
@@ -285,7 +286,7 @@ DEVICE_SYMBOLS = [
     "vk_render_aov", "vk_render_aov_device",
     "vk_guide_default_params", "vk_render_guides", "vk_render_guides_device",
     "vk_trace_rays", "vk_trace_rays_device", "vk_trace_occluded", "vk_trace_occluded_device",
-    "vk_trace_radiance", "vk_trace_irradiance",
+    "vk_trace_radiance", "vk_trace_irradiance", "vk_trace_probes", "vk_probe_eval",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -372,6 +373,10 @@ def _bind(lib):
     lib.vk_trace_radiance.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
     lib.vk_trace_irradiance.restype = C.c_int
     lib.vk_trace_irradiance.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_trace_probes.restype = C.c_int
+    lib.vk_trace_probes.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_probe_eval.restype = C.c_int
+    lib.vk_probe_eval.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.vk_trace_occluded_device.restype = C.c_int
     lib.vk_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                              C.POINTER(Stats)]
@@ -412,6 +417,9 @@ def _bind(lib):
     lib.vk_debug_trace_irradiance_samples.restype = C.c_int
     lib.vk_debug_trace_irradiance_samples.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                       C.POINTER(Stats)]
+    lib.vk_debug_trace_probe_samples.restype = C.c_int
+    lib.vk_debug_trace_probe_samples.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(Stats)]
     lib.vk_debug_trace_occluded_device.restype = C.c_int
     lib.vk_debug_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_uint32, C.c_uint32]

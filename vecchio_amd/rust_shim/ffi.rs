@@ -12,6 +12,7 @@ use std::os::raw::{c_char, c_int, c_void};
 
 pub type vk_ref = u32;
 pub const VK_ABI_VERSION: u32 = 7;
+pub const VK_PROBE_COEFFS: u32 = 9;
 pub const VK_SCENE_FAST_ACCEL: u32 = 1;
 pub const VK_SCENE_REFERENCE_TREE: u32 = 2;
 pub const VK_SCENE_EMPIRICAL_TREES: u32 = 4;
@@ -174,6 +175,12 @@ extern "C" {
     // normal; rgb_out[i] = the mean radiance over samples_per_ray cosine-weighted directions drawn on the device (irradiance = pi * that)
     pub fn vk_trace_irradiance(scene: *mut vk_scene, params: *const vk_radiance_params, points: *const vk_ray, n_points: u64,
                                rgb_out: *mut f32, stats_out: *mut vk_stats) -> c_int;
+    // probe queries (additive symbols of ABI 7): a probe is a vk_ray whose origin is the position (the direction is not read);
+    // sh_out[(i * 9 + k) * 3 + c] = the mean of Y_k(u) * L_c(u) over samples_per_ray uniform directions drawn on the device (the
+    // radiance's SH coefficient = 4 pi * that).  vk_probe_eval touches no device: mode 0 = radiance along n, 1 = irradiance / pi
+    pub fn vk_trace_probes(scene: *mut vk_scene, params: *const vk_radiance_params, probes: *const vk_ray, n_probes: u64,
+                           sh_out: *mut f32, stats_out: *mut vk_stats) -> c_int;
+    pub fn vk_probe_eval(sh27: *const f32, n: *const f32, mode: u32, rgb: *mut f32) -> c_int;
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

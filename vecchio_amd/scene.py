@@ -100,6 +100,24 @@ def points_from_hits(hits, time=0.0):
     return make_points(hits["p"][index], hits["normal"][index], time), index
 
 
+def make_probes(p, time=0.0, tmax=np.inf):
+    """Probes for DeviceScene.trace_probes(): a RAY_DTYPE array whose origin is the position (the direction is not read), from positions
+    (n, 3) and per-probe or scalar times and tmax."""
+    p = np.asarray(p, np.float32).reshape(-1, 3)
+    return make_rays(p, np.zeros_like(p), time, tmax)
+
+
+def probe_eval(sh, normal, mode=1, lib=None):
+    """vk_probe_eval for one probe: sh (9, 3) as trace_probes() returns it, normal of any non-zero length.  mode 0: the band-limited
+    radiance arriving along the normal; mode 1: irradiance / pi for it (what trace_irradiance() estimates).  A (3,) float32 array."""
+    lib = lib or ffi.load_device_lib()
+    sh = np.ascontiguousarray(sh, np.float32).reshape(27)
+    n = (C.c_float * 3)(*[float(v) for v in np.asarray(normal, np.float32).reshape(3)])
+    rgb = (C.c_float * 3)()
+    check(lib, lib.vk_probe_eval(sh.ctypes.data_as(C.POINTER(C.c_float)), n, mode, rgb))
+    return np.array(list(rgb), np.float32)
+
+
 def check(lib, status):
     if status != ffi.VK_OK:
         raise RuntimeError(f"vecchio_amd status {status}: {lib.vk_last_error().decode()}")
@@ -290,6 +308,36 @@ class DeviceScene:
         samples = np.zeros((n, rp.samples_per_ray, 4), np.float32)
         dirs = np.zeros((n, rp.samples_per_ray, 4), np.float32)
         self._host_batch("vk_debug_trace_irradiance_samples", rp, stats, points, samples, dirs)
+        return (samples, dirs, stats) if return_stats else (samples, dirs)
+
+    def trace_probes(self, probes, seed=0, first_index=0, samples_per_ray=1, first_sample=0, max_depth=50,
+                     integrator=ffi.VK_INTEGRATOR_PDF, background=ffi.VK_BACKGROUND_SOLID, background_color=(0.0, 0.0, 0.0), out=None,
+                     return_stats=False):
+        """Spherical-harmonic light probes at caller-supplied points (vk_trace_probes): an (n, 9, 3) float32 array, out[i, k, c] the mean
+        over samples first_sample .. first_sample + samples_per_ray - 1 of probes[i] of Y_k(u) * L_c(u), each a uniform direction u drawn
+        on the device and ray_color along it on the same stream.  The radiance's SH coefficient is 4 pi * out; probe_eval() answers for a
+        normal.  probes: make_probes() (host memory; the call has no device-pointer variant yet)."""
+        rp = self.radiance_params(seed, first_index, samples_per_ray, first_sample, max_depth, integrator, background, background_color)
+        stats = ffi.Stats()
+        probes = self._host_rays(probes)
+        n = probes.shape[0]
+        if out is None:
+            out = np.zeros((n, ffi.VK_PROBE_COEFFS, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (n, ffi.VK_PROBE_COEFFS, 3)
+        self._host_batch("vk_trace_probes", rp, stats, probes, out)
+        return (out, stats) if return_stats else out
+
+    def debug_probe_samples(self, probes, return_stats=False, **params):
+        """Every sample of trace_probes() (vk_debug_trace_probe_samples, a test hook): (samples, dirs), both (n, samples_per_ray, 4)
+        float32 — samples[..., :3] the radiance before the finite filter, samples[..., 3] the stream's final counter (bit pattern),
+        dirs[..., :3] the unit direction drawn for the sample.  params: radiance_params()'s keywords."""
+        rp = self.radiance_params(**params)
+        stats = ffi.Stats()
+        probes = self._host_rays(probes)
+        n = probes.shape[0]
+        samples = np.zeros((n, rp.samples_per_ray, 4), np.float32)
+        dirs = np.zeros((n, rp.samples_per_ray, 4), np.float32)
+        self._host_batch("vk_debug_trace_probe_samples", rp, stats, probes, samples, dirs)
         return (samples, dirs, stats) if return_stats else (samples, dirs)
 
     GUIDE_CHANNELS = AOV_CHANNELS + ("bounces",)
