@@ -790,6 +790,71 @@ int vk_trace_probes(vk_scene *scene, const vk_radiance_params *params, const vk_
  *   VK_ERR_BAD_ARG for a null pointer or another mode; rgb is then untouched.  A zero or non-finite n gives NaN.                    */
 int vk_probe_eval(const float *sh27, const float n[3], uint32_t mode, float rgb[3]);
 
+/* ---- shade queries: one bounce of ray_color on the caller's hits (additive symbols of ABI 7) ----------------------------------------
+ * replaces: the body of ray_color (main.rs:123-153; ray_color_scatter for VK_INTEGRATOR_SCATTER) behind its world.hit, for a (ray, hit,
+ * path state) the CALLER supplies: the other half of a wavefront integrator's loop around vk_trace_rays — per-bounce outputs, a
+ * termination rule or next-event rays of the caller's own (through vk_trace_occluded), split paths — with the library's materials,
+ * textures, light sampling and sky, and its samples.  Everything is f32 and unfused, in the reference's order.
+ *   Item i is one call of that body with r.direction = rays[i].direction, r.time = rays[i].time (origin and tmax are not read), the
+ *     throughput thr, the radiance so far acc and the depth of states[i] (`depth` as ray_color's argument: a fresh path has thr (1,1,1),
+ *     acc (0,0,0), depth 1), and the stream rng_for_sample(seed, pixel, sample) standing at draw `counter` (fresh: 0); max_depth, the
+ *     integrator and the background from params.
+ *   Miss (hits[i].hit == 0): acc += thr * background(unit(direction)) — the direction is normalised only for the sky; status
+ *     VK_SHADE_MISS; nothing is drawn.
+ *   Hit (hits[i].hit == 1): the HitRec is p, normal, t, u, v, front != 0 and material of hits[i], the material
+ *     materials[hits[i].material] of the description.  Then emitted, scatter / scatter_with_pdf (SpecDiffuse resolved by its draws), the
+ *     mixture-PDF light sampling and the update of acc and thr exactly as vk_render makes them, the PDF integrator's time 0 for a Metal's
+ *     ray included; then depth += 1, and a depth above max_depth ends the path with acc += thr * 0 (which keeps the reference's NaN).
+ *     status VK_SHADE_SCATTERED with the next ray in `next` (origin = hits[i].p, tmax = +INFINITY), or VK_SHADE_ENDED (an emitter, an
+ *     absorbing Metal, the depth) with `next` zeros.  `medium` needs no special case: an Isotropic material shades from the record.
+ *     lobe: VK_MAT_* of the material finally sampled (the SpecDiffuse's child the draws chose); 0xFFFFFFFF for MISS and BAD_HIT.
+ *   Bad hit (hits[i].hit > 1, or hit == 1 and material >= the description's n_materials): status VK_SHADE_BAD_HIT, the state copied
+ *     through, `next` zeros, nothing drawn, and no memory read by that index.
+ *   state: thr, depth, acc and counter after the bounce; seed, pixel and sample copied.  _pad is written 0.
+ *   THE CONTRACT.  In a scene without a ConstantMedium (vk_trace_rays then draws nothing): start ray i of a batch with the state {thr 1,
+ *     depth 1, acc 0, counter 0, seed + 0x9E3779B97F4A7C15 * (first_index + i) in wrapping u64, pixel 0, sample s}, then repeat
+ *     hits = vk_trace_rays(rays); out = vk_shade_hits(rays, hits, states); rays, states = out.next, out.state while status is
+ *     VK_SHADE_SCATTERED.  state.acc then equals sample s of vk_trace_radiance for that ray, seed, first_index and parameters, before its
+ *     finite filter, bit for bit (a NaN's payload aside), and state.counter its stream's final counter.  The first call uses the ray's
+ *     own tmax; next.tmax is +INFINITY: vk_trace_radiance's "first segment only" rule.
+ *     With media the loop is still a valid estimator but not that sample: vk_trace_rays draws a medium's distance from its own per-ray
+ *     stream, not from the path's.
+ *   max_depth = 0 gets no special case here: a hit at depth 1 ends with acc += thr * 0 and a miss adds the background.  The contract is
+ *     for max_depth >= 1; vk_trace_radiance's (0,0,0) for max_depth = 0 starts no path at all, and neither should the caller.
+ *   Arguments: VK_ERR_BAD_ARG with nothing enqueued and the outputs untouched for a null scene or params, a null rays, hits, states or
+ *     out with n > 0, flags != 0, an unknown integrator or background, n > 2^32.  VK_ERR_UNSUPPORTED where vk_render answers it (the PDF
+ *     integrator without lights, the scatter integrator with a SpecDiffuse), in the same words.  n == 0: VK_OK, nothing done (stats_out
+ *     zeroed).
+ *   Scene state: vk_trace_rays' rules.  The call is the scene's one render in flight; it touches nothing that describes vk_render's last
+ *     frame and no vk_progress or vk_temporal handle.  A multi-device scene runs the call on devices[0].  Rays, hits, states and results
+ *     are staged through the ray queries' scratch of the scene handle, at most 2^19 items at a time (longer batches run in chunks; an
+ *     item's result depends on the item alone).  stats_out: samples = n, kernel_ms (summed over the chunks), kernel_launches.
+ *   There is no device-pointer variant yet.                                                                                         */
+typedef struct vk_path_state {        /* 48 bytes */
+    float thr[3]; uint32_t depth;     /* throughput; depth as ray_color's (a fresh path: 1,1,1 and 1) */
+    float acc[3]; uint32_t counter;   /* radiance so far; the stream's counter (fresh: 0) */
+    uint64_t seed; uint32_t pixel, sample;   /* the stream rng_for_sample(seed, pixel, sample) */
+} vk_path_state;
+enum { VK_SHADE_MISS = 0, VK_SHADE_SCATTERED = 1, VK_SHADE_ENDED = 2, VK_SHADE_BAD_HIT = 3 };
+struct vk_shaded {                    /* 96 bytes */
+    vk_ray next;                      /* SCATTERED: origin = hit.p, tmax = +INFINITY, direction, time; else zeros */
+    vk_path_state state;              /* the state after this bounce */
+    uint32_t status;                  /* VK_SHADE_* */
+    uint32_t lobe;                    /* VK_MAT_* of the material finally sampled (behind SpecDiffuse draws); 0xFFFFFFFF for MISS / BAD_HIT */
+    uint32_t _pad[2];                 /* written 0 */
+};
+typedef struct vk_shaded vk_shaded;
+typedef struct vk_shade_params {
+    uint32_t max_depth;               /* as vk_render_params.max_depth */
+    uint32_t integrator;              /* VK_INTEGRATOR_* */
+    uint32_t background;              /* VK_BACKGROUND_* */
+    float background_color[3];
+    uint32_t flags;                   /* 0 */
+    uint32_t _pad;
+} vk_shade_params;
+int vk_shade_hits(vk_scene *scene, const vk_shade_params *params, const vk_ray *rays, const vk_hit *hits,
+                  const vk_path_state *states, uint64_t n, vk_shaded *out, vk_stats *stats_out);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

@@ -1936,7 +1936,7 @@ int vk_render_guides_device(vk_scene *scene, const vk_camera *cam, const vk_rend
 
 }  // extern "C"
 
-// ---- ray-batch queries (vk_trace_rays, vk_trace_occluded, vk_trace_radiance, vk_trace_irradiance, vk_trace_probes and their hooks): one kernel per
+// ---- ray-batch queries (vk_trace_rays, vk_trace_occluded, vk_trace_radiance, vk_trace_irradiance, vk_trace_probes, vk_shade_hits and their hooks): one kernel per
 // family on the tree view of the first-hit buffers (query_view), on the scene's device (devices[0] of a multi-device scene), with events
 // and a staging buffer of their own: nothing that describes vk_render's last frame is read or written.  What the families share is
 // here: the argument checks of a batch (check_batch_args) and the host-pointer calls' chunked loop (run_batch).  A family adds its
@@ -2403,6 +2403,77 @@ int vk_probe_eval(const float *sh27, const float n[3], uint32_t mode, float rgb[
             rgb[c] = (float)v;
         }
         return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- shade queries (vk_shade_hits): shade_hits_kernel.  The scratch of one chunk: [rays][hits][states][results], 240 bytes an item.
+namespace {
+
+constexpr uint64_t SHADE_CHUNK = 1ull << 19;     // items staged at a time (120 MiB of scratch: vk_trace_rays' chunk takes 96)
+static_assert(sizeof(vk_path_state) == 48 && sizeof(vk_shaded) == 96, "what shade_hits_kernel reads and writes");
+
+// the call's parameters as the radiance family's, for its checks (one sample, nothing of a batch's indices)
+vk_radiance_params shade_as_radiance(const vk_shade_params *sp) {
+    vk_radiance_params rp;
+    memset(&rp, 0, sizeof(rp));
+    rp.samples_per_ray = 1u; rp.max_depth = sp->max_depth; rp.integrator = sp->integrator; rp.background = sp->background;
+    rp.background_color[0] = sp->background_color[0]; rp.background_color[1] = sp->background_color[1];
+    rp.background_color[2] = sp->background_color[2];
+    rp.flags = sp->flags;
+    return rp;
+}
+
+// one launch for items [0, n) of d_rays, d_hits and d_states
+int enqueue_shade(vk_scene *q, const vk_shade_params *sp, const void *d_rays, const void *d_hits, const void *d_states, uint64_t n,
+    void *d_out, hipStream_t st) {
+    ShadeArgs A;
+    memset(&A, 0, sizeof(A));
+    int rc = query_view(q, "a shade query", &A.S);
+    if (rc != VK_OK) return rc;
+    A.C.spp = 1u; A.C.max_depth = sp->max_depth; A.C.integrator = sp->integrator; A.C.background = sp->background;
+    A.C.bg[0] = sp->background_color[0]; A.C.bg[1] = sp->background_color[1]; A.C.bg[2] = sp->background_color[2];
+    A.rays = static_cast<const float4 *>(d_rays); A.hits = static_cast<const uint4 *>(d_hits);
+    A.states = static_cast<const uint4 *>(d_states); A.out = static_cast<uint4 *>(d_out);
+    A.n = n; A.n_materials = (uint32_t)q->host->materials.size();
+    const dim3 grid((uint32_t)((n + AOV_BLOCK - 1) / AOV_BLOCK));
+    // every scene feature, whatever the scene has: with_variant's last two cases
+    with_variant(VKF_ALL_SCENE | (sp->integrator == VK_INTEGRATOR_PDF ? (uint32_t)VKF_INTEG_PDF : 0u), [&](auto f) {
+        constexpr uint32_t FV = decltype(f)::value;
+        if constexpr ((FV & VKF_ALL_SCENE) == VKF_ALL_SCENE) hipLaunchKernelGGL(shade_hits_kernel<FV>, grid, dim3(AOV_BLOCK), 0, st, A);
+    });
+    HIP_TRY(hipGetLastError());
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_shade_hits(vk_scene *scene, const vk_shade_params *params, const vk_ray *rays, const vk_hit *hits, const vk_path_state *states,
+    uint64_t n, vk_shaded *out, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        const void *in = rays && hits && states ? static_cast<const void *>(rays) : nullptr;
+        int rc = check_batch_args(scene, params, params ? params->flags : 0u, n, in, out, {"shade", "shaded"});
+        if (rc != VK_OK) return rc;
+        const vk_radiance_params rp = shade_as_radiance(params);
+        if ((rc = check_radiance_args(scene, &rp, in, n, out)) != VK_OK) return rc;
+        if (stats_out) memset(stats_out, 0, sizeof(*stats_out));
+        if (n == 0u) return VK_OK;
+        // (the handle is read from here on)
+        if ((rc = check_integrator_for_scene(*scene->host, params->integrator)) != VK_OK) return rc;
+        const auto t0 = std::chrono::steady_clock::now();
+        vk_scene *q = first_part(scene);
+        HIP_TRY(hipSetDevice(q->device));
+        BatchLayout L;
+        L.cap = SHADE_CHUNK; L.n_streams = 4;
+        L.stream[0] = {sizeof(vk_ray), rays, nullptr}; L.stream[1] = {sizeof(vk_hit), hits, nullptr};
+        L.stream[2] = {sizeof(vk_path_state), states, nullptr}; L.stream[3] = {sizeof(vk_shaded), nullptr, out};
+        return run_batch(q, L, n, 0u, t0, stats_out,
+            [&](uint64_t, uint64_t m, uint8_t *, uint8_t *const d[4], hipStream_t st) {
+                return enqueue_shade(q, params, d[0], d[1], d[2], m, d[3], st);
+            });
     });
 }
 

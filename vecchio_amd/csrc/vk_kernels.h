@@ -2077,6 +2077,44 @@ __global__ void radiance_resolve_kernel(const long long *accum, float *out, uint
     out[i] = ((float)accum[i] * inv_scale) / (float)spp;
 }
 
+// ---- shade queries (vk_shade_hits): vk_trace.h shade_hit for (ray, hit, path state) items read from memory, one item per lane, 64
+// consecutive items per wave.  A lane reads its vk_ray, vk_hit and vk_path_state as two, four and three 16-byte loads and writes its
+// vk_shaded as six 16-byte stores.  No walk, no LDS, no atomics: item i's result depends on (scene, params, item i) alone.  Perlin noise
+// and the unit ball's rejection loop run inside the lane (no_pre_turb, no_pre_ball): the wave-cooperative forms of the path kernels
+// give the same values by construction.  Two instances: every scene feature, with and without VKF_INTEG_PDF — nothing here is a
+// traversal whose registers a narrower variant would save, and the material table is read by material index for every scene.
+struct ShadeArgs {
+    DScene S;                // a tree view (vk_api.hip aov_view); only its material, texture, light and primitive tables are read
+    RenderConsts C;          // max_depth, integrator, background
+    const float4 *rays;      // vk_ray[n]
+    const uint4 *hits;       // vk_hit[n]
+    const uint4 *states;     // vk_path_state[n]
+    uint4 *out;              // vk_shaded[n]
+    uint64_t n;
+    uint32_t n_materials;    // the description's: the bound a caller's material index is checked against
+};
+template <uint32_t F>
+__global__ __launch_bounds__(AOV_BLOCK) void shade_hits_kernel(ShadeArgs A) {
+    const uint64_t i = (uint64_t)blockIdx.x * AOV_BLOCK + threadIdx.x;
+    if (i >= A.n) return;
+    uint32_t ray[8], hit[16], st[12], w[24];
+    {
+        const float4 r0 = A.rays[i * 2u], r1 = A.rays[i * 2u + 1u];
+        ray[0] = __float_as_uint(r0.x); ray[1] = __float_as_uint(r0.y); ray[2] = __float_as_uint(r0.z); ray[3] = __float_as_uint(r0.w);
+        ray[4] = __float_as_uint(r1.x); ray[5] = __float_as_uint(r1.y); ray[6] = __float_as_uint(r1.z); ray[7] = __float_as_uint(r1.w);
+        const uint4 *h = A.hits + i * 4u, *s = A.states + i * 3u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const uint4 v = h[k]; hit[k * 4] = v.x; hit[k * 4 + 1] = v.y; hit[k * 4 + 2] = v.z; hit[k * 4 + 3] = v.w; }
+#pragma unroll
+        for (int k = 0; k < 3; k++) { const uint4 v = s[k]; st[k * 4] = v.x; st[k * 4 + 1] = v.y; st[k * 4 + 2] = v.z; st[k * 4 + 3] = v.w; }
+    }
+    const GlobalMem M{A.S.items, A.S.spheres, A.S.sphere_mat, A.S.boxes};
+    shade_hit<F, GlobalMem>(A.S, M, A.C, A.n_materials, ray, hit, st, w);
+    uint4 *out = A.out + i * 6u;
+#pragma unroll
+    for (int k = 0; k < 6; k++) out[k] = make_uint4(w[k * 4], w[k * 4 + 1], w[k * 4 + 2], w[k * 4 + 3]);
+}
+
 #ifdef VK_DEBUG_LIB
 // device math probe (tests: GPU transcendental/draw functions are bit-identical to the host's)
 __global__ void math_probe_kernel(int op, const float *a, const float *b, float *out, size_t n) {

@@ -1772,5 +1772,189 @@ VK_HD V3 probe_sample(Lane &L, const DScene &S, const Mem &M, const RenderConsts
     return radiance_sample<F, Mem>(L, S, M, C, p, u, time, tmax, g);
 }
 
+// ------------------------------------------------------------------ shade queries (vk_shade_hits, include/vecchio_amd.h)
+// One bounce of ray_color behind the walk: the segment's outcome is `miss`, or the record R whose material record is m (both unread
+// on a miss).  Reads L.wd, L.time and the path state (thr, acc, depth, rng), nothing of the walk.  Returns true when the path continues
+// with the ray (no, nd, ntime), false when it ended (L.acc is its radiance).  lobe: VK_MAT_* of the material finally sampled (behind
+// SpecDiffuse's draws), 0xFFFFFFFF on a miss.
+// A SECOND COPY of shade_core's body behind its build_record and material lookup, line for line, plus `lobe`: calling this from
+// shade_core moved the register allocation of thirteen kernels (Shade queries), so shade_core stays as it was and the
+// bit-for-bit loop tests (tests/test_shade_emu.py, tests/test_gpu_shade.py) hold the two together.  A change to one is a change to both.
+template <uint32_t F, class Mem>
+VK_HD bool shade_record(Lane &L, const DScene &S, const Mem &M, const RenderConsts &C, const Rec &R, const DMaterial *m, bool miss, V3 &no,
+    V3 &ndir, float &ntime, const PreTurb &pt, const PreBall &pb, uint32_t &lobe) {
+    lobe = 0xFFFFFFFFu;
+    uint32_t k0 = VK_MAT_LAMBERTIAN;
+    if (!miss) k0 = m->kind;
+    V3 rd = L.wd;                                             // `r` of ray_color is the world-space ray
+    // unit_vector(r.direction) is what the sky, Metal and Dielectric start from (main.rs IOW sky; material.rs:119,
+    // 155,182): one copy of its three divisions + square root for the whole wave instead of one per branch
+    V3 ud = rd;
+    {
+        if (F & VKF_SPEC_DIFFUSE) k0 = (k0 == VK_MAT_SPEC_DIFFUSE) ? (uint32_t)VK_MAT_METAL : k0;   // its children may need it
+        bool need_ud = miss ? (C.background == VK_BACKGROUND_SKY) : (k0 == VK_MAT_METAL || k0 == VK_MAT_DIELECTRIC);
+        if (need_ud) ud = unit(rd);
+    }
+    if (miss) {                                               // miss: main.rs:150-152
+        L.acc = L.acc + L.thr * background_of(C, ud);
+        return false;
+    }
+    ntime = L.time;
+    if (!(F & VKF_INTEG_PDF)) {
+        // emitted + attenuation * ray_color(scattered): Material::emitted + Material::scatter
+        V3 emitted = v3s(0.0f);
+        V3 atten;
+        bool scattered = true;
+        uint32_t kind = m->kind;
+        lobe = kind;
+        if (kind == VK_MAT_LAMBERTIAN) {                      // material.rs:85-90
+            ndir = R.n + lambertian_random(L.rng);
+            atten = material_color<F>(S, *m, R, pt);
+        } else if (kind == VK_MAT_METAL) {                    // material.rs:118-132
+            V3 reflected = reflect(ud, R.n);
+            ndir = reflected + ball_sample(L.rng, pb) * m->param;      // (no draw before it: see cooperative_ball)
+            atten = material_color<F>(S, *m, R, pt);
+            scattered = dot(ndir, R.n) > 0.0f;
+        } else if (kind == VK_MAT_DIELECTRIC) {               // material.rs:150-175
+            atten = v3s(1.0f);
+            float eta = R.front ? 1.0f / m->param : m->param;
+            float cos_theta = fminf(dot(-ud, R.n), 1.0f);
+            float sin_theta = sqrtf(1.0f - cos_theta * cos_theta);
+            if (eta * sin_theta > 1.0f) ndir = reflect(ud, R.n);
+            else {
+                float reflect_prob = schlick(cos_theta, eta);
+                if (vk::gen_f32(L.rng) < reflect_prob) ndir = reflect(ud, R.n);
+                else ndir = refract(ud, R.n, eta);
+            }
+        } else if (kind == VK_MAT_ISOTROPIC) {                // material.rs:442-446
+            ndir = ball_sample(L.rng, pb);
+            atten = material_color<F>(S, *m, R, pt);
+        } else {                                              // DiffuseLight: material.rs:215-225
+            scattered = false;
+            if (kind == VK_MAT_DIFFUSE_LIGHT && R.front) emitted = material_color<F>(S, *m, R, pt);
+        }
+        L.acc = L.acc + L.thr * emitted;
+        if (!scattered) return false;
+        L.thr = L.thr * atten;
+    } else {
+        // HEAD integrator, main.rs:131-149
+        V3 emitted = v3s(0.0f);
+        lobe = m->kind;
+        if (m->kind == VK_MAT_DIFFUSE_LIGHT) {
+            if (R.front) emitted = material_color<F>(S, *m, R, pt);
+            L.acc = L.acc + L.thr * emitted;                  // scatter_with_pdf is None: return emitted
+            return false;
+        }
+        const DMaterial *outer = m;
+        if (F & VKF_SPEC_DIFFUSE) {
+            for (int guard = 0; guard < 8 && m->kind == VK_MAT_SPEC_DIFFUSE; guard++) {   // material.rs:475-483
+                uint32_t pick = vk::gen_f32(L.rng) < m->param ? (m->ab & 0xFFFFu) : (m->ab >> 16);
+                m = &S.materials[pick];
+            }
+            lobe = m->kind;
+            if (m->kind == VK_MAT_DIFFUSE_LIGHT) { L.acc = L.acc + L.thr * emitted; return false; }
+        }
+        uint32_t kind = m->kind;
+        if (kind == VK_MAT_METAL) {                           // material.rs:134-141 (Ray::new: time 0, never absorbs)
+            V3 reflected = reflect(ud, R.n);
+            // (computed ahead only where the hit's own material is the Metal: no SpecDiffuse draw before it)
+            ndir = reflected + ball_sample(L.rng, pb) * m->param;
+            ntime = 0.0f;
+            L.thr = L.thr * material_color<F>(S, *m, R, pt);         // specular: emitted is NOT added (main.rs:134-137)
+        } else if (kind == VK_MAT_DIELECTRIC) {               // material.rs:177-206
+            float eta = R.front ? 1.0f / m->param : m->param;
+            float cos_theta = fminf(dot(-ud, R.n), 1.0f);
+            float sin_theta = sqrtf(1.0f - cos_theta * cos_theta);
+            if (eta * sin_theta > 1.0f) ndir = reflect(ud, R.n);
+            else {
+                float reflect_prob = schlick(cos_theta, eta);
+                if (vk::gen_f32(L.rng) < reflect_prob) ndir = reflect(ud, R.n);
+                else ndir = refract(ud, R.n, eta);
+            }
+        } else {                                              // Lambertian / Isotropic: material.rs:92-98,448-454
+            V3 atten = material_color<F>(S, *m, R, pt);
+            Onb uvw = onb_from_w(R.n);                        // CosinePDF::new(rec.normal)
+            // MixturePDF::generate, util.rs:177-185
+            if (vk::gen_f32(L.rng) < 0.5f) {
+                // HittablePDF::generate -> lights.random(o): Vec::random, hittable.rs:429-433
+                uint32_t li = vk::gen_index(L.rng, S.n_lights);
+                ndir = object_random(S, M, L.rng, S.lights[li], R.p);
+            } else {
+                ndir = onb_local(uvw, random_cosine_direction(L.rng));
+            }
+            // MixturePDF::value, util.rs:173-175
+            float weight = 1.0f / (float)S.n_lights;          // Vec::pdf_value, hittable.rs:420-427
+            float lsum = 0.0f;
+            for (uint32_t j = 0; j < S.n_lights; j++) lsum += weight * object_pdf_value(S, M, S.lights[j], R.p, ndir);
+            float cosv = dot(unit(ndir), uvw.w);              // CosinePDF::value, util.rs:134-142
+            float cpdf = cosv <= 0.0f ? 0.0f : cosv / PI_F;
+            float pdf = 0.5f * lsum + 0.5f * cpdf;
+            // scattering_pdf of the OUTER material (main.rs:145; SpecDiffuse forwards to its diffuse child)
+            const DMaterial *sm = outer;
+            if (F & VKF_SPEC_DIFFUSE) {
+                for (int guard = 0; guard < 8 && sm->kind == VK_MAT_SPEC_DIFFUSE; guard++) sm = &S.materials[sm->ab >> 16];
+            }
+            float spdf = 0.0f;
+            if (sm->kind == VK_MAT_LAMBERTIAN || sm->kind == VK_MAT_ISOTROPIC) {   // material.rs:100-108,456-464
+                float cs = dot(R.n, unit(ndir));
+                spdf = cs < 0.0f ? 0.0f : cs / PI_F;
+            }
+            L.acc = L.acc + L.thr * emitted;
+            L.thr = (L.thr * (atten * spdf)) / pdf;
+        }
+    }
+    L.depth += 1;
+    if (L.depth > C.max_depth) {                              // main.rs:126-128: the next call returns 0
+        L.acc = L.acc + L.thr * v3s(0.0f);                    // keeps the reference's 0*inf / 0/0 -> NaN drops
+        return false;
+    }
+    no = R.p;
+    return true;
+}
+// One bounce for a (ray, hit, path state) the caller supplies, each as its 32-bit words (vk_ray: 8, vk_hit: 16, vk_path_state: 12):
+// shade_record on a Lane that holds the ray's direction and time and the state, with a record built from the vk_hit in place of
+// build_record and the material looked up in S.materials (n_materials of them).  out: the 24 words of vk_shaded.  A hit word above 1 or
+// a material index outside the table is VK_SHADE_BAD_HIT: the state copied through, nothing drawn, and no table read by that index.
+VK_HD void shade_hit_words(uint32_t status, uint32_t lobe, bool scattered, V3 no, V3 nd, float ntime, const Lane &L, const uint32_t st[12],
+    uint32_t out[24]) {
+    out[0] = scattered ? vk::f32_bits(no.x) : 0u; out[1] = scattered ? vk::f32_bits(no.y) : 0u; out[2] = scattered ? vk::f32_bits(no.z) : 0u;
+    out[3] = scattered ? vk::f32_bits(INFINITY) : 0u;
+    out[4] = scattered ? vk::f32_bits(nd.x) : 0u; out[5] = scattered ? vk::f32_bits(nd.y) : 0u; out[6] = scattered ? vk::f32_bits(nd.z) : 0u;
+    out[7] = scattered ? vk::f32_bits(ntime) : 0u;
+    out[8] = vk::f32_bits(L.thr.x); out[9] = vk::f32_bits(L.thr.y); out[10] = vk::f32_bits(L.thr.z); out[11] = L.depth;
+    out[12] = vk::f32_bits(L.acc.x); out[13] = vk::f32_bits(L.acc.y); out[14] = vk::f32_bits(L.acc.z); out[15] = L.rng.ctr;
+    out[16] = st[8]; out[17] = st[9]; out[18] = st[10]; out[19] = st[11];
+    out[20] = status; out[21] = lobe; out[22] = 0u; out[23] = 0u;
+}
+template <uint32_t F, class Mem>
+VK_HD void shade_hit(const DScene &S, const Mem &M, const RenderConsts &C, uint32_t n_materials, const uint32_t ray[8], const uint32_t hit[16],
+    const uint32_t st[12], uint32_t out[24]) {
+    Lane L;
+    L.wd = v3(vk::bits_f32(ray[4]), vk::bits_f32(ray[5]), vk::bits_f32(ray[6])); L.time = vk::bits_f32(ray[7]);
+    L.thr = v3(vk::bits_f32(st[0]), vk::bits_f32(st[1]), vk::bits_f32(st[2])); L.depth = st[3];
+    L.acc = v3(vk::bits_f32(st[4]), vk::bits_f32(st[5]), vk::bits_f32(st[6]));
+    L.pixel = st[10]; L.sample = st[11];
+    const uint32_t is_hit = hit[9], mat = hit[11];
+    V3 no = v3s(0.0f), nd = v3s(0.0f); float ntime = 0.0f;
+    if (is_hit > 1u || (is_hit == 1u && mat >= n_materials)) {
+        L.rng.key = 0u; L.rng.ctr = st[7];                    // (the stream is not derived: nothing is drawn)
+        shade_hit_words(VK_SHADE_BAD_HIT, 0xFFFFFFFFu, false, no, nd, ntime, L, st, out);
+        return;
+    }
+    L.rng = vk::rng_for_sample((uint64_t)st[8] | ((uint64_t)st[9] << 32), L.pixel, L.sample);
+    L.rng.ctr = st[7];
+    const bool miss = is_hit == 0u;
+    Rec R;
+    R.p = v3(vk::bits_f32(hit[0]), vk::bits_f32(hit[1]), vk::bits_f32(hit[2]));
+    R.n = v3(vk::bits_f32(hit[4]), vk::bits_f32(hit[5]), vk::bits_f32(hit[6]));
+    R.u = vk::bits_f32(hit[7]); R.v = vk::bits_f32(hit[8]);
+    R.front = hit[10] != 0u; R.mat = mat;
+    const DMaterial *m = miss ? S.materials : &S.materials[mat];
+    uint32_t lobe;
+    const bool scattered = shade_record<F, Mem>(L, S, M, C, R, m, miss, no, nd, ntime, no_pre_turb(), no_pre_ball(), lobe);
+    shade_hit_words(miss ? (uint32_t)VK_SHADE_MISS : (scattered ? (uint32_t)VK_SHADE_SCATTERED : (uint32_t)VK_SHADE_ENDED), lobe, scattered,
+                    no, nd, ntime, L, st, out);
+}
+
 }  // namespace vkd
 #endif

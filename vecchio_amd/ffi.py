@@ -185,6 +185,26 @@ class RadianceParams(C.Structure):
                 ("flags", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class PathState(C.Structure):
+    """vk_path_state (vk_shade_hits): a fresh path has thr (1,1,1), depth 1, acc (0,0,0), counter 0"""
+    _fields_ = [("thr", C.c_float * 3), ("depth", C.c_uint32), ("acc", C.c_float * 3), ("counter", C.c_uint32), ("seed", C.c_uint64),
+                ("pixel", C.c_uint32), ("sample", C.c_uint32)]
+
+
+class Shaded(C.Structure):
+    """vk_shaded (vk_shade_hits)"""
+    _fields_ = [("next", Ray), ("state", PathState), ("status", C.c_uint32), ("lobe", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
+class ShadeParams(C.Structure):
+    """vk_shade_params (vk_shade_hits)"""
+    _fields_ = [("max_depth", C.c_uint32), ("integrator", C.c_uint32), ("background", C.c_uint32), ("background_color", F3),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+VK_SHADE_MISS, VK_SHADE_SCATTERED, VK_SHADE_ENDED, VK_SHADE_BAD_HIT = range(4)
+
+
 class DebugStreamKey(C.Structure):
     """vk_debug_stream_key of include/vecchio_amd_debug.h (vk_debug_trace_radiance_samples)"""
     _fields_ = [("seed", C.c_uint64), ("pixel", C.c_uint32), ("sample", C.c_uint32), ("ctr", C.c_uint32), ("_pad", C.c_uint32)]
@@ -286,7 +306,7 @@ DEVICE_SYMBOLS = [
     "vk_render_aov", "vk_render_aov_device",
     "vk_guide_default_params", "vk_render_guides", "vk_render_guides_device",
     "vk_trace_rays", "vk_trace_rays_device", "vk_trace_occluded", "vk_trace_occluded_device",
-    "vk_trace_radiance", "vk_trace_irradiance", "vk_trace_probes", "vk_probe_eval",
+    "vk_trace_radiance", "vk_trace_irradiance", "vk_trace_probes", "vk_probe_eval", "vk_shade_hits",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -375,6 +395,9 @@ def _bind(lib):
     lib.vk_trace_irradiance.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
     lib.vk_trace_probes.restype = C.c_int
     lib.vk_trace_probes.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_shade_hits.restype = C.c_int
+    lib.vk_shade_hits.argtypes = [C.c_void_p, C.POINTER(ShadeParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                  C.POINTER(Stats)]
     lib.vk_probe_eval.restype = C.c_int
     lib.vk_probe_eval.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.vk_trace_occluded_device.restype = C.c_int

@@ -108,6 +108,20 @@ pub struct vk_trace_params { pub seed: u64, pub first_index: u64, pub flags: u32
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_radiance_params { pub seed: u64, pub first_index: u64, pub samples_per_ray: u32, pub first_sample: u32, pub max_depth: u32, pub integrator: u32, pub background: u32, pub background_color: [f32; 3], pub flags: u32, pub _pad: u32 }
 
+// shade queries: the state of a path between bounces, one bounce's result, the call's parameters
+pub const VK_SHADE_MISS: u32 = 0;
+pub const VK_SHADE_SCATTERED: u32 = 1;
+pub const VK_SHADE_ENDED: u32 = 2;
+pub const VK_SHADE_BAD_HIT: u32 = 3;
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_path_state { pub thr: [f32; 3], pub depth: u32, pub acc: [f32; 3], pub counter: u32, pub seed: u64, pub pixel: u32, pub sample: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_shaded { pub next: vk_ray, pub state: vk_path_state, pub status: u32, pub lobe: u32, pub _pad: [u32; 2] }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_shade_params { pub max_depth: u32, pub integrator: u32, pub background: u32, pub background_color: [f32; 3], pub flags: u32, pub _pad: u32 }
+
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_temporal_params { pub width: u32, pub height: u32, pub max_history: u32, pub depth_tol: f32, pub normal_cos_min: f32, pub albedo_floor: f32, pub flags: u32 }
 
@@ -181,6 +195,10 @@ extern "C" {
     pub fn vk_trace_probes(scene: *mut vk_scene, params: *const vk_radiance_params, probes: *const vk_ray, n_probes: u64,
                            sh_out: *mut f32, stats_out: *mut vk_stats) -> c_int;
     pub fn vk_probe_eval(sh27: *const f32, n: *const f32, mode: u32, rgb: *mut f32) -> c_int;
+    // shade queries (additive symbols of ABI 7): one bounce of ray_color for (rays[i], hits[i], states[i]); out[i].next and out[i].state
+    // feed vk_trace_rays and the next call while out[i].status is VK_SHADE_SCATTERED
+    pub fn vk_shade_hits(scene: *mut vk_scene, params: *const vk_shade_params, rays: *const vk_ray, hits: *const vk_hit,
+                         states: *const vk_path_state, n: u64, out: *mut vk_shaded, stats_out: *mut vk_stats) -> c_int;
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

@@ -71,6 +71,11 @@ HIT_DTYPE = np.dtype([("p", "<f4", 3), ("t", "<f4"), ("normal", "<f4", 3), ("u",
 KEY_DTYPE = np.dtype([("seed", "<u8"), ("pixel", "<u4"), ("sample", "<u4"), ("ctr", "<u4"), ("_pad", "<u4")])   # vk_debug_stream_key
 assert KEY_DTYPE.itemsize == C.sizeof(ffi.DebugStreamKey) == 24
 assert RAY_DTYPE.itemsize == C.sizeof(ffi.Ray) == 32 and HIT_DTYPE.itemsize == C.sizeof(ffi.Hit) == 64
+# numpy twins of vk_path_state and vk_shaded (DeviceScene.shade_hits)
+PATH_STATE_DTYPE = np.dtype([("thr", "<f4", 3), ("depth", "<u4"), ("acc", "<f4", 3), ("counter", "<u4"), ("seed", "<u8"), ("pixel", "<u4"),
+                             ("sample", "<u4")])
+SHADED_DTYPE = np.dtype([("next", RAY_DTYPE), ("state", PATH_STATE_DTYPE), ("status", "<u4"), ("lobe", "<u4"), ("_pad", "<u4", 2)])
+assert PATH_STATE_DTYPE.itemsize == C.sizeof(ffi.PathState) == 48 and SHADED_DTYPE.itemsize == C.sizeof(ffi.Shaded) == 96
 
 
 def make_rays(origin, direction, time=0.0, tmax=np.inf):
@@ -82,6 +87,43 @@ def make_rays(origin, direction, time=0.0, tmax=np.inf):
     rays["time"] = time
     rays["tmax"] = tmax
     return rays
+
+
+def make_path_states(n, seed=0, first_index=0, sample=0):
+    """Fresh path states for DeviceScene.shade_hits(): a PATH_STATE_DTYPE array — thr 1, depth 1, acc 0, counter 0 — on the streams
+    vk_trace_radiance gives sample `sample` of rays first_index .. first_index + n - 1 of a batch: seed + 0x9E3779B97F4A7C15 * index in
+    wrapping u64, pixel 0."""
+    st = np.zeros(n, PATH_STATE_DTYPE)
+    st["thr"] = 1.0
+    st["depth"] = 1
+    mask = 0xFFFFFFFFFFFFFFFF
+    st["seed"] = np.array([((seed & mask) + 0x9E3779B97F4A7C15 * (first_index + i)) & mask for i in range(n)], np.uint64)
+    st["sample"] = sample
+    return st
+
+
+def wavefront_loop(trace, shade, rays, states, trace_seed=0, first_index=0):
+    """The loop of vk_shade_hits' contract around two callables: hits = trace(rays, seed, first_index) (a HIT_DTYPE array) and
+    out = shade(rays, hits, states) (a SHADED_DTYPE array), repeated on out["next"], out["state"] for the items whose status is
+    VK_SHADE_SCATTERED.  trace_seed, first_index: of the media's streams; bounce b traces its live items, compacted, from index
+    first_index + b * n, so that no two segments share a stream.
+    Returns (states, bounces): the final PATH_STATE_DTYPE array in the order of `rays`, and per bounce a dict with the live items'
+    indices, their rays, hits, states and results (the callables' arrays)."""
+    rays = np.ascontiguousarray(rays, RAY_DTYPE).reshape(-1).copy()
+    states = np.ascontiguousarray(states, PATH_STATE_DTYPE).reshape(-1).copy()
+    assert rays.shape == states.shape
+    n = rays.shape[0]
+    live = np.arange(n)
+    final = states.copy()
+    bounces = []
+    while live.size:
+        hits = trace(rays, trace_seed, first_index + len(bounces) * n)
+        out = shade(rays, hits, states)
+        bounces.append({"index": live, "rays": rays, "hits": hits, "states": states, "out": out})
+        final[live] = out["state"]
+        go = out["status"] == ffi.VK_SHADE_SCATTERED
+        live, rays, states = live[go], np.ascontiguousarray(out["next"][go]), np.ascontiguousarray(out["state"][go])
+    return final, bounces
 
 
 def make_points(p, normal, time=0.0, tmax=np.inf):
@@ -264,6 +306,60 @@ class DeviceScene:
         assert out.dtype == np.float32 and out.flags.c_contiguous and out.shape == (n, 3)
         self._host_batch("vk_trace_radiance", rp, stats, rays, out)
         return (out, stats) if return_stats else out
+
+    @staticmethod
+    def shade_params(max_depth=50, integrator=ffi.VK_INTEGRATOR_PDF, background=ffi.VK_BACKGROUND_SOLID, background_color=(0.0, 0.0, 0.0)):
+        """A vk_shade_params (ffi.ShadeParams)."""
+        return ffi.ShadeParams(max_depth, integrator, background, ffi.F3(*background_color), 0, 0)
+
+    def shade_hits(self, rays, hits, states, max_depth=50, integrator=ffi.VK_INTEGRATOR_PDF, background=ffi.VK_BACKGROUND_SOLID,
+                   background_color=(0.0, 0.0, 0.0), out=None, return_stats=False):
+        """One bounce of ray_color for caller-supplied (ray, hit, path state) items (vk_shade_hits): a SHADED_DTYPE array, out[i] the
+        next ray, the state after the bounce, the status (ffi.VK_SHADE_*) and the lobe sampled for (rays[i], hits[i], states[i]).  rays
+        as for trace_rays(), hits as trace_rays() returns them, states a PATH_STATE_DTYPE array (make_path_states()); host memory (the
+        call has no device-pointer variant yet)."""
+        sp = self.shade_params(max_depth, integrator, background, background_color)
+        stats = ffi.Stats()
+        rays = self._host_rays(rays)
+        n = rays.shape[0]
+        hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+        states = np.ascontiguousarray(states, PATH_STATE_DTYPE).reshape(-1)
+        assert hits.shape[0] == n and states.shape[0] == n
+        if out is None:
+            out = np.zeros(n, SHADED_DTYPE)
+        assert out.dtype == SHADED_DTYPE and out.flags.c_contiguous and out.shape == (n,)
+        ptr = lambda a: C.c_void_p(a.ctypes.data if n else None)
+        check(self._lib, self._lib.vk_shade_hits(self._h, C.byref(sp), ptr(rays), ptr(hits), ptr(states), n, ptr(out), C.byref(stats)))
+        return (out, stats) if return_stats else out
+
+    def wavefront_radiance(self, rays, seed=0, first_index=0, sample=0, max_depth=50, integrator=ffi.VK_INTEGRATOR_PDF,
+                           background=ffi.VK_BACKGROUND_SOLID, background_color=(0.0, 0.0, 0.0), return_bounces=False):
+        """The loop of vk_shade_hits' contract: trace_rays() and shade_hits() in turn from fresh path states until no path is left.  An
+        (n, 4) float32 array: [:, :3] the radiance of sample `sample` of every ray, [:, 3] its stream's final counter (bit pattern) —
+        in a scene without media what debug_radiance_samples() returns for that sample, bit for bit.  return_bounces: also the list of
+        per-bounce records of wavefront_loop(), each with the two calls' stats."""
+        rays = self._host_rays(rays)
+        stats = []
+
+        def trace(r, s, fi):
+            hits, st = self.trace_rays(r, seed=s, first_index=fi, return_stats=True)
+            stats.append({"trace": st})
+            return hits
+
+        def shade(r, h, s):
+            out, st = self.shade_hits(r, h, s, max_depth, integrator, background, background_color, return_stats=True)
+            stats[-1]["shade"] = st
+            return out
+
+        final, bounces = wavefront_loop(trace, shade, rays, make_path_states(rays.shape[0], seed, first_index, sample), seed, first_index)
+        res = np.zeros((rays.shape[0], 4), np.float32)
+        res[:, :3] = final["acc"]
+        res[:, 3] = np.ascontiguousarray(final["counter"]).view(np.float32)
+        if return_bounces:
+            for b, st in zip(bounces, stats):
+                b.update(st)
+            return res, bounces
+        return res
 
     def debug_radiance_samples(self, rays, keys=None, return_stats=False, **params):
         """Every sample of trace_radiance() (vk_debug_trace_radiance_samples, a test hook): an (n, samples_per_ray, 4) float32 array,
