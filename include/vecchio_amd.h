@@ -818,7 +818,7 @@ int vk_probe_eval(const float *sh27, const float n[3], uint32_t mode, float rgb[
  *     finite filter, bit for bit (a NaN's payload aside), and state.counter its stream's final counter.  The first call uses the ray's
  *     own tmax; next.tmax is +INFINITY: vk_trace_radiance's "first segment only" rule.
  *     With media the loop is still a valid estimator but not that sample: vk_trace_rays draws a medium's distance from its own per-ray
- *     stream, not from the path's.
+ *     stream, not from the path's.  A path batch (vk_paths_*, below) traces on the path's stream and keeps the contract in every scene.
  *   max_depth = 0 gets no special case here: a hit at depth 1 ends with acc += thr * 0 and a miss adds the background.  The contract is
  *     for max_depth >= 1; vk_trace_radiance's (0,0,0) for max_depth = 0 starts no path at all, and neither should the caller.
  *   Arguments: VK_ERR_BAD_ARG with nothing enqueued and the outputs untouched for a null scene or params, a null rays, hits, states or
@@ -854,6 +854,77 @@ typedef struct vk_shade_params {
 } vk_shade_params;
 int vk_shade_hits(vk_scene *scene, const vk_shade_params *params, const vk_ray *rays, const vk_hit *hits,
                   const vk_path_state *states, uint64_t n, vk_shaded *out, vk_stats *stats_out);
+
+/* ---- path batches: a device-resident wavefront loop (additive symbols of ABI 7) ------------------------------------------------------
+ * replaces: the caller's loop around vk_trace_rays and vk_shade_hits, which stages 336 bytes per live path and bounce through the host
+ * and compacts the survivors there.  A path batch is an opaque handle like vk_progress and vk_temporal: it owns rays, hits, states and
+ * results on the scene's device (devices[0] of a multi-device scene), runs trace, shade and compact per bounce on the null stream, as
+ * the host-pointer calls do, and moves one record of counts across the bus per bounce — more only when the caller asks (vk_paths_read,
+ * vk_paths_cull, vk_paths_results).  No function takes a stream.  Destroy a batch before its scene.
+ *   vk_paths_create: 1 <= capacity <= 2^24 paths.  Memory: 300 bytes a slot (ray 32, state 48, hit 64, vk_shaded 96, ids 2 x 4, result
+ *     48 + 4) and the compaction's tables, 300 * capacity + 24 * ceil(capacity / 256) + 40 bytes of device memory in all; a failed
+ *     allocation is VK_ERR_OOM and leaves *out untouched.
+ *   vk_paths_begin: path i has the id i, the ray rays[i] and the state states[i], 0 <= i < n <= capacity; the live paths are kept in
+ *     ascending id ("live order").  n == 0 is VK_OK with nothing live.  A handle may be begun again, which forgets the previous batch.
+ *     params is checked as vk_shade_hits checks it, in the same words, VK_ERR_UNSUPPORTED where vk_render answers it included.
+ *   vk_paths_step runs bounces until nothing is live or max_bounces of them are run (max_bounces == 0: VK_ERR_BAD_ARG).  One bounce,
+ *     over the live paths:
+ *     1. trace: vk_trace_rays' walk of the path's ray on the same tree view — tmin VK_RAY_TMIN, the ray's own tmax, vk_trace_rays' hit
+ *        record and its rules for non-finite rays — except that a ConstantMedium met on the way draws from the PATH's stream,
+ *        rng_for_sample(state.seed, state.pixel, state.sample) standing at state.counter, and state.counter advances by what was drawn:
+ *        exactly what vk_trace_radiance does inside a sample.
+ *     2. shade: vk_shade_hits' item, bit for bit, on that hit and the advanced state.
+ *     3. retire and compact: a path whose status is not VK_SHADE_SCATTERED is retired — its state after the bounce and its status are
+ *        stored under its id —, a scattered path continues with `next` and `state`.  The survivors keep their relative order (a stable
+ *        compaction on the device), so live order stays ascending by id.
+ *     info (may be NULL): traced = the rays walked, summed over the bounces run; live = the live paths after the call; missed, ended
+ *     and bad = the paths this call retired with VK_SHADE_MISS, VK_SHADE_ENDED and VK_SHADE_BAD_HIT; bounces = run by this call;
+ *     kernel_launches (five a bounce); kernel_ms between two events around each bounce's launches, summed; seconds of wall time.
+ *   THE CONTRACT, in every scene, ConstantMedium included.  Begin with the states of vk_shade_hits' contract — thr 1, depth 1, acc 0,
+ *     counter 0, seed + 0x9E3779B97F4A7C15 * (first_index + i) in wrapping u64, pixel 0, sample s — and step until nothing is live:
+ *     the acc and counter of vk_paths_results' state i are sample s of vk_trace_radiance for that ray, seed, first_index and parameters,
+ *     before that call's finite filter, bit for bit (a NaN's payload aside).  For max_depth >= 1; max_depth == 0 gets vk_shade_hits'
+ *     treatment, no special case.
+ *     In a scene without a ConstantMedium, moreover, vk_paths_read after every bounce returns byte for byte the live indices, out.next
+ *     and out.state of the same bounce of the loop around vk_trace_rays and vk_shade_hits.
+ *   vk_paths_read: the ids, rays and states of the live paths, in live order (vk_paths_info.live entries; any of the three may be NULL).
+ *   vk_paths_cull: the caller's own termination rule (Russian roulette, a budget, a region of interest).  keep holds one byte per live
+ *     path, in live order: a path with 0 is retired as VK_PATHS_CULLED with its state as it stands; a kept path's thr[c] becomes the f32
+ *     product thr[c] * scale[j] where scale (one float per live path, or NULL) is given; the kept paths are compacted stably.  The call
+ *     uploads 1 or 5 bytes per live path.  A NULL keep is VK_ERR_BAD_ARG when anything is live; with nothing live the call does nothing.
+ *   vk_paths_results: per started id (vk_paths_info.started entries; either array may be NULL) a retired path's final state and its
+ *     status — VK_SHADE_MISS, VK_SHADE_ENDED, VK_SHADE_BAD_HIT or VK_PATHS_CULLED —, a live path's current state and VK_PATHS_LIVE.
+ *   vk_paths_get_info: capacity; started = the last begin's n; live; retired[status] since the last begin ([1] stays 0); bounces run
+ *     since the last begin.  vk_paths_read, vk_paths_results and vk_paths_get_info wait for the handle's work.
+ *   Arguments: VK_ERR_BAD_ARG with nothing enqueued and the outputs untouched for a null handle, scene, params, out or info pointer, a
+ *     capacity out of range, null rays or states with n > 0, n > capacity, and vk_paths_step, vk_paths_cull or vk_paths_read before a
+ *     vk_paths_begin.
+ *   Scene state: vk_trace_rays' rules.  A call is the scene's one render in flight; it touches nothing that describes vk_render's last
+ *     frame, not the launch log, no vk_progress or vk_temporal handle, and not the ray queries' scratch of the scene.  Two handles on
+ *     one scene do not disturb each other.  vk_paths_destroy(NULL) does nothing.                                                      */
+typedef struct vk_paths vk_paths;
+enum { VK_PATHS_LIVE = 1 /* == VK_SHADE_SCATTERED */, VK_PATHS_CULLED = 4 };
+typedef struct vk_paths_info {
+    uint64_t capacity, started, live;
+    uint64_t retired[5];              /* by status; [1] stays 0 */
+    uint32_t bounces, _pad;
+} vk_paths_info;
+typedef struct vk_paths_step_info {
+    uint64_t traced;                  /* rays walked, summed over the bounces run */
+    uint64_t live;                    /* after the call */
+    uint64_t missed, ended, bad;
+    uint32_t bounces;                 /* run by this call */
+    uint32_t kernel_launches;
+    double kernel_ms, seconds;
+} vk_paths_step_info;
+int vk_paths_create(vk_scene *scene, uint64_t capacity, vk_paths **out);
+int vk_paths_begin(vk_paths *p, const vk_shade_params *params, const vk_ray *rays, const vk_path_state *states, uint64_t n);
+int vk_paths_step(vk_paths *p, uint32_t max_bounces, vk_paths_step_info *info);
+int vk_paths_read(vk_paths *p, uint32_t *ids, vk_ray *rays, vk_path_state *states);
+int vk_paths_cull(vk_paths *p, const uint8_t *keep, const float *scale);
+int vk_paths_results(vk_paths *p, vk_path_state *states, uint32_t *status);
+int vk_paths_get_info(vk_paths *p, vk_paths_info *out);
+void vk_paths_destroy(vk_paths *p);
 
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter

@@ -99,6 +99,19 @@ int vk_debug_trace_irradiance_samples(vk_scene *scene, const vk_radiance_params 
 int vk_debug_trace_probe_samples(vk_scene *scene, const vk_radiance_params *params, const vk_ray *probes, uint64_t n_probes,
                                  float *samples_out /* n * spp * 4 */, float *dirs_out /* n * spp * 4, may be NULL */,
                                  vk_stats *stats_out);
+/* exactly the compaction a bounce of vk_paths_step runs (vk_kernels.h: count, scan, move), on host arrays staged once: items[n] and
+ * ids[n] (each below n_ids) in; every output array is uploaded as the caller filled it, the three launches run, and every output array
+ * is downloaded whole, so that what the kernels left alone comes back as it went in.  rays, states and ids_out hold n entries (the
+ * survivors fill the first counts[VK_SHADE_SCATTERED] of them, in order), result_state and result_status n_ids entries (written at the
+ * ids of the retired items only), counts[s] the items of status s (a status above 4 counts as 4).  n <= 2^24, n_ids <= 2^26; n == 0:
+ * VK_OK, counts zeroed.  VK_ERR_BAD_ARG for a null pointer or an id >= n_ids.  Takes no stream.  In both libraries. */
+int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32_t *ids, uint64_t n, uint64_t n_ids, vk_ray *rays,
+                           vk_path_state *states, uint32_t *ids_out, vk_path_state *result_state, uint32_t *result_status,
+                           uint64_t counts[5]);
+/* the device milliseconds of the handle's last bounce, part by part: ms[0] trace_paths_kernel, ms[1] shade_hits_kernel, ms[2] the
+ * compaction's three launches (events vk_paths_step records between them; their sum is that bounce's share of kernel_ms).
+ * VK_ERR_BAD_ARG for a null pointer or when no bounce has run since vk_paths_begin.  Takes no stream.  In both libraries. */
+int vk_debug_paths_last_ms(vk_paths *p, double ms[3]);
 
 #ifdef __cplusplus
 }

@@ -2479,6 +2479,326 @@ int vk_shade_hits(vk_scene *scene, const vk_shade_params *params, const vk_ray *
 
 }  // extern "C"
 
+// ---- path batches (vk_paths_*): trace_paths_kernel, shade_hits_kernel (enqueue_shade, unchanged) and the compaction's three launches
+// per bounce, on the null stream, on buffers and events the handle owns: nothing of the scene handle is written but its provenance
+// tables (ensure_provenance), and nothing that describes vk_render's last frame or the ray queries' scratch is touched.
+struct vk_paths {
+    vk_scene *scene = nullptr;                      // as handed to vk_paths_create
+    uint64_t capacity = 0;
+    DeviceBuffer<uint8_t> rays, states, hits, shaded, result_state;      // vk_ray, vk_path_state, vk_hit, vk_shaded, vk_path_state [capacity]
+    DeviceBuffer<uint32_t> ids[2], result_status;   // the live paths' ids, double-buffered (the compaction is never in place); [capacity]
+    DeviceBuffer<uint32_t> wg_counts, wg_offsets;   // the compaction's tables: [5][n_wg], [n_wg]
+    DeviceBuffer<unsigned long long> counts;        // [5]: the one record a bounce sends back
+    Event ev0, ev1;                                 // around a bounce's launches
+    Event ev_t, ev_s;                               // behind its trace and behind its shade (vk_debug_paths_last_ms)
+    vk_shade_params sp{};                           // the last begin's
+    bool begun = false;
+    uint32_t cur = 0;                               // ids[cur] holds the live ids
+    uint64_t started = 0, live = 0, retired[5] = {0, 0, 0, 0, 0};
+    uint32_t bounces = 0;
+};
+
+namespace {
+
+constexpr uint64_t PATHS_MAX = 1ull << 24;
+static_assert(VK_PATHS_LIVE == VK_SHADE_SCATTERED && VK_PATHS_CULLED == PATHS_STATUSES - 1, "the statuses the compaction counts");
+
+inline uint32_t paths_wgs(uint64_t n) { return (uint32_t)((n + PATHS_T - 1) / PATHS_T); }
+
+// the compaction's three launches for A.n > 0 items (A.n_wg set here)
+int enqueue_compact(CompactArgs A, hipStream_t st) {
+    A.n_wg = paths_wgs(A.n);
+    hipLaunchKernelGGL(paths_count_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, st, A);
+    hipLaunchKernelGGL(paths_scan_kernel, dim3(1), dim3(PATHS_SCAN_T), 0, st, A);
+    hipLaunchKernelGGL(paths_move_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    return VK_OK;
+}
+
+// one launch of trace_paths_kernel for items [0, n)
+int enqueue_trace_paths(vk_scene *q, const void *d_rays, void *d_states, void *d_hits, uint64_t n, hipStream_t st) {
+    TracePathsArgs A;
+    memset(&A, 0, sizeof(A));
+    int rc = query_view(q, "a path batch", &A.S);
+    if (rc != VK_OK) return rc;
+    A.P = q->rays.prov;
+    A.rays = static_cast<const float4 *>(d_rays); A.states = static_cast<uint4 *>(d_states); A.hits = static_cast<uint4 *>(d_hits);
+    A.n = n;
+    const dim3 grid((uint32_t)((n + AOV_BLOCK - 1) / AOV_BLOCK));
+    with_walk_variant(q->host->features, [&](auto f) {
+        hipLaunchKernelGGL(trace_paths_kernel<decltype(f)::value>, grid, dim3(AOV_BLOCK), 0, st, A);
+    });
+    HIP_TRY(hipGetLastError());
+    return VK_OK;
+}
+
+// the handle's compaction of shaded[0, live) and ids[cur] into rays, states and ids[cur ^ 1]; then the counts record, read back (which
+// waits for everything enqueued): live and retired[] follow it
+CompactArgs paths_compact_args(vk_paths *p) {
+    CompactArgs A;
+    memset(&A, 0, sizeof(A));
+    A.items = reinterpret_cast<const uint4 *>(p->shaded.get()); A.ids = p->ids[p->cur]; A.n = p->live; A.n_ids = p->capacity;
+    A.rays = reinterpret_cast<uint4 *>(p->rays.get()); A.states = reinterpret_cast<uint4 *>(p->states.get()); A.ids_out = p->ids[p->cur ^ 1u];
+    A.result_state = reinterpret_cast<uint4 *>(p->result_state.get()); A.result_status = p->result_status;
+    A.wg_counts = p->wg_counts; A.wg_offsets = p->wg_offsets; A.counts = p->counts;
+    return A;
+}
+int paths_take_counts(vk_paths *p, unsigned long long c[5]) {
+    HIP_TRY(hipMemcpy(c, p->counts, PATHS_STATUSES * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    p->cur ^= 1u;
+    p->live = c[VK_SHADE_SCATTERED];
+    for (uint32_t s = 0; s < PATHS_STATUSES; s++) if (s != (uint32_t)VK_SHADE_SCATTERED) p->retired[s] += c[s];
+    return VK_OK;
+}
+
+void paths_free(vk_paths *p) {
+    (void)hipSetDevice(first_part(p->scene)->device);
+    (void)hipStreamSynchronize(nullptr);              // (a begin's last launch may still run)
+    (void)hipGetLastError();
+    delete p;
+}
+
+template <class T>
+int paths_alloc(DeviceBuffer<T> &b, size_t bytes) {
+    const hipError_t e = b.alloc(bytes);
+    if (e == hipSuccess) return VK_OK;
+    (void)hipGetLastError();
+    return fail(e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("hipMalloc (path batch): ") + hipGetErrorString(e));
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_paths_create(vk_scene *scene, uint64_t capacity, vk_paths **out) {
+    if (!scene || !out) return fail(VK_ERR_BAD_ARG, "null argument (scene or out)");
+    if (capacity < 1u || capacity > PATHS_MAX) return fail(VK_ERR_BAD_ARG, "capacity must be in 1..2^24");
+    return guarded([&]() -> int {
+        std::unique_ptr<vk_paths, void (*)(vk_paths *)> p(new vk_paths(), paths_free);
+        p->scene = scene; p->capacity = capacity;
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        const size_t n = (size_t)capacity, n_wg = paths_wgs(capacity);
+        int rc;
+        if ((rc = paths_alloc(p->rays, n * sizeof(vk_ray))) != VK_OK || (rc = paths_alloc(p->states, n * sizeof(vk_path_state))) != VK_OK ||
+            (rc = paths_alloc(p->hits, n * sizeof(vk_hit))) != VK_OK || (rc = paths_alloc(p->shaded, n * sizeof(vk_shaded))) != VK_OK ||
+            (rc = paths_alloc(p->ids[0], n * 4u)) != VK_OK || (rc = paths_alloc(p->ids[1], n * 4u)) != VK_OK ||
+            (rc = paths_alloc(p->result_state, n * sizeof(vk_path_state))) != VK_OK || (rc = paths_alloc(p->result_status, n * 4u)) != VK_OK ||
+            (rc = paths_alloc(p->wg_counts, n_wg * PATHS_STATUSES * 4u)) != VK_OK || (rc = paths_alloc(p->wg_offsets, n_wg * 4u)) != VK_OK ||
+            (rc = paths_alloc(p->counts, PATHS_STATUSES * sizeof(unsigned long long))) != VK_OK) return rc;
+        if ((rc = p->ev0.create()) != VK_OK || (rc = p->ev1.create()) != VK_OK || (rc = p->ev_t.create()) != VK_OK ||
+            (rc = p->ev_s.create()) != VK_OK) return rc;
+        *out = p.release();
+        return VK_OK;
+    });
+}
+
+int vk_paths_begin(vk_paths *p, const vk_shade_params *params, const vk_ray *rays, const vk_path_state *states, uint64_t n) {
+    return guarded([&]() -> int {
+        if (!p) return fail(VK_ERR_BAD_ARG, "null path batch");
+        const void *in = rays && states ? static_cast<const void *>(rays) : nullptr;
+        int rc = check_batch_args(p->scene, params, params ? params->flags : 0u, n, in, p, {"shade", "states"});
+        if (rc != VK_OK) return rc;
+        if (n > p->capacity) return fail(VK_ERR_BAD_ARG, "n exceeds the path batch's capacity");
+        const vk_radiance_params rp = shade_as_radiance(params);
+        if ((rc = check_radiance_args(p->scene, &rp, in, n, p)) != VK_OK) return rc;
+        if ((rc = check_integrator_for_scene(*p->scene->host, params->integrator)) != VK_OK) return rc;
+        vk_scene *q = first_part(p->scene);
+        HIP_TRY(hipSetDevice(q->device));
+        if ((rc = ensure_provenance(q)) != VK_OK) return rc;
+        if (n != 0u) {
+            HIP_TRY(hipMemcpy(p->rays, rays, (size_t)n * sizeof(vk_ray), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(p->states, states, (size_t)n * sizeof(vk_path_state), hipMemcpyHostToDevice));
+            hipLaunchKernelGGL(paths_iota_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, nullptr, p->ids[0].get(), (uint32_t)n);
+            HIP_TRY(hipGetLastError());
+        }
+        p->sp = *params; p->begun = true; p->cur = 0u; p->started = n; p->live = n; p->bounces = 0u;
+        for (uint64_t &r : p->retired) r = 0u;
+        return VK_OK;
+    });
+}
+
+int vk_paths_step(vk_paths *p, uint32_t max_bounces, vk_paths_step_info *info) {
+    return guarded([&]() -> int {
+        if (!p) return fail(VK_ERR_BAD_ARG, "null path batch");
+        if (max_bounces == 0u) return fail(VK_ERR_BAD_ARG, "max_bounces must be >= 1");
+        if (!p->begun) return fail(VK_ERR_BAD_ARG, "vk_paths_step before vk_paths_begin");
+        const auto t0 = std::chrono::steady_clock::now();
+        vk_scene *q = first_part(p->scene);
+        HIP_TRY(hipSetDevice(q->device));
+        vk_paths_step_info I;
+        memset(&I, 0, sizeof(I));
+        int rc;
+        while (p->live != 0u && I.bounces < max_bounces) {
+            const uint64_t n = p->live;
+            HIP_TRY(hipEventRecord(p->ev0, nullptr));
+            if ((rc = enqueue_trace_paths(q, p->rays, p->states, p->hits, n, nullptr)) != VK_OK) return rc;
+            HIP_TRY(hipEventRecord(p->ev_t, nullptr));
+            if ((rc = enqueue_shade(q, &p->sp, p->rays, p->hits, p->states, n, p->shaded, nullptr)) != VK_OK) return rc;
+            HIP_TRY(hipEventRecord(p->ev_s, nullptr));
+            if ((rc = enqueue_compact(paths_compact_args(p), nullptr)) != VK_OK) return rc;
+            HIP_TRY(hipEventRecord(p->ev1, nullptr));
+            unsigned long long c[5];
+            if ((rc = paths_take_counts(p, c)) != VK_OK) return rc;
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+            I.kernel_ms += (double)ms; I.kernel_launches += 5u; I.bounces++; I.traced += n;
+            I.missed += c[VK_SHADE_MISS]; I.ended += c[VK_SHADE_ENDED]; I.bad += c[VK_SHADE_BAD_HIT];
+            p->bounces++;
+        }
+        I.live = p->live;
+        I.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (info) *info = I;
+        return VK_OK;
+    });
+}
+
+int vk_paths_read(vk_paths *p, uint32_t *ids, vk_ray *rays, vk_path_state *states) {
+    return guarded([&]() -> int {
+        if (!p) return fail(VK_ERR_BAD_ARG, "null path batch");
+        if (!p->begun) return fail(VK_ERR_BAD_ARG, "vk_paths_read before vk_paths_begin");
+        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
+        const size_t n = (size_t)p->live;
+        if (n == 0u) return VK_OK;
+        if (ids) HIP_TRY(hipMemcpy(ids, p->ids[p->cur], n * 4u, hipMemcpyDeviceToHost));
+        if (rays) HIP_TRY(hipMemcpy(rays, p->rays, n * sizeof(vk_ray), hipMemcpyDeviceToHost));
+        if (states) HIP_TRY(hipMemcpy(states, p->states, n * sizeof(vk_path_state), hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+int vk_paths_cull(vk_paths *p, const uint8_t *keep, const float *scale) {
+    return guarded([&]() -> int {
+        if (!p) return fail(VK_ERR_BAD_ARG, "null path batch");
+        if (!p->begun) return fail(VK_ERR_BAD_ARG, "vk_paths_cull before vk_paths_begin");
+        const uint64_t n = p->live;
+        if (n == 0u) return VK_OK;
+        if (!keep) return fail(VK_ERR_BAD_ARG, "null keep with live paths");
+        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
+        // keep and scale ride in the hit records' buffer, which holds nothing between two bounces: 5 of its 64 bytes a path
+        uint8_t *d_keep = p->hits;
+        float *d_scale = reinterpret_cast<float *>(p->hits.get() + (((size_t)p->capacity + 15u) & ~(size_t)15u));
+        HIP_TRY(hipMemcpy(d_keep, keep, (size_t)n, hipMemcpyHostToDevice));
+        if (scale) HIP_TRY(hipMemcpy(d_scale, scale, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(paths_cull_mark_kernel, dim3(paths_wgs(n)), dim3(PATHS_T), 0, nullptr, reinterpret_cast<const uint4 *>(p->rays.get()),
+                           reinterpret_cast<const uint4 *>(p->states.get()), d_keep, scale ? d_scale : nullptr, n,
+                           reinterpret_cast<uint4 *>(p->shaded.get()));
+        HIP_TRY(hipGetLastError());
+        int rc;
+        if ((rc = enqueue_compact(paths_compact_args(p), nullptr)) != VK_OK) return rc;
+        unsigned long long c[5];
+        return paths_take_counts(p, c);
+    });
+}
+
+int vk_paths_results(vk_paths *p, vk_path_state *states, uint32_t *status) {
+    return guarded([&]() -> int {
+        if (!p) return fail(VK_ERR_BAD_ARG, "null path batch");
+        const size_t n = (size_t)p->started, live = (size_t)p->live;
+        if (n == 0u || (!states && !status)) return VK_OK;
+        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
+        if (states) HIP_TRY(hipMemcpy(states, p->result_state, n * sizeof(vk_path_state), hipMemcpyDeviceToHost));
+        if (status) HIP_TRY(hipMemcpy(status, p->result_status, n * 4u, hipMemcpyDeviceToHost));
+        if (live == 0u) return VK_OK;
+        // the live paths: their current states, under their ids
+        std::vector<uint32_t> ids(live);
+        HIP_TRY(hipMemcpy(ids.data(), p->ids[p->cur], live * 4u, hipMemcpyDeviceToHost));
+        std::vector<vk_path_state> cur;
+        if (states) {
+            cur.resize(live);
+            HIP_TRY(hipMemcpy(cur.data(), p->states, live * sizeof(vk_path_state), hipMemcpyDeviceToHost));
+        }
+        for (size_t j = 0; j < live; j++) {
+            if (ids[j] >= n) return fail(VK_ERR_BAD_ARG, "internal error: a live id outside the batch");
+            if (states) states[ids[j]] = cur[j];
+            if (status) status[ids[j]] = (uint32_t)VK_PATHS_LIVE;
+        }
+        return VK_OK;
+    });
+}
+
+int vk_paths_get_info(vk_paths *p, vk_paths_info *out) {
+    if (!p || !out) return fail(VK_ERR_BAD_ARG, "null argument (path batch or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        memset(out, 0, sizeof(*out));
+        out->capacity = p->capacity; out->started = p->started; out->live = p->live; out->bounces = p->bounces;
+        for (int s = 0; s < 5; s++) out->retired[s] = p->retired[s];
+        return VK_OK;
+    });
+}
+
+void vk_paths_destroy(vk_paths *p) {
+    if (p) paths_free(p);
+}
+
+// test hook (vecchio_amd_debug.h): the last bounce's three parts, from the events vk_paths_step records between them
+int vk_debug_paths_last_ms(vk_paths *p, double ms[3]) {
+    if (!p || !ms) return fail(VK_ERR_BAD_ARG, "null argument (path batch or ms)");
+    return guarded([&]() -> int {
+        if (p->bounces == 0u) return fail(VK_ERR_BAD_ARG, "no bounce has run since vk_paths_begin");
+        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
+        HIP_TRY(hipEventSynchronize(p->ev1));
+        float t = 0.0f, s = 0.0f, c = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&t, p->ev0, p->ev_t));
+        HIP_TRY(hipEventElapsedTime(&s, p->ev_t, p->ev_s));
+        HIP_TRY(hipEventElapsedTime(&c, p->ev_s, p->ev1));
+        ms[0] = (double)t; ms[1] = (double)s; ms[2] = (double)c;
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): the production compaction on host arrays staged once
+int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32_t *ids, uint64_t n, uint64_t n_ids, vk_ray *rays,
+    vk_path_state *states, uint32_t *ids_out, vk_path_state *result_state, uint32_t *result_status, uint64_t counts[5]) {
+    return guarded([&]() -> int {
+        if (!scene || !counts) return fail(VK_ERR_BAD_ARG, "null argument (scene or counts)");
+        if (n > PATHS_MAX || n_ids > (1ull << 26)) return fail(VK_ERR_BAD_ARG, "n exceeds 2^24 or n_ids 2^26");
+        if (n != 0u && (!items || !ids || !rays || !states || !ids_out || !result_state || !result_status))
+            return fail(VK_ERR_BAD_ARG, "null array with n > 0");
+        for (uint64_t i = 0; i < n; i++) if (ids[i] >= n_ids) return fail(VK_ERR_BAD_ARG, "an id is not below n_ids");
+        for (int s = 0; s < 5; s++) counts[s] = 0u;
+        if (n == 0u) return VK_OK;
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        const size_t m = (size_t)n, k = (size_t)n_ids, n_wg = paths_wgs(n);
+        DeviceBuffer<uint8_t> d_items, d_rays, d_states, d_rstate;
+        DeviceBuffer<uint32_t> d_ids, d_ids_out, d_rstatus, d_wc, d_wo;
+        DeviceBuffer<unsigned long long> d_counts;
+        int rc;
+        if ((rc = paths_alloc(d_items, m * sizeof(vk_shaded))) != VK_OK || (rc = paths_alloc(d_ids, m * 4u)) != VK_OK ||
+            (rc = paths_alloc(d_rays, m * sizeof(vk_ray))) != VK_OK || (rc = paths_alloc(d_states, m * sizeof(vk_path_state))) != VK_OK ||
+            (rc = paths_alloc(d_ids_out, m * 4u)) != VK_OK || (rc = paths_alloc(d_rstate, k * sizeof(vk_path_state))) != VK_OK ||
+            (rc = paths_alloc(d_rstatus, k * 4u)) != VK_OK || (rc = paths_alloc(d_wc, n_wg * PATHS_STATUSES * 4u)) != VK_OK ||
+            (rc = paths_alloc(d_wo, n_wg * 4u)) != VK_OK || (rc = paths_alloc(d_counts, PATHS_STATUSES * sizeof(unsigned long long))) != VK_OK)
+            return rc;
+        HIP_TRY(hipMemcpy(d_items, items, m * sizeof(vk_shaded), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_ids, ids, m * 4u, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_rays, rays, m * sizeof(vk_ray), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_states, states, m * sizeof(vk_path_state), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_ids_out, ids_out, m * 4u, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_rstate, result_state, k * sizeof(vk_path_state), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_rstatus, result_status, k * 4u, hipMemcpyHostToDevice));
+        CompactArgs A;
+        memset(&A, 0, sizeof(A));
+        A.items = reinterpret_cast<const uint4 *>(d_items.get()); A.ids = d_ids; A.n = n; A.n_ids = n_ids;
+        A.rays = reinterpret_cast<uint4 *>(d_rays.get()); A.states = reinterpret_cast<uint4 *>(d_states.get()); A.ids_out = d_ids_out;
+        A.result_state = reinterpret_cast<uint4 *>(d_rstate.get()); A.result_status = d_rstatus;
+        A.wg_counts = d_wc; A.wg_offsets = d_wo; A.counts = d_counts;
+        if ((rc = enqueue_compact(A, nullptr)) != VK_OK) return rc;
+        unsigned long long c[5];
+        HIP_TRY(hipMemcpy(c, d_counts, sizeof(c), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(rays, d_rays, m * sizeof(vk_ray), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(states, d_states, m * sizeof(vk_path_state), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ids_out, d_ids_out, m * 4u, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(result_state, d_rstate, k * sizeof(vk_path_state), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(result_status, d_rstatus, k * 4u, hipMemcpyDeviceToHost));
+        for (int s = 0; s < 5; s++) counts[s] = c[s];
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
 // ---- the denoiser (vk_denoise): denoise_prepare_kernel, then one level kernel per pass (vk_kernels.h), on the scene's device (devices[0]
 // of a multi-device scene), on scratch and events of its own: nothing that describes vk_render's last frame is read or written.
 namespace {

@@ -2115,6 +2115,184 @@ __global__ __launch_bounds__(AOV_BLOCK) void shade_hits_kernel(ShadeArgs A) {
     for (int k = 0; k < 6; k++) out[k] = make_uint4(w[k * 4], w[k * 4 + 1], w[k * 4 + 2], w[k * 4 + 3]);
 }
 
+// ---- path batches (vk_paths_*): a bounce is trace_paths_kernel, shade_hits_kernel and the compaction's three launches, all on buffers
+// the handle owns.
+// trace_paths_kernel: trace_rays_kernel's shape and its two variants, with vk_trace.h trace_path in place of trace_ray: a ConstantMedium
+// draws from the PATH's stream — rng_for_sample(state.seed, state.pixel, state.sample) standing at state.counter — and the counter the
+// walk leaves is stored back into the lane's own state.  The sphere-only variant can draw nothing and does not touch the states.
+struct TracePathsArgs {
+    DScene S;                // a tree view (vk_api.hip aov_view)
+    DProvenance P;
+    const float4 *rays;      // vk_ray[n]
+    uint4 *states;           // vk_path_state[n]: the counter (word 7) is rewritten when F has VKF_MEDIUM
+    uint4 *hits;             // vk_hit[n]
+    uint64_t n;
+};
+template <uint32_t F>
+__global__ __launch_bounds__(AOV_BLOCK) void trace_paths_kernel(TracePathsArgs A) {
+    const uint64_t i = (uint64_t)blockIdx.x * AOV_BLOCK + threadIdx.x;
+    if (i >= A.n) return;
+    const float4 r0 = A.rays[i * 2u], r1 = A.rays[i * 2u + 1u];
+    const uint32_t ray[8] = {__float_as_uint(r0.x), __float_as_uint(r0.y), __float_as_uint(r0.z), __float_as_uint(r0.w),
+                             __float_as_uint(r1.x), __float_as_uint(r1.y), __float_as_uint(r1.z), __float_as_uint(r1.w)};
+    uint32_t st47[4] = {0u, 0u, 0u, 0u}, st811[4] = {0u, 0u, 0u, 0u};
+    if (F & VKF_MEDIUM) {
+        const uint4 a = A.states[i * 3u + 1u], b = A.states[i * 3u + 2u];
+        st47[0] = a.x; st47[1] = a.y; st47[2] = a.z; st47[3] = a.w;
+        st811[0] = b.x; st811[1] = b.y; st811[2] = b.z; st811[3] = b.w;
+    }
+    const GlobalMem M{A.S.items, A.S.spheres, A.S.sphere_mat, A.S.boxes};
+    uint32_t w[16];
+    const uint32_t ctr = trace_path<F, GlobalMem>(A.S, M, A.P, ray, st47, st811, w);
+    if (F & VKF_MEDIUM) A.states[i * 3u + 1u] = make_uint4(st47[0], st47[1], st47[2], ctr);
+    uint4 *out = A.hits + i * 4u;
+    out[0] = make_uint4(w[0], w[1], w[2], w[3]);
+    out[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    out[2] = make_uint4(w[8], w[9], w[10], w[11]);
+    out[3] = make_uint4(w[12], w[13], w[14], w[15]);
+}
+
+// The stable compaction of a bounce's vk_shaded[n] + ids[n]: item i survives when its status is VK_SHADE_SCATTERED; the survivors'
+// next rays, states and ids go to rays[], states[] and ids_out[] in their order, a retired item's state and status to result_state[id]
+// and result_status[id].  Three launches, joined by memory alone — no workgroup waits for another, no atomics, inputs and outputs
+// distinct buffers — so the result does not depend on how the workgroups are scheduled:
+//   paths_count_kernel   one item per lane, PATHS_T items per workgroup: the workgroup's items by status (ballots, joined through LDS)
+//                        into wg_counts[status * n_wg + workgroup];
+//   paths_scan_kernel    ONE workgroup: the exclusive prefix sums of the survivors' row into wg_offsets[], PATHS_SCAN_T workgroup counts
+//                        per pass with the running total carried from pass to pass, and the five totals into counts[5];
+//   paths_move_kernel    the count pass's shape: a survivor's slot is wg_offsets[workgroup] + the survivors of the workgroup's earlier
+//                        waves (LDS) + its rank among its wave's survivors (mbcnt of the ballot's lower lanes); 16-byte accesses.
+// A status above 4 is counted with VK_PATHS_CULLED (no kernel of the library writes one; the debug hook's caller may).
+constexpr int PATHS_T = 256;             // items per workgroup of the count and move passes
+constexpr int PATHS_SCAN_T = 256;        // workgroup counts per pass of the scan
+constexpr uint32_t PATHS_STATUSES = 5u;  // VK_SHADE_MISS, SCATTERED, ENDED, BAD_HIT, VK_PATHS_CULLED
+struct CompactArgs {
+    const uint4 *items;         // vk_shaded[n]
+    const uint32_t *ids;        // [n], each below n_ids
+    uint64_t n, n_ids;
+    uint4 *rays;                // vk_ray[survivors]
+    uint4 *states;              // vk_path_state[survivors]
+    uint32_t *ids_out;          // [survivors]
+    uint4 *result_state;        // vk_path_state[n_ids]
+    uint32_t *result_status;    // [n_ids]
+    uint32_t *wg_counts;        // [PATHS_STATUSES][n_wg]
+    uint32_t *wg_offsets;       // [n_wg]
+    unsigned long long *counts; // [PATHS_STATUSES]
+    uint32_t n_wg;
+};
+__global__ __launch_bounds__(PATHS_T) void paths_count_kernel(CompactArgs A) {
+    __shared__ uint32_t wc[PATHS_T / 64][PATHS_STATUSES];
+    const uint64_t i = (uint64_t)blockIdx.x * PATHS_T + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const bool in = i < A.n;
+    uint32_t status = 0u;
+    if (in) { status = reinterpret_cast<const uint32_t *>(A.items + i * 6u)[20]; if (status >= PATHS_STATUSES) status = PATHS_STATUSES - 1u; }
+#pragma unroll
+    for (uint32_t s = 0; s < PATHS_STATUSES; s++) {
+        const unsigned long long m = __ballot(in && status == s);
+        if (lane == 0) wc[w][s] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x < PATHS_STATUSES) {
+        uint32_t t = 0;
+        for (int k = 0; k < PATHS_T / 64; k++) t += wc[k][threadIdx.x];
+        A.wg_counts[(size_t)threadIdx.x * A.n_wg + blockIdx.x] = t;
+    }
+}
+__global__ __launch_bounds__(PATHS_SCAN_T) void paths_scan_kernel(CompactArgs A) {
+    __shared__ uint32_t wt[PATHS_SCAN_T / 64];
+    __shared__ unsigned long long tot[PATHS_SCAN_T / 64][PATHS_STATUSES];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    unsigned long long mine[PATHS_STATUSES] = {0ull, 0ull, 0ull, 0ull, 0ull};
+    uint32_t running = 0u;                                       // survivors of the passes before this one
+    for (uint32_t base = 0; base < A.n_wg; base += PATHS_SCAN_T) {
+        const uint32_t b = base + threadIdx.x;
+        const bool in = b < A.n_wg;
+#pragma unroll
+        for (uint32_t s = 0; s < PATHS_STATUSES; s++) mine[s] += in ? A.wg_counts[(size_t)s * A.n_wg + b] : 0u;
+        const uint32_t v = in ? A.wg_counts[(size_t)VK_SHADE_SCATTERED * A.n_wg + b] : 0u;
+        uint32_t incl = v;                                       // inclusive scan within the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= (uint32_t)d) incl += up;
+        }
+        if (lane == 63u) wt[w] = incl;
+        __syncthreads();
+        uint32_t before = running, all = 0u;
+        for (uint32_t k = 0; k < PATHS_SCAN_T / 64; k++) { if (k < w) before += wt[k]; all += wt[k]; }
+        if (in) A.wg_offsets[b] = before + incl - v;
+        running += all;
+        __syncthreads();                                         // (wt is rewritten by the next pass)
+    }
+#pragma unroll
+    for (uint32_t s = 0; s < PATHS_STATUSES; s++) {              // the totals: a wave's sum by shuffles, the waves' through LDS
+        unsigned long long t = mine[s];
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) t += __shfl_down(t, d, 64);
+        if (lane == 0) tot[w][s] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < PATHS_STATUSES) {
+        unsigned long long t = 0ull;
+        for (int k = 0; k < PATHS_SCAN_T / 64; k++) t += tot[k][threadIdx.x];
+        A.counts[threadIdx.x] = t;
+    }
+}
+__global__ __launch_bounds__(PATHS_T) void paths_move_kernel(CompactArgs A) {
+    __shared__ uint32_t wc[PATHS_T / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * PATHS_T + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const bool in = i < A.n;
+    const uint4 *item = A.items + i * 6u;
+    uint4 tail = make_uint4(0u, 0u, 0u, 0u);                     // status, lobe, pad
+    uint32_t id = 0u;
+    if (in) { tail = item[5]; id = A.ids[i]; }
+    const bool go = in && tail.x == (uint32_t)VK_SHADE_SCATTERED;
+    const unsigned long long m = __ballot(go);
+    if (lane == 0) wc[w] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (!in) return;
+    if (go) {
+        uint32_t slot = A.wg_offsets[blockIdx.x];
+        for (uint32_t k = 0; k < w; k++) slot += wc[k];
+        slot += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (slot >= A.n) return;                                 // (cannot happen: the offsets count these very items)
+        uint4 *r = A.rays + (size_t)slot * 2u, *s = A.states + (size_t)slot * 3u;
+        r[0] = item[0]; r[1] = item[1];
+        s[0] = item[2]; s[1] = item[3]; s[2] = item[4];
+        A.ids_out[slot] = id;
+    } else if (id < A.n_ids) {
+        uint4 *s = A.result_state + (size_t)id * 3u;
+        s[0] = item[2]; s[1] = item[3]; s[2] = item[4];
+        A.result_status[id] = tail.x;
+    }
+}
+// ids[i] = i: the ids of a batch just begun
+__global__ void paths_iota_kernel(uint32_t *ids, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) ids[i] = i;
+}
+// vk_paths_cull's marking pass: live item j as a vk_shaded record the compaction reads — next = its ray, state = its state (thr times
+// scale[j], three f32 products, where scale is given and the path is kept), status VK_SHADE_SCATTERED for keep[j] != 0 and
+// VK_PATHS_CULLED otherwise (the state then as it stands), lobe 0xFFFFFFFF.  The same compaction then runs: no second move pass.
+__global__ __launch_bounds__(PATHS_T) void paths_cull_mark_kernel(const uint4 *rays, const uint4 *states, const uint8_t *keep, const float *scale,
+                                                                  uint64_t n, uint4 *items) {
+    const uint64_t i = (uint64_t)blockIdx.x * PATHS_T + threadIdx.x;
+    if (i >= n) return;
+    const bool kept = keep[i] != 0u;
+    uint4 s0 = states[i * 3u];
+    if (kept && scale) {
+        const float k = scale[i];
+        s0.x = __float_as_uint(__uint_as_float(s0.x) * k); s0.y = __float_as_uint(__uint_as_float(s0.y) * k);
+        s0.z = __float_as_uint(__uint_as_float(s0.z) * k);
+    }
+    uint4 *out = items + i * 6u;
+    out[0] = rays[i * 2u]; out[1] = rays[i * 2u + 1u];
+    out[2] = s0; out[3] = states[i * 3u + 1u]; out[4] = states[i * 3u + 2u];
+    out[5] = make_uint4(kept ? (uint32_t)VK_SHADE_SCATTERED : (uint32_t)VK_PATHS_CULLED, 0xFFFFFFFFu, 0u, 0u);
+}
+
 #ifdef VK_DEBUG_LIB
 // device math probe (tests: GPU transcendental/draw functions are bit-identical to the host's)
 __global__ void math_probe_kernel(int op, const float *a, const float *b, float *out, size_t n) {

@@ -1956,5 +1956,52 @@ VK_HD void shade_hit(const DScene &S, const Mem &M, const RenderConsts &C, uint3
                     no, nd, ntime, L, st, out);
 }
 
+// ------------------------------------------------------------------ path batches (vk_paths_*, include/vecchio_amd.h)
+// trace_ray's sibling for a segment of a PATH: the same guard, begin_segment, walk, record and provenance, but a ConstantMedium met on
+// the way draws from `rng`, the path's own stream taken where it stands — what radiance_sample's walk does inside a sample.  L.rng holds
+// the stream afterwards (untouched by a segment that is not walked).  A second copy of trace_ray's dozen lines: trace_ray itself stays
+// as it is, and with it every earlier kernel's register allocation.
+template <uint32_t F, class Mem>
+VK_HD void trace_ray_on_stream(Lane &L, const DScene &S, const Mem &M, const DProvenance &P, V3 o, V3 d, float time, float tmax, const Rng &rng,
+    RayHit &H) {
+    H.R.p = v3s(0.0f); H.R.n = v3s(0.0f); H.R.u = 0.0f; H.R.v = 0.0f; H.R.front = false; H.R.mat = 0u;
+    H.t = INFINITY; H.hit = 0u; H.object = 0u; H.medium = 0u;
+    if (F & VKF_MEDIUM) L.rng = rng;
+    if (!(tmax > T_MIN)) return;
+    L.depth = 0u; L.pixel = 0u; L.sample = 0u;
+    begin_segment<Mem::ISHIFT, fused_box<F, Mem>(), spheres_only<F>()>(L, S, o, d, time, false, tmax);
+    while (traversing(L)) traverse_step<F, Mem>(L, S, M);
+    if (L.best_prim == 0u) return;
+    build_record<F, Mem, true>(L, S, M, H.R);
+    H.t = L.T; H.hit = 1u;
+    const uint32_t k = VKD_KIND(L.best_prim), idx = VKD_INDEX(L.best_prim);
+    if ((F & VKF_MEDIUM) && k == DK_MEDIUM) { H.object = VK_MAKE_REF(VK_KIND_MEDIUM, P.medium[idx]); H.medium = 1u; }
+    else if ((F & VKF_BOX) && k == DK_BOX) H.object = VK_MAKE_REF(VK_KIND_RECT, P.box_face[idx * 6u + vk::f32_bits(L.best_aux)]);
+    else if ((F & VKF_RECT) && k == DK_RECT) H.object = VK_MAKE_REF(VK_KIND_RECT, P.rect[idx]);
+    else if ((F & VKF_MOVING) && k == DK_MOVING) H.object = VK_MAKE_REF(VK_KIND_MOVING_SPHERE, P.moving[idx]);
+    else H.object = VK_MAKE_REF(VK_KIND_SPHERE, P.sphere[idx]);
+}
+// One segment of a path batch on the words of its vk_ray (8) and of the second and third quarter of its vk_path_state (st47: acc and
+// counter, st811: seed, pixel, sample): the stream is set up the way shade_hit sets it up, the vk_hit goes to hit[16], and the return
+// value is the counter after the walk (F without VKF_MEDIUM: nothing can draw, the state is not read and st47[3] comes back).
+template <uint32_t F, class Mem>
+VK_HD uint32_t trace_path(const DScene &S, const Mem &M, const DProvenance &P, const uint32_t ray[8], const uint32_t st47[4],
+    const uint32_t st811[4], uint32_t hit[16]) {
+    Lane L;
+    RayHit H;
+    Rng g;
+    if (F & VKF_MEDIUM) {
+        g = vk::rng_for_sample((uint64_t)st811[0] | ((uint64_t)st811[1] << 32), st811[2], st811[3]);
+        g.ctr = st47[3];
+    } else {
+        g.key = 0u; g.ctr = st47[3];
+    }
+    trace_ray_on_stream<F, Mem>(L, S, M, P, v3(vk::bits_f32(ray[0]), vk::bits_f32(ray[1]), vk::bits_f32(ray[2])),
+                                v3(vk::bits_f32(ray[4]), vk::bits_f32(ray[5]), vk::bits_f32(ray[6])), vk::bits_f32(ray[7]), vk::bits_f32(ray[3]),
+                                g, H);
+    hit_words(H, hit);
+    return (F & VKF_MEDIUM) ? L.rng.ctr : st47[3];
+}
+
 }  // namespace vkd
 #endif

@@ -203,6 +203,19 @@ class ShadeParams(C.Structure):
 
 
 VK_SHADE_MISS, VK_SHADE_SCATTERED, VK_SHADE_ENDED, VK_SHADE_BAD_HIT = range(4)
+VK_PATHS_LIVE, VK_PATHS_CULLED = 1, 4
+
+
+class PathsInfo(C.Structure):
+    """vk_paths_info (vk_paths_get_info)"""
+    _fields_ = [("capacity", C.c_uint64), ("started", C.c_uint64), ("live", C.c_uint64), ("retired", C.c_uint64 * 5), ("bounces", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+class PathsStepInfo(C.Structure):
+    """vk_paths_step_info (vk_paths_step)"""
+    _fields_ = [("traced", C.c_uint64), ("live", C.c_uint64), ("missed", C.c_uint64), ("ended", C.c_uint64), ("bad", C.c_uint64),
+                ("bounces", C.c_uint32), ("kernel_launches", C.c_uint32), ("kernel_ms", C.c_double), ("seconds", C.c_double)]
 
 
 class DebugStreamKey(C.Structure):
@@ -307,6 +320,8 @@ DEVICE_SYMBOLS = [
     "vk_guide_default_params", "vk_render_guides", "vk_render_guides_device",
     "vk_trace_rays", "vk_trace_rays_device", "vk_trace_occluded", "vk_trace_occluded_device",
     "vk_trace_radiance", "vk_trace_irradiance", "vk_trace_probes", "vk_probe_eval", "vk_shade_hits",
+    "vk_paths_create", "vk_paths_begin", "vk_paths_step", "vk_paths_read", "vk_paths_cull", "vk_paths_results", "vk_paths_get_info",
+    "vk_paths_destroy",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -398,6 +413,22 @@ def _bind(lib):
     lib.vk_shade_hits.restype = C.c_int
     lib.vk_shade_hits.argtypes = [C.c_void_p, C.POINTER(ShadeParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                   C.POINTER(Stats)]
+    lib.vk_paths_create.restype = C.c_int
+    lib.vk_paths_create.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+    lib.vk_paths_begin.restype = C.c_int
+    lib.vk_paths_begin.argtypes = [C.c_void_p, C.POINTER(ShadeParams), C.c_void_p, C.c_void_p, C.c_uint64]
+    lib.vk_paths_step.restype = C.c_int
+    lib.vk_paths_step.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PathsStepInfo)]
+    lib.vk_paths_read.restype = C.c_int
+    lib.vk_paths_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_paths_cull.restype = C.c_int
+    lib.vk_paths_cull.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_paths_results.restype = C.c_int
+    lib.vk_paths_results.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_paths_get_info.restype = C.c_int
+    lib.vk_paths_get_info.argtypes = [C.c_void_p, C.POINTER(PathsInfo)]
+    lib.vk_paths_destroy.restype = None
+    lib.vk_paths_destroy.argtypes = [C.c_void_p]
     lib.vk_probe_eval.restype = C.c_int
     lib.vk_probe_eval.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.vk_trace_occluded_device.restype = C.c_int
@@ -443,6 +474,11 @@ def _bind(lib):
     lib.vk_debug_trace_probe_samples.restype = C.c_int
     lib.vk_debug_trace_probe_samples.argtypes = [C.c_void_p, C.POINTER(RadianceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                  C.POINTER(Stats)]
+    lib.vk_debug_compact_paths.restype = C.c_int
+    lib.vk_debug_compact_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5 + \
+        [C.POINTER(C.c_uint64 * 5)]
+    lib.vk_debug_paths_last_ms.restype = C.c_int
+    lib.vk_debug_paths_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 3)]
     lib.vk_debug_trace_occluded_device.restype = C.c_int
     lib.vk_debug_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_uint32, C.c_uint32]

@@ -122,6 +122,15 @@ pub struct vk_shaded { pub next: vk_ray, pub state: vk_path_state, pub status: u
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_shade_params { pub max_depth: u32, pub integrator: u32, pub background: u32, pub background_color: [f32; 3], pub flags: u32, pub _pad: u32 }
 
+// path batches: what a handle holds, and what one vk_paths_step did
+pub const VK_PATHS_LIVE: u32 = 1;
+pub const VK_PATHS_CULLED: u32 = 4;
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_paths_info { pub capacity: u64, pub started: u64, pub live: u64, pub retired: [u64; 5], pub bounces: u32, pub _pad: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_paths_step_info { pub traced: u64, pub live: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
+
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_temporal_params { pub width: u32, pub height: u32, pub max_history: u32, pub depth_tol: f32, pub normal_cos_min: f32, pub albedo_floor: f32, pub flags: u32 }
 
@@ -131,6 +140,7 @@ pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, 
 #[repr(C)] pub struct vk_scene { _private: [u8; 0] }
 #[repr(C)] pub struct vk_progress { _private: [u8; 0] }
 #[repr(C)] pub struct vk_temporal { _private: [u8; 0] }
+#[repr(C)] pub struct vk_paths { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -199,6 +209,16 @@ extern "C" {
     // feed vk_trace_rays and the next call while out[i].status is VK_SHADE_SCATTERED
     pub fn vk_shade_hits(scene: *mut vk_scene, params: *const vk_shade_params, rays: *const vk_ray, hits: *const vk_hit,
                          states: *const vk_path_state, n: u64, out: *mut vk_shaded, stats_out: *mut vk_stats) -> c_int;
+    // path batches (additive symbols of ABI 7): the loop around trace and shade on the device, with a stable compaction per bounce;
+    // begin, then step until vk_paths_step_info.live is 0, then results; read and cull between steps; destroy before the scene
+    pub fn vk_paths_create(scene: *mut vk_scene, capacity: u64, out: *mut *mut vk_paths) -> c_int;
+    pub fn vk_paths_begin(p: *mut vk_paths, params: *const vk_shade_params, rays: *const vk_ray, states: *const vk_path_state, n: u64) -> c_int;
+    pub fn vk_paths_step(p: *mut vk_paths, max_bounces: u32, info: *mut vk_paths_step_info) -> c_int;
+    pub fn vk_paths_read(p: *mut vk_paths, ids: *mut u32, rays: *mut vk_ray, states: *mut vk_path_state) -> c_int;
+    pub fn vk_paths_cull(p: *mut vk_paths, keep: *const u8, scale: *const f32) -> c_int;
+    pub fn vk_paths_results(p: *mut vk_paths, states: *mut vk_path_state, status: *mut u32) -> c_int;
+    pub fn vk_paths_get_info(p: *mut vk_paths, out: *mut vk_paths_info) -> c_int;
+    pub fn vk_paths_destroy(p: *mut vk_paths);
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

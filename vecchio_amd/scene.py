@@ -578,6 +578,29 @@ class DeviceScene:
             setattr(tp, k, v)
         return Temporal(self, tp)
 
+    def paths(self, capacity):
+        """A path batch of up to `capacity` paths on this scene (vk_paths_create): the loop of wavefront_radiance() on the device, with
+        a stable compaction of the survivors per bounce.  Use as a context manager, or close() it before the scene."""
+        return PathBatch(self, capacity)
+
+    def debug_compact_paths(self, items, ids, n_ids, canary=0xA5):
+        """The compaction of a path batch's bounce on host arrays (vk_debug_compact_paths, a test hook): items a SHADED_DTYPE array, ids
+        their uint32 ids (each below n_ids).  Every output is prefilled with the byte `canary`.  Returns (rays, states, ids_out — n
+        entries each, the survivors first —, result_state, result_status — n_ids entries —, counts by status)."""
+        items = np.ascontiguousarray(items, SHADED_DTYPE).reshape(-1)
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        n = items.shape[0]
+        assert ids.shape[0] == n
+        outs = [np.zeros(n, RAY_DTYPE), np.zeros(n, PATH_STATE_DTYPE), np.zeros(n, np.uint32), np.zeros(n_ids, PATH_STATE_DTYPE),
+                np.zeros(n_ids, np.uint32)]
+        for a in outs:
+            a.view(np.uint8)[:] = canary
+        counts = (C.c_uint64 * 5)()
+        ptr = lambda a: C.c_void_p(a.ctypes.data if a.size else None)
+        check(self._lib, self._lib.vk_debug_compact_paths(self._h, ptr(items), ptr(ids), n, n_ids, *[C.c_void_p(a.ctypes.data) for a in outs],
+                                                          C.byref(counts)))
+        return (*outs, np.array(list(counts), np.uint64))
+
     def to_color_device(self, d_rgb, width, height, d_rgb8, stream=None):
         check(self._lib, self._lib.vk_to_color_device(self._h, C.c_void_p(d_rgb), width, height, C.c_void_p(d_rgb8), C.c_void_p(stream or 0)))
 
@@ -736,6 +759,108 @@ class Temporal:
     def close(self):
         if self._h:
             self._lib.vk_temporal_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PathBatch:
+    """vk_paths handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed): begin() a batch of rays and
+    path states, step() it bounce by bounce on the device, read() or cull() the live paths between steps, results() at any time."""
+
+    def __init__(self, scene, capacity):
+        self._lib = scene._lib
+        self._scene = scene
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_paths_create(scene._h, capacity, C.byref(h)))
+        self._h = h
+
+    def begin(self, rays, states, max_depth=50, integrator=ffi.VK_INTEGRATOR_PDF, background=ffi.VK_BACKGROUND_SOLID,
+              background_color=(0.0, 0.0, 0.0)):
+        """Start a batch (vk_paths_begin): path i has the id i, rays[i] (a RAY_DTYPE array) and states[i] (a PATH_STATE_DTYPE array,
+        make_path_states()); the keywords are DeviceScene.shade_params()'s.  Forgets the handle's previous batch."""
+        sp = DeviceScene.shade_params(max_depth, integrator, background, background_color)
+        rays = DeviceScene._host_rays(rays)
+        states = np.ascontiguousarray(states, PATH_STATE_DTYPE).reshape(-1)
+        n = rays.shape[0]
+        assert states.shape[0] == n
+        ptr = lambda a: C.c_void_p(a.ctypes.data if n else None)
+        check(self._lib, self._lib.vk_paths_begin(self._h, C.byref(sp), ptr(rays), ptr(states), n))
+
+    def step(self, max_bounces=1):
+        """Run bounces until nothing is live or max_bounces are run (vk_paths_step): the call's ffi.PathsStepInfo."""
+        info = ffi.PathsStepInfo()
+        check(self._lib, self._lib.vk_paths_step(self._h, max_bounces, C.byref(info)))
+        return info
+
+    def run(self):
+        """step() until nothing is live: the list of the calls' ffi.PathsStepInfo, one bounce each."""
+        out = []
+        while self.info().live:
+            out.append(self.step(1))
+        return out
+
+    def read(self):
+        """The live paths in live order (vk_paths_read): (ids uint32, rays RAY_DTYPE, states PATH_STATE_DTYPE)."""
+        n = int(self.info().live)
+        ids, rays, states = np.zeros(n, np.uint32), np.zeros(n, RAY_DTYPE), np.zeros(n, PATH_STATE_DTYPE)
+        ptr = lambda a: C.c_void_p(a.ctypes.data if n else None)
+        check(self._lib, self._lib.vk_paths_read(self._h, ptr(ids), ptr(rays), ptr(states)))
+        return ids, rays, states
+
+    def cull(self, keep, scale=None):
+        """Retire the live paths whose keep byte is 0 as ffi.VK_PATHS_CULLED and multiply the kept ones' throughput by scale (one float
+        per live path) where that is given (vk_paths_cull); both in live order."""
+        n = int(self.info().live)
+        keep = np.ascontiguousarray(keep, np.uint8).reshape(-1)
+        assert keep.shape[0] == n
+        if scale is not None:
+            scale = np.ascontiguousarray(scale, np.float32).reshape(-1)
+            assert scale.shape[0] == n
+        check(self._lib, self._lib.vk_paths_cull(self._h, C.c_void_p(keep.ctypes.data if n else None),
+                                                 C.c_void_p(scale.ctypes.data) if scale is not None and n else None))
+
+    def results(self):
+        """Per started id the final (or, for a live path, current) state and the status (vk_paths_results): (PATH_STATE_DTYPE array,
+        uint32 array of ffi.VK_SHADE_* / ffi.VK_PATHS_*)."""
+        n = int(self.info().started)
+        states, status = np.zeros(n, PATH_STATE_DTYPE), np.zeros(n, np.uint32)
+        ptr = lambda a: C.c_void_p(a.ctypes.data if n else None)
+        check(self._lib, self._lib.vk_paths_results(self._h, ptr(states), ptr(status)))
+        return states, status
+
+    def radiance(self):
+        """results() in debug_radiance_samples()' form: an (n, 4) float32 array, [:, :3] acc and [:, 3] the counter's bit pattern"""
+        states, _ = self.results()
+        res = np.zeros((states.shape[0], 4), np.float32)
+        res[:, :3] = states["acc"]
+        res[:, 3] = np.ascontiguousarray(states["counter"]).view(np.float32)
+        return res
+
+    def last_ms(self):
+        """(trace, shade, compaction) device milliseconds of the last bounce (vk_debug_paths_last_ms, a test hook)"""
+        ms = (C.c_double * 3)()
+        check(self._lib, self._lib.vk_debug_paths_last_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
+    def info(self):
+        inf = ffi.PathsInfo()
+        check(self._lib, self._lib.vk_paths_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def close(self):
+        if self._h:
+            self._lib.vk_paths_destroy(self._h)
             self._h = None
 
     def __enter__(self):
