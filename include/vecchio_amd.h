@@ -926,6 +926,71 @@ int vk_paths_results(vk_paths *p, vk_path_state *states, uint32_t *status);
 int vk_paths_get_info(vk_paths *p, vk_paths_info *out);
 void vk_paths_destroy(vk_paths *p);
 
+/* ---- films: camera paths and frame sums for path batches, on the device (additive symbols of ABI 7) ----------------------------------
+ * replaces: the caller's own camera (Camera::get_ray, the lens disk's rejection loop and the stream's counter behind them, restated bit
+ * for bit), the 80 bytes per path vk_paths_begin uploads, the 52 bytes per path vk_paths_results downloads, and the finite filter, clamp
+ * and fixed-point sums redone on the host.  A film is an opaque handle like a path batch: a frame's fixed-point accumulators on the
+ * scene's device (devices[0] of a multi-device scene) together with its camera and render parameters.  It EMITS camera paths into a path
+ * batch and DEPOSITS a finished batch into the frame, both on the device, on the null stream.  No function takes a stream.  Destroy a
+ * film before its scene.
+ *   vk_film_create: params is checked as vk_render checks it, in the same words, VK_ERR_UNSUPPORTED where vk_render answers it included.
+ *     Refused besides, each VK_ERR_BAD_ARG: a tile partition other than the whole image (tile_world > 1), output_format other than
+ *     VK_OUTPUT_F32, max_depth == 0 (vk_shade_hits' contract starts no path there), width * height > 2^26.  Memory: width * height * 24
+ *     bytes of sums and one counter record of 32 bytes (and, from the first vk_film_resolve on, width * height * 12 bytes for the frame on
+ *     its way to the host); a failed allocation is VK_ERR_OOM and leaves *out untouched.  The sums start at zero.
+ *   vk_film_emit begins `batch` as vk_paths_begin does, forgetting its previous batch, with n = win.width * win.height * win.n_samples
+ *     paths generated on the device: nothing crosses the bus.  Path id = ((y - y0) * win.width + (x - x0)) * n_samples + k is sample
+ *     s = first_sample + k of pixel (x, y) of the film's frame: its ray is the render kernel's — the stream rng_for_sample(params.seed,
+ *     y * width + x, s), the draws for u, v, the lens disk and the time, (float)(width - 1) and (float)(height - 1) of the FILM's frame —
+ *     as origin, tmax = +INFINITY, the unnormalised direction and the time; its state is thr (1,1,1), depth 1, acc 0, seed = params.seed,
+ *     pixel = y * width + x, sample = s, and counter = the stream's counter behind those draws.  The batch's shade parameters are the
+ *     film's: max_depth, integrator, background.
+ *     VK_ERR_BAD_ARG with nothing enqueued and the batch left as it was: a null pointer, a batch of another scene, an empty window, a
+ *     window outside the frame, first_sample + n_samples > samples_per_pixel, n above the batch's capacity.
+ *   vk_film_deposit adds the batch's retired paths to the film.  For every started id whose status is VK_SHADE_MISS, VK_SHADE_ENDED or
+ *     VK_PATHS_CULLED the pixel is state.pixel of the RESULT, not the id — a batch begun by vk_paths_begin with the caller's own rays (a
+ *     fisheye camera, a jitter of one's own) deposits too: the caller sets state.pixel.  pixel >= width * height: `skipped`, counted, no
+ *     memory touched by that index.  An acc with a non-finite component: `dropped`, adds nothing (main.rs:192-194).  Otherwise the render
+ *     kernel's conversion — 2^-26 fixed point, truncated; a sample with a component beyond 31.999 in magnitude is first clamped to
+ *     +-min(1e10, 1.3e11 / samples_per_pixel) and, where that changed it, counted in `clamped` — and three additions to the pixel's 64-bit
+ *     sums.  VK_SHADE_BAD_HIT results are `skipped`.
+ *     VK_ERR_BAD_ARG: a batch with live paths (step or cull them first), a batch never begun, a batch of another scene, a batch already
+ *     deposited since its last vk_paths_begin or vk_film_emit.  Emitting the same (pixel, sample) twice is the caller's error and is not
+ *     detected.
+ *   vk_film_resolve: rgb_out[(y * width + x) * 3 + c] = ((float)sum * 2^-26) / (float)n, vk_render's own arithmetic, into a host buffer in
+ *     vk_render's f32 layout (y = 0 the bottom row).  n >= 1.  The call waits; it does not clear the sums.
+ *   vk_film_reset zeroes the sums and the counters; cam may be NULL to keep the camera, otherwise it replaces it (checked as at create),
+ *     as in vk_progress_reset.
+ *   vk_film_get_info waits and returns the counters since the last reset: emitted = paths emitted, deposited + dropped + skipped = results
+ *     read by the deposits, clamped (a part of deposited), deposits = calls.
+ *   THE CONTRACT, on every scene whose vk_render is proven to equal the tree as handed over (everything but VK_SCENE_EMPIRICAL_TREES):
+ *     1. after vk_film_emit and vk_paths_step until nothing is live, the acc and counter of vk_paths_results' state for an id are that
+ *        sample of vk_render (vk_debug_render_samples' entry [pixel * samples_per_pixel + s]), bit for bit, a NaN's payload aside;
+ *     2. once every (pixel, sample) with sample < samples_per_pixel has been emitted, finished and deposited exactly once — window shapes,
+ *        batch sizes and order are free — vk_film_resolve(film, samples_per_pixel, out) is vk_render's f32 frame for the same camera
+ *        and parameters BIT FOR BIT, and `clamped` is that call's clamped_samples;
+ *     3. for n < samples_per_pixel deposited samples per pixel the image is vk_render's at n samples per pixel wherever no sample lies
+ *        beyond either clamp.
+ *   Scene state: the path batch's rules.  A call is the scene's one render in flight; it touches nothing that describes vk_render's last
+ *     frame, not the launch log, no vk_progress or vk_temporal handle, and not the ray queries' scratch.  Two films and two batches on
+ *     one scene do not disturb each other.  vk_film_destroy(NULL) does nothing.                                                       */
+typedef struct vk_film vk_film;
+typedef struct vk_film_window {          /* 24 bytes */
+    uint32_t x0, y0, width, height;      /* a pixel rectangle inside the film's frame, y = 0 the bottom row */
+    uint32_t first_sample, n_samples;    /* samples [first_sample, first_sample + n_samples) of each of its pixels */
+} vk_film_window;
+typedef struct vk_film_info {            /* 64 bytes */
+    uint32_t width, height, samples_per_pixel, _pad;
+    uint64_t emitted, deposited, dropped, clamped, skipped, deposits;
+} vk_film_info;
+int vk_film_create(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, vk_film **out);
+int vk_film_emit(vk_film *film, vk_paths *batch, const vk_film_window *win);
+int vk_film_deposit(vk_film *film, vk_paths *batch);
+int vk_film_resolve(vk_film *film, uint32_t n, float *rgb_out);
+int vk_film_reset(vk_film *film, const vk_camera *cam);
+int vk_film_get_info(vk_film *film, vk_film_info *out);
+void vk_film_destroy(vk_film *film);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

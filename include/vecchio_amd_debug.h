@@ -113,6 +113,18 @@ int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32
  * VK_ERR_BAD_ARG for a null pointer or when no bounce has run since vk_paths_begin.  Takes no stream.  In both libraries. */
 int vk_debug_paths_last_ms(vk_paths *p, double ms[3]);
 
+/* a film's raw sums: width * height * 3 two's-complement 64-bit values in 2^-26 units, [(y * width + x) * 3 + c].  Waits.
+ * VK_ERR_BAD_ARG for a null pointer.  Takes no stream.  In both libraries. */
+int vk_debug_film_sums(vk_film *film, long long *sums);
+/* the device milliseconds of the film's last vk_film_emit (ms[0]), vk_film_deposit (ms[1]) and vk_film_resolve (ms[2], the kernel without
+ * the copy to the host), between two events around each; 0 for one that has not run.  Waits for those.  Takes no stream.  In both
+ * libraries. */
+int vk_debug_film_last_ms(vk_film *film, double ms[3]);
+/* the form of film_deposit_kernel (vk_kernels.h) from the film's next vk_film_deposit on: PLAIN = three atomics per depositing lane; RUNS =
+ * a wave's neighbouring lanes of one pixel summed first, the head lane of each run issuing the atomics.  Both give the same bytes.
+ * VK_ERR_BAD_ARG for a null film or another form.  In both libraries. */
+enum { VK_DEBUG_FILM_DEPOSIT_PLAIN = 0, VK_DEBUG_FILM_DEPOSIT_RUNS = 1 };
+int vk_debug_film_deposit_form(vk_film *film, int form);
 #ifdef __cplusplus
 }
 #endif

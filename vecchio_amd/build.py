@@ -198,7 +198,7 @@ def build_emu(force=False):
     srcs = [os.path.join(edir, "emu.cpp"), os.path.join(edir, "emu_guides.cpp"), os.path.join(edir, "emu_rays.cpp"),
             os.path.join(edir, "emu_occlusion.cpp"), os.path.join(edir, "emu_radiance.cpp"),
             os.path.join(edir, "emu_irradiance.cpp"), os.path.join(edir, "emu_probes.cpp"), os.path.join(edir, "emu_shade.cpp"),
-            os.path.join(edir, "emu_paths.cpp"), os.path.join(CSRC, "vk_linearize.cpp")]
+            os.path.join(edir, "emu_paths.cpp"), os.path.join(edir, "emu_film.cpp"), os.path.join(CSRC, "vk_linearize.cpp")]
     # (the tool's own headers: whichever are there)
     deps = srcs + sorted(os.path.join(edir, f) for f in os.listdir(edir) if f.endswith(".h")) + \
         [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h")] + \

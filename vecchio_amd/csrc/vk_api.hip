@@ -2493,6 +2493,7 @@ struct vk_paths {
     Event ev_t, ev_s;                               // behind its trace and behind its shade (vk_debug_paths_last_ms)
     vk_shade_params sp{};                           // the last begin's
     bool begun = false;
+    bool deposited = false;                         // vk_film_deposit has taken this batch (cleared by vk_paths_begin and vk_film_emit)
     uint32_t cur = 0;                               // ids[cur] holds the live ids
     uint64_t started = 0, live = 0, retired[5] = {0, 0, 0, 0, 0};
     uint32_t bounces = 0;
@@ -2611,7 +2612,7 @@ int vk_paths_begin(vk_paths *p, const vk_shade_params *params, const vk_ray *ray
             hipLaunchKernelGGL(paths_iota_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, nullptr, p->ids[0].get(), (uint32_t)n);
             HIP_TRY(hipGetLastError());
         }
-        p->sp = *params; p->begun = true; p->cur = 0u; p->started = n; p->live = n; p->bounces = 0u;
+        p->sp = *params; p->begun = true; p->deposited = false; p->cur = 0u; p->started = n; p->live = n; p->bounces = 0u;
         for (uint64_t &r : p->retired) r = 0u;
         return VK_OK;
     });
@@ -2795,6 +2796,234 @@ int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32
         for (int s = 0; s < 5; s++) counts[s] = c[s];
         return VK_OK;
     });
+}
+
+}  // extern "C"
+
+// ---- films (vk_film_*): a frame's fixed-point sums on the scene's device (devices[0] of a multi-device scene) with its camera and render
+// parameters.  film_emit_kernel fills a path batch with camera paths, film_deposit_kernel adds a finished batch to the sums, resolve_kernel
+// (vk_render's own, on the whole-image partition) divides; all on the null stream, on buffers and events the handle owns.  Of the batch
+// an emit writes what vk_paths_begin writes; a deposit reads its results and sets its `deposited` flag.
+struct vk_film {
+    vk_scene *scene = nullptr;                      // as handed to vk_film_create
+    vk_camera cam;
+    vk_render_params params;
+    DeviceBuffer<unsigned long long> sums;          // [width * height * 3], two's complement
+    DeviceBuffer<unsigned long long> counters;      // the counter record: deposited, dropped, clamped, skipped
+    DeviceBuffer<float> out;                        // the resolved frame on its way to the host (allocated by the first vk_film_resolve)
+    Event ev[6];                                    // around the last emit, deposit and resolve
+    bool timed[3] = {false, false, false};
+    uint64_t emitted = 0, deposits = 0;
+    bool runs = FILM_DEPOSIT_RUNS;                  // the deposit's form (vk_debug_film_deposit_form)
+};
+
+namespace {
+
+constexpr uint64_t FILM_MAX_PIXELS = 1ull << 26;
+
+void film_free(vk_film *f) {
+    (void)hipSetDevice(first_part(f->scene)->device);
+    (void)hipStreamSynchronize(nullptr);              // (a deposit may still run)
+    (void)hipGetLastError();
+    delete f;
+}
+
+int film_zero(vk_film *f) {
+    HIP_TRY(hipMemsetAsync(f->sums, 0, (size_t)f->params.width * f->params.height * 3u * sizeof(unsigned long long), nullptr));
+    HIP_TRY(hipMemsetAsync(f->counters, 0, 4u * sizeof(unsigned long long), nullptr));
+    f->emitted = 0u; f->deposits = 0u;
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_film_create(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, vk_film **out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    int rc = check_render_args(scene, cam, params);
+    if (rc != VK_OK) return rc;
+    if ((params->tile_world ? params->tile_world : 1u) > 1u) return fail(VK_ERR_BAD_ARG, "a film holds the whole image (tile_world must be 0 or 1)");
+    if (params->output_format != VK_OUTPUT_F32) return fail(VK_ERR_BAD_ARG, "a film is f32 only (output_format must be VK_OUTPUT_F32)");
+    if (params->max_depth == 0u) return fail(VK_ERR_BAD_ARG, "max_depth must be >= 1 (vk_shade_hits' contract starts no path at max_depth 0)");
+    if ((uint64_t)params->width * params->height > FILM_MAX_PIXELS) return fail(VK_ERR_BAD_ARG, "width * height exceeds 2^26");
+    return guarded([&]() -> int {
+        std::unique_ptr<vk_film, void (*)(vk_film *)> f(new vk_film(), film_free);
+        f->scene = scene; f->cam = *cam; f->params = *params;
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        int r;
+        if ((r = paths_alloc(f->sums, (size_t)params->width * params->height * 3u * sizeof(unsigned long long))) != VK_OK ||
+            (r = paths_alloc(f->counters, 4u * sizeof(unsigned long long))) != VK_OK) return r;
+        for (Event &e : f->ev) if ((r = e.create()) != VK_OK) return r;
+        if ((r = film_zero(f.get())) != VK_OK) return r;
+        *out = f.release();
+        return VK_OK;
+    });
+}
+
+int vk_film_emit(vk_film *film, vk_paths *batch, const vk_film_window *win) {
+    return guarded([&]() -> int {
+        if (!film || !batch || !win) return fail(VK_ERR_BAD_ARG, "null argument (film, path batch or window)");
+        if (batch->scene != film->scene) return fail(VK_ERR_BAD_ARG, "the path batch belongs to another scene than the film");
+        const vk_render_params &P = film->params;
+        if (win->width == 0u || win->height == 0u || win->n_samples == 0u) return fail(VK_ERR_BAD_ARG, "empty window");
+        if ((uint64_t)win->x0 + win->width > P.width || (uint64_t)win->y0 + win->height > P.height)
+            return fail(VK_ERR_BAD_ARG, "the window lies outside the film's frame");
+        if ((uint64_t)win->first_sample + win->n_samples > P.samples_per_pixel)
+            return fail(VK_ERR_BAD_ARG, "first_sample + n_samples exceeds the film's samples_per_pixel");
+        // (width * height <= 2^26 and n_samples <= 2^26: the product fits 64 bits)
+        const uint64_t n = (uint64_t)win->width * win->height * win->n_samples;
+        if (n > batch->capacity) return fail(VK_ERR_BAD_ARG, "the window's paths exceed the path batch's capacity");
+        vk_scene *q = first_part(film->scene);
+        HIP_TRY(hipSetDevice(q->device));
+        int rc = ensure_provenance(q);
+        if (rc != VK_OK) return rc;
+        FilmEmitArgs A;
+        memset(&A, 0, sizeof(A));
+        A.C.cam = film->cam;
+        A.C.width = P.width; A.C.height = P.height; A.C.spp = P.samples_per_pixel; A.C.max_depth = P.max_depth;
+        A.C.seed = P.seed; A.C.integrator = P.integrator; A.C.background = P.background;
+        A.C.bg[0] = P.background_color[0]; A.C.bg[1] = P.background_color[1]; A.C.bg[2] = P.background_color[2];
+        A.rays = reinterpret_cast<uint4 *>(batch->rays.get()); A.states = reinterpret_cast<uint4 *>(batch->states.get());
+        A.ids = batch->ids[0];
+        A.x0 = win->x0; A.y0 = win->y0; A.win_width = win->width; A.first_sample = win->first_sample; A.n_samples = win->n_samples;
+        A.n = (uint32_t)n;                           // (capacity <= 2^24)
+        HIP_TRY(hipEventRecord(film->ev[0], nullptr));
+        hipLaunchKernelGGL(film_emit_kernel, dim3((uint32_t)((n + FILM_T - 1) / FILM_T)), dim3(FILM_T), 0, nullptr, A);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(film->ev[1], nullptr));
+        film->timed[0] = true;
+        film->emitted += n;
+        vk_shade_params sp;
+        memset(&sp, 0, sizeof(sp));
+        sp.max_depth = P.max_depth; sp.integrator = P.integrator; sp.background = P.background;
+        sp.background_color[0] = P.background_color[0]; sp.background_color[1] = P.background_color[1]; sp.background_color[2] = P.background_color[2];
+        batch->sp = sp; batch->begun = true; batch->deposited = false; batch->cur = 0u; batch->started = n; batch->live = n; batch->bounces = 0u;
+        for (uint64_t &r : batch->retired) r = 0u;
+        return VK_OK;
+    });
+}
+
+int vk_film_deposit(vk_film *film, vk_paths *batch) {
+    return guarded([&]() -> int {
+        if (!film || !batch) return fail(VK_ERR_BAD_ARG, "null argument (film or path batch)");
+        if (batch->scene != film->scene) return fail(VK_ERR_BAD_ARG, "the path batch belongs to another scene than the film");
+        if (!batch->begun) return fail(VK_ERR_BAD_ARG, "vk_film_deposit before vk_paths_begin or vk_film_emit");
+        if (batch->live != 0u) return fail(VK_ERR_BAD_ARG, "the path batch has live paths (step or cull them first)");
+        if (batch->deposited) return fail(VK_ERR_BAD_ARG, "the path batch has been deposited since its last begin or emit");
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        const uint64_t n = batch->started;
+        HIP_TRY(hipEventRecord(film->ev[2], nullptr));
+        if (n != 0u) {
+            FilmDepositArgs A;
+            memset(&A, 0, sizeof(A));
+            A.result_state = reinterpret_cast<const uint4 *>(batch->result_state.get()); A.result_status = batch->result_status;
+            A.sums = film->sums; A.counters = film->counters;
+            A.n = (uint32_t)n; A.n_pixels = film->params.width * film->params.height;
+            A.accum_clamp = accum_clamp_for(film->params.samples_per_pixel);
+            const dim3 grid((uint32_t)((n + FILM_T - 1) / FILM_T));
+            if (film->runs) hipLaunchKernelGGL(film_deposit_kernel<true>, grid, dim3(FILM_T), 0, nullptr, A);
+            else hipLaunchKernelGGL(film_deposit_kernel<false>, grid, dim3(FILM_T), 0, nullptr, A);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(film->ev[3], nullptr));
+        film->timed[1] = true;
+        film->deposits++;
+        batch->deposited = true;
+        return VK_OK;
+    });
+}
+
+int vk_film_resolve(vk_film *film, uint32_t n, float *rgb_out) {
+    return guarded([&]() -> int {
+        if (!film || !rgb_out) return fail(VK_ERR_BAD_ARG, "null argument (film or rgb_out)");
+        if (n == 0u) return fail(VK_ERR_BAD_ARG, "n must be >= 1");
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        const vk_render_params &P = film->params;
+        const size_t bytes = (size_t)P.width * P.height * 3u * sizeof(float);
+        if (!film->out) {
+            int rc = paths_alloc(film->out, bytes);
+            if (rc != VK_OK) return rc;
+        }
+        const uint32_t n_pixels = P.width * P.height;
+        HIP_TRY(hipEventRecord(film->ev[4], nullptr));
+        hipLaunchKernelGGL(resolve_kernel, dim3((n_pixels + 255u) / 256u), dim3(256), 0, nullptr,
+                           reinterpret_cast<const long long *>(film->sums.get()), film->out.get(), P.width, P.height, n, (P.width + TILE - 1) / TILE, 0u, 1u);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(film->ev[5], nullptr));
+        film->timed[2] = true;
+        HIP_TRY(hipMemcpy(rgb_out, film->out, bytes, hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+int vk_film_reset(vk_film *film, const vk_camera *cam) {
+    if (!film) return fail(VK_ERR_BAD_ARG, "null film");
+    if (cam) {
+        int rc = check_render_args(film->scene, cam, &film->params);
+        if (rc != VK_OK) return rc;
+    }
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        int rc = film_zero(film);
+        if (rc != VK_OK) return rc;
+        if (cam) film->cam = *cam;
+        return VK_OK;
+    });
+}
+
+int vk_film_get_info(vk_film *film, vk_film_info *out) {
+    if (!film || !out) return fail(VK_ERR_BAD_ARG, "null argument (film or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        unsigned long long c[4];
+        HIP_TRY(hipMemcpy(c, film->counters, sizeof(c), hipMemcpyDeviceToHost));      // (waits for the null stream)
+        memset(out, 0, sizeof(*out));
+        out->width = film->params.width; out->height = film->params.height; out->samples_per_pixel = film->params.samples_per_pixel;
+        out->emitted = film->emitted; out->deposited = c[0]; out->dropped = c[1]; out->clamped = c[2]; out->skipped = c[3];
+        out->deposits = film->deposits;
+        return VK_OK;
+    });
+}
+
+void vk_film_destroy(vk_film *film) {
+    if (film) film_free(film);
+}
+
+// test hook (vecchio_amd_debug.h): the raw sums
+int vk_debug_film_sums(vk_film *film, long long *sums) {
+    if (!film || !sums) return fail(VK_ERR_BAD_ARG, "null argument (film or sums)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        HIP_TRY(hipMemcpy(sums, film->sums, (size_t)film->params.width * film->params.height * 3u * sizeof(long long), hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): the last emit, deposit and resolve, from the events recorded around each; 0 for one not yet run
+int vk_debug_film_last_ms(vk_film *film, double ms[3]) {
+    if (!film || !ms) return fail(VK_ERR_BAD_ARG, "null argument (film or ms)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        double got[3] = {0.0, 0.0, 0.0};
+        for (int k = 0; k < 3; k++) {
+            if (!film->timed[k]) continue;
+            HIP_TRY(hipEventSynchronize(film->ev[2 * k + 1]));
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, film->ev[2 * k], film->ev[2 * k + 1]));
+            got[k] = (double)t;
+        }
+        for (int k = 0; k < 3; k++) ms[k] = got[k];
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): the deposit's form from the next vk_film_deposit on
+int vk_debug_film_deposit_form(vk_film *film, int form) {
+    if (!film) return fail(VK_ERR_BAD_ARG, "null film");
+    if (form != VK_DEBUG_FILM_DEPOSIT_PLAIN && form != VK_DEBUG_FILM_DEPOSIT_RUNS) return fail(VK_ERR_BAD_ARG, "unknown deposit form");
+    film->runs = form == VK_DEBUG_FILM_DEPOSIT_RUNS;
+    return VK_OK;
 }
 
 }  // extern "C"

@@ -2293,6 +2293,112 @@ __global__ __launch_bounds__(PATHS_T) void paths_cull_mark_kernel(const uint4 *r
     out[5] = make_uint4(kept ? (uint32_t)VK_SHADE_SCATTERED : (uint32_t)VK_PATHS_CULLED, 0xFFFFFFFFu, 0u, 0u);
 }
 
+// ---- films (vk_film_*): the two ends of a frame made of path batches, on the device.
+// film_emit_kernel: one lane per path of a window of the film's frame.  Path id = (row-major pixel of the window) * n_samples + k is
+// sample first_sample + k of that pixel: start_sample_core itself — the render kernel's camera, on the film's frame — gives the ray, and
+// the state resumes the sample's stream right behind the camera's draws.  The lens disk's rejection loop diverges, and may.  The ray (32
+// bytes), the state (48) and the id are written as the batch's begin would have staged them: no iota launch.
+constexpr int FILM_T = 256;
+// the deposit's default form, measured (DESIGN.md "Film"): on C2's frame at 8 samples per pixel RUNS takes 0.79 of PLAIN's time, far
+// beyond the spread of the repetitions; at 1 sample per pixel, where no two neighbours share a pixel, the two are level
+constexpr bool FILM_DEPOSIT_RUNS = true;
+struct FilmEmitArgs {
+    RenderConsts C;          // the film's camera, frame and seed
+    uint4 *rays;             // vk_ray[n]
+    uint4 *states;           // vk_path_state[n]
+    uint32_t *ids;           // [n]
+    uint32_t x0, y0, win_width, first_sample, n_samples, n;
+};
+__global__ __launch_bounds__(FILM_T) void film_emit_kernel(FilmEmitArgs A) {
+    const uint32_t i = blockIdx.x * FILM_T + threadIdx.x;
+    if (i >= A.n) return;
+    const uint32_t wp = i / A.n_samples, k = i - wp * A.n_samples;
+    const uint32_t wy = wp / A.win_width, wx = wp - wy * A.win_width;
+    Lane L;
+    V3 o, d;
+    float time;
+    start_sample_core(L, A.C, A.x0 + wx, A.y0 + wy, A.first_sample + k, o, d, time);
+    uint4 *r = A.rays + (size_t)i * 2u, *s = A.states + (size_t)i * 3u;
+    r[0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), 0x7F800000u /* tmax = +INFINITY */);
+    r[1] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(time));
+    s[0] = make_uint4(__float_as_uint(L.thr.x), __float_as_uint(L.thr.y), __float_as_uint(L.thr.z), L.depth);
+    s[1] = make_uint4(__float_as_uint(L.acc.x), __float_as_uint(L.acc.y), __float_as_uint(L.acc.z), L.rng.ctr);
+    s[2] = make_uint4((uint32_t)A.C.seed, (uint32_t)(A.C.seed >> 32), L.pixel, L.sample);
+    A.ids[i] = i;
+}
+
+// film_deposit_kernel<RUNS>: one lane per started id of a batch with nothing live.  A result retired as VK_SHADE_MISS, VK_SHADE_ENDED
+// or VK_PATHS_CULLED goes to the pixel its STATE names: the render kernel's finite filter (main.rs:192-194), its conversion (to_fixed_small
+// at or below ACCUM_SMALL, else to_fixed with the film's clamp) and three 64-bit integer atomics on the pixel's sums.  A pixel outside the
+// frame and every other status is skipped without touching memory by that index.  The four counters — deposited, dropped, clamped,
+// skipped — are ballots, added once per wave.  Only the second and third quarter of the state (acc, pixel) are loaded.
+//   RUNS = false (PLAIN): every depositing lane issues its three atomics.
+//   RUNS = true: a wave's neighbouring lanes that deposit into the same pixel — after an emit, a pixel's n_samples paths — are summed
+//     first, by a segmented suffix sum (six __shfl_down steps, a lane adds its neighbour at distance d while that one lies in its run),
+//     and the head lane of a run issues the atomics for all of it.  Integer sums: both forms give the same bytes.
+struct FilmDepositArgs {
+    const uint4 *result_state;     // vk_path_state[n]
+    const uint32_t *result_status; // [n]
+    unsigned long long *sums;      // [n_pixels * 3]
+    unsigned long long *counters;  // deposited, dropped, clamped, skipped
+    uint32_t n, n_pixels;
+    float accum_clamp;             // accum_clamp_for(the film's samples_per_pixel)
+};
+template <bool RUNS>
+__global__ __launch_bounds__(FILM_T) void film_deposit_kernel(FilmDepositArgs A) {
+    const uint32_t i = blockIdx.x * FILM_T + threadIdx.x, lane = threadIdx.x & 63u;
+    const bool in = i < A.n;
+    uint32_t status = (uint32_t)VK_SHADE_BAD_HIT, pixel = 0xFFFFFFFFu;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f;
+    if (in) {
+        status = A.result_status[i];
+        const uint4 s1 = A.result_state[(size_t)i * 3u + 1u], s2 = A.result_state[(size_t)i * 3u + 2u];
+        ax = __uint_as_float(s1.x); ay = __uint_as_float(s1.y); az = __uint_as_float(s1.z);
+        pixel = s2.z;
+    }
+    const bool retired = status == (uint32_t)VK_SHADE_MISS || status == (uint32_t)VK_SHADE_ENDED || status == (uint32_t)VK_PATHS_CULLED;
+    const bool ours = in && retired && pixel < A.n_pixels;
+    const bool finite = isfinite(ax) && isfinite(ay) && isfinite(az);
+    const bool deposit = ours && finite;
+    const float big = fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az));
+    const bool large = big > ACCUM_SMALL;
+    unsigned long long fx = 0ull, fy = 0ull, fz = 0ull;
+    if (deposit) {
+        if (!large) {
+            fx = (unsigned long long)to_fixed_small(ax); fy = (unsigned long long)to_fixed_small(ay); fz = (unsigned long long)to_fixed_small(az);
+        } else {
+            fx = (unsigned long long)to_fixed(ax, A.accum_clamp); fy = (unsigned long long)to_fixed(ay, A.accum_clamp);
+            fz = (unsigned long long)to_fixed(az, A.accum_clamp);
+        }
+    }
+    const unsigned long long m_dep = __ballot(deposit), m_drop = __ballot(ours && !finite);
+    const unsigned long long m_clamp = __ballot(deposit && large && big > A.accum_clamp), m_skip = __ballot(in && !ours);
+    if (lane == 0u) {
+        if (m_dep) atomicAdd(A.counters + 0, (unsigned long long)__popcll(m_dep));
+        if (m_drop) atomicAdd(A.counters + 1, (unsigned long long)__popcll(m_drop));
+        if (m_clamp) atomicAdd(A.counters + 2, (unsigned long long)__popcll(m_clamp));
+        if (m_skip) atomicAdd(A.counters + 3, (unsigned long long)__popcll(m_skip));
+    }
+    bool issue = deposit;
+    if (RUNS) {
+        const uint32_t key = deposit ? pixel : 0xFFFFFFFFu;                 // (a depositing pixel is below n_pixels <= 2^26)
+        const uint32_t prev = __shfl_up(key, 1, 64);
+        const unsigned long long heads = __ballot(lane == 0u || prev != key);
+        const unsigned long long above = heads & ~(((2ull << lane) - 1ull));     // the heads behind this lane (lane 63: none)
+        const uint32_t end = above ? (uint32_t)__builtin_ctzll(above) : 64u;    // one past the lane's run
+#pragma unroll
+        for (uint32_t d = 1u; d < 64u; d <<= 1) {
+            const unsigned long long vx = __shfl_down(fx, d, 64), vy = __shfl_down(fy, d, 64), vz = __shfl_down(fz, d, 64);
+            if (lane + d < end) { fx += vx; fy += vy; fz += vz; }
+        }
+        issue = deposit && ((heads >> lane) & 1ull);
+    }
+    if (issue) {
+        unsigned long long *a = A.sums + (size_t)pixel * 3u;
+        atomicAdd(a + 0, fx); atomicAdd(a + 1, fy); atomicAdd(a + 2, fz);
+    }
+}
+
 #ifdef VK_DEBUG_LIB
 // device math probe (tests: GPU transcendental/draw functions are bit-identical to the host's)
 __global__ void math_probe_kernel(int op, const float *a, const float *b, float *out, size_t n) {

@@ -218,6 +218,22 @@ class PathsStepInfo(C.Structure):
                 ("bounces", C.c_uint32), ("kernel_launches", C.c_uint32), ("kernel_ms", C.c_double), ("seconds", C.c_double)]
 
 
+class FilmWindow(C.Structure):
+    """vk_film_window (vk_film_emit)"""
+    _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("first_sample", C.c_uint32),
+                ("n_samples", C.c_uint32)]
+
+
+class FilmInfo(C.Structure):
+    """vk_film_info (vk_film_get_info)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("samples_per_pixel", C.c_uint32), ("_pad", C.c_uint32),
+                ("emitted", C.c_uint64), ("deposited", C.c_uint64), ("dropped", C.c_uint64), ("clamped", C.c_uint64), ("skipped", C.c_uint64),
+                ("deposits", C.c_uint64)]
+
+
+VK_DEBUG_FILM_DEPOSIT_PLAIN, VK_DEBUG_FILM_DEPOSIT_RUNS = 0, 1
+
+
 class DebugStreamKey(C.Structure):
     """vk_debug_stream_key of include/vecchio_amd_debug.h (vk_debug_trace_radiance_samples)"""
     _fields_ = [("seed", C.c_uint64), ("pixel", C.c_uint32), ("sample", C.c_uint32), ("ctr", C.c_uint32), ("_pad", C.c_uint32)]
@@ -322,6 +338,7 @@ DEVICE_SYMBOLS = [
     "vk_trace_radiance", "vk_trace_irradiance", "vk_trace_probes", "vk_probe_eval", "vk_shade_hits",
     "vk_paths_create", "vk_paths_begin", "vk_paths_step", "vk_paths_read", "vk_paths_cull", "vk_paths_results", "vk_paths_get_info",
     "vk_paths_destroy",
+    "vk_film_create", "vk_film_emit", "vk_film_deposit", "vk_film_resolve", "vk_film_reset", "vk_film_get_info", "vk_film_destroy",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -429,6 +446,20 @@ def _bind(lib):
     lib.vk_paths_get_info.argtypes = [C.c_void_p, C.POINTER(PathsInfo)]
     lib.vk_paths_destroy.restype = None
     lib.vk_paths_destroy.argtypes = [C.c_void_p]
+    lib.vk_film_create.restype = C.c_int
+    lib.vk_film_create.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(C.c_void_p)]
+    lib.vk_film_emit.restype = C.c_int
+    lib.vk_film_emit.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FilmWindow)]
+    lib.vk_film_deposit.restype = C.c_int
+    lib.vk_film_deposit.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_film_resolve.restype = C.c_int
+    lib.vk_film_resolve.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.vk_film_reset.restype = C.c_int
+    lib.vk_film_reset.argtypes = [C.c_void_p, C.POINTER(Camera)]
+    lib.vk_film_get_info.restype = C.c_int
+    lib.vk_film_get_info.argtypes = [C.c_void_p, C.POINTER(FilmInfo)]
+    lib.vk_film_destroy.restype = None
+    lib.vk_film_destroy.argtypes = [C.c_void_p]
     lib.vk_probe_eval.restype = C.c_int
     lib.vk_probe_eval.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.vk_trace_occluded_device.restype = C.c_int
@@ -479,6 +510,12 @@ def _bind(lib):
         [C.POINTER(C.c_uint64 * 5)]
     lib.vk_debug_paths_last_ms.restype = C.c_int
     lib.vk_debug_paths_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 3)]
+    lib.vk_debug_film_sums.restype = C.c_int
+    lib.vk_debug_film_sums.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_debug_film_last_ms.restype = C.c_int
+    lib.vk_debug_film_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 3)]
+    lib.vk_debug_film_deposit_form.restype = C.c_int
+    lib.vk_debug_film_deposit_form.argtypes = [C.c_void_p, C.c_int]
     lib.vk_debug_trace_occluded_device.restype = C.c_int
     lib.vk_debug_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_uint32, C.c_uint32]

@@ -131,6 +131,13 @@ pub struct vk_paths_info { pub capacity: u64, pub started: u64, pub live: u64, p
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_paths_step_info { pub traced: u64, pub live: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
 
+// films: a window of camera paths to emit, and a film's counters
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_film_window { pub x0: u32, pub y0: u32, pub width: u32, pub height: u32, pub first_sample: u32, pub n_samples: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_film_info { pub width: u32, pub height: u32, pub samples_per_pixel: u32, pub _pad: u32, pub emitted: u64, pub deposited: u64, pub dropped: u64, pub clamped: u64, pub skipped: u64, pub deposits: u64 }
+
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_temporal_params { pub width: u32, pub height: u32, pub max_history: u32, pub depth_tol: f32, pub normal_cos_min: f32, pub albedo_floor: f32, pub flags: u32 }
 
@@ -141,6 +148,7 @@ pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, 
 #[repr(C)] pub struct vk_progress { _private: [u8; 0] }
 #[repr(C)] pub struct vk_temporal { _private: [u8; 0] }
 #[repr(C)] pub struct vk_paths { _private: [u8; 0] }
+#[repr(C)] pub struct vk_film { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -219,6 +227,15 @@ extern "C" {
     pub fn vk_paths_results(p: *mut vk_paths, states: *mut vk_path_state, status: *mut u32) -> c_int;
     pub fn vk_paths_get_info(p: *mut vk_paths, out: *mut vk_paths_info) -> c_int;
     pub fn vk_paths_destroy(p: *mut vk_paths);
+    // films (additive symbols of ABI 7): a frame's sums on the device; emit camera paths into a batch, step the batch until nothing is
+    // live, deposit it; resolve(samples_per_pixel) once every (pixel, sample) went through is vk_render's frame; destroy before the scene
+    pub fn vk_film_create(scene: *mut vk_scene, cam: *const vk_camera, params: *const vk_render_params, out: *mut *mut vk_film) -> c_int;
+    pub fn vk_film_emit(film: *mut vk_film, batch: *mut vk_paths, win: *const vk_film_window) -> c_int;
+    pub fn vk_film_deposit(film: *mut vk_film, batch: *mut vk_paths) -> c_int;
+    pub fn vk_film_resolve(film: *mut vk_film, n: u32, rgb_out: *mut f32) -> c_int;
+    pub fn vk_film_reset(film: *mut vk_film, cam: *const vk_camera) -> c_int;
+    pub fn vk_film_get_info(film: *mut vk_film, out: *mut vk_film_info) -> c_int;
+    pub fn vk_film_destroy(film: *mut vk_film);
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

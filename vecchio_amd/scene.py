@@ -583,6 +583,12 @@ class DeviceScene:
         a stable compaction of the survivors per bounce.  Use as a context manager, or close() it before the scene."""
         return PathBatch(self, capacity)
 
+    def film(self, cam, params):
+        """A film on this scene (vk_film_create): a frame's fixed-point sums with its camera and render parameters, which emits camera
+        paths into a path batch and deposits finished batches, both on the device.  Use as a context manager, or close() it before the
+        scene."""
+        return Film(self, cam, params)
+
     def debug_compact_paths(self, items, ids, n_ids, canary=0xA5):
         """The compaction of a path batch's bounce on host arrays (vk_debug_compact_paths, a test hook): items a SHADED_DTYPE array, ids
         their uint32 ids (each below n_ids).  Every output is prefilled with the byte `canary`.  Returns (rays, states, ids_out — n
@@ -861,6 +867,104 @@ class PathBatch:
     def close(self):
         if self._h:
             self._lib.vk_paths_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Film:
+    """vk_film handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed): emit() camera paths of a
+    window of the frame into a PathBatch, step the batch to its end, deposit() it; resolve() once every sample went through is render()'s
+    frame, bit for bit."""
+
+    def __init__(self, scene, cam, params):
+        self._lib = scene._lib
+        self._scene = scene
+        self.params = ffi.RenderParams.from_buffer_copy(params)
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_film_create(scene._h, C.byref(cam), C.byref(params), C.byref(h)))
+        self._h = h
+
+    def emit(self, batch, x0, y0, w, h, first_sample=0, n_samples=1):
+        """Begin `batch` with the w * h * n_samples camera paths of the window (vk_film_emit): id ((y - y0) * w + (x - x0)) * n_samples + k
+        is sample first_sample + k of pixel (x, y)."""
+        win = ffi.FilmWindow(x0, y0, w, h, first_sample, n_samples)
+        check(self._lib, self._lib.vk_film_emit(self._h, batch._h, C.byref(win)))
+
+    def deposit(self, batch):
+        """Add the retired paths of `batch`, which has nothing live, to the frame's sums (vk_film_deposit), each at its state's pixel."""
+        check(self._lib, self._lib.vk_film_deposit(self._h, batch._h))
+
+    def resolve(self, n=None, out=None):
+        """The frame as the mean over n samples per pixel (vk_film_resolve; default: the film's samples_per_pixel): float32 (height,
+        width, 3), y = 0 the bottom row.  out: an array of that shape to write into."""
+        p = self.params
+        if out is None:
+            out = np.zeros((p.height, p.width, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == p.width * p.height * 3
+        check(self._lib, self._lib.vk_film_resolve(self._h, p.samples_per_pixel if n is None else n, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def reset(self, cam=None):
+        """Zero the sums and the counters; cam, where given, replaces the camera (vk_film_reset)."""
+        check(self._lib, self._lib.vk_film_reset(self._h, C.byref(cam) if cam is not None else None))
+
+    def info(self):
+        inf = ffi.FilmInfo()
+        check(self._lib, self._lib.vk_film_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def render(self, batch, cull=None):
+        """The whole frame through `batch`: the frame is walked in windows that fit the batch's capacity — whole rows of all samples
+        where a row fits, else pieces of a row, else a pixel's samples in pieces —, each emitted, stepped to its end and deposited.
+        cull, where given, is called with the batch between two bounces while anything is live (PathBatch.read() and cull() are its
+        tools).  Returns resolve()."""
+        p = self.params
+        cap = int(batch.info().capacity)
+        spp = p.samples_per_pixel
+        ns = min(spp, cap)
+        w = max(1, min(p.width, cap // ns))
+        h = max(1, min(p.height, cap // (ns * w))) if w == p.width else 1
+        for s0 in range(0, spp, ns):
+            for y0 in range(0, p.height, h):
+                for x0 in range(0, p.width, w):
+                    self.emit(batch, x0, y0, min(w, p.width - x0), min(h, p.height - y0), s0, min(ns, spp - s0))
+                    while batch.step(1).live:
+                        if cull is not None:
+                            cull(batch)
+                    self.deposit(batch)
+        return self.resolve()
+
+    def debug_sums(self):
+        """The raw sums (vk_debug_film_sums, a test hook): int64 (height, width, 3) in 2^-26 units"""
+        p = self.params
+        out = np.zeros((p.height, p.width, 3), np.int64)
+        check(self._lib, self._lib.vk_debug_film_sums(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def last_ms(self):
+        """(emit, deposit, resolve) device milliseconds of the last call of each (vk_debug_film_last_ms, a test hook)"""
+        ms = (C.c_double * 3)()
+        check(self._lib, self._lib.vk_debug_film_last_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
+    def debug_deposit_form(self, form):
+        """ffi.VK_DEBUG_FILM_DEPOSIT_PLAIN or _RUNS from the next deposit() on (vk_debug_film_deposit_form, a test hook)"""
+        check(self._lib, self._lib.vk_debug_film_deposit_form(self._h, form))
+
+    def close(self):
+        if self._h:
+            self._lib.vk_film_destroy(self._h)
             self._h = None
 
     def __enter__(self):
