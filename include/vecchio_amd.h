@@ -991,6 +991,67 @@ int vk_film_reset(vk_film *film, const vk_camera *cam);
 int vk_film_get_info(vk_film *film, vk_film_info *out);
 void vk_film_destroy(vk_film *film);
 
+/* ---- regeneration: a path batch refilled from a film's window as its paths retire (additive symbols of ABI 7) -------------------------
+ * replaces: the caller's loop of windows, each emitted, stepped to its end and deposited (vk_film_emit, vk_paths_step, vk_film_deposit),
+ * which walks the ever shorter tail of every window and needs a window to fit the batch.  A regenerating run sends a window of ANY number
+ * of paths through a batch of ANY capacity: every bounce first tops the batch up with the window's next camera paths, and a path that
+ * retires is deposited into the film there and then.  Only the last tail of a run is walked thin.  No function takes a stream; all work
+ * is on the null stream, on the scene's device (devices[0] of a multi-device scene).
+ *   The window's sequence.  Path number q = ((y - y0) * win.width + (x - x0)) * n_samples + k, 0 <= q < total = win.width * win.height *
+ *     win.n_samples, is exactly path id q of vk_film_emit for the same window: the same ray and state, the same stream position behind
+ *     the camera's draws.  Its id in the batch is q.  Ids are 32 bits: total >= 2^32 is VK_ERR_BAD_ARG (split the window by sample
+ *     ranges).  total is not bounded by the batch's capacity.
+ *   vk_regen_begin checks what vk_film_emit checks, in the same words, except the capacity rule, and puts `batch` into its REGENERATING
+ *     state for this film and window: nothing live, next = 0, counters as after a begin, the film's shade parameters.  It enqueues
+ *     nothing that emits.  It forgets a previous batch or run, as vk_paths_begin does.
+ *   vk_regen_step runs bounces until the run is finished or max_bounces of them are run (max_bounces == 0: VK_ERR_BAD_ARG).  One bounce:
+ *     1. top up: m = min(capacity - live, total - next) fresh paths next .. next + m go to slots live .. live + m, ids = their numbers;
+ *        live += m, next += m;
+ *     2. if nothing is live, the run is finished;
+ *     3. trace and shade exactly as vk_paths_step does: the same kernels, the same tree view, the path's own stream through media;
+ *     4. retire and compact: a path whose status is not VK_SHADE_SCATTERED is deposited into the film there and then, by
+ *        vk_film_deposit's rule applied to its state after the bounce — VK_SHADE_MISS and VK_SHADE_ENDED at state.pixel, a non-finite acc
+ *        `dropped`, both conversions and the clamp of the film's samples_per_pixel as there, VK_SHADE_BAD_HIT and a pixel outside the
+ *        frame `skipped`.  Nothing is stored under its id.  The survivors are compacted stably to the front.
+ *     The run is finished when live == 0 and remaining == 0.  A finished run leaves the batch begun, with nothing live and marked as
+ *     deposited; a step on a finished run is VK_OK and does nothing.  info (may be NULL): see vk_regen_info; kernel_launches counts six
+ *     a bounce, five where nothing was left to top up.
+ *     The invariant: live order is ascending by id at every moment — the survivors keep their order, the top-up appends larger numbers.
+ *   vk_regen_cull is vk_paths_cull's rule between two steps: keep and scale in live order, a kept path's thr scaled, a culled path
+ *     deposited as VK_PATHS_CULLED with its state as it stands, as vk_film_deposit would, the kept paths compacted stably.  There is no
+ *     top-up: the next step does it.
+ *   Arguments: for each of the three calls VK_ERR_BAD_ARG with nothing enqueued and film and batch left as they were for a null pointer, a
+ *     batch of another scene, for step and cull a batch that is not regenerating, and a film other than the one the run was begun with.
+ *   Existing functions on a regenerating batch: vk_paths_read works (live ids, rays and states) and so does vk_paths_get_info (started =
+ *     emitted so far, live, retired[], bounces); vk_paths_step, vk_paths_cull, vk_paths_results and vk_film_deposit are VK_ERR_BAD_ARG;
+ *     vk_paths_begin and vk_film_emit end the run and forget what was live and what remained.  vk_film_reset or vk_film_destroy during
+ *     a run is the caller's error and is not detected.
+ *   vk_film_info: emitted grows by the top-ups; deposited, dropped, clamped and skipped by the retirements; deposits counts
+ *     vk_film_deposit calls only.
+ *   THE CONTRACT, on every scene where the film's contract holds:
+ *     1. per path: the state a path retires with is the state the window route (vk_film_emit, vk_paths_step, vk_film_deposit) retires it
+ *        with, bit for bit — a path's trajectory depends on its own state alone — so the sums are equal;
+ *     2. per frame: once every (pixel, sample) with sample < samples_per_pixel went through exactly once — by regenerating runs, by the
+ *        emit / deposit route, or both mixed across windows; any capacity >= 1, any slicing by max_bounces, any order —
+ *        vk_film_resolve(film, samples_per_pixel, out) is vk_render's f32 frame BIT FOR BIT, and `clamped` is its clamped_samples;
+ *     3. per bounce: after every bounce vk_paths_read returns ids, rays and states that are a function of the window, the capacity and
+ *        the paths' lifetimes (the bounces until each retires) alone: the schedule is deterministic, nothing depends on how workgroups
+ *        are scheduled.
+ *   Scene state: the path batch's rules.  A call touches nothing that describes vk_render's last frame, not the launch log, no vk_progress
+ *     or vk_temporal handle, and not the ray queries' scratch.                                                                          */
+typedef struct vk_regen_info {          /* 80 bytes */
+    uint64_t traced;                    /* rays walked, summed over the bounces run by this call */
+    uint64_t live;                      /* after the call (before the next top-up) */
+    uint64_t remaining;                 /* paths of the window not yet emitted */
+    uint64_t emitted;                   /* by this call's top-ups */
+    uint64_t missed, ended, bad;        /* retired by this call, by status */
+    uint32_t bounces, kernel_launches;
+    double kernel_ms, seconds;
+} vk_regen_info;
+int vk_regen_begin(vk_film *film, vk_paths *batch, const vk_film_window *win);
+int vk_regen_step(vk_film *film, vk_paths *batch, uint32_t max_bounces, vk_regen_info *info);
+int vk_regen_cull(vk_film *film, vk_paths *batch, const uint8_t *keep, const float *scale);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

@@ -125,6 +125,13 @@ int vk_debug_film_last_ms(vk_film *film, double ms[3]);
  * VK_ERR_BAD_ARG for a null film or another form.  In both libraries. */
 enum { VK_DEBUG_FILM_DEPOSIT_PLAIN = 0, VK_DEBUG_FILM_DEPOSIT_RUNS = 1 };
 int vk_debug_film_deposit_form(vk_film *film, int form);
+
+/* the device milliseconds of a regenerating batch's last bounce, part by part: ms[0] the top-up (regen_emit_kernel; next to nothing
+ * where nothing was left to emit), ms[1] trace_paths_kernel, ms[2] shade_hits_kernel, ms[3] the compaction with the deposit (count, scan,
+ * regen_move_kernel), from events vk_regen_step records between them on the handle; their sum is that bounce's share of kernel_ms.
+ * VK_ERR_BAD_ARG for a null pointer, a batch that is not regenerating, or when no bounce has run since vk_regen_begin.  Takes no stream.
+ * In both libraries. */
+int vk_debug_regen_last_ms(vk_paths *batch, double ms[4]);
 #ifdef __cplusplus
 }
 #endif

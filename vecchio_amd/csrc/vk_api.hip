@@ -2491,12 +2491,18 @@ struct vk_paths {
     DeviceBuffer<unsigned long long> counts;        // [5]: the one record a bounce sends back
     Event ev0, ev1;                                 // around a bounce's launches
     Event ev_t, ev_s;                               // behind its trace and behind its shade (vk_debug_paths_last_ms)
+    Event ev_e;                                     // behind a regenerating bounce's top-up (vk_debug_regen_last_ms)
     vk_shade_params sp{};                           // the last begin's
     bool begun = false;
     bool deposited = false;                         // vk_film_deposit has taken this batch (cleared by vk_paths_begin and vk_film_emit)
     uint32_t cur = 0;                               // ids[cur] holds the live ids
     uint64_t started = 0, live = 0, retired[5] = {0, 0, 0, 0, 0};
     uint32_t bounces = 0;
+    // the regenerating state (vk_regen_*), host side only: set by vk_regen_begin, cleared by vk_paths_begin and vk_film_emit
+    bool regen = false;
+    const vk_film *regen_film = nullptr;            // the run's film, for the identity check only: never dereferenced
+    vk_film_window regen_win{};
+    uint64_t regen_next = 0, regen_total = 0;       // the window's paths [0, regen_next) are emitted, of regen_total
 };
 
 namespace {
@@ -2587,7 +2593,7 @@ int vk_paths_create(vk_scene *scene, uint64_t capacity, vk_paths **out) {
             (rc = paths_alloc(p->wg_counts, n_wg * PATHS_STATUSES * 4u)) != VK_OK || (rc = paths_alloc(p->wg_offsets, n_wg * 4u)) != VK_OK ||
             (rc = paths_alloc(p->counts, PATHS_STATUSES * sizeof(unsigned long long))) != VK_OK) return rc;
         if ((rc = p->ev0.create()) != VK_OK || (rc = p->ev1.create()) != VK_OK || (rc = p->ev_t.create()) != VK_OK ||
-            (rc = p->ev_s.create()) != VK_OK) return rc;
+            (rc = p->ev_s.create()) != VK_OK || (rc = p->ev_e.create()) != VK_OK) return rc;
         *out = p.release();
         return VK_OK;
     });
@@ -2613,6 +2619,7 @@ int vk_paths_begin(vk_paths *p, const vk_shade_params *params, const vk_ray *ray
             HIP_TRY(hipGetLastError());
         }
         p->sp = *params; p->begun = true; p->deposited = false; p->cur = 0u; p->started = n; p->live = n; p->bounces = 0u;
+        p->regen = false;
         for (uint64_t &r : p->retired) r = 0u;
         return VK_OK;
     });
@@ -2623,6 +2630,7 @@ int vk_paths_step(vk_paths *p, uint32_t max_bounces, vk_paths_step_info *info) {
         if (!p) return fail(VK_ERR_BAD_ARG, "null path batch");
         if (max_bounces == 0u) return fail(VK_ERR_BAD_ARG, "max_bounces must be >= 1");
         if (!p->begun) return fail(VK_ERR_BAD_ARG, "vk_paths_step before vk_paths_begin");
+        if (p->regen) return fail(VK_ERR_BAD_ARG, "vk_paths_step on a regenerating path batch (vk_regen_step runs it)");
         const auto t0 = std::chrono::steady_clock::now();
         vk_scene *q = first_part(p->scene);
         HIP_TRY(hipSetDevice(q->device));
@@ -2671,6 +2679,7 @@ int vk_paths_cull(vk_paths *p, const uint8_t *keep, const float *scale) {
     return guarded([&]() -> int {
         if (!p) return fail(VK_ERR_BAD_ARG, "null path batch");
         if (!p->begun) return fail(VK_ERR_BAD_ARG, "vk_paths_cull before vk_paths_begin");
+        if (p->regen) return fail(VK_ERR_BAD_ARG, "vk_paths_cull on a regenerating path batch (vk_regen_cull culls it)");
         const uint64_t n = p->live;
         if (n == 0u) return VK_OK;
         if (!keep) return fail(VK_ERR_BAD_ARG, "null keep with live paths");
@@ -2694,6 +2703,7 @@ int vk_paths_cull(vk_paths *p, const uint8_t *keep, const float *scale) {
 int vk_paths_results(vk_paths *p, vk_path_state *states, uint32_t *status) {
     return guarded([&]() -> int {
         if (!p) return fail(VK_ERR_BAD_ARG, "null path batch");
+        if (p->regen) return fail(VK_ERR_BAD_ARG, "vk_paths_results on a regenerating path batch (its paths are deposited as they retire)");
         const size_t n = (size_t)p->started, live = (size_t)p->live;
         if (n == 0u || (!states && !status)) return VK_OK;
         HIP_TRY(hipSetDevice(first_part(p->scene)->device));
@@ -2835,6 +2845,43 @@ int film_zero(vk_film *f) {
     return VK_OK;
 }
 
+// what vk_film_emit and vk_regen_begin check of their three arguments, in the same words; *n = the window's paths
+int film_check_window(const vk_film *film, const vk_paths *batch, const vk_film_window *win, uint64_t *n) {
+    if (!film || !batch || !win) return fail(VK_ERR_BAD_ARG, "null argument (film, path batch or window)");
+    if (batch->scene != film->scene) return fail(VK_ERR_BAD_ARG, "the path batch belongs to another scene than the film");
+    const vk_render_params &P = film->params;
+    if (win->width == 0u || win->height == 0u || win->n_samples == 0u) return fail(VK_ERR_BAD_ARG, "empty window");
+    if ((uint64_t)win->x0 + win->width > P.width || (uint64_t)win->y0 + win->height > P.height)
+        return fail(VK_ERR_BAD_ARG, "the window lies outside the film's frame");
+    if ((uint64_t)win->first_sample + win->n_samples > P.samples_per_pixel)
+        return fail(VK_ERR_BAD_ARG, "first_sample + n_samples exceeds the film's samples_per_pixel");
+    // (width * height <= 2^26 and n_samples <= 2^26: the product fits 64 bits)
+    *n = (uint64_t)win->width * win->height * win->n_samples;
+    return VK_OK;
+}
+
+// the film's camera, frame and seed as the emitting kernels take them
+RenderConsts film_consts(const vk_film *film) {
+    const vk_render_params &P = film->params;
+    RenderConsts C;
+    memset(&C, 0, sizeof(C));
+    C.cam = film->cam;
+    C.width = P.width; C.height = P.height; C.spp = P.samples_per_pixel; C.max_depth = P.max_depth;
+    C.seed = P.seed; C.integrator = P.integrator; C.background = P.background;
+    C.bg[0] = P.background_color[0]; C.bg[1] = P.background_color[1]; C.bg[2] = P.background_color[2];
+    return C;
+}
+
+// the film's shade parameters: what a batch it fills is shaded with
+vk_shade_params film_shade_params(const vk_film *film) {
+    const vk_render_params &P = film->params;
+    vk_shade_params sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.max_depth = P.max_depth; sp.integrator = P.integrator; sp.background = P.background;
+    sp.background_color[0] = P.background_color[0]; sp.background_color[1] = P.background_color[1]; sp.background_color[2] = P.background_color[2];
+    return sp;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2863,27 +2910,16 @@ int vk_film_create(vk_scene *scene, const vk_camera *cam, const vk_render_params
 
 int vk_film_emit(vk_film *film, vk_paths *batch, const vk_film_window *win) {
     return guarded([&]() -> int {
-        if (!film || !batch || !win) return fail(VK_ERR_BAD_ARG, "null argument (film, path batch or window)");
-        if (batch->scene != film->scene) return fail(VK_ERR_BAD_ARG, "the path batch belongs to another scene than the film");
-        const vk_render_params &P = film->params;
-        if (win->width == 0u || win->height == 0u || win->n_samples == 0u) return fail(VK_ERR_BAD_ARG, "empty window");
-        if ((uint64_t)win->x0 + win->width > P.width || (uint64_t)win->y0 + win->height > P.height)
-            return fail(VK_ERR_BAD_ARG, "the window lies outside the film's frame");
-        if ((uint64_t)win->first_sample + win->n_samples > P.samples_per_pixel)
-            return fail(VK_ERR_BAD_ARG, "first_sample + n_samples exceeds the film's samples_per_pixel");
-        // (width * height <= 2^26 and n_samples <= 2^26: the product fits 64 bits)
-        const uint64_t n = (uint64_t)win->width * win->height * win->n_samples;
+        uint64_t n = 0;
+        int rc = film_check_window(film, batch, win, &n);
+        if (rc != VK_OK) return rc;
         if (n > batch->capacity) return fail(VK_ERR_BAD_ARG, "the window's paths exceed the path batch's capacity");
         vk_scene *q = first_part(film->scene);
         HIP_TRY(hipSetDevice(q->device));
-        int rc = ensure_provenance(q);
-        if (rc != VK_OK) return rc;
+        if ((rc = ensure_provenance(q)) != VK_OK) return rc;
         FilmEmitArgs A;
         memset(&A, 0, sizeof(A));
-        A.C.cam = film->cam;
-        A.C.width = P.width; A.C.height = P.height; A.C.spp = P.samples_per_pixel; A.C.max_depth = P.max_depth;
-        A.C.seed = P.seed; A.C.integrator = P.integrator; A.C.background = P.background;
-        A.C.bg[0] = P.background_color[0]; A.C.bg[1] = P.background_color[1]; A.C.bg[2] = P.background_color[2];
+        A.C = film_consts(film);
         A.rays = reinterpret_cast<uint4 *>(batch->rays.get()); A.states = reinterpret_cast<uint4 *>(batch->states.get());
         A.ids = batch->ids[0];
         A.x0 = win->x0; A.y0 = win->y0; A.win_width = win->width; A.first_sample = win->first_sample; A.n_samples = win->n_samples;
@@ -2894,11 +2930,8 @@ int vk_film_emit(vk_film *film, vk_paths *batch, const vk_film_window *win) {
         HIP_TRY(hipEventRecord(film->ev[1], nullptr));
         film->timed[0] = true;
         film->emitted += n;
-        vk_shade_params sp;
-        memset(&sp, 0, sizeof(sp));
-        sp.max_depth = P.max_depth; sp.integrator = P.integrator; sp.background = P.background;
-        sp.background_color[0] = P.background_color[0]; sp.background_color[1] = P.background_color[1]; sp.background_color[2] = P.background_color[2];
-        batch->sp = sp; batch->begun = true; batch->deposited = false; batch->cur = 0u; batch->started = n; batch->live = n; batch->bounces = 0u;
+        batch->sp = film_shade_params(film); batch->begun = true; batch->deposited = false; batch->cur = 0u; batch->started = n; batch->live = n; batch->bounces = 0u;
+        batch->regen = false;
         for (uint64_t &r : batch->retired) r = 0u;
         return VK_OK;
     });
@@ -2909,6 +2942,7 @@ int vk_film_deposit(vk_film *film, vk_paths *batch) {
         if (!film || !batch) return fail(VK_ERR_BAD_ARG, "null argument (film or path batch)");
         if (batch->scene != film->scene) return fail(VK_ERR_BAD_ARG, "the path batch belongs to another scene than the film");
         if (!batch->begun) return fail(VK_ERR_BAD_ARG, "vk_film_deposit before vk_paths_begin or vk_film_emit");
+        if (batch->regen) return fail(VK_ERR_BAD_ARG, "vk_film_deposit on a regenerating path batch (its paths are deposited as they retire)");
         if (batch->live != 0u) return fail(VK_ERR_BAD_ARG, "the path batch has live paths (step or cull them first)");
         if (batch->deposited) return fail(VK_ERR_BAD_ARG, "the path batch has been deposited since its last begin or emit");
         HIP_TRY(hipSetDevice(first_part(film->scene)->device));
@@ -3024,6 +3058,167 @@ int vk_debug_film_deposit_form(vk_film *film, int form) {
     if (form != VK_DEBUG_FILM_DEPOSIT_PLAIN && form != VK_DEBUG_FILM_DEPOSIT_RUNS) return fail(VK_ERR_BAD_ARG, "unknown deposit form");
     film->runs = form == VK_DEBUG_FILM_DEPOSIT_RUNS;
     return VK_OK;
+}
+
+}  // extern "C"
+
+// ---- regeneration (vk_regen_*): a path batch refilled from a film's window as its paths retire.  A bounce is at most six launches on the
+// null stream — regen_emit_kernel (the top-up), trace_paths_kernel, shade_hits_kernel, paths_count_kernel, paths_scan_kernel and
+// regen_move_kernel, which deposits the retired paths into the film and compacts the survivors — and one readback of the counts record,
+// from which the host computes the next top-up.  The state of a run lives in vk_paths' host-side regen fields; a batch's device memory is
+// what it was.
+namespace {
+
+constexpr uint64_t REGEN_MAX = 1ull << 32;         // ids are 32 bits
+
+// vk_regen_step's and vk_regen_cull's argument checks
+int regen_check(const vk_film *film, const vk_paths *batch, const char *who) {
+    if (!film || !batch) return fail(VK_ERR_BAD_ARG, "null argument (film or path batch)");
+    if (batch->scene != film->scene) return fail(VK_ERR_BAD_ARG, "the path batch belongs to another scene than the film");
+    if (!batch->begun || !batch->regen) return fail(VK_ERR_BAD_ARG, std::string(who) + " on a path batch that is not regenerating (vk_regen_begin first)");
+    if (batch->regen_film != film) return fail(VK_ERR_BAD_ARG, "the run was begun with another film");
+    return VK_OK;
+}
+
+// the count and scan passes as they are, then regen_move_kernel, over shaded[0, live)
+int enqueue_regen_compact(vk_film *film, vk_paths *p) {
+    CompactArgs A = paths_compact_args(p);
+    A.n_wg = paths_wgs(A.n);
+    hipLaunchKernelGGL(paths_count_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, nullptr, A);
+    hipLaunchKernelGGL(paths_scan_kernel, dim3(1), dim3(PATHS_SCAN_T), 0, nullptr, A);
+    RegenMoveArgs M;
+    memset(&M, 0, sizeof(M));
+    M.items = A.items; M.ids = A.ids; M.n = A.n; M.rays = A.rays; M.states = A.states; M.ids_out = A.ids_out; M.wg_offsets = A.wg_offsets;
+    M.sums = film->sums; M.counters = film->counters;
+    M.n_pixels = film->params.width * film->params.height;
+    M.accum_clamp = accum_clamp_for(film->params.samples_per_pixel);
+    hipLaunchKernelGGL(regen_move_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, nullptr, M);
+    HIP_TRY(hipGetLastError());
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_regen_begin(vk_film *film, vk_paths *batch, const vk_film_window *win) {
+    return guarded([&]() -> int {
+        uint64_t total = 0;
+        int rc = film_check_window(film, batch, win, &total);
+        if (rc != VK_OK) return rc;
+        if (total >= REGEN_MAX) return fail(VK_ERR_BAD_ARG, "the window's paths exceed 2^32 - 1 (split it by sample ranges)");
+        vk_scene *q = first_part(film->scene);
+        HIP_TRY(hipSetDevice(q->device));
+        if ((rc = ensure_provenance(q)) != VK_OK) return rc;
+        batch->sp = film_shade_params(film); batch->begun = true; batch->deposited = false; batch->cur = 0u; batch->started = 0u; batch->live = 0u;
+        batch->bounces = 0u;
+        for (uint64_t &r : batch->retired) r = 0u;
+        batch->regen = true; batch->regen_film = film; batch->regen_win = *win; batch->regen_next = 0u; batch->regen_total = total;
+        return VK_OK;
+    });
+}
+
+int vk_regen_step(vk_film *film, vk_paths *batch, uint32_t max_bounces, vk_regen_info *info) {
+    return guarded([&]() -> int {
+        int rc = regen_check(film, batch, "vk_regen_step");
+        if (rc != VK_OK) return rc;
+        if (max_bounces == 0u) return fail(VK_ERR_BAD_ARG, "max_bounces must be >= 1");
+        const auto t0 = std::chrono::steady_clock::now();
+        vk_paths *p = batch;
+        vk_scene *q = first_part(p->scene);
+        HIP_TRY(hipSetDevice(q->device));
+        vk_regen_info I;
+        memset(&I, 0, sizeof(I));
+        while (I.bounces < max_bounces) {
+            // 1. top up: the window's next m paths behind the survivors, ids = their numbers (above every live id: live order stays ascending)
+            const uint64_t m = std::min(p->capacity - p->live, p->regen_total - p->regen_next);
+            if (p->live + m == 0u) break;                                // 2. the run is finished
+            HIP_TRY(hipEventRecord(p->ev0, nullptr));
+            uint32_t launches = 5u;
+            if (m != 0u) {
+                RegenEmitArgs A;
+                memset(&A, 0, sizeof(A));
+                A.C = film_consts(film);
+                A.rays = reinterpret_cast<uint4 *>(p->rays.get()); A.states = reinterpret_cast<uint4 *>(p->states.get());
+                A.ids = p->ids[p->cur];                                  // (the last compaction's flip is behind us)
+                const vk_film_window &w = p->regen_win;
+                A.x0 = w.x0; A.y0 = w.y0; A.win_width = w.width; A.first_sample = w.first_sample; A.n_samples = w.n_samples;
+                A.first = (uint32_t)p->regen_next; A.slot0 = (uint32_t)p->live; A.m = (uint32_t)m;      // (total < 2^32, capacity <= 2^24)
+                hipLaunchKernelGGL(regen_emit_kernel, dim3((uint32_t)((m + FILM_T - 1) / FILM_T)), dim3(FILM_T), 0, nullptr, A);
+                HIP_TRY(hipGetLastError());
+                p->live += m; p->regen_next += m; p->started = p->regen_next;
+                film->emitted += m; I.emitted += m;
+                launches++;
+            }
+            HIP_TRY(hipEventRecord(p->ev_e, nullptr));
+            // 3. trace and shade as vk_paths_step does
+            const uint64_t n = p->live;
+            if ((rc = enqueue_trace_paths(q, p->rays, p->states, p->hits, n, nullptr)) != VK_OK) return rc;
+            HIP_TRY(hipEventRecord(p->ev_t, nullptr));
+            if ((rc = enqueue_shade(q, &p->sp, p->rays, p->hits, p->states, n, p->shaded, nullptr)) != VK_OK) return rc;
+            HIP_TRY(hipEventRecord(p->ev_s, nullptr));
+            // 4. retire into the film and compact
+            if ((rc = enqueue_regen_compact(film, p)) != VK_OK) return rc;
+            HIP_TRY(hipEventRecord(p->ev1, nullptr));
+            unsigned long long c[5];
+            if ((rc = paths_take_counts(p, c)) != VK_OK) return rc;
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+            I.kernel_ms += (double)ms; I.kernel_launches += launches; I.bounces++; I.traced += n;
+            I.missed += c[VK_SHADE_MISS]; I.ended += c[VK_SHADE_ENDED]; I.bad += c[VK_SHADE_BAD_HIT];
+            p->bounces++;
+        }
+        if (p->live == 0u && p->regen_next == p->regen_total) p->deposited = true;      // finished: nothing is left to deposit
+        I.live = p->live; I.remaining = p->regen_total - p->regen_next;
+        I.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (info) *info = I;
+        return VK_OK;
+    });
+}
+
+int vk_regen_cull(vk_film *film, vk_paths *batch, const uint8_t *keep, const float *scale) {
+    return guarded([&]() -> int {
+        int rc = regen_check(film, batch, "vk_regen_cull");
+        if (rc != VK_OK) return rc;
+        vk_paths *p = batch;
+        const uint64_t n = p->live;
+        if (n == 0u) return VK_OK;
+        if (!keep) return fail(VK_ERR_BAD_ARG, "null keep with live paths");
+        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
+        // keep and scale ride in the hit records' buffer, as in vk_paths_cull
+        uint8_t *d_keep = p->hits;
+        float *d_scale = reinterpret_cast<float *>(p->hits.get() + (((size_t)p->capacity + 15u) & ~(size_t)15u));
+        HIP_TRY(hipMemcpy(d_keep, keep, (size_t)n, hipMemcpyHostToDevice));
+        if (scale) HIP_TRY(hipMemcpy(d_scale, scale, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(paths_cull_mark_kernel, dim3(paths_wgs(n)), dim3(PATHS_T), 0, nullptr, reinterpret_cast<const uint4 *>(p->rays.get()),
+                           reinterpret_cast<const uint4 *>(p->states.get()), d_keep, scale ? d_scale : nullptr, n,
+                           reinterpret_cast<uint4 *>(p->shaded.get()));
+        HIP_TRY(hipGetLastError());
+        if ((rc = enqueue_regen_compact(film, p)) != VK_OK) return rc;
+        unsigned long long c[5];
+        if ((rc = paths_take_counts(p, c)) != VK_OK) return rc;
+        if (p->live == 0u && p->regen_next == p->regen_total) p->deposited = true;
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): the last regenerating bounce's four parts, from the events vk_regen_step records between them
+int vk_debug_regen_last_ms(vk_paths *p, double ms[4]) {
+    if (!p || !ms) return fail(VK_ERR_BAD_ARG, "null argument (path batch or ms)");
+    return guarded([&]() -> int {
+        if (!p->regen || p->bounces == 0u) return fail(VK_ERR_BAD_ARG, "no bounce has run since vk_regen_begin");
+        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
+        HIP_TRY(hipEventSynchronize(p->ev1));
+        Event *ev[5] = {&p->ev0, &p->ev_e, &p->ev_t, &p->ev_s, &p->ev1};
+        double got[4];
+        for (int k = 0; k < 4; k++) {
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, *ev[k], *ev[k + 1]));
+            got[k] = (double)t;
+        }
+        for (int k = 0; k < 4; k++) ms[k] = got[k];
+        return VK_OK;
+    });
 }
 
 }  // extern "C"

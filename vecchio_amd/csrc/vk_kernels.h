@@ -2399,6 +2399,118 @@ __global__ __launch_bounds__(FILM_T) void film_deposit_kernel(FilmDepositArgs A)
     }
 }
 
+// ---- regeneration (vk_regen_*): a batch refilled from a film's window as its paths retire.  A bounce is regen_emit_kernel (the top-up),
+// trace_paths_kernel, shade_hits_kernel, the compaction's count and scan passes as they are, and regen_move_kernel.
+// regen_emit_kernel: film_emit_kernel's body with a first number and a slot offset: lane j < m starts path q = first + j of the window's
+// sequence — q = (row-major pixel of the window) * n_samples + k, the id vk_film_emit gives it — in slot slot0 + j, id q.  q < 2^32 (the
+// host refuses a longer window), slot0 + m <= the batch's capacity.
+struct RegenEmitArgs {
+    RenderConsts C;          // the film's camera, frame and seed
+    uint4 *rays;             // vk_ray[capacity]
+    uint4 *states;           // vk_path_state[capacity]
+    uint32_t *ids;           // [capacity]: the buffer that holds the live ids of this bounce
+    uint32_t x0, y0, win_width, first_sample, n_samples;
+    uint32_t first, slot0, m;
+};
+__global__ __launch_bounds__(FILM_T) void regen_emit_kernel(RegenEmitArgs A) {
+    const uint32_t j = blockIdx.x * FILM_T + threadIdx.x;
+    if (j >= A.m) return;
+    const uint32_t q = A.first + j;
+    const uint32_t wp = q / A.n_samples, k = q - wp * A.n_samples;
+    const uint32_t wy = wp / A.win_width, wx = wp - wy * A.win_width;
+    Lane L;
+    V3 o, d;
+    float time;
+    start_sample_core(L, A.C, A.x0 + wx, A.y0 + wy, A.first_sample + k, o, d, time);
+    const size_t slot = (size_t)A.slot0 + j;
+    uint4 *r = A.rays + slot * 2u, *s = A.states + slot * 3u;
+    r[0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), 0x7F800000u /* tmax = +INFINITY */);
+    r[1] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(time));
+    s[0] = make_uint4(__float_as_uint(L.thr.x), __float_as_uint(L.thr.y), __float_as_uint(L.thr.z), L.depth);
+    s[1] = make_uint4(__float_as_uint(L.acc.x), __float_as_uint(L.acc.y), __float_as_uint(L.acc.z), L.rng.ctr);
+    s[2] = make_uint4((uint32_t)A.C.seed, (uint32_t)(A.C.seed >> 32), L.pixel, L.sample);
+    A.ids[slot] = q;
+}
+
+// regen_move_kernel: the compaction's third pass and the film's deposit in one, behind paths_count_kernel and paths_scan_kernel on the same
+// records.  A survivor does what paths_move_kernel does: its slot is wg_offsets[workgroup] + the survivors of the workgroup's earlier waves
+// (LDS) + its rank among its wave's (mbcnt); ray, state and id go there, 16-byte accesses.  A retired item is deposited there and then,
+// from its record (acc in quarter 3, pixel in quarter 4), by film_deposit_kernel's arithmetic in its PLAIN form: MISS, ENDED and CULLED at
+// the pixel the state names, the finite filter, to_fixed_small at or below ACCUM_SMALL, else to_fixed with the film's clamp, three 64-bit
+// integer atomics; the four counters are ballots, one atomic per wave and non-zero counter.  Nothing is stored under the id, which may
+// exceed the batch's capacity.  No lane leaves before the ballots.
+struct RegenMoveArgs {
+    const uint4 *items;            // vk_shaded[n]
+    const uint32_t *ids;           // [n]
+    uint64_t n;
+    uint4 *rays;                   // vk_ray[survivors]
+    uint4 *states;                 // vk_path_state[survivors]
+    uint32_t *ids_out;             // [survivors]
+    const uint32_t *wg_offsets;    // [n_wg], paths_scan_kernel's
+    unsigned long long *sums;      // the film's [n_pixels * 3]
+    unsigned long long *counters;  // the film's deposited, dropped, clamped, skipped
+    uint32_t n_pixels;
+    float accum_clamp;             // accum_clamp_for(the film's samples_per_pixel)
+};
+__global__ __launch_bounds__(PATHS_T) void regen_move_kernel(RegenMoveArgs A) {
+    __shared__ uint32_t wc[PATHS_T / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * PATHS_T + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const bool in = i < A.n;
+    const uint4 *item = A.items + i * 6u;
+    uint4 tail = make_uint4((uint32_t)VK_SHADE_BAD_HIT, 0u, 0u, 0u);             // status, lobe, pad
+    if (in) tail = item[5];
+    const bool go = in && tail.x == (uint32_t)VK_SHADE_SCATTERED;
+    const unsigned long long m = __ballot(go);
+    if (lane == 0) wc[w] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (go) {
+        uint32_t slot = A.wg_offsets[blockIdx.x];
+        for (uint32_t k = 0; k < w; k++) slot += wc[k];
+        slot += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (slot < A.n) {                                        // (always: the offsets count these very items)
+            uint4 *r = A.rays + (size_t)slot * 2u, *s = A.states + (size_t)slot * 3u;
+            r[0] = item[0]; r[1] = item[1];
+            s[0] = item[2]; s[1] = item[3]; s[2] = item[4];
+            A.ids_out[slot] = A.ids[i];
+        }
+    }
+    const bool gone = in && !go;
+    uint32_t pixel = 0xFFFFFFFFu;
+    float ax = 0.0f, ay = 0.0f, az = 0.0f;
+    if (gone) {
+        const uint4 s1 = item[3], s2 = item[4];
+        ax = __uint_as_float(s1.x); ay = __uint_as_float(s1.y); az = __uint_as_float(s1.z);
+        pixel = s2.z;
+    }
+    const uint32_t status = tail.x;
+    const bool retired = status == (uint32_t)VK_SHADE_MISS || status == (uint32_t)VK_SHADE_ENDED || status == (uint32_t)VK_PATHS_CULLED;
+    const bool ours = gone && retired && pixel < A.n_pixels;
+    const bool finite = isfinite(ax) && isfinite(ay) && isfinite(az);
+    const bool deposit = ours && finite;
+    const float big = fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az));
+    const bool large = big > ACCUM_SMALL;
+    const unsigned long long m_dep = __ballot(deposit), m_drop = __ballot(ours && !finite);
+    const unsigned long long m_clamp = __ballot(deposit && large && big > A.accum_clamp), m_skip = __ballot(gone && !ours);
+    if (lane == 0u) {
+        if (m_dep) atomicAdd(A.counters + 0, (unsigned long long)__popcll(m_dep));
+        if (m_drop) atomicAdd(A.counters + 1, (unsigned long long)__popcll(m_drop));
+        if (m_clamp) atomicAdd(A.counters + 2, (unsigned long long)__popcll(m_clamp));
+        if (m_skip) atomicAdd(A.counters + 3, (unsigned long long)__popcll(m_skip));
+    }
+    if (deposit) {
+        unsigned long long fx, fy, fz;
+        if (!large) {
+            fx = (unsigned long long)to_fixed_small(ax); fy = (unsigned long long)to_fixed_small(ay); fz = (unsigned long long)to_fixed_small(az);
+        } else {
+            fx = (unsigned long long)to_fixed(ax, A.accum_clamp); fy = (unsigned long long)to_fixed(ay, A.accum_clamp);
+            fz = (unsigned long long)to_fixed(az, A.accum_clamp);
+        }
+        unsigned long long *a = A.sums + (size_t)pixel * 3u;
+        atomicAdd(a + 0, fx); atomicAdd(a + 1, fy); atomicAdd(a + 2, fz);
+    }
+}
+
 #ifdef VK_DEBUG_LIB
 // device math probe (tests: GPU transcendental/draw functions are bit-identical to the host's)
 __global__ void math_probe_kernel(int op, const float *a, const float *b, float *out, size_t n) {

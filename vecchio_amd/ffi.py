@@ -234,6 +234,13 @@ class FilmInfo(C.Structure):
 VK_DEBUG_FILM_DEPOSIT_PLAIN, VK_DEBUG_FILM_DEPOSIT_RUNS = 0, 1
 
 
+class RegenInfo(C.Structure):
+    """vk_regen_info (vk_regen_step)"""
+    _fields_ = [("traced", C.c_uint64), ("live", C.c_uint64), ("remaining", C.c_uint64), ("emitted", C.c_uint64), ("missed", C.c_uint64),
+                ("ended", C.c_uint64), ("bad", C.c_uint64), ("bounces", C.c_uint32), ("kernel_launches", C.c_uint32),
+                ("kernel_ms", C.c_double), ("seconds", C.c_double)]
+
+
 class DebugStreamKey(C.Structure):
     """vk_debug_stream_key of include/vecchio_amd_debug.h (vk_debug_trace_radiance_samples)"""
     _fields_ = [("seed", C.c_uint64), ("pixel", C.c_uint32), ("sample", C.c_uint32), ("ctr", C.c_uint32), ("_pad", C.c_uint32)]
@@ -339,6 +346,7 @@ DEVICE_SYMBOLS = [
     "vk_paths_create", "vk_paths_begin", "vk_paths_step", "vk_paths_read", "vk_paths_cull", "vk_paths_results", "vk_paths_get_info",
     "vk_paths_destroy",
     "vk_film_create", "vk_film_emit", "vk_film_deposit", "vk_film_resolve", "vk_film_reset", "vk_film_get_info", "vk_film_destroy",
+    "vk_regen_begin", "vk_regen_step", "vk_regen_cull",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -460,6 +468,12 @@ def _bind(lib):
     lib.vk_film_get_info.argtypes = [C.c_void_p, C.POINTER(FilmInfo)]
     lib.vk_film_destroy.restype = None
     lib.vk_film_destroy.argtypes = [C.c_void_p]
+    lib.vk_regen_begin.restype = C.c_int
+    lib.vk_regen_begin.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(FilmWindow)]
+    lib.vk_regen_step.restype = C.c_int
+    lib.vk_regen_step.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RegenInfo)]
+    lib.vk_regen_cull.restype = C.c_int
+    lib.vk_regen_cull.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vk_probe_eval.restype = C.c_int
     lib.vk_probe_eval.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.vk_trace_occluded_device.restype = C.c_int
@@ -516,6 +530,8 @@ def _bind(lib):
     lib.vk_debug_film_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 3)]
     lib.vk_debug_film_deposit_form.restype = C.c_int
     lib.vk_debug_film_deposit_form.argtypes = [C.c_void_p, C.c_int]
+    lib.vk_debug_regen_last_ms.restype = C.c_int
+    lib.vk_debug_regen_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 4)]
     lib.vk_debug_trace_occluded_device.restype = C.c_int
     lib.vk_debug_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_uint32, C.c_uint32]

@@ -138,6 +138,10 @@ pub struct vk_film_window { pub x0: u32, pub y0: u32, pub width: u32, pub height
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_film_info { pub width: u32, pub height: u32, pub samples_per_pixel: u32, pub _pad: u32, pub emitted: u64, pub deposited: u64, pub dropped: u64, pub clamped: u64, pub skipped: u64, pub deposits: u64 }
 
+// regeneration: what one vk_regen_step did
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_regen_info { pub traced: u64, pub live: u64, pub remaining: u64, pub emitted: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
+
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_temporal_params { pub width: u32, pub height: u32, pub max_history: u32, pub depth_tol: f32, pub normal_cos_min: f32, pub albedo_floor: f32, pub flags: u32 }
 
@@ -236,6 +240,11 @@ extern "C" {
     pub fn vk_film_reset(film: *mut vk_film, cam: *const vk_camera) -> c_int;
     pub fn vk_film_get_info(film: *mut vk_film, out: *mut vk_film_info) -> c_int;
     pub fn vk_film_destroy(film: *mut vk_film);
+    // regeneration (additive symbols of ABI 7): begin a run of a window of any size through a batch of any capacity, then step until
+    // vk_regen_info.live and .remaining are both 0; the retired paths are deposited into the film as they retire
+    pub fn vk_regen_begin(film: *mut vk_film, batch: *mut vk_paths, win: *const vk_film_window) -> c_int;
+    pub fn vk_regen_step(film: *mut vk_film, batch: *mut vk_paths, max_bounces: u32, info: *mut vk_regen_info) -> c_int;
+    pub fn vk_regen_cull(film: *mut vk_film, batch: *mut vk_paths, keep: *const u8, scale: *const f32) -> c_int;
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

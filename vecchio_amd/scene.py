@@ -945,6 +945,57 @@ class Film:
                     self.deposit(batch)
         return self.resolve()
 
+    def regen_begin(self, batch, x0, y0, w, h, first_sample=0, n_samples=1):
+        """Put `batch` into its regenerating state for the window (vk_regen_begin): its w * h * n_samples paths, numbered as emit() numbers
+        them, will go through the batch whatever its capacity.  Nothing is emitted yet."""
+        win = ffi.FilmWindow(x0, y0, w, h, first_sample, n_samples)
+        check(self._lib, self._lib.vk_regen_begin(self._h, batch._h, C.byref(win)))
+
+    def regen_step(self, batch, max_bounces=1):
+        """Run bounces of the regenerating `batch` until its run is finished or max_bounces are run (vk_regen_step): each tops the batch up
+        from the window, traces, shades, deposits the retired paths into the film and compacts the survivors.  The call's ffi.RegenInfo;
+        the run is finished when its live and remaining are both 0."""
+        info = ffi.RegenInfo()
+        check(self._lib, self._lib.vk_regen_step(self._h, batch._h, max_bounces, C.byref(info)))
+        return info
+
+    def regen_cull(self, batch, keep, scale=None):
+        """PathBatch.cull()'s rule on a regenerating batch between two steps (vk_regen_cull): keep and scale in live order; a culled path
+        is deposited as ffi.VK_PATHS_CULLED with its state as it stands."""
+        n = int(batch.info().live)
+        keep = np.ascontiguousarray(keep, np.uint8).reshape(-1)
+        assert keep.shape[0] == n
+        if scale is not None:
+            scale = np.ascontiguousarray(scale, np.float32).reshape(-1)
+            assert scale.shape[0] == n
+        check(self._lib, self._lib.vk_regen_cull(self._h, batch._h, C.c_void_p(keep.ctypes.data if n else None),
+                                                 C.c_void_p(scale.ctypes.data) if scale is not None and n else None))
+
+    def render_regen(self, batch, cull=None):
+        """The whole frame through `batch` by regenerating runs: one run over the whole frame per range of samples, the ranges chosen so
+        that a run has fewer than 2^32 paths (one run, unless width * height * samples_per_pixel reaches that).  cull, where given, is
+        called with the batch between two bounces while anything is live (PathBatch.read() and regen_cull() are its tools).  Returns
+        resolve()."""
+        p = self.params
+        spp = p.samples_per_pixel
+        ns = max(1, min(spp, (2 ** 32 - 1) // (p.width * p.height)))
+        for s0 in range(0, spp, ns):
+            self.regen_begin(batch, 0, 0, p.width, p.height, s0, min(ns, spp - s0))
+            while True:
+                info = self.regen_step(batch, 1 if cull is not None else 0xFFFFFFFF)
+                if info.live == 0 and info.remaining == 0:
+                    break
+                if cull is not None and info.live:
+                    cull(batch)
+        return self.resolve()
+
+    def regen_last_ms(self, batch):
+        """(top-up, trace, shade, compaction with deposit) device milliseconds of the regenerating batch's last bounce
+        (vk_debug_regen_last_ms, a test hook)"""
+        ms = (C.c_double * 4)()
+        check(self._lib, self._lib.vk_debug_regen_last_ms(batch._h, C.byref(ms)))
+        return tuple(ms)
+
     def debug_sums(self):
         """The raw sums (vk_debug_film_sums, a test hook): int64 (height, width, 3) in 2^-26 units"""
         p = self.params
