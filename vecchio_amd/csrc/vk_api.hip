@@ -2504,6 +2504,19 @@ struct vk_paths {
     vk_film_window regen_win{};
     uint64_t regen_next = 0, regen_total = 0;       // the window's paths [0, regen_next) are emitted, of regen_total
 };
+// a film (vk_film_*, below): here because a regenerating batch's compaction deposits into one
+struct vk_film {
+    vk_scene *scene = nullptr;                      // as handed to vk_film_create
+    vk_camera cam;
+    vk_render_params params;
+    DeviceBuffer<unsigned long long> sums;          // [width * height * 3], two's complement
+    DeviceBuffer<unsigned long long> counters;      // the counter record: deposited, dropped, clamped, skipped
+    DeviceBuffer<float> out;                        // the resolved frame on its way to the host (allocated by the first vk_film_resolve)
+    Event ev[6];                                    // around the last emit, deposit and resolve
+    bool timed[3] = {false, false, false};
+    uint64_t emitted = 0, deposits = 0;
+    bool runs = FILM_DEPOSIT_RUNS;                  // the deposit's form (vk_debug_film_deposit_form)
+};
 
 namespace {
 
@@ -2512,12 +2525,23 @@ static_assert(VK_PATHS_LIVE == VK_SHADE_SCATTERED && VK_PATHS_CULLED == PATHS_ST
 
 inline uint32_t paths_wgs(uint64_t n) { return (uint32_t)((n + PATHS_T - 1) / PATHS_T); }
 
-// the compaction's three launches for A.n > 0 items (A.n_wg set here)
-int enqueue_compact(CompactArgs A, hipStream_t st) {
+// the compaction's three launches for A.n > 0 items (A.n_wg set here).  With a film the third is regen_move_kernel, which deposits what
+// retires into the film's sums instead of storing it under its id.
+int enqueue_compact(CompactArgs A, hipStream_t st, const vk_film *film = nullptr) {
     A.n_wg = paths_wgs(A.n);
     hipLaunchKernelGGL(paths_count_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, st, A);
     hipLaunchKernelGGL(paths_scan_kernel, dim3(1), dim3(PATHS_SCAN_T), 0, st, A);
-    hipLaunchKernelGGL(paths_move_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, st, A);
+    if (!film) {
+        hipLaunchKernelGGL(paths_move_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, st, A);
+    } else {
+        RegenMoveArgs M;
+        memset(&M, 0, sizeof(M));
+        M.items = A.items; M.ids = A.ids; M.n = A.n; M.rays = A.rays; M.states = A.states; M.ids_out = A.ids_out; M.wg_offsets = A.wg_offsets;
+        M.sums = film->sums; M.counters = film->counters;
+        M.n_pixels = film->params.width * film->params.height;
+        M.accum_clamp = accum_clamp_for(film->params.samples_per_pixel);
+        hipLaunchKernelGGL(regen_move_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, st, M);
+    }
     HIP_TRY(hipGetLastError());
     return VK_OK;
 }
@@ -2539,22 +2563,92 @@ int enqueue_trace_paths(vk_scene *q, const void *d_rays, void *d_states, void *d
     return VK_OK;
 }
 
+// a compaction's arguments from its device buffers (n_wg is enqueue_compact's)
+CompactArgs compact_args(const void *items, const uint32_t *ids, uint64_t n, uint64_t n_ids, void *rays, void *states, uint32_t *ids_out,
+                         void *result_state, uint32_t *result_status, uint32_t *wg_counts, uint32_t *wg_offsets, unsigned long long *counts) {
+    return CompactArgs{static_cast<const uint4 *>(items), ids, n, n_ids, static_cast<uint4 *>(rays), static_cast<uint4 *>(states), ids_out,
+                       static_cast<uint4 *>(result_state), result_status, wg_counts, wg_offsets, counts, 0u};
+}
 // the handle's compaction of shaded[0, live) and ids[cur] into rays, states and ids[cur ^ 1]; then the counts record, read back (which
 // waits for everything enqueued): live and retired[] follow it
 CompactArgs paths_compact_args(vk_paths *p) {
-    CompactArgs A;
-    memset(&A, 0, sizeof(A));
-    A.items = reinterpret_cast<const uint4 *>(p->shaded.get()); A.ids = p->ids[p->cur]; A.n = p->live; A.n_ids = p->capacity;
-    A.rays = reinterpret_cast<uint4 *>(p->rays.get()); A.states = reinterpret_cast<uint4 *>(p->states.get()); A.ids_out = p->ids[p->cur ^ 1u];
-    A.result_state = reinterpret_cast<uint4 *>(p->result_state.get()); A.result_status = p->result_status;
-    A.wg_counts = p->wg_counts; A.wg_offsets = p->wg_offsets; A.counts = p->counts;
-    return A;
+    return compact_args(p->shaded, p->ids[p->cur], p->live, p->capacity, p->rays, p->states, p->ids[p->cur ^ 1u], p->result_state,
+                        p->result_status, p->wg_counts, p->wg_offsets, p->counts);
 }
 int paths_take_counts(vk_paths *p, unsigned long long c[5]) {
     HIP_TRY(hipMemcpy(c, p->counts, PATHS_STATUSES * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     p->cur ^= 1u;
     p->live = c[VK_SHADE_SCATTERED];
     for (uint32_t s = 0; s < PATHS_STATUSES; s++) if (s != (uint32_t)VK_SHADE_SCATTERED) p->retired[s] += c[s];
+    return VK_OK;
+}
+
+// a batch as a begin leaves it: `started` paths of which `live` are live, nothing retired, no bounce run, not regenerating.  Called behind
+// every check and every launch of a begin that can fail: a refused call leaves the batch as it was.
+void paths_reset(vk_paths *p, const vk_shade_params &sp, uint64_t started, uint64_t live) {
+    p->sp = sp; p->begun = true; p->deposited = false; p->cur = 0u; p->started = started; p->live = live; p->bounces = 0u;
+    for (uint64_t &r : p->retired) r = 0u;
+    p->regen = false; p->regen_film = nullptr; p->regen_win = vk_film_window{}; p->regen_next = 0u; p->regen_total = 0u;
+}
+
+// what the bounces of one step call add up to: vk_paths_step and vk_regen_step copy it into their info structs
+struct BounceTally {
+    uint64_t traced, missed, ended, bad;
+    double kernel_ms;
+    uint32_t launches, bounces;
+};
+// one bounce of p's live paths (> 0) on the null stream, behind ev0, which the caller has recorded: trace, shade and the compaction — with
+// a film, the one that deposits what retires — five launches, then the counts record and the time from ev0 to ev1
+int paths_bounce(vk_paths *p, vk_scene *q, const vk_film *film, BounceTally &T) {
+    const uint64_t n = p->live;
+    int rc;
+    if ((rc = enqueue_trace_paths(q, p->rays, p->states, p->hits, n, nullptr)) != VK_OK) return rc;
+    HIP_TRY(hipEventRecord(p->ev_t, nullptr));
+    if ((rc = enqueue_shade(q, &p->sp, p->rays, p->hits, p->states, n, p->shaded, nullptr)) != VK_OK) return rc;
+    HIP_TRY(hipEventRecord(p->ev_s, nullptr));
+    if ((rc = enqueue_compact(paths_compact_args(p), nullptr, film)) != VK_OK) return rc;
+    HIP_TRY(hipEventRecord(p->ev1, nullptr));
+    unsigned long long c[5];
+    if ((rc = paths_take_counts(p, c)) != VK_OK) return rc;
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
+    T.kernel_ms += (double)ms; T.launches += 5u; T.bounces++; T.traced += n;
+    T.missed += c[VK_SHADE_MISS]; T.ended += c[VK_SHADE_ENDED]; T.bad += c[VK_SHADE_BAD_HIT];
+    p->bounces++;
+    return VK_OK;
+}
+
+// the cull of p's live paths (> 0, keep not null): the marking pass writes them as the records the compaction reads, and the same
+// compaction runs — with a film, the one that deposits the culled paths
+int paths_cull(vk_paths *p, const vk_film *film, const uint8_t *keep, const float *scale) {
+    const uint64_t n = p->live;
+    HIP_TRY(hipSetDevice(first_part(p->scene)->device));
+    // keep and scale ride in the hit records' buffer, which holds nothing between two bounces: 5 of its 64 bytes a path
+    uint8_t *d_keep = p->hits;
+    float *d_scale = reinterpret_cast<float *>(p->hits.get() + (((size_t)p->capacity + 15u) & ~(size_t)15u));
+    HIP_TRY(hipMemcpy(d_keep, keep, (size_t)n, hipMemcpyHostToDevice));
+    if (scale) HIP_TRY(hipMemcpy(d_scale, scale, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(paths_cull_mark_kernel, dim3(paths_wgs(n)), dim3(PATHS_T), 0, nullptr, reinterpret_cast<const uint4 *>(p->rays.get()),
+                       reinterpret_cast<const uint4 *>(p->states.get()), d_keep, scale ? d_scale : nullptr, n,
+                       reinterpret_cast<uint4 *>(p->shaded.get()));
+    HIP_TRY(hipGetLastError());
+    int rc;
+    if ((rc = enqueue_compact(paths_compact_args(p), nullptr, film)) != VK_OK) return rc;
+    unsigned long long c[5];
+    return paths_take_counts(p, c);
+}
+
+// the hooks vk_debug_paths_last_ms and vk_debug_regen_last_ms: the times between the n + 1 events of p's last bounce
+int paths_parts_ms(vk_paths *p, const Event *const *ev, int n, double *ms) {
+    HIP_TRY(hipSetDevice(first_part(p->scene)->device));
+    HIP_TRY(hipEventSynchronize(p->ev1));
+    double got[4];
+    for (int k = 0; k < n; k++) {
+        float t = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&t, *ev[k], *ev[k + 1]));
+        got[k] = (double)t;
+    }
+    for (int k = 0; k < n; k++) ms[k] = got[k];
     return VK_OK;
 }
 
@@ -2565,12 +2659,14 @@ void paths_free(vk_paths *p) {
     delete p;
 }
 
+// a device buffer of a path batch, a film or the compaction's hook: the first failure of a chain stays in rc and ends it
 template <class T>
-int paths_alloc(DeviceBuffer<T> &b, size_t bytes) {
+void handle_alloc(int &rc, DeviceBuffer<T> &b, size_t bytes) {
+    if (rc != VK_OK) return;
     const hipError_t e = b.alloc(bytes);
-    if (e == hipSuccess) return VK_OK;
+    if (e == hipSuccess) return;
     (void)hipGetLastError();
-    return fail(e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("hipMalloc (path batch): ") + hipGetErrorString(e));
+    rc = fail(e == hipErrorOutOfMemory ? VK_ERR_OOM : VK_ERR_HIP, std::string("hipMalloc (path batch): ") + hipGetErrorString(e));
 }
 
 }  // namespace
@@ -2585,13 +2681,14 @@ int vk_paths_create(vk_scene *scene, uint64_t capacity, vk_paths **out) {
         p->scene = scene; p->capacity = capacity;
         HIP_TRY(hipSetDevice(first_part(scene)->device));
         const size_t n = (size_t)capacity, n_wg = paths_wgs(capacity);
-        int rc;
-        if ((rc = paths_alloc(p->rays, n * sizeof(vk_ray))) != VK_OK || (rc = paths_alloc(p->states, n * sizeof(vk_path_state))) != VK_OK ||
-            (rc = paths_alloc(p->hits, n * sizeof(vk_hit))) != VK_OK || (rc = paths_alloc(p->shaded, n * sizeof(vk_shaded))) != VK_OK ||
-            (rc = paths_alloc(p->ids[0], n * 4u)) != VK_OK || (rc = paths_alloc(p->ids[1], n * 4u)) != VK_OK ||
-            (rc = paths_alloc(p->result_state, n * sizeof(vk_path_state))) != VK_OK || (rc = paths_alloc(p->result_status, n * 4u)) != VK_OK ||
-            (rc = paths_alloc(p->wg_counts, n_wg * PATHS_STATUSES * 4u)) != VK_OK || (rc = paths_alloc(p->wg_offsets, n_wg * 4u)) != VK_OK ||
-            (rc = paths_alloc(p->counts, PATHS_STATUSES * sizeof(unsigned long long))) != VK_OK) return rc;
+        int rc = VK_OK;
+        handle_alloc(rc, p->rays, n * sizeof(vk_ray)); handle_alloc(rc, p->states, n * sizeof(vk_path_state));
+        handle_alloc(rc, p->hits, n * sizeof(vk_hit)); handle_alloc(rc, p->shaded, n * sizeof(vk_shaded));
+        handle_alloc(rc, p->ids[0], n * 4u); handle_alloc(rc, p->ids[1], n * 4u);
+        handle_alloc(rc, p->result_state, n * sizeof(vk_path_state)); handle_alloc(rc, p->result_status, n * 4u);
+        handle_alloc(rc, p->wg_counts, n_wg * PATHS_STATUSES * 4u); handle_alloc(rc, p->wg_offsets, n_wg * 4u);
+        handle_alloc(rc, p->counts, PATHS_STATUSES * sizeof(unsigned long long));
+        if (rc != VK_OK) return rc;
         if ((rc = p->ev0.create()) != VK_OK || (rc = p->ev1.create()) != VK_OK || (rc = p->ev_t.create()) != VK_OK ||
             (rc = p->ev_s.create()) != VK_OK || (rc = p->ev_e.create()) != VK_OK) return rc;
         *out = p.release();
@@ -2618,9 +2715,7 @@ int vk_paths_begin(vk_paths *p, const vk_shade_params *params, const vk_ray *ray
             hipLaunchKernelGGL(paths_iota_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, nullptr, p->ids[0].get(), (uint32_t)n);
             HIP_TRY(hipGetLastError());
         }
-        p->sp = *params; p->begun = true; p->deposited = false; p->cur = 0u; p->started = n; p->live = n; p->bounces = 0u;
-        p->regen = false;
-        for (uint64_t &r : p->retired) r = 0u;
+        paths_reset(p, *params, n, n);
         return VK_OK;
     });
 }
@@ -2634,26 +2729,16 @@ int vk_paths_step(vk_paths *p, uint32_t max_bounces, vk_paths_step_info *info) {
         const auto t0 = std::chrono::steady_clock::now();
         vk_scene *q = first_part(p->scene);
         HIP_TRY(hipSetDevice(q->device));
+        BounceTally T{};
+        while (p->live != 0u && T.bounces < max_bounces) {
+            HIP_TRY(hipEventRecord(p->ev0, nullptr));
+            int rc = paths_bounce(p, q, nullptr, T);
+            if (rc != VK_OK) return rc;
+        }
         vk_paths_step_info I;
         memset(&I, 0, sizeof(I));
-        int rc;
-        while (p->live != 0u && I.bounces < max_bounces) {
-            const uint64_t n = p->live;
-            HIP_TRY(hipEventRecord(p->ev0, nullptr));
-            if ((rc = enqueue_trace_paths(q, p->rays, p->states, p->hits, n, nullptr)) != VK_OK) return rc;
-            HIP_TRY(hipEventRecord(p->ev_t, nullptr));
-            if ((rc = enqueue_shade(q, &p->sp, p->rays, p->hits, p->states, n, p->shaded, nullptr)) != VK_OK) return rc;
-            HIP_TRY(hipEventRecord(p->ev_s, nullptr));
-            if ((rc = enqueue_compact(paths_compact_args(p), nullptr)) != VK_OK) return rc;
-            HIP_TRY(hipEventRecord(p->ev1, nullptr));
-            unsigned long long c[5];
-            if ((rc = paths_take_counts(p, c)) != VK_OK) return rc;
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-            I.kernel_ms += (double)ms; I.kernel_launches += 5u; I.bounces++; I.traced += n;
-            I.missed += c[VK_SHADE_MISS]; I.ended += c[VK_SHADE_ENDED]; I.bad += c[VK_SHADE_BAD_HIT];
-            p->bounces++;
-        }
+        I.traced = T.traced; I.missed = T.missed; I.ended = T.ended; I.bad = T.bad;
+        I.bounces = T.bounces; I.kernel_launches = T.launches; I.kernel_ms = T.kernel_ms;
         I.live = p->live;
         I.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (info) *info = I;
@@ -2680,23 +2765,9 @@ int vk_paths_cull(vk_paths *p, const uint8_t *keep, const float *scale) {
         if (!p) return fail(VK_ERR_BAD_ARG, "null path batch");
         if (!p->begun) return fail(VK_ERR_BAD_ARG, "vk_paths_cull before vk_paths_begin");
         if (p->regen) return fail(VK_ERR_BAD_ARG, "vk_paths_cull on a regenerating path batch (vk_regen_cull culls it)");
-        const uint64_t n = p->live;
-        if (n == 0u) return VK_OK;
+        if (p->live == 0u) return VK_OK;
         if (!keep) return fail(VK_ERR_BAD_ARG, "null keep with live paths");
-        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
-        // keep and scale ride in the hit records' buffer, which holds nothing between two bounces: 5 of its 64 bytes a path
-        uint8_t *d_keep = p->hits;
-        float *d_scale = reinterpret_cast<float *>(p->hits.get() + (((size_t)p->capacity + 15u) & ~(size_t)15u));
-        HIP_TRY(hipMemcpy(d_keep, keep, (size_t)n, hipMemcpyHostToDevice));
-        if (scale) HIP_TRY(hipMemcpy(d_scale, scale, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(paths_cull_mark_kernel, dim3(paths_wgs(n)), dim3(PATHS_T), 0, nullptr, reinterpret_cast<const uint4 *>(p->rays.get()),
-                           reinterpret_cast<const uint4 *>(p->states.get()), d_keep, scale ? d_scale : nullptr, n,
-                           reinterpret_cast<uint4 *>(p->shaded.get()));
-        HIP_TRY(hipGetLastError());
-        int rc;
-        if ((rc = enqueue_compact(paths_compact_args(p), nullptr)) != VK_OK) return rc;
-        unsigned long long c[5];
-        return paths_take_counts(p, c);
+        return paths_cull(p, nullptr, keep, scale);
     });
 }
 
@@ -2748,14 +2819,8 @@ int vk_debug_paths_last_ms(vk_paths *p, double ms[3]) {
     if (!p || !ms) return fail(VK_ERR_BAD_ARG, "null argument (path batch or ms)");
     return guarded([&]() -> int {
         if (p->bounces == 0u) return fail(VK_ERR_BAD_ARG, "no bounce has run since vk_paths_begin");
-        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
-        HIP_TRY(hipEventSynchronize(p->ev1));
-        float t = 0.0f, s = 0.0f, c = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&t, p->ev0, p->ev_t));
-        HIP_TRY(hipEventElapsedTime(&s, p->ev_t, p->ev_s));
-        HIP_TRY(hipEventElapsedTime(&c, p->ev_s, p->ev1));
-        ms[0] = (double)t; ms[1] = (double)s; ms[2] = (double)c;
-        return VK_OK;
+        const Event *ev[4] = {&p->ev0, &p->ev_t, &p->ev_s, &p->ev1};
+        return paths_parts_ms(p, ev, 3, ms);
     });
 }
 
@@ -2775,13 +2840,13 @@ int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32
         DeviceBuffer<uint8_t> d_items, d_rays, d_states, d_rstate;
         DeviceBuffer<uint32_t> d_ids, d_ids_out, d_rstatus, d_wc, d_wo;
         DeviceBuffer<unsigned long long> d_counts;
-        int rc;
-        if ((rc = paths_alloc(d_items, m * sizeof(vk_shaded))) != VK_OK || (rc = paths_alloc(d_ids, m * 4u)) != VK_OK ||
-            (rc = paths_alloc(d_rays, m * sizeof(vk_ray))) != VK_OK || (rc = paths_alloc(d_states, m * sizeof(vk_path_state))) != VK_OK ||
-            (rc = paths_alloc(d_ids_out, m * 4u)) != VK_OK || (rc = paths_alloc(d_rstate, k * sizeof(vk_path_state))) != VK_OK ||
-            (rc = paths_alloc(d_rstatus, k * 4u)) != VK_OK || (rc = paths_alloc(d_wc, n_wg * PATHS_STATUSES * 4u)) != VK_OK ||
-            (rc = paths_alloc(d_wo, n_wg * 4u)) != VK_OK || (rc = paths_alloc(d_counts, PATHS_STATUSES * sizeof(unsigned long long))) != VK_OK)
-            return rc;
+        int rc = VK_OK;
+        handle_alloc(rc, d_items, m * sizeof(vk_shaded)); handle_alloc(rc, d_ids, m * 4u);
+        handle_alloc(rc, d_rays, m * sizeof(vk_ray)); handle_alloc(rc, d_states, m * sizeof(vk_path_state));
+        handle_alloc(rc, d_ids_out, m * 4u); handle_alloc(rc, d_rstate, k * sizeof(vk_path_state));
+        handle_alloc(rc, d_rstatus, k * 4u); handle_alloc(rc, d_wc, n_wg * PATHS_STATUSES * 4u);
+        handle_alloc(rc, d_wo, n_wg * 4u); handle_alloc(rc, d_counts, PATHS_STATUSES * sizeof(unsigned long long));
+        if (rc != VK_OK) return rc;
         HIP_TRY(hipMemcpy(d_items, items, m * sizeof(vk_shaded), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_ids, ids, m * 4u, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_rays, rays, m * sizeof(vk_ray), hipMemcpyHostToDevice));
@@ -2789,12 +2854,7 @@ int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32
         HIP_TRY(hipMemcpy(d_ids_out, ids_out, m * 4u, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_rstate, result_state, k * sizeof(vk_path_state), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_rstatus, result_status, k * 4u, hipMemcpyHostToDevice));
-        CompactArgs A;
-        memset(&A, 0, sizeof(A));
-        A.items = reinterpret_cast<const uint4 *>(d_items.get()); A.ids = d_ids; A.n = n; A.n_ids = n_ids;
-        A.rays = reinterpret_cast<uint4 *>(d_rays.get()); A.states = reinterpret_cast<uint4 *>(d_states.get()); A.ids_out = d_ids_out;
-        A.result_state = reinterpret_cast<uint4 *>(d_rstate.get()); A.result_status = d_rstatus;
-        A.wg_counts = d_wc; A.wg_offsets = d_wo; A.counts = d_counts;
+        const CompactArgs A = compact_args(d_items, d_ids, n, n_ids, d_rays, d_states, d_ids_out, d_rstate, d_rstatus, d_wc, d_wo, d_counts);
         if ((rc = enqueue_compact(A, nullptr)) != VK_OK) return rc;
         unsigned long long c[5];
         HIP_TRY(hipMemcpy(c, d_counts, sizeof(c), hipMemcpyDeviceToHost));
@@ -2814,18 +2874,6 @@ int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32
 // parameters.  film_emit_kernel fills a path batch with camera paths, film_deposit_kernel adds a finished batch to the sums, resolve_kernel
 // (vk_render's own, on the whole-image partition) divides; all on the null stream, on buffers and events the handle owns.  Of the batch
 // an emit writes what vk_paths_begin writes; a deposit reads its results and sets its `deposited` flag.
-struct vk_film {
-    vk_scene *scene = nullptr;                      // as handed to vk_film_create
-    vk_camera cam;
-    vk_render_params params;
-    DeviceBuffer<unsigned long long> sums;          // [width * height * 3], two's complement
-    DeviceBuffer<unsigned long long> counters;      // the counter record: deposited, dropped, clamped, skipped
-    DeviceBuffer<float> out;                        // the resolved frame on its way to the host (allocated by the first vk_film_resolve)
-    Event ev[6];                                    // around the last emit, deposit and resolve
-    bool timed[3] = {false, false, false};
-    uint64_t emitted = 0, deposits = 0;
-    bool runs = FILM_DEPOSIT_RUNS;                  // the deposit's form (vk_debug_film_deposit_form)
-};
 
 namespace {
 
@@ -2872,6 +2920,9 @@ RenderConsts film_consts(const vk_film *film) {
     return C;
 }
 
+// a window as the emitting kernels take it
+EmitWindow emit_window(const vk_film_window &w) { return EmitWindow{w.x0, w.y0, w.width, w.first_sample, w.n_samples}; }
+
 // the film's shade parameters: what a batch it fills is shaded with
 vk_shade_params film_shade_params(const vk_film *film) {
     const vk_render_params &P = film->params;
@@ -2898,9 +2949,10 @@ int vk_film_create(vk_scene *scene, const vk_camera *cam, const vk_render_params
         std::unique_ptr<vk_film, void (*)(vk_film *)> f(new vk_film(), film_free);
         f->scene = scene; f->cam = *cam; f->params = *params;
         HIP_TRY(hipSetDevice(first_part(scene)->device));
-        int r;
-        if ((r = paths_alloc(f->sums, (size_t)params->width * params->height * 3u * sizeof(unsigned long long))) != VK_OK ||
-            (r = paths_alloc(f->counters, 4u * sizeof(unsigned long long))) != VK_OK) return r;
+        int r = VK_OK;
+        handle_alloc(r, f->sums, (size_t)params->width * params->height * 3u * sizeof(unsigned long long));
+        handle_alloc(r, f->counters, 4u * sizeof(unsigned long long));
+        if (r != VK_OK) return r;
         for (Event &e : f->ev) if ((r = e.create()) != VK_OK) return r;
         if ((r = film_zero(f.get())) != VK_OK) return r;
         *out = f.release();
@@ -2922,7 +2974,7 @@ int vk_film_emit(vk_film *film, vk_paths *batch, const vk_film_window *win) {
         A.C = film_consts(film);
         A.rays = reinterpret_cast<uint4 *>(batch->rays.get()); A.states = reinterpret_cast<uint4 *>(batch->states.get());
         A.ids = batch->ids[0];
-        A.x0 = win->x0; A.y0 = win->y0; A.win_width = win->width; A.first_sample = win->first_sample; A.n_samples = win->n_samples;
+        A.W = emit_window(*win);
         A.n = (uint32_t)n;                           // (capacity <= 2^24)
         HIP_TRY(hipEventRecord(film->ev[0], nullptr));
         hipLaunchKernelGGL(film_emit_kernel, dim3((uint32_t)((n + FILM_T - 1) / FILM_T)), dim3(FILM_T), 0, nullptr, A);
@@ -2930,9 +2982,7 @@ int vk_film_emit(vk_film *film, vk_paths *batch, const vk_film_window *win) {
         HIP_TRY(hipEventRecord(film->ev[1], nullptr));
         film->timed[0] = true;
         film->emitted += n;
-        batch->sp = film_shade_params(film); batch->begun = true; batch->deposited = false; batch->cur = 0u; batch->started = n; batch->live = n; batch->bounces = 0u;
-        batch->regen = false;
-        for (uint64_t &r : batch->retired) r = 0u;
+        paths_reset(batch, film_shade_params(film), n, n);
         return VK_OK;
     });
 }
@@ -2976,7 +3026,8 @@ int vk_film_resolve(vk_film *film, uint32_t n, float *rgb_out) {
         const vk_render_params &P = film->params;
         const size_t bytes = (size_t)P.width * P.height * 3u * sizeof(float);
         if (!film->out) {
-            int rc = paths_alloc(film->out, bytes);
+            int rc = VK_OK;
+            handle_alloc(rc, film->out, bytes);
             if (rc != VK_OK) return rc;
         }
         const uint32_t n_pixels = P.width * P.height;
@@ -3080,21 +3131,9 @@ int regen_check(const vk_film *film, const vk_paths *batch, const char *who) {
     return VK_OK;
 }
 
-// the count and scan passes as they are, then regen_move_kernel, over shaded[0, live)
-int enqueue_regen_compact(vk_film *film, vk_paths *p) {
-    CompactArgs A = paths_compact_args(p);
-    A.n_wg = paths_wgs(A.n);
-    hipLaunchKernelGGL(paths_count_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, nullptr, A);
-    hipLaunchKernelGGL(paths_scan_kernel, dim3(1), dim3(PATHS_SCAN_T), 0, nullptr, A);
-    RegenMoveArgs M;
-    memset(&M, 0, sizeof(M));
-    M.items = A.items; M.ids = A.ids; M.n = A.n; M.rays = A.rays; M.states = A.states; M.ids_out = A.ids_out; M.wg_offsets = A.wg_offsets;
-    M.sums = film->sums; M.counters = film->counters;
-    M.n_pixels = film->params.width * film->params.height;
-    M.accum_clamp = accum_clamp_for(film->params.samples_per_pixel);
-    hipLaunchKernelGGL(regen_move_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, nullptr, M);
-    HIP_TRY(hipGetLastError());
-    return VK_OK;
+// a run whose window is emitted and whose last path has retired: nothing is left to deposit
+void regen_note_finished(vk_paths *p) {
+    if (p->live == 0u && p->regen_next == p->regen_total) p->deposited = true;
 }
 
 }  // namespace
@@ -3110,10 +3149,8 @@ int vk_regen_begin(vk_film *film, vk_paths *batch, const vk_film_window *win) {
         vk_scene *q = first_part(film->scene);
         HIP_TRY(hipSetDevice(q->device));
         if ((rc = ensure_provenance(q)) != VK_OK) return rc;
-        batch->sp = film_shade_params(film); batch->begun = true; batch->deposited = false; batch->cur = 0u; batch->started = 0u; batch->live = 0u;
-        batch->bounces = 0u;
-        for (uint64_t &r : batch->retired) r = 0u;
-        batch->regen = true; batch->regen_film = film; batch->regen_win = *win; batch->regen_next = 0u; batch->regen_total = total;
+        paths_reset(batch, film_shade_params(film), 0u, 0u);
+        batch->regen = true; batch->regen_film = film; batch->regen_win = *win; batch->regen_total = total;
         return VK_OK;
     });
 }
@@ -3127,48 +3164,36 @@ int vk_regen_step(vk_film *film, vk_paths *batch, uint32_t max_bounces, vk_regen
         vk_paths *p = batch;
         vk_scene *q = first_part(p->scene);
         HIP_TRY(hipSetDevice(q->device));
-        vk_regen_info I;
-        memset(&I, 0, sizeof(I));
-        while (I.bounces < max_bounces) {
+        BounceTally T{};
+        uint64_t emitted = 0;
+        while (T.bounces < max_bounces) {
             // 1. top up: the window's next m paths behind the survivors, ids = their numbers (above every live id: live order stays ascending)
             const uint64_t m = std::min(p->capacity - p->live, p->regen_total - p->regen_next);
             if (p->live + m == 0u) break;                                // 2. the run is finished
             HIP_TRY(hipEventRecord(p->ev0, nullptr));
-            uint32_t launches = 5u;
             if (m != 0u) {
                 RegenEmitArgs A;
                 memset(&A, 0, sizeof(A));
                 A.C = film_consts(film);
                 A.rays = reinterpret_cast<uint4 *>(p->rays.get()); A.states = reinterpret_cast<uint4 *>(p->states.get());
                 A.ids = p->ids[p->cur];                                  // (the last compaction's flip is behind us)
-                const vk_film_window &w = p->regen_win;
-                A.x0 = w.x0; A.y0 = w.y0; A.win_width = w.width; A.first_sample = w.first_sample; A.n_samples = w.n_samples;
+                A.W = emit_window(p->regen_win);
                 A.first = (uint32_t)p->regen_next; A.slot0 = (uint32_t)p->live; A.m = (uint32_t)m;      // (total < 2^32, capacity <= 2^24)
                 hipLaunchKernelGGL(regen_emit_kernel, dim3((uint32_t)((m + FILM_T - 1) / FILM_T)), dim3(FILM_T), 0, nullptr, A);
                 HIP_TRY(hipGetLastError());
                 p->live += m; p->regen_next += m; p->started = p->regen_next;
-                film->emitted += m; I.emitted += m;
-                launches++;
+                film->emitted += m; emitted += m;
+                T.launches++;
             }
             HIP_TRY(hipEventRecord(p->ev_e, nullptr));
-            // 3. trace and shade as vk_paths_step does
-            const uint64_t n = p->live;
-            if ((rc = enqueue_trace_paths(q, p->rays, p->states, p->hits, n, nullptr)) != VK_OK) return rc;
-            HIP_TRY(hipEventRecord(p->ev_t, nullptr));
-            if ((rc = enqueue_shade(q, &p->sp, p->rays, p->hits, p->states, n, p->shaded, nullptr)) != VK_OK) return rc;
-            HIP_TRY(hipEventRecord(p->ev_s, nullptr));
-            // 4. retire into the film and compact
-            if ((rc = enqueue_regen_compact(film, p)) != VK_OK) return rc;
-            HIP_TRY(hipEventRecord(p->ev1, nullptr));
-            unsigned long long c[5];
-            if ((rc = paths_take_counts(p, c)) != VK_OK) return rc;
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-            I.kernel_ms += (double)ms; I.kernel_launches += launches; I.bounces++; I.traced += n;
-            I.missed += c[VK_SHADE_MISS]; I.ended += c[VK_SHADE_ENDED]; I.bad += c[VK_SHADE_BAD_HIT];
-            p->bounces++;
+            // 3. trace, shade, retire into the film and compact
+            if ((rc = paths_bounce(p, q, film, T)) != VK_OK) return rc;
         }
-        if (p->live == 0u && p->regen_next == p->regen_total) p->deposited = true;      // finished: nothing is left to deposit
+        regen_note_finished(p);
+        vk_regen_info I;
+        memset(&I, 0, sizeof(I));
+        I.traced = T.traced; I.emitted = emitted; I.missed = T.missed; I.ended = T.ended; I.bad = T.bad;
+        I.bounces = T.bounces; I.kernel_launches = T.launches; I.kernel_ms = T.kernel_ms;
         I.live = p->live; I.remaining = p->regen_total - p->regen_next;
         I.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (info) *info = I;
@@ -3180,24 +3205,10 @@ int vk_regen_cull(vk_film *film, vk_paths *batch, const uint8_t *keep, const flo
     return guarded([&]() -> int {
         int rc = regen_check(film, batch, "vk_regen_cull");
         if (rc != VK_OK) return rc;
-        vk_paths *p = batch;
-        const uint64_t n = p->live;
-        if (n == 0u) return VK_OK;
+        if (batch->live == 0u) return VK_OK;
         if (!keep) return fail(VK_ERR_BAD_ARG, "null keep with live paths");
-        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
-        // keep and scale ride in the hit records' buffer, as in vk_paths_cull
-        uint8_t *d_keep = p->hits;
-        float *d_scale = reinterpret_cast<float *>(p->hits.get() + (((size_t)p->capacity + 15u) & ~(size_t)15u));
-        HIP_TRY(hipMemcpy(d_keep, keep, (size_t)n, hipMemcpyHostToDevice));
-        if (scale) HIP_TRY(hipMemcpy(d_scale, scale, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(paths_cull_mark_kernel, dim3(paths_wgs(n)), dim3(PATHS_T), 0, nullptr, reinterpret_cast<const uint4 *>(p->rays.get()),
-                           reinterpret_cast<const uint4 *>(p->states.get()), d_keep, scale ? d_scale : nullptr, n,
-                           reinterpret_cast<uint4 *>(p->shaded.get()));
-        HIP_TRY(hipGetLastError());
-        if ((rc = enqueue_regen_compact(film, p)) != VK_OK) return rc;
-        unsigned long long c[5];
-        if ((rc = paths_take_counts(p, c)) != VK_OK) return rc;
-        if (p->live == 0u && p->regen_next == p->regen_total) p->deposited = true;
+        if ((rc = paths_cull(batch, film, keep, scale)) != VK_OK) return rc;
+        regen_note_finished(batch);
         return VK_OK;
     });
 }
@@ -3207,17 +3218,8 @@ int vk_debug_regen_last_ms(vk_paths *p, double ms[4]) {
     if (!p || !ms) return fail(VK_ERR_BAD_ARG, "null argument (path batch or ms)");
     return guarded([&]() -> int {
         if (!p->regen || p->bounces == 0u) return fail(VK_ERR_BAD_ARG, "no bounce has run since vk_regen_begin");
-        HIP_TRY(hipSetDevice(first_part(p->scene)->device));
-        HIP_TRY(hipEventSynchronize(p->ev1));
-        Event *ev[5] = {&p->ev0, &p->ev_e, &p->ev_t, &p->ev_s, &p->ev1};
-        double got[4];
-        for (int k = 0; k < 4; k++) {
-            float t = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&t, *ev[k], *ev[k + 1]));
-            got[k] = (double)t;
-        }
-        for (int k = 0; k < 4; k++) ms[k] = got[k];
-        return VK_OK;
+        const Event *ev[5] = {&p->ev0, &p->ev_e, &p->ev_t, &p->ev_s, &p->ev1};
+        return paths_parts_ms(p, ev, 4, ms);
     });
 }
 

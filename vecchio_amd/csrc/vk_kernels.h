@@ -2239,33 +2239,48 @@ __global__ __launch_bounds__(PATHS_SCAN_T) void paths_scan_kernel(CompactArgs A)
         A.counts[threadIdx.x] = t;
     }
 }
-__global__ __launch_bounds__(PATHS_T) void paths_move_kernel(CompactArgs A) {
-    __shared__ uint32_t wc[PATHS_T / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * PATHS_T + threadIdx.x;
+// The move pass's survivor half, for a lane of paths_move_kernel or regen_move_kernel (A: either's arguments): item i's tail (status,
+// lobe, pad; zeros outside [0, n)) is read and the SCATTERED lanes balloted; the waves' counts meet in wc[] behind the ONE barrier, which
+// every lane of the workgroup reaches; a survivor's ray, state and id then go to its slot, 16-byte accesses.  (slot < n always: the
+// offsets count these very items.)  What becomes of a retired item is the caller's.
+struct Moved {
+    bool go;                 // the lane holds a survivor
+    uint4 tail;
+};
+template <class Args>
+__device__ __forceinline__ Moved move_survivor(const Args &A, uint64_t i, uint32_t (&wc)[PATHS_T / 64]) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const bool in = i < A.n;
     const uint4 *item = A.items + i * 6u;
-    uint4 tail = make_uint4(0u, 0u, 0u, 0u);                     // status, lobe, pad
-    uint32_t id = 0u;
-    if (in) { tail = item[5]; id = A.ids[i]; }
-    const bool go = in && tail.x == (uint32_t)VK_SHADE_SCATTERED;
-    const unsigned long long m = __ballot(go);
+    Moved R{false, make_uint4(0u, 0u, 0u, 0u)};
+    if (i < A.n) R.tail = item[5];
+    R.go = i < A.n && R.tail.x == (uint32_t)VK_SHADE_SCATTERED;
+    const unsigned long long m = __ballot(R.go);
     if (lane == 0) wc[w] = (uint32_t)__popcll(m);
     __syncthreads();
-    if (!in) return;
-    if (go) {
+    if (R.go) {
         uint32_t slot = A.wg_offsets[blockIdx.x];
         for (uint32_t k = 0; k < w; k++) slot += wc[k];
         slot += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        if (slot >= A.n) return;                                 // (cannot happen: the offsets count these very items)
-        uint4 *r = A.rays + (size_t)slot * 2u, *s = A.states + (size_t)slot * 3u;
-        r[0] = item[0]; r[1] = item[1];
-        s[0] = item[2]; s[1] = item[3]; s[2] = item[4];
-        A.ids_out[slot] = id;
-    } else if (id < A.n_ids) {
+        if (slot < A.n) {
+            uint4 *r = A.rays + (size_t)slot * 2u, *s = A.states + (size_t)slot * 3u;
+            r[0] = item[0]; r[1] = item[1];
+            s[0] = item[2]; s[1] = item[3]; s[2] = item[4];
+            A.ids_out[slot] = A.ids[i];
+        }
+    }
+    return R;
+}
+__global__ __launch_bounds__(PATHS_T) void paths_move_kernel(CompactArgs A) {
+    __shared__ uint32_t wc[PATHS_T / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * PATHS_T + threadIdx.x;
+    const Moved R = move_survivor(A, i, wc);
+    if (i >= A.n || R.go) return;
+    const uint32_t id = A.ids[i];
+    if (id < A.n_ids) {
+        const uint4 *item = A.items + i * 6u;
         uint4 *s = A.result_state + (size_t)id * 3u;
         s[0] = item[2]; s[1] = item[3]; s[2] = item[4];
-        A.result_status[id] = tail.x;
+        A.result_status[id] = R.tail.x;
     }
 }
 // ids[i] = i: the ids of a batch just begun
@@ -2293,45 +2308,114 @@ __global__ __launch_bounds__(PATHS_T) void paths_cull_mark_kernel(const uint4 *r
     out[5] = make_uint4(kept ? (uint32_t)VK_SHADE_SCATTERED : (uint32_t)VK_PATHS_CULLED, 0xFFFFFFFFu, 0u, 0u);
 }
 
-// ---- films (vk_film_*): the two ends of a frame made of path batches, on the device.
-// film_emit_kernel: one lane per path of a window of the film's frame.  Path id = (row-major pixel of the window) * n_samples + k is
-// sample first_sample + k of that pixel: start_sample_core itself — the render kernel's camera, on the film's frame — gives the ray, and
-// the state resumes the sample's stream right behind the camera's draws.  The lens disk's rejection loop diverges, and may.  The ray (32
-// bytes), the state (48) and the id are written as the batch's begin would have staged them: no iota launch.
+// ---- films (vk_film_*) and regeneration (vk_regen_*): the two ends of a frame made of path batches, on the device.  vk_film_emit fills
+// a batch with film_emit_kernel and vk_film_deposit adds a finished one to the sums with film_deposit_kernel; a regenerating bounce is
+// regen_emit_kernel (the top-up), trace_paths_kernel, shade_hits_kernel, the compaction's count and scan passes as they are, and
+// regen_move_kernel.
 constexpr int FILM_T = 256;
 // the deposit's default form, measured (DESIGN.md "Film"): on C2's frame at 8 samples per pixel RUNS takes 0.79 of PLAIN's time, far
 // beyond the spread of the repetitions; at 1 sample per pixel, where no two neighbours share a pixel, the two are level
 constexpr bool FILM_DEPOSIT_RUNS = true;
+
+// A window of the film's frame and of its samples.  Its paths are numbered q = (row-major pixel of the window) * n_samples + k; path q is
+// sample first_sample + k of that pixel.
+struct EmitWindow {
+    uint32_t x0, y0, win_width, first_sample, n_samples;
+};
+// The start of camera path q of window W, for one lane: start_sample_core itself — the render kernel's camera, on the film's frame —
+// gives the ray, and the state resumes the sample's stream right behind the camera's draws.  The lens disk's rejection loop diverges, and
+// may.  The ray (32 bytes), the state (48) and the id q are written at `slot` as vk_paths_begin would have staged them.
+__device__ __forceinline__ void start_camera_path(const RenderConsts &C, const EmitWindow &W, uint32_t q, size_t slot, uint4 *rays,
+                                                  uint4 *states, uint32_t *ids) {
+    const uint32_t wp = q / W.n_samples, k = q - wp * W.n_samples;
+    const uint32_t wy = wp / W.win_width, wx = wp - wy * W.win_width;
+    Lane L;
+    V3 o, d;
+    float time;
+    start_sample_core(L, C, W.x0 + wx, W.y0 + wy, W.first_sample + k, o, d, time);
+    uint4 *r = rays + slot * 2u, *s = states + slot * 3u;
+    r[0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), 0x7F800000u /* tmax = +INFINITY */);
+    r[1] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(time));
+    s[0] = make_uint4(__float_as_uint(L.thr.x), __float_as_uint(L.thr.y), __float_as_uint(L.thr.z), L.depth);
+    s[1] = make_uint4(__float_as_uint(L.acc.x), __float_as_uint(L.acc.y), __float_as_uint(L.acc.z), L.rng.ctr);
+    s[2] = make_uint4((uint32_t)C.seed, (uint32_t)(C.seed >> 32), L.pixel, L.sample);
+    ids[slot] = q;
+}
+// film_emit_kernel: one lane per path of the window, path i in slot i: no iota launch.
 struct FilmEmitArgs {
     RenderConsts C;          // the film's camera, frame and seed
     uint4 *rays;             // vk_ray[n]
     uint4 *states;           // vk_path_state[n]
     uint32_t *ids;           // [n]
-    uint32_t x0, y0, win_width, first_sample, n_samples, n;
+    EmitWindow W;
+    uint32_t n;
 };
 __global__ __launch_bounds__(FILM_T) void film_emit_kernel(FilmEmitArgs A) {
     const uint32_t i = blockIdx.x * FILM_T + threadIdx.x;
     if (i >= A.n) return;
-    const uint32_t wp = i / A.n_samples, k = i - wp * A.n_samples;
-    const uint32_t wy = wp / A.win_width, wx = wp - wy * A.win_width;
-    Lane L;
-    V3 o, d;
-    float time;
-    start_sample_core(L, A.C, A.x0 + wx, A.y0 + wy, A.first_sample + k, o, d, time);
-    uint4 *r = A.rays + (size_t)i * 2u, *s = A.states + (size_t)i * 3u;
-    r[0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), 0x7F800000u /* tmax = +INFINITY */);
-    r[1] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(time));
-    s[0] = make_uint4(__float_as_uint(L.thr.x), __float_as_uint(L.thr.y), __float_as_uint(L.thr.z), L.depth);
-    s[1] = make_uint4(__float_as_uint(L.acc.x), __float_as_uint(L.acc.y), __float_as_uint(L.acc.z), L.rng.ctr);
-    s[2] = make_uint4((uint32_t)A.C.seed, (uint32_t)(A.C.seed >> 32), L.pixel, L.sample);
-    A.ids[i] = i;
+    start_camera_path(A.C, A.W, i, (size_t)i, A.rays, A.states, A.ids);
+}
+// regen_emit_kernel: lane j < m starts path first + j of the window in slot slot0 + j.  first + m <= 2^32 - 1 (the host refuses a longer
+// window), slot0 + m <= the batch's capacity.
+struct RegenEmitArgs {
+    RenderConsts C;          // the film's camera, frame and seed
+    uint4 *rays;             // vk_ray[capacity]
+    uint4 *states;           // vk_path_state[capacity]
+    uint32_t *ids;           // [capacity]: the buffer that holds the live ids of this bounce
+    EmitWindow W;
+    uint32_t first, slot0, m;
+};
+__global__ __launch_bounds__(FILM_T) void regen_emit_kernel(RegenEmitArgs A) {
+    const uint32_t j = blockIdx.x * FILM_T + threadIdx.x;
+    if (j >= A.m) return;
+    start_camera_path(A.C, A.W, A.first + j, (size_t)A.slot0 + j, A.rays, A.states, A.ids);
 }
 
-// film_deposit_kernel<RUNS>: one lane per started id of a batch with nothing live.  A result retired as VK_SHADE_MISS, VK_SHADE_ENDED
-// or VK_PATHS_CULLED goes to the pixel its STATE names: the render kernel's finite filter (main.rs:192-194), its conversion (to_fixed_small
-// at or below ACCUM_SMALL, else to_fixed with the film's clamp) and three 64-bit integer atomics on the pixel's sums.  A pixel outside the
-// frame and every other status is skipped without touching memory by that index.  The four counters — deposited, dropped, clamped,
-// skipped — are ballots, added once per wave.  Only the second and third quarter of the state (acc, pixel) are loaded.
+// The deposit of one lane's candidate — a path that has left its batch; cand = the lane holds one — from its status and the second and
+// third quarter of its state (s1: acc, s2: pixel in .z).  A candidate retired as VK_SHADE_MISS, VK_SHADE_ENDED or VK_PATHS_CULLED goes
+// to the pixel its STATE names: the render kernel's finite filter (main.rs:192-194) and its conversion (to_fixed_small at or below
+// ACCUM_SMALL, else to_fixed with the film's clamp); the caller adds the three fixed values to the pixel's sums by 64-bit integer
+// atomics where `deposit` is set.  A pixel outside the frame and every other status is skipped: `deposit` stays clear and nothing may be
+// touched by that index.  The four counters — deposited, dropped, clamped, skipped (every candidate that is neither of the first two)
+// — are ballots, one atomic per wave and non-zero counter: EVERY lane of the wave must call this, from uniform control flow.
+struct Deposit {
+    bool deposit;
+    uint32_t pixel;
+    unsigned long long fx, fy, fz;
+};
+__device__ __forceinline__ Deposit deposit_lane(bool cand, uint32_t status, uint4 s1, uint4 s2, uint32_t n_pixels, float accum_clamp,
+                                                unsigned long long *counters) {
+    const float ax = __uint_as_float(s1.x), ay = __uint_as_float(s1.y), az = __uint_as_float(s1.z);
+    const bool retired = status == (uint32_t)VK_SHADE_MISS || status == (uint32_t)VK_SHADE_ENDED || status == (uint32_t)VK_PATHS_CULLED;
+    const bool ours = cand && retired && s2.z < n_pixels;
+    const bool finite = isfinite(ax) && isfinite(ay) && isfinite(az);
+    const float big = fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az));
+    const bool large = big > ACCUM_SMALL;
+    Deposit D{ours && finite, s2.z, 0ull, 0ull, 0ull};
+    const unsigned long long m_dep = __ballot(D.deposit), m_drop = __ballot(ours && !finite);
+    const unsigned long long m_clamp = __ballot(D.deposit && large && big > accum_clamp), m_skip = __ballot(cand && !ours);
+    if ((threadIdx.x & 63u) == 0u) {
+        if (m_dep) atomicAdd(counters + 0, (unsigned long long)__popcll(m_dep));
+        if (m_drop) atomicAdd(counters + 1, (unsigned long long)__popcll(m_drop));
+        if (m_clamp) atomicAdd(counters + 2, (unsigned long long)__popcll(m_clamp));
+        if (m_skip) atomicAdd(counters + 3, (unsigned long long)__popcll(m_skip));
+    }
+    if (D.deposit) {
+        if (!large) {
+            D.fx = (unsigned long long)to_fixed_small(ax); D.fy = (unsigned long long)to_fixed_small(ay); D.fz = (unsigned long long)to_fixed_small(az);
+        } else {
+            D.fx = (unsigned long long)to_fixed(ax, accum_clamp); D.fy = (unsigned long long)to_fixed(ay, accum_clamp);
+            D.fz = (unsigned long long)to_fixed(az, accum_clamp);
+        }
+    }
+    return D;
+}
+__device__ __forceinline__ void deposit_add(unsigned long long *sums, const Deposit &D) {
+    unsigned long long *a = sums + (size_t)D.pixel * 3u;
+    atomicAdd(a + 0, D.fx); atomicAdd(a + 1, D.fy); atomicAdd(a + 2, D.fz);
+}
+
+// film_deposit_kernel<RUNS>: one lane per started id of a batch with nothing live; every id below n is a candidate, from its result.
 //   RUNS = false (PLAIN): every depositing lane issues its three atomics.
 //   RUNS = true: a wave's neighbouring lanes that deposit into the same pixel — after an emit, a pixel's n_samples paths — are summed
 //     first, by a segmented suffix sum (six __shfl_down steps, a lane adds its neighbour at distance d while that one lies in its run),
@@ -2348,97 +2432,31 @@ template <bool RUNS>
 __global__ __launch_bounds__(FILM_T) void film_deposit_kernel(FilmDepositArgs A) {
     const uint32_t i = blockIdx.x * FILM_T + threadIdx.x, lane = threadIdx.x & 63u;
     const bool in = i < A.n;
-    uint32_t status = (uint32_t)VK_SHADE_BAD_HIT, pixel = 0xFFFFFFFFu;
-    float ax = 0.0f, ay = 0.0f, az = 0.0f;
-    if (in) {
-        status = A.result_status[i];
-        const uint4 s1 = A.result_state[(size_t)i * 3u + 1u], s2 = A.result_state[(size_t)i * 3u + 2u];
-        ax = __uint_as_float(s1.x); ay = __uint_as_float(s1.y); az = __uint_as_float(s1.z);
-        pixel = s2.z;
-    }
-    const bool retired = status == (uint32_t)VK_SHADE_MISS || status == (uint32_t)VK_SHADE_ENDED || status == (uint32_t)VK_PATHS_CULLED;
-    const bool ours = in && retired && pixel < A.n_pixels;
-    const bool finite = isfinite(ax) && isfinite(ay) && isfinite(az);
-    const bool deposit = ours && finite;
-    const float big = fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az));
-    const bool large = big > ACCUM_SMALL;
-    unsigned long long fx = 0ull, fy = 0ull, fz = 0ull;
-    if (deposit) {
-        if (!large) {
-            fx = (unsigned long long)to_fixed_small(ax); fy = (unsigned long long)to_fixed_small(ay); fz = (unsigned long long)to_fixed_small(az);
-        } else {
-            fx = (unsigned long long)to_fixed(ax, A.accum_clamp); fy = (unsigned long long)to_fixed(ay, A.accum_clamp);
-            fz = (unsigned long long)to_fixed(az, A.accum_clamp);
-        }
-    }
-    const unsigned long long m_dep = __ballot(deposit), m_drop = __ballot(ours && !finite);
-    const unsigned long long m_clamp = __ballot(deposit && large && big > A.accum_clamp), m_skip = __ballot(in && !ours);
-    if (lane == 0u) {
-        if (m_dep) atomicAdd(A.counters + 0, (unsigned long long)__popcll(m_dep));
-        if (m_drop) atomicAdd(A.counters + 1, (unsigned long long)__popcll(m_drop));
-        if (m_clamp) atomicAdd(A.counters + 2, (unsigned long long)__popcll(m_clamp));
-        if (m_skip) atomicAdd(A.counters + 3, (unsigned long long)__popcll(m_skip));
-    }
-    bool issue = deposit;
+    uint32_t status = (uint32_t)VK_SHADE_BAD_HIT;
+    uint4 s1 = make_uint4(0u, 0u, 0u, 0u), s2 = s1;
+    if (in) { status = A.result_status[i]; s1 = A.result_state[(size_t)i * 3u + 1u]; s2 = A.result_state[(size_t)i * 3u + 2u]; }
+    Deposit D = deposit_lane(in, status, s1, s2, A.n_pixels, A.accum_clamp, A.counters);
+    bool issue = D.deposit;
     if (RUNS) {
-        const uint32_t key = deposit ? pixel : 0xFFFFFFFFu;                 // (a depositing pixel is below n_pixels <= 2^26)
+        const uint32_t key = D.deposit ? D.pixel : 0xFFFFFFFFu;             // (a depositing pixel is below n_pixels <= 2^26)
         const uint32_t prev = __shfl_up(key, 1, 64);
         const unsigned long long heads = __ballot(lane == 0u || prev != key);
         const unsigned long long above = heads & ~(((2ull << lane) - 1ull));     // the heads behind this lane (lane 63: none)
         const uint32_t end = above ? (uint32_t)__builtin_ctzll(above) : 64u;    // one past the lane's run
 #pragma unroll
         for (uint32_t d = 1u; d < 64u; d <<= 1) {
-            const unsigned long long vx = __shfl_down(fx, d, 64), vy = __shfl_down(fy, d, 64), vz = __shfl_down(fz, d, 64);
-            if (lane + d < end) { fx += vx; fy += vy; fz += vz; }
+            const unsigned long long vx = __shfl_down(D.fx, d, 64), vy = __shfl_down(D.fy, d, 64), vz = __shfl_down(D.fz, d, 64);
+            if (lane + d < end) { D.fx += vx; D.fy += vy; D.fz += vz; }
         }
-        issue = deposit && ((heads >> lane) & 1ull);
+        issue = D.deposit && ((heads >> lane) & 1ull);
     }
-    if (issue) {
-        unsigned long long *a = A.sums + (size_t)pixel * 3u;
-        atomicAdd(a + 0, fx); atomicAdd(a + 1, fy); atomicAdd(a + 2, fz);
-    }
-}
-
-// ---- regeneration (vk_regen_*): a batch refilled from a film's window as its paths retire.  A bounce is regen_emit_kernel (the top-up),
-// trace_paths_kernel, shade_hits_kernel, the compaction's count and scan passes as they are, and regen_move_kernel.
-// regen_emit_kernel: film_emit_kernel's body with a first number and a slot offset: lane j < m starts path q = first + j of the window's
-// sequence — q = (row-major pixel of the window) * n_samples + k, the id vk_film_emit gives it — in slot slot0 + j, id q.  q < 2^32 (the
-// host refuses a longer window), slot0 + m <= the batch's capacity.
-struct RegenEmitArgs {
-    RenderConsts C;          // the film's camera, frame and seed
-    uint4 *rays;             // vk_ray[capacity]
-    uint4 *states;           // vk_path_state[capacity]
-    uint32_t *ids;           // [capacity]: the buffer that holds the live ids of this bounce
-    uint32_t x0, y0, win_width, first_sample, n_samples;
-    uint32_t first, slot0, m;
-};
-__global__ __launch_bounds__(FILM_T) void regen_emit_kernel(RegenEmitArgs A) {
-    const uint32_t j = blockIdx.x * FILM_T + threadIdx.x;
-    if (j >= A.m) return;
-    const uint32_t q = A.first + j;
-    const uint32_t wp = q / A.n_samples, k = q - wp * A.n_samples;
-    const uint32_t wy = wp / A.win_width, wx = wp - wy * A.win_width;
-    Lane L;
-    V3 o, d;
-    float time;
-    start_sample_core(L, A.C, A.x0 + wx, A.y0 + wy, A.first_sample + k, o, d, time);
-    const size_t slot = (size_t)A.slot0 + j;
-    uint4 *r = A.rays + slot * 2u, *s = A.states + slot * 3u;
-    r[0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), 0x7F800000u /* tmax = +INFINITY */);
-    r[1] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(time));
-    s[0] = make_uint4(__float_as_uint(L.thr.x), __float_as_uint(L.thr.y), __float_as_uint(L.thr.z), L.depth);
-    s[1] = make_uint4(__float_as_uint(L.acc.x), __float_as_uint(L.acc.y), __float_as_uint(L.acc.z), L.rng.ctr);
-    s[2] = make_uint4((uint32_t)A.C.seed, (uint32_t)(A.C.seed >> 32), L.pixel, L.sample);
-    A.ids[slot] = q;
+    if (issue) deposit_add(A.sums, D);
 }
 
 // regen_move_kernel: the compaction's third pass and the film's deposit in one, behind paths_count_kernel and paths_scan_kernel on the same
-// records.  A survivor does what paths_move_kernel does: its slot is wg_offsets[workgroup] + the survivors of the workgroup's earlier waves
-// (LDS) + its rank among its wave's (mbcnt); ray, state and id go there, 16-byte accesses.  A retired item is deposited there and then,
-// from its record (acc in quarter 3, pixel in quarter 4), by film_deposit_kernel's arithmetic in its PLAIN form: MISS, ENDED and CULLED at
-// the pixel the state names, the finite filter, to_fixed_small at or below ACCUM_SMALL, else to_fixed with the film's clamp, three 64-bit
-// integer atomics; the four counters are ballots, one atomic per wave and non-zero counter.  Nothing is stored under the id, which may
-// exceed the batch's capacity.  No lane leaves before the ballots.
+// records.  A survivor moves as in paths_move_kernel; a retired item is a candidate there and then, from its record (acc in quarter 3,
+// pixel in quarter 4), in the deposit's PLAIN form.  Nothing is stored under the id, which may exceed the batch's capacity.  No lane
+// leaves before the ballots.
 struct RegenMoveArgs {
     const uint4 *items;            // vk_shaded[n]
     const uint32_t *ids;           // [n]
@@ -2455,60 +2473,12 @@ struct RegenMoveArgs {
 __global__ __launch_bounds__(PATHS_T) void regen_move_kernel(RegenMoveArgs A) {
     __shared__ uint32_t wc[PATHS_T / 64];
     const uint64_t i = (uint64_t)blockIdx.x * PATHS_T + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const bool in = i < A.n;
-    const uint4 *item = A.items + i * 6u;
-    uint4 tail = make_uint4((uint32_t)VK_SHADE_BAD_HIT, 0u, 0u, 0u);             // status, lobe, pad
-    if (in) tail = item[5];
-    const bool go = in && tail.x == (uint32_t)VK_SHADE_SCATTERED;
-    const unsigned long long m = __ballot(go);
-    if (lane == 0) wc[w] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (go) {
-        uint32_t slot = A.wg_offsets[blockIdx.x];
-        for (uint32_t k = 0; k < w; k++) slot += wc[k];
-        slot += __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        if (slot < A.n) {                                        // (always: the offsets count these very items)
-            uint4 *r = A.rays + (size_t)slot * 2u, *s = A.states + (size_t)slot * 3u;
-            r[0] = item[0]; r[1] = item[1];
-            s[0] = item[2]; s[1] = item[3]; s[2] = item[4];
-            A.ids_out[slot] = A.ids[i];
-        }
-    }
-    const bool gone = in && !go;
-    uint32_t pixel = 0xFFFFFFFFu;
-    float ax = 0.0f, ay = 0.0f, az = 0.0f;
-    if (gone) {
-        const uint4 s1 = item[3], s2 = item[4];
-        ax = __uint_as_float(s1.x); ay = __uint_as_float(s1.y); az = __uint_as_float(s1.z);
-        pixel = s2.z;
-    }
-    const uint32_t status = tail.x;
-    const bool retired = status == (uint32_t)VK_SHADE_MISS || status == (uint32_t)VK_SHADE_ENDED || status == (uint32_t)VK_PATHS_CULLED;
-    const bool ours = gone && retired && pixel < A.n_pixels;
-    const bool finite = isfinite(ax) && isfinite(ay) && isfinite(az);
-    const bool deposit = ours && finite;
-    const float big = fmaxf(fmaxf(fabsf(ax), fabsf(ay)), fabsf(az));
-    const bool large = big > ACCUM_SMALL;
-    const unsigned long long m_dep = __ballot(deposit), m_drop = __ballot(ours && !finite);
-    const unsigned long long m_clamp = __ballot(deposit && large && big > A.accum_clamp), m_skip = __ballot(gone && !ours);
-    if (lane == 0u) {
-        if (m_dep) atomicAdd(A.counters + 0, (unsigned long long)__popcll(m_dep));
-        if (m_drop) atomicAdd(A.counters + 1, (unsigned long long)__popcll(m_drop));
-        if (m_clamp) atomicAdd(A.counters + 2, (unsigned long long)__popcll(m_clamp));
-        if (m_skip) atomicAdd(A.counters + 3, (unsigned long long)__popcll(m_skip));
-    }
-    if (deposit) {
-        unsigned long long fx, fy, fz;
-        if (!large) {
-            fx = (unsigned long long)to_fixed_small(ax); fy = (unsigned long long)to_fixed_small(ay); fz = (unsigned long long)to_fixed_small(az);
-        } else {
-            fx = (unsigned long long)to_fixed(ax, A.accum_clamp); fy = (unsigned long long)to_fixed(ay, A.accum_clamp);
-            fz = (unsigned long long)to_fixed(az, A.accum_clamp);
-        }
-        unsigned long long *a = A.sums + (size_t)pixel * 3u;
-        atomicAdd(a + 0, fx); atomicAdd(a + 1, fy); atomicAdd(a + 2, fz);
-    }
+    const Moved R = move_survivor(A, i, wc);
+    const bool gone = i < A.n && !R.go;
+    uint4 s1 = make_uint4(0u, 0u, 0u, 0u), s2 = s1;
+    if (gone) { s1 = A.items[i * 6u + 3u]; s2 = A.items[i * 6u + 4u]; }
+    const Deposit D = deposit_lane(gone, R.tail.x, s1, s2, A.n_pixels, A.accum_clamp, A.counters);
+    if (D.deposit) deposit_add(A.sums, D);
 }
 
 #ifdef VK_DEBUG_LIB
