@@ -906,7 +906,7 @@ typedef struct vk_paths vk_paths;
 enum { VK_PATHS_LIVE = 1 /* == VK_SHADE_SCATTERED */, VK_PATHS_CULLED = 4 };
 typedef struct vk_paths_info {
     uint64_t capacity, started, live;
-    uint64_t retired[5];              /* by status; [1] stays 0 */
+    uint64_t retired[5];              /* by status; [1] stays 0; [4]: culled, by vk_paths_cull / vk_regen_cull or the handle's roulette */
     uint32_t bounces, _pad;
 } vk_paths_info;
 typedef struct vk_paths_step_info {
@@ -925,6 +925,38 @@ int vk_paths_cull(vk_paths *p, const uint8_t *keep, const float *scale);
 int vk_paths_results(vk_paths *p, vk_path_state *states, uint32_t *status);
 int vk_paths_get_info(vk_paths *p, vk_paths_info *out);
 void vk_paths_destroy(vk_paths *p);
+
+/* ---- Russian roulette on the device for path batches and regenerating runs (additive symbols of ABI 7) -------------------------------
+ * replaces: a throughput-based termination rule done through the host with vk_paths_read, vk_paths_cull / vk_regen_cull and a second
+ * compaction per bounce (89 bytes per live path and bounce over the bus, and a regenerating run stepped one bounce a call).  The rule
+ * is a property of the HANDLE: off after vk_paths_create, kept across vk_paths_begin, vk_film_emit and vk_regen_begin, and settable
+ * between any two calls, mid-batch and mid-run too; it holds from the next bounce on.  It runs inside the compaction's count pass of
+ * every bounce of vk_paths_step and vk_regen_step: no launch and no transfer is added (kernel_launches stays five a bounce, six with a
+ * top-up), and with the rule off every kernel and launch is what it is without these symbols.
+ *   The rule, everything f32, unfused, in this order.  A bounce's shaded record has state.depth after the bounce.  The rule applies to
+ *     a record whose status is VK_SHADE_SCATTERED and whose state.depth >= first_depth:
+ *     m = fmaxf(fmaxf(thr[0], thr[1]), thr[2])      (fmaxf drops a NaN)
+ *     q = fminf(fmaxf(m, q_min), q_max)             (so q lies in [q_min, q_max], for NaN, infinite or negative throughputs too)
+ *     u = the draw of a stream of the rule's own — the path's stream and state.counter are not touched: with key the key of
+ *         rng_for_sample(state.seed ^ 0x52D1E7A9C3B5F04B, state.pixel, state.sample), u = gen_f32 of the value next_u32 returns from
+ *         Rng{key, state.depth - 1}, that stream's draw number `depth`.
+ *     u < q: the path goes on with thr[c] = thr[c] * (1.0f / q) — one IEEE division, then three products: vk_paths_cull's thr * scale
+ *         with scale = 1.0f / q; q == 1 leaves thr bit for bit.
+ *     otherwise the path is retired as VK_PATHS_CULLED with its state after the bounce as it stands, thr unscaled: vk_paths_step
+ *         stores it under its id, vk_regen_step deposits it by vk_film_deposit's rule, vk_paths_info.retired[4] counts it.
+ *   THE CONTRACT: a batch stepped with the rule set is, after every bounce and bit for bit, the batch stepped one bounce a call with
+ *     the rule off that is given vk_paths_read, this rule on the host and vk_paths_cull (vk_regen_cull) after each bounce.
+ *   vk_paths_cull and vk_regen_cull are unchanged and combine with the rule; vk_paths_step_info and vk_regen_info keep their layout.
+ *   vk_roulette_set: rp == NULL turns the rule off.  VK_ERR_BAD_ARG, with the handle's setting left as it was, for a null
+ *     handle, first_depth < 2, flags != 0, a non-finite q_min or q_max, and anything outside 2^-24 <= q_min <= q_max <= 1.
+ *   vk_roulette_get: *enabled = 1 and *out = the rule where one is set, else 0 and zeros.  VK_ERR_BAD_ARG for a null pointer.  */
+typedef struct vk_roulette_params {          /* 16 bytes */
+    uint32_t first_depth;                    /* the first state.depth (after the bounce) the rule applies to; >= 2 */
+    float q_min, q_max;                      /* 2^-24 <= q_min <= q_max <= 1 */
+    uint32_t flags;                          /* 0 */
+} vk_roulette_params;
+int vk_roulette_set(vk_paths *p, const vk_roulette_params *rp);
+int vk_roulette_get(vk_paths *p, vk_roulette_params *out, int *enabled);
 
 /* ---- films: camera paths and frame sums for path batches, on the device (additive symbols of ABI 7) ----------------------------------
  * replaces: the caller's own camera (Camera::get_ray, the lens disk's rejection loop and the stream's counter behind them, restated bit

@@ -108,6 +108,13 @@ int vk_debug_trace_probe_samples(vk_scene *scene, const vk_radiance_params *para
 int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32_t *ids, uint64_t n, uint64_t n_ids, vk_ray *rays,
                            vk_path_state *states, uint32_t *ids_out, vk_path_state *result_state, uint32_t *result_status,
                            uint64_t counts[5]);
+/* vk_debug_compact_paths with the termination rule *rp (vk_roulette_set's checks, in its words; NULL: VK_ERR_BAD_ARG) in the count
+ * pass: roulette_count_kernel, then the scan and the move pass as they are.  The items are staged in a buffer of the hook's own: the
+ * caller's array is not rewritten.  For driving the rule at its edge values and at exact sizes without a scene's paths.  Takes no stream.
+ * In both libraries. */
+int vk_debug_compact_roulette(vk_scene *scene, const vk_roulette_params *rp, const vk_shaded *items, const uint32_t *ids, uint64_t n,
+                              uint64_t n_ids, vk_ray *rays, vk_path_state *states, uint32_t *ids_out, vk_path_state *result_state,
+                              uint32_t *result_status, uint64_t counts[5]);
 /* the device milliseconds of the handle's last bounce, part by part: ms[0] trace_paths_kernel, ms[1] shade_hits_kernel, ms[2] the
  * compaction's three launches (events vk_paths_step records between them; their sum is that bounce's share of kernel_ms).
  * VK_ERR_BAD_ARG for a null pointer or when no bounce has run since vk_paths_begin.  Takes no stream.  In both libraries. */

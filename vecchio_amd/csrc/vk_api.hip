@@ -2503,6 +2503,9 @@ struct vk_paths {
     const vk_film *regen_film = nullptr;            // the run's film, for the identity check only: never dereferenced
     vk_film_window regen_win{};
     uint64_t regen_next = 0, regen_total = 0;       // the window's paths [0, regen_next) are emitted, of regen_total
+    // the termination rule (vk_roulette_set): the handle's, not a batch's — no begin, emit or reset touches it
+    bool roulette = false;
+    vk_roulette_params rr{};
 };
 // a film (vk_film_*, below): here because a regenerating batch's compaction deposits into one
 struct vk_film {
@@ -2525,11 +2528,22 @@ static_assert(VK_PATHS_LIVE == VK_SHADE_SCATTERED && VK_PATHS_CULLED == PATHS_ST
 
 inline uint32_t paths_wgs(uint64_t n) { return (uint32_t)((n + PATHS_T - 1) / PATHS_T); }
 
-// the compaction's three launches for A.n > 0 items (A.n_wg set here).  With a film the third is regen_move_kernel, which deposits what
-// retires into the film's sums instead of storing it under its id.
-int enqueue_compact(CompactArgs A, hipStream_t st, const vk_film *film = nullptr) {
+// the words vk_roulette_set and the compaction's second hook refuse a rule with (nullptr: the rule is fine)
+const char *roulette_refusal(const vk_roulette_params &rp) {
+    if (rp.first_depth < 2u) return "roulette first_depth must be >= 2";
+    if (rp.flags != 0u) return "roulette flags must be 0";
+    if (!std::isfinite(rp.q_min) || !std::isfinite(rp.q_max)) return "roulette q_min and q_max must be finite";
+    if (!(rp.q_min >= 5.9604644775390625e-8f && rp.q_min <= rp.q_max && rp.q_max <= 1.0f)) return "roulette needs 2^-24 <= q_min <= q_max <= 1";
+    return nullptr;
+}
+
+// the compaction's three launches for A.n > 0 items (A.n_wg set here).  With a rule the first is roulette_count_kernel, which ends or
+// rescales the scattered records before it counts them; with a film the third is regen_move_kernel, which deposits what retires into the
+// film's sums instead of storing it under its id.
+int enqueue_compact(CompactArgs A, hipStream_t st, const vk_film *film = nullptr, const vk_roulette_params *rule = nullptr) {
     A.n_wg = paths_wgs(A.n);
-    hipLaunchKernelGGL(paths_count_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, st, A);
+    if (!rule) hipLaunchKernelGGL(paths_count_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, st, A);
+    else hipLaunchKernelGGL(roulette_count_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, st, A, RouletteRule{rule->first_depth, rule->q_min, rule->q_max});
     hipLaunchKernelGGL(paths_scan_kernel, dim3(1), dim3(PATHS_SCAN_T), 0, st, A);
     if (!film) {
         hipLaunchKernelGGL(paths_move_kernel, dim3(A.n_wg), dim3(PATHS_T), 0, st, A);
@@ -2598,7 +2612,8 @@ struct BounceTally {
     uint32_t launches, bounces;
 };
 // one bounce of p's live paths (> 0) on the null stream, behind ev0, which the caller has recorded: trace, shade and the compaction — with
-// a film, the one that deposits what retires — five launches, then the counts record and the time from ev0 to ev1
+// a film, the one that deposits what retires; with the handle's rule set, the one whose count pass applies it — five launches, then the
+// counts record and the time from ev0 to ev1
 int paths_bounce(vk_paths *p, vk_scene *q, const vk_film *film, BounceTally &T) {
     const uint64_t n = p->live;
     int rc;
@@ -2606,7 +2621,7 @@ int paths_bounce(vk_paths *p, vk_scene *q, const vk_film *film, BounceTally &T) 
     HIP_TRY(hipEventRecord(p->ev_t, nullptr));
     if ((rc = enqueue_shade(q, &p->sp, p->rays, p->hits, p->states, n, p->shaded, nullptr)) != VK_OK) return rc;
     HIP_TRY(hipEventRecord(p->ev_s, nullptr));
-    if ((rc = enqueue_compact(paths_compact_args(p), nullptr, film)) != VK_OK) return rc;
+    if ((rc = enqueue_compact(paths_compact_args(p), nullptr, film, p->roulette ? &p->rr : nullptr)) != VK_OK) return rc;
     HIP_TRY(hipEventRecord(p->ev1, nullptr));
     unsigned long long c[5];
     if ((rc = paths_take_counts(p, c)) != VK_OK) return rc;
@@ -2810,6 +2825,21 @@ int vk_paths_get_info(vk_paths *p, vk_paths_info *out) {
     });
 }
 
+// the handle's termination rule: host state only, read by the next bounce's compaction
+int vk_roulette_set(vk_paths *p, const vk_roulette_params *rp) {
+    if (!p) return fail(VK_ERR_BAD_ARG, "null path batch");
+    if (!rp) { p->roulette = false; p->rr = vk_roulette_params{}; return VK_OK; }
+    if (const char *why = roulette_refusal(*rp)) return fail(VK_ERR_BAD_ARG, why);
+    p->rr = *rp; p->roulette = true;
+    return VK_OK;
+}
+
+int vk_roulette_get(vk_paths *p, vk_roulette_params *out, int *enabled) {
+    if (!p || !out || !enabled) return fail(VK_ERR_BAD_ARG, "null argument (path batch, out or enabled)");
+    *out = p->rr; *enabled = p->roulette ? 1 : 0;
+    return VK_OK;
+}
+
 void vk_paths_destroy(vk_paths *p) {
     if (p) paths_free(p);
 }
@@ -2824,11 +2854,13 @@ int vk_debug_paths_last_ms(vk_paths *p, double ms[3]) {
     });
 }
 
-// test hook (vecchio_amd_debug.h): the production compaction on host arrays staged once
-int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32_t *ids, uint64_t n, uint64_t n_ids, vk_ray *rays,
-    vk_path_state *states, uint32_t *ids_out, vk_path_state *result_state, uint32_t *result_status, uint64_t counts[5]) {
+// the two compaction hooks: the production compaction — with a rule, the one whose count pass applies it — on host arrays staged once
+static int debug_compact(vk_scene *scene, const vk_roulette_params *rule, const vk_shaded *items, const uint32_t *ids, uint64_t n,
+    uint64_t n_ids, vk_ray *rays, vk_path_state *states, uint32_t *ids_out, vk_path_state *result_state, uint32_t *result_status,
+    uint64_t counts[5]) {
     return guarded([&]() -> int {
         if (!scene || !counts) return fail(VK_ERR_BAD_ARG, "null argument (scene or counts)");
+        if (rule) if (const char *why = roulette_refusal(*rule)) return fail(VK_ERR_BAD_ARG, why);
         if (n > PATHS_MAX || n_ids > (1ull << 26)) return fail(VK_ERR_BAD_ARG, "n exceeds 2^24 or n_ids 2^26");
         if (n != 0u && (!items || !ids || !rays || !states || !ids_out || !result_state || !result_status))
             return fail(VK_ERR_BAD_ARG, "null array with n > 0");
@@ -2855,7 +2887,7 @@ int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32
         HIP_TRY(hipMemcpy(d_rstate, result_state, k * sizeof(vk_path_state), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_rstatus, result_status, k * 4u, hipMemcpyHostToDevice));
         const CompactArgs A = compact_args(d_items, d_ids, n, n_ids, d_rays, d_states, d_ids_out, d_rstate, d_rstatus, d_wc, d_wo, d_counts);
-        if ((rc = enqueue_compact(A, nullptr)) != VK_OK) return rc;
+        if ((rc = enqueue_compact(A, nullptr, nullptr, rule)) != VK_OK) return rc;
         unsigned long long c[5];
         HIP_TRY(hipMemcpy(c, d_counts, sizeof(c), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(rays, d_rays, m * sizeof(vk_ray), hipMemcpyDeviceToHost));
@@ -2866,6 +2898,20 @@ int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32
         for (int s = 0; s < 5; s++) counts[s] = c[s];
         return VK_OK;
     });
+}
+
+// test hook (vecchio_amd_debug.h)
+int vk_debug_compact_paths(vk_scene *scene, const vk_shaded *items, const uint32_t *ids, uint64_t n, uint64_t n_ids, vk_ray *rays,
+    vk_path_state *states, uint32_t *ids_out, vk_path_state *result_state, uint32_t *result_status, uint64_t counts[5]) {
+    return debug_compact(scene, nullptr, items, ids, n, n_ids, rays, states, ids_out, result_state, result_status, counts);
+}
+
+// test hook (vecchio_amd_debug.h): its twin with the termination rule in the count pass
+int vk_debug_compact_roulette(vk_scene *scene, const vk_roulette_params *rp, const vk_shaded *items, const uint32_t *ids, uint64_t n,
+    uint64_t n_ids, vk_ray *rays, vk_path_state *states, uint32_t *ids_out, vk_path_state *result_state, uint32_t *result_status,
+    uint64_t counts[5]) {
+    if (!rp) return fail(VK_ERR_BAD_ARG, "null argument (roulette parameters)");
+    return debug_compact(scene, rp, items, ids, n, n_ids, rays, states, ids_out, result_state, result_status, counts);
 }
 
 }  // extern "C"

@@ -2180,13 +2180,11 @@ struct CompactArgs {
     unsigned long long *counts; // [PATHS_STATUSES]
     uint32_t n_wg;
 };
-__global__ __launch_bounds__(PATHS_T) void paths_count_kernel(CompactArgs A) {
-    __shared__ uint32_t wc[PATHS_T / 64][PATHS_STATUSES];
-    const uint64_t i = (uint64_t)blockIdx.x * PATHS_T + threadIdx.x;
+// The count pass's tally, for a lane of paths_count_kernel or roulette_count_kernel: the lane's status (below PATHS_STATUSES; `in` = the
+// lane holds an item) is balloted status by status, the waves' counts meet in wc[] behind the ONE barrier, which every lane of the
+// workgroup reaches, and the first five lanes write the workgroup's row entries.
+__device__ __forceinline__ void tally_statuses(const CompactArgs &A, bool in, uint32_t status, uint32_t (&wc)[PATHS_T / 64][PATHS_STATUSES]) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const bool in = i < A.n;
-    uint32_t status = 0u;
-    if (in) { status = reinterpret_cast<const uint32_t *>(A.items + i * 6u)[20]; if (status >= PATHS_STATUSES) status = PATHS_STATUSES - 1u; }
 #pragma unroll
     for (uint32_t s = 0; s < PATHS_STATUSES; s++) {
         const unsigned long long m = __ballot(in && status == s);
@@ -2198,6 +2196,65 @@ __global__ __launch_bounds__(PATHS_T) void paths_count_kernel(CompactArgs A) {
         for (int k = 0; k < PATHS_T / 64; k++) t += wc[k][threadIdx.x];
         A.wg_counts[(size_t)threadIdx.x * A.n_wg + blockIdx.x] = t;
     }
+}
+__global__ __launch_bounds__(PATHS_T) void paths_count_kernel(CompactArgs A) {
+    __shared__ uint32_t wc[PATHS_T / 64][PATHS_STATUSES];
+    const uint64_t i = (uint64_t)blockIdx.x * PATHS_T + threadIdx.x;
+    const bool in = i < A.n;
+    uint32_t status = 0u;
+    if (in) { status = reinterpret_cast<const uint32_t *>(A.items + i * 6u)[20]; if (status >= PATHS_STATUSES) status = PATHS_STATUSES - 1u; }
+    tally_statuses(A, in, status, wc);
+}
+// roulette_count_kernel: the count pass's second form, with the handle's termination rule (vk_roulette_set) in front of the tally.
+// A record that is VK_SHADE_SCATTERED with state.depth >= first_depth is decided here, everything f32 and unfused:
+//   m = fmaxf(fmaxf(thr.x, thr.y), thr.z), q = fminf(fmaxf(m, q_min), q_max)      (fmaxf drops a NaN: q lies in [q_min, q_max] whatever thr)
+//       — as np.fmax does, for a signalling NaN too: v_max_f32 in IEEE mode answers one with a NaN, so the two are spelled as the
+//       compare and select of max_drop_nan / min_drop_nan, whose answer never depends on a NaN's kind
+//   u = draw number `depth` of the rule's own stream, rng_for_sample(state.seed ^ ROULETTE_SALT, state.pixel, state.sample): the
+//       path's stream and state.counter are not touched
+//   u < q: the path goes on with thr * (1.0f / q) — one IEEE division, three products: vk_paths_cull's thr * scale —, the first quarter
+//       of its state rewritten; otherwise its status word becomes VK_PATHS_CULLED, the last quarter of the record rewritten, and the
+//       state stays as the bounce left it.
+// Both are 16-byte stores into the lane's own record, in front of the ballots, so that the scan and the move pass run unchanged on the
+// rewritten records; the statuses are counted as they then stand.  No lane leaves before the tally.
+constexpr uint64_t ROULETTE_SALT = 0x52D1E7A9C3B5F04Bull;
+__device__ __forceinline__ float max_drop_nan(float a, float b) { return (a >= b || b != b) ? a : b; }
+__device__ __forceinline__ float min_drop_nan(float a, float b) { return (a <= b || b != b) ? a : b; }
+struct RouletteRule {
+    uint32_t first_depth;
+    float q_min, q_max;
+};
+__global__ __launch_bounds__(PATHS_T) void roulette_count_kernel(CompactArgs A, RouletteRule R) {
+    __shared__ uint32_t wc[PATHS_T / 64][PATHS_STATUSES];
+    const uint64_t i = (uint64_t)blockIdx.x * PATHS_T + threadIdx.x;
+    const bool in = i < A.n;
+    uint32_t status = 0u;
+    if (in) {
+        uint4 *item = const_cast<uint4 *>(A.items) + i * 6u;      // (the records are the handle's, or the hook's, own buffer)
+        uint4 tail = item[5];
+        status = tail.x;
+        if (status == (uint32_t)VK_SHADE_SCATTERED) {
+            uint4 s0 = item[2];                                   // thr, depth
+            if (s0.w >= R.first_depth) {
+                const uint4 s2 = item[4];                         // seed, pixel, sample
+                const float tx = __uint_as_float(s0.x), ty = __uint_as_float(s0.y), tz = __uint_as_float(s0.z);
+                const float q = min_drop_nan(max_drop_nan(max_drop_nan(max_drop_nan(tx, ty), tz), R.q_min), R.q_max);
+                vk::Rng g = vk::rng_for_sample((((uint64_t)s2.y << 32) | (uint64_t)s2.x) ^ ROULETTE_SALT, s2.z, s2.w);
+                g.ctr = s0.w - 1u;
+                const float u = vk::gen_f32(g);
+                if (u < q) {
+                    const float k = 1.0f / q;
+                    s0.x = __float_as_uint(tx * k); s0.y = __float_as_uint(ty * k); s0.z = __float_as_uint(tz * k);
+                    item[2] = s0;
+                } else {
+                    status = tail.x = (uint32_t)VK_PATHS_CULLED;
+                    item[5] = tail;
+                }
+            }
+        }
+        if (status >= PATHS_STATUSES) status = PATHS_STATUSES - 1u;
+    }
+    tally_statuses(A, in, status, wc);
 }
 __global__ __launch_bounds__(PATHS_SCAN_T) void paths_scan_kernel(CompactArgs A) {
     __shared__ uint32_t wt[PATHS_SCAN_T / 64];

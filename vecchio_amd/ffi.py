@@ -218,6 +218,11 @@ class PathsStepInfo(C.Structure):
                 ("bounces", C.c_uint32), ("kernel_launches", C.c_uint32), ("kernel_ms", C.c_double), ("seconds", C.c_double)]
 
 
+class RouletteParams(C.Structure):
+    """vk_roulette_params (vk_roulette_set)"""
+    _fields_ = [("first_depth", C.c_uint32), ("q_min", C.c_float), ("q_max", C.c_float), ("flags", C.c_uint32)]
+
+
 class FilmWindow(C.Structure):
     """vk_film_window (vk_film_emit)"""
     _fields_ = [("x0", C.c_uint32), ("y0", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("first_sample", C.c_uint32),
@@ -344,7 +349,7 @@ DEVICE_SYMBOLS = [
     "vk_trace_rays", "vk_trace_rays_device", "vk_trace_occluded", "vk_trace_occluded_device",
     "vk_trace_radiance", "vk_trace_irradiance", "vk_trace_probes", "vk_probe_eval", "vk_shade_hits",
     "vk_paths_create", "vk_paths_begin", "vk_paths_step", "vk_paths_read", "vk_paths_cull", "vk_paths_results", "vk_paths_get_info",
-    "vk_paths_destroy",
+    "vk_paths_destroy", "vk_roulette_set", "vk_roulette_get",
     "vk_film_create", "vk_film_emit", "vk_film_deposit", "vk_film_resolve", "vk_film_reset", "vk_film_get_info", "vk_film_destroy",
     "vk_regen_begin", "vk_regen_step", "vk_regen_cull",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
@@ -454,6 +459,10 @@ def _bind(lib):
     lib.vk_paths_get_info.argtypes = [C.c_void_p, C.POINTER(PathsInfo)]
     lib.vk_paths_destroy.restype = None
     lib.vk_paths_destroy.argtypes = [C.c_void_p]
+    lib.vk_roulette_set.restype = C.c_int
+    lib.vk_roulette_set.argtypes = [C.c_void_p, C.POINTER(RouletteParams)]
+    lib.vk_roulette_get.restype = C.c_int
+    lib.vk_roulette_get.argtypes = [C.c_void_p, C.POINTER(RouletteParams), C.POINTER(C.c_int)]
     lib.vk_film_create.restype = C.c_int
     lib.vk_film_create.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(C.c_void_p)]
     lib.vk_film_emit.restype = C.c_int
@@ -522,6 +531,9 @@ def _bind(lib):
     lib.vk_debug_compact_paths.restype = C.c_int
     lib.vk_debug_compact_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64] + [C.c_void_p] * 5 + \
         [C.POINTER(C.c_uint64 * 5)]
+    lib.vk_debug_compact_roulette.restype = C.c_int
+    lib.vk_debug_compact_roulette.argtypes = [C.c_void_p, C.POINTER(RouletteParams), C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64] + \
+        [C.c_void_p] * 5 + [C.POINTER(C.c_uint64 * 5)]
     lib.vk_debug_paths_last_ms.restype = C.c_int
     lib.vk_debug_paths_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 3)]
     lib.vk_debug_film_sums.restype = C.c_int

@@ -131,6 +131,10 @@ pub struct vk_paths_info { pub capacity: u64, pub started: u64, pub live: u64, p
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_paths_step_info { pub traced: u64, pub live: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
 
+// the termination rule of a path batch handle (vk_roulette_set)
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_roulette_params { pub first_depth: u32, pub q_min: f32, pub q_max: f32, pub flags: u32 }
+
 // films: a window of camera paths to emit, and a film's counters
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_film_window { pub x0: u32, pub y0: u32, pub width: u32, pub height: u32, pub first_sample: u32, pub n_samples: u32 }
@@ -231,6 +235,9 @@ extern "C" {
     pub fn vk_paths_results(p: *mut vk_paths, states: *mut vk_path_state, status: *mut u32) -> c_int;
     pub fn vk_paths_get_info(p: *mut vk_paths, out: *mut vk_paths_info) -> c_int;
     pub fn vk_paths_destroy(p: *mut vk_paths);
+    // the handle's Russian roulette: on the device inside every bounce of vk_paths_step and vk_regen_step; rp null turns it off
+    pub fn vk_roulette_set(p: *mut vk_paths, rp: *const vk_roulette_params) -> c_int;
+    pub fn vk_roulette_get(p: *mut vk_paths, out: *mut vk_roulette_params, enabled: *mut c_int) -> c_int;
     // films (additive symbols of ABI 7): a frame's sums on the device; emit camera paths into a batch, step the batch until nothing is
     // live, deposit it; resolve(samples_per_pixel) once every (pixel, sample) went through is vk_render's frame; destroy before the scene
     pub fn vk_film_create(scene: *mut vk_scene, cam: *const vk_camera, params: *const vk_render_params, out: *mut *mut vk_film) -> c_int;

@@ -589,10 +589,11 @@ class DeviceScene:
         scene."""
         return Film(self, cam, params)
 
-    def debug_compact_paths(self, items, ids, n_ids, canary=0xA5):
+    def debug_compact_paths(self, items, ids, n_ids, canary=0xA5, roulette=None):
         """The compaction of a path batch's bounce on host arrays (vk_debug_compact_paths, a test hook): items a SHADED_DTYPE array, ids
         their uint32 ids (each below n_ids).  Every output is prefilled with the byte `canary`.  Returns (rays, states, ids_out — n
-        entries each, the survivors first —, result_state, result_status — n_ids entries —, counts by status)."""
+        entries each, the survivors first —, result_state, result_status — n_ids entries —, counts by status).  roulette = (first_depth,
+        q_min, q_max): the compaction with that termination rule in its count pass (vk_debug_compact_roulette)."""
         items = np.ascontiguousarray(items, SHADED_DTYPE).reshape(-1)
         ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
         n = items.shape[0]
@@ -603,8 +604,11 @@ class DeviceScene:
             a.view(np.uint8)[:] = canary
         counts = (C.c_uint64 * 5)()
         ptr = lambda a: C.c_void_p(a.ctypes.data if a.size else None)
-        check(self._lib, self._lib.vk_debug_compact_paths(self._h, ptr(items), ptr(ids), n, n_ids, *[C.c_void_p(a.ctypes.data) for a in outs],
-                                                          C.byref(counts)))
+        tail = (ptr(items), ptr(ids), n, n_ids, *[C.c_void_p(a.ctypes.data) for a in outs], C.byref(counts))
+        if roulette is None:
+            check(self._lib, self._lib.vk_debug_compact_paths(self._h, *tail))
+        else:
+            check(self._lib, self._lib.vk_debug_compact_roulette(self._h, C.byref(ffi.RouletteParams(*roulette, 0)), *tail))
         return (*outs, np.array(list(counts), np.uint64))
 
     def to_color_device(self, d_rgb, width, height, d_rgb8, stream=None):
@@ -836,6 +840,22 @@ class PathBatch:
         check(self._lib, self._lib.vk_paths_cull(self._h, C.c_void_p(keep.ctypes.data if n else None),
                                                  C.c_void_p(scale.ctypes.data) if scale is not None and n else None))
 
+    def set_roulette(self, first_depth, q_min=None, q_max=None):
+        """The handle's termination rule (vk_roulette_set): from the next bounce on, every bounce of step() and of Film.regen_step()
+        ends a scattered path of state.depth >= first_depth with probability 1 - q, q = its largest throughput component clamped to
+        [q_min, q_max], and scales a continuing one's throughput by 1 / q — on the device, inside the compaction.  set_roulette(None)
+        turns the rule off.  It is the handle's: begin(), Film.emit() and Film.regen_begin() keep it."""
+        if first_depth is None:
+            check(self._lib, self._lib.vk_roulette_set(self._h, None))
+        else:
+            check(self._lib, self._lib.vk_roulette_set(self._h, C.byref(ffi.RouletteParams(first_depth, q_min, q_max, 0))))
+
+    def roulette(self):
+        """(first_depth, q_min, q_max) of the rule that is set, or None (vk_roulette_get)"""
+        rp, on = ffi.RouletteParams(), C.c_int()
+        check(self._lib, self._lib.vk_roulette_get(self._h, C.byref(rp), C.byref(on)))
+        return (rp.first_depth, rp.q_min, rp.q_max) if on.value else None
+
     def results(self):
         """Per started id the final (or, for a live path, current) state and the status (vk_paths_results): (PATH_STATE_DTYPE array,
         uint32 array of ffi.VK_SHADE_* / ffi.VK_PATHS_*)."""
@@ -924,11 +944,16 @@ class Film:
         check(self._lib, self._lib.vk_film_get_info(self._h, C.byref(inf)))
         return inf
 
-    def render(self, batch, cull=None):
+    _KEEP = object()      # roulette=: leave the batch's rule as it is
+
+    def render(self, batch, cull=None, roulette=_KEEP):
         """The whole frame through `batch`: the frame is walked in windows that fit the batch's capacity — whole rows of all samples
         where a row fits, else pieces of a row, else a pixel's samples in pieces —, each emitted, stepped to its end and deposited.
         cull, where given, is called with the batch between two bounces while anything is live (PathBatch.read() and cull() are its
-        tools).  Returns resolve()."""
+        tools).  roulette, where given, is set on the batch first: (first_depth, q_min, q_max) or None (PathBatch.set_roulette).  Returns
+        resolve()."""
+        if roulette is not Film._KEEP:
+            batch.set_roulette(*(roulette or (None,)))
         p = self.params
         cap = int(batch.info().capacity)
         spp = p.samples_per_pixel
@@ -971,11 +996,14 @@ class Film:
         check(self._lib, self._lib.vk_regen_cull(self._h, batch._h, C.c_void_p(keep.ctypes.data if n else None),
                                                  C.c_void_p(scale.ctypes.data) if scale is not None and n else None))
 
-    def render_regen(self, batch, cull=None):
+    def render_regen(self, batch, cull=None, roulette=_KEEP):
         """The whole frame through `batch` by regenerating runs: one run over the whole frame per range of samples, the ranges chosen so
         that a run has fewer than 2^32 paths (one run, unless width * height * samples_per_pixel reaches that).  cull, where given, is
-        called with the batch between two bounces while anything is live (PathBatch.read() and regen_cull() are its tools).  Returns
-        resolve()."""
+        called with the batch between two bounces while anything is live (PathBatch.read() and regen_cull() are its tools).  roulette,
+        where given, is set on the batch first: (first_depth, q_min, q_max) or None (PathBatch.set_roulette); the rule runs on the
+        device, so a run without a cull callback is still stepped in one call.  Returns resolve()."""
+        if roulette is not Film._KEEP:
+            batch.set_roulette(*(roulette or (None,)))
         p = self.params
         spp = p.samples_per_pixel
         ns = max(1, min(spp, (2 ** 32 - 1) // (p.width * p.height)))
