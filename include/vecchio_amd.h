@@ -1084,6 +1084,65 @@ int vk_regen_begin(vk_film *film, vk_paths *batch, const vk_film_window *win);
 int vk_regen_step(vk_film *film, vk_paths *batch, uint32_t max_bounces, vk_regen_info *info);
 int vk_regen_cull(vk_film *film, vk_paths *batch, const uint8_t *keep, const float *scale);
 
+/* ---- a film's error moments and adaptive regeneration (vk_adapt_*, additive symbols of ABI 7) -----------------------------------------
+ * replaces: nothing.  What vk_progress keeps next to its running sums — the batch-means moments behind vk_progress_stderr and the tile
+ * map of vk_progress_set_adaptive — kept next to a film's sums, so that a frame made of path batches has an error estimate (the stderr3
+ * image vk_denoise and vk_temporal_accumulate take) and stops sampling the 8x8 tiles that have converged.  The handle stays vk_film; a
+ * film on which vk_adapt_enable was never called allocates and does what it did.  No call takes a stream: all work is on the null stream
+ * of the film's device, as for films.
+ *
+ *   State, from vk_adapt_enable on (48 bytes per pixel and 16 per tile of device memory, nothing before): prev = the sums at the last
+ *     close; m2 = sum_j n_j m_j^2 per component in double; per tile tile_n (0 = active, else the count it froze with) and tile_k;
+ *     samples_done and steps; the ascending list of the active tiles with the pixels before each.
+ *   vk_adapt_enable: ap == NULL keeps moments only and no tile ever freezes; otherwise ap is checked as vk_progress_set_adaptive checks
+ *     it, in its words.  VK_ERR_BAD_ARG, the film as it was, once the film has emitted or deposited anything since create or reset;
+ *     called again before that it takes the new parameters.  VK_ERR_OOM: the film as it was, nothing kept.  vk_film_reset keeps the
+ *     setting and zeroes prev, m2, the tile map, samples_done and steps.
+ *   vk_adapt_begin puts `batch` into the regenerating state (vk_regen_*) for the TILE WINDOW: samples [samples_done, samples_done +
+ *     n_samples) of every in-image pixel of every active tile, the tile set being the one at the time of the call.  The sequence: active
+ *     tiles in ascending tile index t = ty * tiles_x + tx (tile row 0 at the bottom); tw = min(8, W - 8 tx), th = min(8, H - 8 ty); pixel
+ *     j < tw * th of a tile is x = 8 tx + j % tw, y = 8 ty + j / tw; P_a = the in-image pixels of the active tiles before the a-th.  Path
+ *     q has p = q / n_samples, k = q - p * n_samples, a = the largest index with P_a <= p, j = p - P_a: it is sample samples_done + k of
+ *     that pixel, its ray and state vk_film_emit's for that (pixel, sample) bit for bit, its id q.  The run is stepped, culled, read and
+ *     finished by vk_regen_step, vk_regen_cull, vk_paths_read and vk_paths_get_info as any regenerating run (six launches a bounce, five
+ *     without a top-up).  VK_ERR_BAD_ARG, nothing enqueued, film and batch as they were: a null pointer, a film not enabled, n_samples
+ *     == 0, samples_done + n_samples > samples_per_pixel, 2^32 paths or more, a batch of another scene.  With no tile active: VK_OK, and
+ *     the run is finished at once.
+ *   vk_adapt_close is the caller's statement that every pixel of every active tile has received exactly the samples [samples_done,
+ *     samples_done + n_samples) since the last close — by a tile run, by rectangular vk_regen_begin runs, by vk_film_emit and
+ *     vk_film_deposit, or a mix.  A wrong statement is the caller's error and is not detected (as emitting a sample twice is not); what
+ *     is deposited into a frozen tile never enters its moments, its count or vk_adapt_resolve's image.  On the device, for the pixels
+ *     of the active tiles, in this order and without contraction: w = sums - prev; prev = sums; s = (double)w * 2^-26; m2 += s * s /
+ *     (double)n_samples.  Then samples_done += n_samples, steps += 1 and, with parameters set, vk_progress_set_adaptive's rule at
+ *     (samples_done, steps): a converged tile freezes there.  The list is rebuilt on the device; one record of counts comes back.  With
+ *     no tile active a close is VK_OK: samples_done and steps advance, no tile changes.  info may be NULL.  VK_ERR_BAD_ARG, the film
+ *     unchanged: not enabled, n_samples == 0, samples_done + n_samples > samples_per_pixel.  Call it with no run of this film under way.
+ *   vk_adapt_resolve: vk_film_resolve's arithmetic on the sums of the last close, each pixel divided by its tile's own count (tile_n, or
+ *     samples_done for an active tile).  VK_ERR_BAD_ARG while samples_done == 0.
+ *   vk_adapt_stderr: vk_progress_stderr's expression with each tile's own N and k, f32 [height][width][3], y = 0 the bottom row.
+ *     VK_ERR_BAD_ARG while steps < 2.
+ *   vk_adapt_tile_samples: the layout and meaning of vk_progress_tile_samples (out and info may each be NULL).
+ *   Contract, with no roulette rule and no cull, where the film's own contract holds:
+ *     1. moments: when the n_samples of the closes are the n_samples of the steps of a vk_progress handle with VK_PROGRESS_STDERR, the
+ *        same scene, camera and parameters and clamped_samples == 0, prev and m2 are that handle's running sums and moments and
+ *        vk_adapt_stderr is its vk_progress_stderr, bit for bit — whatever routes, capacities and slicing carried the samples;
+ *     2. decisions: with the same vk_adaptive_params the tile map after every close is the handle's after the same step and
+ *        vk_adapt_resolve that step's image, bit for bit: every pixel is vk_render's at its tile's count;
+ *     3. schedule: a tile run's vk_paths_read after every bounce is a function of the sequence above, the capacity and the paths'
+ *        lifetimes alone.                                                                                                         */
+typedef struct vk_adapt_info {           /* 32 bytes */
+    uint32_t samples_done, steps;
+    uint32_t tiles_total, tiles_active;
+    uint64_t pixels_active;              /* in-image pixels of the active tiles */
+    uint64_t samples_rendered;           /* pixel-samples the closes have counted, summed over the tiles */
+} vk_adapt_info;
+int vk_adapt_enable(vk_film *film, const vk_adaptive_params *ap);
+int vk_adapt_begin(vk_film *film, vk_paths *batch, uint32_t n_samples);
+int vk_adapt_close(vk_film *film, uint32_t n_samples, vk_adapt_info *info);
+int vk_adapt_resolve(vk_film *film, float *rgb_out);
+int vk_adapt_stderr(vk_film *film, float *out);
+int vk_adapt_tile_samples(vk_film *film, uint32_t *out, vk_adaptive_info *info);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

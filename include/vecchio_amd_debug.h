@@ -139,6 +139,19 @@ int vk_debug_film_deposit_form(vk_film *film, int form);
  * VK_ERR_BAD_ARG for a null pointer, a batch that is not regenerating, or when no bounce has run since vk_regen_begin.  Takes no stream.
  * In both libraries. */
 int vk_debug_regen_last_ms(vk_paths *batch, double ms[4]);
+
+/* the error moments of a film with vk_adapt_enable, in vk_debug_progress_moments' layout: run = the sums at the last close (prev), m2 =
+ * the batch-means moments, width * height * 3 values each, [(y * width + x) * 3 + c]; each may be NULL.  Waits.  VK_ERR_BAD_ARG for a
+ * null film or one that is not enabled.  Takes no stream.  In both libraries. */
+int vk_debug_adapt_moments(vk_film *film, long long *run, double *m2);
+/* imposes a tile map on an enabled film and rebuilds the device list of active tiles from it: tile_n[t] (0 = active, else the count the
+ * tile froze with) and tile_k[t] for every tile t = ty * tiles_x + tx.  The moments are left as they are.  For tests: the schedule of a
+ * tile run on a chosen set of tiles.  VK_ERR_BAD_ARG for a null pointer or a film that is not enabled.  In both libraries. */
+int vk_debug_adapt_set_tiles(vk_film *film, const uint32_t *tile_n, const uint32_t *tile_k);
+/* the top-up kernel's own index code (vk_adapt.h adapt_locate) on the device, for paths first .. first + m of a tile run of n_samples over
+ * the film's current tile set: pixel_out[i] = y * width + x and sample_out[i] = samples_done + k of path first + i.  m <= 2^24.
+ * VK_ERR_BAD_ARG for a null pointer, a film that is not enabled, n_samples == 0 or first + m beyond the run's paths.  In both libraries. */
+int vk_debug_adapt_sequence(vk_film *film, uint32_t n_samples, uint64_t first, uint32_t m, uint32_t *pixel_out, uint32_t *sample_out);
 #ifdef __cplusplus
 }
 #endif

@@ -74,7 +74,8 @@ def _host_deps():
 
 def _device_deps():
     srcs = [os.path.join(CSRC, "vk_api.hip"), os.path.join(CSRC, "vk_linearize.cpp")]
-    return srcs, srcs + [os.path.join(CSRC, f) for f in ("vk_kernels.h", "vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_resources.h")] + \
+    return srcs, srcs + [os.path.join(CSRC, f) for f in ("vk_kernels.h", "vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_resources.h",
+                                                         "vk_emit.h", "vk_adapt.h", "vk_adapt.hip")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
 
 
@@ -83,7 +84,8 @@ def host_is_stale():
 
 
 def device_is_stale():
-    return _newer(os.path.join(LIB, "libvecchio_amd.so"), _device_deps()[1], HIPFLAGS) or not os.path.exists(kernel_resources_path())
+    return _newer(os.path.join(LIB, "libvecchio_amd.so"), _device_deps()[1], HIPFLAGS) or not os.path.exists(kernel_resources_path()) or \
+        not os.path.exists(kernel_resources_adapt_path())
 
 
 def build_host(force=False):
@@ -118,7 +120,7 @@ def build_device_debug(force=False):
     flags = HIPFLAGS + ["-DVK_DEBUG_LIB"]
     if force or _newer(out, deps, flags):
         os.makedirs(LIB, exist_ok=True)
-        _run_atomic([HIPCC] + flags + ["-shared", "-o"], out, srcs)
+        _run_atomic([HIPCC] + flags + ["-shared", "-o"], out, srcs + [_adapt_src()])
         _stamp(out, deps, flags)
     return out
 
@@ -127,41 +129,66 @@ def debug_is_stale():
     return _newer(os.path.join(LIB, "libvecchio_amd_debug.so"), _device_deps()[1], HIPFLAGS + ["-DVK_DEBUG_LIB"])
 
 
+def _adapt_src():
+    """the kernels of vk_adapt_* (films: error moments and tile runs): a translation unit of its own"""
+    return os.path.join(CSRC, "vk_adapt.hip")
+
+
+def _hipcc_with_remarks(cmd, cwd, cleanup=()):
+    """runs a hipcc line that carries -Rpass-analysis=kernel-resource-usage and -save-temps in `cwd`: (the remark lines, kernel symbol ->
+    scratch instructions from the gfx950 assembly it left there); everything else it wrote to stderr is passed on"""
+    print("+", " ".join(cmd), file=sys.stderr)
+    r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True, cwd=cwd)
+    remarks = [l for l in r.stderr.splitlines() if "-Rpass-analysis=kernel-resource-usage" in l]
+    other = [l for l in r.stderr.splitlines() if "-Rpass-analysis=kernel-resource-usage" not in l]
+    if other:
+        print("\n".join(other), file=sys.stderr)
+    if r.returncode != 0:
+        for f in cleanup:
+            if os.path.exists(f):
+                os.remove(f)
+        raise subprocess.CalledProcessError(r.returncode, cmd)
+    spills = {}
+    for f in os.listdir(cwd):
+        if f.endswith("gfx950.s"):
+            spills.update(_scratch_ops(open(os.path.join(cwd, f)).read()))
+    return remarks, spills
+
+
+def _write_resources(path, remarks, spills):
+    """registers / scratch / occupancy of every kernel, kept next to the library: the megakernel's
+    throughput collapses when a variant starts spilling, so tests/test_kernel_resources.py pins them.
+    ScratchOps = number of scratch_load/scratch_store instructions in the kernel's code: the remark's
+    ScratchSize does not move when the allocator spills the same slots in twice as many places."""
+    text = "\n".join(re.sub(r"^.*remark: [^ ]* ", "", l).replace(" [-Rpass-analysis=kernel-resource-usage]", "") for l in remarks) + "\n"
+    blocks = text.split("Function Name: ")
+    text = blocks[0] + "".join("Name: " + b.rstrip("\n") + f"\n   ScratchOps: {spills.get(b.split()[0], -1)}\n" for b in blocks[1:])
+    with open(path, "w") as f:
+        f.write(text)
+
+
 def build_device(force=False):
-    """hipcc cross-compiles for gfx950 without a GPU present."""
+    """hipcc cross-compiles for gfx950 without a GPU present.  Two steps: vk_adapt.hip to an object of its own (its resource remarks go
+    to kernel_resources_adapt.txt), then vk_api.hip and vk_linearize.cpp, linked with that object (kernel_resources.txt: theirs alone)."""
     out = os.path.join(LIB, "libvecchio_amd.so")
     srcs, deps = _device_deps()
-    if force or _newer(out, deps, HIPFLAGS) or not os.path.exists(kernel_resources_path()):
+    if force or device_is_stale():
         os.makedirs(LIB, exist_ok=True)
         # -save-temps in a scratch directory: the gfx950 assembly is read back for the per-kernel spill counts
         import tempfile
         with tempfile.TemporaryDirectory() as tmp:
+            analysis = ["-Rpass-analysis=kernel-resource-usage", "-save-temps"]
+            tmp_adapt, tmp_main = os.path.join(tmp, "adapt"), os.path.join(tmp, "main")
+            os.makedirs(tmp_adapt)
+            os.makedirs(tmp_main)
+            adapt_obj = os.path.join(tmp_adapt, "vk_adapt.o")
+            adapt = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", adapt_obj, _adapt_src()], tmp_adapt)
             tmp_out = f"{out}.tmp.{os.getpid()}"
-            cmd = [HIPCC] + HIPFLAGS + ["-Rpass-analysis=kernel-resource-usage", "-save-temps", "-shared", "-o", tmp_out] + srcs
-            print("+", " ".join(cmd), file=sys.stderr)
-            r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True, cwd=tmp)
-            remarks = [l for l in r.stderr.splitlines() if "-Rpass-analysis=kernel-resource-usage" in l]
-            other = [l for l in r.stderr.splitlines() if "-Rpass-analysis=kernel-resource-usage" not in l]
-            if other:
-                print("\n".join(other), file=sys.stderr)
-            if r.returncode != 0:
-                if os.path.exists(tmp_out):
-                    os.remove(tmp_out)
-                raise subprocess.CalledProcessError(r.returncode, cmd)
+            # (the object in front of the sources: hipcc reads whatever follows a source file as HIP)
+            main = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-shared", "-o", tmp_out, adapt_obj] + srcs, tmp_main, [tmp_out])
             os.replace(tmp_out, out)
-            spills = {}
-            for f in os.listdir(tmp):
-                if f.endswith("gfx950.s"):
-                    spills.update(_scratch_ops(open(os.path.join(tmp, f)).read()))
-        # registers / scratch / occupancy of every kernel, kept next to the library: the megakernel's
-        # throughput collapses when a variant starts spilling, so tests/test_kernel_resources.py pins them.
-        # ScratchOps = number of scratch_load/scratch_store instructions in the kernel's code: the remark's
-        # ScratchSize does not move when the allocator spills the same slots in twice as many places.
-        text = "\n".join(re.sub(r"^.*remark: [^ ]* ", "", l).replace(" [-Rpass-analysis=kernel-resource-usage]", "") for l in remarks) + "\n"
-        blocks = text.split("Function Name: ")
-        text = blocks[0] + "".join("Name: " + b.rstrip("\n") + f"\n   ScratchOps: {spills.get(b.split()[0], -1)}\n" for b in blocks[1:])
-        with open(kernel_resources_path(), "w") as f:
-            f.write(text)
+        _write_resources(kernel_resources_path(), *main)
+        _write_resources(kernel_resources_adapt_path(), *adapt)
         _stamp(out, deps, HIPFLAGS)
     return out
 
@@ -176,6 +203,11 @@ def _scratch_ops(asm):
 
 def kernel_resources_path():
     return os.path.join(LIB, "kernel_resources.txt")
+
+
+def kernel_resources_adapt_path():
+    """the same record for the kernels of vk_adapt.hip"""
+    return os.path.join(LIB, "kernel_resources_adapt.txt")
 
 
 def build_oracle(force=False):
@@ -198,10 +230,11 @@ def build_emu(force=False):
     srcs = [os.path.join(edir, "emu.cpp"), os.path.join(edir, "emu_guides.cpp"), os.path.join(edir, "emu_rays.cpp"),
             os.path.join(edir, "emu_occlusion.cpp"), os.path.join(edir, "emu_radiance.cpp"),
             os.path.join(edir, "emu_irradiance.cpp"), os.path.join(edir, "emu_probes.cpp"), os.path.join(edir, "emu_shade.cpp"),
-            os.path.join(edir, "emu_paths.cpp"), os.path.join(edir, "emu_film.cpp"), os.path.join(CSRC, "vk_linearize.cpp")]
+            os.path.join(edir, "emu_paths.cpp"), os.path.join(edir, "emu_film.cpp"), os.path.join(edir, "emu_adapt.cpp"),
+            os.path.join(CSRC, "vk_linearize.cpp")]
     # (the tool's own headers: whichever are there)
     deps = srcs + sorted(os.path.join(edir, f) for f in os.listdir(edir) if f.endswith(".h")) + \
-        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h")] + \
+        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_adapt.h")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
     if force or _newer(out, deps, CXXFLAGS):
         os.makedirs(os.path.dirname(out), exist_ok=True)

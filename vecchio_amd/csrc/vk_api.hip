@@ -51,6 +51,7 @@
 #include "../../include/vecchio_amd_debug.h"
 #include "vk_linearize.h"
 #include "vk_kernels.h"
+#include "vk_adapt.h"        // the kernels of vk_adapt.hip: argument records and launchers
 
 namespace {
 
@@ -2503,9 +2504,27 @@ struct vk_paths {
     const vk_film *regen_film = nullptr;            // the run's film, for the identity check only: never dereferenced
     vk_film_window regen_win{};
     uint64_t regen_next = 0, regen_total = 0;       // the window's paths [0, regen_next) are emitted, of regen_total
+    // a tile run (vk_adapt_begin): the window is the film's active tiles, samples [regen_first_sample, + regen_n_samples); regen_win unused
+    bool regen_tiles = false;
+    uint32_t regen_first_sample = 0, regen_n_samples = 0;
     // the termination rule (vk_roulette_set): the handle's, not a batch's — no begin, emit or reset touches it
     bool roulette = false;
     vk_roulette_params rr{};
+};
+// a film's error moments and tile map (vk_adapt_*, below): allocated by vk_adapt_enable, on the film's device
+struct AdaptState {
+    bool judged = false;                            // parameters given: the rule runs behind every close
+    vk_adaptive_params ap{};
+    DeviceBuffer<long long> prev;                   // the sums at the last close, [width * height * 3]
+    DeviceBuffer<double> m2;                        // sum_j n_j m_j^2, [width * height * 3]
+    DeviceBuffer<uint32_t> tile_n, tile_k;          // [tiles]: 0 = active, else the count and the closes the tile froze with
+    DeviceBuffer<uint32_t> list, prefix;            // [tiles], [tiles + 1]: the active tiles, ascending, and the pixels before each
+    DeviceBuffer<uint32_t> block_tiles, block_px;   // the rebuild's tables, [ceil(tiles / 1024)]
+    DeviceBuffer<unsigned long long> record;        // [2]: the one record a close sends back — active tiles, their pixels
+    uint32_t tiles_x = 0, tiles = 0;
+    uint32_t done = 0, steps = 0;                   // samples_done, steps
+    uint32_t n_active = 0;                          // as of the last rebuild
+    uint64_t px_active = 0, samples_rendered = 0;   // the active tiles' in-image pixels; pixel-samples the closes have counted
 };
 // a film (vk_film_*, below): here because a regenerating batch's compaction deposits into one
 struct vk_film {
@@ -2519,6 +2538,7 @@ struct vk_film {
     bool timed[3] = {false, false, false};
     uint64_t emitted = 0, deposits = 0;
     bool runs = FILM_DEPOSIT_RUNS;                  // the deposit's form (vk_debug_film_deposit_form)
+    std::unique_ptr<AdaptState> adapt;              // vk_adapt_enable; null: the film as it always was
 };
 
 namespace {
@@ -2603,6 +2623,7 @@ void paths_reset(vk_paths *p, const vk_shade_params &sp, uint64_t started, uint6
     p->sp = sp; p->begun = true; p->deposited = false; p->cur = 0u; p->started = started; p->live = live; p->bounces = 0u;
     for (uint64_t &r : p->retired) r = 0u;
     p->regen = false; p->regen_film = nullptr; p->regen_win = vk_film_window{}; p->regen_next = 0u; p->regen_total = 0u;
+    p->regen_tiles = false; p->regen_first_sample = 0u; p->regen_n_samples = 0u;
 }
 
 // what the bounces of one step call add up to: vk_paths_step and vk_regen_step copy it into their info structs
@@ -2932,11 +2953,13 @@ void film_free(vk_film *f) {
     delete f;
 }
 
+int adapt_zero(vk_film *f);        // (vk_adapt_*, below)
+
 int film_zero(vk_film *f) {
     HIP_TRY(hipMemsetAsync(f->sums, 0, (size_t)f->params.width * f->params.height * 3u * sizeof(unsigned long long), nullptr));
     HIP_TRY(hipMemsetAsync(f->counters, 0, 4u * sizeof(unsigned long long), nullptr));
     f->emitted = 0u; f->deposits = 0u;
-    return VK_OK;
+    return f->adapt ? adapt_zero(f) : VK_OK;
 }
 
 // what vk_film_emit and vk_regen_begin check of their three arguments, in the same words; *n = the window's paths
@@ -3161,7 +3184,8 @@ int vk_debug_film_deposit_form(vk_film *film, int form) {
 
 // ---- regeneration (vk_regen_*): a path batch refilled from a film's window as its paths retire.  A bounce is at most six launches on the
 // null stream — regen_emit_kernel (the top-up), trace_paths_kernel, shade_hits_kernel, paths_count_kernel, paths_scan_kernel and
-// regen_move_kernel, which deposits the retired paths into the film and compacts the survivors — and one readback of the counts record,
+// regen_move_kernel, which deposits the retired paths into the film and compacts the survivors (a tile run, vk_adapt_begin below, tops up
+// with adapt_emit_kernel instead) — and one readback of the counts record,
 // from which the host computes the next top-up.  The state of a run lives in vk_paths' host-side regen fields; a batch's device memory is
 // what it was.
 namespace {
@@ -3180,6 +3204,26 @@ int regen_check(const vk_film *film, const vk_paths *batch, const char *who) {
 // a run whose window is emitted and whose last path has retired: nothing is left to deposit
 void regen_note_finished(vk_paths *p) {
     if (p->live == 0u && p->regen_next == p->regen_total) p->deposited = true;
+}
+
+// the film's tile set as the kernels of vk_adapt.hip index it
+AdaptTiles adapt_tiles(const vk_film *film) {
+    const AdaptState &a = *film->adapt;
+    const vk_render_params &P = film->params;
+    return AdaptTiles{a.list, a.prefix, a.n_active, P.width, P.height, a.tiles_x, (P.width % TILE == 0u && P.height % TILE == 0u) ? 1u : 0u};
+}
+
+// the top-up of a tile run (vk_adapt_begin): the run's next m paths behind p's survivors
+AdaptEmitArgs adapt_emit_args(const vk_film *film, const vk_paths *p, uint32_t m) {
+    AdaptEmitArgs A;
+    memset(&A, 0, sizeof(A));
+    A.C = film_consts(film);
+    A.rays = reinterpret_cast<uint4 *>(p->rays.get()); A.states = reinterpret_cast<uint4 *>(p->states.get());
+    A.ids = p->ids[p->cur];                                  // (the last compaction's flip is behind us)
+    A.T = adapt_tiles(film);
+    A.first_sample = p->regen_first_sample; A.n_samples = p->regen_n_samples;
+    A.first = (uint32_t)p->regen_next; A.slot0 = (uint32_t)p->live; A.m = m;      // (total < 2^32, capacity <= 2^24)
+    return A;
 }
 
 }  // namespace
@@ -3218,14 +3262,18 @@ int vk_regen_step(vk_film *film, vk_paths *batch, uint32_t max_bounces, vk_regen
             if (p->live + m == 0u) break;                                // 2. the run is finished
             HIP_TRY(hipEventRecord(p->ev0, nullptr));
             if (m != 0u) {
-                RegenEmitArgs A;
-                memset(&A, 0, sizeof(A));
-                A.C = film_consts(film);
-                A.rays = reinterpret_cast<uint4 *>(p->rays.get()); A.states = reinterpret_cast<uint4 *>(p->states.get());
-                A.ids = p->ids[p->cur];                                  // (the last compaction's flip is behind us)
-                A.W = emit_window(p->regen_win);
-                A.first = (uint32_t)p->regen_next; A.slot0 = (uint32_t)p->live; A.m = (uint32_t)m;      // (total < 2^32, capacity <= 2^24)
-                hipLaunchKernelGGL(regen_emit_kernel, dim3((uint32_t)((m + FILM_T - 1) / FILM_T)), dim3(FILM_T), 0, nullptr, A);
+                if (p->regen_tiles) {                                    // a tile run (vk_adapt_begin): adapt_emit_kernel
+                    launch_adapt_emit(adapt_emit_args(film, p, (uint32_t)m));
+                } else {
+                    RegenEmitArgs A;
+                    memset(&A, 0, sizeof(A));
+                    A.C = film_consts(film);
+                    A.rays = reinterpret_cast<uint4 *>(p->rays.get()); A.states = reinterpret_cast<uint4 *>(p->states.get());
+                    A.ids = p->ids[p->cur];                              // (the last compaction's flip is behind us)
+                    A.W = emit_window(p->regen_win);
+                    A.first = (uint32_t)p->regen_next; A.slot0 = (uint32_t)p->live; A.m = (uint32_t)m;  // (total < 2^32, capacity <= 2^24)
+                    hipLaunchKernelGGL(regen_emit_kernel, dim3((uint32_t)((m + FILM_T - 1) / FILM_T)), dim3(FILM_T), 0, nullptr, A);
+                }
                 HIP_TRY(hipGetLastError());
                 p->live += m; p->regen_next += m; p->started = p->regen_next;
                 film->emitted += m; emitted += m;
@@ -3266,6 +3314,280 @@ int vk_debug_regen_last_ms(vk_paths *p, double ms[4]) {
         if (!p->regen || p->bounces == 0u) return fail(VK_ERR_BAD_ARG, "no bounce has run since vk_regen_begin");
         const Event *ev[5] = {&p->ev0, &p->ev_e, &p->ev_t, &p->ev_s, &p->ev1};
         return paths_parts_ms(p, ev, 4, ms);
+    });
+}
+
+}  // extern "C"
+
+// ---- a film's error moments and adaptive regeneration (vk_adapt_*): vk_progress' batch-means moments and tile map kept next to a film's
+// sums.  The kernels are vk_adapt.hip's (vk_adapt.h): adapt_emit_kernel tops a tile run up in vk_regen_step, adapt_close_kernel folds and
+// judges, adapt_count_kernel and adapt_scatter_kernel rebuild the list of active tiles with its pixel prefix, adapt_resolve_kernel and
+// adapt_stderr_kernel write the images.  All on the null stream of the film's device; the host keeps samples_done, steps and the counts
+// of the one record a rebuild sends back.
+namespace {
+
+// the words vk_progress_set_adaptive refuses parameters with (nullptr: they are fine)
+const char *adaptive_refusal(const vk_adaptive_params &ap) {
+    if (ap.min_steps < 2) return "min_steps must be >= 2 (the error estimate needs two windows)";
+    if (!(std::isfinite(ap.abs_tol) && ap.abs_tol >= 0.0f && std::isfinite(ap.rel_tol) && ap.rel_tol >= 0.0f))
+        return "abs_tol and rel_tol must be finite and >= 0";
+    return nullptr;
+}
+
+// the list and its prefix from the tile map as it stands, then the record: n_active and px_active follow it (waits)
+int adapt_rebuild(vk_film *f) {
+    AdaptState &a = *f->adapt;
+    AdaptListArgs L;
+    memset(&L, 0, sizeof(L));
+    L.tile_n = a.tile_n; L.list = a.list; L.prefix = a.prefix; L.block_tiles = a.block_tiles; L.block_px = a.block_px; L.record = a.record;
+    L.tiles = a.tiles; L.width = f->params.width; L.height = f->params.height; L.tiles_x = a.tiles_x;
+    launch_adapt_list(L);
+    HIP_TRY(hipGetLastError());
+    unsigned long long rec[2];
+    HIP_TRY(hipMemcpy(rec, a.record, sizeof(rec), hipMemcpyDeviceToHost));
+    a.n_active = (uint32_t)rec[0]; a.px_active = rec[1];
+    return VK_OK;
+}
+
+// back to sample 0 with every tile active (vk_film_reset; the film's device is current)
+int adapt_zero(vk_film *f) {
+    AdaptState &a = *f->adapt;
+    const size_t words = (size_t)f->params.width * f->params.height * 3u;
+    HIP_TRY(hipMemsetAsync(a.prev, 0, words * sizeof(long long), nullptr));
+    HIP_TRY(hipMemsetAsync(a.m2, 0, words * sizeof(double), nullptr));
+    HIP_TRY(hipMemsetAsync(a.tile_n, 0, (size_t)a.tiles * sizeof(uint32_t), nullptr));
+    HIP_TRY(hipMemsetAsync(a.tile_k, 0, (size_t)a.tiles * sizeof(uint32_t), nullptr));
+    a.done = 0u; a.steps = 0u; a.samples_rendered = 0u;
+    return adapt_rebuild(f);
+}
+
+int adapt_check(const vk_film *film, const char *who) {
+    if (!film) return fail(VK_ERR_BAD_ARG, "null film");
+    if (!film->adapt) return fail(VK_ERR_BAD_ARG, std::string(who) + " on a film without vk_adapt_enable");
+    return VK_OK;
+}
+
+AdaptImageArgs adapt_image_args(vk_film *film) {
+    const AdaptState &a = *film->adapt;
+    AdaptImageArgs A;
+    memset(&A, 0, sizeof(A));
+    A.prev = a.prev; A.m2 = a.m2; A.tile_n = a.tile_n; A.tile_k = a.tile_k; A.out = film->out;
+    A.width = film->params.width; A.height = film->params.height; A.tiles_x = a.tiles_x; A.done = a.done; A.steps = a.steps;
+    return A;
+}
+
+// the film's image buffer on the device (vk_film_resolve's), made on first use
+int film_out(vk_film *film, size_t bytes) {
+    int rc = VK_OK;
+    if (!film->out) handle_alloc(rc, film->out, bytes);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_adapt_enable(vk_film *film, const vk_adaptive_params *ap) {
+    if (!film) return fail(VK_ERR_BAD_ARG, "null film");
+    if (ap) if (const char *why = adaptive_refusal(*ap)) return fail(VK_ERR_BAD_ARG, why);
+    if (film->emitted != 0u || film->deposits != 0u)
+        return fail(VK_ERR_BAD_ARG, "vk_adapt_enable comes before the film's first emit or deposit since create / reset");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        if (!film->adapt) {
+            const vk_render_params &P = film->params;
+            std::unique_ptr<AdaptState> a(new AdaptState());
+            a->tiles_x = (P.width + TILE - 1) / TILE;
+            a->tiles = a->tiles_x * ((P.height + TILE - 1) / TILE);
+            const size_t words = (size_t)P.width * P.height * 3u, nb = ((size_t)a->tiles + 1023u) / 1024u;
+            int rc = VK_OK;
+            handle_alloc(rc, a->prev, words * sizeof(long long)); handle_alloc(rc, a->m2, words * sizeof(double));
+            handle_alloc(rc, a->tile_n, (size_t)a->tiles * 4u); handle_alloc(rc, a->tile_k, (size_t)a->tiles * 4u);
+            handle_alloc(rc, a->list, (size_t)a->tiles * 4u); handle_alloc(rc, a->prefix, ((size_t)a->tiles + 1u) * 4u);
+            handle_alloc(rc, a->block_tiles, nb * 4u); handle_alloc(rc, a->block_px, nb * 4u);
+            handle_alloc(rc, a->record, 2u * sizeof(unsigned long long));
+            if (rc != VK_OK) return rc;                  // (the film as it was: `a` lets go of what it got)
+            film->adapt = std::move(a);
+            if ((rc = adapt_zero(film)) != VK_OK) { film->adapt.reset(); return rc; }
+        }
+        film->adapt->judged = ap != nullptr;
+        film->adapt->ap = ap ? *ap : vk_adaptive_params{};
+        return VK_OK;
+    });
+}
+
+int vk_adapt_begin(vk_film *film, vk_paths *batch, uint32_t n_samples) {
+    return guarded([&]() -> int {
+        if (!film || !batch) return fail(VK_ERR_BAD_ARG, "null argument (film or path batch)");
+        int rc = adapt_check(film, "vk_adapt_begin");
+        if (rc != VK_OK) return rc;
+        if (batch->scene != film->scene) return fail(VK_ERR_BAD_ARG, "the path batch belongs to another scene than the film");
+        const AdaptState &a = *film->adapt;
+        if (n_samples == 0u) return fail(VK_ERR_BAD_ARG, "n_samples must be >= 1");
+        if ((uint64_t)a.done + n_samples > film->params.samples_per_pixel)
+            return fail(VK_ERR_BAD_ARG, "samples_done + n_samples exceeds the film's samples_per_pixel");
+        // (pixels <= 2^26 and n_samples <= 2^32: the product fits 64 bits)
+        const uint64_t total = a.px_active * n_samples;
+        if (total >= REGEN_MAX) return fail(VK_ERR_BAD_ARG, "the tile window's paths exceed 2^32 - 1 (fewer samples a run)");
+        vk_scene *q = first_part(film->scene);
+        HIP_TRY(hipSetDevice(q->device));
+        if ((rc = ensure_provenance(q)) != VK_OK) return rc;
+        paths_reset(batch, film_shade_params(film), 0u, 0u);
+        batch->regen = true; batch->regen_film = film; batch->regen_total = total;
+        batch->regen_tiles = true; batch->regen_first_sample = a.done; batch->regen_n_samples = n_samples;
+        regen_note_finished(batch);                        // (no tile active: finished at once)
+        return VK_OK;
+    });
+}
+
+int vk_adapt_close(vk_film *film, uint32_t n_samples, vk_adapt_info *info) {
+    return guarded([&]() -> int {
+        int rc = adapt_check(film, "vk_adapt_close");
+        if (rc != VK_OK) return rc;
+        AdaptState &a = *film->adapt;
+        if (n_samples == 0u) return fail(VK_ERR_BAD_ARG, "n_samples must be >= 1");
+        if ((uint64_t)a.done + n_samples > film->params.samples_per_pixel)
+            return fail(VK_ERR_BAD_ARG, "samples_done + n_samples exceeds the film's samples_per_pixel");
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        const uint32_t done = a.done + n_samples, steps = a.steps + 1u;
+        if (a.n_active != 0u) {
+            AdaptCloseArgs A;
+            memset(&A, 0, sizeof(A));
+            A.sums = reinterpret_cast<const long long *>(film->sums.get()); A.prev = a.prev; A.m2 = a.m2;
+            A.list = a.list; A.tile_n = a.tile_n; A.tile_k = a.tile_k;
+            A.n_active = a.n_active; A.width = film->params.width; A.height = film->params.height; A.tiles_x = a.tiles_x;
+            A.window = n_samples; A.done = done; A.steps = steps;
+            A.gate = (a.judged && done >= a.ap.min_samples && steps >= a.ap.min_steps) ? 1u : 0u;
+            A.abs_tol = a.ap.abs_tol; A.rel_tol = a.ap.rel_tol;
+            launch_adapt_close(A);
+            HIP_TRY(hipGetLastError());
+            const uint64_t px = a.px_active;
+            if (A.gate) { if ((rc = adapt_rebuild(film)) != VK_OK) return rc; }      // (no gate: no tile changed, the list stands)
+            a.samples_rendered += px * n_samples;
+        }
+        a.done = done; a.steps = steps;
+        if (info) {
+            vk_adapt_info I;
+            memset(&I, 0, sizeof(I));
+            I.samples_done = a.done; I.steps = a.steps; I.tiles_total = a.tiles; I.tiles_active = a.n_active;
+            I.pixels_active = a.px_active; I.samples_rendered = a.samples_rendered;
+            *info = I;
+        }
+        return VK_OK;
+    });
+}
+
+int vk_adapt_resolve(vk_film *film, float *rgb_out) {
+    return guarded([&]() -> int {
+        if (!film || !rgb_out) return fail(VK_ERR_BAD_ARG, "null argument (film or rgb_out)");
+        int rc = adapt_check(film, "vk_adapt_resolve");
+        if (rc != VK_OK) return rc;
+        if (film->adapt->done == 0u) return fail(VK_ERR_BAD_ARG, "vk_adapt_resolve before the first vk_adapt_close");
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        const size_t bytes = (size_t)film->params.width * film->params.height * 3u * sizeof(float);
+        if ((rc = film_out(film, bytes)) != VK_OK) return rc;
+        launch_adapt_resolve(adapt_image_args(film));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(rgb_out, film->out, bytes, hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+int vk_adapt_stderr(vk_film *film, float *out) {
+    return guarded([&]() -> int {
+        if (!film || !out) return fail(VK_ERR_BAD_ARG, "null argument (film or out)");
+        int rc = adapt_check(film, "vk_adapt_stderr");
+        if (rc != VK_OK) return rc;
+        if (film->adapt->steps < 2u) return fail(VK_ERR_BAD_ARG, "the standard error needs two closes or more");
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        const size_t bytes = (size_t)film->params.width * film->params.height * 3u * sizeof(float);
+        if ((rc = film_out(film, bytes)) != VK_OK) return rc;
+        launch_adapt_stderr(adapt_image_args(film));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(out, film->out, bytes, hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+int vk_adapt_tile_samples(vk_film *film, uint32_t *out, vk_adaptive_info *info) {
+    return guarded([&]() -> int {
+        int rc = adapt_check(film, "vk_adapt_tile_samples");
+        if (rc != VK_OK) return rc;
+        const AdaptState &a = *film->adapt;
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        if (out) {
+            HIP_TRY(hipMemcpy(out, a.tile_n, (size_t)a.tiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (uint32_t t = 0; t < a.tiles; t++) if (out[t] == 0u) out[t] = a.done;
+        }
+        if (info) {
+            memset(info, 0, sizeof(*info));
+            info->tiles_total = a.tiles; info->tiles_active = a.n_active; info->samples_rendered = a.samples_rendered;
+        }
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): the sums at the last close and the moments
+int vk_debug_adapt_moments(vk_film *film, long long *run, double *m2) {
+    return guarded([&]() -> int {
+        int rc = adapt_check(film, "vk_debug_adapt_moments");
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        const size_t words = (size_t)film->params.width * film->params.height * 3u;
+        if (run) HIP_TRY(hipMemcpy(run, film->adapt->prev, words * sizeof(long long), hipMemcpyDeviceToHost));
+        if (m2) HIP_TRY(hipMemcpy(m2, film->adapt->m2, words * sizeof(double), hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): a tile map imposed, the list rebuilt from it
+int vk_debug_adapt_set_tiles(vk_film *film, const uint32_t *tile_n, const uint32_t *tile_k) {
+    return guarded([&]() -> int {
+        if (!film || !tile_n || !tile_k) return fail(VK_ERR_BAD_ARG, "null argument (film, tile_n or tile_k)");
+        int rc = adapt_check(film, "vk_debug_adapt_set_tiles");
+        if (rc != VK_OK) return rc;
+        AdaptState &a = *film->adapt;
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        HIP_TRY(hipMemcpy(a.tile_n, tile_n, (size_t)a.tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(a.tile_k, tile_k, (size_t)a.tiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+        if ((rc = adapt_rebuild(film)) != VK_OK) return rc;
+        const vk_render_params &P = film->params;
+        a.samples_rendered = 0u;
+        for (uint32_t t = 0; t < a.tiles; t++) {
+            const uint32_t tx = (t % a.tiles_x) * TILE, ty = (t / a.tiles_x) * TILE;
+            const uint64_t px = (uint64_t)std::min<uint32_t>(TILE, P.width - tx) * std::min<uint32_t>(TILE, P.height - ty);
+            a.samples_rendered += px * (tile_n[t] ? tile_n[t] : a.done);
+        }
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): adapt_locate on the device for paths first .. first + m of a tile run over the current tile set
+int vk_debug_adapt_sequence(vk_film *film, uint32_t n_samples, uint64_t first, uint32_t m, uint32_t *pixel_out, uint32_t *sample_out) {
+    return guarded([&]() -> int {
+        if (!film || !pixel_out || !sample_out) return fail(VK_ERR_BAD_ARG, "null argument (film, pixel_out or sample_out)");
+        int rc = adapt_check(film, "vk_debug_adapt_sequence");
+        if (rc != VK_OK) return rc;
+        const AdaptState &a = *film->adapt;
+        if (n_samples == 0u) return fail(VK_ERR_BAD_ARG, "n_samples must be >= 1");
+        const uint64_t total = a.px_active * n_samples;
+        if (total >= REGEN_MAX || (uint64_t)m > PATHS_MAX || first > total || (uint64_t)m > total - first)
+            return fail(VK_ERR_BAD_ARG, "first + m lies beyond the tile run's paths (or m > 2^24, or the run has 2^32 paths or more)");
+        if (m == 0u) return VK_OK;
+        HIP_TRY(hipSetDevice(first_part(film->scene)->device));
+        DeviceBuffer<uint32_t> d;
+        handle_alloc(rc, d, (size_t)m * 2u * sizeof(uint32_t));
+        if (rc != VK_OK) return rc;
+        AdaptSequenceArgs A;
+        memset(&A, 0, sizeof(A));
+        A.T = adapt_tiles(film);
+        A.first_sample = a.done; A.n_samples = n_samples; A.first = (uint32_t)first; A.m = m;
+        A.pixel_out = d.get(); A.sample_out = d.get() + m;
+        launch_adapt_sequence(A);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(pixel_out, A.pixel_out, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(sample_out, A.sample_out, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return VK_OK;
     });
 }
 

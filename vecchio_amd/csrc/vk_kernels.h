@@ -11,13 +11,13 @@
 
 #include "../../include/vecchio_amd.h"
 #include "vk_trace.h"
+#include "vk_emit.h"      // TILE, ACCUM_SCALE, to_fixed*, EmitWindow, start_camera_path: shared with vk_adapt.hip
 
 using namespace vkd;
 
 namespace {
 
 constexpr size_t LDS_PER_CU = 160 * 1024;
-constexpr int TILE = 8;   // 8x8 pixels = one wave
 #ifndef VK_BOX_UNROLL
 #define VK_BOX_UNROLL 4
 #endif
@@ -184,8 +184,8 @@ template <uint32_t F> constexpr uint32_t wave_block_floats() { return 64u * (uin
 // waiting for another one's path.  (The reference's `c += color` in f32, main.rs:193, is re-associated anyway: it never
 // feeds control flow.)  The sums SATURATE instead of wrapping: a sample's components are clamped to +-min(1e10, 1.3e11 / spp), so
 // that spp of them stay below 2^63 * 2^-26 = 1.37e11, and every clamped sample is counted (vk_stats.clamped_samples): the reference
-// adds such a sample in f32 (main.rs:193) and the caller can tell that this frame deviates from it.
-constexpr float ACCUM_SCALE = 67108864.0f;          // 2^26
+// adds such a sample in f32 (main.rs:193) and the caller can tell that this frame deviates from it.  (ACCUM_SCALE, to_fixed_small and
+// to_fixed: vk_emit.h)
 constexpr float ACCUM_CLAMP = 1.0e10f;
 constexpr float ACCUM_RANGE = 1.3e11f;
 inline float accum_clamp_for(uint32_t spp) { float c = ACCUM_RANGE / (float)spp; return c < ACCUM_CLAMP ? c : ACCUM_CLAMP; }     // (host)
@@ -193,11 +193,6 @@ inline float accum_clamp_for(uint32_t spp) { float c = ACCUM_RANGE / (float)spp;
 // at 2^-26: ONE v_cvt_i32_f32 (truncating, like the 64-bit cast) and a sign extension, against ~17 instructions for the float ->
 // 64-bit integer conversion the compiler has to expand.
 constexpr float ACCUM_SMALL = 31.999f;
-__device__ __forceinline__ long long to_fixed_small(float v) { return (long long)(int)(v * ACCUM_SCALE); }
-__device__ __forceinline__ long long to_fixed(float v, float clampv) {
-    v = fminf(fmaxf(v, -clampv), clampv);
-    return (long long)(v * ACCUM_SCALE);             // scaling by a power of two is exact; the cast truncates toward zero
-}
 
 template <uint32_t F>
 __device__ __forceinline__ void cold_store_path(float *c, uint32_t lane, const Lane &L) {
@@ -2374,30 +2369,7 @@ constexpr int FILM_T = 256;
 // beyond the spread of the repetitions; at 1 sample per pixel, where no two neighbours share a pixel, the two are level
 constexpr bool FILM_DEPOSIT_RUNS = true;
 
-// A window of the film's frame and of its samples.  Its paths are numbered q = (row-major pixel of the window) * n_samples + k; path q is
-// sample first_sample + k of that pixel.
-struct EmitWindow {
-    uint32_t x0, y0, win_width, first_sample, n_samples;
-};
-// The start of camera path q of window W, for one lane: start_sample_core itself — the render kernel's camera, on the film's frame —
-// gives the ray, and the state resumes the sample's stream right behind the camera's draws.  The lens disk's rejection loop diverges, and
-// may.  The ray (32 bytes), the state (48) and the id q are written at `slot` as vk_paths_begin would have staged them.
-__device__ __forceinline__ void start_camera_path(const RenderConsts &C, const EmitWindow &W, uint32_t q, size_t slot, uint4 *rays,
-                                                  uint4 *states, uint32_t *ids) {
-    const uint32_t wp = q / W.n_samples, k = q - wp * W.n_samples;
-    const uint32_t wy = wp / W.win_width, wx = wp - wy * W.win_width;
-    Lane L;
-    V3 o, d;
-    float time;
-    start_sample_core(L, C, W.x0 + wx, W.y0 + wy, W.first_sample + k, o, d, time);
-    uint4 *r = rays + slot * 2u, *s = states + slot * 3u;
-    r[0] = make_uint4(__float_as_uint(o.x), __float_as_uint(o.y), __float_as_uint(o.z), 0x7F800000u /* tmax = +INFINITY */);
-    r[1] = make_uint4(__float_as_uint(d.x), __float_as_uint(d.y), __float_as_uint(d.z), __float_as_uint(time));
-    s[0] = make_uint4(__float_as_uint(L.thr.x), __float_as_uint(L.thr.y), __float_as_uint(L.thr.z), L.depth);
-    s[1] = make_uint4(__float_as_uint(L.acc.x), __float_as_uint(L.acc.y), __float_as_uint(L.acc.z), L.rng.ctr);
-    s[2] = make_uint4((uint32_t)C.seed, (uint32_t)(C.seed >> 32), L.pixel, L.sample);
-    ids[slot] = q;
-}
+// (EmitWindow and start_camera_path: vk_emit.h)
 // film_emit_kernel: one lane per path of the window, path i in slot i: no iota launch.
 struct FilmEmitArgs {
     RenderConsts C;          // the film's camera, frame and seed

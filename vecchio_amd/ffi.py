@@ -246,6 +246,12 @@ class RegenInfo(C.Structure):
                 ("kernel_ms", C.c_double), ("seconds", C.c_double)]
 
 
+class AdaptInfo(C.Structure):
+    """vk_adapt_info (vk_adapt_close)"""
+    _fields_ = [("samples_done", C.c_uint32), ("steps", C.c_uint32), ("tiles_total", C.c_uint32), ("tiles_active", C.c_uint32),
+                ("pixels_active", C.c_uint64), ("samples_rendered", C.c_uint64)]
+
+
 class DebugStreamKey(C.Structure):
     """vk_debug_stream_key of include/vecchio_amd_debug.h (vk_debug_trace_radiance_samples)"""
     _fields_ = [("seed", C.c_uint64), ("pixel", C.c_uint32), ("sample", C.c_uint32), ("ctr", C.c_uint32), ("_pad", C.c_uint32)]
@@ -352,6 +358,7 @@ DEVICE_SYMBOLS = [
     "vk_paths_destroy", "vk_roulette_set", "vk_roulette_get",
     "vk_film_create", "vk_film_emit", "vk_film_deposit", "vk_film_resolve", "vk_film_reset", "vk_film_get_info", "vk_film_destroy",
     "vk_regen_begin", "vk_regen_step", "vk_regen_cull",
+    "vk_adapt_enable", "vk_adapt_begin", "vk_adapt_close", "vk_adapt_resolve", "vk_adapt_stderr", "vk_adapt_tile_samples",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -483,6 +490,18 @@ def _bind(lib):
     lib.vk_regen_step.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(RegenInfo)]
     lib.vk_regen_cull.restype = C.c_int
     lib.vk_regen_cull.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_adapt_enable.restype = C.c_int
+    lib.vk_adapt_enable.argtypes = [C.c_void_p, C.POINTER(AdaptiveParams)]
+    lib.vk_adapt_begin.restype = C.c_int
+    lib.vk_adapt_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.vk_adapt_close.restype = C.c_int
+    lib.vk_adapt_close.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(AdaptInfo)]
+    lib.vk_adapt_resolve.restype = C.c_int
+    lib.vk_adapt_resolve.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_adapt_stderr.restype = C.c_int
+    lib.vk_adapt_stderr.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_adapt_tile_samples.restype = C.c_int
+    lib.vk_adapt_tile_samples.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AdaptiveInfo)]
     lib.vk_probe_eval.restype = C.c_int
     lib.vk_probe_eval.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.vk_trace_occluded_device.restype = C.c_int
@@ -544,6 +563,12 @@ def _bind(lib):
     lib.vk_debug_film_deposit_form.argtypes = [C.c_void_p, C.c_int]
     lib.vk_debug_regen_last_ms.restype = C.c_int
     lib.vk_debug_regen_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 4)]
+    lib.vk_debug_adapt_moments.restype = C.c_int
+    lib.vk_debug_adapt_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_debug_adapt_set_tiles.restype = C.c_int
+    lib.vk_debug_adapt_set_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_debug_adapt_sequence.restype = C.c_int
+    lib.vk_debug_adapt_sequence.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.vk_debug_trace_occluded_device.restype = C.c_int
     lib.vk_debug_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_uint32, C.c_uint32]

@@ -142,6 +142,10 @@ pub struct vk_film_window { pub x0: u32, pub y0: u32, pub width: u32, pub height
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_film_info { pub width: u32, pub height: u32, pub samples_per_pixel: u32, pub _pad: u32, pub emitted: u64, pub deposited: u64, pub dropped: u64, pub clamped: u64, pub skipped: u64, pub deposits: u64 }
 
+// a film's error moments and tile map: what one vk_adapt_close left
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_adapt_info { pub samples_done: u32, pub steps: u32, pub tiles_total: u32, pub tiles_active: u32, pub pixels_active: u64, pub samples_rendered: u64 }
+
 // regeneration: what one vk_regen_step did
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_regen_info { pub traced: u64, pub live: u64, pub remaining: u64, pub emitted: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
@@ -252,6 +256,14 @@ extern "C" {
     pub fn vk_regen_begin(film: *mut vk_film, batch: *mut vk_paths, win: *const vk_film_window) -> c_int;
     pub fn vk_regen_step(film: *mut vk_film, batch: *mut vk_paths, max_bounces: u32, info: *mut vk_regen_info) -> c_int;
     pub fn vk_regen_cull(film: *mut vk_film, batch: *mut vk_paths, keep: *const u8, scale: *const f32) -> c_int;
+    // a film's error moments and adaptive regeneration (additive symbols of ABI 7): enable before the first emit, then per window
+    // vk_adapt_begin, vk_regen_step until the run is finished, vk_adapt_close; ap null keeps the moments and freezes no tile
+    pub fn vk_adapt_enable(film: *mut vk_film, ap: *const vk_adaptive_params) -> c_int;
+    pub fn vk_adapt_begin(film: *mut vk_film, batch: *mut vk_paths, n_samples: u32) -> c_int;
+    pub fn vk_adapt_close(film: *mut vk_film, n_samples: u32, info: *mut vk_adapt_info) -> c_int;
+    pub fn vk_adapt_resolve(film: *mut vk_film, rgb_out: *mut f32) -> c_int;
+    pub fn vk_adapt_stderr(film: *mut vk_film, out: *mut f32) -> c_int;
+    pub fn vk_adapt_tile_samples(film: *mut vk_film, out: *mut u32, info: *mut vk_adaptive_info) -> c_int;
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

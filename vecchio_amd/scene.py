@@ -1017,6 +1017,96 @@ class Film:
                     cull(batch)
         return self.resolve()
 
+    def enable_adaptive(self, abs_tol=None, rel_tol=0.0, min_samples=0, min_steps=2):
+        """Error moments next to the sums (vk_adapt_enable), before the first emit or deposit since create / reset.  With abs_tol None
+        moments only: no tile ever freezes.  Otherwise Progress.set_adaptive's rule runs behind every adapt_close()."""
+        ap = None if abs_tol is None else ffi.AdaptiveParams(abs_tol, rel_tol, min_samples, min_steps)
+        check(self._lib, self._lib.vk_adapt_enable(self._h, C.byref(ap) if ap is not None else None))
+
+    def adapt_begin(self, batch, n_samples):
+        """Put `batch` into its regenerating state for the tile window (vk_adapt_begin): the next n_samples samples of every pixel of
+        every active tile; regen_step() and regen_cull() run it."""
+        check(self._lib, self._lib.vk_adapt_begin(self._h, batch._h, n_samples))
+
+    def adapt_close(self, n_samples):
+        """Every pixel of every active tile has received its next n_samples samples (vk_adapt_close): fold them into the moments, judge
+        the tiles, rebuild the list.  The ffi.AdaptInfo behind it."""
+        info = ffi.AdaptInfo()
+        check(self._lib, self._lib.vk_adapt_close(self._h, n_samples, C.byref(info)))
+        return info
+
+    def resolve_adaptive(self, out=None):
+        """The frame of the last adapt_close(), every pixel the mean over its tile's own count (vk_adapt_resolve)"""
+        p = self.params
+        if out is None:
+            out = np.zeros((p.height, p.width, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == p.width * p.height * 3
+        check(self._lib, self._lib.vk_adapt_resolve(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def stderr(self):
+        """Batch-means standard error of resolve_adaptive()'s frame (vk_adapt_stderr), float32 (height, width, 3), y = 0 the bottom row:
+        the stderr3 image denoise() and Temporal.accumulate() take.  Two closes or more."""
+        p = self.params
+        out = np.zeros((p.height, p.width, 3), np.float32)
+        check(self._lib, self._lib.vk_adapt_stderr(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def tile_samples(self):
+        """(samples per tile as uint32 (tiles_y, tiles_x), tile row 0 at the bottom; vk_adaptive_info): Progress.tile_samples()' layout"""
+        p = self.params
+        out = np.zeros(((p.height + 7) // 8, (p.width + 7) // 8), np.uint32)
+        inf = ffi.AdaptiveInfo()
+        check(self._lib, self._lib.vk_adapt_tile_samples(self._h, out.ctypes.data_as(C.c_void_p), C.byref(inf)))
+        return out, inf
+
+    def render_adaptive(self, batch, window, cull=None):
+        """Windows of `window` samples through tile runs — adapt_begin(), regen_step() to the run's end, adapt_close() — until the
+        film's samples_per_pixel is reached or no tile is active.  cull as in render_regen().  Returns (resolve_adaptive(), the last
+        close's ffi.AdaptInfo, None where no window was run); needs enable_adaptive()."""
+        spp = self.params.samples_per_pixel
+        tiles, inf = self.tile_samples()
+        # (a frozen tile's count is at most samples_done, an active tile's is samples_done)
+        done, active, info = int(tiles.max()), inf.tiles_active, None
+        while active and done < spp:
+            n = min(window, spp - done)
+            self.adapt_begin(batch, n)
+            while True:
+                r = self.regen_step(batch, 1 if cull is not None else 0xFFFFFFFF)
+                if r.live == 0 and r.remaining == 0:
+                    break
+                if cull is not None and r.live:
+                    cull(batch)
+            info = self.adapt_close(n)
+            done, active = info.samples_done, info.tiles_active
+        return self.resolve_adaptive(), info
+
+    def debug_moments(self):
+        """(the sums at the last close as int64, the error moments as float64), each (height, width, 3) y up: vk_debug_adapt_moments, a
+        test hook in Progress.moments()' layout"""
+        p = self.params
+        run, m2 = np.zeros((p.height, p.width, 3), np.int64), np.zeros((p.height, p.width, 3), np.float64)
+        check(self._lib, self._lib.vk_debug_adapt_moments(self._h, run.ctypes.data_as(C.c_void_p), m2.ctypes.data_as(C.c_void_p)))
+        return run, m2
+
+    def debug_set_tiles(self, tile_n, tile_k=None):
+        """Impose a tile map (vk_debug_adapt_set_tiles, a test hook): tile_n (tiles_y, tiles_x), 0 = active; tile_k defaults to 2 where
+        a tile is frozen"""
+        p = self.params
+        tile_n = np.ascontiguousarray(tile_n, np.uint32).reshape(-1)
+        assert tile_n.size == ((p.height + 7) // 8) * ((p.width + 7) // 8)
+        tile_k = np.where(tile_n != 0, 2, 0).astype(np.uint32) if tile_k is None else np.ascontiguousarray(tile_k, np.uint32).reshape(-1)
+        assert tile_k.size == tile_n.size
+        check(self._lib, self._lib.vk_debug_adapt_set_tiles(self._h, tile_n.ctypes.data_as(C.c_void_p), tile_k.ctypes.data_as(C.c_void_p)))
+
+    def debug_sequence(self, n_samples, first, m):
+        """(pixel, sample) uint32 arrays of paths first .. first + m of a tile run of n_samples over the current tile set, from the top-up
+        kernel's index code on the device (vk_debug_adapt_sequence, a test hook)"""
+        pixel, sample = np.zeros(m, np.uint32), np.zeros(m, np.uint32)
+        check(self._lib, self._lib.vk_debug_adapt_sequence(self._h, n_samples, first, m, pixel.ctypes.data_as(C.c_void_p),
+                                                           sample.ctypes.data_as(C.c_void_p)))
+        return pixel, sample
+
     def regen_last_ms(self, batch):
         """(top-up, trace, shade, compaction with deposit) device milliseconds of the regenerating batch's last bounce
         (vk_debug_regen_last_ms, a test hook)"""
