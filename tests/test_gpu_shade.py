@@ -1,5 +1,6 @@
 """Shade queries on the device: the loop of vk_shade_hits' contract (DeviceScene.wavefront_radiance: vk_trace_rays and vk_shade_hits in
-turn) against the radiance query's per-sample hook on the scenes and rays of tests/test_shade_emu.py, bit for bit; vk_shade_hits against
+turn) against the radiance query's per-sample hook on the scenes and rays of tests/test_shade_emu.py, bit for bit — the record form of
+vk_trace.h shade_core (shade_hits_kernel) against the walk form of the same body (radiance_kernel); vk_shade_hits against
 the emulator on identical inputs in the scenes with media and for bad hits; batch sizes around a wave, a cut batch, a chunk cut;
 refusals; no side effect on vk_render or a vk_progress handle."""
 import ctypes as C

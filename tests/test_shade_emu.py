@@ -1,7 +1,8 @@
 """Shade queries on the CPU: vk_trace.h shade_hit (through tests/emu/emu_shade.cpp) in the loop of vk_shade_hits' contract around the rays
 emulator, against the radiance emulator (vk_trace.h radiance_sample, which the existing suite ties to the oracle): in every scene
 without a ConstantMedium the loop's radiance and final stream counter equal the radiance query's sample bit for bit, for both
-integrators and two depth limits.  With media the loop runs to its end on valid records.  Bad hits are refused per item.
+integrators and two depth limits.  The two sides are the two forms of ONE body, vk_trace.h shade_core: shade_hit runs its record form
+(the hit as the caller's record), radiance_sample its walk form (the hit as the walk left it in the lane).  With media the loop runs to its end on valid records.  Bad hits are refused per item.
 tests/test_gpu_shade.py runs the same scenes and rays on the device."""
 import numpy as np
 import pytest

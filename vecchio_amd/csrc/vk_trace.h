@@ -1392,19 +1392,32 @@ VK_HD V3 background_of(const RenderConsts &C, V3 ud) {       // ud = unit(ray di
 // Called when traversal of the current segment has finished.  Returns true when the path continues with
 // the ray (no, nd, ntime) (the caller installs it with begin_segment), false when the path ended (L.acc is
 // its radiance).
-template <uint32_t F, class Mem>
+// ONE body, two forms.  The walk form (REC false: the path kernels) takes the segment's outcome from the Lane: best_prim, build_record,
+// the material lookup.  The record form (REC true: shade_record, the shade queries) takes it from `in` — the outcome `miss`, the
+// record and its material record, both unread on a miss — reads nothing of the walk, and reports through `lobe` the VK_MAT_* of the
+// material finally sampled (behind SpecDiffuse's draws), 0xFFFFFFFF on a miss.  The record is a LOCAL in both forms, filled by
+// build_record or copied from the caller's: a body that reaches it through a reference or a pointer, even one bound to this same
+// local, moves the register allocation of 33 of the walk form's kernels (Shade queries).  With REC false this is the
+// function those kernels were tuned on, statement for statement: keep the order of its declarations, and compare every kernel's
+// assembly with the build before after a change here.
+struct ShadeInput { const Rec *R; const DMaterial *m; bool miss; };   // the record form's inputs
+template <uint32_t F, class Mem, bool REC = false>
 VK_HD bool shade_core(Lane &L, const DScene &S, const Mem &M, const RenderConsts &C, V3 &no, V3 &ndir, float &ntime,
-    const PreTurb &pt = no_pre_turb(), const PreBall &pb = no_pre_ball()) {
-    const bool miss = L.best_prim == 0;
+    const PreTurb &pt = no_pre_turb(), const PreBall &pb = no_pre_ball(), const ShadeInput *in = nullptr, uint32_t *lobe = nullptr) {
+    bool miss;
+    if constexpr (REC) { miss = in->miss; *lobe = 0xFFFFFFFFu; } else miss = L.best_prim == 0;
     Rec R;
     const DMaterial *m = S.materials;
+    if constexpr (REC) { R = *in->R; m = in->m; }
     uint32_t k0 = VK_MAT_LAMBERTIAN;
     if (!miss) {
-        build_record<F, Mem>(L, S, M, R);
-        // sphere-only variants: the material record by SPHERE index (DScene::sphere_material), one gather instead of two dependent ones
-        // (sphere -> material index -> record): the 1 M-sphere scene +1.5 %, C2 +-0
-        if constexpr ((F & ~(uint32_t)VKF_INTEG_PDF) == 0u) m = &S.sphere_material[VKD_INDEX(L.best_prim)];
-        else m = &S.materials[R.mat];
+        if constexpr (!REC) {
+            build_record<F, Mem>(L, S, M, R);
+            // sphere-only variants: the material record by SPHERE index (DScene::sphere_material), one gather instead of two dependent ones
+            // (sphere -> material index -> record): the 1 M-sphere scene +1.5 %, C2 +-0
+            if constexpr ((F & ~(uint32_t)VKF_INTEG_PDF) == 0u) m = &S.sphere_material[VKD_INDEX(L.best_prim)];
+            else m = &S.materials[R.mat];
+        }
         k0 = m->kind;
     }
     V3 rd = L.wd;                                             // `r` of ray_color is the world-space ray
@@ -1427,6 +1440,7 @@ VK_HD bool shade_core(Lane &L, const DScene &S, const Mem &M, const RenderConsts
         V3 atten;
         bool scattered = true;
         uint32_t kind = m->kind;
+        if constexpr (REC) *lobe = kind;
         if (kind == VK_MAT_LAMBERTIAN) {                      // material.rs:85-90
             ndir = R.n + lambertian_random(L.rng);
             atten = material_color<F>(S, *m, R, pt);
@@ -1451,7 +1465,9 @@ VK_HD bool shade_core(Lane &L, const DScene &S, const Mem &M, const RenderConsts
             atten = material_color<F>(S, *m, R, pt);
         } else {                                              // DiffuseLight: material.rs:215-225
             scattered = false;
-            if (kind == VK_MAT_DIFFUSE_LIGHT && R.front) emitted = material_color<F>(S, *m, R, pt);
+            // (the record form reads this one `front` where the caller has it, the same value: behind the comparison it is a load,
+            // the && stays a branch, and shade_hits_kernel<0x17F> keeps 92 VGPRs where R.front gives 98 — DESIGN.md, Shade queries)
+            if (kind == VK_MAT_DIFFUSE_LIGHT && (REC ? in->R->front : R.front)) emitted = material_color<F>(S, *m, R, pt);
         }
         L.acc = L.acc + L.thr * emitted;
         if (!scattered) return false;
@@ -1459,6 +1475,7 @@ VK_HD bool shade_core(Lane &L, const DScene &S, const Mem &M, const RenderConsts
     } else {
         // HEAD integrator, main.rs:131-149
         V3 emitted = v3s(0.0f);
+        if constexpr (REC) *lobe = m->kind;
         if (m->kind == VK_MAT_DIFFUSE_LIGHT) {
             if (R.front) emitted = material_color<F>(S, *m, R, pt);
             L.acc = L.acc + L.thr * emitted;                  // scatter_with_pdf is None: return emitted
@@ -1470,6 +1487,7 @@ VK_HD bool shade_core(Lane &L, const DScene &S, const Mem &M, const RenderConsts
                 uint32_t pick = vk::gen_f32(L.rng) < m->param ? (m->ab & 0xFFFFu) : (m->ab >> 16);
                 m = &S.materials[pick];
             }
+            if constexpr (REC) *lobe = m->kind;
             if (m->kind == VK_MAT_DIFFUSE_LIGHT) { L.acc = L.acc + L.thr * emitted; return false; }
         }
         uint32_t kind = m->kind;
@@ -1647,14 +1665,19 @@ VK_HD uint64_t ray_seed(uint64_t seed, uint64_t index) { return seed + 0x9E3779B
 // world.hit(&Ray{o, d, time}, T_MIN, tmax) on S (which must be a tree view: no grid, no rebuilt-form gates): begin_segment with tmax as
 // the closest distance so far, the walk, the full record (u and v always), and the description record whose own hit() produced the
 // winner (P).  A tmax that is a NaN or <= T_MIN misses without a walk (the walk's bounds need a positive tmax).
-template <uint32_t F, class Mem>
+// ONE walk, two forms, which differ in the stream a ConstantMedium met on the way draws from.  The seed form (STREAM false: the ray
+// queries) derives it from the ray's own seed, and only for a segment that is walked: L.rng is left alone otherwise.  The stream form
+// (STREAM true: trace_path, the path batches) takes `rng`, the path's own stream, where it stands, and L.rng holds it afterwards whether
+// the segment was walked or not; rseed is not read.
+template <uint32_t F, class Mem, bool STREAM = false>
 VK_HD void trace_ray(Lane &L, const DScene &S, const Mem &M, const DProvenance &P, V3 o, V3 d, float time, float tmax, uint64_t rseed,
-    RayHit &H) {
+    RayHit &H, const Rng *rng = nullptr) {
     H.R.p = v3s(0.0f); H.R.n = v3s(0.0f); H.R.u = 0.0f; H.R.v = 0.0f; H.R.front = false; H.R.mat = 0u;
     H.t = INFINITY; H.hit = 0u; H.object = 0u; H.medium = 0u;
+    if constexpr (STREAM) { if (F & VKF_MEDIUM) L.rng = *rng; }
     if (!(tmax > T_MIN)) return;
     L.depth = 0u; L.pixel = 0u; L.sample = 0u;
-    if (F & VKF_MEDIUM) L.rng = vk::rng_for_sample(rseed, 0u, 0u);
+    if constexpr (!STREAM) { if (F & VKF_MEDIUM) L.rng = vk::rng_for_sample(rseed, 0u, 0u); }
     begin_segment<Mem::ISHIFT, fused_box<F, Mem>(), spheres_only<F>()>(L, S, o, d, time, false, tmax);
     while (traversing(L)) traverse_step<F, Mem>(L, S, M);
     if (L.best_prim == 0u) return;
@@ -1773,143 +1796,14 @@ VK_HD V3 probe_sample(Lane &L, const DScene &S, const Mem &M, const RenderConsts
 }
 
 // ------------------------------------------------------------------ shade queries (vk_shade_hits, include/vecchio_amd.h)
-// One bounce of ray_color behind the walk: the segment's outcome is `miss`, or the record R whose material record is m (both unread
-// on a miss).  Reads L.wd, L.time and the path state (thr, acc, depth, rng), nothing of the walk.  Returns true when the path continues
-// with the ray (no, nd, ntime), false when it ended (L.acc is its radiance).  lobe: VK_MAT_* of the material finally sampled (behind
-// SpecDiffuse's draws), 0xFFFFFFFF on a miss.
-// A SECOND COPY of shade_core's body behind its build_record and material lookup, line for line, plus `lobe`: calling this from
-// shade_core moved the register allocation of thirteen kernels (Shade queries), so shade_core stays as it was and the
-// bit-for-bit loop tests (tests/test_shade_emu.py, tests/test_gpu_shade.py) hold the two together.  A change to one is a change to both.
+// One bounce of ray_color behind the walk: shade_core's record form (REC), for a segment whose outcome is `miss`, or the record R whose
+// material record is m (both unread on a miss).  Reads L.wd, L.time and the path state (thr, acc, depth, rng), nothing of the walk.
+// Returns what shade_core returns.  lobe: VK_MAT_* of the material finally sampled (behind SpecDiffuse's draws), 0xFFFFFFFF on a miss.
 template <uint32_t F, class Mem>
 VK_HD bool shade_record(Lane &L, const DScene &S, const Mem &M, const RenderConsts &C, const Rec &R, const DMaterial *m, bool miss, V3 &no,
     V3 &ndir, float &ntime, const PreTurb &pt, const PreBall &pb, uint32_t &lobe) {
-    lobe = 0xFFFFFFFFu;
-    uint32_t k0 = VK_MAT_LAMBERTIAN;
-    if (!miss) k0 = m->kind;
-    V3 rd = L.wd;                                             // `r` of ray_color is the world-space ray
-    // unit_vector(r.direction) is what the sky, Metal and Dielectric start from (main.rs IOW sky; material.rs:119,
-    // 155,182): one copy of its three divisions + square root for the whole wave instead of one per branch
-    V3 ud = rd;
-    {
-        if (F & VKF_SPEC_DIFFUSE) k0 = (k0 == VK_MAT_SPEC_DIFFUSE) ? (uint32_t)VK_MAT_METAL : k0;   // its children may need it
-        bool need_ud = miss ? (C.background == VK_BACKGROUND_SKY) : (k0 == VK_MAT_METAL || k0 == VK_MAT_DIELECTRIC);
-        if (need_ud) ud = unit(rd);
-    }
-    if (miss) {                                               // miss: main.rs:150-152
-        L.acc = L.acc + L.thr * background_of(C, ud);
-        return false;
-    }
-    ntime = L.time;
-    if (!(F & VKF_INTEG_PDF)) {
-        // emitted + attenuation * ray_color(scattered): Material::emitted + Material::scatter
-        V3 emitted = v3s(0.0f);
-        V3 atten;
-        bool scattered = true;
-        uint32_t kind = m->kind;
-        lobe = kind;
-        if (kind == VK_MAT_LAMBERTIAN) {                      // material.rs:85-90
-            ndir = R.n + lambertian_random(L.rng);
-            atten = material_color<F>(S, *m, R, pt);
-        } else if (kind == VK_MAT_METAL) {                    // material.rs:118-132
-            V3 reflected = reflect(ud, R.n);
-            ndir = reflected + ball_sample(L.rng, pb) * m->param;      // (no draw before it: see cooperative_ball)
-            atten = material_color<F>(S, *m, R, pt);
-            scattered = dot(ndir, R.n) > 0.0f;
-        } else if (kind == VK_MAT_DIELECTRIC) {               // material.rs:150-175
-            atten = v3s(1.0f);
-            float eta = R.front ? 1.0f / m->param : m->param;
-            float cos_theta = fminf(dot(-ud, R.n), 1.0f);
-            float sin_theta = sqrtf(1.0f - cos_theta * cos_theta);
-            if (eta * sin_theta > 1.0f) ndir = reflect(ud, R.n);
-            else {
-                float reflect_prob = schlick(cos_theta, eta);
-                if (vk::gen_f32(L.rng) < reflect_prob) ndir = reflect(ud, R.n);
-                else ndir = refract(ud, R.n, eta);
-            }
-        } else if (kind == VK_MAT_ISOTROPIC) {                // material.rs:442-446
-            ndir = ball_sample(L.rng, pb);
-            atten = material_color<F>(S, *m, R, pt);
-        } else {                                              // DiffuseLight: material.rs:215-225
-            scattered = false;
-            if (kind == VK_MAT_DIFFUSE_LIGHT && R.front) emitted = material_color<F>(S, *m, R, pt);
-        }
-        L.acc = L.acc + L.thr * emitted;
-        if (!scattered) return false;
-        L.thr = L.thr * atten;
-    } else {
-        // HEAD integrator, main.rs:131-149
-        V3 emitted = v3s(0.0f);
-        lobe = m->kind;
-        if (m->kind == VK_MAT_DIFFUSE_LIGHT) {
-            if (R.front) emitted = material_color<F>(S, *m, R, pt);
-            L.acc = L.acc + L.thr * emitted;                  // scatter_with_pdf is None: return emitted
-            return false;
-        }
-        const DMaterial *outer = m;
-        if (F & VKF_SPEC_DIFFUSE) {
-            for (int guard = 0; guard < 8 && m->kind == VK_MAT_SPEC_DIFFUSE; guard++) {   // material.rs:475-483
-                uint32_t pick = vk::gen_f32(L.rng) < m->param ? (m->ab & 0xFFFFu) : (m->ab >> 16);
-                m = &S.materials[pick];
-            }
-            lobe = m->kind;
-            if (m->kind == VK_MAT_DIFFUSE_LIGHT) { L.acc = L.acc + L.thr * emitted; return false; }
-        }
-        uint32_t kind = m->kind;
-        if (kind == VK_MAT_METAL) {                           // material.rs:134-141 (Ray::new: time 0, never absorbs)
-            V3 reflected = reflect(ud, R.n);
-            // (computed ahead only where the hit's own material is the Metal: no SpecDiffuse draw before it)
-            ndir = reflected + ball_sample(L.rng, pb) * m->param;
-            ntime = 0.0f;
-            L.thr = L.thr * material_color<F>(S, *m, R, pt);         // specular: emitted is NOT added (main.rs:134-137)
-        } else if (kind == VK_MAT_DIELECTRIC) {               // material.rs:177-206
-            float eta = R.front ? 1.0f / m->param : m->param;
-            float cos_theta = fminf(dot(-ud, R.n), 1.0f);
-            float sin_theta = sqrtf(1.0f - cos_theta * cos_theta);
-            if (eta * sin_theta > 1.0f) ndir = reflect(ud, R.n);
-            else {
-                float reflect_prob = schlick(cos_theta, eta);
-                if (vk::gen_f32(L.rng) < reflect_prob) ndir = reflect(ud, R.n);
-                else ndir = refract(ud, R.n, eta);
-            }
-        } else {                                              // Lambertian / Isotropic: material.rs:92-98,448-454
-            V3 atten = material_color<F>(S, *m, R, pt);
-            Onb uvw = onb_from_w(R.n);                        // CosinePDF::new(rec.normal)
-            // MixturePDF::generate, util.rs:177-185
-            if (vk::gen_f32(L.rng) < 0.5f) {
-                // HittablePDF::generate -> lights.random(o): Vec::random, hittable.rs:429-433
-                uint32_t li = vk::gen_index(L.rng, S.n_lights);
-                ndir = object_random(S, M, L.rng, S.lights[li], R.p);
-            } else {
-                ndir = onb_local(uvw, random_cosine_direction(L.rng));
-            }
-            // MixturePDF::value, util.rs:173-175
-            float weight = 1.0f / (float)S.n_lights;          // Vec::pdf_value, hittable.rs:420-427
-            float lsum = 0.0f;
-            for (uint32_t j = 0; j < S.n_lights; j++) lsum += weight * object_pdf_value(S, M, S.lights[j], R.p, ndir);
-            float cosv = dot(unit(ndir), uvw.w);              // CosinePDF::value, util.rs:134-142
-            float cpdf = cosv <= 0.0f ? 0.0f : cosv / PI_F;
-            float pdf = 0.5f * lsum + 0.5f * cpdf;
-            // scattering_pdf of the OUTER material (main.rs:145; SpecDiffuse forwards to its diffuse child)
-            const DMaterial *sm = outer;
-            if (F & VKF_SPEC_DIFFUSE) {
-                for (int guard = 0; guard < 8 && sm->kind == VK_MAT_SPEC_DIFFUSE; guard++) sm = &S.materials[sm->ab >> 16];
-            }
-            float spdf = 0.0f;
-            if (sm->kind == VK_MAT_LAMBERTIAN || sm->kind == VK_MAT_ISOTROPIC) {   // material.rs:100-108,456-464
-                float cs = dot(R.n, unit(ndir));
-                spdf = cs < 0.0f ? 0.0f : cs / PI_F;
-            }
-            L.acc = L.acc + L.thr * emitted;
-            L.thr = (L.thr * (atten * spdf)) / pdf;
-        }
-    }
-    L.depth += 1;
-    if (L.depth > C.max_depth) {                              // main.rs:126-128: the next call returns 0
-        L.acc = L.acc + L.thr * v3s(0.0f);                    // keeps the reference's 0*inf / 0/0 -> NaN drops
-        return false;
-    }
-    no = R.p;
-    return true;
+    const ShadeInput in{&R, m, miss};
+    return shade_core<F, Mem, true>(L, S, M, C, no, ndir, ntime, pt, pb, &in, &lobe);
 }
 // One bounce for a (ray, hit, path state) the caller supplies, each as its 32-bit words (vk_ray: 8, vk_hit: 16, vk_path_state: 12):
 // shade_record on a Lane that holds the ray's direction and time and the state, with a record built from the vk_hit in place of
@@ -1957,33 +1851,11 @@ VK_HD void shade_hit(const DScene &S, const Mem &M, const RenderConsts &C, uint3
 }
 
 // ------------------------------------------------------------------ path batches (vk_paths_*, include/vecchio_amd.h)
-// trace_ray's sibling for a segment of a PATH: the same guard, begin_segment, walk, record and provenance, but a ConstantMedium met on
-// the way draws from `rng`, the path's own stream taken where it stands — what radiance_sample's walk does inside a sample.  L.rng holds
-// the stream afterwards (untouched by a segment that is not walked).  A second copy of trace_ray's dozen lines: trace_ray itself stays
-// as it is, and with it every earlier kernel's register allocation.
-template <uint32_t F, class Mem>
-VK_HD void trace_ray_on_stream(Lane &L, const DScene &S, const Mem &M, const DProvenance &P, V3 o, V3 d, float time, float tmax, const Rng &rng,
-    RayHit &H) {
-    H.R.p = v3s(0.0f); H.R.n = v3s(0.0f); H.R.u = 0.0f; H.R.v = 0.0f; H.R.front = false; H.R.mat = 0u;
-    H.t = INFINITY; H.hit = 0u; H.object = 0u; H.medium = 0u;
-    if (F & VKF_MEDIUM) L.rng = rng;
-    if (!(tmax > T_MIN)) return;
-    L.depth = 0u; L.pixel = 0u; L.sample = 0u;
-    begin_segment<Mem::ISHIFT, fused_box<F, Mem>(), spheres_only<F>()>(L, S, o, d, time, false, tmax);
-    while (traversing(L)) traverse_step<F, Mem>(L, S, M);
-    if (L.best_prim == 0u) return;
-    build_record<F, Mem, true>(L, S, M, H.R);
-    H.t = L.T; H.hit = 1u;
-    const uint32_t k = VKD_KIND(L.best_prim), idx = VKD_INDEX(L.best_prim);
-    if ((F & VKF_MEDIUM) && k == DK_MEDIUM) { H.object = VK_MAKE_REF(VK_KIND_MEDIUM, P.medium[idx]); H.medium = 1u; }
-    else if ((F & VKF_BOX) && k == DK_BOX) H.object = VK_MAKE_REF(VK_KIND_RECT, P.box_face[idx * 6u + vk::f32_bits(L.best_aux)]);
-    else if ((F & VKF_RECT) && k == DK_RECT) H.object = VK_MAKE_REF(VK_KIND_RECT, P.rect[idx]);
-    else if ((F & VKF_MOVING) && k == DK_MOVING) H.object = VK_MAKE_REF(VK_KIND_MOVING_SPHERE, P.moving[idx]);
-    else H.object = VK_MAKE_REF(VK_KIND_SPHERE, P.sphere[idx]);
-}
 // One segment of a path batch on the words of its vk_ray (8) and of the second and third quarter of its vk_path_state (st47: acc and
-// counter, st811: seed, pixel, sample): the stream is set up the way shade_hit sets it up, the vk_hit goes to hit[16], and the return
-// value is the counter after the walk (F without VKF_MEDIUM: nothing can draw, the state is not read and st47[3] comes back).
+// counter, st811: seed, pixel, sample): the stream is set up the way shade_hit sets it up, and the walk is trace_ray's stream form — a
+// ConstantMedium met on the way draws from the path's own stream, taken where it stands, which is what radiance_sample's walk does
+// inside a sample.  The vk_hit goes to hit[16], and the return value is the counter after the walk (F without VKF_MEDIUM: nothing
+// can draw, the state is not read and st47[3] comes back).
 template <uint32_t F, class Mem>
 VK_HD uint32_t trace_path(const DScene &S, const Mem &M, const DProvenance &P, const uint32_t ray[8], const uint32_t st47[4],
     const uint32_t st811[4], uint32_t hit[16]) {
@@ -1996,9 +1868,8 @@ VK_HD uint32_t trace_path(const DScene &S, const Mem &M, const DProvenance &P, c
     } else {
         g.key = 0u; g.ctr = st47[3];
     }
-    trace_ray_on_stream<F, Mem>(L, S, M, P, v3(vk::bits_f32(ray[0]), vk::bits_f32(ray[1]), vk::bits_f32(ray[2])),
-                                v3(vk::bits_f32(ray[4]), vk::bits_f32(ray[5]), vk::bits_f32(ray[6])), vk::bits_f32(ray[7]), vk::bits_f32(ray[3]),
-                                g, H);
+    trace_ray<F, Mem, true>(L, S, M, P, v3(vk::bits_f32(ray[0]), vk::bits_f32(ray[1]), vk::bits_f32(ray[2])),
+                            v3(vk::bits_f32(ray[4]), vk::bits_f32(ray[5]), vk::bits_f32(ray[6])), vk::bits_f32(ray[7]), vk::bits_f32(ray[3]), 0u, H, &g);
     hit_words(H, hit);
     return (F & VKF_MEDIUM) ? L.rng.ctr : st47[3];
 }
