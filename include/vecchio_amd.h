@@ -1143,6 +1143,74 @@ int vk_adapt_resolve(vk_film *film, float *rgb_out);
 int vk_adapt_stderr(vk_film *film, float *out);
 int vk_adapt_tile_samples(vk_film *film, uint32_t *out, vk_adaptive_info *info);
 
+/* ---- reconstruction filters: a finished path batch splatted into a filtered frame (additive symbols of ABI 7) -----------------------
+ * replaces: nothing (the reference's frame is box-filtered: a sample of pixel (x, y) adds to pixel (x, y) only, and vk_render,
+ * vk_progress_* and vk_film_deposit keep doing that).  An accumulator holds, per pixel, four 64-bit two's-complement sums in 2^-26
+ * units — r, g, b and the filter weight, interleaved, width * height * 32 bytes — and one record of counters (8 KiB), on the scene's device
+ * (devices[0] of a multi-device scene).  All work is on the null stream there; no function takes a stream.  A batch goes in as it goes
+ * into a film: finished (nothing live), once per begin or emit — a flag of its own next to the film's, cleared where that one is
+ * cleared, so that one batch may go once into a film and once into an accumulator, in either order.
+ *
+ * The definition, operation by operation.  Everything is f32, unfused, in the order written.
+ *   1. Which results.  Every started id is a candidate.  One whose status is VK_SHADE_MISS, VK_SHADE_ENDED or VK_PATHS_CULLED and whose
+ *      position (2.) lies in the frame is PLACED; every other candidate counts in `skipped`.  A placed one whose acc has a non-finite
+ *      component counts in `dropped`; the rest count in `deposited`.
+ *   2. Position.  positions == NULL: the anchor is ix = state.pixel % width, iy = state.pixel / width; state.pixel >= width * height is
+ *      not placed; fx and fy are draws 0 and 1 (gen::<f32>(), vk_math.h gen_f32) of the stream of (state.seed, state.pixel,
+ *      state.sample) — for a film's camera path exactly the jitter its ray was generated with.  positions != NULL: host memory, 2 *
+ *      started floats (px, py) per id, frame coordinates in pixels, y up, pixel (i, j) covering [i, i + 1) x [j, j + 1): ix =
+ *      floor(px), fx = px - floor(px), the same in y; a non-finite coordinate, floor(px) < 0 or >= width, floor(py) < 0 or >= height
+ *      is not placed (-0.0 is pixel 0).  state.pixel is not read then.
+ *   3. Weights.  Per axis, for k = -2 .. 2: d = (fx - 0.5f) - (float)k, the sample's distance from the centre of pixel ix + k; it is in
+ *      support iff -radius <= d < radius (half-open: BOX at 0.5 gives each sample to exactly one pixel, fx = 0 included).  With a =
+ *      |d| and inv_r = 1.0f / radius:
+ *        BOX       w1 = 1
+ *        TENT      w1 = 1 - a * inv_r
+ *        MITCHELL  t = a * (2 * inv_r);  t < 1: w1 = ((p3 * t + p2) * t) * t + p0;  else w1 = ((q3 * t + q2) * t + q1) * t + q0, with
+ *                  p3 = ((12 - 9 * b) - 6 * c) / 6, p2 = ((-18 + 12 * b) + 6 * c) / 6, p0 = (6 - 2 * b) / 6, q3 = (-b - 6 * c) / 6,
+ *                  q2 = (6 * b + 30 * c) / 6, q1 = (-12 * b - 48 * c) / 6, q0 = (8 * b + 24 * c) / 6, computed once by the host.
+ *      The weight on pixel (ix + kx, iy + ky) is w = wx * wy.  Pairs in support on both axes whose pixel lies inside the frame count in
+ *      `contributions`; footprint pixels outside the frame get nothing (the weight sum makes up for it at the resolve).
+ *   4. Sums.  With F = ceil(2 * radius)^2 and clamp = min(1e10, 1.3e11 / (float)(samples_per_pixel * F)): a sample whose largest
+ *      |component| exceeds 31.999 has its components clamped to +-clamp first and counts in `clamped` if that largest exceeds the clamp
+ *      — the film's rule, and at radius 0.5 (F = 1) the film's clamp; F keeps samples_per_pixel * F samples a pixel from wrapping
+ *      the 64-bit sums.  Then per footprint pixel: trunc((w * a_c) * 2^26) is added to the sum of c = r, g, b and trunc(w * 2^26) to
+ *      the weight sum (|w| <= 1 for all three filters).
+ *   5. Resolve.  rgb_c = w_sum > 0 ? ((float)c_sum * 2^-26) / ((float)w_sum * 2^-26) : 0 — a pixel that received nothing, or negative
+ *      lobes only, is black —, in vk_render's f32 layout (y = 0 the bottom row).  The call waits; the sums stay.
+ * Contract: the sums and counters are a function of the set of deposited results alone — not of windows, batch sizes, order or the
+ * kernel's form —, equal tests/splat_ref.py's numpy restatement bit for bit, and with BOX at radius 0.5 the colour sums are
+ * vk_film_deposit's, the weight sum is 2^26 per deposited sample and the resolve is vk_film_resolve's at that count: a film's camera
+ * paths give vk_render's frame.
+ *
+ *   vk_splat_default_params: MITCHELL, radius 2, b = c = 1/3.
+ *   vk_splat_create: VK_ERR_BAD_ARG for a null pointer, width or height 0, width * height > 2^26, samples_per_pixel outside 1..2^26,
+ *     an unknown filter, a radius that is not finite or outside [0.5, 2], MITCHELL with b or c not finite or outside [0, 1].
+ *     VK_ERR_OOM leaves *out untouched.
+ *   vk_splat_deposit: VK_ERR_BAD_ARG, nothing enqueued or written: a null accumulator or batch, a batch of another scene, one never
+ *     begun, a regenerating one, one with live paths, one already deposited into an accumulator since its last vk_paths_begin /
+ *     vk_film_emit.
+ *   vk_splat_reset zeroes sums and counters.  vk_splat_get_info waits.  vk_splat_destroy(NULL) does nothing.                       */
+enum { VK_SPLAT_BOX = 0, VK_SPLAT_TENT = 1, VK_SPLAT_MITCHELL = 2 };
+typedef struct vk_splat vk_splat;        /* opaque */
+typedef struct vk_splat_params {         /* 16 bytes */
+    uint32_t filter;                     /* VK_SPLAT_* */
+    float radius;                        /* in pixels, 0.5 .. 2 */
+    float b, c;                          /* MITCHELL's; ignored otherwise */
+} vk_splat_params;
+typedef struct vk_splat_info {           /* 64 bytes */
+    uint32_t width, height, samples_per_pixel, filter;
+    uint64_t deposited, dropped, clamped, skipped, deposits, contributions;      /* deposits: accepted vk_splat_deposit calls */
+} vk_splat_info;
+int vk_splat_default_params(vk_splat_params *out);
+int vk_splat_create(vk_scene *scene, uint32_t width, uint32_t height, uint32_t samples_per_pixel, const vk_splat_params *sp,
+                    vk_splat **out);
+int vk_splat_deposit(vk_splat *s, vk_paths *batch, const float *positions);
+int vk_splat_resolve(vk_splat *s, float *rgb_out);
+int vk_splat_reset(vk_splat *s);
+int vk_splat_get_info(vk_splat *s, vk_splat_info *out);
+void vk_splat_destroy(vk_splat *s);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

@@ -152,6 +152,19 @@ int vk_debug_adapt_set_tiles(vk_film *film, const uint32_t *tile_n, const uint32
  * the film's current tile set: pixel_out[i] = y * width + x and sample_out[i] = samples_done + k of path first + i.  m <= 2^24.
  * VK_ERR_BAD_ARG for a null pointer, a film that is not enabled, n_samples == 0 or first + m beyond the run's paths.  In both libraries. */
 int vk_debug_adapt_sequence(vk_film *film, uint32_t n_samples, uint64_t first, uint32_t m, uint32_t *pixel_out, uint32_t *sample_out);
+
+/* an accumulator's raw sums: width * height * 4 two's-complement 64-bit values in 2^-26 units, [(y * width + x) * 4 + c], c = r, g, b,
+ * weight.  Waits.  VK_ERR_BAD_ARG for a null pointer.  Takes no stream.  In both libraries. */
+int vk_debug_splat_sums(vk_splat *s, int64_t *sums4);
+/* the form of splat_deposit_kernel (vk_splat.hip) from the accumulator's next vk_splat_deposit on: PLAIN = every (pixel, sum) a global
+ * atomic; TILED = through an LDS tile per workgroup; DEFAULT = the measured one (DESIGN.md "Reconstruction filters").  All give the
+ * same bytes.  VK_ERR_BAD_ARG for a null accumulator or another form.  In both libraries. */
+enum { VK_DEBUG_SPLAT_FORM_DEFAULT = 0, VK_DEBUG_SPLAT_FORM_PLAIN = 1, VK_DEBUG_SPLAT_FORM_TILED = 2 };
+int vk_debug_splat_form(vk_splat *s, uint32_t form);
+/* the device milliseconds of the accumulator's last vk_splat_deposit (ms[0]: the kernel, without the copy of positions) and
+ * vk_splat_resolve (ms[1]: the kernel without the copy to the host), between two events around each; 0 for one that has not run.
+ * Waits for those.  Takes no stream.  In both libraries. */
+int vk_debug_splat_last_ms(vk_splat *s, double ms[2]);
 #ifdef __cplusplus
 }
 #endif

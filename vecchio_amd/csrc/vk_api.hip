@@ -52,6 +52,7 @@
 #include "vk_linearize.h"
 #include "vk_kernels.h"
 #include "vk_adapt.h"        // the kernels of vk_adapt.hip: argument records and launchers
+#include "vk_splat.h"        // the kernels of vk_splat.hip: the filter, argument records and launchers
 
 namespace {
 
@@ -2496,6 +2497,7 @@ struct vk_paths {
     vk_shade_params sp{};                           // the last begin's
     bool begun = false;
     bool deposited = false;                         // vk_film_deposit has taken this batch (cleared by vk_paths_begin and vk_film_emit)
+    bool splatted = false;                          // vk_splat_deposit has taken this batch (cleared where `deposited` is)
     uint32_t cur = 0;                               // ids[cur] holds the live ids
     uint64_t started = 0, live = 0, retired[5] = {0, 0, 0, 0, 0};
     uint32_t bounces = 0;
@@ -2620,7 +2622,7 @@ int paths_take_counts(vk_paths *p, unsigned long long c[5]) {
 // a batch as a begin leaves it: `started` paths of which `live` are live, nothing retired, no bounce run, not regenerating.  Called behind
 // every check and every launch of a begin that can fail: a refused call leaves the batch as it was.
 void paths_reset(vk_paths *p, const vk_shade_params &sp, uint64_t started, uint64_t live) {
-    p->sp = sp; p->begun = true; p->deposited = false; p->cur = 0u; p->started = started; p->live = live; p->bounces = 0u;
+    p->sp = sp; p->begun = true; p->deposited = false; p->splatted = false; p->cur = 0u; p->started = started; p->live = live; p->bounces = 0u;
     for (uint64_t &r : p->retired) r = 0u;
     p->regen = false; p->regen_film = nullptr; p->regen_win = vk_film_window{}; p->regen_next = 0u; p->regen_total = 0u;
     p->regen_tiles = false; p->regen_first_sample = 0u; p->regen_n_samples = 0u;
@@ -3587,6 +3589,222 @@ int vk_debug_adapt_sequence(vk_film *film, uint32_t n_samples, uint64_t first, u
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(pixel_out, A.pixel_out, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(sample_out, A.sample_out, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- reconstruction filters (vk_splat_*): a frame's filtered fixed-point sums — r, g, b and the weight per pixel — on the scene's device
+// (devices[0] of a multi-device scene).  splat_deposit_kernel adds a finished batch, splat_resolve_kernel divides (vk_splat.hip); all on
+// the null stream, on buffers and events the handle owns.  Of the batch a deposit reads its results and sets its `splatted` flag; nothing
+// of the scene handle is read but its device.
+struct vk_splat {
+    vk_scene *scene = nullptr;                      // as handed to vk_splat_create
+    uint32_t width = 0, height = 0, spp = 0;
+    vk_splat_params sp{};
+    SplatFilter filter{};
+    float accum_clamp = 0.0f;
+    DeviceBuffer<unsigned long long> sums;          // [width * height * 4], two's complement
+    DeviceBuffer<unsigned long long> counters;      // deposited, dropped, clamped, skipped, contributions, in SPLAT_STRIPES stripes
+    DeviceBuffer<float> out;                        // the resolved frame on its way to the host (allocated by the first resolve)
+    DeviceBuffer<float> positions;                  // the caller's positions on their way to the device (grown by a deposit that has some)
+    size_t positions_cap = 0;                       // floats
+    Event ev[4];                                    // around the last deposit and resolve
+    bool timed[2] = {false, false};
+    uint64_t deposits = 0;
+    bool tiled = SPLAT_DEFAULT_TILED;               // the deposit's form (vk_debug_splat_form)
+};
+
+namespace {
+
+constexpr size_t SPLAT_COUNTER_BYTES = (size_t)SPLAT_STRIPES * SPLAT_STRIPE_WORDS * sizeof(unsigned long long);
+
+void splat_free(vk_splat *s) {
+    (void)hipSetDevice(first_part(s->scene)->device);
+    (void)hipStreamSynchronize(nullptr);              // (a deposit may still run)
+    (void)hipGetLastError();
+    delete s;
+}
+
+int splat_zero(vk_splat *s) {
+    HIP_TRY(hipMemsetAsync(s->sums, 0, (size_t)s->width * s->height * 4u * sizeof(unsigned long long), nullptr));
+    HIP_TRY(hipMemsetAsync(s->counters, 0, SPLAT_COUNTER_BYTES, nullptr));
+    s->deposits = 0u;
+    return VK_OK;
+}
+
+const char *splat_refusal(const vk_splat_params &sp) {
+    if (sp.filter != VK_SPLAT_BOX && sp.filter != VK_SPLAT_TENT && sp.filter != VK_SPLAT_MITCHELL) return "unknown filter";
+    if (!std::isfinite(sp.radius) || !(sp.radius >= 0.5f && sp.radius <= 2.0f)) return "radius must be finite and in [0.5, 2]";
+    if (sp.filter == VK_SPLAT_MITCHELL)
+        for (float v : {sp.b, sp.c})
+            if (!std::isfinite(v) || !(v >= 0.0f && v <= 1.0f)) return "b and c must be finite and in [0, 1]";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_splat_default_params(vk_splat_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    out->filter = VK_SPLAT_MITCHELL; out->radius = 2.0f; out->b = 1.0f / 3.0f; out->c = 1.0f / 3.0f;
+    return VK_OK;
+}
+
+int vk_splat_create(vk_scene *scene, uint32_t width, uint32_t height, uint32_t samples_per_pixel, const vk_splat_params *sp, vk_splat **out) {
+    if (!scene || !sp || !out) return fail(VK_ERR_BAD_ARG, "null argument (scene, params or out)");
+    if (width == 0u || height == 0u) return fail(VK_ERR_BAD_ARG, "width and height must be >= 1");
+    if ((uint64_t)width * height > FILM_MAX_PIXELS) return fail(VK_ERR_BAD_ARG, "width * height exceeds 2^26");
+    if (samples_per_pixel == 0u || samples_per_pixel > (1u << 26)) return fail(VK_ERR_BAD_ARG, "samples_per_pixel must be in 1..2^26");
+    if (const char *why = splat_refusal(*sp)) return fail(VK_ERR_BAD_ARG, why);
+    return guarded([&]() -> int {
+        std::unique_ptr<vk_splat, void (*)(vk_splat *)> s(new vk_splat(), splat_free);
+        s->scene = scene; s->width = width; s->height = height; s->spp = samples_per_pixel; s->sp = *sp;
+        if (sp->filter != VK_SPLAT_MITCHELL) { s->sp.b = 0.0f; s->sp.c = 0.0f; }
+        s->filter = splat_filter_for(sp->filter, sp->radius, s->sp.b, s->sp.c);
+        const uint32_t side = (uint32_t)std::ceil(2.0f * sp->radius);            // 1 .. 4
+        s->accum_clamp = accum_clamp_for(samples_per_pixel * side * side);
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        int r = VK_OK;
+        handle_alloc(r, s->sums, (size_t)width * height * 4u * sizeof(unsigned long long));
+        handle_alloc(r, s->counters, SPLAT_COUNTER_BYTES);
+        if (r != VK_OK) return r;
+        for (Event &e : s->ev) if ((r = e.create()) != VK_OK) return r;
+        if ((r = splat_zero(s.get())) != VK_OK) return r;
+        *out = s.release();
+        return VK_OK;
+    });
+}
+
+int vk_splat_deposit(vk_splat *s, vk_paths *batch, const float *positions) {
+    return guarded([&]() -> int {
+        if (!s || !batch) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or path batch)");
+        if (batch->scene != s->scene) return fail(VK_ERR_BAD_ARG, "the path batch belongs to another scene than the accumulator");
+        if (!batch->begun) return fail(VK_ERR_BAD_ARG, "vk_splat_deposit before vk_paths_begin or vk_film_emit");
+        if (batch->regen) return fail(VK_ERR_BAD_ARG, "vk_splat_deposit on a regenerating path batch (its results are not kept)");
+        if (batch->live != 0u) return fail(VK_ERR_BAD_ARG, "the path batch has live paths (step or cull them first)");
+        if (batch->splatted) return fail(VK_ERR_BAD_ARG, "the path batch has been deposited into an accumulator since its last begin or emit");
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        const uint64_t n = batch->started;
+        if (n != 0u && positions) {
+            const size_t floats = (size_t)n * 2u;
+            if (floats > s->positions_cap) {
+                DeviceBuffer<float> grown;
+                int rc = VK_OK;
+                handle_alloc(rc, grown, floats * sizeof(float));
+                if (rc != VK_OK) return rc;
+                s->positions = std::move(grown);
+                s->positions_cap = floats;
+            }
+            HIP_TRY(hipMemcpy(s->positions, positions, floats * sizeof(float), hipMemcpyHostToDevice));
+        }
+        HIP_TRY(hipEventRecord(s->ev[0], nullptr));
+        if (n != 0u) {
+            SplatDepositArgs A;
+            memset(&A, 0, sizeof(A));
+            A.result_state = reinterpret_cast<const uint4 *>(batch->result_state.get()); A.result_status = batch->result_status;
+            A.positions = positions ? reinterpret_cast<const float2 *>(s->positions.get()) : nullptr;
+            A.sums = s->sums; A.counters = s->counters;
+            A.P = s->filter;
+            A.n = (uint32_t)n; A.width = s->width; A.height = s->height;
+            A.accum_clamp = s->accum_clamp;
+            launch_splat_deposit(A, s->tiled);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(s->ev[1], nullptr));
+        s->timed[0] = true;
+        s->deposits++;
+        batch->splatted = true;
+        return VK_OK;
+    });
+}
+
+int vk_splat_resolve(vk_splat *s, float *rgb_out) {
+    return guarded([&]() -> int {
+        if (!s || !rgb_out) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or rgb_out)");
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        const size_t bytes = (size_t)s->width * s->height * 3u * sizeof(float);
+        if (!s->out) {
+            int rc = VK_OK;
+            handle_alloc(rc, s->out, bytes);
+            if (rc != VK_OK) return rc;
+        }
+        SplatResolveArgs A;
+        memset(&A, 0, sizeof(A));
+        A.sums = reinterpret_cast<const long long *>(s->sums.get()); A.out = s->out; A.n_pixels = s->width * s->height;
+        HIP_TRY(hipEventRecord(s->ev[2], nullptr));
+        launch_splat_resolve(A);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(s->ev[3], nullptr));
+        s->timed[1] = true;
+        HIP_TRY(hipMemcpy(rgb_out, s->out, bytes, hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+int vk_splat_reset(vk_splat *s) {
+    if (!s) return fail(VK_ERR_BAD_ARG, "null accumulator");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        return splat_zero(s);
+    });
+}
+
+int vk_splat_get_info(vk_splat *s, vk_splat_info *out) {
+    if (!s || !out) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        std::vector<unsigned long long> stripes((size_t)SPLAT_STRIPES * SPLAT_STRIPE_WORDS);
+        HIP_TRY(hipMemcpy(stripes.data(), s->counters, SPLAT_COUNTER_BYTES, hipMemcpyDeviceToHost));      // (waits for the null stream)
+        unsigned long long c[SPLAT_COUNTERS] = {0ull, 0ull, 0ull, 0ull, 0ull};
+        for (uint32_t k = 0; k < SPLAT_STRIPES; k++)
+            for (uint32_t j = 0; j < SPLAT_COUNTERS; j++) c[j] += stripes[(size_t)k * SPLAT_STRIPE_WORDS + j];
+        memset(out, 0, sizeof(*out));
+        out->width = s->width; out->height = s->height; out->samples_per_pixel = s->spp; out->filter = s->sp.filter;
+        out->deposited = c[0]; out->dropped = c[1]; out->clamped = c[2]; out->skipped = c[3];
+        out->deposits = s->deposits; out->contributions = c[4];
+        return VK_OK;
+    });
+}
+
+void vk_splat_destroy(vk_splat *s) {
+    if (s) splat_free(s);
+}
+
+// test hook (vecchio_amd_debug.h): the raw sums
+int vk_debug_splat_sums(vk_splat *s, int64_t *sums4) {
+    if (!s || !sums4) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or sums4)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        HIP_TRY(hipMemcpy(sums4, s->sums, (size_t)s->width * s->height * 4u * sizeof(int64_t), hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): the deposit's form from the next vk_splat_deposit on
+int vk_debug_splat_form(vk_splat *s, uint32_t form) {
+    if (!s) return fail(VK_ERR_BAD_ARG, "null accumulator");
+    if (form > (uint32_t)VK_DEBUG_SPLAT_FORM_TILED) return fail(VK_ERR_BAD_ARG, "unknown deposit form");
+    s->tiled = form == (uint32_t)VK_DEBUG_SPLAT_FORM_DEFAULT ? SPLAT_DEFAULT_TILED : form == (uint32_t)VK_DEBUG_SPLAT_FORM_TILED;
+    return VK_OK;
+}
+
+// test hook (vecchio_amd_debug.h): the last deposit and resolve, from the events recorded around each; 0 for one not yet run
+int vk_debug_splat_last_ms(vk_splat *s, double ms[2]) {
+    if (!s || !ms) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or ms)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        double got[2] = {0.0, 0.0};
+        for (int k = 0; k < 2; k++) {
+            if (!s->timed[k]) continue;
+            HIP_TRY(hipEventSynchronize(s->ev[2 * k + 1]));
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, s->ev[2 * k], s->ev[2 * k + 1]));
+            got[k] = (double)t;
+        }
+        for (int k = 0; k < 2; k++) ms[k] = got[k];
         return VK_OK;
     });
 }

@@ -1,5 +1,5 @@
-// vk_emit.h — what the kernels of vk_kernels.h (vk_api.hip) and those of vk_adapt.hip share: the tile size, the fixed-point scale of the
-// pixel sums with its conversions, and the start of a camera path of a film's window.  Device code, moved here from vk_kernels.h as it
+// vk_emit.h — what the kernels of vk_kernels.h (vk_api.hip), of vk_adapt.hip and of vk_splat.hip share: the tile size, the fixed-point
+// scale of the pixel sums with its conversions, and the start of a camera path of a film's window.  Device code, moved here from vk_kernels.h as it
 // stood (vk_kernels.h defines non-template __global__ functions: one translation unit only may include it).  Everything is internal to
 // the translation unit that includes it.
 #ifndef VK_EMIT_H
@@ -18,6 +18,10 @@ constexpr int TILE = 8;   // 8x8 pixels = one wave
 
 // the scale of the pixel sums (see vk_kernels.h "Pixel sums are ORDER-INDEPENDENT")
 constexpr float ACCUM_SCALE = 67108864.0f;          // 2^26
+// Components below 32 in magnitude — every sample of a scene without bright emitters, and nearly every one otherwise — fit 31 bits
+// at 2^-26: ONE v_cvt_i32_f32 (truncating, like the 64-bit cast) and a sign extension, against ~17 instructions for the float ->
+// 64-bit integer conversion the compiler has to expand.
+constexpr float ACCUM_SMALL = 31.999f;
 __device__ __forceinline__ long long to_fixed_small(float v) { return (long long)(int)(v * ACCUM_SCALE); }
 __device__ __forceinline__ long long to_fixed(float v, float clampv) {
     v = fminf(fmaxf(v, -clampv), clampv);

@@ -189,10 +189,7 @@ template <uint32_t F> constexpr uint32_t wave_block_floats() { return 64u * (uin
 constexpr float ACCUM_CLAMP = 1.0e10f;
 constexpr float ACCUM_RANGE = 1.3e11f;
 inline float accum_clamp_for(uint32_t spp) { float c = ACCUM_RANGE / (float)spp; return c < ACCUM_CLAMP ? c : ACCUM_CLAMP; }     // (host)
-// Components below 32 in magnitude — every sample of a scene without bright emitters, and nearly every one otherwise — fit 31 bits
-// at 2^-26: ONE v_cvt_i32_f32 (truncating, like the 64-bit cast) and a sign extension, against ~17 instructions for the float ->
-// 64-bit integer conversion the compiler has to expand.
-constexpr float ACCUM_SMALL = 31.999f;
+// (ACCUM_SMALL, the bound of to_fixed_small's operand: vk_emit.h)
 
 template <uint32_t F>
 __device__ __forceinline__ void cold_store_path(float *c, uint32_t lane, const Lane &L) {

@@ -239,6 +239,22 @@ class FilmInfo(C.Structure):
 VK_DEBUG_FILM_DEPOSIT_PLAIN, VK_DEBUG_FILM_DEPOSIT_RUNS = 0, 1
 
 
+class SplatParams(C.Structure):
+    """vk_splat_params (vk_splat_create)"""
+    _fields_ = [("filter", C.c_uint32), ("radius", C.c_float), ("b", C.c_float), ("c", C.c_float)]
+
+
+class SplatInfo(C.Structure):
+    """vk_splat_info (vk_splat_get_info)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("samples_per_pixel", C.c_uint32), ("filter", C.c_uint32),
+                ("deposited", C.c_uint64), ("dropped", C.c_uint64), ("clamped", C.c_uint64), ("skipped", C.c_uint64),
+                ("deposits", C.c_uint64), ("contributions", C.c_uint64)]
+
+
+VK_SPLAT_BOX, VK_SPLAT_TENT, VK_SPLAT_MITCHELL = 0, 1, 2
+VK_DEBUG_SPLAT_FORM_DEFAULT, VK_DEBUG_SPLAT_FORM_PLAIN, VK_DEBUG_SPLAT_FORM_TILED = 0, 1, 2
+
+
 class RegenInfo(C.Structure):
     """vk_regen_info (vk_regen_step)"""
     _fields_ = [("traced", C.c_uint64), ("live", C.c_uint64), ("remaining", C.c_uint64), ("emitted", C.c_uint64), ("missed", C.c_uint64),
@@ -359,6 +375,8 @@ DEVICE_SYMBOLS = [
     "vk_film_create", "vk_film_emit", "vk_film_deposit", "vk_film_resolve", "vk_film_reset", "vk_film_get_info", "vk_film_destroy",
     "vk_regen_begin", "vk_regen_step", "vk_regen_cull",
     "vk_adapt_enable", "vk_adapt_begin", "vk_adapt_close", "vk_adapt_resolve", "vk_adapt_stderr", "vk_adapt_tile_samples",
+    "vk_splat_default_params", "vk_splat_create", "vk_splat_deposit", "vk_splat_resolve", "vk_splat_reset", "vk_splat_get_info",
+    "vk_splat_destroy",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -502,6 +520,20 @@ def _bind(lib):
     lib.vk_adapt_stderr.argtypes = [C.c_void_p, C.c_void_p]
     lib.vk_adapt_tile_samples.restype = C.c_int
     lib.vk_adapt_tile_samples.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AdaptiveInfo)]
+    lib.vk_splat_default_params.restype = C.c_int
+    lib.vk_splat_default_params.argtypes = [C.POINTER(SplatParams)]
+    lib.vk_splat_create.restype = C.c_int
+    lib.vk_splat_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(SplatParams), C.POINTER(C.c_void_p)]
+    lib.vk_splat_deposit.restype = C.c_int
+    lib.vk_splat_deposit.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_splat_resolve.restype = C.c_int
+    lib.vk_splat_resolve.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_splat_reset.restype = C.c_int
+    lib.vk_splat_reset.argtypes = [C.c_void_p]
+    lib.vk_splat_get_info.restype = C.c_int
+    lib.vk_splat_get_info.argtypes = [C.c_void_p, C.POINTER(SplatInfo)]
+    lib.vk_splat_destroy.restype = None
+    lib.vk_splat_destroy.argtypes = [C.c_void_p]
     lib.vk_probe_eval.restype = C.c_int
     lib.vk_probe_eval.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.vk_trace_occluded_device.restype = C.c_int
@@ -569,6 +601,12 @@ def _bind(lib):
     lib.vk_debug_adapt_set_tiles.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vk_debug_adapt_sequence.restype = C.c_int
     lib.vk_debug_adapt_sequence.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.vk_debug_splat_sums.restype = C.c_int
+    lib.vk_debug_splat_sums.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_debug_splat_form.restype = C.c_int
+    lib.vk_debug_splat_form.argtypes = [C.c_void_p, C.c_uint32]
+    lib.vk_debug_splat_last_ms.restype = C.c_int
+    lib.vk_debug_splat_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 2)]
     lib.vk_debug_trace_occluded_device.restype = C.c_int
     lib.vk_debug_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_uint32, C.c_uint32]

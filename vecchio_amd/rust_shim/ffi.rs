@@ -146,6 +146,16 @@ pub struct vk_film_info { pub width: u32, pub height: u32, pub samples_per_pixel
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_adapt_info { pub samples_done: u32, pub steps: u32, pub tiles_total: u32, pub tiles_active: u32, pub pixels_active: u64, pub samples_rendered: u64 }
 
+// reconstruction filters: an accumulator's filter, and its counters
+pub const VK_SPLAT_BOX: u32 = 0;
+pub const VK_SPLAT_TENT: u32 = 1;
+pub const VK_SPLAT_MITCHELL: u32 = 2;
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_splat_params { pub filter: u32, pub radius: f32, pub b: f32, pub c: f32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_splat_info { pub width: u32, pub height: u32, pub samples_per_pixel: u32, pub filter: u32, pub deposited: u64, pub dropped: u64, pub clamped: u64, pub skipped: u64, pub deposits: u64, pub contributions: u64 }
+
 // regeneration: what one vk_regen_step did
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_regen_info { pub traced: u64, pub live: u64, pub remaining: u64, pub emitted: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
@@ -161,6 +171,7 @@ pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, 
 #[repr(C)] pub struct vk_temporal { _private: [u8; 0] }
 #[repr(C)] pub struct vk_paths { _private: [u8; 0] }
 #[repr(C)] pub struct vk_film { _private: [u8; 0] }
+#[repr(C)] pub struct vk_splat { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -264,6 +275,15 @@ extern "C" {
     pub fn vk_adapt_resolve(film: *mut vk_film, rgb_out: *mut f32) -> c_int;
     pub fn vk_adapt_stderr(film: *mut vk_film, out: *mut f32) -> c_int;
     pub fn vk_adapt_tile_samples(film: *mut vk_film, out: *mut u32, info: *mut vk_adaptive_info) -> c_int;
+    // reconstruction filters (additive symbols of ABI 7): a finished batch splatted into a filtered frame (box, tent, Mitchell-Netravali);
+    // positions: null (the state's pixel and the sample's own jitter) or 2 * started frame coordinates
+    pub fn vk_splat_default_params(out: *mut vk_splat_params) -> c_int;
+    pub fn vk_splat_create(scene: *mut vk_scene, width: u32, height: u32, samples_per_pixel: u32, sp: *const vk_splat_params, out: *mut *mut vk_splat) -> c_int;
+    pub fn vk_splat_deposit(s: *mut vk_splat, batch: *mut vk_paths, positions: *const f32) -> c_int;
+    pub fn vk_splat_resolve(s: *mut vk_splat, rgb_out: *mut f32) -> c_int;
+    pub fn vk_splat_reset(s: *mut vk_splat) -> c_int;
+    pub fn vk_splat_get_info(s: *mut vk_splat, out: *mut vk_splat_info) -> c_int;
+    pub fn vk_splat_destroy(s: *mut vk_splat);
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

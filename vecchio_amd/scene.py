@@ -589,6 +589,12 @@ class DeviceScene:
         scene."""
         return Film(self, cam, params)
 
+    def splat(self, width, height, spp, filter=ffi.VK_SPLAT_MITCHELL, radius=2.0, b=1.0 / 3.0, c=1.0 / 3.0):
+        """A filtered accumulator on this scene (vk_splat_create): per pixel the sums of r, g, b and of the reconstruction filter's
+        weight, into which finished path batches are splatted on the device.  filter: ffi.VK_SPLAT_BOX, _TENT or _MITCHELL (b, c); radius
+        in pixels, 0.5 .. 2.  Use as a context manager, or close() it before the scene."""
+        return Splat(self, width, height, spp, ffi.SplatParams(filter, radius, b, c))
+
     def debug_compact_paths(self, items, ids, n_ids, canary=0xA5, roulette=None):
         """The compaction of a path batch's bounce on host arrays (vk_debug_compact_paths, a test hook): items a SHADED_DTYPE array, ids
         their uint32 ids (each below n_ids).  Every output is prefilled with the byte `canary`.  Returns (rays, states, ids_out — n
@@ -954,8 +960,18 @@ class Film:
         resolve()."""
         if roulette is not Film._KEEP:
             batch.set_roulette(*(roulette or (None,)))
+        for win in self.windows(int(batch.info().capacity)):
+            self.emit(batch, *win)
+            while batch.step(1).live:
+                if cull is not None:
+                    cull(batch)
+            self.deposit(batch)
+        return self.resolve()
+
+    def windows(self, capacity):
+        """render()'s walk of the frame for a batch of `capacity` paths: (x0, y0, w, h, first_sample, n_samples) per window"""
         p = self.params
-        cap = int(batch.info().capacity)
+        cap = int(capacity)
         spp = p.samples_per_pixel
         ns = min(spp, cap)
         w = max(1, min(p.width, cap // ns))
@@ -963,12 +979,7 @@ class Film:
         for s0 in range(0, spp, ns):
             for y0 in range(0, p.height, h):
                 for x0 in range(0, p.width, w):
-                    self.emit(batch, x0, y0, min(w, p.width - x0), min(h, p.height - y0), s0, min(ns, spp - s0))
-                    while batch.step(1).live:
-                        if cull is not None:
-                            cull(batch)
-                    self.deposit(batch)
-        return self.resolve()
+                    yield x0, y0, min(w, p.width - x0), min(h, p.height - y0), s0, min(ns, spp - s0)
 
     def regen_begin(self, batch, x0, y0, w, h, first_sample=0, n_samples=1):
         """Put `batch` into its regenerating state for the window (vk_regen_begin): its w * h * n_samples paths, numbered as emit() numbers
@@ -1134,6 +1145,93 @@ class Film:
     def close(self):
         if self._h:
             self._lib.vk_film_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Splat:
+    """vk_splat handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed): deposit() finished path
+    batches, each sample spread over the pixels its filter reaches; resolve() divides the colour sums by the weight sums.  With
+    ffi.VK_SPLAT_BOX at radius 0.5 the frame of a film's camera paths is render()'s, bit for bit."""
+
+    def __init__(self, scene, width, height, spp, params):
+        self._lib = scene._lib
+        self._scene = scene
+        self.width, self.height, self.spp = int(width), int(height), int(spp)
+        self.params = ffi.SplatParams.from_buffer_copy(params)
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_splat_create(scene._h, width, height, spp, C.byref(self.params), C.byref(h)))
+        self._h = h
+
+    def deposit(self, batch, positions=None):
+        """Splat the retired paths of `batch`, which has nothing live (vk_splat_deposit).  positions: None — each sample at its state's
+        pixel, offset by the jitter its stream starts with (a film's camera paths) — or float32 (started, 2) frame coordinates."""
+        ptr = None
+        if positions is not None:
+            positions = np.ascontiguousarray(positions, np.float32)
+            assert positions.size == 2 * int(batch.info().started)
+            ptr = positions.ctypes.data_as(C.c_void_p)
+        check(self._lib, self._lib.vk_splat_deposit(self._h, batch._h, ptr))
+
+    def resolve(self, out=None):
+        """The filtered frame (vk_splat_resolve): float32 (height, width, 3), y = 0 the bottom row; a pixel whose weights sum to zero or
+        less is black.  out: an array of that shape to write into."""
+        if out is None:
+            out = np.zeros((self.height, self.width, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == self.width * self.height * 3
+        check(self._lib, self._lib.vk_splat_resolve(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def reset(self):
+        """Zero the sums and the counters (vk_splat_reset)."""
+        check(self._lib, self._lib.vk_splat_reset(self._h))
+
+    def info(self):
+        inf = ffi.SplatInfo()
+        check(self._lib, self._lib.vk_splat_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def render(self, film, batch, cull=None):
+        """The whole frame of `film` through `batch`, filtered: Film.render()'s windows, each emitted, stepped to its end and deposited
+        here instead of into the film.  Returns resolve()."""
+        for win in film.windows(int(batch.info().capacity)):
+            film.emit(batch, *win)
+            while batch.step(1).live:
+                if cull is not None:
+                    cull(batch)
+            self.deposit(batch)
+        return self.resolve()
+
+    def debug_sums(self):
+        """The raw sums (vk_debug_splat_sums, a test hook): int64 (height, width, 4) in 2^-26 units — r, g, b, weight"""
+        out = np.zeros((self.height, self.width, 4), np.int64)
+        check(self._lib, self._lib.vk_debug_splat_sums(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def debug_form(self, form):
+        """ffi.VK_DEBUG_SPLAT_FORM_DEFAULT, _PLAIN or _TILED from the next deposit() on (vk_debug_splat_form, a test hook)"""
+        check(self._lib, self._lib.vk_debug_splat_form(self._h, form))
+
+    def last_ms(self):
+        """(deposit, resolve) device milliseconds of the last call of each (vk_debug_splat_last_ms, a test hook)"""
+        ms = (C.c_double * 2)()
+        check(self._lib, self._lib.vk_debug_splat_last_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
+    def close(self):
+        if self._h:
+            self._lib.vk_splat_destroy(self._h)
             self._h = None
 
     def __enter__(self):
