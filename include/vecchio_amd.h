@@ -1341,6 +1341,54 @@ int vk_temporal_reset(vk_temporal *t);            /* forget the history; the nex
 int vk_temporal_get_info(vk_temporal *t, vk_temporal_info *out);   /* waits for the last frame */
 void vk_temporal_destroy(vk_temporal *t);          /* NULL: nothing; destroy before its scene */
 
+/* ---- ID mattes: per-pixel object and material coverage of primary rays (additive symbols of ABI 7) ---------------------------------
+ * replaces: nothing.  Next to vk_render_aov's and vk_render_guides' buffers, the third thing a compositor takes: WHICH object, or which
+ * material, each pixel shows, and with how much of its area (an "ID matte" or Cryptomatte AOV: per-object masks, selection outlines,
+ * picking, per-object statistics).  Everything here is an integer: every result is exact and no sample is ever dropped.
+ *   Samples.  first_sample .. first_sample + spp - 1, spp = params->samples_per_pixel.  Sample s of pixel (x, y) is exactly
+ *     vk_render_aov's: the stream (seed, y * width + x, s), the camera's draws first, the walk with tmin 0.001 and tmax inf on the tree
+ *     view vk_render_aov walks (the tree as handed over; the rebuilt tree under VK_SCENE_FAST_ACCEL), a ConstantMedium's draws
+ *     continuing that stream.
+ *   The id of a sample.  VK_MATTE_OBJECT: vk_hit.object as vk_trace_rays names it — VK_MAKE_REF(kind, index) of the description record
+ *     whose own hit() produced the winner, without the flip bit; a Boxy reports its face's Rect, a medium its VK_KIND_MEDIUM record.
+ *     VK_MATTE_MATERIAL: the hit record's material index; for a medium its phase function's material.  A miss is VK_MATTE_BACKGROUND
+ *     under either kind: an id like any other, which takes a slot.
+ *   The table of a pixel, exact and in a fixed order: `ranks` slots (1..8), empty at first.  Samples are taken in increasing order.  A
+ *     sample whose id is in a slot adds 1 to that slot; otherwise, if a slot is free, it takes it with count 1; otherwise it adds 1 to
+ *     the pixel's overflow (first come, no eviction).  At the end the used slots are sorted by count descending, ties by id ascending;
+ *     an unused slot is written as (id 0, count 0).  ids[pix * ranks + r], counts[pix * ranks + r], overflow[pix], pix = y * width + x,
+ *     y = 0 the bottom row.  overflow may be NULL; ids and counts may not.  Pixels outside the call's tile partition are left
+ *     untouched.  One value per (scene, camera, seed, window, kind, ranks), whatever the launch shape; in every pixel
+ *     sum(counts) + overflow == spp.
+ *   vk_matte_merge (host code, no device) folds table b into table a, pixel by pixel: b's used slots in b's order, the same rule for
+ *     each (found: add its count; a free slot: take it; else overflow += count), then overflow += overflow_b, and the slots are sorted
+ *     again.  The three overflow pointers of a call are all given or all NULL.  A frame's windows merged in any order equal the one
+ *     call over their union wherever that call's overflow is 0, and the merged overflow is 0 exactly there.
+ *   vk_matte_mask (host code): mask_out[pix] = (float)(sum of the counts of the slots whose id is in want[0 .. n_want)) /
+ *     (float)n_samples.  A set of ids, because one box is six face ids.
+ *   Arguments: vk_render's checks, in the same words; output_format, max_depth, integrator and the background are not read.
+ *     VK_ERR_BAD_ARG with nothing enqueued and every output untouched for a null mp, ids or counts, an unknown kind, ranks outside 1..8,
+ *     flags != 0, first_sample + spp > 2^32 - 1.  vk_matte_merge and vk_matte_mask refuse null arrays with n_pixels > 0, ranks outside
+ *     1..8, n_samples == 0, a null want with n_want > 0.
+ *   Scene state: vk_render_aov's rules.  The call is the scene's one render in flight and runs on devices[0] of a multi-device scene;
+ *     it touches nothing of vk_render's last frame, nor the launch log, any vk_progress or vk_temporal handle, or vk_render_aov's own
+ *     results and times.  It uploads the tables that map device primitives back to the description on first use, as the first ray
+ *     query does.  stats_out: samples = partition pixels x spp, kernel_ms, kernel_launches.
+ *   What this is not.  Ids are not followed through mirrors and glass: a glass sphere is its own id, whatever is seen in it
+ *     (vk_render_guides does not keep the name of the hit it reports).                                                             */
+enum { VK_MATTE_OBJECT = 0, VK_MATTE_MATERIAL = 1 };
+#define VK_MATTE_BACKGROUND 0xFFFFFFFFu
+#define VK_MATTE_MAX_RANKS 8u
+typedef struct vk_matte_params { uint32_t kind, ranks, flags, _pad; } vk_matte_params;   /* 16 bytes */
+/* VK_MATTE_OBJECT, 6 ranks, flags 0; touches no device */
+int vk_matte_default_params(vk_matte_params *out);
+int vk_render_mattes(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
+                     const vk_matte_params *mp, uint32_t *ids, uint32_t *counts, uint32_t *overflow, vk_stats *stats_out);
+int vk_matte_merge(uint32_t ranks, uint64_t n_pixels, uint32_t *ids, uint32_t *counts, uint32_t *overflow,
+                   const uint32_t *ids_b, const uint32_t *counts_b, const uint32_t *overflow_b);
+int vk_matte_mask(uint32_t ranks, uint64_t n_pixels, const uint32_t *ids, const uint32_t *counts, uint32_t n_samples,
+                  const uint32_t *want, uint32_t n_want, float *mask_out);
+
 /* test/diagnostic entry points (vk_debug_*) are declared in vecchio_amd_debug.h */
 
 #ifdef __cplusplus

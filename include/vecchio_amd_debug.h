@@ -165,6 +165,12 @@ int vk_debug_splat_form(vk_splat *s, uint32_t form);
  * vk_splat_resolve (ms[1]: the kernel without the copy to the host), between two events around each; 0 for one that has not run.
  * Waits for those.  Takes no stream.  In both libraries. */
 int vk_debug_splat_last_ms(vk_splat *s, double ms[2]);
+
+/* the id of every sample vk_render_mattes would count, by the same per-lane code on the same lanes: ids_out[(y * width + x) * spp + k] is
+ * the id of sample first_sample + k under `kind` (VK_MATTE_OBJECT or VK_MATTE_MATERIAL), spp = params->samples_per_pixel; pixels outside
+ * the call's tile partition are left untouched.  vk_render_mattes' checks.  Waits.  In both libraries. */
+int vk_debug_matte_samples(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample,
+                           uint32_t kind, uint32_t *ids_out);
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,7 @@
 #include "vk_kernels.h"
 #include "vk_adapt.h"        // the kernels of vk_adapt.hip: argument records and launchers
 #include "vk_splat.h"        // the kernels of vk_splat.hip: the filter, argument records and launchers
+#include "vk_matte.h"        // the kernels of vk_matte.hip: the table of a pixel, the argument record and launchers
 
 namespace {
 
@@ -290,6 +291,13 @@ struct vk_scene {
         Event ev0, ev1;
         DeviceBuffer<float> buf;
     } aov;
+
+    // ---- vk_render_mattes: its own events and staging buffer (ids, counts, overflow side by side), so that nothing of vk_render's last
+    // frame or of vk_render_aov's results and times is touched
+    struct Matte {
+        Event ev0, ev1;
+        DeviceBuffer<uint8_t> buf;
+    } matte;
 
     // ---- vk_trace_rays: the provenance tables (uploaded by the scene's first ray query), the staging buffer of the host variant (rays,
     // then hits) and its events
@@ -2097,6 +2105,166 @@ int vk_trace_rays_device(vk_scene *scene, const vk_trace_params *params, const v
         if ((rc = enqueue_trace(q, params, params->first_index, d_rays, n_rays, d_hits, reinterpret_cast<hipStream_t>(hip_stream))) != VK_OK)
             return rc;
         if (stats_out) { stats_out->samples = n_rays; stats_out->kernel_launches = 1u; }
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- ID mattes (vk_render_mattes): one launch of matte_kernel (vk_matte.hip) on the scene's device (devices[0] of a multi-device scene),
+// on events and a staging buffer of the call's own; vk_matte_merge and vk_matte_mask are host code on the table's own insert and sort
+// (vk_matte.h).  The provenance tables are the ray queries' (ensure_provenance).
+namespace {
+
+int check_matte_table(uint32_t ranks) {
+    if (ranks < 1u || ranks > VK_MATTE_MAX_RANKS) return fail(VK_ERR_BAD_ARG, "matte ranks must be in 1..8");
+    return VK_OK;
+}
+
+// vk_render_mattes' own checks, made first (they need no scene), then vk_render's; ids may be the hook's only array (counts_needed false)
+int check_matte_args(vk_scene *scene, const vk_camera *cam, const vk_render_params *p, uint32_t first_sample, uint32_t kind,
+    const void *ids, const void *counts, bool counts_needed) {
+    if (!ids || (counts_needed && !counts)) return fail(VK_ERR_BAD_ARG, "null matte ids or counts");
+    if (kind > (uint32_t)VK_MATTE_MATERIAL) return fail(VK_ERR_BAD_ARG, "unknown matte kind");
+    int rc = check_call_args(scene, cam, p);
+    if (rc != VK_OK) return rc;
+    if ((uint64_t)first_sample + p->samples_per_pixel > 0xFFFFFFFFull) return fail(VK_ERR_BAD_ARG,
+        "first_sample + samples_per_pixel exceeds 2^32 - 1");
+    return VK_OK;
+}
+
+// the kernels' arguments without their arrays; the provenance tables are on the device afterwards
+int matte_args(vk_scene *q, const vk_camera *cam, const vk_render_params *p, uint32_t first_sample, uint32_t kind, uint32_t ranks,
+    const TileGeom &g, MatteArgs *A) {
+    memset(A, 0, sizeof(*A));
+    int rc = query_view(q, "the matte walk", &A->S);
+    if (rc != VK_OK) return rc;
+    if ((rc = ensure_provenance(q)) != VK_OK) return rc;
+    A->P = q->rays.prov;
+    A->C.cam = *cam;
+    A->C.width = p->width; A->C.height = p->height; A->C.spp = p->samples_per_pixel; A->C.seed = p->seed;
+    A->kind = kind; A->ranks = ranks;
+    A->first_sample = first_sample; A->tiles_x = g.tiles_x; A->tile_rank = g.rank; A->tile_world = g.world; A->n_local = g.n_local;
+    return VK_OK;
+}
+
+size_t round16(size_t bytes) { return (bytes + 15u) & ~(size_t)15u; }
+
+// folds (id, c) pairs and overflow of table b's pixel into a's, in b's order, and sorts again (vk_matte_merge; vk_matte.h's rule)
+void matte_merge_pixel(uint32_t ranks, uint32_t *ids, uint32_t *counts, uint32_t *overflow, const uint32_t *ids_b, const uint32_t *counts_b,
+    const uint32_t *overflow_b) {
+    MatteTable T;
+    matte_clear(T);
+    for (uint32_t r = 0; r < ranks && counts[r] != 0u; r++) { T.id[r] = ids[r]; T.cnt[r] = counts[r]; T.used = r + 1u; }
+    for (uint32_t r = 0; r < ranks && counts_b[r] != 0u; r++) matte_insert(T, ranks, ids_b[r], counts_b[r]);
+    matte_sort(T);
+    for (uint32_t r = 0; r < ranks; r++) { ids[r] = T.id[r]; counts[r] = T.cnt[r]; }
+    if (overflow) *overflow += T.overflow + *overflow_b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_matte_default_params(vk_matte_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null matte parameters");
+    out->kind = VK_MATTE_OBJECT; out->ranks = 6u; out->flags = 0u; out->_pad = 0u;
+    return VK_OK;
+}
+
+int vk_render_mattes(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample, const vk_matte_params *mp,
+    uint32_t *ids, uint32_t *counts, uint32_t *overflow, vk_stats *stats_out) {
+    return guarded([&]() -> int {
+        if (!mp) return fail(VK_ERR_BAD_ARG, "null matte parameters");
+        int rc = check_matte_table(mp->ranks);
+        if (rc != VK_OK) return rc;
+        if (mp->flags != 0u) return fail(VK_ERR_BAD_ARG, "matte flags must be 0");
+        if ((rc = check_matte_args(scene, cam, params, first_sample, mp->kind, ids, counts, true)) != VK_OK) return rc;
+        const auto t0 = std::chrono::steady_clock::now();
+        vk_scene *q = first_part(scene);
+        HIP_TRY(hipSetDevice(q->device));
+        const TileGeom g(params);
+        MatteArgs A;
+        if ((rc = matte_args(q, cam, params, first_sample, mp->kind, mp->ranks, g, &A)) != VK_OK) return rc;
+        // ids, counts and overflow side by side in the call's own staging buffer, each slice 16-byte aligned
+        const size_t n_pixels = (size_t)params->width * params->height;
+        const size_t slots = n_pixels * mp->ranks * sizeof(uint32_t), per_pixel = n_pixels * sizeof(uint32_t);
+        if ((rc = q->matte.buf.ensure(2u * round16(slots) + (overflow ? per_pixel : 0u))) != VK_OK) return rc;
+        A.ids = reinterpret_cast<uint32_t *>(q->matte.buf.get());
+        A.counts = reinterpret_cast<uint32_t *>(q->matte.buf.get() + round16(slots));
+        A.overflow = overflow ? reinterpret_cast<uint32_t *>(q->matte.buf.get() + 2u * round16(slots)) : nullptr;
+        // a partition: the caller's pixels outside it must come back untouched
+        if (g.world > 1u) {
+            HIP_TRY(hipMemcpy(A.ids, ids, slots, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(A.counts, counts, slots, hipMemcpyHostToDevice));
+            if (overflow) HIP_TRY(hipMemcpy(A.overflow, overflow, per_pixel, hipMemcpyHostToDevice));
+        }
+        if ((rc = q->matte.ev0.create()) != VK_OK || (rc = q->matte.ev1.create()) != VK_OK) return rc;
+        HIP_TRY(hipEventRecord(q->matte.ev0, nullptr));
+        if (g.n_local != 0u) {
+            launch_matte(q->host->features, A);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(q->matte.ev1, nullptr));
+        HIP_TRY(hipMemcpy(ids, A.ids, slots, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(counts, A.counts, slots, hipMemcpyDeviceToHost));
+        if (overflow) HIP_TRY(hipMemcpy(overflow, A.overflow, per_pixel, hipMemcpyDeviceToHost));
+        if (stats_out) aov_stats(params, stats_out);
+        return end_timed_call(q->matte.ev0, q->matte.ev1, t0, stats_out);
+    });
+}
+
+int vk_matte_merge(uint32_t ranks, uint64_t n_pixels, uint32_t *ids, uint32_t *counts, uint32_t *overflow, const uint32_t *ids_b,
+    const uint32_t *counts_b, const uint32_t *overflow_b) {
+    int rc = check_matte_table(ranks);
+    if (rc != VK_OK) return rc;
+    if ((overflow != nullptr) != (overflow_b != nullptr)) return fail(VK_ERR_BAD_ARG, "matte overflow arrays: both or neither");
+    if (n_pixels > 0u && (!ids || !counts || !ids_b || !counts_b)) return fail(VK_ERR_BAD_ARG, "null matte table");
+    for (uint64_t i = 0; i < n_pixels; i++)
+        matte_merge_pixel(ranks, ids + i * ranks, counts + i * ranks, overflow ? overflow + i : nullptr, ids_b + i * ranks,
+                          counts_b + i * ranks, overflow_b ? overflow_b + i : nullptr);
+    return VK_OK;
+}
+
+int vk_matte_mask(uint32_t ranks, uint64_t n_pixels, const uint32_t *ids, const uint32_t *counts, uint32_t n_samples, const uint32_t *want,
+    uint32_t n_want, float *mask_out) {
+    int rc = check_matte_table(ranks);
+    if (rc != VK_OK) return rc;
+    if (n_samples == 0u) return fail(VK_ERR_BAD_ARG, "matte mask: n_samples must be >= 1");
+    if (!want && n_want > 0u) return fail(VK_ERR_BAD_ARG, "null matte id set");
+    if (n_pixels > 0u && (!ids || !counts || !mask_out)) return fail(VK_ERR_BAD_ARG, "null matte table");
+    for (uint64_t i = 0; i < n_pixels; i++) {
+        uint32_t sum = 0u;
+        for (uint32_t r = 0; r < ranks; r++) {
+            if (counts[i * ranks + r] == 0u) continue;                // a free slot holds no id
+            bool in = false;
+            for (uint32_t w = 0; w < n_want && !in; w++) in = want[w] == ids[i * ranks + r];
+            if (in) sum += counts[i * ranks + r];
+        }
+        mask_out[i] = (float)sum / (float)n_samples;
+    }
+    return VK_OK;
+}
+
+int vk_debug_matte_samples(vk_scene *scene, const vk_camera *cam, const vk_render_params *params, uint32_t first_sample, uint32_t kind,
+    uint32_t *ids_out) {
+    return guarded([&]() -> int {
+        int rc = check_matte_args(scene, cam, params, first_sample, kind, ids_out, nullptr, false);
+        if (rc != VK_OK) return rc;
+        vk_scene *q = first_part(scene);
+        HIP_TRY(hipSetDevice(q->device));
+        const TileGeom g(params);
+        MatteArgs A;
+        if ((rc = matte_args(q, cam, params, first_sample, kind, 1u, g, &A)) != VK_OK) return rc;
+        const size_t bytes = (size_t)params->width * params->height * params->samples_per_pixel * sizeof(uint32_t);
+        if ((rc = q->matte.buf.ensure(bytes)) != VK_OK) return rc;
+        A.ids = reinterpret_cast<uint32_t *>(q->matte.buf.get());
+        if (g.world > 1u) HIP_TRY(hipMemcpy(A.ids, ids_out, bytes, hipMemcpyHostToDevice));
+        if (g.n_local != 0u) {
+            launch_matte_samples(q->host->features, A);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpy(ids_out, A.ids, bytes, hipMemcpyDeviceToHost));
         return VK_OK;
     });
 }

@@ -255,6 +255,16 @@ VK_SPLAT_BOX, VK_SPLAT_TENT, VK_SPLAT_MITCHELL = 0, 1, 2
 VK_DEBUG_SPLAT_FORM_DEFAULT, VK_DEBUG_SPLAT_FORM_PLAIN, VK_DEBUG_SPLAT_FORM_TILED = 0, 1, 2
 
 
+class MatteParams(C.Structure):
+    """vk_matte_params (vk_render_mattes)"""
+    _fields_ = [("kind", C.c_uint32), ("ranks", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+VK_MATTE_OBJECT, VK_MATTE_MATERIAL = 0, 1
+VK_MATTE_BACKGROUND = 0xFFFFFFFF
+VK_MATTE_MAX_RANKS = 8
+
+
 class RegenInfo(C.Structure):
     """vk_regen_info (vk_regen_step)"""
     _fields_ = [("traced", C.c_uint64), ("live", C.c_uint64), ("remaining", C.c_uint64), ("emitted", C.c_uint64), ("missed", C.c_uint64),
@@ -377,6 +387,7 @@ DEVICE_SYMBOLS = [
     "vk_adapt_enable", "vk_adapt_begin", "vk_adapt_close", "vk_adapt_resolve", "vk_adapt_stderr", "vk_adapt_tile_samples",
     "vk_splat_default_params", "vk_splat_create", "vk_splat_deposit", "vk_splat_resolve", "vk_splat_reset", "vk_splat_get_info",
     "vk_splat_destroy",
+    "vk_matte_default_params", "vk_render_mattes", "vk_matte_merge", "vk_matte_mask",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
     "vk_temporal_get_info", "vk_temporal_destroy",
@@ -534,6 +545,15 @@ def _bind(lib):
     lib.vk_splat_get_info.argtypes = [C.c_void_p, C.POINTER(SplatInfo)]
     lib.vk_splat_destroy.restype = None
     lib.vk_splat_destroy.argtypes = [C.c_void_p]
+    lib.vk_matte_default_params.restype = C.c_int
+    lib.vk_matte_default_params.argtypes = [C.POINTER(MatteParams)]
+    lib.vk_render_mattes.restype = C.c_int
+    lib.vk_render_mattes.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.POINTER(MatteParams),
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    lib.vk_matte_merge.restype = C.c_int
+    lib.vk_matte_merge.argtypes = [C.c_uint32, C.c_uint64] + [C.c_void_p] * 6
+    lib.vk_matte_mask.restype = C.c_int
+    lib.vk_matte_mask.argtypes = [C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.vk_probe_eval.restype = C.c_int
     lib.vk_probe_eval.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_float)]
     lib.vk_trace_occluded_device.restype = C.c_int
@@ -607,6 +627,8 @@ def _bind(lib):
     lib.vk_debug_splat_form.argtypes = [C.c_void_p, C.c_uint32]
     lib.vk_debug_splat_last_ms.restype = C.c_int
     lib.vk_debug_splat_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 2)]
+    lib.vk_debug_matte_samples.restype = C.c_int
+    lib.vk_debug_matte_samples.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.c_void_p]
     lib.vk_debug_trace_occluded_device.restype = C.c_int
     lib.vk_debug_trace_occluded_device.argtypes = [C.c_void_p, C.POINTER(TraceParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                    C.c_int, C.c_uint32, C.c_uint32]

@@ -156,6 +156,14 @@ pub struct vk_splat_params { pub filter: u32, pub radius: f32, pub b: f32, pub c
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_splat_info { pub width: u32, pub height: u32, pub samples_per_pixel: u32, pub filter: u32, pub deposited: u64, pub dropped: u64, pub clamped: u64, pub skipped: u64, pub deposits: u64, pub contributions: u64 }
 
+// ID mattes: the kind of id and the table's size
+pub const VK_MATTE_OBJECT: u32 = 0;
+pub const VK_MATTE_MATERIAL: u32 = 1;
+pub const VK_MATTE_BACKGROUND: u32 = 0xFFFF_FFFF;
+pub const VK_MATTE_MAX_RANKS: u32 = 8;
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_matte_params { pub kind: u32, pub ranks: u32, pub flags: u32, pub _pad: u32 }
+
 // regeneration: what one vk_regen_step did
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_regen_info { pub traced: u64, pub live: u64, pub remaining: u64, pub emitted: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
@@ -284,6 +292,15 @@ extern "C" {
     pub fn vk_splat_reset(s: *mut vk_splat) -> c_int;
     pub fn vk_splat_get_info(s: *mut vk_splat, out: *mut vk_splat_info) -> c_int;
     pub fn vk_splat_destroy(s: *mut vk_splat);
+    // ID mattes (additive symbols of ABI 7): a ranked table of object or material ids per pixel, ids / counts ranks words per pixel,
+    // overflow one (may be null); merge and mask are host code
+    pub fn vk_matte_default_params(out: *mut vk_matte_params) -> c_int;
+    pub fn vk_render_mattes(scene: *mut vk_scene, cam: *const vk_camera, params: *const vk_render_params, first_sample: u32,
+                            mp: *const vk_matte_params, ids: *mut u32, counts: *mut u32, overflow: *mut u32, stats_out: *mut vk_stats) -> c_int;
+    pub fn vk_matte_merge(ranks: u32, n_pixels: u64, ids: *mut u32, counts: *mut u32, overflow: *mut u32, ids_b: *const u32,
+                          counts_b: *const u32, overflow_b: *const u32) -> c_int;
+    pub fn vk_matte_mask(ranks: u32, n_pixels: u64, ids: *const u32, counts: *const u32, n_samples: u32, want: *const u32, n_want: u32,
+                         mask_out: *mut f32) -> c_int;
     // the denoiser (additive symbols of ABI 7): color and out are required, each of stderr3 / albedo / normal / depth may be null
     pub fn vk_denoise_default_params(width: u32, height: u32, out: *mut vk_denoise_params) -> c_int;
     pub fn vk_denoise(scene: *mut vk_scene, dp: *const vk_denoise_params, color: *const f32, stderr3: *const f32, albedo: *const f32,

@@ -165,6 +165,39 @@ def check(lib, status):
         raise RuntimeError(f"vecchio_amd status {status}: {lib.vk_last_error().decode()}")
 
 
+def _matte_table(ids, counts, overflow):
+    """a matte table's arrays as vk_matte_* take them: uint32, contiguous, (..., ranks) with one overflow per pixel or none"""
+    for a in (ids, counts) + (() if overflow is None else (overflow,)):
+        assert a.dtype == np.uint32 and a.flags.c_contiguous
+    ranks = ids.shape[-1]
+    assert counts.shape == ids.shape and (overflow is None or overflow.shape == ids.shape[:-1])
+    return ranks, ids.size // ranks
+
+
+def matte_merge(ids, counts, overflow, ids_b, counts_b, overflow_b, lib=None):
+    """vk_matte_merge: folds table b into table a IN PLACE (host code, no device).  The tables are what DeviceScene.render_mattes()
+    returns, for windows of one frame: (..., ranks) uint32 ids and counts, and per-pixel overflow arrays — both given or both None.
+    Merged in any order, a frame's windows equal the one call over their union wherever that call's overflow is 0."""
+    lib = lib or ffi.load_device_lib()
+    ranks, n = _matte_table(ids, counts, overflow)
+    assert _matte_table(ids_b, counts_b, overflow_b) == (ranks, n)
+    ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)
+    check(lib, lib.vk_matte_merge(ranks, n, ptr(ids), ptr(counts), ptr(overflow), ptr(ids_b), ptr(counts_b), ptr(overflow_b)))
+    return ids, counts, overflow
+
+
+def matte_mask(ids, counts, n_samples, want, lib=None):
+    """vk_matte_mask: the share of a pixel's n_samples samples whose id is one of `want` (a set, because one box is six face ids), as a
+    float32 array of the table's pixel shape."""
+    lib = lib or ffi.load_device_lib()
+    ranks, n = _matte_table(ids, counts, None)
+    want = np.ascontiguousarray(want, np.uint32).reshape(-1)
+    out = np.zeros(ids.shape[:-1], np.float32)
+    check(lib, lib.vk_matte_mask(ranks, n, C.c_void_p(ids.ctypes.data), C.c_void_p(counts.ctypes.data), n_samples,
+                                 C.c_void_p(want.ctypes.data) if len(want) else None, len(want), C.c_void_p(out.ctypes.data)))
+    return out
+
+
 class DeviceScene:
     def __init__(self, desc, device=0, devices=None, lib=None):
         """device: one MI355X (vk_scene_create).  devices=[...]: one handle over several (vk_scene_create_multi):
@@ -478,6 +511,34 @@ class DeviceScene:
         check(self._lib, self._lib.vk_render_guides_device(self._h, C.byref(cam), C.byref(params), first_sample, C.byref(gp), *ptrs,
                                                            C.c_void_p(stream or 0), C.byref(stats)))
         return stats
+
+    def render_mattes(self, cam, params, first_sample=0, kind=ffi.VK_MATTE_OBJECT, ranks=6, overflow=True, out=None, return_stats=False):
+        """ID mattes of samples [first_sample, first_sample + params.samples_per_pixel) (vk_render_mattes): which object (kind
+        VK_MATTE_OBJECT: a vk_ref as trace_rays() names it) or which material (VK_MATTE_MATERIAL) the primary rays of each pixel show,
+        VK_MATTE_BACKGROUND for a miss.  Returns uint32 arrays, y = 0 the bottom row: ids and counts (height, width, ranks), sorted by
+        count descending, unused slots (0, 0), and overflow (height, width) — the samples that found the table full — or None with
+        overflow=False.  out: (ids, counts, overflow) to write into (pixels outside this call's tile partition keep their values)."""
+        shape = (params.height, params.width)
+        ids, counts, over = out if out is not None else (np.zeros(shape + (ranks,), np.uint32), np.zeros(shape + (ranks,), np.uint32),
+                                                        np.zeros(shape, np.uint32) if overflow else None)
+        assert _matte_table(ids, counts, over) == (ranks, params.height * params.width)
+        mp = ffi.MatteParams()
+        check(self._lib, self._lib.vk_matte_default_params(C.byref(mp)))
+        mp.kind, mp.ranks = kind, ranks
+        stats = ffi.Stats()
+        check(self._lib, self._lib.vk_render_mattes(self._h, C.byref(cam), C.byref(params), first_sample, C.byref(mp),
+                                                    C.c_void_p(ids.ctypes.data), C.c_void_p(counts.ctypes.data),
+                                                    C.c_void_p(over.ctypes.data) if over is not None else None, C.byref(stats)))
+        return (ids, counts, over, stats) if return_stats else (ids, counts, over)
+
+    def debug_matte_samples(self, cam, params, first_sample=0, kind=ffi.VK_MATTE_OBJECT, out=None):
+        """vk_debug_matte_samples: the id of every sample render_mattes() would count, (height, width, samples_per_pixel) uint32"""
+        if out is None:
+            out = np.zeros((params.height, params.width, params.samples_per_pixel), np.uint32)
+        assert out.dtype == np.uint32 and out.flags.c_contiguous
+        check(self._lib, self._lib.vk_debug_matte_samples(self._h, C.byref(cam), C.byref(params), first_sample, kind,
+                                                          C.c_void_p(out.ctypes.data)))
+        return out
 
     def denoise_params(self, width, height, **overrides):
         """vk_denoise_default_params for a width x height image, with fields overridden by keyword (levels=, sigma_l=, ...)"""
