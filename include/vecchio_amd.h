@@ -1211,6 +1211,84 @@ int vk_splat_reset(vk_splat *s);
 int vk_splat_get_info(vk_splat *s, vk_splat_info *out);
 void vk_splat_destroy(vk_splat *s);
 
+/* ---- robust film: bucketed sums and Gini-trimmed means for path batches (additive symbols of ABI 7) --------------------------------
+ * replaces: nothing (every other frame is a plain mean, as the reference's is: one firefly — one bright sample — lands in the image at
+ * full strength and spoils the error estimate, see vk_progress_stderr).  The answer is median of means: an accumulator keeps K partial
+ * sums per pixel instead of one and resolves them with an estimator that drops the outlying buckets only where the buckets disagree
+ * (the Gini-weighted form, "G-MoN"); on smooth pixels it stays the plain mean.  The standard error of the kept bucket means is a
+ * robust stderr3 for vk_denoise and vk_temporal_accumulate.
+ *
+ * State.  Per pixel and bucket b < K four 64-bit two's-complement words — the sums of r, g, b in 2^-26 units and a count —, width *
+ * height * K * 32 bytes, and one record of counters (8 KiB), on the scene's device (devices[0] of a multi-device scene).  All work is on
+ * the null stream there; no function takes a stream.  A batch goes in as it goes into a film: finished (nothing live), once per begin
+ * or emit — a flag of its own next to the film's and the splat accumulator's, cleared where those are cleared, so that one batch may go
+ * once each into a film, a splat accumulator and a robust accumulator, in any order.
+ *
+ * Deposit.  Every started id is a candidate.  Placement, drop, skip and clamp are vk_film_deposit's rule exactly, with clamp = min(1e10,
+ * 1.3e11 / (float)samples_per_pixel): a candidate whose status is VK_SHADE_MISS, VK_SHADE_ENDED or VK_PATHS_CULLED and whose
+ * state.pixel < width * height is placed, every other one counts in `skipped` and touches nothing; a placed one whose acc has a
+ * non-finite component counts in `dropped`, the rest in `deposited`; a sample whose largest |component| exceeds 31.999 has its
+ * components clamped to +-clamp first and counts in `clamped` if that largest exceeds the clamp; the fixed value of a component is
+ * trunc(a_c * 2^26).  The target is pixel state.pixel, bucket b = state.sample % K.  A deposited result adds its three fixed values to
+ * the sums and 1 to the count; a dropped one adds 1 to the count only (the reference divides by every sample, main.rs:192-197).
+ *
+ * Resolve, per pixel.  Everything is f32, unfused, in the order written.
+ *   1. j = the number of buckets with count > 0.  j = 0: rgb = 0 and stderr = 0.
+ *   2. Per non-empty bucket: m_c = ((float)sum_c * 2^-26) / (float)count, Y = (0.2126f * m_r + 0.7152f * m_g) + 0.0722f * m_b.
+ *   3. The non-empty buckets are ordered by Y ascending, ties by bucket index ascending: Y_1 .. Y_j.
+ *   4. tmax = (j - 2) / 2 in integer division, 0 for j < 2.  The trim t per side:
+ *        MEAN  t = 0.
+ *        TRIM  t = min(trim, tmax).
+ *        GINI  accumulated ascending from 0: num = sum_i (float)(2i - j - 1) * Y_i and s = sum_i Y_i;
+ *              G = (Y_1 >= 0 && s > 0) ? num / ((float)j * s) : 0;  h = (G * (float)j) * 0.5f;
+ *              t = min(h >= 1 ? (uint32_t)floorf(h) : 0, tmax)  (an h below 1 — a G that rounding left below 0 included — trims nothing).
+ *   5. The kept set S is the ordered buckets t + 1 .. j - t; q = j - 2t.
+ *   6. rgb_c = ((float)(sum over S of sum_c) * 2^-26) / (float)(sum over S of count); both are integer sums (64-bit, wrapping).
+ *   7. q >= 2, in kept order, accumulated ascending from 0: M_c = (sum over S of m_c) / (float)q, e_c = sum over S of (m_c - M_c) *
+ *      (m_c - M_c), stderr_c = sqrtf(e_c / (float)(q * (q - 1))).  Otherwise stderr_c = 0.
+ * The output is in vk_render's f32 layout (y = 0 the bottom row).  The sums stay; the call waits.  `how` (NULL: create's) lets one
+ * accumulator be resolved several ways: its mode and, in TRIM mode, its trim are taken; how->buckets must be the accumulator's or 0.
+ *
+ * Contract.  (1) The state is a function of the set of deposited results alone — not of windows, batch sizes or order — and equals
+ * tests/robust_ref.py's numpy restatement bit for bit.  (2) Summed over the buckets the colour sums are vk_film_deposit's and the
+ * counters are the film's.  (3) MEAN on a frame in which every (pixel, sample) below samples_per_pixel went in exactly once is
+ * vk_film_resolve(film, samples_per_pixel): vk_render's frame bit for bit wherever the film's contract holds.  (4) The TRIM and GINI
+ * images and the stderr equal the restatement bit for bit.
+ * What this is not.  TRIM and GINI are biased towards dark where a pixel's buckets legitimately disagree (a light seen by few samples);
+ * the bias is bounded by the trimmed share, 2t / j of the buckets.  Buckets of unequal count are ranked as equals.  stderr3 is 0 where
+ * fewer than two buckets are kept.  A regenerating batch is refused (its results are not kept), as vk_splat_deposit refuses it.
+ *
+ *   vk_robust_default_params: 8 buckets, GINI, trim 0.
+ *   vk_robust_create: VK_ERR_BAD_ARG for a null pointer, width or height 0, buckets outside 2..16, width * height * buckets > 2^27,
+ *     samples_per_pixel outside 1..2^26, an unknown mode, a non-zero _pad.  trim is read in TRIM mode only.  VK_ERR_OOM leaves *out
+ *     untouched.
+ *   vk_robust_deposit: VK_ERR_BAD_ARG, nothing enqueued or written: a null accumulator or batch, a batch of another scene, one never
+ *     begun, a regenerating one, one with live paths, one already deposited into a robust accumulator since its last vk_paths_begin /
+ *     vk_film_emit.
+ *   vk_robust_resolve: VK_ERR_BAD_ARG for a null accumulator or rgb_out, a `how` of other buckets, of an unknown mode or with a
+ *     non-zero _pad.  stderr3_out may be NULL.
+ *   vk_robust_reset zeroes sums and counters.  vk_robust_get_info waits.  vk_robust_destroy(NULL) does nothing.                    */
+enum { VK_ROBUST_MEAN = 0, VK_ROBUST_TRIM = 1, VK_ROBUST_GINI = 2 };
+typedef struct vk_robust vk_robust;      /* opaque */
+typedef struct vk_robust_params {        /* 16 bytes */
+    uint32_t buckets;                    /* K, 2 .. 16 */
+    uint32_t mode;                       /* VK_ROBUST_* */
+    uint32_t trim;                       /* TRIM's buckets per side; ignored otherwise */
+    uint32_t _pad;                       /* 0 */
+} vk_robust_params;
+typedef struct vk_robust_info {          /* 64 bytes */
+    uint32_t width, height, samples_per_pixel, buckets;
+    uint64_t deposited, dropped, clamped, skipped, deposits, _reserved;          /* deposits: accepted vk_robust_deposit calls */
+} vk_robust_info;
+int vk_robust_default_params(vk_robust_params *out);
+int vk_robust_create(vk_scene *scene, uint32_t width, uint32_t height, uint32_t samples_per_pixel, const vk_robust_params *rp,
+                     vk_robust **out);
+int vk_robust_deposit(vk_robust *s, vk_paths *batch);
+int vk_robust_resolve(vk_robust *s, const vk_robust_params *how, float *rgb_out, float *stderr3_out);
+int vk_robust_reset(vk_robust *s);
+int vk_robust_get_info(vk_robust *s, vk_robust_info *out);
+void vk_robust_destroy(vk_robust *s);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

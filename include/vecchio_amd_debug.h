@@ -166,6 +166,15 @@ int vk_debug_splat_form(vk_splat *s, uint32_t form);
  * Waits for those.  Takes no stream.  In both libraries. */
 int vk_debug_splat_last_ms(vk_splat *s, double ms[2]);
 
+/* a robust accumulator's raw state: width * height * K * 4 two's-complement 64-bit values in the fixed logical order [(pixel * K + b) *
+ * 4 + c], pixel = y * width + x, c = r, g, b (2^-26 units), count — whatever the device layout is.  Waits.  VK_ERR_BAD_ARG for a null
+ * pointer.  Takes no stream.  In both libraries. */
+int vk_debug_robust_sums(vk_robust *s, int64_t *out);
+/* the device milliseconds of the accumulator's last vk_robust_deposit (ms[0]) and vk_robust_resolve (ms[1]: the kernel without the
+ * copies to the host), between two events around each; 0 for one that has not run.  Waits for those.  Takes no stream.  In both
+ * libraries. */
+int vk_debug_robust_last_ms(vk_robust *s, double ms[2]);
+
 /* the id of every sample vk_render_mattes would count, by the same per-lane code on the same lanes: ids_out[(y * width + x) * spp + k] is
  * the id of sample first_sample + k under `kind` (VK_MATTE_OBJECT or VK_MATTE_MATERIAL), spp = params->samples_per_pixel; pixels outside
  * the call's tile partition are left untouched.  vk_render_mattes' checks.  Waits.  In both libraries. */

@@ -76,7 +76,7 @@ def _device_deps():
     srcs = [os.path.join(CSRC, "vk_api.hip"), os.path.join(CSRC, "vk_linearize.cpp")]
     return srcs, srcs + [os.path.join(CSRC, f) for f in ("vk_kernels.h", "vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_resources.h",
                                                          "vk_emit.h", "vk_adapt.h", "vk_adapt.hip", "vk_splat.h", "vk_splat.hip", "vk_matte.h",
-                                                         "vk_matte.hip")] + \
+                                                         "vk_matte.hip", "vk_robust.h", "vk_robust.hip")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
 
 
@@ -87,7 +87,7 @@ def host_is_stale():
 def device_is_stale():
     return _newer(os.path.join(LIB, "libvecchio_amd.so"), _device_deps()[1], HIPFLAGS) or not os.path.exists(kernel_resources_path()) or \
         not os.path.exists(kernel_resources_adapt_path()) or not os.path.exists(kernel_resources_splat_path()) or \
-        not os.path.exists(kernel_resources_matte_path())
+        not os.path.exists(kernel_resources_matte_path()) or not os.path.exists(kernel_resources_robust_path())
 
 
 def build_host(force=False):
@@ -122,7 +122,7 @@ def build_device_debug(force=False):
     flags = HIPFLAGS + ["-DVK_DEBUG_LIB"]
     if force or _newer(out, deps, flags):
         os.makedirs(LIB, exist_ok=True)
-        _run_atomic([HIPCC] + flags + ["-shared", "-o"], out, srcs + [_adapt_src(), _splat_src(), _matte_src()])
+        _run_atomic([HIPCC] + flags + ["-shared", "-o"], out, srcs + [_adapt_src(), _splat_src(), _matte_src(), _robust_src()])
         _stamp(out, deps, flags)
     return out
 
@@ -144,6 +144,11 @@ def _splat_src():
 def _matte_src():
     """the kernels of vk_render_mattes (ID mattes: a ranked table of object or material ids per pixel): a translation unit of its own"""
     return os.path.join(CSRC, "vk_matte.hip")
+
+
+def _robust_src():
+    """the kernels of vk_robust_* (robust film: the bucketed deposit of a path batch and its trimmed resolve): a translation unit of its own"""
+    return os.path.join(CSRC, "vk_robust.hip")
 
 
 def _hipcc_with_remarks(cmd, cwd, cleanup=()):
@@ -180,9 +185,9 @@ def _write_resources(path, remarks, spills):
 
 
 def build_device(force=False):
-    """hipcc cross-compiles for gfx950 without a GPU present.  Four steps: vk_adapt.hip, vk_splat.hip and vk_matte.hip to an object of
-    their own each (their resource remarks go to kernel_resources_adapt.txt, kernel_resources_splat.txt and kernel_resources_matte.txt),
-    then vk_api.hip and vk_linearize.cpp, linked with those objects (kernel_resources.txt: theirs alone)."""
+    """hipcc cross-compiles for gfx950 without a GPU present.  Five steps: vk_adapt.hip, vk_splat.hip, vk_matte.hip and vk_robust.hip to an
+    object of their own each (their resource remarks go to kernel_resources_adapt.txt, kernel_resources_splat.txt,
+    kernel_resources_matte.txt and kernel_resources_robust.txt), then vk_api.hip and vk_linearize.cpp, linked with those objects (kernel_resources.txt: theirs alone)."""
     out = os.path.join(LIB, "libvecchio_amd.so")
     srcs, deps = _device_deps()
     if force or device_is_stale():
@@ -192,10 +197,11 @@ def build_device(force=False):
         with tempfile.TemporaryDirectory() as tmp:
             analysis = ["-Rpass-analysis=kernel-resource-usage", "-save-temps"]
             tmp_adapt, tmp_splat, tmp_main = os.path.join(tmp, "adapt"), os.path.join(tmp, "splat"), os.path.join(tmp, "main")
-            tmp_matte = os.path.join(tmp, "matte")
+            tmp_matte, tmp_robust = os.path.join(tmp, "matte"), os.path.join(tmp, "robust")
             os.makedirs(tmp_adapt)
             os.makedirs(tmp_splat)
             os.makedirs(tmp_matte)
+            os.makedirs(tmp_robust)
             os.makedirs(tmp_main)
             adapt_obj = os.path.join(tmp_adapt, "vk_adapt.o")
             adapt = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", adapt_obj, _adapt_src()], tmp_adapt)
@@ -203,14 +209,17 @@ def build_device(force=False):
             splat = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", splat_obj, _splat_src()], tmp_splat)
             matte_obj = os.path.join(tmp_matte, "vk_matte.o")
             matte = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", matte_obj, _matte_src()], tmp_matte)
+            robust_obj = os.path.join(tmp_robust, "vk_robust.o")
+            robust = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", robust_obj, _robust_src()], tmp_robust)
             tmp_out = f"{out}.tmp.{os.getpid()}"
             # (the objects in front of the sources: hipcc reads whatever follows a source file as HIP)
-            main = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-shared", "-o", tmp_out, adapt_obj, splat_obj, matte_obj] + srcs, tmp_main, [tmp_out])
+            main = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-shared", "-o", tmp_out, adapt_obj, splat_obj, matte_obj, robust_obj] + srcs, tmp_main, [tmp_out])
             os.replace(tmp_out, out)
         _write_resources(kernel_resources_path(), *main)
         _write_resources(kernel_resources_adapt_path(), *adapt)
         _write_resources(kernel_resources_splat_path(), *splat)
         _write_resources(kernel_resources_matte_path(), *matte)
+        _write_resources(kernel_resources_robust_path(), *robust)
         _stamp(out, deps, HIPFLAGS)
     return out
 
@@ -242,6 +251,11 @@ def kernel_resources_matte_path():
     return os.path.join(LIB, "kernel_resources_matte.txt")
 
 
+def kernel_resources_robust_path():
+    """the same record for the kernels of vk_robust.hip"""
+    return os.path.join(LIB, "kernel_resources_robust.txt")
+
+
 def build_oracle(force=False):
     """CPU oracle (test infrastructure).  oracle/_ref does not exist: the reference is Rust and
     there is no cargo/rustc in this image."""
@@ -263,11 +277,11 @@ def build_emu(force=False):
             os.path.join(edir, "emu_occlusion.cpp"), os.path.join(edir, "emu_radiance.cpp"),
             os.path.join(edir, "emu_irradiance.cpp"), os.path.join(edir, "emu_probes.cpp"), os.path.join(edir, "emu_shade.cpp"),
             os.path.join(edir, "emu_paths.cpp"), os.path.join(edir, "emu_film.cpp"), os.path.join(edir, "emu_adapt.cpp"),
-            os.path.join(edir, "emu_splat.cpp"), os.path.join(edir, "emu_matte.cpp"),
+            os.path.join(edir, "emu_splat.cpp"), os.path.join(edir, "emu_matte.cpp"), os.path.join(edir, "emu_robust.cpp"),
             os.path.join(CSRC, "vk_linearize.cpp")]
     # (the tool's own headers: whichever are there)
     deps = srcs + sorted(os.path.join(edir, f) for f in os.listdir(edir) if f.endswith(".h")) + \
-        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_adapt.h", "vk_splat.h", "vk_matte.h")] + \
+        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_adapt.h", "vk_splat.h", "vk_matte.h", "vk_robust.h")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
     if force or _newer(out, deps, CXXFLAGS):
         os.makedirs(os.path.dirname(out), exist_ok=True)

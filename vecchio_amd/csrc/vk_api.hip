@@ -53,6 +53,7 @@
 #include "vk_kernels.h"
 #include "vk_adapt.h"        // the kernels of vk_adapt.hip: argument records and launchers
 #include "vk_splat.h"        // the kernels of vk_splat.hip: the filter, argument records and launchers
+#include "vk_robust.h"       // the kernels of vk_robust.hip: the per-pixel resolve, argument records and launchers
 #include "vk_matte.h"        // the kernels of vk_matte.hip: the table of a pixel, the argument record and launchers
 
 namespace {
@@ -2666,6 +2667,7 @@ struct vk_paths {
     bool begun = false;
     bool deposited = false;                         // vk_film_deposit has taken this batch (cleared by vk_paths_begin and vk_film_emit)
     bool splatted = false;                          // vk_splat_deposit has taken this batch (cleared where `deposited` is)
+    bool bucketed = false;                          // vk_robust_deposit has taken this batch (cleared where `deposited` is)
     uint32_t cur = 0;                               // ids[cur] holds the live ids
     uint64_t started = 0, live = 0, retired[5] = {0, 0, 0, 0, 0};
     uint32_t bounces = 0;
@@ -2790,7 +2792,7 @@ int paths_take_counts(vk_paths *p, unsigned long long c[5]) {
 // a batch as a begin leaves it: `started` paths of which `live` are live, nothing retired, no bounce run, not regenerating.  Called behind
 // every check and every launch of a begin that can fail: a refused call leaves the batch as it was.
 void paths_reset(vk_paths *p, const vk_shade_params &sp, uint64_t started, uint64_t live) {
-    p->sp = sp; p->begun = true; p->deposited = false; p->splatted = false; p->cur = 0u; p->started = started; p->live = live; p->bounces = 0u;
+    p->sp = sp; p->begun = true; p->deposited = false; p->splatted = false; p->bucketed = false; p->cur = 0u; p->started = started; p->live = live; p->bounces = 0u;
     for (uint64_t &r : p->retired) r = 0u;
     p->regen = false; p->regen_film = nullptr; p->regen_win = vk_film_window{}; p->regen_next = 0u; p->regen_total = 0u;
     p->regen_tiles = false; p->regen_first_sample = 0u; p->regen_n_samples = 0u;
@@ -3961,6 +3963,202 @@ int vk_debug_splat_form(vk_splat *s, uint32_t form) {
 
 // test hook (vecchio_amd_debug.h): the last deposit and resolve, from the events recorded around each; 0 for one not yet run
 int vk_debug_splat_last_ms(vk_splat *s, double ms[2]) {
+    if (!s || !ms) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or ms)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        double got[2] = {0.0, 0.0};
+        for (int k = 0; k < 2; k++) {
+            if (!s->timed[k]) continue;
+            HIP_TRY(hipEventSynchronize(s->ev[2 * k + 1]));
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, s->ev[2 * k], s->ev[2 * k + 1]));
+            got[k] = (double)t;
+        }
+        for (int k = 0; k < 2; k++) ms[k] = got[k];
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- robust film (vk_robust_*): a frame's fixed-point sums kept in K buckets per pixel — r, g, b and the count per bucket — on the scene's
+// device (devices[0] of a multi-device scene).  robust_deposit_kernel adds a finished batch, robust_resolve_kernel<K> orders, trims and
+// divides (vk_robust.hip); all on the null stream, on buffers and events the handle owns.  Of the batch a deposit reads its results and
+// sets its `bucketed` flag; nothing of the scene handle is read but its device.
+struct vk_robust {
+    vk_scene *scene = nullptr;                      // as handed to vk_robust_create
+    uint32_t width = 0, height = 0, spp = 0;
+    vk_robust_params rp{};
+    float accum_clamp = 0.0f;
+    DeviceBuffer<unsigned long long> sums;          // [width * height][buckets][4], two's complement
+    DeviceBuffer<unsigned long long> counters;      // deposited, dropped, clamped, skipped, in SPLAT_STRIPES stripes
+    DeviceBuffer<float> out;                        // the resolved frame and its standard error on their way to the host (first resolve)
+    Event ev[4];                                    // around the last deposit and resolve
+    bool timed[2] = {false, false};
+    uint64_t deposits = 0;
+};
+
+namespace {
+
+void robust_free(vk_robust *s) {
+    (void)hipSetDevice(first_part(s->scene)->device);
+    (void)hipStreamSynchronize(nullptr);              // (a deposit may still run)
+    (void)hipGetLastError();
+    delete s;
+}
+
+size_t robust_words(const vk_robust *s) { return (size_t)s->width * s->height * s->rp.buckets * 4u; }
+
+int robust_zero(vk_robust *s) {
+    HIP_TRY(hipMemsetAsync(s->sums, 0, robust_words(s) * sizeof(unsigned long long), nullptr));
+    HIP_TRY(hipMemsetAsync(s->counters, 0, SPLAT_COUNTER_BYTES, nullptr));
+    s->deposits = 0u;
+    return VK_OK;
+}
+
+const char *robust_refusal(const vk_robust_params &rp) {
+    if (rp.mode != VK_ROBUST_MEAN && rp.mode != VK_ROBUST_TRIM && rp.mode != VK_ROBUST_GINI) return "unknown mode";
+    if (rp._pad != 0u) return "_pad must be 0";
+    return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_robust_default_params(vk_robust_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    out->buckets = 8u; out->mode = VK_ROBUST_GINI; out->trim = 0u; out->_pad = 0u;
+    return VK_OK;
+}
+
+int vk_robust_create(vk_scene *scene, uint32_t width, uint32_t height, uint32_t samples_per_pixel, const vk_robust_params *rp, vk_robust **out) {
+    if (!scene || !rp || !out) return fail(VK_ERR_BAD_ARG, "null argument (scene, params or out)");
+    if (width == 0u || height == 0u) return fail(VK_ERR_BAD_ARG, "width and height must be >= 1");
+    if (rp->buckets < ROBUST_MIN_BUCKETS || rp->buckets > ROBUST_MAX_BUCKETS) return fail(VK_ERR_BAD_ARG, "buckets must be in 2..16");
+    // (width * height < 2^64, and the product with buckets is taken only once that is below 2^27)
+    if ((uint64_t)width * height > ROBUST_MAX_CELLS || (uint64_t)width * height * rp->buckets > ROBUST_MAX_CELLS)
+        return fail(VK_ERR_BAD_ARG, "width * height * buckets exceeds 2^27");
+    if (samples_per_pixel == 0u || samples_per_pixel > (1u << 26)) return fail(VK_ERR_BAD_ARG, "samples_per_pixel must be in 1..2^26");
+    if (const char *why = robust_refusal(*rp)) return fail(VK_ERR_BAD_ARG, why);
+    return guarded([&]() -> int {
+        std::unique_ptr<vk_robust, void (*)(vk_robust *)> s(new vk_robust(), robust_free);
+        s->scene = scene; s->width = width; s->height = height; s->spp = samples_per_pixel; s->rp = *rp;
+        if (rp->mode != VK_ROBUST_TRIM) s->rp.trim = 0u;
+        s->accum_clamp = accum_clamp_for(samples_per_pixel);
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        int r = VK_OK;
+        handle_alloc(r, s->sums, robust_words(s.get()) * sizeof(unsigned long long));
+        handle_alloc(r, s->counters, SPLAT_COUNTER_BYTES);
+        if (r != VK_OK) return r;
+        for (Event &e : s->ev) if ((r = e.create()) != VK_OK) return r;
+        if ((r = robust_zero(s.get())) != VK_OK) return r;
+        *out = s.release();
+        return VK_OK;
+    });
+}
+
+int vk_robust_deposit(vk_robust *s, vk_paths *batch) {
+    return guarded([&]() -> int {
+        if (!s || !batch) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or path batch)");
+        if (batch->scene != s->scene) return fail(VK_ERR_BAD_ARG, "the path batch belongs to another scene than the accumulator");
+        if (!batch->begun) return fail(VK_ERR_BAD_ARG, "vk_robust_deposit before vk_paths_begin or vk_film_emit");
+        if (batch->regen) return fail(VK_ERR_BAD_ARG, "vk_robust_deposit on a regenerating path batch (its results are not kept)");
+        if (batch->live != 0u) return fail(VK_ERR_BAD_ARG, "the path batch has live paths (step or cull them first)");
+        if (batch->bucketed) return fail(VK_ERR_BAD_ARG, "the path batch has been deposited into a robust accumulator since its last begin or emit");
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        const uint64_t n = batch->started;
+        HIP_TRY(hipEventRecord(s->ev[0], nullptr));
+        if (n != 0u) {
+            RobustDepositArgs A;
+            memset(&A, 0, sizeof(A));
+            A.result_state = reinterpret_cast<const uint4 *>(batch->result_state.get()); A.result_status = batch->result_status;
+            A.sums = s->sums; A.counters = s->counters;
+            A.n = (uint32_t)n; A.n_pixels = s->width * s->height; A.buckets = s->rp.buckets;
+            A.accum_clamp = s->accum_clamp;
+            launch_robust_deposit(A);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(s->ev[1], nullptr));
+        s->timed[0] = true;
+        s->deposits++;
+        batch->bucketed = true;
+        return VK_OK;
+    });
+}
+
+int vk_robust_resolve(vk_robust *s, const vk_robust_params *how, float *rgb_out, float *stderr3_out) {
+    return guarded([&]() -> int {
+        if (!s || !rgb_out) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or rgb_out)");
+        vk_robust_params rp = s->rp;
+        if (how) {
+            if (how->buckets != 0u && how->buckets != s->rp.buckets) return fail(VK_ERR_BAD_ARG, "how->buckets must be 0 or the accumulator's");
+            if (const char *why = robust_refusal(*how)) return fail(VK_ERR_BAD_ARG, why);
+            rp.mode = how->mode; rp.trim = how->mode == VK_ROBUST_TRIM ? how->trim : 0u;
+        }
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        const size_t floats = (size_t)s->width * s->height * 3u;
+        if (!s->out) {
+            int rc = VK_OK;
+            handle_alloc(rc, s->out, 2u * floats * sizeof(float));
+            if (rc != VK_OK) return rc;
+        }
+        RobustResolveArgs A;
+        memset(&A, 0, sizeof(A));
+        A.sums = reinterpret_cast<const RobustCell *>(s->sums.get()); A.rgb = s->out; A.se = stderr3_out ? s->out.get() + floats : nullptr;
+        A.n_pixels = s->width * s->height; A.mode = rp.mode; A.trim = rp.trim;
+        HIP_TRY(hipEventRecord(s->ev[2], nullptr));
+        launch_robust_resolve(A, s->rp.buckets);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(s->ev[3], nullptr));
+        s->timed[1] = true;
+        HIP_TRY(hipMemcpy(rgb_out, s->out, floats * sizeof(float), hipMemcpyDeviceToHost));
+        if (stderr3_out) HIP_TRY(hipMemcpy(stderr3_out, s->out.get() + floats, floats * sizeof(float), hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+int vk_robust_reset(vk_robust *s) {
+    if (!s) return fail(VK_ERR_BAD_ARG, "null accumulator");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        return robust_zero(s);
+    });
+}
+
+int vk_robust_get_info(vk_robust *s, vk_robust_info *out) {
+    if (!s || !out) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        std::vector<unsigned long long> stripes((size_t)SPLAT_STRIPES * SPLAT_STRIPE_WORDS);
+        HIP_TRY(hipMemcpy(stripes.data(), s->counters, SPLAT_COUNTER_BYTES, hipMemcpyDeviceToHost));      // (waits for the null stream)
+        unsigned long long c[ROBUST_COUNTERS] = {0ull, 0ull, 0ull, 0ull};
+        for (uint32_t k = 0; k < SPLAT_STRIPES; k++)
+            for (uint32_t j = 0; j < ROBUST_COUNTERS; j++) c[j] += stripes[(size_t)k * SPLAT_STRIPE_WORDS + j];
+        memset(out, 0, sizeof(*out));
+        out->width = s->width; out->height = s->height; out->samples_per_pixel = s->spp; out->buckets = s->rp.buckets;
+        out->deposited = c[0]; out->dropped = c[1]; out->clamped = c[2]; out->skipped = c[3];
+        out->deposits = s->deposits;
+        return VK_OK;
+    });
+}
+
+void vk_robust_destroy(vk_robust *s) {
+    if (s) robust_free(s);
+}
+
+// test hook (vecchio_amd_debug.h): the raw state, [(pixel * K + b) * 4 + c] — the device's own layout
+int vk_debug_robust_sums(vk_robust *s, int64_t *out) {
+    if (!s || !out) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        HIP_TRY(hipMemcpy(out, s->sums, robust_words(s) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): the last deposit and resolve, from the events recorded around each; 0 for one not yet run
+int vk_debug_robust_last_ms(vk_robust *s, double ms[2]) {
     if (!s || !ms) return fail(VK_ERR_BAD_ARG, "null argument (accumulator or ms)");
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(first_part(s->scene)->device));

@@ -265,6 +265,21 @@ VK_MATTE_BACKGROUND = 0xFFFFFFFF
 VK_MATTE_MAX_RANKS = 8
 
 
+class RobustParams(C.Structure):
+    """vk_robust_params (vk_robust_create, vk_robust_resolve)"""
+    _fields_ = [("buckets", C.c_uint32), ("mode", C.c_uint32), ("trim", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class RobustInfo(C.Structure):
+    """vk_robust_info (vk_robust_get_info)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("samples_per_pixel", C.c_uint32), ("buckets", C.c_uint32),
+                ("deposited", C.c_uint64), ("dropped", C.c_uint64), ("clamped", C.c_uint64), ("skipped", C.c_uint64),
+                ("deposits", C.c_uint64), ("_reserved", C.c_uint64)]
+
+
+VK_ROBUST_MEAN, VK_ROBUST_TRIM, VK_ROBUST_GINI = 0, 1, 2
+
+
 class RegenInfo(C.Structure):
     """vk_regen_info (vk_regen_step)"""
     _fields_ = [("traced", C.c_uint64), ("live", C.c_uint64), ("remaining", C.c_uint64), ("emitted", C.c_uint64), ("missed", C.c_uint64),
@@ -387,6 +402,8 @@ DEVICE_SYMBOLS = [
     "vk_adapt_enable", "vk_adapt_begin", "vk_adapt_close", "vk_adapt_resolve", "vk_adapt_stderr", "vk_adapt_tile_samples",
     "vk_splat_default_params", "vk_splat_create", "vk_splat_deposit", "vk_splat_resolve", "vk_splat_reset", "vk_splat_get_info",
     "vk_splat_destroy",
+    "vk_robust_default_params", "vk_robust_create", "vk_robust_deposit", "vk_robust_resolve", "vk_robust_reset", "vk_robust_get_info",
+    "vk_robust_destroy",
     "vk_matte_default_params", "vk_render_mattes", "vk_matte_merge", "vk_matte_mask",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
@@ -545,6 +562,20 @@ def _bind(lib):
     lib.vk_splat_get_info.argtypes = [C.c_void_p, C.POINTER(SplatInfo)]
     lib.vk_splat_destroy.restype = None
     lib.vk_splat_destroy.argtypes = [C.c_void_p]
+    lib.vk_robust_default_params.restype = C.c_int
+    lib.vk_robust_default_params.argtypes = [C.POINTER(RobustParams)]
+    lib.vk_robust_create.restype = C.c_int
+    lib.vk_robust_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RobustParams), C.POINTER(C.c_void_p)]
+    lib.vk_robust_deposit.restype = C.c_int
+    lib.vk_robust_deposit.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_robust_resolve.restype = C.c_int
+    lib.vk_robust_resolve.argtypes = [C.c_void_p, C.POINTER(RobustParams), C.c_void_p, C.c_void_p]
+    lib.vk_robust_reset.restype = C.c_int
+    lib.vk_robust_reset.argtypes = [C.c_void_p]
+    lib.vk_robust_get_info.restype = C.c_int
+    lib.vk_robust_get_info.argtypes = [C.c_void_p, C.POINTER(RobustInfo)]
+    lib.vk_robust_destroy.restype = None
+    lib.vk_robust_destroy.argtypes = [C.c_void_p]
     lib.vk_matte_default_params.restype = C.c_int
     lib.vk_matte_default_params.argtypes = [C.POINTER(MatteParams)]
     lib.vk_render_mattes.restype = C.c_int
@@ -627,6 +658,10 @@ def _bind(lib):
     lib.vk_debug_splat_form.argtypes = [C.c_void_p, C.c_uint32]
     lib.vk_debug_splat_last_ms.restype = C.c_int
     lib.vk_debug_splat_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 2)]
+    lib.vk_debug_robust_sums.restype = C.c_int
+    lib.vk_debug_robust_sums.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_debug_robust_last_ms.restype = C.c_int
+    lib.vk_debug_robust_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 2)]
     lib.vk_debug_matte_samples.restype = C.c_int
     lib.vk_debug_matte_samples.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.c_void_p]
     lib.vk_debug_trace_occluded_device.restype = C.c_int

@@ -164,6 +164,16 @@ pub const VK_MATTE_MAX_RANKS: u32 = 8;
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_matte_params { pub kind: u32, pub ranks: u32, pub flags: u32, pub _pad: u32 }
 
+// robust film: an accumulator's buckets and estimator, and its counters
+pub const VK_ROBUST_MEAN: u32 = 0;
+pub const VK_ROBUST_TRIM: u32 = 1;
+pub const VK_ROBUST_GINI: u32 = 2;
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_robust_params { pub buckets: u32, pub mode: u32, pub trim: u32, pub _pad: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_robust_info { pub width: u32, pub height: u32, pub samples_per_pixel: u32, pub buckets: u32, pub deposited: u64, pub dropped: u64, pub clamped: u64, pub skipped: u64, pub deposits: u64, pub _reserved: u64 }
+
 // regeneration: what one vk_regen_step did
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_regen_info { pub traced: u64, pub live: u64, pub remaining: u64, pub emitted: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
@@ -180,6 +190,7 @@ pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, 
 #[repr(C)] pub struct vk_paths { _private: [u8; 0] }
 #[repr(C)] pub struct vk_film { _private: [u8; 0] }
 #[repr(C)] pub struct vk_splat { _private: [u8; 0] }
+#[repr(C)] pub struct vk_robust { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -292,6 +303,15 @@ extern "C" {
     pub fn vk_splat_reset(s: *mut vk_splat) -> c_int;
     pub fn vk_splat_get_info(s: *mut vk_splat, out: *mut vk_splat_info) -> c_int;
     pub fn vk_splat_destroy(s: *mut vk_splat);
+    // robust film (additive symbols of ABI 7): a finished batch added to K bucketed sums per pixel, resolved as a plain, trimmed or
+    // Gini-trimmed mean of the buckets with the standard error of the kept bucket means; how: null (create's) or another mode / trim
+    pub fn vk_robust_default_params(out: *mut vk_robust_params) -> c_int;
+    pub fn vk_robust_create(scene: *mut vk_scene, width: u32, height: u32, samples_per_pixel: u32, rp: *const vk_robust_params, out: *mut *mut vk_robust) -> c_int;
+    pub fn vk_robust_deposit(s: *mut vk_robust, batch: *mut vk_paths) -> c_int;
+    pub fn vk_robust_resolve(s: *mut vk_robust, how: *const vk_robust_params, rgb_out: *mut f32, stderr3_out: *mut f32) -> c_int;
+    pub fn vk_robust_reset(s: *mut vk_robust) -> c_int;
+    pub fn vk_robust_get_info(s: *mut vk_robust, out: *mut vk_robust_info) -> c_int;
+    pub fn vk_robust_destroy(s: *mut vk_robust);
     // ID mattes (additive symbols of ABI 7): a ranked table of object or material ids per pixel, ids / counts ranks words per pixel,
     // overflow one (may be null); merge and mask are host code
     pub fn vk_matte_default_params(out: *mut vk_matte_params) -> c_int;

@@ -656,6 +656,13 @@ class DeviceScene:
         in pixels, 0.5 .. 2.  Use as a context manager, or close() it before the scene."""
         return Splat(self, width, height, spp, ffi.SplatParams(filter, radius, b, c))
 
+    def robust(self, width, height, spp, buckets=8, mode=ffi.VK_ROBUST_GINI, trim=0):
+        """A robust accumulator on this scene (vk_robust_create): per pixel `buckets` partial sums of r, g, b and a count, into which
+        finished path batches are deposited on the device (sample s of a pixel into bucket s % buckets), resolved as the plain mean
+        (ffi.VK_ROBUST_MEAN), the mean without `trim` buckets per side (_TRIM) or without as many as the buckets' Gini coefficient asks
+        for (_GINI).  Use as a context manager, or close() it before the scene."""
+        return Robust(self, width, height, spp, ffi.RobustParams(buckets, mode, trim, 0))
+
     def debug_compact_paths(self, items, ids, n_ids, canary=0xA5, roulette=None):
         """The compaction of a path batch's bounce on host arrays (vk_debug_compact_paths, a test hook): items a SHADED_DTYPE array, ids
         their uint32 ids (each below n_ids).  Every output is prefilled with the byte `canary`.  Returns (rays, states, ids_out — n
@@ -1293,6 +1300,91 @@ class Splat:
     def close(self):
         if self._h:
             self._lib.vk_splat_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Robust:
+    """vk_robust handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed): deposit() finished path
+    batches into the buckets of their pixels; resolve() orders each pixel's buckets, trims and divides.  With ffi.VK_ROBUST_MEAN the
+    frame of a film's camera paths is the film's, bit for bit."""
+
+    def __init__(self, scene, width, height, spp, params):
+        self._lib = scene._lib
+        self._scene = scene
+        self.width, self.height, self.spp = int(width), int(height), int(spp)
+        self.params = ffi.RobustParams.from_buffer_copy(params)
+        self.buckets = int(self.params.buckets)
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_robust_create(scene._h, width, height, spp, C.byref(self.params), C.byref(h)))
+        self._h = h
+
+    def deposit(self, batch):
+        """Add the retired paths of `batch`, which has nothing live (vk_robust_deposit): sample s of a pixel goes to bucket s % buckets."""
+        check(self._lib, self._lib.vk_robust_deposit(self._h, batch._h))
+
+    def resolve(self, mode=None, trim=None, want_stderr=False, out=None):
+        """The frame (vk_robust_resolve): float32 (height, width, 3), y = 0 the bottom row.  mode / trim: None — the accumulator's own —
+        or another way to resolve the same sums.  want_stderr: return (image, stderr3), the standard error of the kept bucket means
+        in the same layout.  out: an array of the image's shape to write into."""
+        if out is None:
+            out = np.zeros((self.height, self.width, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == self.width * self.height * 3
+        how = None
+        if mode is not None or trim is not None:
+            how = C.byref(ffi.RobustParams(0, self.params.mode if mode is None else mode, self.params.trim if trim is None else trim, 0))
+        se = np.zeros((self.height, self.width, 3), np.float32) if want_stderr else None
+        check(self._lib, self._lib.vk_robust_resolve(self._h, how, out.ctypes.data_as(C.c_void_p),
+                                                     se.ctypes.data_as(C.c_void_p) if want_stderr else None))
+        return (out, se) if want_stderr else out
+
+    def reset(self):
+        """Zero the sums and the counters (vk_robust_reset)."""
+        check(self._lib, self._lib.vk_robust_reset(self._h))
+
+    def info(self):
+        inf = ffi.RobustInfo()
+        check(self._lib, self._lib.vk_robust_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def render(self, film, batch, cull=None):
+        """The whole frame of `film` through `batch`: Film.render()'s windows, each emitted, stepped to its end and deposited into the
+        film and here.  Returns resolve()."""
+        for win in film.windows(int(batch.info().capacity)):
+            film.emit(batch, *win)
+            while batch.step(1).live:
+                if cull is not None:
+                    cull(batch)
+            film.deposit(batch)
+            self.deposit(batch)
+        return self.resolve()
+
+    def debug_sums(self):
+        """The raw state (vk_debug_robust_sums, a test hook): int64 (height, width, buckets, 4) — r, g, b in 2^-26 units, count"""
+        out = np.zeros((self.height, self.width, self.buckets, 4), np.int64)
+        check(self._lib, self._lib.vk_debug_robust_sums(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def last_ms(self):
+        """(deposit, resolve) device milliseconds of the last call of each (vk_debug_robust_last_ms, a test hook)"""
+        ms = (C.c_double * 2)()
+        check(self._lib, self._lib.vk_debug_robust_last_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
+    def close(self):
+        if self._h:
+            self._lib.vk_robust_destroy(self._h)
             self._h = None
 
     def __enter__(self):
