@@ -1289,6 +1289,106 @@ int vk_robust_reset(vk_robust *s);
 int vk_robust_get_info(vk_robust *s, vk_robust_info *out);
 void vk_robust_destroy(vk_robust *s);
 
+/* ---- light-path layers: a path batch's frame split by bounce history (additive symbols of ABI 7) ---------------------------------
+ * replaces: a host loop around vk_trace_rays and vk_shade_hits kept only to see each bounce's status and lobe (336 bytes per path and
+ * bounce over the bus, and in a scene with a medium not the same sample).  Every other accumulator takes a finished path's final acc
+ * and nothing else; this one also knows what the path did: emission seen directly, sky, direct against indirect light, a diffuse
+ * against a specular or glass first bounce, a medium's in-scatter, one light's contribution.  In this integrator a path has ONE
+ * contribution — it ends on an emitter or on the sky — so the class of a path is the class of its whole acc, and layers partition the
+ * film's integer sums exactly.
+ *
+ * Tags.  A tracker keeps two 32-bit words per path id, `sig` and `term`, in a table of `capacity` entries.  A bounce's event code (4
+ * bits) is a function of its vk_shaded record's status and lobe as the compaction's count pass leaves them (a roulette cull shows as
+ * VK_PATHS_CULLED and keeps its lobe):
+ *     VK_SHADE_MISS                          1   VK_LPE_SKY
+ *     VK_SHADE_BAD_HIT                      15   VK_LPE_BAD
+ *     any other status, lobe 0 .. 5   2 + lobe   2 Lambertian, 3 Metal, 4 Dielectric, 5 DiffuseLight (VK_LPE_EMIT), 6 Isotropic,
+ *                                                7 SpecDiffuse
+ *     any other status, any other lobe      14   VK_LPE_OTHER
+ * and 0 means "no bounce recorded".  For bounce number b of the batch (vk_paths_info.bounces before the bounce; the first is 0) every
+ * item of the bounce has its tag updated: b == 0: sig = code | code << 28; otherwise nibble b becomes the code if b < 7, and nibble 7
+ * becomes the code whatever b is.  term = the hit record's material where hit == 1, else 0xFFFFFFFF.  So nibbles 0 .. 6 are the first
+ * seven bounces, and nibble 7 and term describe the last bounce the path took part in.  A started id no bounce has touched since the
+ * tracker was bound has sig 0 and term 0.
+ *
+ * vk_lpe_step is vk_paths_step with one more launch per bounce (kernel_launches counts six a bounce): lpe_record_kernel, behind the
+ * compaction, on the bounce's records, hits and ids.  It launches what vk_paths_step launches, the handle's roulette rule included:
+ * after every bounce vk_paths_read and vk_paths_results are byte for byte vk_paths_step's.  A step on a batch whose bounces == 0 BINDS
+ * the tracker to that batch and that begin (vk_paths_begin or vk_film_emit); every later call checks the binding.  vk_paths_cull
+ * between steps is allowed: a path culled by it keeps the tag of its last recorded bounce.  vk_lpe_tags returns the tags of the
+ * started ids (either pointer may be NULL) and waits.
+ *
+ * Rules and layers.  A result — status, state.depth and the id's tag — matches a rule when (sig & sig_mask) == sig_value, and
+ * status_mask >> status & 1, and depth_min <= state.depth <= depth_max, and emitter == 0xFFFFFFFF or emitter == term.  The first
+ * matching rule gives the layer; without one the layer is rest_layer.
+ *
+ * State.  Per pixel and layer four 64-bit two's-complement words — the sums of r, g, b in 2^-26 units and a count —, width * height *
+ * n_layers * 32 bytes, 8 bytes per id of the tag table and one record of counters (8 KiB), on the scene's device (devices[0] of a
+ * multi-device scene).  All work is on the null stream there; no function takes a stream.
+ *
+ * Deposit.  Placement, drop, skip, clamp and the counters are vk_film_deposit's rule exactly, as vk_robust_deposit restates it; the
+ * target cell is (state.pixel, layer).  A deposited result adds its three fixed values and 1 to the count, a dropped one 1 to the
+ * count only.  The batch carries a flag of its own next to the film's, the splat accumulator's and the robust accumulator's, cleared
+ * where those are: one batch goes once each into a film, a splat, a robust and a layer accumulator, in any order.
+ *
+ * Resolve.  rgb_c = ((float)sum_c * 2^-26) / (float)n per channel, in vk_render's f32 layout (y = 0 the bottom row); share_out (may be
+ * NULL, one float per pixel) = (float)count / (float)n.  layer == VK_LPE_ALL adds the layers' integer sums first (64-bit, wrapping).
+ *
+ * Contract.  (1) vk_lpe_tags equals the tags tests/lpe_ref.py derives from every bounce's records of the CPU emulation, bit for bit.
+ * (2) The state is a function of the set of deposited results and their tags alone and equals that restatement; summed over the layers
+ * the colour sums are vk_film_deposit's, the counts the samples, the counters the film's.  (3) VK_LPE_ALL on a frame in which every
+ * (pixel, sample) below n went in once is vk_film_resolve(film, n): vk_render's frame bit for bit wherever the film's contract holds.
+ * What this is not.  Regenerating runs are refused: their results are not kept and their ids are not bounded by a capacity.  A
+ * multi-device scene uses devices[0] only.  No function takes a stream.  Nothing the integrator samples changes: a layer is a
+ * classification of the samples vk_paths_step draws, not a different estimator (light groups split by the emitter that was HIT).
+ *
+ *   vk_lpe_create: VK_ERR_BAD_ARG for a null pointer, width or height 0, n_layers outside 1..16, width * height * n_layers > 2^27,
+ *     samples_per_pixel outside 1..2^26, capacity outside 1..2^24, rest_layer >= n_layers, n_rules > 32, n_rules > 0 with null rules, a
+ *     non-zero _pad, and a rule with sig_value & ~sig_mask non-zero, a status_mask that is 0 or has a bit other than MISS, ENDED and
+ *     CULLED (1 << status), depth_min > depth_max, layer >= n_layers or a non-zero _pad.  The rules are copied.  VK_ERR_OOM leaves *out
+ *     untouched.
+ *   vk_lpe_step: VK_ERR_BAD_ARG, nothing enqueued: a null pointer, a batch of another scene, one never begun, a regenerating one,
+ *     started > capacity, max_bounces == 0, a batch with bounces > 0 the tracker is not bound to, or whose bounces differ from the
+ *     bounces the tracker recorded (a vk_paths_step in between).
+ *   vk_lpe_tags: refused for a batch the tracker is not bound to.
+ *   vk_lpe_deposit: VK_ERR_BAD_ARG, nothing enqueued or written: what vk_robust_deposit refuses (the flag being this accumulator's
+ *     kind), started > capacity, a batch the tracker is not bound to, a batch whose bounces were not all recorded.
+ *   vk_lpe_resolve: VK_ERR_BAD_ARG for a null tracker or rgb_out, a layer that is neither below n_layers nor VK_LPE_ALL, n == 0.
+ *   vk_lpe_reset zeroes sums and counters (not the tags or the binding).  vk_lpe_get_info waits.  vk_lpe_destroy(NULL) does nothing.
+ *   Destroy a tracker before its scene.                                                                                              */
+enum { VK_LPE_SKY = 1, VK_LPE_EMIT = 5, VK_LPE_OTHER = 14, VK_LPE_BAD = 15 };
+#define VK_LPE_ALL 0xFFFFFFFFu
+typedef struct vk_lpe vk_lpe;            /* opaque */
+typedef struct vk_lpe_rule {             /* 32 bytes */
+    uint32_t sig_mask, sig_value;        /* (sig & sig_mask) == sig_value */
+    uint32_t status_mask;                /* bit VK_SHADE_MISS, VK_SHADE_ENDED, VK_PATHS_CULLED */
+    uint32_t depth_min, depth_max;       /* of state.depth, inclusive */
+    uint32_t emitter;                    /* 0xFFFFFFFF: any; else term must equal it */
+    uint32_t layer;
+    uint32_t _pad;                       /* 0 */
+} vk_lpe_rule;
+typedef struct vk_lpe_params {           /* 24 bytes */
+    uint32_t n_layers;                   /* 1 .. 16 */
+    uint32_t rest_layer;
+    uint32_t n_rules;                    /* 0 .. 32 */
+    uint32_t _pad;                       /* 0 */
+    const vk_lpe_rule *rules;
+} vk_lpe_params;
+typedef struct vk_lpe_info {             /* 80 bytes */
+    uint32_t width, height, samples_per_pixel, n_layers, rest_layer, n_rules;
+    uint64_t capacity;
+    uint64_t deposited, dropped, clamped, skipped, deposits, recorded;      /* deposits: accepted calls; recorded: path-bounces */
+} vk_lpe_info;
+int vk_lpe_create(vk_scene *scene, uint32_t width, uint32_t height, uint32_t samples_per_pixel, uint64_t capacity,
+                  const vk_lpe_params *lp, vk_lpe **out);
+int vk_lpe_step(vk_lpe *s, vk_paths *batch, uint32_t max_bounces, vk_paths_step_info *info);
+int vk_lpe_tags(vk_lpe *s, vk_paths *batch, uint32_t *sig, uint32_t *term);
+int vk_lpe_deposit(vk_lpe *s, vk_paths *batch);
+int vk_lpe_resolve(vk_lpe *s, uint32_t layer, uint32_t n, float *rgb_out, float *share_out);
+int vk_lpe_reset(vk_lpe *s);
+int vk_lpe_get_info(vk_lpe *s, vk_lpe_info *out);
+void vk_lpe_destroy(vk_lpe *s);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

@@ -175,6 +175,19 @@ int vk_debug_robust_sums(vk_robust *s, int64_t *out);
  * libraries. */
 int vk_debug_robust_last_ms(vk_robust *s, double ms[2]);
 
+/* a layer accumulator's raw state: width * height * n_layers * 4 two's-complement 64-bit values in the order [(pixel * n_layers + l) * 4
+ * + c], pixel = y * width + x, c = r, g, b (2^-26 units), count.  Waits.  VK_ERR_BAD_ARG for a null pointer.  Takes no stream.  In both
+ * libraries. */
+int vk_debug_lpe_sums(vk_lpe *s, int64_t *out);
+/* uploads sig[i] and term[i] as the tag of id i for the batch's started ids and binds the tracker to the batch as if it had recorded
+ * every bounce the batch has run: the deposit can then be tested on injected results and tags.  vk_lpe_step's checks of the batch but
+ * the binding's; null sig or term with started paths is VK_ERR_BAD_ARG.  Waits.  Takes no stream.  In both libraries. */
+int vk_debug_lpe_set_tags(vk_lpe *s, vk_paths *batch, const uint32_t *sig, const uint32_t *term);
+/* the device milliseconds of the tracker's last lpe_record_kernel launch (ms[0]), vk_lpe_deposit (ms[1]) and vk_lpe_resolve (ms[2]: the
+ * kernel without the copies to the host), between two events around each; 0 for one that has not run.  Waits for those.  Takes no
+ * stream.  In both libraries. */
+int vk_debug_lpe_last_ms(vk_lpe *s, double ms[3]);
+
 /* the id of every sample vk_render_mattes would count, by the same per-lane code on the same lanes: ids_out[(y * width + x) * spp + k] is
  * the id of sample first_sample + k under `kind` (VK_MATTE_OBJECT or VK_MATTE_MATERIAL), spp = params->samples_per_pixel; pixels outside
  * the call's tile partition are left untouched.  vk_render_mattes' checks.  Waits.  In both libraries. */

@@ -76,7 +76,7 @@ def _device_deps():
     srcs = [os.path.join(CSRC, "vk_api.hip"), os.path.join(CSRC, "vk_linearize.cpp")]
     return srcs, srcs + [os.path.join(CSRC, f) for f in ("vk_kernels.h", "vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_resources.h",
                                                          "vk_emit.h", "vk_adapt.h", "vk_adapt.hip", "vk_splat.h", "vk_splat.hip", "vk_matte.h",
-                                                         "vk_matte.hip", "vk_robust.h", "vk_robust.hip")] + \
+                                                         "vk_matte.hip", "vk_robust.h", "vk_robust.hip", "vk_lpe.h", "vk_lpe.hip")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
 
 
@@ -87,7 +87,8 @@ def host_is_stale():
 def device_is_stale():
     return _newer(os.path.join(LIB, "libvecchio_amd.so"), _device_deps()[1], HIPFLAGS) or not os.path.exists(kernel_resources_path()) or \
         not os.path.exists(kernel_resources_adapt_path()) or not os.path.exists(kernel_resources_splat_path()) or \
-        not os.path.exists(kernel_resources_matte_path()) or not os.path.exists(kernel_resources_robust_path())
+        not os.path.exists(kernel_resources_matte_path()) or not os.path.exists(kernel_resources_robust_path()) or \
+        not os.path.exists(kernel_resources_lpe_path())
 
 
 def build_host(force=False):
@@ -122,7 +123,7 @@ def build_device_debug(force=False):
     flags = HIPFLAGS + ["-DVK_DEBUG_LIB"]
     if force or _newer(out, deps, flags):
         os.makedirs(LIB, exist_ok=True)
-        _run_atomic([HIPCC] + flags + ["-shared", "-o"], out, srcs + [_adapt_src(), _splat_src(), _matte_src(), _robust_src()])
+        _run_atomic([HIPCC] + flags + ["-shared", "-o"], out, srcs + [_adapt_src(), _splat_src(), _matte_src(), _robust_src(), _lpe_src()])
         _stamp(out, deps, flags)
     return out
 
@@ -149,6 +150,12 @@ def _matte_src():
 def _robust_src():
     """the kernels of vk_robust_* (robust film: the bucketed deposit of a path batch and its trimmed resolve): a translation unit of its own"""
     return os.path.join(CSRC, "vk_robust.hip")
+
+
+def _lpe_src():
+    """the kernels of vk_lpe_* (light-path layers: a path's tag per bounce, the layered deposit of a path batch and a layer's resolve): a
+    translation unit of its own"""
+    return os.path.join(CSRC, "vk_lpe.hip")
 
 
 def _hipcc_with_remarks(cmd, cwd, cleanup=()):
@@ -185,9 +192,9 @@ def _write_resources(path, remarks, spills):
 
 
 def build_device(force=False):
-    """hipcc cross-compiles for gfx950 without a GPU present.  Five steps: vk_adapt.hip, vk_splat.hip, vk_matte.hip and vk_robust.hip to an
-    object of their own each (their resource remarks go to kernel_resources_adapt.txt, kernel_resources_splat.txt,
-    kernel_resources_matte.txt and kernel_resources_robust.txt), then vk_api.hip and vk_linearize.cpp, linked with those objects (kernel_resources.txt: theirs alone)."""
+    """hipcc cross-compiles for gfx950 without a GPU present.  Six steps: vk_adapt.hip, vk_splat.hip, vk_matte.hip, vk_robust.hip and
+    vk_lpe.hip to an object of their own each (their resource remarks go to kernel_resources_adapt.txt, kernel_resources_splat.txt,
+    kernel_resources_matte.txt, kernel_resources_robust.txt and kernel_resources_lpe.txt), then vk_api.hip and vk_linearize.cpp, linked with those objects (kernel_resources.txt: theirs alone)."""
     out = os.path.join(LIB, "libvecchio_amd.so")
     srcs, deps = _device_deps()
     if force or device_is_stale():
@@ -202,6 +209,8 @@ def build_device(force=False):
             os.makedirs(tmp_splat)
             os.makedirs(tmp_matte)
             os.makedirs(tmp_robust)
+            tmp_lpe = os.path.join(tmp, "lpe")
+            os.makedirs(tmp_lpe)
             os.makedirs(tmp_main)
             adapt_obj = os.path.join(tmp_adapt, "vk_adapt.o")
             adapt = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", adapt_obj, _adapt_src()], tmp_adapt)
@@ -211,15 +220,18 @@ def build_device(force=False):
             matte = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", matte_obj, _matte_src()], tmp_matte)
             robust_obj = os.path.join(tmp_robust, "vk_robust.o")
             robust = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", robust_obj, _robust_src()], tmp_robust)
+            lpe_obj = os.path.join(tmp_lpe, "vk_lpe.o")
+            lpe = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", lpe_obj, _lpe_src()], tmp_lpe)
             tmp_out = f"{out}.tmp.{os.getpid()}"
             # (the objects in front of the sources: hipcc reads whatever follows a source file as HIP)
-            main = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-shared", "-o", tmp_out, adapt_obj, splat_obj, matte_obj, robust_obj] + srcs, tmp_main, [tmp_out])
+            main = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-shared", "-o", tmp_out, adapt_obj, splat_obj, matte_obj, robust_obj, lpe_obj] + srcs, tmp_main, [tmp_out])
             os.replace(tmp_out, out)
         _write_resources(kernel_resources_path(), *main)
         _write_resources(kernel_resources_adapt_path(), *adapt)
         _write_resources(kernel_resources_splat_path(), *splat)
         _write_resources(kernel_resources_matte_path(), *matte)
         _write_resources(kernel_resources_robust_path(), *robust)
+        _write_resources(kernel_resources_lpe_path(), *lpe)
         _stamp(out, deps, HIPFLAGS)
     return out
 
@@ -256,6 +268,11 @@ def kernel_resources_robust_path():
     return os.path.join(LIB, "kernel_resources_robust.txt")
 
 
+def kernel_resources_lpe_path():
+    """the same record for the kernels of vk_lpe.hip"""
+    return os.path.join(LIB, "kernel_resources_lpe.txt")
+
+
 def build_oracle(force=False):
     """CPU oracle (test infrastructure).  oracle/_ref does not exist: the reference is Rust and
     there is no cargo/rustc in this image."""
@@ -278,10 +295,11 @@ def build_emu(force=False):
             os.path.join(edir, "emu_irradiance.cpp"), os.path.join(edir, "emu_probes.cpp"), os.path.join(edir, "emu_shade.cpp"),
             os.path.join(edir, "emu_paths.cpp"), os.path.join(edir, "emu_film.cpp"), os.path.join(edir, "emu_adapt.cpp"),
             os.path.join(edir, "emu_splat.cpp"), os.path.join(edir, "emu_matte.cpp"), os.path.join(edir, "emu_robust.cpp"),
+            os.path.join(edir, "emu_lpe.cpp"),
             os.path.join(CSRC, "vk_linearize.cpp")]
     # (the tool's own headers: whichever are there)
     deps = srcs + sorted(os.path.join(edir, f) for f in os.listdir(edir) if f.endswith(".h")) + \
-        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_adapt.h", "vk_splat.h", "vk_matte.h", "vk_robust.h")] + \
+        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_adapt.h", "vk_splat.h", "vk_matte.h", "vk_robust.h", "vk_lpe.h")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
     if force or _newer(out, deps, CXXFLAGS):
         os.makedirs(os.path.dirname(out), exist_ok=True)

@@ -54,6 +54,7 @@
 #include "vk_adapt.h"        // the kernels of vk_adapt.hip: argument records and launchers
 #include "vk_splat.h"        // the kernels of vk_splat.hip: the filter, argument records and launchers
 #include "vk_robust.h"       // the kernels of vk_robust.hip: the per-pixel resolve, argument records and launchers
+#include "vk_lpe.h"          // the kernels of vk_lpe.hip: the tag, the rule match, argument records and launchers
 #include "vk_matte.h"        // the kernels of vk_matte.hip: the table of a pixel, the argument record and launchers
 
 namespace {
@@ -2668,6 +2669,8 @@ struct vk_paths {
     bool deposited = false;                         // vk_film_deposit has taken this batch (cleared by vk_paths_begin and vk_film_emit)
     bool splatted = false;                          // vk_splat_deposit has taken this batch (cleared where `deposited` is)
     bool bucketed = false;                          // vk_robust_deposit has taken this batch (cleared where `deposited` is)
+    bool layered = false;                           // vk_lpe_deposit has taken this batch (cleared where `deposited` is)
+    uint64_t begins = 0;                            // host only: the begins, emits and regen begins so far (a vk_lpe tracker binds to one)
     uint32_t cur = 0;                               // ids[cur] holds the live ids
     uint64_t started = 0, live = 0, retired[5] = {0, 0, 0, 0, 0};
     uint32_t bounces = 0;
@@ -2792,7 +2795,7 @@ int paths_take_counts(vk_paths *p, unsigned long long c[5]) {
 // a batch as a begin leaves it: `started` paths of which `live` are live, nothing retired, no bounce run, not regenerating.  Called behind
 // every check and every launch of a begin that can fail: a refused call leaves the batch as it was.
 void paths_reset(vk_paths *p, const vk_shade_params &sp, uint64_t started, uint64_t live) {
-    p->sp = sp; p->begun = true; p->deposited = false; p->splatted = false; p->bucketed = false; p->cur = 0u; p->started = started; p->live = live; p->bounces = 0u;
+    p->sp = sp; p->begun = true; p->deposited = false; p->splatted = false; p->bucketed = false; p->layered = false; p->begins++; p->cur = 0u; p->started = started; p->live = live; p->bounces = 0u;
     for (uint64_t &r : p->retired) r = 0u;
     p->regen = false; p->regen_film = nullptr; p->regen_win = vk_film_window{}; p->regen_next = 0u; p->regen_total = 0u;
     p->regen_tiles = false; p->regen_first_sample = 0u; p->regen_n_samples = 0u;
@@ -4171,6 +4174,335 @@ int vk_debug_robust_last_ms(vk_robust *s, double ms[2]) {
             got[k] = (double)t;
         }
         for (int k = 0; k < 2; k++) ms[k] = got[k];
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- light-path layers (vk_lpe_*): a tag per path id, kept up to date by lpe_record_kernel behind every bounce of vk_lpe_step, and a
+// frame's fixed-point sums kept per pixel and layer — lpe_deposit_kernel adds a finished batch by the class of each result,
+// lpe_resolve_kernel divides (vk_lpe.hip); all on the null stream of the scene's device (devices[0] of a multi-device scene), on buffers
+// and events the handle owns.  Of the batch a step runs paths_bounce as vk_paths_step does and reads the bounce's records, hits and
+// ids; a deposit reads its results and sets its `layered` flag.  Nothing of the scene handle is read but its device.
+struct vk_lpe {
+    vk_scene *scene = nullptr;                      // as handed to vk_lpe_create
+    uint32_t width = 0, height = 0, spp = 0;
+    uint64_t capacity = 0;
+    uint32_t n_layers = 0, rest_layer = 0, n_rules = 0;
+    LpeRule rules[LPE_MAX_RULES] = {};
+    float accum_clamp = 0.0f;
+    DeviceBuffer<uint32_t> tags;                    // [capacity][2]: sig, term
+    DeviceBuffer<unsigned long long> sums;          // [width * height][n_layers][4], two's complement
+    DeviceBuffer<unsigned long long> counters;      // deposited, dropped, clamped, skipped, in SPLAT_STRIPES stripes
+    DeviceBuffer<float> out;                        // the resolved layer and its share on their way to the host (first resolve)
+    Event ev[8];                                    // around the last record, deposit and resolve; [6], [7]: the record before the last
+    bool timed[3] = {false, false, false};
+    int rec_pair = 0;                               // the last record's events: ev[0], ev[1] (0) or ev[6], ev[7] (1)
+    uint64_t deposits = 0, recorded = 0;            // accepted deposits; path-bounces recorded
+    // the binding: the batch and the begin the tags describe, and how many of its bounces they hold (host state only)
+    const vk_paths *bound = nullptr;                // for the identity check only
+    uint64_t bound_begin = 0;
+    uint32_t bound_bounces = 0;
+};
+
+namespace {
+
+void lpe_free(vk_lpe *s) {
+    (void)hipSetDevice(first_part(s->scene)->device);
+    (void)hipStreamSynchronize(nullptr);              // (a record or a deposit may still run)
+    (void)hipGetLastError();
+    delete s;
+}
+
+size_t lpe_words(const vk_lpe *s) { return (size_t)s->width * s->height * s->n_layers * 4u; }
+
+int lpe_zero(vk_lpe *s) {
+    HIP_TRY(hipMemsetAsync(s->sums, 0, lpe_words(s) * sizeof(unsigned long long), nullptr));
+    HIP_TRY(hipMemsetAsync(s->counters, 0, SPLAT_COUNTER_BYTES, nullptr));
+    s->deposits = 0u;
+    return VK_OK;
+}
+
+const char *lpe_rule_refusal(const vk_lpe_rule &r, uint32_t n_layers) {
+    if ((r.sig_value & ~r.sig_mask) != 0u) return "a rule's sig_value has bits outside its sig_mask";
+    if (r.status_mask == 0u || (r.status_mask & ~LPE_STATUS_BITS) != 0u) return "a rule's status_mask must name MISS, ENDED or CULLED and nothing else";
+    if (r.depth_min > r.depth_max) return "a rule's depth_min exceeds its depth_max";
+    if (r.layer >= n_layers) return "a rule's layer is not below n_layers";
+    if (r._pad != 0u) return "a rule's _pad must be 0";
+    return nullptr;
+}
+
+bool lpe_bound_to(const vk_lpe *s, const vk_paths *batch) { return s->bound == batch && s->bound_begin == batch->begins; }
+
+// what vk_lpe_step, vk_lpe_tags, vk_lpe_deposit and vk_debug_lpe_set_tags ask of any batch (nullptr: fine)
+const char *lpe_batch_refusal(const vk_lpe *s, const vk_paths *batch, const char *who) {
+    static thread_local std::string words;
+    if (batch->scene != s->scene) words = "the path batch belongs to another scene than the tracker";
+    else if (!batch->begun) words = std::string(who) + " before vk_paths_begin or vk_film_emit";
+    else if (batch->regen) words = std::string(who) + " on a regenerating path batch (its results are not kept)";
+    else if (batch->started > s->capacity) words = "the path batch has started more paths than the tracker's capacity";
+    else return nullptr;
+    return words.c_str();
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_lpe_create(vk_scene *scene, uint32_t width, uint32_t height, uint32_t samples_per_pixel, uint64_t capacity, const vk_lpe_params *lp,
+                  vk_lpe **out) {
+    if (!scene || !lp || !out) return fail(VK_ERR_BAD_ARG, "null argument (scene, params or out)");
+    if (width == 0u || height == 0u) return fail(VK_ERR_BAD_ARG, "width and height must be >= 1");
+    if (lp->n_layers < 1u || lp->n_layers > LPE_MAX_LAYERS) return fail(VK_ERR_BAD_ARG, "n_layers must be in 1..16");
+    // (width * height < 2^64, and the product with n_layers is taken only once that is below 2^27)
+    if ((uint64_t)width * height > LPE_MAX_CELLS || (uint64_t)width * height * lp->n_layers > LPE_MAX_CELLS)
+        return fail(VK_ERR_BAD_ARG, "width * height * n_layers exceeds 2^27");
+    if (samples_per_pixel == 0u || samples_per_pixel > (1u << 26)) return fail(VK_ERR_BAD_ARG, "samples_per_pixel must be in 1..2^26");
+    if (capacity < 1u || capacity > PATHS_MAX) return fail(VK_ERR_BAD_ARG, "capacity must be in 1..2^24");
+    if (lp->rest_layer >= lp->n_layers) return fail(VK_ERR_BAD_ARG, "rest_layer is not below n_layers");
+    if (lp->n_rules > LPE_MAX_RULES) return fail(VK_ERR_BAD_ARG, "n_rules must be in 0..32");
+    if (lp->n_rules > 0u && !lp->rules) return fail(VK_ERR_BAD_ARG, "null rules with n_rules > 0");
+    if (lp->_pad != 0u) return fail(VK_ERR_BAD_ARG, "_pad must be 0");
+    for (uint32_t k = 0; k < lp->n_rules; k++)
+        if (const char *why = lpe_rule_refusal(lp->rules[k], lp->n_layers)) return fail(VK_ERR_BAD_ARG, why);
+    return guarded([&]() -> int {
+        std::unique_ptr<vk_lpe, void (*)(vk_lpe *)> s(new vk_lpe(), lpe_free);
+        s->scene = scene; s->width = width; s->height = height; s->spp = samples_per_pixel; s->capacity = capacity;
+        s->n_layers = lp->n_layers; s->rest_layer = lp->rest_layer; s->n_rules = lp->n_rules;
+        static_assert(sizeof(LpeRule) == sizeof(vk_lpe_rule), "one rule, two names");
+        for (uint32_t k = 0; k < lp->n_rules; k++) memcpy(&s->rules[k], &lp->rules[k], sizeof(LpeRule));
+        s->accum_clamp = accum_clamp_for(samples_per_pixel);
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        int r = VK_OK;
+        handle_alloc(r, s->tags, (size_t)capacity * 8u);
+        handle_alloc(r, s->sums, lpe_words(s.get()) * sizeof(unsigned long long));
+        handle_alloc(r, s->counters, SPLAT_COUNTER_BYTES);
+        if (r != VK_OK) return r;
+        for (Event &e : s->ev) if ((r = e.create()) != VK_OK) return r;
+        HIP_TRY(hipMemsetAsync(s->tags, 0, (size_t)capacity * 8u, nullptr));
+        if ((r = lpe_zero(s.get())) != VK_OK) return r;
+        *out = s.release();
+        return VK_OK;
+    });
+}
+
+int vk_lpe_step(vk_lpe *s, vk_paths *p, uint32_t max_bounces, vk_paths_step_info *info) {
+    return guarded([&]() -> int {
+        if (!s || !p) return fail(VK_ERR_BAD_ARG, "null argument (tracker or path batch)");
+        if (const char *why = lpe_batch_refusal(s, p, "vk_lpe_step")) return fail(VK_ERR_BAD_ARG, why);
+        if (max_bounces == 0u) return fail(VK_ERR_BAD_ARG, "max_bounces must be >= 1");
+        if (p->bounces != 0u) {
+            if (!lpe_bound_to(s, p)) return fail(VK_ERR_BAD_ARG, "the path batch has run bounces and the tracker is not bound to it (bind with a step at bounce 0)");
+            if (s->bound_bounces != p->bounces) return fail(VK_ERR_BAD_ARG, "the path batch has run bounces the tracker did not record (vk_paths_step in between)");
+        }
+        const auto t0 = std::chrono::steady_clock::now();
+        vk_scene *q = first_part(p->scene);
+        HIP_TRY(hipSetDevice(q->device));
+        if (p->bounces == 0u) {
+            // bind: the tags of this begin's ids start as "no bounce recorded"
+            if (p->started != 0u) HIP_TRY(hipMemsetAsync(s->tags, 0, (size_t)p->started * 8u, nullptr));
+            s->bound = p; s->bound_begin = p->begins; s->bound_bounces = 0u;
+        }
+        BounceTally T{};
+        // a record's time is read behind the NEXT bounce's counts, which have waited for it: two pairs of events take turns, and only
+        // the last record of the call is waited for
+        bool pending = false;
+        const auto record_ms = [&](int pair, double &ms_out) -> int {
+            float ms = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&ms, s->ev[pair ? 6 : 0], s->ev[pair ? 7 : 1]));
+            ms_out += (double)ms;
+            return VK_OK;
+        };
+        while (p->live != 0u && T.bounces < max_bounces) {
+            const uint64_t n = p->live;
+            const uint32_t bounce = p->bounces;
+            HIP_TRY(hipEventRecord(p->ev0, nullptr));
+            int rc = paths_bounce(p, q, nullptr, T);
+            if (rc != VK_OK) return rc;
+            if (pending && (rc = record_ms(s->rec_pair, T.kernel_ms)) != VK_OK) return rc;
+            // the bounce's records, hits and ids are where the compaction read them: shaded[0, n), hits[0, n), ids[cur ^ 1][0, n)
+            LpeRecordArgs A;
+            memset(&A, 0, sizeof(A));
+            A.shaded = reinterpret_cast<const uint4 *>(p->shaded.get()); A.hits = reinterpret_cast<const uint4 *>(p->hits.get());
+            A.ids = p->ids[p->cur ^ 1u]; A.tags = reinterpret_cast<uint2 *>(s->tags.get());
+            A.n = (uint32_t)n; A.capacity = (uint32_t)s->capacity; A.bounce = bounce;
+            const int pair = pending ? s->rec_pair ^ 1 : 0;
+            HIP_TRY(hipEventRecord(s->ev[pair ? 6 : 0], nullptr));
+            launch_lpe_record(A);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(s->ev[pair ? 7 : 1], nullptr));
+            s->rec_pair = pair; pending = true; s->timed[0] = true;
+            T.launches++;
+            s->bound_bounces = p->bounces;
+            s->recorded += n;
+        }
+        if (pending) {
+            HIP_TRY(hipEventSynchronize(s->ev[s->rec_pair ? 7 : 1]));
+            int rc = record_ms(s->rec_pair, T.kernel_ms);
+            if (rc != VK_OK) return rc;
+        }
+        vk_paths_step_info I;
+        memset(&I, 0, sizeof(I));
+        I.traced = T.traced; I.missed = T.missed; I.ended = T.ended; I.bad = T.bad;
+        I.bounces = T.bounces; I.kernel_launches = T.launches; I.kernel_ms = T.kernel_ms;
+        I.live = p->live;
+        I.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (info) *info = I;
+        return VK_OK;
+    });
+}
+
+int vk_lpe_tags(vk_lpe *s, vk_paths *p, uint32_t *sig, uint32_t *term) {
+    return guarded([&]() -> int {
+        if (!s || !p) return fail(VK_ERR_BAD_ARG, "null argument (tracker or path batch)");
+        if (const char *why = lpe_batch_refusal(s, p, "vk_lpe_tags")) return fail(VK_ERR_BAD_ARG, why);
+        if (!lpe_bound_to(s, p)) return fail(VK_ERR_BAD_ARG, "the tracker is not bound to the path batch");
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        const size_t n = (size_t)p->started;
+        if (n == 0u || (!sig && !term)) { HIP_TRY(hipStreamSynchronize(nullptr)); return VK_OK; }
+        std::vector<uint32_t> both(2u * n);
+        HIP_TRY(hipMemcpy(both.data(), s->tags, n * 8u, hipMemcpyDeviceToHost));      // (waits for the null stream)
+        for (size_t i = 0; i < n; i++) {
+            if (sig) sig[i] = both[2u * i];
+            if (term) term[i] = both[2u * i + 1u];
+        }
+        return VK_OK;
+    });
+}
+
+int vk_lpe_deposit(vk_lpe *s, vk_paths *batch) {
+    return guarded([&]() -> int {
+        if (!s || !batch) return fail(VK_ERR_BAD_ARG, "null argument (tracker or path batch)");
+        if (const char *why = lpe_batch_refusal(s, batch, "vk_lpe_deposit")) return fail(VK_ERR_BAD_ARG, why);
+        if (batch->live != 0u) return fail(VK_ERR_BAD_ARG, "the path batch has live paths (step or cull them first)");
+        if (batch->layered) return fail(VK_ERR_BAD_ARG, "the path batch has been deposited into a layer accumulator since its last begin or emit");
+        if (!lpe_bound_to(s, batch)) return fail(VK_ERR_BAD_ARG, "the tracker is not bound to the path batch");
+        if (s->bound_bounces != batch->bounces) return fail(VK_ERR_BAD_ARG, "the path batch has run bounces the tracker did not record (vk_paths_step in between)");
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        const uint64_t n = batch->started;
+        HIP_TRY(hipEventRecord(s->ev[2], nullptr));
+        if (n != 0u) {
+            LpeDepositArgs A;
+            memset(&A, 0, sizeof(A));
+            A.result_state = reinterpret_cast<const uint4 *>(batch->result_state.get()); A.result_status = batch->result_status;
+            A.tags = reinterpret_cast<const uint2 *>(s->tags.get());
+            A.sums = s->sums; A.counters = s->counters;
+            A.n = (uint32_t)n; A.n_pixels = s->width * s->height; A.n_layers = s->n_layers; A.rest_layer = s->rest_layer; A.n_rules = s->n_rules;
+            A.accum_clamp = s->accum_clamp;
+            for (uint32_t k = 0; k < s->n_rules; k++) A.rules[k] = s->rules[k];
+            launch_lpe_deposit(A);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipEventRecord(s->ev[3], nullptr));
+        s->timed[1] = true;
+        s->deposits++;
+        batch->layered = true;
+        return VK_OK;
+    });
+}
+
+int vk_lpe_resolve(vk_lpe *s, uint32_t layer, uint32_t n, float *rgb_out, float *share_out) {
+    return guarded([&]() -> int {
+        if (!s || !rgb_out) return fail(VK_ERR_BAD_ARG, "null argument (tracker or rgb_out)");
+        if (layer != VK_LPE_ALL && layer >= s->n_layers) return fail(VK_ERR_BAD_ARG, "layer must be below n_layers or VK_LPE_ALL");
+        if (n == 0u) return fail(VK_ERR_BAD_ARG, "n must be >= 1");
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        const size_t px = (size_t)s->width * s->height;
+        if (!s->out) {
+            int rc = VK_OK;
+            handle_alloc(rc, s->out, 4u * px * sizeof(float));
+            if (rc != VK_OK) return rc;
+        }
+        LpeResolveArgs A;
+        memset(&A, 0, sizeof(A));
+        A.sums = reinterpret_cast<const long long *>(s->sums.get()); A.rgb = s->out; A.share = share_out ? s->out.get() + 3u * px : nullptr;
+        A.n_pixels = (uint32_t)px; A.n_layers = s->n_layers; A.layer = layer; A.n = (float)n;
+        HIP_TRY(hipEventRecord(s->ev[4], nullptr));
+        launch_lpe_resolve(A);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(s->ev[5], nullptr));
+        s->timed[2] = true;
+        HIP_TRY(hipMemcpy(rgb_out, s->out, 3u * px * sizeof(float), hipMemcpyDeviceToHost));
+        if (share_out) HIP_TRY(hipMemcpy(share_out, s->out.get() + 3u * px, px * sizeof(float), hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+int vk_lpe_reset(vk_lpe *s) {
+    if (!s) return fail(VK_ERR_BAD_ARG, "null tracker");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        return lpe_zero(s);
+    });
+}
+
+int vk_lpe_get_info(vk_lpe *s, vk_lpe_info *out) {
+    if (!s || !out) return fail(VK_ERR_BAD_ARG, "null argument (tracker or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        std::vector<unsigned long long> stripes((size_t)SPLAT_STRIPES * SPLAT_STRIPE_WORDS);
+        HIP_TRY(hipMemcpy(stripes.data(), s->counters, SPLAT_COUNTER_BYTES, hipMemcpyDeviceToHost));      // (waits for the null stream)
+        unsigned long long c[LPE_COUNTERS] = {0ull, 0ull, 0ull, 0ull};
+        for (uint32_t k = 0; k < SPLAT_STRIPES; k++)
+            for (uint32_t j = 0; j < LPE_COUNTERS; j++) c[j] += stripes[(size_t)k * SPLAT_STRIPE_WORDS + j];
+        memset(out, 0, sizeof(*out));
+        out->width = s->width; out->height = s->height; out->samples_per_pixel = s->spp; out->n_layers = s->n_layers;
+        out->rest_layer = s->rest_layer; out->n_rules = s->n_rules; out->capacity = s->capacity;
+        out->deposited = c[0]; out->dropped = c[1]; out->clamped = c[2]; out->skipped = c[3];
+        out->deposits = s->deposits; out->recorded = s->recorded;
+        return VK_OK;
+    });
+}
+
+void vk_lpe_destroy(vk_lpe *s) {
+    if (s) lpe_free(s);
+}
+
+// test hook (vecchio_amd_debug.h): the raw state, [(pixel * n_layers + l) * 4 + c] — the device's own layout
+int vk_debug_lpe_sums(vk_lpe *s, int64_t *out) {
+    if (!s || !out) return fail(VK_ERR_BAD_ARG, "null argument (tracker or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        HIP_TRY(hipMemcpy(out, s->sums, lpe_words(s) * sizeof(int64_t), hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): the tags of the batch's started ids from the host, and the tracker bound to the batch as if it had
+// recorded every bounce the batch has run
+int vk_debug_lpe_set_tags(vk_lpe *s, vk_paths *batch, const uint32_t *sig, const uint32_t *term) {
+    return guarded([&]() -> int {
+        if (!s || !batch) return fail(VK_ERR_BAD_ARG, "null argument (tracker or path batch)");
+        if (const char *why = lpe_batch_refusal(s, batch, "vk_debug_lpe_set_tags")) return fail(VK_ERR_BAD_ARG, why);
+        const size_t n = (size_t)batch->started;
+        if (n != 0u && (!sig || !term)) return fail(VK_ERR_BAD_ARG, "null sig or term with started paths");
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        if (n != 0u) {
+            std::vector<uint32_t> both(2u * n);
+            for (size_t i = 0; i < n; i++) { both[2u * i] = sig[i]; both[2u * i + 1u] = term[i]; }
+            HIP_TRY(hipMemcpy(s->tags, both.data(), n * 8u, hipMemcpyHostToDevice));
+        }
+        s->bound = batch; s->bound_begin = batch->begins; s->bound_bounces = batch->bounces;
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): the last record, deposit and resolve, from the events recorded around each; 0 for one not yet run
+int vk_debug_lpe_last_ms(vk_lpe *s, double ms[3]) {
+    if (!s || !ms) return fail(VK_ERR_BAD_ARG, "null argument (tracker or ms)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(s->scene)->device));
+        double got[3] = {0.0, 0.0, 0.0};
+        for (int k = 0; k < 3; k++) {
+            if (!s->timed[k]) continue;
+            const int a = k == 0 && s->rec_pair ? 6 : 2 * k, b = a + 1;
+            HIP_TRY(hipEventSynchronize(s->ev[b]));
+            float t = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&t, s->ev[a], s->ev[b]));
+            got[k] = (double)t;
+        }
+        for (int k = 0; k < 3; k++) ms[k] = got[k];
         return VK_OK;
     });
 }

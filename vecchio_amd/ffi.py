@@ -280,6 +280,30 @@ class RobustInfo(C.Structure):
 VK_ROBUST_MEAN, VK_ROBUST_TRIM, VK_ROBUST_GINI = 0, 1, 2
 
 
+class LpeRule(C.Structure):
+    """vk_lpe_rule (vk_lpe_create)"""
+    _fields_ = [("sig_mask", C.c_uint32), ("sig_value", C.c_uint32), ("status_mask", C.c_uint32), ("depth_min", C.c_uint32),
+                ("depth_max", C.c_uint32), ("emitter", C.c_uint32), ("layer", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class LpeParams(C.Structure):
+    """vk_lpe_params (vk_lpe_create)"""
+    _fields_ = [("n_layers", C.c_uint32), ("rest_layer", C.c_uint32), ("n_rules", C.c_uint32), ("_pad", C.c_uint32),
+                ("rules", C.POINTER(LpeRule))]
+
+
+class LpeInfo(C.Structure):
+    """vk_lpe_info (vk_lpe_get_info)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("samples_per_pixel", C.c_uint32), ("n_layers", C.c_uint32),
+                ("rest_layer", C.c_uint32), ("n_rules", C.c_uint32), ("capacity", C.c_uint64),
+                ("deposited", C.c_uint64), ("dropped", C.c_uint64), ("clamped", C.c_uint64), ("skipped", C.c_uint64),
+                ("deposits", C.c_uint64), ("recorded", C.c_uint64)]
+
+
+VK_LPE_SKY, VK_LPE_EMIT, VK_LPE_OTHER, VK_LPE_BAD = 1, 5, 14, 15
+VK_LPE_ALL = 0xFFFFFFFF
+
+
 class RegenInfo(C.Structure):
     """vk_regen_info (vk_regen_step)"""
     _fields_ = [("traced", C.c_uint64), ("live", C.c_uint64), ("remaining", C.c_uint64), ("emitted", C.c_uint64), ("missed", C.c_uint64),
@@ -404,6 +428,7 @@ DEVICE_SYMBOLS = [
     "vk_splat_destroy",
     "vk_robust_default_params", "vk_robust_create", "vk_robust_deposit", "vk_robust_resolve", "vk_robust_reset", "vk_robust_get_info",
     "vk_robust_destroy",
+    "vk_lpe_create", "vk_lpe_step", "vk_lpe_tags", "vk_lpe_deposit", "vk_lpe_resolve", "vk_lpe_reset", "vk_lpe_get_info", "vk_lpe_destroy",
     "vk_matte_default_params", "vk_render_mattes", "vk_matte_merge", "vk_matte_mask",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
@@ -576,6 +601,22 @@ def _bind(lib):
     lib.vk_robust_get_info.argtypes = [C.c_void_p, C.POINTER(RobustInfo)]
     lib.vk_robust_destroy.restype = None
     lib.vk_robust_destroy.argtypes = [C.c_void_p]
+    lib.vk_lpe_create.restype = C.c_int
+    lib.vk_lpe_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(LpeParams), C.POINTER(C.c_void_p)]
+    lib.vk_lpe_step.restype = C.c_int
+    lib.vk_lpe_step.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PathsStepInfo)]
+    lib.vk_lpe_tags.restype = C.c_int
+    lib.vk_lpe_tags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_lpe_deposit.restype = C.c_int
+    lib.vk_lpe_deposit.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_lpe_resolve.restype = C.c_int
+    lib.vk_lpe_resolve.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.vk_lpe_reset.restype = C.c_int
+    lib.vk_lpe_reset.argtypes = [C.c_void_p]
+    lib.vk_lpe_get_info.restype = C.c_int
+    lib.vk_lpe_get_info.argtypes = [C.c_void_p, C.POINTER(LpeInfo)]
+    lib.vk_lpe_destroy.restype = None
+    lib.vk_lpe_destroy.argtypes = [C.c_void_p]
     lib.vk_matte_default_params.restype = C.c_int
     lib.vk_matte_default_params.argtypes = [C.POINTER(MatteParams)]
     lib.vk_render_mattes.restype = C.c_int
@@ -662,6 +703,12 @@ def _bind(lib):
     lib.vk_debug_robust_sums.argtypes = [C.c_void_p, C.c_void_p]
     lib.vk_debug_robust_last_ms.restype = C.c_int
     lib.vk_debug_robust_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 2)]
+    lib.vk_debug_lpe_sums.restype = C.c_int
+    lib.vk_debug_lpe_sums.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_debug_lpe_set_tags.restype = C.c_int
+    lib.vk_debug_lpe_set_tags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_debug_lpe_last_ms.restype = C.c_int
+    lib.vk_debug_lpe_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 3)]
     lib.vk_debug_matte_samples.restype = C.c_int
     lib.vk_debug_matte_samples.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.c_void_p]
     lib.vk_debug_trace_occluded_device.restype = C.c_int

@@ -174,6 +174,21 @@ pub struct vk_robust_params { pub buckets: u32, pub mode: u32, pub trim: u32, pu
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_robust_info { pub width: u32, pub height: u32, pub samples_per_pixel: u32, pub buckets: u32, pub deposited: u64, pub dropped: u64, pub clamped: u64, pub skipped: u64, pub deposits: u64, pub _reserved: u64 }
 
+// light-path layers: a rule, the rule set of a tracker, and its counters
+pub const VK_LPE_SKY: u32 = 1;
+pub const VK_LPE_EMIT: u32 = 5;
+pub const VK_LPE_OTHER: u32 = 14;
+pub const VK_LPE_BAD: u32 = 15;
+pub const VK_LPE_ALL: u32 = 0xFFFF_FFFF;
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_lpe_rule { pub sig_mask: u32, pub sig_value: u32, pub status_mask: u32, pub depth_min: u32, pub depth_max: u32, pub emitter: u32, pub layer: u32, pub _pad: u32 }
+
+#[repr(C)] #[derive(Copy, Clone)]
+pub struct vk_lpe_params { pub n_layers: u32, pub rest_layer: u32, pub n_rules: u32, pub _pad: u32, pub rules: *const vk_lpe_rule }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_lpe_info { pub width: u32, pub height: u32, pub samples_per_pixel: u32, pub n_layers: u32, pub rest_layer: u32, pub n_rules: u32, pub capacity: u64, pub deposited: u64, pub dropped: u64, pub clamped: u64, pub skipped: u64, pub deposits: u64, pub recorded: u64 }
+
 // regeneration: what one vk_regen_step did
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_regen_info { pub traced: u64, pub live: u64, pub remaining: u64, pub emitted: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
@@ -191,6 +206,7 @@ pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, 
 #[repr(C)] pub struct vk_film { _private: [u8; 0] }
 #[repr(C)] pub struct vk_splat { _private: [u8; 0] }
 #[repr(C)] pub struct vk_robust { _private: [u8; 0] }
+#[repr(C)] pub struct vk_lpe { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -312,6 +328,17 @@ extern "C" {
     pub fn vk_robust_reset(s: *mut vk_robust) -> c_int;
     pub fn vk_robust_get_info(s: *mut vk_robust, out: *mut vk_robust_info) -> c_int;
     pub fn vk_robust_destroy(s: *mut vk_robust);
+    // light-path layers (additive symbols of ABI 7): vk_paths_step with a tag per path kept behind every bounce, a finished batch added
+    // to per-layer sums by the first matching rule, and a layer's (or with VK_LPE_ALL every layer's) resolve; sig, term and share_out may
+    // be null
+    pub fn vk_lpe_create(scene: *mut vk_scene, width: u32, height: u32, samples_per_pixel: u32, capacity: u64, lp: *const vk_lpe_params, out: *mut *mut vk_lpe) -> c_int;
+    pub fn vk_lpe_step(s: *mut vk_lpe, batch: *mut vk_paths, max_bounces: u32, info: *mut vk_paths_step_info) -> c_int;
+    pub fn vk_lpe_tags(s: *mut vk_lpe, batch: *mut vk_paths, sig: *mut u32, term: *mut u32) -> c_int;
+    pub fn vk_lpe_deposit(s: *mut vk_lpe, batch: *mut vk_paths) -> c_int;
+    pub fn vk_lpe_resolve(s: *mut vk_lpe, layer: u32, n: u32, rgb_out: *mut f32, share_out: *mut f32) -> c_int;
+    pub fn vk_lpe_reset(s: *mut vk_lpe) -> c_int;
+    pub fn vk_lpe_get_info(s: *mut vk_lpe, out: *mut vk_lpe_info) -> c_int;
+    pub fn vk_lpe_destroy(s: *mut vk_lpe);
     // ID mattes (additive symbols of ABI 7): a ranked table of object or material ids per pixel, ids / counts ranks words per pixel,
     // overflow one (may be null); merge and mask are host code
     pub fn vk_matte_default_params(out: *mut vk_matte_params) -> c_int;

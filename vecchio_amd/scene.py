@@ -663,6 +663,18 @@ class DeviceScene:
         for (_GINI).  Use as a context manager, or close() it before the scene."""
         return Robust(self, width, height, spp, ffi.RobustParams(buckets, mode, trim, 0))
 
+    def lpe(self, width, height, spp, capacity, rules=None, n_layers=None, rest_layer=None):
+        """Light-path layers on this scene (vk_lpe_create): a tracker that steps path batches of up to `capacity` paths as
+        PathBatch.step() does while keeping a tag of every path's bounces, and per pixel and layer the sums of r, g, b and a count, into
+        which finished batches are deposited by the first matching rule.  rules: a list of lpe_rule() values with n_layers and
+        rest_layer; None: standard_rules(), whose layers are STANDARD_LAYERS.  Use as a context manager, or close() it before the
+        scene."""
+        if rules is None:
+            rules = standard_rules()
+            n_layers = len(STANDARD_LAYERS) if n_layers is None else n_layers
+            rest_layer = STANDARD_LAYERS.index("rest") if rest_layer is None else rest_layer
+        return LightPathLayers(self, width, height, spp, capacity, rules, n_layers, 0 if rest_layer is None else rest_layer)
+
     def debug_compact_paths(self, items, ids, n_ids, canary=0xA5, roulette=None):
         """The compaction of a path batch's bounce on host arrays (vk_debug_compact_paths, a test hook): items a SHADED_DTYPE array, ids
         their uint32 ids (each below n_ids).  Every output is prefilled with the byte `canary`.  Returns (rays, states, ids_out — n
@@ -1385,6 +1397,155 @@ class Robust:
     def close(self):
         if self._h:
             self._lib.vk_robust_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+STANDARD_LAYERS = ("emission", "sky", "direct_diffuse", "direct_specular", "volume", "indirect", "rest")
+_ANY_STATUS = (ffi.VK_SHADE_MISS, ffi.VK_SHADE_ENDED, ffi.VK_PATHS_CULLED)
+
+
+def lpe_rule(layer, sig_mask=0, sig_value=0, status=_ANY_STATUS, depth=(0, 0xFFFFFFFF), emitter=None):
+    """One vk_lpe_rule: a result goes to `layer` when (sig & sig_mask) == sig_value, its status is one of `status`, depth[0] <=
+    state.depth <= depth[1] and — with emitter, a material index — the last bounce hit that material."""
+    mask = 0
+    for s in status:
+        mask |= 1 << s
+    return ffi.LpeRule(sig_mask, sig_value, mask, depth[0], depth[1], 0xFFFFFFFF if emitter is None else emitter, layer, 0)
+
+
+def lpe_events(*codes):
+    """(sig_mask, sig_value) of a path whose first len(codes) bounces have these event codes (2 + ffi.VK_MAT_*, ffi.VK_LPE_*); a code of
+    None leaves its bounce open and 0 asks for "no such bounce" — lpe_events(2, 5, 0) is camera, Lambertian, light and nothing after."""
+    mask = value = 0
+    for b, c in enumerate(codes):
+        if c is not None:
+            mask |= 0xF << (4 * b)
+            value |= c << (4 * b)
+    return mask, value
+
+
+def standard_rules():
+    """The rules of STANDARD_LAYERS, by a path's first bounces and its last: emission and sky seen by the camera; light (an emitter
+    or the sky) reached right after one Lambertian bounce (direct diffuse) or one Metal or Dielectric bounce (direct specular or glass);
+    every path whose first bounce scattered in a medium (volume); whatever else ended on an emitter or the sky (indirect); the rest —
+    paths that carry nothing: ended by the depth or an absorbing Metal, culled, bad."""
+    L = {name: i for i, name in enumerate(STANDARD_LAYERS)}
+    lamb, metal, glass, iso = (2 + m for m in (ffi.VK_MAT_LAMBERTIAN, ffi.VK_MAT_METAL, ffi.VK_MAT_DIELECTRIC, ffi.VK_MAT_ISOTROPIC))
+    ended, missed = (ffi.VK_SHADE_ENDED,), (ffi.VK_SHADE_MISS,)
+    rules = [lpe_rule(L["emission"], *lpe_events(ffi.VK_LPE_EMIT), status=ended), lpe_rule(L["sky"], *lpe_events(ffi.VK_LPE_SKY), status=missed)]
+    for first, layer in ((lamb, "direct_diffuse"), (metal, "direct_specular"), (glass, "direct_specular")):
+        rules.append(lpe_rule(L[layer], *lpe_events(first, ffi.VK_LPE_EMIT, 0), status=ended))
+        rules.append(lpe_rule(L[layer], *lpe_events(first, ffi.VK_LPE_SKY, 0), status=missed))
+    rules.append(lpe_rule(L["volume"], *lpe_events(iso)))
+    rules.append(lpe_rule(L["indirect"], 0xF0000000, ffi.VK_LPE_EMIT << 28, status=ended))
+    rules.append(lpe_rule(L["indirect"], 0xF0000000, ffi.VK_LPE_SKY << 28, status=missed))
+    return rules
+
+
+class LightPathLayers:
+    """vk_lpe handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed): step() a path batch as
+    PathBatch.step() does while the tracker records every bounce's event per path, deposit() the finished batch into the layers its
+    results' classes name, resolve() a layer.  All layers together are the film's frame, bit for bit."""
+
+    def __init__(self, scene, width, height, spp, capacity, rules, n_layers, rest_layer):
+        self._lib = scene._lib
+        self._scene = scene
+        self.width, self.height, self.spp, self.capacity = int(width), int(height), int(spp), int(capacity)
+        self.rules = [ffi.LpeRule.from_buffer_copy(r) for r in rules]
+        self.n_layers, self.rest_layer = int(n_layers), int(rest_layer)
+        arr = (ffi.LpeRule * max(1, len(self.rules)))(*self.rules)
+        lp = ffi.LpeParams(self.n_layers, self.rest_layer, len(self.rules), 0, arr if self.rules else None)
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_lpe_create(scene._h, width, height, spp, capacity, C.byref(lp), C.byref(h)))
+        self._h = h
+
+    def step(self, batch, max_bounces=1):
+        """PathBatch.step() with the tags kept (vk_lpe_step): the call's ffi.PathsStepInfo, six launches a bounce.  The first step of a
+        begun or emitted batch binds the tracker to it."""
+        info = ffi.PathsStepInfo()
+        check(self._lib, self._lib.vk_lpe_step(self._h, batch._h, max_bounces, C.byref(info)))
+        return info
+
+    def tags(self, batch):
+        """(sig, term) uint32 arrays per started id of the bound batch (vk_lpe_tags)"""
+        n = int(batch.info().started)
+        sig, term = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        ptr = lambda a: C.c_void_p(a.ctypes.data if n else None)
+        check(self._lib, self._lib.vk_lpe_tags(self._h, batch._h, ptr(sig), ptr(term)))
+        return sig, term
+
+    def deposit(self, batch):
+        """Add the retired paths of the bound `batch`, which has nothing live, each to the layer of its class (vk_lpe_deposit)."""
+        check(self._lib, self._lib.vk_lpe_deposit(self._h, batch._h))
+
+    def resolve(self, layer=ffi.VK_LPE_ALL, n=None, want_share=False, out=None):
+        """A layer's image as its sums over n samples per pixel (vk_lpe_resolve; default: the tracker's spp): float32 (height, width, 3),
+        y = 0 the bottom row; ffi.VK_LPE_ALL: every layer together, the film's frame.  want_share: return (image, share), share (height,
+        width) the layer's part of the pixel's samples."""
+        if out is None:
+            out = np.zeros((self.height, self.width, 3), np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == self.width * self.height * 3
+        share = np.zeros((self.height, self.width), np.float32) if want_share else None
+        check(self._lib, self._lib.vk_lpe_resolve(self._h, layer, self.spp if n is None else n, out.ctypes.data_as(C.c_void_p),
+                                                  share.ctypes.data_as(C.c_void_p) if want_share else None))
+        return (out, share) if want_share else out
+
+    def reset(self):
+        """Zero the sums and the counters (vk_lpe_reset)."""
+        check(self._lib, self._lib.vk_lpe_reset(self._h))
+
+    def info(self):
+        inf = ffi.LpeInfo()
+        check(self._lib, self._lib.vk_lpe_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def render(self, film, batch, cull=None):
+        """The whole frame of `film` through `batch`: Film.render()'s windows, each emitted, stepped to its end here and deposited into
+        the film and into the layers.  Returns the list of every layer's image."""
+        for win in film.windows(min(int(batch.info().capacity), self.capacity)):
+            film.emit(batch, *win)
+            while self.step(batch, 1).live:
+                if cull is not None:
+                    cull(batch)
+            film.deposit(batch)
+            self.deposit(batch)
+        return [self.resolve(layer) for layer in range(self.n_layers)]
+
+    def debug_sums(self):
+        """The raw state (vk_debug_lpe_sums, a test hook): int64 (height, width, n_layers, 4) — r, g, b in 2^-26 units, count"""
+        out = np.zeros((self.height, self.width, self.n_layers, 4), np.int64)
+        check(self._lib, self._lib.vk_debug_lpe_sums(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def debug_set_tags(self, batch, sig, term):
+        """Upload the tags of the batch's started ids and bind the tracker to it, every bounce counted as recorded
+        (vk_debug_lpe_set_tags, a test hook)"""
+        sig, term = np.ascontiguousarray(sig, np.uint32).reshape(-1), np.ascontiguousarray(term, np.uint32).reshape(-1)
+        assert len(sig) == len(term) == int(batch.info().started)
+        ptr = lambda a: C.c_void_p(a.ctypes.data if len(a) else None)
+        check(self._lib, self._lib.vk_debug_lpe_set_tags(self._h, batch._h, ptr(sig), ptr(term)))
+
+    def last_ms(self):
+        """(record, deposit, resolve) device milliseconds of the last launch of each (vk_debug_lpe_last_ms, a test hook)"""
+        ms = (C.c_double * 3)()
+        check(self._lib, self._lib.vk_debug_lpe_last_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
+    def close(self):
+        if self._h:
+            self._lib.vk_lpe_destroy(self._h)
             self._h = None
 
     def __enter__(self):
