@@ -1389,6 +1389,124 @@ int vk_lpe_reset(vk_lpe *s);
 int vk_lpe_get_info(vk_lpe *s, vk_lpe_info *out);
 void vk_lpe_destroy(vk_lpe *s);
 
+/* ---- display transform: auto-exposure, tone curves and sRGB on the device (additive symbols of ABI 7) ------------------------------
+ * replaces: nothing (Vec3::to_color — square-root gamma, clamp at 0.999, times 256: vk_to_color_device, VK_OUTPUT_RGB8 — stays what it
+ * is and is this transform's identity setting).  What a frame of a path tracer needs before a screen can show it: an exposure metered
+ * from the frame itself, stable over an animation; a tone curve with a shoulder; a real transfer function, with dither.
+ *
+ * State.  A handle for one width x height on the scene's device (devices[0] of a multi-device scene): a frame (f32, vk_render's layout,
+ * y = 0 the bottom row), a luminance histogram of 640 bins with four counters, the metered exposure, and the two tables of the table
+ * transfers.  All work is on the null stream there; no function takes a stream.  vk_tone_load_device and vk_tone_encode_device are
+ * ENQUEUED on the null stream: work the caller issued earlier on the null stream or on a blocking stream is ordered before them, and
+ * the encoded bytes are ready when the null stream is; a caller with a non-blocking stream synchronises first (and waits for the null
+ * stream afterwards).  Every other call waits.
+ *
+ * Definitions.  Everything is integers and f32 / f64 basic arithmetic, unfused, in the order written.
+ * Luminance.  Y = (0.2126f * r + 0.7152f * g) + 0.0722f * b, the robust film's.
+ * Histogram.  640 bins of u32 — 40 octaves, 16 per octave, taken from the float's own bits — and four 64-bit counters.  Per pixel, in this
+ *   order: a pixel with a non-finite component counts in `nonfinite`; else one with Y < 2^-20 (negative and zero included) in `below`;
+ *   else one with Y >= 2^20 in `above`; else it counts in bin (f32_bits(Y) >> 19) - (f32_bits(2^-20f) >> 19) and in `binned`.  All
+ *   integers: the result depends on neither the launch shape nor the kernel's form.
+ * Exposure (vk_tone_solve: f64 basic operations only, no libm call, built without contraction).
+ *   1. N = the sum of the bins.  N = 0 (or no weight in step 3): the info carries VK_TONE_METER_EMPTY, log2_target = log2_used = the
+ *      previous meter's log2_used (clamped as in step 5) with the exposure of step 6, or, without a previous one, 0 and the exposure
+ *      1.0f; an empty meter is not a previous meter for the next.
+ *   2. lo = (double)low_fraction * N, hi = (1.0 - (double)high_fraction) * N.
+ *   3. Ascending over the bins, c the count before bin b: w_b = max(0, min(c + bins[b], hi) - max(c, lo)); l_b = -20 + (b + 0.5) / 16;
+ *      S += w_b * l_b; W += w_b.
+ *   4. log2_target = S / W.
+ *   5. log2_used = prev ? prev + (double)blend * (log2_target - prev) : log2_target, then clamped to [min_log2, max_log2].
+ *   6. exposure = (float)((double)key * pexp2(-log2_used)), pexp2(x) = ldexp(1 + (x - floor(x)), (int)floor(x)).
+ *   l_b and pexp2 are the piecewise-linear log and exp the float format gives for free: each is within 0.0861 octave of the true log2 /
+ *   exp2, and a bin's centre within half a bin (1/32 octave) of its members.  The metered exposure therefore puts the trimmed
+ *   geometric-mean luminance of the frame within 0.21 octave of `key`.
+ *   vk_tone_default_meter_params: key 0.18, low_fraction 0.10, high_fraction 0.02, blend 1, min_log2 -16, max_log2 16.
+ * Encode, per pixel and component, f32.  E = params.exposure * (VK_TONE_USE_METERED ? the metered exposure : 1.0f), once on the host.
+ *   1. x = rgb_c * E.
+ *   2. The curve.  VK_TONE_CLAMP: y = x untouched (NaN and negatives go on to the transfer as they are).  Every other curve first
+ *      sanitises: s = x > 0 ? (x < 1048576.0f ? x : 1048576.0f) : 0.0f (NaN becomes 0, +inf 2^20).
+ *        VK_TONE_REINHARD (on luminance; w2 = white * white on the host): Ys = Y(s_r, s_g, s_b); k = (1 + Ys / w2) / (1 + Ys); y_c = s_c * k.
+ *        VK_TONE_HABLE (per channel): h(v) = ((v * (A * v + C * B) + D * E_) / (v * (A * v + B) + D * F)) - E_ / F with A .15f, B .5f,
+ *          C .1f, D .2f, E_ .02f, F .3f; y = h(2.0f * s) / h(white), h(white) computed on the host in f32 by the same function.
+ *        VK_TONE_ACES (Narkowicz's fit, per channel): y = (s * (2.51f * s + 0.03f)) / (s * (2.43f * s + 0.59f) + 0.14f).
+ *   3. The transfer.  VK_TONE_TRANSFER_REFERENCE: Vec3::to_color's component — sqrtf, the hand-written clamp that NaN falls through,
+ *      256.0f *, the saturating cast.  VK_TONE_TRANSFER_SRGB and VK_TONE_TRANSFER_GAMMA22: a table of 510 ascending floats H[j], j = 1 ..
+ *      510, H[j] the smallest f32 not below inv(j / 510), inv the inverse sRGB encoding (c <= 0.04045 ? c / 12.92 : ((c + 0.055) /
+ *      1.055)^2.4) or c^2.2, evaluated in f64 on the host.  Undithered: code = #{k in 1 .. 255 : y >= H[2k - 1]} (round to nearest).
+ *      Dithered (VK_TONE_DITHER): base = #{k in 1 .. 255 : y >= H[2k]}; base = 255 stays 255; otherwise lo = base ? H[2 base] : 0, hi =
+ *      H[2 base + 2], fr = (y - lo) / (hi - lo), u = the next gen_f32 of rng_for_stream(params.seed, pixel) (vk_math.h; pixel = the
+ *      input index y * width + x, y up; three draws per pixel in r, g, b order, drawn whether used or not), code = base + (u < fr).
+ *   4. The byte goes to row height - 1 - y: width * height * 3 bytes, row 0 the TOP, as VK_OUTPUT_RGB8.
+ *   vk_tone_default_params: VK_TONE_ACES, VK_TONE_TRANSFER_SRGB, VK_TONE_USE_METERED, exposure 1, white 11.2, seed 0.
+ *
+ * Contract.  (1) Histogram and counters equal tests/tone_ref.py's numpy restatement exactly, in both kernel forms.  (2) vk_tone_meter's
+ * info is vk_tone_solve's on that histogram (vk_tone_meter calls it; below, above and nonfinite are the meter's own, 0 from
+ * vk_tone_solve), bit for bit the Python restatement's.  (3) VK_TONE_CLAMP + VK_TONE_TRANSFER_REFERENCE with E = 1.0f gives
+ * vk_to_color_device's bytes — NaN, +-inf, -0 and negatives included —, hence vk_render's VK_OUTPUT_RGB8 frame.  (4) Every other
+ * combination equals the restatement bit for bit given the library's own table (vk_debug_tone_table), and the host build of the
+ * per-pixel code.  (5) The table is strictly increasing, each entry not below the f64 value and within one f32 ulp of it.  (6) Against
+ * the f64 closed form round(255 * OETF(curve(E * x))) no component is off by more than one code, and at most 1e-4 of them by one.
+ * What this is not.  No bloom or glare, no white balance or grading, no 16-bit or float output, no metering weights; a multi-device
+ * scene's frame is its devices[0]'s; the frame comes from the caller's buffer.
+ *
+ *   vk_tone_create: VK_ERR_BAD_ARG for a null pointer, width or height 0, width * height > 2^27.  VK_ERR_OOM leaves *out untouched.
+ *   vk_tone_load / vk_tone_load_device: width * height * 3 floats from the host (through the staging path of the host-pointer calls; waits)
+ *     or from memory of the handle's device (enqueued).  VK_ERR_BAD_ARG for a null pointer.
+ *   vk_tone_solve / vk_tone_meter: VK_ERR_BAD_ARG, nothing enqueued and *out untouched, for a null pointer, a non-zero _pad,
+ *     low_fraction or high_fraction negative or non-finite or their sum >= 1, key not finite and positive, blend outside [0, 1], min_log2
+ *     or max_log2 non-finite or beyond +-1000, min_log2 > max_log2, a non-finite *prev_log2; vk_tone_meter before a load.
+ *   vk_tone_encode / vk_tone_encode_device: VK_ERR_BAD_ARG, nothing enqueued or written, for a null pointer, a non-zero _pad, an unknown
+ *     curve, transfer or flag, VK_TONE_DITHER with VK_TONE_TRANSFER_REFERENCE, exposure or white not finite and positive (white = +inf
+ *     is allowed with VK_TONE_REINHARD), an encode before a load, VK_TONE_USE_METERED before a meter, a d_rgb8_out that is not 4-byte
+ *     aligned.
+ *   vk_tone_reset forgets the metered exposure and the frame: the next meter is a first one.  vk_tone_destroy(NULL) does nothing.   */
+enum { VK_TONE_CLAMP = 0, VK_TONE_REINHARD = 1, VK_TONE_HABLE = 2, VK_TONE_ACES = 3 };
+enum { VK_TONE_TRANSFER_REFERENCE = 0, VK_TONE_TRANSFER_SRGB = 1, VK_TONE_TRANSFER_GAMMA22 = 2 };
+enum { VK_TONE_USE_METERED = 1, VK_TONE_DITHER = 2 };            /* vk_tone_params.flags */
+enum { VK_TONE_METER_EMPTY = 1 };                                /* vk_tone_meter_info.flags */
+typedef struct vk_tone vk_tone;          /* opaque */
+typedef struct vk_tone_meter_params {    /* 32 bytes */
+    float key;                           /* the luminance the trimmed geometric mean is mapped to */
+    float low_fraction, high_fraction;   /* the shares of the binned pixels left out at the dark and at the bright end */
+    float blend;                         /* 0 .. 1: how far a later meter moves from the previous log2_used to its own target */
+    float min_log2, max_log2;            /* log2_used is clamped to this range */
+    uint32_t _pad[2];                    /* 0 */
+} vk_tone_meter_params;
+typedef struct vk_tone_meter_info {      /* 56 bytes */
+    double log2_target, log2_used;
+    uint64_t binned, below, above, nonfinite;
+    float exposure;
+    uint32_t flags;                      /* VK_TONE_METER_* */
+} vk_tone_meter_info;
+typedef struct vk_tone_params {          /* 32 bytes */
+    uint32_t curve;                      /* VK_TONE_CLAMP .. VK_TONE_ACES */
+    uint32_t transfer;                   /* VK_TONE_TRANSFER_* */
+    uint32_t flags;                      /* VK_TONE_USE_METERED | VK_TONE_DITHER */
+    uint32_t _pad;                       /* 0 */
+    float exposure;                      /* a factor on top of the metered exposure (or alone) */
+    float white;                         /* REINHARD's and HABLE's white point */
+    uint64_t seed;                       /* the dither's */
+} vk_tone_params;
+typedef struct vk_tone_info {            /* 48 bytes */
+    uint32_t width, height;
+    uint64_t loads, meters, encodes;     /* accepted calls since create */
+    float exposure;                      /* the metered exposure; 1.0f before a meter */
+    uint32_t metered;                    /* 1 once vk_tone_meter has run since create or reset */
+    double log2_used;                    /* the last non-empty meter's; 0 without one */
+} vk_tone_info;
+int vk_tone_default_meter_params(vk_tone_meter_params *out);
+int vk_tone_default_params(vk_tone_params *out);
+int vk_tone_create(vk_scene *scene, uint32_t width, uint32_t height, vk_tone **out);
+int vk_tone_load(vk_tone *t, const float *rgb);
+int vk_tone_load_device(vk_tone *t, const void *d_rgb);
+int vk_tone_meter(vk_tone *t, const vk_tone_meter_params *mp, vk_tone_meter_info *out);
+int vk_tone_solve(const uint32_t bins[640], const vk_tone_meter_params *mp, const double *prev_log2, vk_tone_meter_info *out);
+int vk_tone_encode(vk_tone *t, const vk_tone_params *tp, uint8_t *rgb8_out);
+int vk_tone_encode_device(vk_tone *t, const vk_tone_params *tp, void *d_rgb8_out);
+int vk_tone_reset(vk_tone *t);
+int vk_tone_get_info(vk_tone *t, vk_tone_info *out);
+void vk_tone_destroy(vk_tone *t);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

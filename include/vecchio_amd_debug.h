@@ -188,6 +188,21 @@ int vk_debug_lpe_set_tags(vk_lpe *s, vk_paths *batch, const uint32_t *sig, const
  * stream.  In both libraries. */
 int vk_debug_lpe_last_ms(vk_lpe *s, double ms[3]);
 
+/* the histogram and the four counters (binned, below, above, nonfinite) of a tone handle's last vk_tone_meter, zeros before the first.
+ * Waits.  VK_ERR_BAD_ARG for a null pointer.  Takes no stream.  In both libraries. */
+int vk_debug_tone_histogram(vk_tone *t, uint32_t bins[640], uint64_t counters[4]);
+/* the 510 thresholds H[1 .. 510] of VK_TONE_TRANSFER_SRGB or VK_TONE_TRANSFER_GAMMA22 as every handle holds them: host code, needs no
+ * device.  VK_ERR_BAD_ARG for a null pointer or another transfer.  In both libraries. */
+int vk_debug_tone_table(uint32_t transfer, float out[510]);
+/* the form of vk_tone_meter's kernel from the next call on: LDS = a histogram per workgroup in LDS, flushed with one global atomic per
+ * non-zero bin (the default, DESIGN.md "Display transform"); PLAIN = one global atomic per pixel.  Both give the same histogram.
+ * VK_ERR_BAD_ARG for a null handle or another form.  In both libraries. */
+enum { VK_TONE_FORM_LDS = 0, VK_TONE_FORM_PLAIN = 1 };
+int vk_debug_tone_set_form(vk_tone *t, uint32_t form);
+/* the device milliseconds of the handle's last meter kernel (ms[0]) and encode kernel (ms[1]: without the copy to the host), between
+ * two events around each; 0 for one that has not run.  Waits for those.  Takes no stream.  In both libraries. */
+int vk_debug_tone_last_ms(vk_tone *t, double ms[2]);
+
 /* the id of every sample vk_render_mattes would count, by the same per-lane code on the same lanes: ids_out[(y * width + x) * spp + k] is
  * the id of sample first_sample + k under `kind` (VK_MATTE_OBJECT or VK_MATTE_MATERIAL), spp = params->samples_per_pixel; pixels outside
  * the call's tile partition are left untouched.  vk_render_mattes' checks.  Waits.  In both libraries. */

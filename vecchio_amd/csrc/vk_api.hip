@@ -55,6 +55,7 @@
 #include "vk_splat.h"        // the kernels of vk_splat.hip: the filter, argument records and launchers
 #include "vk_robust.h"       // the kernels of vk_robust.hip: the per-pixel resolve, argument records and launchers
 #include "vk_lpe.h"          // the kernels of vk_lpe.hip: the tag, the rule match, argument records and launchers
+#include "vk_tone.h"         // the kernels of vk_tone.hip: the per-pixel display transform, argument records and launchers
 #include "vk_matte.h"        // the kernels of vk_matte.hip: the table of a pixel, the argument record and launchers
 
 namespace {
@@ -4503,6 +4504,349 @@ int vk_debug_lpe_last_ms(vk_lpe *s, double ms[3]) {
             got[k] = (double)t;
         }
         for (int k = 0; k < 3; k++) ms[k] = got[k];
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- display transform (vk_tone_*): a frame on the scene's device (devices[0] of a multi-device scene), its luminance histogram
+// (tone_meter_*_kernel), the exposure metered from it on the host (vk_tone_solve) and its encoding to 8-bit codes
+// (tone_encode_kernel<curve, table, dither>, vk_tone.hip); all on the null stream, on buffers and events the handle owns.  Nothing of
+// the scene handle is read but its device.
+struct vk_tone {
+    vk_scene *scene = nullptr;                      // as handed to vk_tone_create
+    uint32_t width = 0, height = 0;
+    DeviceBuffer<float> frame;                      // [width * height * 3], y up: vk_tone_load's staging buffer and the kernels' input
+    DeviceBuffer<uint32_t> hist;                    // TONE_BINS bins, then TONE_COUNTERS 64-bit counters
+    DeviceBuffer<float> tables;                     // sRGB's and gamma 2.2's thresholds, TONE_TABLE floats each
+    DeviceBuffer<uint8_t> out;                      // the codes on their way to the host (first vk_tone_encode)
+    Event ev[4];                                    // around the last meter and encode kernels
+    bool timed[2] = {false, false};
+    bool loaded = false, metered = false, has_prev = false;
+    double log2_used = 0.0;                         // the last non-empty meter's (has_prev)
+    float exposure = 1.0f;
+    uint32_t form = TONE_FORM_LDS;
+    uint64_t loads = 0, meters = 0, encodes = 0;
+};
+
+namespace {
+
+void tone_free(vk_tone *t) {
+    (void)hipSetDevice(first_part(t->scene)->device);
+    (void)hipStreamSynchronize(nullptr);              // (an encode or a copy may still run)
+    (void)hipGetLastError();
+    delete t;
+}
+
+size_t tone_pixels(const vk_tone *t) { return (size_t)t->width * t->height; }
+
+constexpr size_t TONE_HIST_BYTES = TONE_BINS * sizeof(uint32_t) + TONE_COUNTERS * sizeof(unsigned long long);
+
+// the inverse of a transfer's encoding at c in [0, 1], in f64
+double tone_inverse(uint32_t transfer, double c) {
+    if (transfer == VK_TONE_TRANSFER_SRGB) return c <= 0.04045 ? c / 12.92 : std::pow((c + 0.055) / 1.055, 2.4);
+    return std::pow(c, 2.2);
+}
+
+// H[j], j = 1 .. 510, into h[j - 1]: the smallest f32 not below inverse(j / 510)
+void tone_table(uint32_t transfer, float h[TONE_TABLE]) {
+    for (uint32_t j = 1; j <= TONE_TABLE; j++) {
+        const double v = tone_inverse(transfer, (double)j / 510.0);
+        float f = (float)v;
+        if ((double)f < v) f = std::nextafterf(f, INFINITY);
+        h[j - 1u] = f;
+    }
+}
+
+// 2^e * (1 + f) for x = e + f, e = floor(x): the piecewise-linear exp2 of the float format, from basic operations (|x| <= 1000)
+double tone_pexp2(double x) {
+    long long e = (long long)x;
+    if ((double)e > x) e -= 1;
+    const double f = x - (double)e;
+    return (1.0 + f) * vk::bits_f64((uint64_t)(e + 1023) << 52);
+}
+
+const char *tone_meter_refusal(const vk_tone_meter_params &mp) {
+    if (mp._pad[0] != 0u || mp._pad[1] != 0u) return "_pad must be 0";
+    if (!std::isfinite(mp.low_fraction) || !std::isfinite(mp.high_fraction) || mp.low_fraction < 0.0f || mp.high_fraction < 0.0f)
+        return "low_fraction and high_fraction must be finite and >= 0";
+    if ((double)mp.low_fraction + (double)mp.high_fraction >= 1.0) return "low_fraction + high_fraction must be below 1";
+    if (!std::isfinite(mp.key) || !(mp.key > 0.0f)) return "key must be finite and > 0";
+    if (!(mp.blend >= 0.0f && mp.blend <= 1.0f)) return "blend must be in 0..1";
+    if (!std::isfinite(mp.min_log2) || !std::isfinite(mp.max_log2) || std::fabs(mp.min_log2) > 1000.0f || std::fabs(mp.max_log2) > 1000.0f)
+        return "min_log2 and max_log2 must be finite and within -1000..1000";
+    if (mp.min_log2 > mp.max_log2) return "min_log2 must not exceed max_log2";
+    return nullptr;
+}
+
+const char *tone_refusal(const vk_tone_params &tp) {
+    if (tp._pad != 0u) return "_pad must be 0";
+    if (tp.curve > (uint32_t)VK_TONE_ACES) return "unknown curve";
+    if (tp.transfer > (uint32_t)VK_TONE_TRANSFER_GAMMA22) return "unknown transfer";
+    if (tp.flags & ~(uint32_t)(VK_TONE_USE_METERED | VK_TONE_DITHER)) return "unknown tone flags";
+    if ((tp.flags & VK_TONE_DITHER) && tp.transfer == (uint32_t)VK_TONE_TRANSFER_REFERENCE) return "dither needs a table transfer (not the reference transfer)";
+    if (!std::isfinite(tp.exposure) || !(tp.exposure > 0.0f)) return "exposure must be finite and > 0";
+    const bool inf_ok = tp.curve == (uint32_t)VK_TONE_REINHARD && tp.white == INFINITY;
+    if (!inf_ok && (!std::isfinite(tp.white) || !(tp.white > 0.0f))) return "white must be finite and > 0 (+inf with VK_TONE_REINHARD)";
+    return nullptr;
+}
+
+// the encode of the handle's frame into d_out (4-byte aligned, the handle's device); the arguments have been checked
+int enqueue_tone_encode(vk_tone *t, const vk_tone_params &tp, uint8_t *d_out) {
+    ToneEncodeArgs A;
+    memset(&A, 0, sizeof(A));
+    const bool table = tp.transfer != (uint32_t)VK_TONE_TRANSFER_REFERENCE;
+    A.rgb = t->frame; A.out = d_out; A.width = t->width; A.height = t->height;
+    A.table = table ? t->tables.get() + (tp.transfer == (uint32_t)VK_TONE_TRANSFER_GAMMA22 ? TONE_TABLE : 0u) : nullptr;
+    A.E = tp.exposure * ((tp.flags & VK_TONE_USE_METERED) ? t->exposure : 1.0f);
+    A.p = tp.curve == (uint32_t)VK_TONE_REINHARD ? tp.white * tp.white : tp.curve == (uint32_t)VK_TONE_HABLE ? tone_hable(tp.white) : 0.0f;
+    A.seed = tp.seed;
+    HIP_TRY(hipEventRecord(t->ev[2], nullptr));
+    launch_tone_encode(A, tp.curve, table, (tp.flags & VK_TONE_DITHER) != 0u);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(t->ev[3], nullptr));
+    t->timed[1] = true;
+    t->encodes++;
+    return VK_OK;
+}
+
+int check_tone_encode(vk_tone *t, const vk_tone_params *tp, const void *out) {
+    if (!t || !tp || !out) return fail(VK_ERR_BAD_ARG, "null argument (tone handle, params or output)");
+    if (const char *why = tone_refusal(*tp)) return fail(VK_ERR_BAD_ARG, why);
+    if (!t->loaded) return fail(VK_ERR_BAD_ARG, "vk_tone_encode before vk_tone_load");
+    if ((tp->flags & VK_TONE_USE_METERED) && !t->metered) return fail(VK_ERR_BAD_ARG, "VK_TONE_USE_METERED before vk_tone_meter");
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_tone_default_meter_params(vk_tone_meter_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    memset(out, 0, sizeof(*out));
+    out->key = 0.18f; out->low_fraction = 0.10f; out->high_fraction = 0.02f; out->blend = 1.0f; out->min_log2 = -16.0f; out->max_log2 = 16.0f;
+    return VK_OK;
+}
+
+int vk_tone_default_params(vk_tone_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    memset(out, 0, sizeof(*out));
+    out->curve = VK_TONE_ACES; out->transfer = VK_TONE_TRANSFER_SRGB; out->flags = VK_TONE_USE_METERED;
+    out->exposure = 1.0f; out->white = 11.2f; out->seed = 0u;
+    return VK_OK;
+}
+
+int vk_tone_solve(const uint32_t bins[640], const vk_tone_meter_params *mp, const double *prev_log2, vk_tone_meter_info *out) {
+    if (!bins || !mp || !out) return fail(VK_ERR_BAD_ARG, "null argument (bins, params or out)");
+    if (const char *why = tone_meter_refusal(*mp)) return fail(VK_ERR_BAD_ARG, why);
+    if (prev_log2 && !std::isfinite(*prev_log2)) return fail(VK_ERR_BAD_ARG, "prev_log2 must be finite");
+    uint64_t N = 0u;
+    for (uint32_t b = 0; b < TONE_BINS; b++) N += bins[b];
+    const double lo = (double)mp->low_fraction * (double)N, hi = (1.0 - (double)mp->high_fraction) * (double)N;
+    double S = 0.0, W = 0.0, c = 0.0;
+    for (uint32_t b = 0; b < TONE_BINS; b++) {
+        const double next = c + (double)bins[b];
+        const double top = next < hi ? next : hi, bottom = c > lo ? c : lo;
+        const double w = top - bottom > 0.0 ? top - bottom : 0.0;
+        const double l = -20.0 + ((double)b + 0.5) / 16.0;
+        S += w * l; W += w;
+        c = next;
+    }
+    vk_tone_meter_info info;
+    memset(&info, 0, sizeof(info));
+    info.binned = N;
+    const double mn = (double)mp->min_log2, mx = (double)mp->max_log2;
+    if (N == 0u || !(W > 0.0)) {
+        info.flags = VK_TONE_METER_EMPTY;
+        if (prev_log2) {
+            const double u = *prev_log2 < mn ? mn : (*prev_log2 > mx ? mx : *prev_log2);
+            info.log2_target = *prev_log2; info.log2_used = u;
+            info.exposure = (float)((double)mp->key * tone_pexp2(-u));
+        } else {
+            info.exposure = 1.0f;
+        }
+    } else {
+        const double target = S / W;
+        double u = prev_log2 ? *prev_log2 + (double)mp->blend * (target - *prev_log2) : target;
+        u = u < mn ? mn : (u > mx ? mx : u);
+        info.log2_target = target; info.log2_used = u;
+        info.exposure = (float)((double)mp->key * tone_pexp2(-u));
+    }
+    *out = info;
+    return VK_OK;
+}
+
+int vk_tone_create(vk_scene *scene, uint32_t width, uint32_t height, vk_tone **out) {
+    if (!scene || !out) return fail(VK_ERR_BAD_ARG, "null argument (scene or out)");
+    if (width == 0u || height == 0u) return fail(VK_ERR_BAD_ARG, "width and height must be >= 1");
+    if ((uint64_t)width * height > TONE_MAX_PIXELS) return fail(VK_ERR_BAD_ARG, "width * height exceeds 2^27");
+    return guarded([&]() -> int {
+        std::unique_ptr<vk_tone, void (*)(vk_tone *)> t(new vk_tone(), tone_free);
+        t->scene = scene; t->width = width; t->height = height;
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        int r = VK_OK;
+        handle_alloc(r, t->frame, tone_pixels(t.get()) * 3u * sizeof(float));
+        handle_alloc(r, t->hist, TONE_HIST_BYTES);
+        handle_alloc(r, t->tables, 2u * TONE_TABLE * sizeof(float));
+        if (r != VK_OK) return r;
+        for (Event &e : t->ev) if ((r = e.create()) != VK_OK) return r;
+        float h[2u * TONE_TABLE];
+        tone_table(VK_TONE_TRANSFER_SRGB, h);
+        tone_table(VK_TONE_TRANSFER_GAMMA22, h + TONE_TABLE);
+        HIP_TRY(hipMemcpy(t->tables, h, sizeof(h), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(t->hist, 0, TONE_HIST_BYTES));
+        *out = t.release();
+        return VK_OK;
+    });
+}
+
+int vk_tone_load(vk_tone *t, const float *rgb) {
+    if (!t || !rgb) return fail(VK_ERR_BAD_ARG, "null argument (tone handle or rgb)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(t->scene)->device));
+        float *const host[1] = {const_cast<float *>(rgb)};
+        const uint32_t comps[1] = {3u};
+        StagedImages im;
+        int rc = im.upload(t->frame, host, comps, 1, tone_pixels(t), 0x1u);
+        if (rc != VK_OK) return rc;
+        t->loaded = true; t->loads++;
+        return VK_OK;
+    });
+}
+
+int vk_tone_load_device(vk_tone *t, const void *d_rgb) {
+    if (!t || !d_rgb) return fail(VK_ERR_BAD_ARG, "null argument (tone handle or d_rgb)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(t->scene)->device));
+        HIP_TRY(hipMemcpyAsync(t->frame, d_rgb, tone_pixels(t) * 3u * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+        t->loaded = true; t->loads++;
+        return VK_OK;
+    });
+}
+
+int vk_tone_meter(vk_tone *t, const vk_tone_meter_params *mp, vk_tone_meter_info *out) {
+    if (!t || !mp || !out) return fail(VK_ERR_BAD_ARG, "null argument (tone handle, params or out)");
+    if (const char *why = tone_meter_refusal(*mp)) return fail(VK_ERR_BAD_ARG, why);
+    if (!t->loaded) return fail(VK_ERR_BAD_ARG, "vk_tone_meter before vk_tone_load");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(t->scene)->device));
+        ToneMeterArgs A;
+        memset(&A, 0, sizeof(A));
+        A.rgb = t->frame; A.bins = t->hist; A.counters = reinterpret_cast<unsigned long long *>(t->hist.get() + TONE_BINS);
+        A.n_pixels = (uint32_t)tone_pixels(t);
+        HIP_TRY(hipMemsetAsync(t->hist, 0, TONE_HIST_BYTES, nullptr));
+        HIP_TRY(hipEventRecord(t->ev[0], nullptr));
+        launch_tone_meter(A, t->form);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(t->ev[1], nullptr));
+        t->timed[0] = true;
+        uint32_t host[TONE_HIST_BYTES / sizeof(uint32_t)];
+        HIP_TRY(hipMemcpy(host, t->hist, TONE_HIST_BYTES, hipMemcpyDeviceToHost));      // (waits for the null stream)
+        unsigned long long counters[TONE_COUNTERS];
+        memcpy(counters, host + TONE_BINS, sizeof(counters));
+        vk_tone_meter_info info;
+        const int rc = vk_tone_solve(host, mp, t->has_prev ? &t->log2_used : nullptr, &info);
+        if (rc != VK_OK) return rc;
+        info.below = counters[TONE_BELOW]; info.above = counters[TONE_ABOVE]; info.nonfinite = counters[TONE_NONFINITE];
+        if (!(info.flags & VK_TONE_METER_EMPTY)) { t->has_prev = true; t->log2_used = info.log2_used; }
+        t->exposure = info.exposure; t->metered = true; t->meters++;
+        *out = info;
+        return VK_OK;
+    });
+}
+
+int vk_tone_encode(vk_tone *t, const vk_tone_params *tp, uint8_t *rgb8_out) {
+    int rc = check_tone_encode(t, tp, rgb8_out);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(t->scene)->device));
+        const size_t bytes = tone_pixels(t) * 3u;
+        if (!t->out) {
+            int r = VK_OK;
+            handle_alloc(r, t->out, bytes);
+            if (r != VK_OK) return r;
+        }
+        int r = enqueue_tone_encode(t, *tp, t->out);
+        if (r != VK_OK) return r;
+        HIP_TRY(hipMemcpy(rgb8_out, t->out, bytes, hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+int vk_tone_encode_device(vk_tone *t, const vk_tone_params *tp, void *d_rgb8_out) {
+    int rc = check_tone_encode(t, tp, d_rgb8_out);
+    if (rc != VK_OK) return rc;
+    if (reinterpret_cast<uintptr_t>(d_rgb8_out) & 3u) return fail(VK_ERR_BAD_ARG, "d_rgb8_out must be 4-byte aligned");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(t->scene)->device));
+        return enqueue_tone_encode(t, *tp, static_cast<uint8_t *>(d_rgb8_out));
+    });
+}
+
+int vk_tone_reset(vk_tone *t) {
+    if (!t) return fail(VK_ERR_BAD_ARG, "null tone handle");
+    t->loaded = false; t->metered = false; t->has_prev = false; t->log2_used = 0.0; t->exposure = 1.0f;
+    return VK_OK;
+}
+
+int vk_tone_get_info(vk_tone *t, vk_tone_info *out) {
+    if (!t || !out) return fail(VK_ERR_BAD_ARG, "null argument (tone handle or out)");
+    memset(out, 0, sizeof(*out));
+    out->width = t->width; out->height = t->height; out->loads = t->loads; out->meters = t->meters; out->encodes = t->encodes;
+    out->exposure = t->exposure; out->metered = t->metered ? 1u : 0u; out->log2_used = t->log2_used;
+    return VK_OK;
+}
+
+void vk_tone_destroy(vk_tone *t) {
+    if (t) tone_free(t);
+}
+
+// test hook (vecchio_amd_debug.h): the last meter's histogram and counters (zeros before the first)
+int vk_debug_tone_histogram(vk_tone *t, uint32_t bins[640], uint64_t counters[4]) {
+    if (!t || !bins || !counters) return fail(VK_ERR_BAD_ARG, "null argument (tone handle, bins or counters)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(t->scene)->device));
+        uint32_t host[TONE_HIST_BYTES / sizeof(uint32_t)];
+        HIP_TRY(hipMemcpy(host, t->hist, TONE_HIST_BYTES, hipMemcpyDeviceToHost));
+        memcpy(bins, host, TONE_BINS * sizeof(uint32_t));
+        memcpy(counters, host + TONE_BINS, TONE_COUNTERS * sizeof(uint64_t));
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): a table transfer's 510 thresholds, as every handle holds them; host code
+int vk_debug_tone_table(uint32_t transfer, float out[510]) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    if (transfer != (uint32_t)VK_TONE_TRANSFER_SRGB && transfer != (uint32_t)VK_TONE_TRANSFER_GAMMA22)
+        return fail(VK_ERR_BAD_ARG, "not a table transfer");
+    tone_table(transfer, out);
+    return VK_OK;
+}
+
+// test hook (vecchio_amd_debug.h): the meter kernel's form
+int vk_debug_tone_set_form(vk_tone *t, uint32_t form) {
+    if (!t) return fail(VK_ERR_BAD_ARG, "null tone handle");
+    if (form != (uint32_t)VK_TONE_FORM_LDS && form != (uint32_t)VK_TONE_FORM_PLAIN) return fail(VK_ERR_BAD_ARG, "unknown meter form");
+    t->form = form;
+    return VK_OK;
+}
+
+// test hook (vecchio_amd_debug.h): the last meter and encode kernels, from the events recorded around each; 0 for one not yet run
+int vk_debug_tone_last_ms(vk_tone *t, double ms[2]) {
+    if (!t || !ms) return fail(VK_ERR_BAD_ARG, "null argument (tone handle or ms)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(t->scene)->device));
+        double got[2] = {0.0, 0.0};
+        for (int k = 0; k < 2; k++) {
+            if (!t->timed[k]) continue;
+            HIP_TRY(hipEventSynchronize(t->ev[2 * k + 1]));
+            float e = 0.0f;
+            HIP_TRY(hipEventElapsedTime(&e, t->ev[2 * k], t->ev[2 * k + 1]));
+            got[k] = (double)e;
+        }
+        for (int k = 0; k < 2; k++) ms[k] = got[k];
         return VK_OK;
     });
 }

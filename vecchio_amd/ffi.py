@@ -304,6 +304,37 @@ VK_LPE_SKY, VK_LPE_EMIT, VK_LPE_OTHER, VK_LPE_BAD = 1, 5, 14, 15
 VK_LPE_ALL = 0xFFFFFFFF
 
 
+class ToneMeterParams(C.Structure):
+    """vk_tone_meter_params (vk_tone_meter, vk_tone_solve)"""
+    _fields_ = [("key", C.c_float), ("low_fraction", C.c_float), ("high_fraction", C.c_float), ("blend", C.c_float),
+                ("min_log2", C.c_float), ("max_log2", C.c_float), ("_pad", C.c_uint32 * 2)]
+
+
+class ToneMeterInfo(C.Structure):
+    """vk_tone_meter_info (vk_tone_meter, vk_tone_solve)"""
+    _fields_ = [("log2_target", C.c_double), ("log2_used", C.c_double), ("binned", C.c_uint64), ("below", C.c_uint64),
+                ("above", C.c_uint64), ("nonfinite", C.c_uint64), ("exposure", C.c_float), ("flags", C.c_uint32)]
+
+
+class ToneParams(C.Structure):
+    """vk_tone_params (vk_tone_encode, vk_tone_encode_device)"""
+    _fields_ = [("curve", C.c_uint32), ("transfer", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32),
+                ("exposure", C.c_float), ("white", C.c_float), ("seed", C.c_uint64)]
+
+
+class ToneInfo(C.Structure):
+    """vk_tone_info (vk_tone_get_info)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("loads", C.c_uint64), ("meters", C.c_uint64), ("encodes", C.c_uint64),
+                ("exposure", C.c_float), ("metered", C.c_uint32), ("log2_used", C.c_double)]
+
+
+VK_TONE_CLAMP, VK_TONE_REINHARD, VK_TONE_HABLE, VK_TONE_ACES = 0, 1, 2, 3
+VK_TONE_TRANSFER_REFERENCE, VK_TONE_TRANSFER_SRGB, VK_TONE_TRANSFER_GAMMA22 = 0, 1, 2
+VK_TONE_USE_METERED, VK_TONE_DITHER = 1, 2
+VK_TONE_METER_EMPTY = 1
+VK_TONE_FORM_LDS, VK_TONE_FORM_PLAIN = 0, 1
+
+
 class RegenInfo(C.Structure):
     """vk_regen_info (vk_regen_step)"""
     _fields_ = [("traced", C.c_uint64), ("live", C.c_uint64), ("remaining", C.c_uint64), ("emitted", C.c_uint64), ("missed", C.c_uint64),
@@ -429,6 +460,8 @@ DEVICE_SYMBOLS = [
     "vk_robust_default_params", "vk_robust_create", "vk_robust_deposit", "vk_robust_resolve", "vk_robust_reset", "vk_robust_get_info",
     "vk_robust_destroy",
     "vk_lpe_create", "vk_lpe_step", "vk_lpe_tags", "vk_lpe_deposit", "vk_lpe_resolve", "vk_lpe_reset", "vk_lpe_get_info", "vk_lpe_destroy",
+    "vk_tone_default_meter_params", "vk_tone_default_params", "vk_tone_create", "vk_tone_load", "vk_tone_load_device", "vk_tone_meter",
+    "vk_tone_solve", "vk_tone_encode", "vk_tone_encode_device", "vk_tone_reset", "vk_tone_get_info", "vk_tone_destroy",
     "vk_matte_default_params", "vk_render_mattes", "vk_matte_merge", "vk_matte_mask",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
@@ -617,6 +650,30 @@ def _bind(lib):
     lib.vk_lpe_get_info.argtypes = [C.c_void_p, C.POINTER(LpeInfo)]
     lib.vk_lpe_destroy.restype = None
     lib.vk_lpe_destroy.argtypes = [C.c_void_p]
+    lib.vk_tone_default_meter_params.restype = C.c_int
+    lib.vk_tone_default_meter_params.argtypes = [C.POINTER(ToneMeterParams)]
+    lib.vk_tone_default_params.restype = C.c_int
+    lib.vk_tone_default_params.argtypes = [C.POINTER(ToneParams)]
+    lib.vk_tone_create.restype = C.c_int
+    lib.vk_tone_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.vk_tone_load.restype = C.c_int
+    lib.vk_tone_load.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_tone_load_device.restype = C.c_int
+    lib.vk_tone_load_device.argtypes = [C.c_void_p, C.c_void_p]
+    lib.vk_tone_meter.restype = C.c_int
+    lib.vk_tone_meter.argtypes = [C.c_void_p, C.POINTER(ToneMeterParams), C.POINTER(ToneMeterInfo)]
+    lib.vk_tone_solve.restype = C.c_int
+    lib.vk_tone_solve.argtypes = [C.c_void_p, C.POINTER(ToneMeterParams), C.POINTER(C.c_double), C.POINTER(ToneMeterInfo)]
+    lib.vk_tone_encode.restype = C.c_int
+    lib.vk_tone_encode.argtypes = [C.c_void_p, C.POINTER(ToneParams), C.c_void_p]
+    lib.vk_tone_encode_device.restype = C.c_int
+    lib.vk_tone_encode_device.argtypes = [C.c_void_p, C.POINTER(ToneParams), C.c_void_p]
+    lib.vk_tone_reset.restype = C.c_int
+    lib.vk_tone_reset.argtypes = [C.c_void_p]
+    lib.vk_tone_get_info.restype = C.c_int
+    lib.vk_tone_get_info.argtypes = [C.c_void_p, C.POINTER(ToneInfo)]
+    lib.vk_tone_destroy.restype = None
+    lib.vk_tone_destroy.argtypes = [C.c_void_p]
     lib.vk_matte_default_params.restype = C.c_int
     lib.vk_matte_default_params.argtypes = [C.POINTER(MatteParams)]
     lib.vk_render_mattes.restype = C.c_int
@@ -709,6 +766,14 @@ def _bind(lib):
     lib.vk_debug_lpe_set_tags.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vk_debug_lpe_last_ms.restype = C.c_int
     lib.vk_debug_lpe_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 3)]
+    lib.vk_debug_tone_histogram.restype = C.c_int
+    lib.vk_debug_tone_histogram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_debug_tone_table.restype = C.c_int
+    lib.vk_debug_tone_table.argtypes = [C.c_uint32, C.c_void_p]
+    lib.vk_debug_tone_set_form.restype = C.c_int
+    lib.vk_debug_tone_set_form.argtypes = [C.c_void_p, C.c_uint32]
+    lib.vk_debug_tone_last_ms.restype = C.c_int
+    lib.vk_debug_tone_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 2)]
     lib.vk_debug_matte_samples.restype = C.c_int
     lib.vk_debug_matte_samples.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.c_void_p]
     lib.vk_debug_trace_occluded_device.restype = C.c_int

@@ -2,7 +2,7 @@
 // scene, build the BVH, upload once, then per Camera of cam_iter: render through the C ABI
 // (the call that replaces main.rs:181-198), write output_%04d.ppm, print the frame time.
 // The reference hard-codes scene/width/spp/depth (main.rs:28-29,159-167,171); here they are
-// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0] [guide_bounces=0]
+// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0] [guide_bounces=0] [display=0]
 // steps > 1: each frame is rendered progressively (vk_progress_*) in `steps` equal sample windows; after each window the running image
 // is written to output_%04d_step%02d.ppm and the samples done and the image's mean relative standard error are printed.  The final
 // output_%04d.ppm is byte-identical to the one of steps = 1.
@@ -19,6 +19,10 @@
 // the other parameters the library's defaults) are written as output_%04d_guide_albedo.pfm, _guide_normal.pfm, _guide_depth.pfm and
 // _guide_bounces.pfm, and the temporal and denoise steps take their albedo, normal and depth from them instead of from the first-hit
 // buffers.  0 or absent: no such call is made and every file is what it was.
+// display = 1, 2 or 3: each frame's last float image — the denoised one, else the temporally accumulated one, else the plain frame — also
+// goes through the display transform (vk_tone_*): metered with the library's default parameters (over an animation, frames > 1, with
+// blend 0.25, so that the exposure follows the frames smoothly), encoded with the Reinhard (1), Hable (2) or ACES (3) curve, the metered
+// exposure and the sRGB transfer, and written as output_%04d_display.ppm.  display = 0 or absent: every file is what it was.
 // Texture images are read from ./assets (as in the reference) or $VECCHIO_ASSETS: <name>.ppm.gz, see host_api.h.
 #include <dlfcn.h>
 
@@ -41,6 +45,15 @@ static bool write_pfm(const char *fn, const float *data, uint32_t width, uint32_
     return fclose(f) == 0 && ok;
 }
 
+// the display transform's 8-bit codes (row 0 the top) in vkh_write_ppm's P3 layout
+static bool write_ppm_codes(const char *fn, const uint8_t *rgb8, uint32_t width, uint32_t height) {
+    FILE *f = fopen(fn, "w");
+    if (!f) { fprintf(stderr, "cannot write %s\n", fn); return false; }
+    fprintf(f, "P3\n%u %u\n255\n", width, height);
+    for (size_t i = 0; i < (size_t)width * height; i++) fprintf(f, "%u %u %u\n", rgb8[i * 3], rgb8[i * 3 + 1], rgb8[i * 3 + 2]);
+    return fclose(f) == 0;
+}
+
 template <class T>
 static T sym(void *h, const char *name) {
     void *p = dlsym(h, name);
@@ -51,7 +64,7 @@ static T sym(void *h, const char *name) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <balls_demo|random_spheres_demo|random_spheres_iow|perlin_demo|bowser_demo|cornell_box|final_scene|"
-                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal] [guide_bounces]\n", argv[0]);
+                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal] [guide_bounces] [display]\n", argv[0]);
         return 2;
     }
     const char *name = argv[1];
@@ -65,6 +78,11 @@ int main(int argc, char **argv) {
     const bool denoise = argc > 9 && atoi(argv[9]) != 0;
     const bool temporal = argc > 10 && atoi(argv[10]) != 0;
     const uint32_t guide_bounces = argc > 11 ? (uint32_t)atoi(argv[11]) : 0;
+    const uint32_t display = argc > 12 ? (uint32_t)atoi(argv[12]) : 0;
+    if (display > 3) {
+        fprintf(stderr, "display is 0 (off), 1 (Reinhard), 2 (Hable) or 3 (ACES)\n");
+        return 2;
+    }
     if (steps < 1) steps = 1;
     if (steps > spp) steps = spp;                                     // every window holds at least one sample
     if (denoise && (steps < 2 || aov_spp == 0)) {
@@ -107,6 +125,13 @@ int main(int argc, char **argv) {
                                 float *, float *, float *, vk_stats *)>(h, "vk_temporal_accumulate");
     auto p_tinfo = sym<int (*)(vk_temporal *, vk_temporal_info *)>(h, "vk_temporal_get_info");
     auto p_tdestroy = sym<void (*)(vk_temporal *)>(h, "vk_temporal_destroy");
+    auto p_tone_mdefaults = sym<int (*)(vk_tone_meter_params *)>(h, "vk_tone_default_meter_params");
+    auto p_tone_defaults = sym<int (*)(vk_tone_params *)>(h, "vk_tone_default_params");
+    auto p_tone_create = sym<int (*)(vk_scene *, uint32_t, uint32_t, vk_tone **)>(h, "vk_tone_create");
+    auto p_tone_load = sym<int (*)(vk_tone *, const float *)>(h, "vk_tone_load");
+    auto p_tone_meter = sym<int (*)(vk_tone *, const vk_tone_meter_params *, vk_tone_meter_info *)>(h, "vk_tone_meter");
+    auto p_tone_encode = sym<int (*)(vk_tone *, const vk_tone_params *, uint8_t *)>(h, "vk_tone_encode");
+    auto p_tone_destroy = sym<void (*)(vk_tone *)>(h, "vk_tone_destroy");
 
     fprintf(stderr, "Generating scene...\n");                        // main.rs:157
     vkh_scene *hs = vkh_scene_build(name, seed);
@@ -129,6 +154,8 @@ int main(int argc, char **argv) {
         if (p_tp_defaults(width, height, &tp) != VK_OK || p_tcreate(scene, &tp, &history) != VK_OK) {
             fprintf(stderr, "vk_temporal_create: %s\n", p_err()); return 1; }
     }
+    vk_tone *tone = nullptr;
+    if (display && p_tone_create(scene, width, height, &tone) != VK_OK) { fprintf(stderr, "vk_tone_create: %s\n", p_err()); return 1; }
     vk_camera cam;
     int file_idx = 0;
     while (file_idx < frames && vkh_scene_next_camera(hs, &cam)) {   // main.rs:176
@@ -167,6 +194,7 @@ int main(int argc, char **argv) {
         char fn[64];
         snprintf(fn, sizeof fn, "output_%04d.ppm", file_idx);         // main.rs:201
         if (vkh_write_ppm(fn, pixels.data(), width, height)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }
+        std::vector<float> shown;                                     // the last stage's float frame (display): empty = `pixels`
         if (aov_spp > 0) {
             const size_t np = (size_t)width * height;
             std::vector<float> albedo(np * 3), normal(np * 3), zdepth(np), coverage(np);
@@ -223,6 +251,7 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "  accumulated: %.1f %% of the pixels with history, kernel %.2f ms\n",
                         100.0 * (double)ti.pixels_with_history / (double)np, ts.kernel_ms);
                 dn_color = acc.data(); dn_err = acc_err.data();
+                if (display) shown = acc;
             }
             if (denoise) {
                 vk_denoise_params dp;
@@ -237,13 +266,31 @@ int main(int argc, char **argv) {
                 snprintf(dfn, sizeof dfn, "output_%04d_denoised.pfm", file_idx);
                 if (!write_pfm(dfn, clean.data(), width, height, 3)) return 1;
                 fprintf(stderr, "  denoised (%u levels): kernels %.2f ms\n", dp.levels, ds.kernel_ms);
+                if (display) shown = clean;
             }
+        }
+        if (display) {
+            vk_tone_meter_params mp;
+            vk_tone_params tp;
+            vk_tone_meter_info mi{};
+            std::vector<uint8_t> codes((size_t)width * height * 3);
+            if (p_tone_mdefaults(&mp) != VK_OK || p_tone_defaults(&tp) != VK_OK) { fprintf(stderr, "vk_tone defaults: %s\n", p_err()); return 1; }
+            if (frames > 1) mp.blend = 0.25f;
+            tp.curve = display == 1 ? VK_TONE_REINHARD : display == 2 ? VK_TONE_HABLE : VK_TONE_ACES;
+            if (p_tone_load(tone, shown.empty() ? pixels.data() : shown.data()) != VK_OK || p_tone_meter(tone, &mp, &mi) != VK_OK ||
+                p_tone_encode(tone, &tp, codes.data()) != VK_OK) {
+                fprintf(stderr, "vk_tone: %s\n", p_err()); return 1; }
+            char sfn[64];
+            snprintf(sfn, sizeof sfn, "output_%04d_display.ppm", file_idx);
+            if (!write_ppm_codes(sfn, codes.data(), width, height)) return 1;
+            fprintf(stderr, "  display: exposure %.4g (log2 luminance %.3f, target %.3f)\n", (double)mi.exposure, mi.log2_used, mi.log2_target);
         }
         double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
         fprintf(stderr, "Wrote frame %s in %.3fs (kernel %.1f ms, %.1f Msamples/s)\n", fn, secs, st.kernel_ms,
                 st.kernel_ms > 0 ? (double)st.samples / st.kernel_ms / 1e3 : 0.0);   // main.rs:215
         file_idx++;
     }
+    if (tone) p_tone_destroy(tone);
     if (history) p_tdestroy(history);
     p_destroy(scene);
     vkh_scene_free(hs);

@@ -189,6 +189,29 @@ pub struct vk_lpe_params { pub n_layers: u32, pub rest_layer: u32, pub n_rules: 
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_lpe_info { pub width: u32, pub height: u32, pub samples_per_pixel: u32, pub n_layers: u32, pub rest_layer: u32, pub n_rules: u32, pub capacity: u64, pub deposited: u64, pub dropped: u64, pub clamped: u64, pub skipped: u64, pub deposits: u64, pub recorded: u64 }
 
+// display transform: the meter's and the encode's parameters, what a meter found, a handle's counts
+pub const VK_TONE_CLAMP: u32 = 0;
+pub const VK_TONE_REINHARD: u32 = 1;
+pub const VK_TONE_HABLE: u32 = 2;
+pub const VK_TONE_ACES: u32 = 3;
+pub const VK_TONE_TRANSFER_REFERENCE: u32 = 0;
+pub const VK_TONE_TRANSFER_SRGB: u32 = 1;
+pub const VK_TONE_TRANSFER_GAMMA22: u32 = 2;
+pub const VK_TONE_USE_METERED: u32 = 1;
+pub const VK_TONE_DITHER: u32 = 2;
+pub const VK_TONE_METER_EMPTY: u32 = 1;
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_tone_meter_params { pub key: f32, pub low_fraction: f32, pub high_fraction: f32, pub blend: f32, pub min_log2: f32, pub max_log2: f32, pub _pad: [u32; 2] }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_tone_meter_info { pub log2_target: f64, pub log2_used: f64, pub binned: u64, pub below: u64, pub above: u64, pub nonfinite: u64, pub exposure: f32, pub flags: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_tone_params { pub curve: u32, pub transfer: u32, pub flags: u32, pub _pad: u32, pub exposure: f32, pub white: f32, pub seed: u64 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_tone_info { pub width: u32, pub height: u32, pub loads: u64, pub meters: u64, pub encodes: u64, pub exposure: f32, pub metered: u32, pub log2_used: f64 }
+
 // regeneration: what one vk_regen_step did
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_regen_info { pub traced: u64, pub live: u64, pub remaining: u64, pub emitted: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
@@ -207,6 +230,7 @@ pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, 
 #[repr(C)] pub struct vk_splat { _private: [u8; 0] }
 #[repr(C)] pub struct vk_robust { _private: [u8; 0] }
 #[repr(C)] pub struct vk_lpe { _private: [u8; 0] }
+#[repr(C)] pub struct vk_tone { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -339,6 +363,21 @@ extern "C" {
     pub fn vk_lpe_reset(s: *mut vk_lpe) -> c_int;
     pub fn vk_lpe_get_info(s: *mut vk_lpe, out: *mut vk_lpe_info) -> c_int;
     pub fn vk_lpe_destroy(s: *mut vk_lpe);
+    // display transform (additive symbols of ABI 7): a frame's luminance histogram and metered exposure, and its encoding through a tone
+    // curve and a transfer to width * height * 3 bytes, row 0 the top; load_device and encode_device are enqueued on the null stream;
+    // solve is host code (bins: 640 words; prev_log2: null for a first meter)
+    pub fn vk_tone_default_meter_params(out: *mut vk_tone_meter_params) -> c_int;
+    pub fn vk_tone_default_params(out: *mut vk_tone_params) -> c_int;
+    pub fn vk_tone_create(scene: *mut vk_scene, width: u32, height: u32, out: *mut *mut vk_tone) -> c_int;
+    pub fn vk_tone_load(t: *mut vk_tone, rgb: *const f32) -> c_int;
+    pub fn vk_tone_load_device(t: *mut vk_tone, d_rgb: *const c_void) -> c_int;
+    pub fn vk_tone_meter(t: *mut vk_tone, mp: *const vk_tone_meter_params, out: *mut vk_tone_meter_info) -> c_int;
+    pub fn vk_tone_solve(bins: *const u32, mp: *const vk_tone_meter_params, prev_log2: *const f64, out: *mut vk_tone_meter_info) -> c_int;
+    pub fn vk_tone_encode(t: *mut vk_tone, tp: *const vk_tone_params, rgb8_out: *mut u8) -> c_int;
+    pub fn vk_tone_encode_device(t: *mut vk_tone, tp: *const vk_tone_params, d_rgb8_out: *mut c_void) -> c_int;
+    pub fn vk_tone_reset(t: *mut vk_tone) -> c_int;
+    pub fn vk_tone_get_info(t: *mut vk_tone, out: *mut vk_tone_info) -> c_int;
+    pub fn vk_tone_destroy(t: *mut vk_tone);
     // ID mattes (additive symbols of ABI 7): a ranked table of object or material ids per pixel, ids / counts ranks words per pixel,
     // overflow one (may be null); merge and mask are host code
     pub fn vk_matte_default_params(out: *mut vk_matte_params) -> c_int;

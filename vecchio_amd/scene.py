@@ -675,6 +675,12 @@ class DeviceScene:
             rest_layer = STANDARD_LAYERS.index("rest") if rest_layer is None else rest_layer
         return LightPathLayers(self, width, height, spp, capacity, rules, n_layers, 0 if rest_layer is None else rest_layer)
 
+    def tone(self, width, height):
+        """A display transform on this scene's device (vk_tone_create) for frames of width x height: auto-exposure from a luminance
+        histogram, a tone curve (clamp, Reinhard, Hable, ACES) and a transfer (the reference's, sRGB, gamma 2.2; optionally dithered) to
+        8-bit codes.  Use as a context manager, or close() it before the scene."""
+        return Tone(self, width, height)
+
     def debug_compact_paths(self, items, ids, n_ids, canary=0xA5, roulette=None):
         """The compaction of a path batch's bounce on host arrays (vk_debug_compact_paths, a test hook): items a SHADED_DTYPE array, ids
         their uint32 ids (each below n_ids).  Every output is prefilled with the byte `canary`.  Returns (rays, states, ids_out — n
@@ -1414,6 +1420,129 @@ class Robust:
 
 STANDARD_LAYERS = ("emission", "sky", "direct_diffuse", "direct_specular", "volume", "indirect", "rest")
 _ANY_STATUS = (ffi.VK_SHADE_MISS, ffi.VK_SHADE_ENDED, ffi.VK_PATHS_CULLED)
+
+
+class Tone:
+    """vk_tone handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed): the display transform of one
+    width x height.  load() or load_device() a float frame (y = 0 the bottom row), meter() its exposure from a luminance histogram,
+    encode() it through a tone curve and a transfer to uint8 (height, width, 3), row 0 the top, as VK_OUTPUT_RGB8.  With
+    ffi.VK_TONE_CLAMP, ffi.VK_TONE_TRANSFER_REFERENCE and no metering the bytes are vk_to_color_device's."""
+
+    def __init__(self, scene, width, height):
+        self._lib = scene._lib
+        self._scene = scene
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_tone_create(scene._h, width, height, C.byref(h)))
+        self._h = h
+
+    def load(self, rgb):
+        """The frame from host memory (vk_tone_load): float32, width * height * 3 values."""
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        assert rgb.size == self.width * self.height * 3
+        check(self._lib, self._lib.vk_tone_load(self._h, rgb.ctypes.data_as(C.c_void_p)))
+
+    def load_device(self, d_rgb):
+        """The frame from memory of the handle's device (vk_tone_load_device, enqueued on the null stream): a contiguous float32 tensor
+        (an object with data_ptr()) of width * height * 3 values, or a device pointer."""
+        if hasattr(d_rgb, "data_ptr"):
+            assert d_rgb.is_contiguous() and d_rgb.numel() == self.width * self.height * 3 and d_rgb.element_size() == 4
+            d_rgb = d_rgb.data_ptr()
+        check(self._lib, self._lib.vk_tone_load_device(self._h, C.c_void_p(d_rgb)))
+
+    @staticmethod
+    def meter_params(**kw):
+        """ffi.ToneMeterParams: the library's defaults (a loaded library is needed) with the given fields replaced"""
+        mp = ffi.ToneMeterParams()
+        lib = ffi.load_device_lib()
+        check(lib, lib.vk_tone_default_meter_params(C.byref(mp)))
+        for k, v in kw.items():
+            setattr(mp, k, v)
+        return mp
+
+    @staticmethod
+    def params(**kw):
+        """ffi.ToneParams: the library's defaults (ACES, sRGB, the metered exposure) with the given fields replaced"""
+        tp = ffi.ToneParams()
+        lib = ffi.load_device_lib()
+        check(lib, lib.vk_tone_default_params(C.byref(tp)))
+        for k, v in kw.items():
+            setattr(tp, k, v)
+        return tp
+
+    def meter(self, params=None, **kw):
+        """Meter the loaded frame (vk_tone_meter): the histogram on the device, the exposure on the host.  params: an
+        ffi.ToneMeterParams, or keywords over the defaults (key, low_fraction, high_fraction, blend, min_log2, max_log2).  Returns the
+        ffi.ToneMeterInfo."""
+        mp = params if params is not None else self.meter_params(**kw)
+        info = ffi.ToneMeterInfo()
+        check(self._lib, self._lib.vk_tone_meter(self._h, C.byref(mp), C.byref(info)))
+        return info
+
+    def encode(self, params=None, out=None, **kw):
+        """The loaded frame as display codes (vk_tone_encode): uint8 (height, width, 3), row 0 the top.  params: an ffi.ToneParams, or
+        keywords over the defaults (curve, transfer, flags, exposure, white, seed)."""
+        tp = params if params is not None else self.params(**kw)
+        if out is None:
+            out = np.zeros((self.height, self.width, 3), np.uint8)
+        assert out.dtype == np.uint8 and out.flags.c_contiguous and out.size == self.width * self.height * 3
+        check(self._lib, self._lib.vk_tone_encode(self._h, C.byref(tp), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def encode_device(self, d_out, params=None, **kw):
+        """The codes into memory of the handle's device (vk_tone_encode_device, enqueued on the null stream): a contiguous uint8 tensor of
+        width * height * 3 values, or a 4-byte aligned device pointer.  Returns d_out."""
+        tp = params if params is not None else self.params(**kw)
+        ptr = d_out
+        if hasattr(d_out, "data_ptr"):
+            assert d_out.is_contiguous() and d_out.numel() == self.width * self.height * 3 and d_out.element_size() == 1
+            ptr = d_out.data_ptr()
+        check(self._lib, self._lib.vk_tone_encode_device(self._h, C.byref(tp), C.c_void_p(ptr)))
+        return d_out
+
+    def reset(self):
+        """Forget the metered exposure and the frame (vk_tone_reset): the next meter is a first one."""
+        check(self._lib, self._lib.vk_tone_reset(self._h))
+
+    def info(self):
+        inf = ffi.ToneInfo()
+        check(self._lib, self._lib.vk_tone_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def histogram(self):
+        """The last meter's (bins (640,) uint32, counters (4,) uint64: binned, below, above, nonfinite) (vk_debug_tone_histogram, a test
+        hook)"""
+        bins, counters = np.zeros(640, np.uint32), np.zeros(4, np.uint64)
+        check(self._lib, self._lib.vk_debug_tone_histogram(self._h, bins.ctypes.data_as(C.c_void_p), counters.ctypes.data_as(C.c_void_p)))
+        return bins, counters
+
+    def set_form(self, form):
+        """The meter kernel's form, ffi.VK_TONE_FORM_LDS or _PLAIN (vk_debug_tone_set_form, a test hook)"""
+        check(self._lib, self._lib.vk_debug_tone_set_form(self._h, form))
+
+    def last_ms(self):
+        """(meter, encode) device milliseconds of the last kernel of each (vk_debug_tone_last_ms, a test hook)"""
+        ms = (C.c_double * 2)()
+        check(self._lib, self._lib.vk_debug_tone_last_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
+    def close(self):
+        if self._h:
+            self._lib.vk_tone_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 
 def lpe_rule(layer, sig_mask=0, sig_value=0, status=_ANY_STATUS, depth=(0, 0xFFFFFFFF), emitter=None):
