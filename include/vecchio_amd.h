@@ -1507,6 +1507,83 @@ int vk_tone_reset(vk_tone *t);
 int vk_tone_get_info(vk_tone *t, vk_tone_info *out);
 void vk_tone_destroy(vk_tone *t);
 
+/* ---- non-local means: denoising a frame from its own standard error (additive symbols of ABI 7) -------------------------------------
+ * replaces: nothing.  The spatial filter for frames whose first-hit buffers say little (small textured, glass and metal objects): its
+ * weights come from the colour image and its variance alone, by variance-cancelling patch distances (Rousselle, Knaus, Zwicker 2012).
+ * The stderr3 of vk_progress_stderr, vk_adapt_stderr, vk_robust_resolve or vk_temporal_* goes in with the frame; a filtered frame and
+ * its propagated standard error come out, in the shapes vk_denoise and vk_tone_load take.
+ *
+ * State.  A handle for one width x height on the scene's device (devices[0] of a multi-device scene, on the whole image): a copy of
+ * the loaded images and four planes of three floats a pixel (I, V, Vf, a below) that vk_nlm_load fills from it — 84 bytes a pixel —, so
+ * that a second vk_nlm_filter with other parameters needs no reload and the caller's buffers may be reused after the load.  The planes
+ * are prepared with the albedo_floor of the last filter (1e-3 before one); a filter with another floor prepares them again from the
+ * handle's copy first, one more kernel.  All work is on the null stream there; no function takes a stream.  vk_nlm_load_device and
+ * vk_nlm_filter_device are ordered exactly as vk_tone_load_device and vk_tone_encode_device are: ENQUEUED on the null stream: work the
+ * caller issued earlier on the null stream or on a blocking stream is ordered before them, and the outputs are ready when the null
+ * stream is; a caller with a non-blocking stream synchronises first (and waits for the null stream afterwards).  Every other call
+ * waits.
+ *
+ * The filter, exactly.  Everything is f32, unfused, in the order written, with + - * /, sqrtf, fmaxf, fminf (each returns its other
+ * argument when one is a NaN) and compares only; tests/nlm_ref.py restates it in numpy and the two agree bit for bit (a NaN's payload
+ * aside).  All images are in vk_render's layout (y = 0 the bottom row), 3 floats per pixel.  E(x) = t^8 with t = fmaxf(0, 1 - x *
+ * 0.125f), by three squarings: vk_denoise's.
+ *   Prepare (vk_nlm_load), per pixel p.  a_c = fmaxf(albedo_c, albedo_floor), or 1 without albedo; I_c = color_c / a_c; s_c = stderr_c /
+ *     a_c, V_c = s_c * s_c, per channel (not vk_denoise's luminance variance).  p is INVALID if a component of color or stderr3 is not
+ *     finite: it is never a neighbour and never part of a patch, its out is its color and its stderr3_out its stderr3, unchanged.
+ *     Vf_c(p) = (sum of k3 * V_c(q)) / (sum of k3) over the 3x3 adjacent pixels q that are in the image and valid, rows bottom to top, x
+ *     ascending, k3 = (1 2 1; 2 4 2; 1 2 1), both sums from 0: vk_denoise's Vg, per channel.
+ *   Pair term, for valid a and b, kk = k * k (once, on the host).  Per channel d = I_c(a) - I_c(b); num = d * d - alpha * (Vf_c(a) +
+ *     fminf(Vf_c(a), Vf_c(b))); den = 1e-10f + kk * (Vf_c(a) + Vf_c(b)).  e(a, b) = ((num_r / den_r) + (num_g / den_g)) + (num_b /
+ *     den_b), c(a, b) = 1.  If a or b is outside the image or invalid: e = 0, c = 0.
+ *   Filter (vk_nlm_filter), per valid p.  Offsets o = (ox, oy), oy = -R..R outer, ox = -R..R inner, ascending, q = p + o; offsets whose
+ *     q is outside the image or invalid are skipped.  The centre offset has w = 1.  For the others, the patch sum, rows first: for j =
+ *     -F..F ascending: r = 0, m = 0; for i = -F..F ascending: r += e(p + (i, j), q + (i, j)), m += c(...); then S += r, n += m (S and n
+ *     from 0, n an integer).  D = S / (float)(3 * n)  (n >= 1: the pair (p, q) counts).  w = E(fmaxf(0, D)), and w = 0 if D is a NaN.
+ *     In offset order from 0: W += w, J_c += w * I_c(q), U_c += (w * w) * V_c(q)  (the unfiltered V).
+ *     out_c = (J_c / W) * a_c, stderr3_out_c = (sqrtf(U_c) / W) * a_c.
+ *   The row-then-column order is part of the definition: a form that shares row sums between neighbouring pixels agrees bit for bit
+ *   with one that does not (the kernel has both: DESIGN.md "Non-local means").
+ * What this is not.  No cross-filtering between two half buffers, no feature-buffer terms in the weights, no multi-scale passes.
+ *
+ *   vk_nlm_default_params: search_radius 7, patch_radius 3, k 0.45, alpha 1, albedo_floor 1e-3, flags 0.  Touches no device.
+ *   vk_nlm_create: VK_ERR_BAD_ARG for a null pointer, width or height 0, a size beyond vk_render's limits (width or height > 65535,
+ *     width * height * 3 > 2^31).  VK_ERR_OOM leaves *out untouched.
+ *   vk_nlm_load / vk_nlm_load_device: color and stderr3 are required (without a variance the filter is meaningless), albedo may be
+ *     NULL; from the host (through the staging path of the host-pointer calls; waits) or from memory of the handle's device (enqueued).
+ *     VK_ERR_BAD_ARG for a null handle, color or stderr3.
+ *   vk_nlm_filter / vk_nlm_filter_device: VK_ERR_BAD_ARG, nothing enqueued and the outputs untouched, for a null handle, params or
+ *     rgb_out (stderr3_out may be NULL), search_radius outside 1..10, patch_radius outside 0..3, k not finite or <= 0, alpha not finite
+ *     or < 0, albedo_floor not finite or <= 0, flags != 0, a filter before a load.
+ *   vk_nlm_reset forgets the frame: the next filter needs a load.  vk_nlm_destroy(NULL) does nothing.                                 */
+typedef struct vk_nlm vk_nlm;            /* opaque */
+typedef struct vk_nlm_params {           /* 24 bytes */
+    uint32_t search_radius;              /* R: 1..10; the window is (2R + 1)^2 offsets */
+    uint32_t patch_radius;               /* F: 0..3; a patch is (2F + 1)^2 pixels */
+    float k;                             /* the distance's scale: larger smooths more */
+    float alpha;                         /* how much of the variance is cancelled from the squared difference */
+    float albedo_floor;                  /* > 0: demodulation divides by max(albedo, albedo_floor) */
+    uint32_t flags;                      /* 0 */
+} vk_nlm_params;
+typedef struct vk_nlm_info {             /* 56 bytes */
+    uint32_t width, height;
+    uint32_t loaded;                     /* 1 between a load and the next reset */
+    uint32_t has_albedo;                 /* 1 if the loaded frame came with an albedo */
+    uint64_t loads, filters;             /* accepted calls since create */
+    uint32_t last_launches;              /* the kernels the last accepted call launched */
+    uint32_t last_form;                  /* VK_NLM_FORM_PLAIN or VK_NLM_FORM_TILED of the last filter; 0 before one */
+    double last_kernel_ms;               /* the last filter kernel's device time; 0 before one (waits for it) */
+    uint64_t scratch_bytes;              /* the device memory the handle owns */
+} vk_nlm_info;
+int vk_nlm_default_params(vk_nlm_params *out);
+int vk_nlm_create(vk_scene *scene, uint32_t width, uint32_t height, vk_nlm **out);
+int vk_nlm_load(vk_nlm *h, const float *color, const float *stderr3, const float *albedo);
+int vk_nlm_load_device(vk_nlm *h, const void *d_color, const void *d_stderr3, const void *d_albedo);
+int vk_nlm_filter(vk_nlm *h, const vk_nlm_params *p, float *rgb_out, float *stderr3_out);
+int vk_nlm_filter_device(vk_nlm *h, const vk_nlm_params *p, void *d_rgb_out, void *d_stderr3_out);
+int vk_nlm_reset(vk_nlm *h);
+int vk_nlm_get_info(vk_nlm *h, vk_nlm_info *out);
+void vk_nlm_destroy(vk_nlm *h);
+
 /* ---- denoising a frame from its error estimate and first-hit buffers (additive symbols of ABI 7) ------------------------------------
  * replaces: nothing.  The consumer of vk_progress_stderr and vk_render_aov: an edge-avoiding, variance-guided a-trous wavelet filter
  * (the spatial half of SVGF: one frame, no history) on the device.  All images are in vk_render's f32 layout (y = 0 the bottom row):

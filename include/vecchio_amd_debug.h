@@ -203,6 +203,16 @@ int vk_debug_tone_set_form(vk_tone *t, uint32_t form);
  * two events around each; 0 for one that has not run.  Waits for those.  Takes no stream.  In both libraries. */
 int vk_debug_tone_last_ms(vk_tone *t, double ms[2]);
 
+/* the form of vk_nlm_filter's kernel from the next call on: PLAIN = one lane per pixel, the definition straight from global memory;
+ * TILED = a workgroup per tile, the frame staged in LDS and the patch sums shared between neighbouring pixels; AUTO (the default) = per
+ * (search_radius, patch_radius) the one measured faster (DESIGN.md "Non-local means").  All give the same bits.  VK_ERR_BAD_ARG for a
+ * null handle or another form.  In both libraries. */
+enum { VK_NLM_FORM_AUTO = 0, VK_NLM_FORM_PLAIN = 1, VK_NLM_FORM_TILED = 2 };
+int vk_debug_nlm_set_form(vk_nlm *h, uint32_t form);
+/* the device milliseconds of the handle's last prepare kernel (ms[0]) and filter kernel (ms[1]: without copies), between two events
+ * around each; 0 for one that has not run.  Waits for those.  Takes no stream.  In both libraries. */
+int vk_debug_nlm_last_ms(vk_nlm *h, double ms[2]);
+
 /* the id of every sample vk_render_mattes would count, by the same per-lane code on the same lanes: ids_out[(y * width + x) * spp + k] is
  * the id of sample first_sample + k under `kind` (VK_MATTE_OBJECT or VK_MATTE_MATERIAL), spp = params->samples_per_pixel; pixels outside
  * the call's tile partition are left untouched.  vk_render_mattes' checks.  Waits.  In both libraries. */

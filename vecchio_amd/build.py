@@ -76,7 +76,8 @@ def _device_deps():
     srcs = [os.path.join(CSRC, "vk_api.hip"), os.path.join(CSRC, "vk_linearize.cpp")]
     return srcs, srcs + [os.path.join(CSRC, f) for f in ("vk_kernels.h", "vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_resources.h",
                                                          "vk_emit.h", "vk_adapt.h", "vk_adapt.hip", "vk_splat.h", "vk_splat.hip", "vk_matte.h",
-                                                         "vk_matte.hip", "vk_robust.h", "vk_robust.hip", "vk_lpe.h", "vk_lpe.hip", "vk_tone.h", "vk_tone.hip")] + \
+                                                         "vk_matte.hip", "vk_robust.h", "vk_robust.hip", "vk_lpe.h", "vk_lpe.hip", "vk_tone.h", "vk_tone.hip",
+                                                         "vk_nlm.h", "vk_nlm.hip")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
 
 
@@ -88,7 +89,8 @@ def device_is_stale():
     return _newer(os.path.join(LIB, "libvecchio_amd.so"), _device_deps()[1], HIPFLAGS) or not os.path.exists(kernel_resources_path()) or \
         not os.path.exists(kernel_resources_adapt_path()) or not os.path.exists(kernel_resources_splat_path()) or \
         not os.path.exists(kernel_resources_matte_path()) or not os.path.exists(kernel_resources_robust_path()) or \
-        not os.path.exists(kernel_resources_lpe_path()) or not os.path.exists(kernel_resources_tone_path())
+        not os.path.exists(kernel_resources_lpe_path()) or not os.path.exists(kernel_resources_tone_path()) or \
+        not os.path.exists(kernel_resources_nlm_path())
 
 
 def build_host(force=False):
@@ -123,7 +125,7 @@ def build_device_debug(force=False):
     flags = HIPFLAGS + ["-DVK_DEBUG_LIB"]
     if force or _newer(out, deps, flags):
         os.makedirs(LIB, exist_ok=True)
-        _run_atomic([HIPCC] + flags + ["-shared", "-o"], out, srcs + [_adapt_src(), _splat_src(), _matte_src(), _robust_src(), _lpe_src(), _tone_src()])
+        _run_atomic([HIPCC] + flags + ["-shared", "-o"], out, srcs + [_adapt_src(), _splat_src(), _matte_src(), _robust_src(), _lpe_src(), _tone_src(), _nlm_src()])
         _stamp(out, deps, flags)
     return out
 
@@ -164,6 +166,12 @@ def _tone_src():
     return os.path.join(CSRC, "vk_tone.hip")
 
 
+def _nlm_src():
+    """the kernels of vk_nlm_* (non-local means: the prepare pass into the handle's planes and the filter in its two forms): a translation
+    unit of its own"""
+    return os.path.join(CSRC, "vk_nlm.hip")
+
+
 def _hipcc_with_remarks(cmd, cwd, cleanup=()):
     """runs a hipcc line that carries -Rpass-analysis=kernel-resource-usage and -save-temps in `cwd`: (the remark lines, kernel symbol ->
     scratch instructions from the gfx950 assembly it left there); everything else it wrote to stderr is passed on"""
@@ -198,10 +206,10 @@ def _write_resources(path, remarks, spills):
 
 
 def build_device(force=False):
-    """hipcc cross-compiles for gfx950 without a GPU present.  Seven steps: vk_adapt.hip, vk_splat.hip, vk_matte.hip, vk_robust.hip,
-    vk_lpe.hip and vk_tone.hip to an object of their own each (their resource remarks go to kernel_resources_adapt.txt,
-    kernel_resources_splat.txt, kernel_resources_matte.txt, kernel_resources_robust.txt, kernel_resources_lpe.txt and
-    kernel_resources_tone.txt), then vk_api.hip and vk_linearize.cpp, linked with those objects (kernel_resources.txt: theirs alone)."""
+    """hipcc cross-compiles for gfx950 without a GPU present.  Eight steps: vk_adapt.hip, vk_splat.hip, vk_matte.hip, vk_robust.hip,
+    vk_lpe.hip, vk_tone.hip and vk_nlm.hip to an object of their own each (their resource remarks go to kernel_resources_adapt.txt,
+    kernel_resources_splat.txt, kernel_resources_matte.txt, kernel_resources_robust.txt, kernel_resources_lpe.txt,
+    kernel_resources_tone.txt and kernel_resources_nlm.txt), then vk_api.hip and vk_linearize.cpp, linked with those objects (kernel_resources.txt: theirs alone)."""
     out = os.path.join(LIB, "libvecchio_amd.so")
     srcs, deps = _device_deps()
     if force or device_is_stale():
@@ -233,9 +241,13 @@ def build_device(force=False):
             lpe = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", lpe_obj, _lpe_src()], tmp_lpe)
             tone_obj = os.path.join(tmp_tone, "vk_tone.o")
             tone = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", tone_obj, _tone_src()], tmp_tone)
+            tmp_nlm = os.path.join(tmp, "nlm")
+            os.makedirs(tmp_nlm)
+            nlm_obj = os.path.join(tmp_nlm, "vk_nlm.o")
+            nlm = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", nlm_obj, _nlm_src()], tmp_nlm)
             tmp_out = f"{out}.tmp.{os.getpid()}"
             # (the objects in front of the sources: hipcc reads whatever follows a source file as HIP)
-            main = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-shared", "-o", tmp_out, adapt_obj, splat_obj, matte_obj, robust_obj, lpe_obj, tone_obj] + srcs, tmp_main, [tmp_out])
+            main = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-shared", "-o", tmp_out, adapt_obj, splat_obj, matte_obj, robust_obj, lpe_obj, tone_obj, nlm_obj] + srcs, tmp_main, [tmp_out])
             os.replace(tmp_out, out)
         _write_resources(kernel_resources_path(), *main)
         _write_resources(kernel_resources_adapt_path(), *adapt)
@@ -244,6 +256,7 @@ def build_device(force=False):
         _write_resources(kernel_resources_robust_path(), *robust)
         _write_resources(kernel_resources_lpe_path(), *lpe)
         _write_resources(kernel_resources_tone_path(), *tone)
+        _write_resources(kernel_resources_nlm_path(), *nlm)
         _stamp(out, deps, HIPFLAGS)
     return out
 
@@ -290,6 +303,11 @@ def kernel_resources_tone_path():
     return os.path.join(LIB, "kernel_resources_tone.txt")
 
 
+def kernel_resources_nlm_path():
+    """the same record for the kernels of vk_nlm.hip"""
+    return os.path.join(LIB, "kernel_resources_nlm.txt")
+
+
 def build_oracle(force=False):
     """CPU oracle (test infrastructure).  oracle/_ref does not exist: the reference is Rust and
     there is no cargo/rustc in this image."""
@@ -312,11 +330,11 @@ def build_emu(force=False):
             os.path.join(edir, "emu_irradiance.cpp"), os.path.join(edir, "emu_probes.cpp"), os.path.join(edir, "emu_shade.cpp"),
             os.path.join(edir, "emu_paths.cpp"), os.path.join(edir, "emu_film.cpp"), os.path.join(edir, "emu_adapt.cpp"),
             os.path.join(edir, "emu_splat.cpp"), os.path.join(edir, "emu_matte.cpp"), os.path.join(edir, "emu_robust.cpp"),
-            os.path.join(edir, "emu_lpe.cpp"), os.path.join(edir, "emu_tone.cpp"),
+            os.path.join(edir, "emu_lpe.cpp"), os.path.join(edir, "emu_tone.cpp"), os.path.join(edir, "emu_nlm.cpp"),
             os.path.join(CSRC, "vk_linearize.cpp")]
     # (the tool's own headers: whichever are there)
     deps = srcs + sorted(os.path.join(edir, f) for f in os.listdir(edir) if f.endswith(".h")) + \
-        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_adapt.h", "vk_splat.h", "vk_matte.h", "vk_robust.h", "vk_lpe.h", "vk_tone.h")] + \
+        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_adapt.h", "vk_splat.h", "vk_matte.h", "vk_robust.h", "vk_lpe.h", "vk_tone.h", "vk_nlm.h")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
     if force or _newer(out, deps, CXXFLAGS):
         os.makedirs(os.path.dirname(out), exist_ok=True)

@@ -56,6 +56,7 @@
 #include "vk_robust.h"       // the kernels of vk_robust.hip: the per-pixel resolve, argument records and launchers
 #include "vk_lpe.h"          // the kernels of vk_lpe.hip: the tag, the rule match, argument records and launchers
 #include "vk_tone.h"         // the kernels of vk_tone.hip: the per-pixel display transform, argument records and launchers
+#include "vk_nlm.h"          // the kernels of vk_nlm.hip: the non-local-means filter's per-pixel code, argument records and launchers
 #include "vk_matte.h"        // the kernels of vk_matte.hip: the table of a pixel, the argument record and launchers
 
 namespace {
@@ -4845,6 +4846,257 @@ int vk_debug_tone_last_ms(vk_tone *t, double ms[2]) {
             float e = 0.0f;
             HIP_TRY(hipEventElapsedTime(&e, t->ev[2 * k], t->ev[2 * k + 1]));
             got[k] = (double)e;
+        }
+        for (int k = 0; k < 2; k++) ms[k] = got[k];
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- non-local means (vk_nlm_*): a copy of the loaded images on the scene's device (devices[0] of a multi-device scene), the four planes
+// nlm_prepare_kernel makes of it and the filter over them (nlm_filter_kernel<form, halo>, vk_nlm.hip); all on the null stream, on buffers
+// and events the handle owns.  Nothing of the scene handle is read but its device.
+struct vk_nlm {
+    vk_scene *scene = nullptr;                      // as handed to vk_nlm_create
+    uint32_t width = 0, height = 0;
+    DeviceBuffer<float> raw;                        // color, stderr3, albedo as loaded: [3][width * height * 3]
+    DeviceBuffer<float> planes;                     // I, V, Vf, a: [4][3][width * height]
+    DeviceBuffer<float> out;                        // rgb_out and stderr3_out on their way to the host (first vk_nlm_filter)
+    Event ev[4];                                    // around the last prepare and filter kernels
+    bool timed[2] = {false, false};
+    bool loaded = false, has_albedo = false;
+    float floor_used = 1e-3f;                       // the albedo_floor the planes were prepared with
+    uint32_t form = NLM_FORM_AUTO, last_form = 0u, last_launches = 0u;
+    uint64_t loads = 0, filters = 0;
+};
+
+namespace {
+
+void nlm_free(vk_nlm *h) {
+    (void)hipSetDevice(first_part(h->scene)->device);
+    (void)hipStreamSynchronize(nullptr);              // (a filter or a copy may still run)
+    (void)hipGetLastError();
+    delete h;
+}
+
+size_t nlm_pixels(const vk_nlm *h) { return (size_t)h->width * h->height; }
+
+// Per (R, F) the form that was measured faster on the MI355X (tools/nlm_report.py, DESIGN.md "Non-local means"): with a patch (F >= 1:
+// measured at (1, 1), (3, 1), (10, 1), (2, 2), (7, 2), (1, 3), (7, 3), (10, 3)) the tiled form, 2.5 to 11 times faster — the pairs of a
+// patch are shared —; without one (F = 0) there is nothing to share and the plain form is level at R = 1 and 1.1 to 1.2 times faster
+// at R = 10.  The gain follows F, not R, so R has no say.
+uint32_t nlm_auto_form(uint32_t R, uint32_t F) {
+    (void)R;
+    return F == 0u ? NLM_FORM_PLAIN : NLM_FORM_TILED;
+}
+
+const char *nlm_refusal(const vk_nlm_params &p) {
+    if (p.search_radius < 1u || p.search_radius > NLM_MAX_R) return "search_radius must be in 1..10";
+    if (p.patch_radius > NLM_MAX_F) return "patch_radius must be in 0..3";
+    if (!std::isfinite(p.k) || !(p.k > 0.0f)) return "k must be finite and > 0";
+    if (!std::isfinite(p.alpha) || !(p.alpha >= 0.0f)) return "alpha must be finite and >= 0";
+    if (!std::isfinite(p.albedo_floor) || !(p.albedo_floor > 0.0f)) return "albedo_floor must be finite and > 0";
+    if (p.flags != 0u) return "unknown nlm flags";
+    return nullptr;
+}
+
+// the prepare kernel over the handle's copy of the loaded images, into its planes
+int enqueue_nlm_prepare(vk_nlm *h, float albedo_floor) {
+    const size_t n = nlm_pixels(h);
+    NlmPrepareArgs A;
+    memset(&A, 0, sizeof(A));
+    A.color = h->raw; A.stderr3 = h->raw.get() + 3u * n; A.albedo = h->has_albedo ? h->raw.get() + 6u * n : nullptr;
+    A.I = h->planes; A.V = h->planes.get() + 3u * n; A.Vf = h->planes.get() + 6u * n; A.a = h->planes.get() + 9u * n;
+    A.width = h->width; A.height = h->height; A.albedo_floor = albedo_floor;
+    HIP_TRY(hipEventRecord(h->ev[0], nullptr));
+    launch_nlm_prepare(A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[1], nullptr));
+    h->timed[0] = true;
+    h->floor_used = albedo_floor;
+    return VK_OK;
+}
+
+// the filter of the handle's planes into d_out and d_se (may be null), on the handle's device; the arguments have been checked
+int enqueue_nlm_filter(vk_nlm *h, const vk_nlm_params &p, float *d_out, float *d_se) {
+    const size_t n = nlm_pixels(h);
+    h->last_launches = 0u;
+    if (h->has_albedo && p.albedo_floor != h->floor_used) {
+        int rc = enqueue_nlm_prepare(h, p.albedo_floor);
+        if (rc != VK_OK) return rc;
+        h->last_launches++;
+    }
+    NlmFilterArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P.I = h->planes; A.P.V = h->planes.get() + 3u * n; A.P.Vf = h->planes.get() + 6u * n; A.P.a = h->planes.get() + 9u * n;
+    A.P.width = h->width; A.P.height = h->height;
+    A.out = d_out; A.stderr3_out = d_se;
+    A.R = (int)p.search_radius; A.F = (int)p.patch_radius;
+    A.alpha = p.alpha; A.kk = p.k * p.k;
+    const uint32_t form = h->form == NLM_FORM_AUTO ? nlm_auto_form(p.search_radius, p.patch_radius) : h->form;
+    HIP_TRY(hipEventRecord(h->ev[2], nullptr));
+    launch_nlm_filter(A, form);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->ev[3], nullptr));
+    h->timed[1] = true;
+    h->last_form = form; h->last_launches++; h->filters++;
+    return VK_OK;
+}
+
+int check_nlm_filter(vk_nlm *h, const vk_nlm_params *p, const void *out) {
+    if (!h || !p || !out) return fail(VK_ERR_BAD_ARG, "null argument (nlm handle, params or output)");
+    if (const char *why = nlm_refusal(*p)) return fail(VK_ERR_BAD_ARG, why);
+    if (!h->loaded) return fail(VK_ERR_BAD_ARG, "vk_nlm_filter before vk_nlm_load");
+    return VK_OK;
+}
+
+// the elapsed time between two recorded events of the handle (waits for the second)
+int nlm_elapsed(vk_nlm *h, int k, double *ms) {
+    *ms = 0.0;
+    if (!h->timed[k]) return VK_OK;
+    HIP_TRY(hipEventSynchronize(h->ev[2 * k + 1]));
+    float e = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&e, h->ev[2 * k], h->ev[2 * k + 1]));
+    *ms = (double)e;
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_nlm_default_params(vk_nlm_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    memset(out, 0, sizeof(*out));
+    out->search_radius = 7u; out->patch_radius = 3u; out->k = 0.45f; out->alpha = 1.0f; out->albedo_floor = 1e-3f;
+    return VK_OK;
+}
+
+int vk_nlm_create(vk_scene *scene, uint32_t width, uint32_t height, vk_nlm **out) {
+    if (!scene || !out) return fail(VK_ERR_BAD_ARG, "null argument (scene or out)");
+    if (width == 0u || height == 0u) return fail(VK_ERR_BAD_ARG, "width and height must be >= 1");
+    if ((uint64_t)width * height > (1ull << 31) / 3 || width > 65535u || height > 65535u) return fail(VK_ERR_BAD_ARG, "image too large");
+    return guarded([&]() -> int {
+        std::unique_ptr<vk_nlm, void (*)(vk_nlm *)> h(new vk_nlm(), nlm_free);
+        h->scene = scene; h->width = width; h->height = height;
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        int r = VK_OK;
+        handle_alloc(r, h->raw, nlm_pixels(h.get()) * 9u * sizeof(float));
+        handle_alloc(r, h->planes, nlm_pixels(h.get()) * 12u * sizeof(float));
+        if (r != VK_OK) return r;
+        for (Event &e : h->ev) if ((r = e.create()) != VK_OK) return r;
+        *out = h.release();
+        return VK_OK;
+    });
+}
+
+int vk_nlm_load(vk_nlm *h, const float *color, const float *stderr3, const float *albedo) {
+    if (!h || !color || !stderr3) return fail(VK_ERR_BAD_ARG, "null argument (nlm handle, color or stderr3)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(h->scene)->device));
+        // (color, stderr3 and, where given, albedo side by side in the handle's copy: the layout enqueue_nlm_prepare reads)
+        float *const host[3] = {const_cast<float *>(color), const_cast<float *>(stderr3), const_cast<float *>(albedo)};
+        const uint32_t comps[3] = {3u, 3u, 3u};
+        StagedImages im;
+        int rc = im.upload(h->raw, host, comps, 3, nlm_pixels(h), 0x7u);
+        if (rc != VK_OK) return rc;
+        h->has_albedo = albedo != nullptr;
+        rc = enqueue_nlm_prepare(h, h->floor_used);
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        h->loaded = true; h->loads++; h->last_launches = 1u;
+        return VK_OK;
+    });
+}
+
+int vk_nlm_load_device(vk_nlm *h, const void *d_color, const void *d_stderr3, const void *d_albedo) {
+    if (!h || !d_color || !d_stderr3) return fail(VK_ERR_BAD_ARG, "null argument (nlm handle, d_color or d_stderr3)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(h->scene)->device));
+        const size_t bytes = nlm_pixels(h) * 3u * sizeof(float);
+        const void *src[3] = {d_color, d_stderr3, d_albedo};
+        for (int k = 0; k < 3; k++)
+            if (src[k]) HIP_TRY(hipMemcpyAsync(h->raw.get() + (size_t)k * 3u * nlm_pixels(h), src[k], bytes, hipMemcpyDeviceToDevice, nullptr));
+        h->has_albedo = d_albedo != nullptr;
+        int rc = enqueue_nlm_prepare(h, h->floor_used);
+        if (rc != VK_OK) return rc;
+        h->loaded = true; h->loads++; h->last_launches = 1u;
+        return VK_OK;
+    });
+}
+
+int vk_nlm_filter(vk_nlm *h, const vk_nlm_params *p, float *rgb_out, float *stderr3_out) {
+    int rc = check_nlm_filter(h, p, rgb_out);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(h->scene)->device));
+        const size_t n = nlm_pixels(h), bytes = n * 3u * sizeof(float);
+        if (!h->out) {
+            int r = VK_OK;
+            handle_alloc(r, h->out, 2u * bytes);
+            if (r != VK_OK) return r;
+        }
+        int r = enqueue_nlm_filter(h, *p, h->out, stderr3_out ? h->out.get() + 3u * n : nullptr);
+        if (r != VK_OK) return r;
+        HIP_TRY(hipMemcpy(rgb_out, h->out, bytes, hipMemcpyDeviceToHost));                           // (waits for the null stream)
+        if (stderr3_out) HIP_TRY(hipMemcpy(stderr3_out, h->out.get() + 3u * n, bytes, hipMemcpyDeviceToHost));
+        return VK_OK;
+    });
+}
+
+int vk_nlm_filter_device(vk_nlm *h, const vk_nlm_params *p, void *d_rgb_out, void *d_stderr3_out) {
+    int rc = check_nlm_filter(h, p, d_rgb_out);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(h->scene)->device));
+        return enqueue_nlm_filter(h, *p, static_cast<float *>(d_rgb_out), static_cast<float *>(d_stderr3_out));
+    });
+}
+
+int vk_nlm_reset(vk_nlm *h) {
+    if (!h) return fail(VK_ERR_BAD_ARG, "null nlm handle");
+    h->loaded = false; h->has_albedo = false;
+    return VK_OK;
+}
+
+int vk_nlm_get_info(vk_nlm *h, vk_nlm_info *out) {
+    if (!h || !out) return fail(VK_ERR_BAD_ARG, "null argument (nlm handle or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(h->scene)->device));
+        double ms = 0.0;
+        int rc = nlm_elapsed(h, 1, &ms);
+        if (rc != VK_OK) return rc;
+        memset(out, 0, sizeof(*out));
+        out->width = h->width; out->height = h->height; out->loaded = h->loaded ? 1u : 0u; out->has_albedo = h->has_albedo ? 1u : 0u;
+        out->loads = h->loads; out->filters = h->filters; out->last_launches = h->last_launches; out->last_form = h->last_form;
+        out->last_kernel_ms = ms;
+        out->scratch_bytes = h->raw.bytes() + h->planes.bytes() + h->out.bytes();
+        return VK_OK;
+    });
+}
+
+void vk_nlm_destroy(vk_nlm *h) {
+    if (h) nlm_free(h);
+}
+
+// test hook (vecchio_amd_debug.h): the filter kernel's form
+int vk_debug_nlm_set_form(vk_nlm *h, uint32_t form) {
+    if (!h) return fail(VK_ERR_BAD_ARG, "null nlm handle");
+    if (form > (uint32_t)VK_NLM_FORM_TILED) return fail(VK_ERR_BAD_ARG, "unknown nlm form");
+    h->form = form;
+    return VK_OK;
+}
+
+// test hook (vecchio_amd_debug.h): the last prepare and filter kernels, from the events recorded around each; 0 for one not yet run
+int vk_debug_nlm_last_ms(vk_nlm *h, double ms[2]) {
+    if (!h || !ms) return fail(VK_ERR_BAD_ARG, "null argument (nlm handle or ms)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(h->scene)->device));
+        double got[2] = {0.0, 0.0};
+        for (int k = 0; k < 2; k++) {
+            int rc = nlm_elapsed(h, k, &got[k]);
+            if (rc != VK_OK) return rc;
         }
         for (int k = 0; k < 2; k++) ms[k] = got[k];
         return VK_OK;

@@ -335,6 +335,22 @@ VK_TONE_METER_EMPTY = 1
 VK_TONE_FORM_LDS, VK_TONE_FORM_PLAIN = 0, 1
 
 
+class NlmParams(C.Structure):
+    """vk_nlm_params (vk_nlm_filter, vk_nlm_filter_device)"""
+    _fields_ = [("search_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("k", C.c_float), ("alpha", C.c_float),
+                ("albedo_floor", C.c_float), ("flags", C.c_uint32)]
+
+
+class NlmInfo(C.Structure):
+    """vk_nlm_info (vk_nlm_get_info)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("loaded", C.c_uint32), ("has_albedo", C.c_uint32),
+                ("loads", C.c_uint64), ("filters", C.c_uint64), ("last_launches", C.c_uint32), ("last_form", C.c_uint32),
+                ("last_kernel_ms", C.c_double), ("scratch_bytes", C.c_uint64)]
+
+
+VK_NLM_FORM_AUTO, VK_NLM_FORM_PLAIN, VK_NLM_FORM_TILED = 0, 1, 2
+
+
 class RegenInfo(C.Structure):
     """vk_regen_info (vk_regen_step)"""
     _fields_ = [("traced", C.c_uint64), ("live", C.c_uint64), ("remaining", C.c_uint64), ("emitted", C.c_uint64), ("missed", C.c_uint64),
@@ -462,6 +478,8 @@ DEVICE_SYMBOLS = [
     "vk_lpe_create", "vk_lpe_step", "vk_lpe_tags", "vk_lpe_deposit", "vk_lpe_resolve", "vk_lpe_reset", "vk_lpe_get_info", "vk_lpe_destroy",
     "vk_tone_default_meter_params", "vk_tone_default_params", "vk_tone_create", "vk_tone_load", "vk_tone_load_device", "vk_tone_meter",
     "vk_tone_solve", "vk_tone_encode", "vk_tone_encode_device", "vk_tone_reset", "vk_tone_get_info", "vk_tone_destroy",
+    "vk_nlm_default_params", "vk_nlm_create", "vk_nlm_load", "vk_nlm_load_device", "vk_nlm_filter", "vk_nlm_filter_device", "vk_nlm_reset",
+    "vk_nlm_get_info", "vk_nlm_destroy",
     "vk_matte_default_params", "vk_render_mattes", "vk_matte_merge", "vk_matte_mask",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
@@ -674,6 +692,24 @@ def _bind(lib):
     lib.vk_tone_get_info.argtypes = [C.c_void_p, C.POINTER(ToneInfo)]
     lib.vk_tone_destroy.restype = None
     lib.vk_tone_destroy.argtypes = [C.c_void_p]
+    lib.vk_nlm_default_params.restype = C.c_int
+    lib.vk_nlm_default_params.argtypes = [C.POINTER(NlmParams)]
+    lib.vk_nlm_create.restype = C.c_int
+    lib.vk_nlm_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.vk_nlm_load.restype = C.c_int
+    lib.vk_nlm_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_nlm_load_device.restype = C.c_int
+    lib.vk_nlm_load_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.vk_nlm_filter.restype = C.c_int
+    lib.vk_nlm_filter.argtypes = [C.c_void_p, C.POINTER(NlmParams), C.c_void_p, C.c_void_p]
+    lib.vk_nlm_filter_device.restype = C.c_int
+    lib.vk_nlm_filter_device.argtypes = [C.c_void_p, C.POINTER(NlmParams), C.c_void_p, C.c_void_p]
+    lib.vk_nlm_reset.restype = C.c_int
+    lib.vk_nlm_reset.argtypes = [C.c_void_p]
+    lib.vk_nlm_get_info.restype = C.c_int
+    lib.vk_nlm_get_info.argtypes = [C.c_void_p, C.POINTER(NlmInfo)]
+    lib.vk_nlm_destroy.restype = None
+    lib.vk_nlm_destroy.argtypes = [C.c_void_p]
     lib.vk_matte_default_params.restype = C.c_int
     lib.vk_matte_default_params.argtypes = [C.POINTER(MatteParams)]
     lib.vk_render_mattes.restype = C.c_int
@@ -774,6 +810,10 @@ def _bind(lib):
     lib.vk_debug_tone_set_form.argtypes = [C.c_void_p, C.c_uint32]
     lib.vk_debug_tone_last_ms.restype = C.c_int
     lib.vk_debug_tone_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 2)]
+    lib.vk_debug_nlm_set_form.restype = C.c_int
+    lib.vk_debug_nlm_set_form.argtypes = [C.c_void_p, C.c_uint32]
+    lib.vk_debug_nlm_last_ms.restype = C.c_int
+    lib.vk_debug_nlm_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 2)]
     lib.vk_debug_matte_samples.restype = C.c_int
     lib.vk_debug_matte_samples.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.c_void_p]
     lib.vk_debug_trace_occluded_device.restype = C.c_int

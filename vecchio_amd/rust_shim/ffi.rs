@@ -212,6 +212,13 @@ pub struct vk_tone_params { pub curve: u32, pub transfer: u32, pub flags: u32, p
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_tone_info { pub width: u32, pub height: u32, pub loads: u64, pub meters: u64, pub encodes: u64, pub exposure: f32, pub metered: u32, pub log2_used: f64 }
 
+// non-local means: the filter's parameters, and what a handle holds and last did
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_nlm_params { pub search_radius: u32, pub patch_radius: u32, pub k: f32, pub alpha: f32, pub albedo_floor: f32, pub flags: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_nlm_info { pub width: u32, pub height: u32, pub loaded: u32, pub has_albedo: u32, pub loads: u64, pub filters: u64, pub last_launches: u32, pub last_form: u32, pub last_kernel_ms: f64, pub scratch_bytes: u64 }
+
 // regeneration: what one vk_regen_step did
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_regen_info { pub traced: u64, pub live: u64, pub remaining: u64, pub emitted: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
@@ -231,6 +238,7 @@ pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, 
 #[repr(C)] pub struct vk_robust { _private: [u8; 0] }
 #[repr(C)] pub struct vk_lpe { _private: [u8; 0] }
 #[repr(C)] pub struct vk_tone { _private: [u8; 0] }
+#[repr(C)] pub struct vk_nlm { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -378,6 +386,17 @@ extern "C" {
     pub fn vk_tone_reset(t: *mut vk_tone) -> c_int;
     pub fn vk_tone_get_info(t: *mut vk_tone, out: *mut vk_tone_info) -> c_int;
     pub fn vk_tone_destroy(t: *mut vk_tone);
+    // non-local means (additive symbols of ABI 7): a frame and its standard error loaded into a handle, filtered by variance-cancelling
+    // patch distances; no function takes a stream (the _device calls are enqueued on the null stream)
+    pub fn vk_nlm_default_params(out: *mut vk_nlm_params) -> c_int;
+    pub fn vk_nlm_create(scene: *mut vk_scene, width: u32, height: u32, out: *mut *mut vk_nlm) -> c_int;
+    pub fn vk_nlm_load(h: *mut vk_nlm, color: *const f32, stderr3: *const f32, albedo: *const f32) -> c_int;
+    pub fn vk_nlm_load_device(h: *mut vk_nlm, d_color: *const c_void, d_stderr3: *const c_void, d_albedo: *const c_void) -> c_int;
+    pub fn vk_nlm_filter(h: *mut vk_nlm, p: *const vk_nlm_params, rgb_out: *mut f32, stderr3_out: *mut f32) -> c_int;
+    pub fn vk_nlm_filter_device(h: *mut vk_nlm, p: *const vk_nlm_params, d_rgb_out: *mut c_void, d_stderr3_out: *mut c_void) -> c_int;
+    pub fn vk_nlm_reset(h: *mut vk_nlm) -> c_int;
+    pub fn vk_nlm_get_info(h: *mut vk_nlm, out: *mut vk_nlm_info) -> c_int;
+    pub fn vk_nlm_destroy(h: *mut vk_nlm);
     // ID mattes (additive symbols of ABI 7): a ranked table of object or material ids per pixel, ids / counts ranks words per pixel,
     // overflow one (may be null); merge and mask are host code
     pub fn vk_matte_default_params(out: *mut vk_matte_params) -> c_int;

@@ -681,6 +681,12 @@ class DeviceScene:
         8-bit codes.  Use as a context manager, or close() it before the scene."""
         return Tone(self, width, height)
 
+    def nlm(self, width, height):
+        """A non-local-means filter on this scene's device (vk_nlm_create) for frames of width x height: a frame and its standard error
+        in, the filtered frame and its propagated standard error out; the weights come from the colour image and its variance alone.  Use
+        as a context manager, or close() it before the scene."""
+        return NonLocalMeans(self, width, height)
+
     def debug_compact_paths(self, items, ids, n_ids, canary=0xA5, roulette=None):
         """The compaction of a path batch's bounce on host arrays (vk_debug_compact_paths, a test hook): items a SHADED_DTYPE array, ids
         their uint32 ids (each below n_ids).  Every output is prefilled with the byte `canary`.  Returns (rays, states, ids_out — n
@@ -1543,6 +1549,106 @@ class Tone:
         except Exception:
             pass
 
+
+class NonLocalMeans:
+    """vk_nlm handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed): non-local means over one
+    width x height.  load() or load_device() a float frame, its per-channel standard error and, optionally, its albedo (y = 0 the
+    bottom row, 3 floats a pixel); filter() or filter_device() it, as often as wanted and with other parameters, without a reload."""
+
+    def __init__(self, scene, width, height):
+        self._lib = scene._lib
+        self._scene = scene
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_nlm_create(scene._h, width, height, C.byref(h)))
+        self._h = h
+
+    def _host(self, img):
+        img = np.ascontiguousarray(img, np.float32)
+        assert img.size == self.width * self.height * 3
+        return img
+
+    def _device(self, t):
+        if hasattr(t, "data_ptr"):
+            assert t.is_contiguous() and t.numel() == self.width * self.height * 3 and t.element_size() == 4
+            return t.data_ptr()
+        return t
+
+    def load(self, color, stderr3, albedo=None):
+        """The frame from host memory (vk_nlm_load): float32 arrays of width * height * 3 values; albedo may be None."""
+        color, stderr3 = self._host(color), self._host(stderr3)
+        albedo = None if albedo is None else self._host(albedo)
+        check(self._lib, self._lib.vk_nlm_load(self._h, color.ctypes.data_as(C.c_void_p), stderr3.ctypes.data_as(C.c_void_p),
+                                               None if albedo is None else albedo.ctypes.data_as(C.c_void_p)))
+
+    def load_device(self, d_color, d_stderr3, d_albedo=None):
+        """The frame from memory of the handle's device (vk_nlm_load_device, enqueued on the null stream): contiguous float32 tensors
+        (objects with data_ptr()) of width * height * 3 values, or device pointers; d_albedo may be None."""
+        check(self._lib, self._lib.vk_nlm_load_device(self._h, C.c_void_p(self._device(d_color)), C.c_void_p(self._device(d_stderr3)),
+                                                      None if d_albedo is None else C.c_void_p(self._device(d_albedo))))
+
+    def params(self, **kw):
+        """ffi.NlmParams: the defaults of the handle's library (vk_nlm_default_params) with the given fields replaced"""
+        p = ffi.NlmParams()
+        check(self._lib, self._lib.vk_nlm_default_params(C.byref(p)))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    def filter(self, params=None, want_stderr=True, **kw):
+        """The loaded frame filtered (vk_nlm_filter): (out, stderr3_out), float32 (height, width, 3) each; stderr3_out is None with
+        want_stderr=False.  params: an ffi.NlmParams, or keywords over the defaults (search_radius, patch_radius, k, alpha,
+        albedo_floor)."""
+        p = params if params is not None else self.params(**kw)
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        se = np.zeros((self.height, self.width, 3), np.float32) if want_stderr else None
+        check(self._lib, self._lib.vk_nlm_filter(self._h, C.byref(p), out.ctypes.data_as(C.c_void_p),
+                                                 None if se is None else se.ctypes.data_as(C.c_void_p)))
+        return out, se
+
+    def filter_device(self, d_out, d_stderr3_out=None, params=None, **kw):
+        """The filtered frame into memory of the handle's device (vk_nlm_filter_device, enqueued on the null stream): contiguous float32
+        tensors of width * height * 3 values, or device pointers; d_stderr3_out may be None.  Returns (d_out, d_stderr3_out)."""
+        p = params if params is not None else self.params(**kw)
+        check(self._lib, self._lib.vk_nlm_filter_device(self._h, C.byref(p), C.c_void_p(self._device(d_out)),
+                                                        None if d_stderr3_out is None else C.c_void_p(self._device(d_stderr3_out))))
+        return d_out, d_stderr3_out
+
+    def reset(self):
+        """Forget the frame (vk_nlm_reset): the next filter needs a load."""
+        check(self._lib, self._lib.vk_nlm_reset(self._h))
+
+    def info(self):
+        inf = ffi.NlmInfo()
+        check(self._lib, self._lib.vk_nlm_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def set_form(self, form):
+        """The filter kernel's form, ffi.VK_NLM_FORM_AUTO, _PLAIN or _TILED (vk_debug_nlm_set_form, a test hook)"""
+        check(self._lib, self._lib.vk_debug_nlm_set_form(self._h, form))
+
+    def last_ms(self):
+        """(prepare, filter) device milliseconds of the last kernel of each (vk_debug_nlm_last_ms, a test hook)"""
+        ms = (C.c_double * 2)()
+        check(self._lib, self._lib.vk_debug_nlm_last_ms(self._h, C.byref(ms)))
+        return tuple(ms)
+
+    def close(self):
+        if self._h:
+            self._lib.vk_nlm_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def lpe_rule(layer, sig_mask=0, sig_value=0, status=_ANY_STATUS, depth=(0, 0xFFFFFFFF), emitter=None):
