@@ -1447,7 +1447,8 @@ void vk_lpe_destroy(vk_lpe *s);
  * per-pixel code.  (5) The table is strictly increasing, each entry not below the f64 value and within one f32 ulp of it.  (6) Against
  * the f64 closed form round(255 * OETF(curve(E * x))) no component is off by more than one code, and at most 1e-4 of them by one.
  * What this is not.  No bloom or glare, no white balance or grading, no 16-bit or float output, no metering weights; a multi-device
- * scene's frame is its devices[0]'s; the frame comes from the caller's buffer.
+ * scene's frame is its devices[0]'s; the frame comes from the caller's buffer.  Glare is a stage of its own in front of this one:
+ * vk_glare_* below, whose output vk_tone_load / vk_tone_load_device take.
  *
  *   vk_tone_create: VK_ERR_BAD_ARG for a null pointer, width or height 0, width * height > 2^27.  VK_ERR_OOM leaves *out untouched.
  *   vk_tone_load / vk_tone_load_device: width * height * 3 floats from the host (through the staging path of the host-pointer calls; waits)
@@ -1506,6 +1507,75 @@ int vk_tone_encode_device(vk_tone *t, const vk_tone_params *tp, void *d_rgb8_out
 int vk_tone_reset(vk_tone *t);
 int vk_tone_get_info(vk_tone *t, vk_tone_info *out);
 void vk_tone_destroy(vk_tone *t);
+
+/* ---- glare: an energy-conserving bloom stage in front of the display transform (additive symbols of ABI 7) ---------------------------
+ * replaces: nothing.  A tone curve clips: a light of radiance 15 and one of radiance 150 encode to the same white patch.  A camera's or
+ * an eye's point-spread function leaks a small share of every pixel's energy over a wide neighbourhood, and that halo is what tells the
+ * two apart.  vk_glare_apply spreads the share `strength` of a frame's bright part over a pyramid of halved images and takes the same
+ * share away where it came from: a float frame in (vk_render's layout, y = 0 the bottom row, 3 floats a pixel), a float frame of the
+ * same shape out, which vk_tone_load / vk_tone_load_device take.
+ *
+ * State.  A handle for one width x height on the scene's device (devices[0] of a multi-device scene): the pyramid's planes B_1 .. B_7
+ * and A_1 .. A_7 (about two thirds of a frame) and, after the first host-pointer call, room for a frame in and a frame out.  Nothing is
+ * kept between applies.  All work is on the null stream there; no function takes a stream.  vk_glare_apply_device is ordered exactly as
+ * vk_tone_encode_device and vk_nlm_filter_device are: ENQUEUED on the null stream: work the caller issued earlier on the null stream or
+ * on a blocking stream is ordered before it, and the output is ready when the null stream is; a caller with a non-blocking stream
+ * synchronises first (and waits for the null stream afterwards).  d_rgb_out may be d_rgb_in: the last kernel reads its own pixel of
+ * the input only, and every other kernel has read the input before it.  vk_glare_apply goes through the staging path of the
+ * host-pointer calls and waits; rgb_out may be rgb_in.
+ *
+ * The operator, exactly.  Everything is f32, unfused, in the order written, with + - *, fmaxf, fminf and compares; one division, and
+ * only when threshold > 0.  tests/glare_ref.py restates it in numpy and the two agree bit for bit (a NaN's payload aside).
+ *   Sizes.  Level 0 is W x H; level l + 1 is ceil(w_l / 2) x ceil(h_l / 2): a dimension that has reached 1 stays 1.
+ *   Weights, on the host in f64 basic arithmetic.  p_0 = 1, p_l = p_{l-1} * (double)falloff; S = p_0 + .. + p_{L-1}, ascending; c_l =
+ *     (float)(p_l / S).
+ *   Bright part, per pixel of the input I.  s_c = I_c > 0 ? (I_c < 1048576.0f ? I_c : 1048576.0f) : 0.0f (vk_tone's sanitise).  If a
+ *     component of I is not finite, B = 0 for the whole pixel.  If threshold == 0, B_c = s_c.  Otherwise Y = (0.2126f * s_r + 0.7152f *
+ *     s_g) + 0.0722f * s_b, f = fmaxf(0, Y - threshold) / fmaxf(Y, 1e-20f), B_c = s_c * f.  B_0 = B is never stored.
+ *   Down, level l to l + 1: separable, x first.  With clamp(i) = min(max(i, 0), n - 1): d(j) = ((a(clamp(2j - 1)) + 3 * a(clamp(2j))) +
+ *     (3 * a(clamp(2j + 1)) + a(clamp(2j + 2)))) * 0.125f, along x on every source row, then the same along y on the result.
+ *   Up, level l + 1 to the size of level l: separable, x first.  j = x >> 1, nb = clamp(j - 1) for an even x, clamp(j + 1) for an odd
+ *     one; u(x) = (3 * a(j) + a(nb)) * 0.25f, along x, then the same along y.
+ *   Pyramid.  B_{l+1} = Down(B_l), l = 0 .. L - 2.  A_{L-1} = c_{L-1} * B_{L-1};  A_l = c_l * B_l + Up(A_{l+1}), l = L - 2 .. 0.
+ *   Composite.  out_c = I_c + strength * (A_0,c - B_c).  A component that is not finite stays what it was.  L = 1 or strength = 0 give
+ *     out == I as floats (a -0 becomes +0).
+ * Away from the border, with threshold 0, the sum of A_0 is the sum of B: what a pixel loses, its neighbourhood gains.  At the border the
+ * clamp reflects what would have left the frame.
+ * What this is not.  No lens flares, ghosts or diffraction spikes, no chromatic point-spread function, no convolution with a measured
+ * kernel: one radially decaying halo whose width doubles per level.
+ *
+ *   vk_glare_default_params: levels 6, strength 0.15, falloff 1, threshold 0, flags 0.  Touches no device.
+ *   vk_glare_create: VK_ERR_BAD_ARG for a null pointer, width or height 0, a size beyond vk_nlm_create's limits (width or height >
+ *     65535, width * height * 3 > 2^31).  VK_ERR_OOM leaves *out untouched.
+ *   vk_glare_apply / vk_glare_apply_device: VK_ERR_BAD_ARG, nothing enqueued and the output untouched, for a null handle, params, input
+ *     or output, levels outside 1..8, strength not finite or outside [0, 1], falloff not finite or <= 0, threshold not finite or < 0,
+ *     flags or _pad != 0.
+ *   vk_glare_destroy(NULL) does nothing.                                                                                              */
+typedef struct vk_glare vk_glare;        /* opaque */
+typedef struct vk_glare_params {         /* 24 bytes */
+    uint32_t levels;                     /* L: 1..8 */
+    float strength;                      /* 0..1: the share of the bright part that is spread */
+    float falloff;                       /* > 0: level l has weight proportional to falloff^l */
+    float threshold;                     /* >= 0: luminance below which a pixel spreads nothing; 0 = physical glare, everything spreads */
+    uint32_t flags;                      /* 0 */
+    uint32_t _pad;                       /* 0 */
+} vk_glare_params;
+typedef struct vk_glare_info {           /* 48 bytes */
+    uint32_t width, height;
+    uint64_t applies;                    /* accepted calls since create */
+    uint32_t last_levels;                /* L of the last apply; 0 before one */
+    uint32_t last_form;                  /* VK_GLARE_FORM_PLAIN or VK_GLARE_FORM_FUSED of the last apply; 0 before one */
+    uint32_t last_launches;              /* the kernels the last apply launched */
+    uint32_t _pad;
+    double last_kernel_ms;               /* the device time of the last apply's kernels, first to last; 0 before one (waits for it) */
+    uint64_t scratch_bytes;              /* the device memory the handle owns */
+} vk_glare_info;
+int vk_glare_default_params(vk_glare_params *out);
+int vk_glare_create(vk_scene *scene, uint32_t width, uint32_t height, vk_glare **out);
+int vk_glare_apply(vk_glare *g, const vk_glare_params *p, const float *rgb_in, float *rgb_out);
+int vk_glare_apply_device(vk_glare *g, const vk_glare_params *p, const void *d_rgb_in, void *d_rgb_out);
+int vk_glare_get_info(vk_glare *g, vk_glare_info *out);
+void vk_glare_destroy(vk_glare *g);
 
 /* ---- non-local means: denoising a frame from its own standard error (additive symbols of ABI 7) -------------------------------------
  * replaces: nothing.  The spatial filter for frames whose first-hit buffers say little (small textured, glass and metal objects): its

@@ -213,6 +213,16 @@ int vk_debug_nlm_set_form(vk_nlm *h, uint32_t form);
  * around each; 0 for one that has not run.  Waits for those.  Takes no stream.  In both libraries. */
 int vk_debug_nlm_last_ms(vk_nlm *h, double ms[2]);
 
+/* the form of vk_glare_apply's kernels from the next call on: PLAIN = one lane per output pixel straight from global memory, a launch
+ * per down level, per up level and for the composite (2L - 2); FUSED = the down passes through LDS tiles, B_1 and B_2 in one launch,
+ * and every level from the first that fits one workgroup's LDS in one tail launch; AUTO (the default) = per frame size and L the one
+ * measured faster: PLAIN everywhere, FUSED won at no measured size (DESIGN.md "Glare").  All give the same bits.  VK_ERR_BAD_ARG for a null handle or another form.  In both libraries. */
+enum { VK_GLARE_FORM_AUTO = 0, VK_GLARE_FORM_PLAIN = 1, VK_GLARE_FORM_FUSED = 2 };
+int vk_debug_glare_set_form(vk_glare *g, uint32_t form);
+/* the device milliseconds of the handle's last apply, between an event in front of its first kernel and one behind its last (without
+ * copies); 0 before one.  Waits for it.  Takes no stream.  In both libraries. */
+int vk_debug_glare_last_ms(vk_glare *g, double *ms);
+
 /* the id of every sample vk_render_mattes would count, by the same per-lane code on the same lanes: ids_out[(y * width + x) * spp + k] is
  * the id of sample first_sample + k under `kind` (VK_MATTE_OBJECT or VK_MATTE_MATERIAL), spp = params->samples_per_pixel; pixels outside
  * the call's tile partition are left untouched.  vk_render_mattes' checks.  Waits.  In both libraries. */

@@ -57,6 +57,7 @@
 #include "vk_lpe.h"          // the kernels of vk_lpe.hip: the tag, the rule match, argument records and launchers
 #include "vk_tone.h"         // the kernels of vk_tone.hip: the per-pixel display transform, argument records and launchers
 #include "vk_nlm.h"          // the kernels of vk_nlm.hip: the non-local-means filter's per-pixel code, argument records and launchers
+#include "vk_glare.h"        // the kernels of vk_glare.hip: the glare stage's per-pixel code, launch plan, argument records and launchers
 #include "vk_matte.h"        // the kernels of vk_matte.hip: the table of a pixel, the argument record and launchers
 
 namespace {
@@ -5099,6 +5100,247 @@ int vk_debug_nlm_last_ms(vk_nlm *h, double ms[2]) {
             if (rc != VK_OK) return rc;
         }
         for (int k = 0; k < 2; k++) ms[k] = got[k];
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- glare (vk_glare_*): the bright part's pyramid B_1 .. B_{L-1}, the weighted sums A_{L-2} .. A_1 on their way up and the composite
+// (vk_glare.hip) on the scene's device (devices[0] of a multi-device scene); all on the null stream, on buffers and events the handle
+// owns.  Nothing of the scene handle is read but its device.
+struct vk_glare {
+    vk_scene *scene = nullptr;                      // as handed to vk_glare_create
+    uint32_t width = 0, height = 0;
+    GlareDims dims;
+    size_t at[GLARE_MAX_LEVELS] = {};               // where level l's plane begins in one half of `pyramid`, in floats (l >= 1)
+    size_t half = 0;                                // the floats of B_1 .. B_7; A_1 .. A_7 follow them
+    DeviceBuffer<float> pyramid;
+    DeviceBuffer<float> io;                         // a frame in and a frame out of the host-pointer call (first vk_glare_apply)
+    Event ev[2];                                    // around the last apply's kernels
+    bool timed = false;
+    uint32_t form = GLARE_FORM_AUTO, last_form = 0u, last_launches = 0u, last_levels = 0u;
+    uint64_t applies = 0;
+};
+
+namespace {
+
+void glare_free(vk_glare *g) {
+    (void)hipSetDevice(first_part(g->scene)->device);
+    (void)hipStreamSynchronize(nullptr);              // (an apply may still run)
+    (void)hipGetLastError();
+    delete g;
+}
+
+size_t glare_pixels(const vk_glare *g) { return (size_t)g->width * g->height; }
+
+// Per frame size and L the form that was measured faster on the MI355X (tools/glare_report.py, DESIGN.md "Glare"): at 1920 x 1080, 900 x
+// 900 and 800 x 800 with L = 4, 6 and 8 the fused form took 1.04 to 1.29 times the plain form's time per call in a stream of calls, in
+// every one of the nine cells: its fewer launches do not pay for the two-level kernel's occupancy and the tail's three workgroups.  So AUTO is the plain form everywhere, and FUSED stays a debug form.
+uint32_t glare_auto_form(uint32_t width, uint32_t height, uint32_t L) {
+    (void)width; (void)height; (void)L;
+    return GLARE_FORM_PLAIN;
+}
+
+const char *glare_refusal(const vk_glare_params &p) {
+    if (p.levels < 1u || p.levels > GLARE_MAX_LEVELS) return "levels must be in 1..8";
+    if (!std::isfinite(p.strength) || !(p.strength >= 0.0f) || !(p.strength <= 1.0f)) return "strength must be in [0, 1]";
+    if (!std::isfinite(p.falloff) || !(p.falloff > 0.0f)) return "falloff must be finite and > 0";
+    if (!std::isfinite(p.threshold) || !(p.threshold >= 0.0f)) return "threshold must be finite and >= 0";
+    if (p.flags != 0u || p._pad != 0u) return "unknown glare flags";
+    return nullptr;
+}
+
+int check_glare_apply(vk_glare *g, const vk_glare_params *p, const void *in, const void *out) {
+    if (!g || !p || !in || !out) return fail(VK_ERR_BAD_ARG, "null argument (glare handle, params, input or output)");
+    if (const char *why = glare_refusal(*p)) return fail(VK_ERR_BAD_ARG, why);
+    return VK_OK;
+}
+
+// one apply from d_in into d_out (may be the same), on the handle's device; the arguments have been checked
+int enqueue_glare(vk_glare *g, const vk_glare_params &p, const float *d_in, float *d_out) {
+    const uint32_t L = p.levels;
+    const uint32_t form = g->form == GLARE_FORM_AUTO ? glare_auto_form(g->width, g->height, L) : g->form;
+    const GlareDims &d = g->dims;
+    float c[GLARE_MAX_LEVELS];
+    glare_weights(L, p.falloff, c);
+    auto B = [&](uint32_t l) { return g->pyramid.get() + g->at[l]; };
+    auto A = [&](uint32_t l) { return g->pyramid.get() + g->half + g->at[l]; };
+    uint32_t launches = 0u;
+    HIP_TRY(hipEventRecord(g->ev[0], nullptr));
+    // the level the up passes start from, and whether it is a stored A (the tail's) or c_{L-1} * B_{L-1}
+    uint32_t top = L - 1u;
+    bool top_is_a = false;
+    if (form == GLARE_FORM_PLAIN) {
+        for (uint32_t l = 0; l + 1u < L; l++) {
+            GlareDownArgs D;
+            memset(&D, 0, sizeof(D));
+            D.src = l ? B(l) : d_in; D.dst = B(l + 1u); D.sw = (uint32_t)d.w[l]; D.sh = (uint32_t)d.h[l]; D.threshold = p.threshold;
+            launch_glare_down(D, l == 0u, false);
+            launches++;
+        }
+    } else {
+        const uint32_t t = glare_tail_level(d);
+        const bool tail = t + 2u <= L;
+        const uint32_t m = tail ? t : L - 1u;
+        uint32_t l = 0u;
+        if (m >= 2u) {
+            GlareDown2Args D;
+            memset(&D, 0, sizeof(D));
+            D.src = d_in; D.b1 = B(1u); D.b2 = B(2u); D.sw = g->width; D.sh = g->height; D.threshold = p.threshold;
+            launch_glare_down2(D);
+            launches++;
+            l = 2u;
+        }
+        for (; l < m; l++) {
+            GlareDownArgs D;
+            memset(&D, 0, sizeof(D));
+            D.src = l ? B(l) : d_in; D.dst = B(l + 1u); D.sw = (uint32_t)d.w[l]; D.sh = (uint32_t)d.h[l]; D.threshold = p.threshold;
+            launch_glare_down(D, l == 0u, true);
+            launches++;
+        }
+        if (tail) {
+            GlareTailArgs T;
+            memset(&T, 0, sizeof(T));
+            T.bt = B(t); T.at = A(t); T.w = (uint32_t)d.w[t]; T.h = (uint32_t)d.h[t]; T.t = t; T.levels = L;
+            for (uint32_t k = 0; k < GLARE_MAX_LEVELS; k++) T.c[k] = c[k];
+            launch_glare_tail(T);
+            launches++;
+            top = t; top_is_a = true;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    for (uint32_t l = top; l-- > 1u;) {
+        GlareUpArgs U;
+        memset(&U, 0, sizeof(U));
+        U.src = top_is_a || l + 1u < top ? A(l + 1u) : B(l + 1u); U.scale = top_is_a || l + 1u < top ? 1.0f : c[top];
+        U.b = B(l); U.dst = A(l); U.w = (uint32_t)d.w[l]; U.h = (uint32_t)d.h[l]; U.c = c[l];
+        launch_glare_up(U);
+        launches++;
+    }
+    GlareCompositeArgs C;
+    memset(&C, 0, sizeof(C));
+    C.in = d_in; C.out = d_out; C.w = g->width; C.h = g->height; C.c0 = c[0]; C.strength = p.strength; C.threshold = p.threshold;
+    C.scale = 1.0f;
+    if (L >= 2u) {
+        const bool stored = top_is_a || top > 1u;
+        C.src = stored ? A(1u) : B(1u); C.scale = stored ? 1.0f : c[1];
+    }
+    launch_glare_composite(C);
+    launches++;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->ev[1], nullptr));
+    g->timed = true;
+    g->last_form = form; g->last_launches = launches; g->last_levels = L; g->applies++;
+    return VK_OK;
+}
+
+int glare_elapsed(vk_glare *g, double *ms) {
+    *ms = 0.0;
+    if (!g->timed) return VK_OK;
+    HIP_TRY(hipEventSynchronize(g->ev[1]));
+    float e = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&e, g->ev[0], g->ev[1]));
+    *ms = (double)e;
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_glare_default_params(vk_glare_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    memset(out, 0, sizeof(*out));
+    out->levels = 6u; out->strength = 0.15f; out->falloff = 1.0f; out->threshold = 0.0f;
+    return VK_OK;
+}
+
+int vk_glare_create(vk_scene *scene, uint32_t width, uint32_t height, vk_glare **out) {
+    if (!scene || !out) return fail(VK_ERR_BAD_ARG, "null argument (scene or out)");
+    if (width == 0u || height == 0u) return fail(VK_ERR_BAD_ARG, "width and height must be >= 1");
+    if ((uint64_t)width * height > (1ull << 31) / 3 || width > 65535u || height > 65535u) return fail(VK_ERR_BAD_ARG, "image too large");
+    return guarded([&]() -> int {
+        std::unique_ptr<vk_glare, void (*)(vk_glare *)> g(new vk_glare(), glare_free);
+        g->scene = scene; g->width = width; g->height = height;
+        g->dims = glare_dims(width, height);
+        for (uint32_t l = 1; l < GLARE_MAX_LEVELS; l++) {
+            g->at[l] = g->half;
+            g->half += (size_t)g->dims.w[l] * (size_t)g->dims.h[l] * 3u;
+        }
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        int r = VK_OK;
+        handle_alloc(r, g->pyramid, 2u * g->half * sizeof(float));
+        if (r != VK_OK) return r;
+        for (Event &e : g->ev) if ((r = e.create()) != VK_OK) return r;
+        *out = g.release();
+        return VK_OK;
+    });
+}
+
+int vk_glare_apply(vk_glare *g, const vk_glare_params *p, const float *rgb_in, float *rgb_out) {
+    int rc = check_glare_apply(g, p, rgb_in, rgb_out);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(g->scene)->device));
+        // (the frame in and the frame out side by side in the handle's buffer; only the first is uploaded, only the second comes back)
+        float *const host[2] = {const_cast<float *>(rgb_in), rgb_out};
+        const uint32_t comps[2] = {3u, 3u};
+        StagedImages im;
+        int r = im.upload(g->io, host, comps, 2, glare_pixels(g), 0x1u);
+        if (r != VK_OK) return r;
+        r = enqueue_glare(g, *p, im.dev[0], im.dev[1]);
+        if (r != VK_OK) return r;
+        return im.download(0x2u);                                                         // (waits for the null stream)
+    });
+}
+
+int vk_glare_apply_device(vk_glare *g, const vk_glare_params *p, const void *d_rgb_in, void *d_rgb_out) {
+    int rc = check_glare_apply(g, p, d_rgb_in, d_rgb_out);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(g->scene)->device));
+        return enqueue_glare(g, *p, static_cast<const float *>(d_rgb_in), static_cast<float *>(d_rgb_out));
+    });
+}
+
+int vk_glare_get_info(vk_glare *g, vk_glare_info *out) {
+    if (!g || !out) return fail(VK_ERR_BAD_ARG, "null argument (glare handle or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(g->scene)->device));
+        double ms = 0.0;
+        int rc = glare_elapsed(g, &ms);
+        if (rc != VK_OK) return rc;
+        memset(out, 0, sizeof(*out));
+        out->width = g->width; out->height = g->height; out->applies = g->applies;
+        out->last_levels = g->last_levels; out->last_form = g->last_form; out->last_launches = g->last_launches;
+        out->last_kernel_ms = ms;
+        out->scratch_bytes = g->pyramid.bytes() + g->io.bytes();
+        return VK_OK;
+    });
+}
+
+void vk_glare_destroy(vk_glare *g) {
+    if (g) glare_free(g);
+}
+
+// test hook (vecchio_amd_debug.h): the form of the apply's kernels
+int vk_debug_glare_set_form(vk_glare *g, uint32_t form) {
+    if (!g) return fail(VK_ERR_BAD_ARG, "null glare handle");
+    if (form > (uint32_t)VK_GLARE_FORM_FUSED) return fail(VK_ERR_BAD_ARG, "unknown glare form");
+    g->form = form;
+    return VK_OK;
+}
+
+// test hook (vecchio_amd_debug.h): the last apply's kernels, from the events recorded around them; 0 before one
+int vk_debug_glare_last_ms(vk_glare *g, double *ms) {
+    if (!g || !ms) return fail(VK_ERR_BAD_ARG, "null argument (glare handle or ms)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(g->scene)->device));
+        double got = 0.0;
+        int rc = glare_elapsed(g, &got);
+        if (rc != VK_OK) return rc;
+        *ms = got;
         return VK_OK;
     });
 }

@@ -351,6 +351,22 @@ class NlmInfo(C.Structure):
 VK_NLM_FORM_AUTO, VK_NLM_FORM_PLAIN, VK_NLM_FORM_TILED = 0, 1, 2
 
 
+class GlareParams(C.Structure):
+    """vk_glare_params (vk_glare_apply, vk_glare_apply_device)"""
+    _fields_ = [("levels", C.c_uint32), ("strength", C.c_float), ("falloff", C.c_float), ("threshold", C.c_float),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class GlareInfo(C.Structure):
+    """vk_glare_info (vk_glare_get_info)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("applies", C.c_uint64), ("last_levels", C.c_uint32),
+                ("last_form", C.c_uint32), ("last_launches", C.c_uint32), ("_pad", C.c_uint32), ("last_kernel_ms", C.c_double),
+                ("scratch_bytes", C.c_uint64)]
+
+
+VK_GLARE_FORM_AUTO, VK_GLARE_FORM_PLAIN, VK_GLARE_FORM_FUSED = 0, 1, 2
+
+
 class RegenInfo(C.Structure):
     """vk_regen_info (vk_regen_step)"""
     _fields_ = [("traced", C.c_uint64), ("live", C.c_uint64), ("remaining", C.c_uint64), ("emitted", C.c_uint64), ("missed", C.c_uint64),
@@ -480,6 +496,7 @@ DEVICE_SYMBOLS = [
     "vk_tone_solve", "vk_tone_encode", "vk_tone_encode_device", "vk_tone_reset", "vk_tone_get_info", "vk_tone_destroy",
     "vk_nlm_default_params", "vk_nlm_create", "vk_nlm_load", "vk_nlm_load_device", "vk_nlm_filter", "vk_nlm_filter_device", "vk_nlm_reset",
     "vk_nlm_get_info", "vk_nlm_destroy",
+    "vk_glare_default_params", "vk_glare_create", "vk_glare_apply", "vk_glare_apply_device", "vk_glare_get_info", "vk_glare_destroy",
     "vk_matte_default_params", "vk_render_mattes", "vk_matte_merge", "vk_matte_mask",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
@@ -710,6 +727,18 @@ def _bind(lib):
     lib.vk_nlm_get_info.argtypes = [C.c_void_p, C.POINTER(NlmInfo)]
     lib.vk_nlm_destroy.restype = None
     lib.vk_nlm_destroy.argtypes = [C.c_void_p]
+    lib.vk_glare_default_params.restype = C.c_int
+    lib.vk_glare_default_params.argtypes = [C.POINTER(GlareParams)]
+    lib.vk_glare_create.restype = C.c_int
+    lib.vk_glare_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.vk_glare_apply.restype = C.c_int
+    lib.vk_glare_apply.argtypes = [C.c_void_p, C.POINTER(GlareParams), C.c_void_p, C.c_void_p]
+    lib.vk_glare_apply_device.restype = C.c_int
+    lib.vk_glare_apply_device.argtypes = [C.c_void_p, C.POINTER(GlareParams), C.c_void_p, C.c_void_p]
+    lib.vk_glare_get_info.restype = C.c_int
+    lib.vk_glare_get_info.argtypes = [C.c_void_p, C.POINTER(GlareInfo)]
+    lib.vk_glare_destroy.restype = None
+    lib.vk_glare_destroy.argtypes = [C.c_void_p]
     lib.vk_matte_default_params.restype = C.c_int
     lib.vk_matte_default_params.argtypes = [C.POINTER(MatteParams)]
     lib.vk_render_mattes.restype = C.c_int
@@ -814,6 +843,10 @@ def _bind(lib):
     lib.vk_debug_nlm_set_form.argtypes = [C.c_void_p, C.c_uint32]
     lib.vk_debug_nlm_last_ms.restype = C.c_int
     lib.vk_debug_nlm_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 2)]
+    lib.vk_debug_glare_set_form.restype = C.c_int
+    lib.vk_debug_glare_set_form.argtypes = [C.c_void_p, C.c_uint32]
+    lib.vk_debug_glare_last_ms.restype = C.c_int
+    lib.vk_debug_glare_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.vk_debug_matte_samples.restype = C.c_int
     lib.vk_debug_matte_samples.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.c_void_p]
     lib.vk_debug_trace_occluded_device.restype = C.c_int

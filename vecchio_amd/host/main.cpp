@@ -2,7 +2,7 @@
 // scene, build the BVH, upload once, then per Camera of cam_iter: render through the C ABI
 // (the call that replaces main.rs:181-198), write output_%04d.ppm, print the frame time.
 // The reference hard-codes scene/width/spp/depth (main.rs:28-29,159-167,171); here they are
-// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0] [guide_bounces=0] [display=0]
+// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0] [guide_bounces=0] [display=0] [glare=0]
 // steps > 1: each frame is rendered progressively (vk_progress_*) in `steps` equal sample windows; after each window the running image
 // is written to output_%04d_step%02d.ppm and the samples done and the image's mean relative standard error are printed.  The final
 // output_%04d.ppm is byte-identical to the one of steps = 1.
@@ -23,6 +23,9 @@
 // goes through the display transform (vk_tone_*): metered with the library's default parameters (over an animation, frames > 1, with
 // blend 0.25, so that the exposure follows the frames smoothly), encoded with the Reinhard (1), Hable (2) or ACES (3) curve, the metered
 // exposure and the sRGB transfer, and written as output_%04d_display.ppm.  display = 0 or absent: every file is what it was.
+// glare = 1 .. 100: that frame — display's, whether or not display is on — first goes through the glare stage (vk_glare_*) with strength
+// glare / 100 and the library's other default parameters; the result is written as output_%04d_glare.pfm and is what display encodes.
+// glare = 0 or absent: no such call is made and every file is what it was.
 // Texture images are read from ./assets (as in the reference) or $VECCHIO_ASSETS: <name>.ppm.gz, see host_api.h.
 #include <dlfcn.h>
 
@@ -64,7 +67,7 @@ static T sym(void *h, const char *name) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <balls_demo|random_spheres_demo|random_spheres_iow|perlin_demo|bowser_demo|cornell_box|final_scene|"
-                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal] [guide_bounces] [display]\n", argv[0]);
+                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal] [guide_bounces] [display] [glare]\n", argv[0]);
         return 2;
     }
     const char *name = argv[1];
@@ -81,6 +84,11 @@ int main(int argc, char **argv) {
     const uint32_t display = argc > 12 ? (uint32_t)atoi(argv[12]) : 0;
     if (display > 3) {
         fprintf(stderr, "display is 0 (off), 1 (Reinhard), 2 (Hable) or 3 (ACES)\n");
+        return 2;
+    }
+    const uint32_t glare_pct = argc > 13 ? (uint32_t)atoi(argv[13]) : 0;
+    if (glare_pct > 100) {
+        fprintf(stderr, "glare is the strength in percent: 0 (off) to 100\n");
         return 2;
     }
     if (steps < 1) steps = 1;
@@ -132,6 +140,10 @@ int main(int argc, char **argv) {
     auto p_tone_meter = sym<int (*)(vk_tone *, const vk_tone_meter_params *, vk_tone_meter_info *)>(h, "vk_tone_meter");
     auto p_tone_encode = sym<int (*)(vk_tone *, const vk_tone_params *, uint8_t *)>(h, "vk_tone_encode");
     auto p_tone_destroy = sym<void (*)(vk_tone *)>(h, "vk_tone_destroy");
+    auto p_glare_defaults = sym<int (*)(vk_glare_params *)>(h, "vk_glare_default_params");
+    auto p_glare_create = sym<int (*)(vk_scene *, uint32_t, uint32_t, vk_glare **)>(h, "vk_glare_create");
+    auto p_glare_apply = sym<int (*)(vk_glare *, const vk_glare_params *, const float *, float *)>(h, "vk_glare_apply");
+    auto p_glare_destroy = sym<void (*)(vk_glare *)>(h, "vk_glare_destroy");
 
     fprintf(stderr, "Generating scene...\n");                        // main.rs:157
     vkh_scene *hs = vkh_scene_build(name, seed);
@@ -156,6 +168,8 @@ int main(int argc, char **argv) {
     }
     vk_tone *tone = nullptr;
     if (display && p_tone_create(scene, width, height, &tone) != VK_OK) { fprintf(stderr, "vk_tone_create: %s\n", p_err()); return 1; }
+    vk_glare *glare = nullptr;
+    if (glare_pct && p_glare_create(scene, width, height, &glare) != VK_OK) { fprintf(stderr, "vk_glare_create: %s\n", p_err()); return 1; }
     vk_camera cam;
     int file_idx = 0;
     while (file_idx < frames && vkh_scene_next_camera(hs, &cam)) {   // main.rs:176
@@ -251,7 +265,7 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "  accumulated: %.1f %% of the pixels with history, kernel %.2f ms\n",
                         100.0 * (double)ti.pixels_with_history / (double)np, ts.kernel_ms);
                 dn_color = acc.data(); dn_err = acc_err.data();
-                if (display) shown = acc;
+                if (display || glare) shown = acc;
             }
             if (denoise) {
                 vk_denoise_params dp;
@@ -266,8 +280,19 @@ int main(int argc, char **argv) {
                 snprintf(dfn, sizeof dfn, "output_%04d_denoised.pfm", file_idx);
                 if (!write_pfm(dfn, clean.data(), width, height, 3)) return 1;
                 fprintf(stderr, "  denoised (%u levels): kernels %.2f ms\n", dp.levels, ds.kernel_ms);
-                if (display) shown = clean;
+                if (display || glare) shown = clean;
             }
+        }
+        if (glare) {
+            vk_glare_params gp;
+            if (shown.empty()) shown = pixels;
+            if (p_glare_defaults(&gp) != VK_OK) { fprintf(stderr, "vk_glare defaults: %s\n", p_err()); return 1; }
+            gp.strength = (float)glare_pct / 100.0f;
+            if (p_glare_apply(glare, &gp, shown.data(), shown.data()) != VK_OK) { fprintf(stderr, "vk_glare_apply: %s\n", p_err()); return 1; }
+            char sfn[64];
+            snprintf(sfn, sizeof sfn, "output_%04d_glare.pfm", file_idx);
+            if (!write_pfm(sfn, shown.data(), width, height, 3)) return 1;
+            fprintf(stderr, "  glare: strength %.2f over %u levels\n", (double)gp.strength, gp.levels);
         }
         if (display) {
             vk_tone_meter_params mp;
@@ -290,6 +315,7 @@ int main(int argc, char **argv) {
                 st.kernel_ms > 0 ? (double)st.samples / st.kernel_ms / 1e3 : 0.0);   // main.rs:215
         file_idx++;
     }
+    if (glare) p_glare_destroy(glare);
     if (tone) p_tone_destroy(tone);
     if (history) p_tdestroy(history);
     p_destroy(scene);

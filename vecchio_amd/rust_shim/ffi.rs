@@ -219,6 +219,13 @@ pub struct vk_nlm_params { pub search_radius: u32, pub patch_radius: u32, pub k:
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_nlm_info { pub width: u32, pub height: u32, pub loaded: u32, pub has_albedo: u32, pub loads: u64, pub filters: u64, pub last_launches: u32, pub last_form: u32, pub last_kernel_ms: f64, pub scratch_bytes: u64 }
 
+// glare: the stage's parameters, and what a handle holds and last did
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_glare_params { pub levels: u32, pub strength: f32, pub falloff: f32, pub threshold: f32, pub flags: u32, pub _pad: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_glare_info { pub width: u32, pub height: u32, pub applies: u64, pub last_levels: u32, pub last_form: u32, pub last_launches: u32, pub _pad: u32, pub last_kernel_ms: f64, pub scratch_bytes: u64 }
+
 // regeneration: what one vk_regen_step did
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_regen_info { pub traced: u64, pub live: u64, pub remaining: u64, pub emitted: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
@@ -239,6 +246,7 @@ pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, 
 #[repr(C)] pub struct vk_lpe { _private: [u8; 0] }
 #[repr(C)] pub struct vk_tone { _private: [u8; 0] }
 #[repr(C)] pub struct vk_nlm { _private: [u8; 0] }
+#[repr(C)] pub struct vk_glare { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -397,6 +405,14 @@ extern "C" {
     pub fn vk_nlm_reset(h: *mut vk_nlm) -> c_int;
     pub fn vk_nlm_get_info(h: *mut vk_nlm, out: *mut vk_nlm_info) -> c_int;
     pub fn vk_nlm_destroy(h: *mut vk_nlm);
+    // glare (additive symbols of ABI 7): the share `strength` of a frame's bright part spread over a pyramid of halved images, in front
+    // of the display transform; no function takes a stream (the _device call is enqueued on the null stream); out may be in
+    pub fn vk_glare_default_params(out: *mut vk_glare_params) -> c_int;
+    pub fn vk_glare_create(scene: *mut vk_scene, width: u32, height: u32, out: *mut *mut vk_glare) -> c_int;
+    pub fn vk_glare_apply(g: *mut vk_glare, p: *const vk_glare_params, rgb_in: *const f32, rgb_out: *mut f32) -> c_int;
+    pub fn vk_glare_apply_device(g: *mut vk_glare, p: *const vk_glare_params, d_rgb_in: *const c_void, d_rgb_out: *mut c_void) -> c_int;
+    pub fn vk_glare_get_info(g: *mut vk_glare, out: *mut vk_glare_info) -> c_int;
+    pub fn vk_glare_destroy(g: *mut vk_glare);
     // ID mattes (additive symbols of ABI 7): a ranked table of object or material ids per pixel, ids / counts ranks words per pixel,
     // overflow one (may be null); merge and mask are host code
     pub fn vk_matte_default_params(out: *mut vk_matte_params) -> c_int;

@@ -687,6 +687,12 @@ class DeviceScene:
         as a context manager, or close() it before the scene."""
         return NonLocalMeans(self, width, height)
 
+    def glare(self, width, height):
+        """A glare stage on this scene's device (vk_glare_create) for frames of width x height: a float frame in, the frame with the
+        share `strength` of its bright part spread over a pyramid of halved images out, for Tone.load / load_device.  Use as a context
+        manager, or close() it before the scene."""
+        return Glare(self, width, height)
+
     def debug_compact_paths(self, items, ids, n_ids, canary=0xA5, roulette=None):
         """The compaction of a path batch's bounce on host arrays (vk_debug_compact_paths, a test hook): items a SHADED_DTYPE array, ids
         their uint32 ids (each below n_ids).  Every output is prefilled with the byte `canary`.  Returns (rays, states, ids_out — n
@@ -1636,6 +1642,86 @@ class NonLocalMeans:
     def close(self):
         if self._h:
             self._lib.vk_nlm_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Glare:
+    """vk_glare handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed): the glare stage over one
+    width x height.  apply() a float frame from host memory or apply_device() one on the handle's device (y = 0 the bottom row, 3
+    floats a pixel); nothing is kept between applies."""
+
+    def __init__(self, scene, width, height):
+        self._lib = scene._lib
+        self._scene = scene
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_glare_create(scene._h, width, height, C.byref(h)))
+        self._h = h
+
+    def _device(self, t):
+        if hasattr(t, "data_ptr"):
+            assert t.is_contiguous() and t.numel() == self.width * self.height * 3 and t.element_size() == 4
+            return t.data_ptr()
+        return t
+
+    def params(self, **kw):
+        """ffi.GlareParams: the defaults of the handle's library (vk_glare_default_params) with the given fields replaced"""
+        p = ffi.GlareParams()
+        check(self._lib, self._lib.vk_glare_default_params(C.byref(p)))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    def apply(self, rgb, params=None, **kw):
+        """The frame with glare (vk_glare_apply): float32 (height, width, 3) from a float32 array of width * height * 3 values.  params:
+        an ffi.GlareParams, or keywords over the defaults (levels, strength, falloff, threshold)."""
+        p = params if params is not None else self.params(**kw)
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        assert rgb.size == self.width * self.height * 3
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        check(self._lib, self._lib.vk_glare_apply(self._h, C.byref(p), rgb.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def apply_device(self, d_in, d_out=None, params=None, **kw):
+        """The frame with glare in memory of the handle's device (vk_glare_apply_device, enqueued on the null stream): contiguous
+        float32 tensors (objects with data_ptr()) of width * height * 3 values, or device pointers; d_out None = in place.  Returns
+        d_out."""
+        p = params if params is not None else self.params(**kw)
+        if d_out is None:
+            d_out = d_in
+        check(self._lib, self._lib.vk_glare_apply_device(self._h, C.byref(p), C.c_void_p(self._device(d_in)), C.c_void_p(self._device(d_out))))
+        return d_out
+
+    def info(self):
+        inf = ffi.GlareInfo()
+        check(self._lib, self._lib.vk_glare_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def set_form(self, form):
+        """The kernels' form, ffi.VK_GLARE_FORM_AUTO, _PLAIN or _FUSED (vk_debug_glare_set_form, a test hook)"""
+        check(self._lib, self._lib.vk_debug_glare_set_form(self._h, form))
+
+    def last_ms(self):
+        """device milliseconds of the last apply's kernels (vk_debug_glare_last_ms, a test hook)"""
+        ms = C.c_double()
+        check(self._lib, self._lib.vk_debug_glare_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self._h:
+            self._lib.vk_glare_destroy(self._h)
             self._h = None
 
     def __enter__(self):
