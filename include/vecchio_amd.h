@@ -1577,6 +1577,100 @@ int vk_glare_apply_device(vk_glare *g, const vk_glare_params *p, const void *d_r
 int vk_glare_get_info(vk_glare *g, vk_glare_info *out);
 void vk_glare_destroy(vk_glare *g);
 
+/* ---- guided upsampling: a low-resolution frame to full size along the edges of full-size AOVs (additive symbols of ABI 7) ------------
+ * replaces: nothing.  Render scale: the paths are traced at w x h, the first-hit buffers (vk_render_aov, or vk_render_guides for both
+ * sizes) at w x h and at W x H — they cost a small fraction of a frame —, and vk_upsample_apply brings colour and its standard error to
+ * W x H by joint bilateral upsampling (Kopf, Cohen, Lischinski, Uyttendaele 2007) with the variance carried along.  It takes a colour
+ * frame, its stderr3 and first-hit buffers, and gives the colour frame and stderr3 that vk_temporal_accumulate, vk_nlm_load, vk_denoise,
+ * vk_glare_apply and vk_tone_load take.  All images are in vk_render's f32 layout, y = 0 the bottom row: colour, stderr3, albedo and
+ * normal 3 floats a pixel, depth 1.  Both frames come from the same vk_camera.
+ *
+ * State.  A handle for one pair of sizes on the scene's device (devices[0] of a multi-device scene): a copy of the loaded low images
+ * (13 floats a low pixel), the three prepared planes (12 floats a low pixel), two counters and, after the first host-pointer apply, room
+ * for the high guides and the two outputs.  vk_upsample_load packs the low frame into the planes; the caller's buffers are free after
+ * it, and a second apply with other parameters needs no reload.  All work is on the null stream there; no function takes a stream.  The
+ * _device calls are ordered exactly as vk_glare_apply_device and vk_nlm_load_device are: ENQUEUED on the null stream: work the caller
+ * issued earlier on the null stream or on a blocking stream is ordered before it, and the output is ready when the null stream is; a
+ * caller with a non-blocking stream synchronises first (and waits for the null stream afterwards).  The host-pointer calls go through
+ * the staging path of the host-pointer calls and wait.
+ *
+ * The operator, exactly.  Everything is f32, unfused, in the order written, with + - * /, sqrtf, fabsf, fmaxf, fminf, floorf and
+ * compares.  E(x) = fmaxf(0, 1 - x * 0.125f), squared three times (vk_denoise's).  tests/upsample_ref.py restates it in numpy and the
+ * two agree bit for bit (a NaN's payload aside).
+ *   Mapping (the reference's frame convention, main.rs:187, as vk_temporal uses it: pixel x covers u in [x / (w - 1), (x + 1) / (w - 1)]).
+ *     rx = (float)((double)(w - 1) / (double)(W - 1)) on the host, ry likewise from h and H; px = ((float)X + 0.5f) * rx - 0.5f, py
+ *     likewise; x0 = floorf(px), y0 = floorf(py).  sx = (float)((double)(W - 1) / (double)(w - 1)), sy likewise.
+ *   Prepare, per low pixel q, at load.  a_c = fmaxf(albedo_c, albedo_floor), or 1 without albedo; I_c = color_c / a_c; V_c = (stderr_c /
+ *     a_c)^2, or 0 without stderr3.  q is INVALID if a component of colour, or of stderr3 when given, is not finite.  l2 = (n_x n_x + n_y
+ *     n_y) + n_z n_z: l2 < 1e-12f or not finite, or no normal loaded: q has NO NORMAL; otherwise n^ = n / sqrtf(l2).  z = depth if
+ *     finite, else +inf.  The planes depend on the floor: an apply with another floor prepares them again from the handle's copy.
+ *   Per high pixel P.  n^_P and z_P from the high guides by the same rules.  The depth slope g_x, g_y from depth_hi, in high pixels:
+ *     with dl = z_P - z_left and dr = z_right - z_P, where both neighbours are in the image and finite the one smaller in magnitude if
+ *     dl * dr > 0 (fminf for positive ones, fmaxf for negative ones) and 0 otherwise; where one is, that difference; else 0; 0 where z_P
+ *     is +inf.  (vk_denoise's central difference reads a depth edge next to P as a slope and lets the far side in; this one does not.)
+ *   Taps.  ty = y0 - 1 .. y0 + 2 the outer loop, tx = x0 - 1 .. x0 + 2 the inner, ascending; a tap outside the low image or INVALID is
+ *     skipped.  kx = fmaxf(0, 1 - fabsf(px - (float)tx) * 0.5f), ky likewise.  w_n = 1 if the normal term is off or neither pixel has a
+ *     normal, 0 if exactly one has, otherwise fmaxf(0, (n^_P.x n^_q.x + n^_P.y n^_q.y) + n^_P.z n^_q.z) squared normal_squarings times.
+ *     x_z = 0 if the depth term is off or both depths are +inf; the tap is skipped if exactly one is; otherwise fabsf(z_P - z_q) /
+ *     (sigma_z * (fabsf(g_x * ux + g_y * uy) + 0.001f * z_P)), ux = ((float)tx - px) * sx, uy = ((float)ty - py) * sy.
+ *     wt = ((kx * ky) * w_n) * E(x_z).  In tap order from 0: Wt += wt, J_c += wt * I_c(q), U_c += (wt * wt) * V_c(q).
+ *     A term is on when its guide was loaded and is given to apply; one side only switches it off.
+ *   Fallback.  Wt < 1e-4f: no consistent tap; the sums are taken again with wt = kx * ky over the same in-image, valid taps (those the
+ *     depth term skipped included) and P counts in fallback_pixels.  Still Wt < 1e-4f: every tap was invalid; out = 0, stderr3_out = 0
+ *     and P counts in empty_pixels as well.
+ *   Finish.  A_c = fmaxf(albedo_hi_c, albedo_floor), or 1 without albedo; out_c = (J_c / Wt) * A_c; stderr3_out_c = (sqrtf(U_c) / Wt) * A_c.
+ * Laws (tests/upsample_laws_ref.py).  A constant low frame gives the constant, whatever the guides.  The tent's weights sum to 2 and
+ * have zero first moment at any phase, so a low frame affine in (x, y) under flat guides gives that function at (px, py) wherever the
+ * 4 x 4 footprint lies inside the low image.
+ * What this is not.  Scale 1 is not the identity: the tent spans two low pixels on either side.  stderr3_out is each pixel's marginal
+ * error: neighbouring outputs share taps and are correlated, and a downstream vk_denoise will treat them as independent.  Nothing is
+ * followed through mirrors or glass, unless the caller passes vk_render_guides' buffers for both sizes.  No temporal upsampling, no
+ * non-uniform scale.
+ *
+ *   vk_upsample_default_params: sigma_z 1, normal_squarings 7, albedo_floor 1e-3, flags 0 (vk_denoise's).  Touches no device.
+ *   vk_upsample_create: VK_ERR_BAD_ARG for a null pointer, w or h < 2, w > W or h > H, a high size beyond vk_nlm_create's limits (W or H
+ *     > 65535, W * H * 3 > 2^31).  VK_ERR_OOM leaves *out untouched.
+ *   vk_upsample_load / vk_upsample_load_device: VK_ERR_BAD_ARG for a null handle or colour; every other image may be null.
+ *   vk_upsample_apply / vk_upsample_apply_device: VK_ERR_BAD_ARG, nothing enqueued and the outputs untouched, for a null handle, params
+ *     or rgb_out, sigma_z or albedo_floor not finite or not > 0, normal_squarings > 10, flags or _pad != 0, an apply before a load,
+ *     albedo_hi given without a loaded albedo or the other way round (demodulating one side only is a wrong image, not an option),
+ *     stderr3_out wanted without a loaded stderr3.
+ *   vk_upsample_reset forgets the loaded frame.  vk_upsample_destroy(NULL) does nothing.                                              */
+typedef struct vk_upsample vk_upsample;  /* opaque */
+enum { VK_UPSAMPLE_HAS_STDERR = 1, VK_UPSAMPLE_HAS_ALBEDO = 2, VK_UPSAMPLE_HAS_NORMAL = 4, VK_UPSAMPLE_HAS_DEPTH = 8 };
+typedef struct vk_upsample_params {      /* 20 bytes */
+    float sigma_z;                       /* > 0: the depth term's width, in units of the slope's prediction plus 0.1 % of the depth */
+    uint32_t normal_squarings;           /* 0..10: the normal term is the cosine to the power 2^normal_squarings */
+    float albedo_floor;                  /* > 0 */
+    uint32_t flags;                      /* 0 */
+    uint32_t _pad;                       /* 0 */
+} vk_upsample_params;
+typedef struct vk_upsample_info {        /* 80 bytes */
+    uint32_t width_lo, height_lo, width_hi, height_hi;
+    uint32_t loaded;                     /* 1 after a load, 0 after create and reset */
+    uint32_t guides;                     /* VK_UPSAMPLE_HAS_* of the loaded low frame */
+    uint64_t loads, applies;             /* accepted calls since create */
+    uint32_t last_form;                  /* VK_UPSAMPLE_FORM_PLAIN or _TILED of the last apply; 0 before one */
+    uint32_t last_launches;              /* the kernels the last load or apply launched (an apply with a new floor: 2) */
+    double last_kernel_ms;               /* the device time of the last apply's filter kernel; 0 before one (waits for it) */
+    uint64_t scratch_bytes;              /* the device memory the handle owns */
+    uint64_t fallback_pixels;            /* of the last apply (waits for it): pixels filtered by the tent alone, the empty ones included */
+    uint64_t empty_pixels;               /* of the last apply: pixels without a valid tap */
+} vk_upsample_info;
+int vk_upsample_default_params(vk_upsample_params *out);
+int vk_upsample_create(vk_scene *scene, uint32_t w, uint32_t h, uint32_t W, uint32_t H, vk_upsample **out);
+int vk_upsample_load(vk_upsample *u, const float *color_lo, const float *stderr3_lo, const float *albedo_lo, const float *normal_lo,
+                     const float *depth_lo);
+int vk_upsample_load_device(vk_upsample *u, const void *d_color_lo, const void *d_stderr3_lo, const void *d_albedo_lo,
+                            const void *d_normal_lo, const void *d_depth_lo);
+int vk_upsample_apply(vk_upsample *u, const vk_upsample_params *p, const float *albedo_hi, const float *normal_hi, const float *depth_hi,
+                      float *rgb_out, float *stderr3_out);
+int vk_upsample_apply_device(vk_upsample *u, const vk_upsample_params *p, const void *d_albedo_hi, const void *d_normal_hi,
+                             const void *d_depth_hi, void *d_rgb_out, void *d_stderr3_out);
+int vk_upsample_reset(vk_upsample *u);
+int vk_upsample_get_info(vk_upsample *u, vk_upsample_info *out);
+void vk_upsample_destroy(vk_upsample *u);
+
 /* ---- non-local means: denoising a frame from its own standard error (additive symbols of ABI 7) -------------------------------------
  * replaces: nothing.  The spatial filter for frames whose first-hit buffers say little (small textured, glass and metal objects): its
  * weights come from the colour image and its variance alone, by variance-cancelling patch distances (Rousselle, Knaus, Zwicker 2012).

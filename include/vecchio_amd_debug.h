@@ -223,6 +223,17 @@ int vk_debug_glare_set_form(vk_glare *g, uint32_t form);
  * copies); 0 before one.  Waits for it.  Takes no stream.  In both libraries. */
 int vk_debug_glare_last_ms(vk_glare *g, double *ms);
 
+/* the form of vk_upsample_apply's filter kernel from the next call on: PLAIN = one lane per high pixel, its taps' records straight from
+ * global memory; TILED = a 256-lane workgroup stages the low footprint (at most 36 x 12 records) of its 32 x 8 high pixels in LDS and
+ * filters from there; AUTO (the default) = a function of the two sizes alone, the form measured faster: TILED at every size (DESIGN.md
+ * "Guided upsampling").  All give the same bits.
+ * VK_ERR_BAD_ARG for a null handle or another form.  In both libraries. */
+enum { VK_UPSAMPLE_FORM_AUTO = 0, VK_UPSAMPLE_FORM_PLAIN = 1, VK_UPSAMPLE_FORM_TILED = 2 };
+int vk_debug_upsample_set_form(vk_upsample *u, uint32_t form);
+/* the device milliseconds of the handle's last apply's filter kernel, between an event in front of it and one behind it (without copies
+ * and without a prepare pass); 0 before one.  Waits for it.  Takes no stream.  In both libraries. */
+int vk_debug_upsample_last_ms(vk_upsample *u, double *ms);
+
 /* the id of every sample vk_render_mattes would count, by the same per-lane code on the same lanes: ids_out[(y * width + x) * spp + k] is
  * the id of sample first_sample + k under `kind` (VK_MATTE_OBJECT or VK_MATTE_MATERIAL), spp = params->samples_per_pixel; pixels outside
  * the call's tile partition are left untouched.  vk_render_mattes' checks.  Waits.  In both libraries. */

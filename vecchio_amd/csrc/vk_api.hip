@@ -58,6 +58,7 @@
 #include "vk_tone.h"         // the kernels of vk_tone.hip: the per-pixel display transform, argument records and launchers
 #include "vk_nlm.h"          // the kernels of vk_nlm.hip: the non-local-means filter's per-pixel code, argument records and launchers
 #include "vk_glare.h"        // the kernels of vk_glare.hip: the glare stage's per-pixel code, launch plan, argument records and launchers
+#include "vk_upsample.h"     // the kernels of vk_upsample.hip: guided upsampling's per-pixel code, argument records and launchers
 #include "vk_matte.h"        // the kernels of vk_matte.hip: the table of a pixel, the argument record and launchers
 
 namespace {
@@ -5339,6 +5340,270 @@ int vk_debug_glare_last_ms(vk_glare *g, double *ms) {
         HIP_TRY(hipSetDevice(first_part(g->scene)->device));
         double got = 0.0;
         int rc = glare_elapsed(g, &got);
+        if (rc != VK_OK) return rc;
+        *ms = got;
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- guided upsampling (vk_upsample_*): a copy of the loaded low images on the scene's device (devices[0] of a multi-device scene), the
+// three planes upsample_prepare_kernel makes of it and the filter over the high frame (vk_upsample.hip); all on the null stream, on
+// buffers and events the handle owns.  Nothing of the scene handle is read but its device.
+struct vk_upsample {
+    vk_scene *scene = nullptr;                      // as handed to vk_upsample_create
+    uint32_t w = 0, h = 0, W = 0, H = 0;
+    DeviceBuffer<float> raw;                        // color, stderr3, albedo, normal, depth as loaded: room for 13 floats a low pixel
+    float *raw_at[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};       // where each loaded image is in `raw`; null = not loaded
+    DeviceBuffer<UpRec> planes;                     // P0, P1, P2: [3][w * h]
+    DeviceBuffer<uint32_t> counts;                  // fallback_pixels, empty_pixels of the last apply
+    DeviceBuffer<float> io;                         // the high guides in and the two frames out of the host-pointer call (first vk_upsample_apply)
+    Event ev[2];                                    // around the last apply's filter kernel
+    bool timed = false, loaded = false;
+    float floor_used = 1e-3f;                       // the albedo_floor the planes were prepared with
+    uint32_t form = UPSAMPLE_FORM_AUTO, last_form = 0u, last_launches = 0u;
+    uint64_t loads = 0, applies = 0;
+};
+
+namespace {
+
+void upsample_free(vk_upsample *u) {
+    (void)hipSetDevice(first_part(u->scene)->device);
+    (void)hipStreamSynchronize(nullptr);              // (an apply or a copy may still run)
+    (void)hipGetLastError();
+    delete u;
+}
+
+size_t upsample_lo(const vk_upsample *u) { return (size_t)u->w * u->h; }
+size_t upsample_hi(const vk_upsample *u) { return (size_t)u->W * u->H; }
+
+uint32_t upsample_guides(const vk_upsample *u) {
+    return (u->raw_at[1] ? (uint32_t)VK_UPSAMPLE_HAS_STDERR : 0u) | (u->raw_at[2] ? (uint32_t)VK_UPSAMPLE_HAS_ALBEDO : 0u) |
+        (u->raw_at[3] ? (uint32_t)VK_UPSAMPLE_HAS_NORMAL : 0u) | (u->raw_at[4] ? (uint32_t)VK_UPSAMPLE_HAS_DEPTH : 0u);
+}
+
+const char *upsample_refusal(const vk_upsample_params &p) {
+    if (!std::isfinite(p.sigma_z) || !(p.sigma_z > 0.0f)) return "sigma_z must be finite and > 0";
+    if (p.normal_squarings > 10u) return "normal_squarings must be in 0..10";
+    if (!std::isfinite(p.albedo_floor) || !(p.albedo_floor > 0.0f)) return "albedo_floor must be finite and > 0";
+    if (p.flags != 0u || p._pad != 0u) return "unknown upsample flags";
+    return nullptr;
+}
+
+// the prepare kernel over the handle's copy of the loaded images, into its planes
+int enqueue_upsample_prepare(vk_upsample *u, float albedo_floor) {
+    const size_t n = upsample_lo(u);
+    UpsamplePrepareArgs A;
+    memset(&A, 0, sizeof(A));
+    A.color = u->raw_at[0]; A.stderr3 = u->raw_at[1]; A.albedo = u->raw_at[2]; A.normal = u->raw_at[3]; A.depth = u->raw_at[4];
+    A.P0 = u->planes; A.P1 = u->planes.get() + n; A.P2 = u->planes.get() + 2u * n;
+    A.w = u->w; A.h = u->h; A.albedo_floor = albedo_floor;
+    launch_upsample_prepare(A);
+    HIP_TRY(hipGetLastError());
+    u->floor_used = albedo_floor;
+    return VK_OK;
+}
+
+// one apply into d_out and d_se (may be null), on the handle's device; the arguments have been checked
+int enqueue_upsample(vk_upsample *u, const vk_upsample_params &p, const float *d_albedo, const float *d_normal, const float *d_depth,
+    float *d_out, float *d_se) {
+    const size_t n = upsample_lo(u);
+    u->last_launches = 0u;
+    if (u->raw_at[2] && p.albedo_floor != u->floor_used) {
+        int rc = enqueue_upsample_prepare(u, p.albedo_floor);
+        if (rc != VK_OK) return rc;
+        u->last_launches++;
+    }
+    UpsampleArgs A;
+    memset(&A, 0, sizeof(A));
+    A.P0 = u->planes; A.P1 = u->planes.get() + n; A.P2 = u->planes.get() + 2u * n;
+    A.albedo_hi = d_albedo; A.normal_hi = d_normal; A.depth_hi = d_depth;
+    A.out = d_out; A.stderr3_out = d_se; A.counts = u->counts;
+    A.w = u->w; A.h = u->h; A.W = u->W; A.H = u->H;
+    upsample_ratios(u->w, u->W, A.rx, A.sx);
+    upsample_ratios(u->h, u->H, A.ry, A.sy);
+    A.sigma_z = p.sigma_z; A.albedo_floor = p.albedo_floor; A.normal_squarings = p.normal_squarings;
+    A.flags = (d_normal && u->raw_at[3] ? UP_NORMAL : 0u) | (d_depth && u->raw_at[4] ? UP_DEPTH : 0u);
+    const uint32_t form = u->form == UPSAMPLE_FORM_AUTO ? upsample_auto_form(u->w, u->h, u->W, u->H) : u->form;
+    HIP_TRY(hipMemsetAsync(u->counts, 0, 2u * sizeof(uint32_t), nullptr));
+    HIP_TRY(hipEventRecord(u->ev[0], nullptr));
+    launch_upsample_apply(A, form);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(u->ev[1], nullptr));
+    u->timed = true;
+    u->last_form = form; u->last_launches++; u->applies++;
+    return VK_OK;
+}
+
+int check_upsample_apply(vk_upsample *u, const vk_upsample_params *p, const void *albedo, const void *out, const void *se) {
+    if (!u || !p || !out) return fail(VK_ERR_BAD_ARG, "null argument (upsample handle, params or output)");
+    if (const char *why = upsample_refusal(*p)) return fail(VK_ERR_BAD_ARG, why);
+    if (!u->loaded) return fail(VK_ERR_BAD_ARG, "vk_upsample_apply before vk_upsample_load");
+    if ((albedo != nullptr) != (u->raw_at[2] != nullptr)) return fail(VK_ERR_BAD_ARG, "albedo must be given at both sizes or at neither");
+    if (se && !u->raw_at[1]) return fail(VK_ERR_BAD_ARG, "stderr3_out wanted but no stderr3 was loaded");
+    return VK_OK;
+}
+
+int upsample_elapsed(vk_upsample *u, double *ms) {
+    *ms = 0.0;
+    if (!u->timed) return VK_OK;
+    HIP_TRY(hipEventSynchronize(u->ev[1]));
+    float e = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&e, u->ev[0], u->ev[1]));
+    *ms = (double)e;
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_upsample_default_params(vk_upsample_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    memset(out, 0, sizeof(*out));
+    out->sigma_z = 1.0f; out->normal_squarings = 7u; out->albedo_floor = 1e-3f;
+    return VK_OK;
+}
+
+int vk_upsample_create(vk_scene *scene, uint32_t w, uint32_t h, uint32_t W, uint32_t H, vk_upsample **out) {
+    if (!scene || !out) return fail(VK_ERR_BAD_ARG, "null argument (scene or out)");
+    if (w < 2u || h < 2u) return fail(VK_ERR_BAD_ARG, "the low width and height must be >= 2");
+    if (w > W || h > H) return fail(VK_ERR_BAD_ARG, "the low size must not exceed the high size");
+    if ((uint64_t)W * H > (1ull << 31) / 3 || W > 65535u || H > 65535u) return fail(VK_ERR_BAD_ARG, "image too large");
+    return guarded([&]() -> int {
+        std::unique_ptr<vk_upsample, void (*)(vk_upsample *)> u(new vk_upsample(), upsample_free);
+        u->scene = scene; u->w = w; u->h = h; u->W = W; u->H = H;
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        int r = VK_OK;
+        handle_alloc(r, u->raw, upsample_lo(u.get()) * 13u * sizeof(float));
+        handle_alloc(r, u->planes, upsample_lo(u.get()) * 3u * sizeof(UpRec));
+        handle_alloc(r, u->counts, 2u * sizeof(uint32_t));
+        if (r != VK_OK) return r;
+        HIP_TRY(hipMemsetAsync(u->counts, 0, 2u * sizeof(uint32_t), nullptr));
+        for (Event &e : u->ev) if ((r = e.create()) != VK_OK) return r;
+        *out = u.release();
+        return VK_OK;
+    });
+}
+
+int vk_upsample_load(vk_upsample *u, const float *color_lo, const float *stderr3_lo, const float *albedo_lo, const float *normal_lo,
+    const float *depth_lo) {
+    if (!u || !color_lo) return fail(VK_ERR_BAD_ARG, "null argument (upsample handle or color_lo)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(u->scene)->device));
+        HIP_TRY(hipStreamSynchronize(nullptr));              // (an apply may still read the planes the copies' prepare will replace)
+        // (the given images side by side in the handle's copy, which has room for all five)
+        float *const host[5] = {const_cast<float *>(color_lo), const_cast<float *>(stderr3_lo), const_cast<float *>(albedo_lo),
+                                const_cast<float *>(normal_lo), const_cast<float *>(depth_lo)};
+        const uint32_t comps[5] = {3u, 3u, 3u, 3u, 1u};
+        StagedImages im;
+        u->loaded = false;
+        int rc = im.upload(u->raw, host, comps, 5, upsample_lo(u), 0x1Fu);
+        if (rc != VK_OK) return rc;
+        for (int k = 0; k < 5; k++) u->raw_at[k] = im.dev[k];
+        rc = enqueue_upsample_prepare(u, u->floor_used);
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        u->loaded = true; u->loads++; u->last_launches = 1u;
+        return VK_OK;
+    });
+}
+
+int vk_upsample_load_device(vk_upsample *u, const void *d_color_lo, const void *d_stderr3_lo, const void *d_albedo_lo,
+    const void *d_normal_lo, const void *d_depth_lo) {
+    if (!u || !d_color_lo) return fail(VK_ERR_BAD_ARG, "null argument (upsample handle or d_color_lo)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(u->scene)->device));
+        const size_t n = upsample_lo(u);
+        const void *src[5] = {d_color_lo, d_stderr3_lo, d_albedo_lo, d_normal_lo, d_depth_lo};
+        u->loaded = false;
+        for (int k = 0; k < 5; k++) {
+            u->raw_at[k] = src[k] ? u->raw.get() + (size_t)k * 3u * n : nullptr;
+            if (src[k]) HIP_TRY(hipMemcpyAsync(u->raw_at[k], src[k], n * (k == 4 ? 1u : 3u) * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+        }
+        int rc = enqueue_upsample_prepare(u, u->floor_used);
+        if (rc != VK_OK) return rc;
+        u->loaded = true; u->loads++; u->last_launches = 1u;
+        return VK_OK;
+    });
+}
+
+int vk_upsample_apply(vk_upsample *u, const vk_upsample_params *p, const float *albedo_hi, const float *normal_hi, const float *depth_hi,
+    float *rgb_out, float *stderr3_out) {
+    int rc = check_upsample_apply(u, p, albedo_hi, rgb_out, stderr3_out);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(u->scene)->device));
+        // (the high guides and the two outputs side by side in the handle's buffer; the guides are uploaded, the outputs come back)
+        float *const host[5] = {const_cast<float *>(albedo_hi), const_cast<float *>(normal_hi), const_cast<float *>(depth_hi), rgb_out, stderr3_out};
+        const uint32_t comps[5] = {3u, 3u, 1u, 3u, 3u};
+        StagedImages im;
+        int r = im.upload(u->io, host, comps, 5, upsample_hi(u), 0x7u);
+        if (r != VK_OK) return r;
+        r = enqueue_upsample(u, *p, im.dev[0], im.dev[1], im.dev[2], im.dev[3], im.dev[4]);
+        if (r != VK_OK) return r;
+        return im.download(0x18u);                                                        // (waits for the null stream)
+    });
+}
+
+int vk_upsample_apply_device(vk_upsample *u, const vk_upsample_params *p, const void *d_albedo_hi, const void *d_normal_hi,
+    const void *d_depth_hi, void *d_rgb_out, void *d_stderr3_out) {
+    int rc = check_upsample_apply(u, p, d_albedo_hi, d_rgb_out, d_stderr3_out);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(u->scene)->device));
+        return enqueue_upsample(u, *p, static_cast<const float *>(d_albedo_hi), static_cast<const float *>(d_normal_hi),
+                                static_cast<const float *>(d_depth_hi), static_cast<float *>(d_rgb_out), static_cast<float *>(d_stderr3_out));
+    });
+}
+
+int vk_upsample_reset(vk_upsample *u) {
+    if (!u) return fail(VK_ERR_BAD_ARG, "null upsample handle");
+    u->loaded = false;
+    for (float *&at : u->raw_at) at = nullptr;
+    return VK_OK;
+}
+
+int vk_upsample_get_info(vk_upsample *u, vk_upsample_info *out) {
+    if (!u || !out) return fail(VK_ERR_BAD_ARG, "null argument (upsample handle or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(u->scene)->device));
+        double ms = 0.0;
+        int rc = upsample_elapsed(u, &ms);
+        if (rc != VK_OK) return rc;
+        uint32_t counts[2] = {0u, 0u};
+        HIP_TRY(hipMemcpy(counts, u->counts, sizeof(counts), hipMemcpyDeviceToHost));     // (waits for the null stream)
+        memset(out, 0, sizeof(*out));
+        out->width_lo = u->w; out->height_lo = u->h; out->width_hi = u->W; out->height_hi = u->H;
+        out->loaded = u->loaded ? 1u : 0u; out->guides = u->loaded ? upsample_guides(u) : 0u;
+        out->loads = u->loads; out->applies = u->applies; out->last_form = u->last_form; out->last_launches = u->last_launches;
+        out->last_kernel_ms = ms;
+        out->scratch_bytes = u->raw.bytes() + u->planes.bytes() + u->counts.bytes() + u->io.bytes();
+        out->fallback_pixels = counts[0]; out->empty_pixels = counts[1];
+        return VK_OK;
+    });
+}
+
+void vk_upsample_destroy(vk_upsample *u) {
+    if (u) upsample_free(u);
+}
+
+// test hook (vecchio_amd_debug.h): the form of the apply's filter kernel
+int vk_debug_upsample_set_form(vk_upsample *u, uint32_t form) {
+    if (!u) return fail(VK_ERR_BAD_ARG, "null upsample handle");
+    if (form > (uint32_t)VK_UPSAMPLE_FORM_TILED) return fail(VK_ERR_BAD_ARG, "unknown upsample form");
+    u->form = form;
+    return VK_OK;
+}
+
+// test hook (vecchio_amd_debug.h): the last apply's filter kernel, from the events recorded around it; 0 before one
+int vk_debug_upsample_last_ms(vk_upsample *u, double *ms) {
+    if (!u || !ms) return fail(VK_ERR_BAD_ARG, "null argument (upsample handle or ms)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(u->scene)->device));
+        double got = 0.0;
+        int rc = upsample_elapsed(u, &got);
         if (rc != VK_OK) return rc;
         *ms = got;
         return VK_OK;

@@ -367,6 +367,24 @@ class GlareInfo(C.Structure):
 VK_GLARE_FORM_AUTO, VK_GLARE_FORM_PLAIN, VK_GLARE_FORM_FUSED = 0, 1, 2
 
 
+class UpsampleParams(C.Structure):
+    """vk_upsample_params (vk_upsample_apply, vk_upsample_apply_device)"""
+    _fields_ = [("sigma_z", C.c_float), ("normal_squarings", C.c_uint32), ("albedo_floor", C.c_float), ("flags", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+
+class UpsampleInfo(C.Structure):
+    """vk_upsample_info (vk_upsample_get_info)"""
+    _fields_ = [("width_lo", C.c_uint32), ("height_lo", C.c_uint32), ("width_hi", C.c_uint32), ("height_hi", C.c_uint32),
+                ("loaded", C.c_uint32), ("guides", C.c_uint32), ("loads", C.c_uint64), ("applies", C.c_uint64),
+                ("last_form", C.c_uint32), ("last_launches", C.c_uint32), ("last_kernel_ms", C.c_double),
+                ("scratch_bytes", C.c_uint64), ("fallback_pixels", C.c_uint64), ("empty_pixels", C.c_uint64)]
+
+
+VK_UPSAMPLE_FORM_AUTO, VK_UPSAMPLE_FORM_PLAIN, VK_UPSAMPLE_FORM_TILED = 0, 1, 2
+VK_UPSAMPLE_HAS_STDERR, VK_UPSAMPLE_HAS_ALBEDO, VK_UPSAMPLE_HAS_NORMAL, VK_UPSAMPLE_HAS_DEPTH = 1, 2, 4, 8
+
+
 class RegenInfo(C.Structure):
     """vk_regen_info (vk_regen_step)"""
     _fields_ = [("traced", C.c_uint64), ("live", C.c_uint64), ("remaining", C.c_uint64), ("emitted", C.c_uint64), ("missed", C.c_uint64),
@@ -497,6 +515,8 @@ DEVICE_SYMBOLS = [
     "vk_nlm_default_params", "vk_nlm_create", "vk_nlm_load", "vk_nlm_load_device", "vk_nlm_filter", "vk_nlm_filter_device", "vk_nlm_reset",
     "vk_nlm_get_info", "vk_nlm_destroy",
     "vk_glare_default_params", "vk_glare_create", "vk_glare_apply", "vk_glare_apply_device", "vk_glare_get_info", "vk_glare_destroy",
+    "vk_upsample_default_params", "vk_upsample_create", "vk_upsample_load", "vk_upsample_load_device", "vk_upsample_apply",
+    "vk_upsample_apply_device", "vk_upsample_reset", "vk_upsample_get_info", "vk_upsample_destroy",
     "vk_matte_default_params", "vk_render_mattes", "vk_matte_merge", "vk_matte_mask",
     "vk_denoise_default_params", "vk_denoise", "vk_denoise_device", "vk_progress_stderr_device",
     "vk_temporal_default_params", "vk_temporal_create", "vk_temporal_accumulate", "vk_temporal_accumulate_device", "vk_temporal_reset",
@@ -739,6 +759,24 @@ def _bind(lib):
     lib.vk_glare_get_info.argtypes = [C.c_void_p, C.POINTER(GlareInfo)]
     lib.vk_glare_destroy.restype = None
     lib.vk_glare_destroy.argtypes = [C.c_void_p]
+    lib.vk_upsample_default_params.restype = C.c_int
+    lib.vk_upsample_default_params.argtypes = [C.POINTER(UpsampleParams)]
+    lib.vk_upsample_create.restype = C.c_int
+    lib.vk_upsample_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.vk_upsample_load.restype = C.c_int
+    lib.vk_upsample_load.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+    lib.vk_upsample_load_device.restype = C.c_int
+    lib.vk_upsample_load_device.argtypes = [C.c_void_p] + [C.c_void_p] * 5
+    lib.vk_upsample_apply.restype = C.c_int
+    lib.vk_upsample_apply.argtypes = [C.c_void_p, C.POINTER(UpsampleParams)] + [C.c_void_p] * 5
+    lib.vk_upsample_apply_device.restype = C.c_int
+    lib.vk_upsample_apply_device.argtypes = [C.c_void_p, C.POINTER(UpsampleParams)] + [C.c_void_p] * 5
+    lib.vk_upsample_reset.restype = C.c_int
+    lib.vk_upsample_reset.argtypes = [C.c_void_p]
+    lib.vk_upsample_get_info.restype = C.c_int
+    lib.vk_upsample_get_info.argtypes = [C.c_void_p, C.POINTER(UpsampleInfo)]
+    lib.vk_upsample_destroy.restype = None
+    lib.vk_upsample_destroy.argtypes = [C.c_void_p]
     lib.vk_matte_default_params.restype = C.c_int
     lib.vk_matte_default_params.argtypes = [C.POINTER(MatteParams)]
     lib.vk_render_mattes.restype = C.c_int
@@ -847,6 +885,10 @@ def _bind(lib):
     lib.vk_debug_glare_set_form.argtypes = [C.c_void_p, C.c_uint32]
     lib.vk_debug_glare_last_ms.restype = C.c_int
     lib.vk_debug_glare_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.vk_debug_upsample_set_form.restype = C.c_int
+    lib.vk_debug_upsample_set_form.argtypes = [C.c_void_p, C.c_uint32]
+    lib.vk_debug_upsample_last_ms.restype = C.c_int
+    lib.vk_debug_upsample_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.vk_debug_matte_samples.restype = C.c_int
     lib.vk_debug_matte_samples.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.c_uint32, C.c_uint32, C.c_void_p]
     lib.vk_debug_trace_occluded_device.restype = C.c_int

@@ -2,7 +2,7 @@
 // scene, build the BVH, upload once, then per Camera of cam_iter: render through the C ABI
 // (the call that replaces main.rs:181-198), write output_%04d.ppm, print the frame time.
 // The reference hard-codes scene/width/spp/depth (main.rs:28-29,159-167,171); here they are
-// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0] [guide_bounces=0] [display=0] [glare=0]
+// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0] [guide_bounces=0] [display=0] [glare=0] [scale=0]
 // steps > 1: each frame is rendered progressively (vk_progress_*) in `steps` equal sample windows; after each window the running image
 // is written to output_%04d_step%02d.ppm and the samples done and the image's mean relative standard error are printed.  The final
 // output_%04d.ppm is byte-identical to the one of steps = 1.
@@ -26,6 +26,12 @@
 // glare = 1 .. 100: that frame — display's, whether or not display is on — first goes through the glare stage (vk_glare_*) with strength
 // glare / 100 and the library's other default parameters; the result is written as output_%04d_glare.pfm and is what display encodes.
 // glare = 0 or absent: no such call is made and every file is what it was.
+// scale = 1 .. 99 (needs aov_spp > 0): render scale in percent.  The paths — and with steps > 1 their standard error — are traced at
+// width * scale / 100 (output_%04d.ppm, its steps and output_%04d.pfm are that low frame), the first-hit buffers are rendered at that
+// size too (output_%04d_lo_albedo.pfm, _lo_normal.pfm, _lo_depth.pfm) and at full size, and guided upsampling (vk_upsample_* with the
+// library's default parameters) brings the frame and its standard error to full size: output_%04d_upsampled.ppm and .pfm.  The temporal,
+// denoise, glare and display steps then run on that frame at full size.  scale = 0, 100 or absent: no such call is made and every file
+// is what it was.
 // Texture images are read from ./assets (as in the reference) or $VECCHIO_ASSETS: <name>.ppm.gz, see host_api.h.
 #include <dlfcn.h>
 
@@ -67,7 +73,7 @@ static T sym(void *h, const char *name) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <balls_demo|random_spheres_demo|random_spheres_iow|perlin_demo|bowser_demo|cornell_box|final_scene|"
-                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal] [guide_bounces] [display] [glare]\n", argv[0]);
+                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal] [guide_bounces] [display] [glare] [scale]\n", argv[0]);
         return 2;
     }
     const char *name = argv[1];
@@ -89,6 +95,16 @@ int main(int argc, char **argv) {
     const uint32_t glare_pct = argc > 13 ? (uint32_t)atoi(argv[13]) : 0;
     if (glare_pct > 100) {
         fprintf(stderr, "glare is the strength in percent: 0 (off) to 100\n");
+        return 2;
+    }
+    const uint32_t scale_pct = argc > 14 ? (uint32_t)atoi(argv[14]) : 0;
+    if (scale_pct > 100) {
+        fprintf(stderr, "scale is the render scale in percent: 1 to 99; 0 or 100 is off\n");
+        return 2;
+    }
+    const bool scaled = scale_pct != 0 && scale_pct != 100;
+    if (scaled && aov_spp == 0) {
+        fprintf(stderr, "scale needs the first-hit buffers at both sizes: aov_spp > 0\n");
         return 2;
     }
     if (steps < 1) steps = 1;
@@ -144,6 +160,13 @@ int main(int argc, char **argv) {
     auto p_glare_create = sym<int (*)(vk_scene *, uint32_t, uint32_t, vk_glare **)>(h, "vk_glare_create");
     auto p_glare_apply = sym<int (*)(vk_glare *, const vk_glare_params *, const float *, float *)>(h, "vk_glare_apply");
     auto p_glare_destroy = sym<void (*)(vk_glare *)>(h, "vk_glare_destroy");
+    auto p_up_defaults = sym<int (*)(vk_upsample_params *)>(h, "vk_upsample_default_params");
+    auto p_up_create = sym<int (*)(vk_scene *, uint32_t, uint32_t, uint32_t, uint32_t, vk_upsample **)>(h, "vk_upsample_create");
+    auto p_up_load = sym<int (*)(vk_upsample *, const float *, const float *, const float *, const float *, const float *)>(h, "vk_upsample_load");
+    auto p_up_apply = sym<int (*)(vk_upsample *, const vk_upsample_params *, const float *, const float *, const float *, float *, float *)>(
+        h, "vk_upsample_apply");
+    auto p_up_info = sym<int (*)(vk_upsample *, vk_upsample_info *)>(h, "vk_upsample_get_info");
+    auto p_up_destroy = sym<void (*)(vk_upsample *)>(h, "vk_upsample_destroy");
 
     fprintf(stderr, "Generating scene...\n");                        // main.rs:157
     vkh_scene *hs = vkh_scene_build(name, seed);
@@ -155,8 +178,14 @@ int main(int argc, char **argv) {
     if (p_create(vkh_scene_desc(hs), 0, &scene) != VK_OK) { fprintf(stderr, "vk_scene_create: %s\n", p_err()); return 1; }
 
     std::vector<float> pixels((size_t)width * height * 3, 0.0f);     // main.rs:173
+    // the size the paths are traced at, and the frame they land in: the full one, or the low one of a render scale
+    const uint32_t lw = scaled ? (uint32_t)((uint64_t)width * scale_pct / 100u) : width;
+    const uint32_t lh = scaled ? (uint32_t)((float)lw / aspect) : height;
+    std::vector<float> low(scaled ? (size_t)lw * lh * 3 : 0, 0.0f);
+    float *const traced = scaled ? low.data() : pixels.data();
+    const size_t traced_floats = (size_t)lw * lh * 3;
     vk_render_params rp{};
-    rp.width = width; rp.height = height; rp.samples_per_pixel = spp; rp.max_depth = depth; rp.seed = seed + 1;
+    rp.width = lw; rp.height = lh; rp.samples_per_pixel = spp; rp.max_depth = depth; rp.seed = seed + 1;
     rp.integrator = integ; rp.background = bg; rp.background_color[0] = bgc[0]; rp.background_color[1] = bgc[1];
     rp.background_color[2] = bgc[2];
     rp.tile_rank = 0; rp.tile_world = 1;
@@ -170,6 +199,8 @@ int main(int argc, char **argv) {
     if (display && p_tone_create(scene, width, height, &tone) != VK_OK) { fprintf(stderr, "vk_tone_create: %s\n", p_err()); return 1; }
     vk_glare *glare = nullptr;
     if (glare_pct && p_glare_create(scene, width, height, &glare) != VK_OK) { fprintf(stderr, "vk_glare_create: %s\n", p_err()); return 1; }
+    vk_upsample *upsampler = nullptr;
+    if (scaled && p_up_create(scene, lw, lh, width, height, &upsampler) != VK_OK) { fprintf(stderr, "vk_upsample_create: %s\n", p_err()); return 1; }
     vk_camera cam;
     int file_idx = 0;
     while (file_idx < frames && vkh_scene_next_camera(hs, &cam)) {   // main.rs:176
@@ -178,27 +209,27 @@ int main(int argc, char **argv) {
         vk_stats st{};
         std::vector<float> err;                                       // the final standard error (steps >= 2)
         if (steps == 1) {
-            if (p_render(scene, &cam, &rp, pixels.data(), &st) != VK_OK) { fprintf(stderr, "vk_render: %s\n", p_err()); return 1; }
+            if (p_render(scene, &cam, &rp, traced, &st) != VK_OK) { fprintf(stderr, "vk_render: %s\n", p_err()); return 1; }
         } else {
             vk_progress *pr = nullptr;
             if (p_pcreate(scene, &cam, &rp, VK_PROGRESS_STDERR, &pr) != VK_OK) { fprintf(stderr, "vk_progress_create: %s\n", p_err()); return 1; }
-            err.resize(pixels.size());
+            err.resize(traced_floats);
             uint32_t done = 0;
             for (uint32_t k = 0; k < steps; k++) {
                 const uint32_t n = (uint32_t)((uint64_t)spp * (k + 1) / steps) - done;
                 vk_stats sw{};
-                if (p_pstep(pr, n, pixels.data(), &sw) != VK_OK) { fprintf(stderr, "vk_progress_step: %s\n", p_err()); return 1; }
+                if (p_pstep(pr, n, traced, &sw) != VK_OK) { fprintf(stderr, "vk_progress_step: %s\n", p_err()); return 1; }
                 done += n;
                 st.samples += sw.samples; st.kernel_ms += sw.kernel_ms; st.kernel_launches += sw.kernel_launches;
                 char sfn[64];
                 snprintf(sfn, sizeof sfn, "output_%04d_step%02u.ppm", file_idx, k);
-                if (vkh_write_ppm(sfn, pixels.data(), width, height)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }
+                if (vkh_write_ppm(sfn, traced, lw, lh)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }
                 // mean relative standard error over the pixel components with a non-zero mean (needs two windows)
                 double rel = 0.0; size_t cnt = 0;
                 if (k >= 1) {
                     if (p_pstderr(pr, err.data()) != VK_OK) { fprintf(stderr, "vk_progress_stderr: %s\n", p_err()); return 1; }
-                    for (size_t i = 0; i < pixels.size(); i++)
-                        if (pixels[i] > 0.0f && std::isfinite(err[i])) { rel += (double)err[i] / (double)pixels[i]; cnt++; }
+                    for (size_t i = 0; i < traced_floats; i++)
+                        if (traced[i] > 0.0f && std::isfinite(err[i])) { rel += (double)err[i] / (double)traced[i]; cnt++; }
                 }
                 if (k >= 1) fprintf(stderr, "  %s: %u/%u samples, mean relative standard error %.4f\n", sfn, done, spp, cnt ? rel / (double)cnt : 0.0);
                 else fprintf(stderr, "  %s: %u/%u samples, mean relative standard error n/a (one window)\n", sfn, done, spp);
@@ -207,25 +238,58 @@ int main(int argc, char **argv) {
         }
         char fn[64];
         snprintf(fn, sizeof fn, "output_%04d.ppm", file_idx);         // main.rs:201
-        if (vkh_write_ppm(fn, pixels.data(), width, height)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }
+        if (vkh_write_ppm(fn, traced, lw, lh)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }
         std::vector<float> shown;                                     // the last stage's float frame (display): empty = `pixels`
         if (aov_spp > 0) {
             const size_t np = (size_t)width * height;
             std::vector<float> albedo(np * 3), normal(np * 3), zdepth(np), coverage(np);
             vk_render_params ap = rp;
-            ap.samples_per_pixel = aov_spp;
+            ap.width = width; ap.height = height; ap.samples_per_pixel = aov_spp;
             vk_stats as{};
             if (p_aov(scene, &cam, &ap, 0, albedo.data(), normal.data(), zdepth.data(), coverage.data(), &as) != VK_OK) {
                 fprintf(stderr, "vk_render_aov: %s\n", p_err()); return 1; }
             const struct { const char *suffix; const float *data; int ch; } outs[] = {
-                {"", pixels.data(), 3}, {"_albedo", albedo.data(), 3}, {"_normal", normal.data(), 3}, {"_depth", zdepth.data(), 1},
+                {"", traced, 3}, {"_albedo", albedo.data(), 3}, {"_normal", normal.data(), 3}, {"_depth", zdepth.data(), 1},
                 {"_coverage", coverage.data(), 1}};
             for (const auto &o : outs) {
                 char pfn[64];
                 snprintf(pfn, sizeof pfn, "output_%04d%s.pfm", file_idx, o.suffix);
-                if (!write_pfm(pfn, o.data, width, height, o.ch)) return 1;
+                if (!write_pfm(pfn, o.data, o.data == traced ? lw : width, o.data == traced ? lh : height, o.ch)) return 1;
             }
             fprintf(stderr, "  first-hit buffers of %u samples per pixel: kernel %.2f ms\n", aov_spp, as.kernel_ms);
+            if (scaled) {
+                // the same samples' first-hit buffers at the low size, then the low frame (and its standard error) to full size: from here
+                // on `pixels` and `err` are full-size images
+                const size_t nl = (size_t)lw * lh;
+                std::vector<float> lalbedo(nl * 3), lnormal(nl * 3), ldepth(nl), err_hi(err.empty() ? 0 : np * 3);
+                vk_render_params lp = ap;
+                lp.width = lw; lp.height = lh;
+                vk_stats ls{};
+                vk_upsample_params up;
+                vk_upsample_info ui{};
+                if (p_aov(scene, &cam, &lp, 0, lalbedo.data(), lnormal.data(), ldepth.data(), nullptr, &ls) != VK_OK) {
+                    fprintf(stderr, "vk_render_aov: %s\n", p_err()); return 1; }
+                const struct { const char *suffix; const float *data; int ch; } louts[] = {
+                    {"_lo_albedo", lalbedo.data(), 3}, {"_lo_normal", lnormal.data(), 3}, {"_lo_depth", ldepth.data(), 1}};
+                for (const auto &o : louts) {
+                    char pfn[64];
+                    snprintf(pfn, sizeof pfn, "output_%04d%s.pfm", file_idx, o.suffix);
+                    if (!write_pfm(pfn, o.data, lw, lh, o.ch)) return 1;
+                }
+                if (p_up_defaults(&up) != VK_OK ||
+                    p_up_load(upsampler, traced, err.empty() ? nullptr : err.data(), lalbedo.data(), lnormal.data(), ldepth.data()) != VK_OK ||
+                    p_up_apply(upsampler, &up, albedo.data(), normal.data(), zdepth.data(), pixels.data(), err.empty() ? nullptr : err_hi.data()) != VK_OK ||
+                    p_up_info(upsampler, &ui) != VK_OK) {
+                    fprintf(stderr, "vk_upsample: %s\n", p_err()); return 1; }
+                if (!err.empty()) err.swap(err_hi);
+                char ufn[64];
+                snprintf(ufn, sizeof ufn, "output_%04d_upsampled.ppm", file_idx);
+                if (vkh_write_ppm(ufn, pixels.data(), width, height)) { fprintf(stderr, "%s\n", vkh_last_error()); return 1; }
+                snprintf(ufn, sizeof ufn, "output_%04d_upsampled.pfm", file_idx);
+                if (!write_pfm(ufn, pixels.data(), width, height, 3)) return 1;
+                fprintf(stderr, "  upsampled %u x %u to %u x %u: kernel %.2f ms, %llu pixels by the tent alone, %llu empty\n", lw, lh, width, height,
+                        ui.last_kernel_ms, (unsigned long long)ui.fallback_pixels, (unsigned long long)ui.empty_pixels);
+            }
             // what the temporal and denoise steps are guided by: the first-hit buffers, or the specular guides
             const float *g_albedo = albedo.data(), *g_normal = normal.data(), *g_depth = zdepth.data();
             std::vector<float> galbedo, gnormal, gdepth, gbounces;
@@ -315,6 +379,7 @@ int main(int argc, char **argv) {
                 st.kernel_ms > 0 ? (double)st.samples / st.kernel_ms / 1e3 : 0.0);   // main.rs:215
         file_idx++;
     }
+    if (upsampler) p_up_destroy(upsampler);
     if (glare) p_glare_destroy(glare);
     if (tone) p_tone_destroy(tone);
     if (history) p_tdestroy(history);

@@ -226,6 +226,13 @@ pub struct vk_glare_params { pub levels: u32, pub strength: f32, pub falloff: f3
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_glare_info { pub width: u32, pub height: u32, pub applies: u64, pub last_levels: u32, pub last_form: u32, pub last_launches: u32, pub _pad: u32, pub last_kernel_ms: f64, pub scratch_bytes: u64 }
 
+// guided upsampling: the filter's parameters, and what a handle holds and last did
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_upsample_params { pub sigma_z: f32, pub normal_squarings: u32, pub albedo_floor: f32, pub flags: u32, pub _pad: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_upsample_info { pub width_lo: u32, pub height_lo: u32, pub width_hi: u32, pub height_hi: u32, pub loaded: u32, pub guides: u32, pub loads: u64, pub applies: u64, pub last_form: u32, pub last_launches: u32, pub last_kernel_ms: f64, pub scratch_bytes: u64, pub fallback_pixels: u64, pub empty_pixels: u64 }
+
 // regeneration: what one vk_regen_step did
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_regen_info { pub traced: u64, pub live: u64, pub remaining: u64, pub emitted: u64, pub missed: u64, pub ended: u64, pub bad: u64, pub bounces: u32, pub kernel_launches: u32, pub kernel_ms: f64, pub seconds: f64 }
@@ -247,6 +254,7 @@ pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, 
 #[repr(C)] pub struct vk_tone { _private: [u8; 0] }
 #[repr(C)] pub struct vk_nlm { _private: [u8; 0] }
 #[repr(C)] pub struct vk_glare { _private: [u8; 0] }
+#[repr(C)] pub struct vk_upsample { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -413,6 +421,18 @@ extern "C" {
     pub fn vk_glare_apply_device(g: *mut vk_glare, p: *const vk_glare_params, d_rgb_in: *const c_void, d_rgb_out: *mut c_void) -> c_int;
     pub fn vk_glare_get_info(g: *mut vk_glare, out: *mut vk_glare_info) -> c_int;
     pub fn vk_glare_destroy(g: *mut vk_glare);
+    // guided upsampling (additive symbols of ABI 7): a w x h frame and its stderr3 to W x H along the edges of albedo, normal and depth
+    // given at both sizes; every image but color_lo and rgb_out may be null; no function takes a stream (the _device calls are enqueued
+    // on the null stream)
+    pub fn vk_upsample_default_params(out: *mut vk_upsample_params) -> c_int;
+    pub fn vk_upsample_create(scene: *mut vk_scene, w: u32, h: u32, width_hi: u32, height_hi: u32, out: *mut *mut vk_upsample) -> c_int;
+    pub fn vk_upsample_load(u: *mut vk_upsample, color_lo: *const f32, stderr3_lo: *const f32, albedo_lo: *const f32, normal_lo: *const f32, depth_lo: *const f32) -> c_int;
+    pub fn vk_upsample_load_device(u: *mut vk_upsample, d_color_lo: *const c_void, d_stderr3_lo: *const c_void, d_albedo_lo: *const c_void, d_normal_lo: *const c_void, d_depth_lo: *const c_void) -> c_int;
+    pub fn vk_upsample_apply(u: *mut vk_upsample, p: *const vk_upsample_params, albedo_hi: *const f32, normal_hi: *const f32, depth_hi: *const f32, rgb_out: *mut f32, stderr3_out: *mut f32) -> c_int;
+    pub fn vk_upsample_apply_device(u: *mut vk_upsample, p: *const vk_upsample_params, d_albedo_hi: *const c_void, d_normal_hi: *const c_void, d_depth_hi: *const c_void, d_rgb_out: *mut c_void, d_stderr3_out: *mut c_void) -> c_int;
+    pub fn vk_upsample_reset(u: *mut vk_upsample) -> c_int;
+    pub fn vk_upsample_get_info(u: *mut vk_upsample, out: *mut vk_upsample_info) -> c_int;
+    pub fn vk_upsample_destroy(u: *mut vk_upsample);
     // ID mattes (additive symbols of ABI 7): a ranked table of object or material ids per pixel, ids / counts ranks words per pixel,
     // overflow one (may be null); merge and mask are host code
     pub fn vk_matte_default_params(out: *mut vk_matte_params) -> c_int;

@@ -693,6 +693,12 @@ class DeviceScene:
         manager, or close() it before the scene."""
         return Glare(self, width, height)
 
+    def upsample(self, w, h, W, H):
+        """A guided upsampler on this scene's device (vk_upsample_create) from w x h to W x H: load() a low frame with its stderr3 and
+        first-hit buffers, apply() with the first-hit buffers at the high size.  Use as a context manager, or close() it before the
+        scene."""
+        return Upsample(self, w, h, W, H)
+
     def debug_compact_paths(self, items, ids, n_ids, canary=0xA5, roulette=None):
         """The compaction of a path batch's bounce on host arrays (vk_debug_compact_paths, a test hook): items a SHADED_DTYPE array, ids
         their uint32 ids (each below n_ids).  Every output is prefilled with the byte `canary`.  Returns (rays, states, ids_out — n
@@ -1722,6 +1728,114 @@ class Glare:
     def close(self):
         if self._h:
             self._lib.vk_glare_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Upsample:
+    """vk_upsample handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed): guided upsampling from
+    w x h to W x H.  load() the low frame from host memory or load_device() it from the handle's device, then apply() / apply_device()
+    with the high guides (y = 0 the bottom row; colour, stderr3, albedo and normal 3 floats a pixel, depth 1).  The loaded frame stays
+    until the next load or reset()."""
+
+    def __init__(self, scene, w, h, W, H):
+        self._lib = scene._lib
+        self._scene = scene
+        self.w, self.h, self.W, self.H = int(w), int(h), int(W), int(H)
+        u = C.c_void_p()
+        check(self._lib, self._lib.vk_upsample_create(scene._h, w, h, W, H, C.byref(u)))
+        self._h = u
+
+    def _host(self, a, n):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, np.float32)
+        assert a.size == n, (a.size, n)
+        return a, a.ctypes.data_as(C.c_void_p)
+
+    def _device(self, t, n):
+        if t is None:
+            return None
+        if hasattr(t, "data_ptr"):
+            assert t.is_contiguous() and t.numel() == n and t.element_size() == 4
+            return C.c_void_p(t.data_ptr())
+        return C.c_void_p(t)
+
+    def params(self, **kw):
+        """ffi.UpsampleParams: the defaults of the handle's library (vk_upsample_default_params) with the given fields replaced"""
+        p = ffi.UpsampleParams()
+        check(self._lib, self._lib.vk_upsample_default_params(C.byref(p)))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    def load(self, color, stderr3=None, albedo=None, normal=None, depth=None):
+        """The low frame from host memory (vk_upsample_load): float32 arrays of w * h * 3 values (depth: w * h); all but color may be None"""
+        n = self.w * self.h
+        keep = [self._host(a, n * c) for a, c in ((color, 3), (stderr3, 3), (albedo, 3), (normal, 3), (depth, 1))]
+        check(self._lib, self._lib.vk_upsample_load(self._h, *[k[1] for k in keep]))
+
+    def load_device(self, color, stderr3=None, albedo=None, normal=None, depth=None):
+        """The low frame from memory of the handle's device (vk_upsample_load_device, enqueued on the null stream): contiguous float32
+        tensors (objects with data_ptr()) or device pointers"""
+        n = self.w * self.h
+        check(self._lib, self._lib.vk_upsample_load_device(self._h, *[self._device(t, n * c) for t, c in
+                                                                      ((color, 3), (stderr3, 3), (albedo, 3), (normal, 3), (depth, 1))]))
+
+    def apply(self, albedo=None, normal=None, depth=None, want_stderr=True, params=None, **kw):
+        """The upsampled frame (vk_upsample_apply): (rgb, stderr3) as float32 (H, W, 3), stderr3 None when want_stderr is False.  albedo,
+        normal, depth: the first-hit buffers at W x H, or None.  params: an ffi.UpsampleParams, or keywords over the defaults (sigma_z,
+        normal_squarings, albedo_floor)."""
+        p = params if params is not None else self.params(**kw)
+        n = self.W * self.H
+        keep = [self._host(a, n * c) for a, c in ((albedo, 3), (normal, 3), (depth, 1))]
+        out = np.zeros((self.H, self.W, 3), np.float32)
+        se = np.zeros((self.H, self.W, 3), np.float32) if want_stderr else None
+        check(self._lib, self._lib.vk_upsample_apply(self._h, C.byref(p), *[k[1] for k in keep], out.ctypes.data_as(C.c_void_p),
+                                                     se.ctypes.data_as(C.c_void_p) if want_stderr else None))
+        return out, se
+
+    def apply_device(self, d_out, d_stderr3=None, albedo=None, normal=None, depth=None, params=None, **kw):
+        """The upsampled frame in memory of the handle's device (vk_upsample_apply_device, enqueued on the null stream): contiguous
+        float32 tensors (objects with data_ptr()) or device pointers; d_stderr3 None = not wanted.  Returns (d_out, d_stderr3)."""
+        p = params if params is not None else self.params(**kw)
+        n = self.W * self.H
+        check(self._lib, self._lib.vk_upsample_apply_device(self._h, C.byref(p), self._device(albedo, n * 3), self._device(normal, n * 3),
+                                                            self._device(depth, n), self._device(d_out, n * 3), self._device(d_stderr3, n * 3)))
+        return d_out, d_stderr3
+
+    def reset(self):
+        check(self._lib, self._lib.vk_upsample_reset(self._h))
+
+    def info(self):
+        inf = ffi.UpsampleInfo()
+        check(self._lib, self._lib.vk_upsample_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def set_form(self, form):
+        """The filter kernel's form, ffi.VK_UPSAMPLE_FORM_AUTO, _PLAIN or _TILED (vk_debug_upsample_set_form, a test hook)"""
+        check(self._lib, self._lib.vk_debug_upsample_set_form(self._h, form))
+
+    def last_ms(self):
+        """device milliseconds of the last apply's filter kernel (vk_debug_upsample_last_ms, a test hook)"""
+        ms = C.c_double()
+        check(self._lib, self._lib.vk_debug_upsample_last_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if self._h:
+            self._lib.vk_upsample_destroy(self._h)
             self._h = None
 
     def __enter__(self):
