@@ -1577,6 +1577,101 @@ int vk_glare_apply_device(vk_glare *g, const vk_glare_params *p, const void *d_r
 int vk_glare_get_info(vk_glare *g, vk_glare_info *out);
 void vk_glare_destroy(vk_glare *g);
 
+/* ---- point-spread function: aperture glare by FFT convolution with a caller's kernel (additive symbols of ABI 7) --------------------
+ * replaces: nothing.  vk_glare is one radially decaying halo; the star, the streaks and the coloured fringe by which a camera or an eye
+ * tells one clipped highlight from another are the aperture's point-spread function.  vk_psf_apply convolves the bright part of a float
+ * frame with an arbitrary K x K kernel per colour component, up to 1023 pixels wide, spreads the share `strength` of it and takes the
+ * same share away where it came from: a float frame in (vk_render's layout, y = 0 the bottom row, 3 floats a pixel), a float frame of
+ * the same shape out, which vk_tone_load / vk_tone_load_device take.  In the pipeline it sits between vk_glare and vk_tone.
+ *
+ * State.  A handle for one width x height and kernels up to kmax on the scene's device (devices[0] of a multi-device scene): three
+ * planes F and three planes G of Px x Py complex f32 at kmax's padded size (8 bytes a value), the two twiddle tables, the normalised
+ * kernel, and, after the first call that needs them, room for a frame in and a frame out of the host-pointer call and a copy of the
+ * input of an in-place apply.  vk_psf_load keeps the kernel's transform G until the next load or vk_psf_reset; nothing else is kept
+ * between applies.  All work is on the null stream there; no function takes a stream.  vk_psf_apply_device is ordered exactly as
+ * vk_glare_apply_device is: ENQUEUED on the null stream: work the caller issued earlier on the null stream or on a blocking stream is
+ * ordered before it, and the output is ready when the null stream is; a caller with a non-blocking stream synchronises first (and waits
+ * for the null stream afterwards).  d_rgb_out may be d_rgb_in: the kernel that writes a pixel reads that pixel of the input only (in
+ * the LDS form from a copy made first), and every other kernel has read the input before it.  vk_psf_apply goes through the staging path
+ * of the host-pointer calls and waits; rgb_out may be rgb_in.  vk_psf_load waits; vk_psf_load_device brings the kernel to the host
+ * first (which waits for the null stream), checks and normalises it there, and enqueues the rest.
+ *
+ * The operator, exactly.  Everything on the device is f32, unfused, in the order written, with + - *, fmaxf, fminf and compares; one
+ * division, and only when threshold > 0; no transcendental function.  tests/psf_ref.py restates it in numpy and the two agree bit for
+ * bit as floats (-0 equal to +0, a NaN's payload aside).
+ *   Kernel.  K x K x 3 floats, K odd, 3 <= K <= 1023, tap (kx, ky) at (ky * K + kx) * 3 + c, y up as the frame, centre at r = (K - 1)
+ *     / 2.  Every component finite and >= 0.  S_c = the f64 sum of channel c in ascending index order, > 0; k_c[i] = (float)((double)
+ *     k_c[i] / S_c).
+ *   Padded size.  Px = the smallest power of two >= W + K - 1, Py the same of H + K - 1; at most 4096 each.  Outside the frame the
+ *     source is zero: energy that leaves the frame is lost, and nothing wraps.
+ *   Bright part, per pixel of the input I: vk_glare's.  s_c = I_c > 0 ? (I_c < 1048576.0f ? I_c : 1048576.0f) : 0.0f.  If a component
+ *     of I is not finite, B = 0 for the whole pixel.  If threshold == 0, B_c = s_c.  Otherwise Y = (0.2126f * s_r + 0.7152f * s_g) +
+ *     0.0722f * s_b, f = fmaxf(0, Y - threshold) / fmaxf(Y, 1e-20f), B_c = s_c * f.
+ *   Twiddle tables, on the host in f64 with + - * / and sqrt only.  R_q = (c_q, s_q) = (cos, sin)(pi / 2^q): c_1 = 0, s_1 = 1; c_{q+1}
+ *     = sqrt((1 + c_q) / 2), s_{q+1} = s_q / (2 * c_{q+1}).  For N = 2^m and k < N / 2: z = (1, 0); for t = 0 .. m - 2 in this order,
+ *     if bit t of k is set, z = (z.re * c_q - z.im * s_q, z.re * s_q + z.im * c_q) with q = m - 1 - t.  T[k] = ((float)z.re, (float)(0
+ *     - z.im)) = exp(-2 pi i k / N) rounded; T[0] = (1, 0) and T[N/4] = (0, -1) exactly.
+ *   1-D transform of a length N = 2^m: radix 2, decimation in time.  a[rev_m(i)] = input[i] (rev_m reverses the m bits).  For s = 1 ..
+ *     m, half = 2^(s-1), for every block start b (a multiple of 2^s) and j < half: p = b + j, w = T[j * N / 2^s] (the inverse
+ *     transform negates w.im), u = a[p], v = a[p + half]; t.re = v.re * w.re - v.im * w.im, t.im = v.re * w.im + v.im * w.re; a[p] = u
+ *     + t, a[p + half] = u - t, componentwise.  Every butterfly does the full multiply.
+ *   2-D transform.  Every row along x, then every column along y; the input's imaginary parts are +0.  The inverse is the same with
+ *     inverse 1-D transforms, and ends with ONE multiplication by the exact power of two 1 / (Px * Py).
+ *   Convolution.  F_c = FFT2(B_c, +0 outside the frame).  G_c = FFT2(k_c placed with its centre at (0, 0), wrapped: tap (kx, ky) at
+ *     ((kx - r) mod Px, (ky - r) mod Py)), made once at load.  P = F ⊙ G with the butterfly's multiply, v = F, w = G.  C_c = re(IFFT2(P))
+ *     * (1 / (Px * Py)) at the W x H pixels.
+ *   Composite.  out_c = I_c + strength * (C_c - B_c).  A component that is not finite stays what it was.  strength = 0 gives out == I
+ *     as floats (a -0 becomes +0).
+ * vk_psf_star fills a kernel for the CLI and the Python layer; the operator takes any.  In f64, not bit-pinned (it calls libm): with r
+ * = (K - 1) / 2, g_c = 1 + chroma * (c - 1) for c = 0, 1, 2, d = sqrt(x^2 + y^2) / g_c for x, y in -r .. r:
+ *   v = exp(-d^2 / 2) + [streaks > 0, d > 0, d < r] 0.25 * |cos(streaks / 2 * (atan2(y, x) - rotation))|^sharpness * (1 - d / r)^2 /
+ *   (1 + d), each channel then divided by its sum.  `streaks` rays at a spacing of 2 pi / streaks from `rotation` (an even count gives
+ *   pairs of opposite rays); with chroma = 0 the three channels are equal.
+ * What this is not.  No kernel from an aperture mask, no ghosts or flares, no real-to-complex packing, no sizes that are no power of
+ * two, no tiling beyond 4096, no multi-device partition, no clamped or mirrored border.
+ *
+ *   vk_psf_default_params: strength 0.15, threshold 0, form AUTO, flags and _pad 0.  Touches no device.
+ *   vk_psf_star: VK_ERR_BAD_ARG for a null pointer, K even or outside 3..1023, streaks > 64, rotation not finite, sharpness not finite
+ *     or < 1, chroma not finite or outside [0, 0.5].  Touches no device.
+ *   vk_psf_create: VK_ERR_BAD_ARG for a null pointer, width or height 0, kmax even or outside 3..1023, width + kmax - 1 or height +
+ *     kmax - 1 > 4096.  VK_ERR_OOM leaves *out untouched.
+ *   vk_psf_load / vk_psf_load_device: VK_ERR_BAD_ARG, the loaded kernel untouched, for a null pointer, K even, outside 3..1023 or >
+ *     kmax, a component that is not finite or is negative, a channel whose sum is not > 0.
+ *   vk_psf_apply / vk_psf_apply_device: VK_ERR_BAD_ARG, nothing enqueued and the output untouched, for a null handle, params, input or
+ *     output, an apply before a load (or after vk_psf_reset), strength not finite or outside [0, 1], threshold not finite or < 0, an
+ *     unknown form, flags or _pad != 0.
+ *   vk_psf_reset forgets the loaded kernel.  vk_psf_destroy(NULL) does nothing.                                                         */
+enum { VK_PSF_FORM_AUTO = 0, VK_PSF_FORM_PLAIN = 1, VK_PSF_FORM_LDS = 2 };
+typedef struct vk_psf vk_psf;            /* opaque */
+typedef struct vk_psf_params {           /* 20 bytes */
+    float strength;                      /* 0..1: the share of the bright part that is spread */
+    float threshold;                     /* >= 0: luminance below which a pixel spreads nothing; 0 = everything spreads */
+    uint32_t form;                       /* VK_PSF_FORM_*: PLAIN = a launch per butterfly stage over global memory; LDS = whole lines in
+                                            LDS, four launches; AUTO = LDS (DESIGN.md "Point-spread function").  All give the same bits. */
+    uint32_t flags;                      /* 0 */
+    uint32_t _pad;                       /* 0 */
+} vk_psf_params;
+typedef struct vk_psf_info {             /* 64 bytes */
+    uint32_t width, height;
+    uint32_t K, Px, Py;                  /* of the loaded kernel; 0 before a load */
+    uint32_t kmax;
+    uint32_t last_form;                  /* VK_PSF_FORM_PLAIN or VK_PSF_FORM_LDS of the last apply; 0 before one */
+    uint32_t last_launches;              /* the kernels the last apply (or, after a load, the load) launched */
+    uint64_t loads, applies;             /* accepted calls since create */
+    double last_kernel_ms;               /* the device time of the last apply's kernels, first to last; 0 before one (waits for it) */
+    uint64_t scratch_bytes;              /* the device memory the handle owns */
+} vk_psf_info;
+int vk_psf_default_params(vk_psf_params *out);
+int vk_psf_star(uint32_t K, uint32_t streaks, float rotation, float sharpness, float chroma, float *out);
+int vk_psf_create(vk_scene *scene, uint32_t width, uint32_t height, uint32_t kmax, vk_psf **out);
+int vk_psf_load(vk_psf *h, uint32_t K, const float *kernel);
+int vk_psf_load_device(vk_psf *h, uint32_t K, const void *d_kernel);
+int vk_psf_apply(vk_psf *h, const vk_psf_params *p, const float *rgb_in, float *rgb_out);
+int vk_psf_apply_device(vk_psf *h, const vk_psf_params *p, const void *d_rgb_in, void *d_rgb_out);
+int vk_psf_reset(vk_psf *h);
+int vk_psf_get_info(vk_psf *h, vk_psf_info *out);
+void vk_psf_destroy(vk_psf *h);
+
 /* ---- guided upsampling: a low-resolution frame to full size along the edges of full-size AOVs (additive symbols of ABI 7) ------------
  * replaces: nothing.  Render scale: the paths are traced at w x h, the first-hit buffers (vk_render_aov, or vk_render_guides for both
  * sizes) at w x h and at W x H — they cost a small fraction of a frame —, and vk_upsample_apply brings colour and its standard error to

@@ -234,6 +234,19 @@ int vk_debug_upsample_set_form(vk_upsample *u, uint32_t form);
  * and without a prepare pass); 0 before one.  Waits for it.  Takes no stream.  In both libraries. */
 int vk_debug_upsample_last_ms(vk_upsample *u, double *ms);
 
+/* the library's twiddle table of a length N (vecchio_amd.h "Twiddle tables"): N / 2 entries of (re, im) into out[N].  VK_ERR_BAD_ARG for
+ * a null pointer or an N that is no power of two in 2..4096.  Touches no device.  In both libraries. */
+int vk_psf_debug_twiddles(uint32_t N, float *out);
+/* one bare 2-D transform (vecchio_amd.h "2-D transform") of the caller's Px x Py complex values in host memory, (re, im) pairs, row y at
+ * y * Px, in place: forward, or inverse with its closing multiplication by 1 / (Px * Py), by the kernels of the form VK_PSF_FORM_PLAIN
+ * or VK_PSF_FORM_LDS on the scene's device.  VK_ERR_BAD_ARG for a null pointer, a size that is no power of two in 2..4096, inverse > 1,
+ * another form.  Waits.  Takes no stream.  In both libraries. */
+int vk_psf_debug_fft2(vk_scene *scene, uint32_t Px, uint32_t Py, uint32_t inverse, uint32_t form, float *data);
+/* the device milliseconds of the four passes of the handle's last apply, between events recorded around them: rows forward (with the
+ * bright part), columns forward, the product and rows inverse, columns inverse with the composite; zeros before an apply and after one
+ * in the PLAIN form.  Waits for it.  Takes no stream.  In both libraries. */
+int vk_psf_debug_last_pass_ms(vk_psf *h, double ms[4]);
+
 /* the id of every sample vk_render_mattes would count, by the same per-lane code on the same lanes: ids_out[(y * width + x) * spp + k] is
  * the id of sample first_sample + k under `kind` (VK_MATTE_OBJECT or VK_MATTE_MATERIAL), spp = params->samples_per_pixel; pixels outside
  * the call's tile partition are left untouched.  vk_render_mattes' checks.  Waits.  In both libraries. */

@@ -77,7 +77,7 @@ def _device_deps():
     return srcs, srcs + [os.path.join(CSRC, f) for f in ("vk_kernels.h", "vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_resources.h",
                                                          "vk_emit.h", "vk_adapt.h", "vk_adapt.hip", "vk_splat.h", "vk_splat.hip", "vk_matte.h",
                                                          "vk_matte.hip", "vk_robust.h", "vk_robust.hip", "vk_lpe.h", "vk_lpe.hip", "vk_tone.h", "vk_tone.hip",
-                                                         "vk_nlm.h", "vk_nlm.hip", "vk_glare.h", "vk_glare.hip", "vk_upsample.h", "vk_upsample.hip")] + \
+                                                         "vk_nlm.h", "vk_nlm.hip", "vk_glare.h", "vk_glare.hip", "vk_upsample.h", "vk_upsample.hip", "vk_psf.h", "vk_psf.hip")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
 
 
@@ -91,7 +91,7 @@ def device_is_stale():
         not os.path.exists(kernel_resources_matte_path()) or not os.path.exists(kernel_resources_robust_path()) or \
         not os.path.exists(kernel_resources_lpe_path()) or not os.path.exists(kernel_resources_tone_path()) or \
         not os.path.exists(kernel_resources_nlm_path()) or not os.path.exists(kernel_resources_glare_path()) or \
-        not os.path.exists(kernel_resources_upsample_path())
+        not os.path.exists(kernel_resources_upsample_path()) or not os.path.exists(kernel_resources_psf_path())
 
 
 def build_host(force=False):
@@ -126,7 +126,7 @@ def build_device_debug(force=False):
     flags = HIPFLAGS + ["-DVK_DEBUG_LIB"]
     if force or _newer(out, deps, flags):
         os.makedirs(LIB, exist_ok=True)
-        _run_atomic([HIPCC] + flags + ["-shared", "-o"], out, srcs + [_adapt_src(), _splat_src(), _matte_src(), _robust_src(), _lpe_src(), _tone_src(), _nlm_src(), _glare_src(), _upsample_src()])
+        _run_atomic([HIPCC] + flags + ["-shared", "-o"], out, srcs + [_adapt_src(), _splat_src(), _matte_src(), _robust_src(), _lpe_src(), _tone_src(), _nlm_src(), _glare_src(), _upsample_src(), _psf_src()])
         _stamp(out, deps, flags)
     return out
 
@@ -185,6 +185,12 @@ def _upsample_src():
     return os.path.join(CSRC, "vk_upsample.hip")
 
 
+def _psf_src():
+    """the kernels of vk_psf_* (point-spread function: the pad, place, bit-reversal, stage, product, scale and composite kernels of the
+    plain form and the line kernel of the LDS form): a translation unit of its own"""
+    return os.path.join(CSRC, "vk_psf.hip")
+
+
 def _hipcc_with_remarks(cmd, cwd, cleanup=()):
     """runs a hipcc line that carries -Rpass-analysis=kernel-resource-usage and -save-temps in `cwd`: (the remark lines, kernel symbol ->
     scratch instructions from the gfx950 assembly it left there); everything else it wrote to stderr is passed on"""
@@ -219,8 +225,8 @@ def _write_resources(path, remarks, spills):
 
 
 def build_device(force=False):
-    """hipcc cross-compiles for gfx950 without a GPU present.  Ten steps: vk_adapt.hip, vk_splat.hip, vk_matte.hip, vk_robust.hip,
-    vk_lpe.hip, vk_tone.hip, vk_nlm.hip, vk_glare.hip and vk_upsample.hip to an object of their own each (their resource remarks go to kernel_resources_adapt.txt,
+    """hipcc cross-compiles for gfx950 without a GPU present.  Eleven steps: vk_adapt.hip, vk_splat.hip, vk_matte.hip, vk_robust.hip,
+    vk_lpe.hip, vk_tone.hip, vk_nlm.hip, vk_glare.hip, vk_upsample.hip and vk_psf.hip (kernel_resources_psf.txt) to an object of their own each (their resource remarks go to kernel_resources_adapt.txt,
     kernel_resources_splat.txt, kernel_resources_matte.txt, kernel_resources_robust.txt, kernel_resources_lpe.txt,
     kernel_resources_tone.txt, kernel_resources_nlm.txt, kernel_resources_glare.txt and kernel_resources_upsample.txt), then vk_api.hip and vk_linearize.cpp, linked with those objects (kernel_resources.txt: theirs alone)."""
     out = os.path.join(LIB, "libvecchio_amd.so")
@@ -266,9 +272,13 @@ def build_device(force=False):
             os.makedirs(tmp_upsample)
             upsample_obj = os.path.join(tmp_upsample, "vk_upsample.o")
             upsample = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", upsample_obj, _upsample_src()], tmp_upsample)
+            tmp_psf = os.path.join(tmp, "psf")
+            os.makedirs(tmp_psf)
+            psf_obj = os.path.join(tmp_psf, "vk_psf.o")
+            psf = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-c", "-o", psf_obj, _psf_src()], tmp_psf)
             tmp_out = f"{out}.tmp.{os.getpid()}"
             # (the objects in front of the sources: hipcc reads whatever follows a source file as HIP)
-            main = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-shared", "-o", tmp_out, adapt_obj, splat_obj, matte_obj, robust_obj, lpe_obj, tone_obj, nlm_obj, glare_obj, upsample_obj] + srcs, tmp_main, [tmp_out])
+            main = _hipcc_with_remarks([HIPCC] + HIPFLAGS + analysis + ["-shared", "-o", tmp_out, adapt_obj, splat_obj, matte_obj, robust_obj, lpe_obj, tone_obj, nlm_obj, glare_obj, upsample_obj, psf_obj] + srcs, tmp_main, [tmp_out])
             os.replace(tmp_out, out)
         _write_resources(kernel_resources_path(), *main)
         _write_resources(kernel_resources_adapt_path(), *adapt)
@@ -280,6 +290,7 @@ def build_device(force=False):
         _write_resources(kernel_resources_nlm_path(), *nlm)
         _write_resources(kernel_resources_glare_path(), *glare)
         _write_resources(kernel_resources_upsample_path(), *upsample)
+        _write_resources(kernel_resources_psf_path(), *psf)
         _stamp(out, deps, HIPFLAGS)
     return out
 
@@ -341,6 +352,11 @@ def kernel_resources_upsample_path():
     return os.path.join(LIB, "kernel_resources_upsample.txt")
 
 
+def kernel_resources_psf_path():
+    """the same record for the kernels of vk_psf.hip"""
+    return os.path.join(LIB, "kernel_resources_psf.txt")
+
+
 def build_oracle(force=False):
     """CPU oracle (test infrastructure).  oracle/_ref does not exist: the reference is Rust and
     there is no cargo/rustc in this image."""
@@ -364,11 +380,11 @@ def build_emu(force=False):
             os.path.join(edir, "emu_paths.cpp"), os.path.join(edir, "emu_film.cpp"), os.path.join(edir, "emu_adapt.cpp"),
             os.path.join(edir, "emu_splat.cpp"), os.path.join(edir, "emu_matte.cpp"), os.path.join(edir, "emu_robust.cpp"),
             os.path.join(edir, "emu_lpe.cpp"), os.path.join(edir, "emu_tone.cpp"), os.path.join(edir, "emu_nlm.cpp"),
-            os.path.join(edir, "emu_glare.cpp"), os.path.join(edir, "emu_upsample.cpp"),
+            os.path.join(edir, "emu_glare.cpp"), os.path.join(edir, "emu_upsample.cpp"), os.path.join(edir, "emu_psf.cpp"),
             os.path.join(CSRC, "vk_linearize.cpp")]
     # (the tool's own headers: whichever are there)
     deps = srcs + sorted(os.path.join(edir, f) for f in os.listdir(edir) if f.endswith(".h")) + \
-        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_adapt.h", "vk_splat.h", "vk_matte.h", "vk_robust.h", "vk_lpe.h", "vk_tone.h", "vk_nlm.h", "vk_glare.h", "vk_upsample.h")] + \
+        [os.path.join(CSRC, f) for f in ("vk_trace.h", "vk_math.h", "vk_device_scene.h", "vk_linearize.h", "vk_adapt.h", "vk_splat.h", "vk_matte.h", "vk_robust.h", "vk_lpe.h", "vk_tone.h", "vk_nlm.h", "vk_glare.h", "vk_upsample.h", "vk_psf.h")] + \
         [os.path.join(ROOT, "include", "vecchio_amd.h"), os.path.join(ROOT, "include", "vecchio_amd_debug.h")]
     if force or _newer(out, deps, CXXFLAGS):
         os.makedirs(os.path.dirname(out), exist_ok=True)

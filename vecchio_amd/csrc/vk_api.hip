@@ -58,6 +58,7 @@
 #include "vk_tone.h"         // the kernels of vk_tone.hip: the per-pixel display transform, argument records and launchers
 #include "vk_nlm.h"          // the kernels of vk_nlm.hip: the non-local-means filter's per-pixel code, argument records and launchers
 #include "vk_glare.h"        // the kernels of vk_glare.hip: the glare stage's per-pixel code, launch plan, argument records and launchers
+#include "vk_psf.h"          // the kernels of vk_psf.hip: the point-spread stage's per-element code, tables, argument records and launchers
 #include "vk_upsample.h"     // the kernels of vk_upsample.hip: guided upsampling's per-pixel code, argument records and launchers
 #include "vk_matte.h"        // the kernels of vk_matte.hip: the table of a pixel, the argument record and launchers
 
@@ -5342,6 +5343,382 @@ int vk_debug_glare_last_ms(vk_glare *g, double *ms) {
         int rc = glare_elapsed(g, &got);
         if (rc != VK_OK) return rc;
         *ms = got;
+        return VK_OK;
+    });
+}
+
+}  // extern "C"
+
+// ---- point-spread function (vk_psf_*): the three planes F of a frame's transform, the three planes G of the loaded kernel's, the
+// twiddle tables of the two padded sizes and the transform kernels (vk_psf.hip) on the scene's device (devices[0] of a multi-device
+// scene); all on the null stream, on buffers and events the handle owns.  Nothing of the scene handle is read but its device.
+struct vk_psf {
+    vk_scene *scene = nullptr;                      // as handed to vk_psf_create
+    uint32_t width = 0, height = 0, kmax = 0;
+    uint32_t K = 0, Px = 0, Py = 0;                 // of the loaded kernel; K = 0: none
+    DeviceBuffer<PsfC> F, G;                        // three planes each, sized for kmax
+    DeviceBuffer<PsfC> tw;                          // T of Px, then T of Py
+    DeviceBuffer<float> kern;                       // the normalised kernel
+    DeviceBuffer<float> keep;                       // the input of an in-place apply in the LDS form (first such apply)
+    DeviceBuffer<float> io;                         // a frame in and a frame out of the host-pointer call (first vk_psf_apply)
+    Event ev[2];                                    // around the last apply's kernels
+    Event pass_ev[3];                               // between the four passes of an apply in the LDS form
+    bool timed = false;
+    uint32_t last_form = 0u, last_launches = 0u;
+    uint64_t loads = 0, applies = 0;
+};
+
+namespace {
+
+void psf_free(vk_psf *g) {
+    (void)hipSetDevice(first_part(g->scene)->device);
+    (void)hipStreamSynchronize(nullptr);              // (an apply may still run)
+    (void)hipGetLastError();
+    delete g;
+}
+
+size_t psf_pixels(const vk_psf *g) { return (size_t)g->width * g->height; }
+
+// AUTO is the LDS form everywhere: four launches that move each plane once per pass, against PLAIN's launch per butterfly stage, each of
+// which reads and writes every plane (48 launches at 2048 x 2048).  tools/psf_report.py times both; its table is not recorded yet
+// (DESIGN.md "Point-spread function"), so this rule rests on that count and is the thing to revisit when it is.
+uint32_t psf_auto_form(uint32_t width, uint32_t height, uint32_t K) {
+    (void)width; (void)height; (void)K;
+    return PSF_FORM_LDS;
+}
+
+const char *psf_refusal(const vk_psf_params &p) {
+    if (!std::isfinite(p.strength) || !(p.strength >= 0.0f) || !(p.strength <= 1.0f)) return "strength must be in [0, 1]";
+    if (!std::isfinite(p.threshold) || !(p.threshold >= 0.0f)) return "threshold must be finite and >= 0";
+    if (p.form > PSF_FORM_LDS) return "unknown psf form";
+    if (p.flags != 0u || p._pad != 0u) return "unknown psf flags";
+    return nullptr;
+}
+
+int check_psf_apply(vk_psf *g, const vk_psf_params *p, const void *in, const void *out) {
+    if (!g || !p || !in || !out) return fail(VK_ERR_BAD_ARG, "null argument (psf handle, params, input or output)");
+    if (const char *why = psf_refusal(*p)) return fail(VK_ERR_BAD_ARG, why);
+    if (g->K == 0u) return fail(VK_ERR_BAD_ARG, "vk_psf_apply before vk_psf_load");
+    return VK_OK;
+}
+
+int check_psf_load(vk_psf *g, uint32_t K, const void *kernel) {
+    if (!g || !kernel) return fail(VK_ERR_BAD_ARG, "null argument (psf handle or kernel)");
+    if (K < PSF_MIN_K || K > PSF_MAX_K || (K & 1u) == 0u) return fail(VK_ERR_BAD_ARG, "K must be odd and in 3..1023");
+    if (K > g->kmax) return fail(VK_ERR_BAD_ARG, "K exceeds the handle's kmax");
+    return VK_OK;
+}
+
+// one bare 2-D transform of `planes` planes in place, rows then columns, in the given form (PLAIN or LDS); *launches counts its kernels
+void enqueue_psf_fft2(PsfC *a, uint32_t planes, uint32_t Px, uint32_t Py, const PsfC *Tx, const PsfC *Ty, bool inverse, bool scaled,
+    uint32_t form, uint32_t *launches) {
+    const float scale = 1.0f / ((float)Px * (float)Py);
+    if (form == PSF_FORM_PLAIN) {
+        for (uint32_t axis = 0; axis < 2u; axis++) {
+            PsfStageArgs S;
+            memset(&S, 0, sizeof(S));
+            S.a = a; S.T = axis ? Ty : Tx; S.Px = Px; S.Py = Py; S.planes = planes; S.axis = axis; S.inverse = inverse ? 1u : 0u;
+            launch_psf_bitrev(S);
+            ++*launches;
+            const uint32_t m = psf_log2(axis ? Py : Px);
+            for (S.s = 1u; S.s <= m; S.s++) { launch_psf_stage(S); ++*launches; }
+        }
+        if (inverse && scaled) {
+            PsfScaleArgs C;
+            memset(&C, 0, sizeof(C));
+            C.a = a; C.n = (uint64_t)planes * Px * Py; C.scale = scale;
+            launch_psf_scale(C);
+            ++*launches;
+        }
+        return;
+    }
+    for (uint32_t axis = 0; axis < 2u; axis++) {
+        PsfLineArgs A;
+        memset(&A, 0, sizeof(A));
+        A.a = a; A.T = axis ? Ty : Tx; A.Px = Px; A.Py = Py; A.planes = planes; A.count = axis ? Px : Py;
+        A.lines = psf_line_tile(axis ? Py : Px, axis != 0u, A.count);
+        A.load = PSF_LOAD_PLANE; A.store = axis && inverse && scaled ? PSF_STORE_SCALED : PSF_STORE_PLANE;
+        A.inverse = inverse ? 1u : 0u; A.scale = scale;
+        launch_psf_line(A, axis != 0u);
+        ++*launches;
+    }
+}
+
+// the kernel in g->kern (normalised, K x K x 3) into G: placed, then transformed
+int enqueue_psf_kernel(vk_psf *g, uint32_t K) {
+    const uint32_t Px = psf_pow2(g->width + K - 1u), Py = psf_pow2(g->height + K - 1u);
+    const std::vector<PsfC> Tx = psf_twiddles(Px), Ty = psf_twiddles(Py);
+    HIP_TRY(hipMemcpy(g->tw.get(), Tx.data(), Tx.size() * sizeof(PsfC), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(g->tw.get() + Px / 2u, Ty.data(), Ty.size() * sizeof(PsfC), hipMemcpyHostToDevice));
+    PsfPlaceArgs P;
+    memset(&P, 0, sizeof(P));
+    P.kernel = g->kern; P.G = g->G; P.K = K; P.Px = Px; P.Py = Py;
+    launch_psf_place(P);
+    uint32_t launches = 1u;
+    enqueue_psf_fft2(g->G, 3u, Px, Py, g->tw.get(), g->tw.get() + Px / 2u, false, false, psf_auto_form(g->width, g->height, K), &launches);
+    HIP_TRY(hipGetLastError());
+    g->K = K; g->Px = Px; g->Py = Py; g->loads++; g->last_launches = launches;
+    return VK_OK;
+}
+
+// validates and normalises the caller's kernel (host memory) and makes G of it
+int psf_load_host(vk_psf *g, uint32_t K, const float *kernel) {
+    std::vector<float> norm((size_t)K * K * 3u);
+    if (const char *why = psf_normalise(K, kernel, norm.data())) return fail(VK_ERR_BAD_ARG, why);
+    HIP_TRY(hipStreamSynchronize(nullptr));              // (an apply may still read the planes and tables this replaces)
+    HIP_TRY(hipMemcpy(g->kern.get(), norm.data(), norm.size() * sizeof(float), hipMemcpyHostToDevice));
+    return enqueue_psf_kernel(g, K);
+}
+
+// one apply from d_in into d_out (may be the same), on the handle's device; the arguments have been checked
+int enqueue_psf(vk_psf *g, const vk_psf_params &p, const float *d_in, float *d_out) {
+    const uint32_t form = p.form == PSF_FORM_AUTO ? psf_auto_form(g->width, g->height, g->K) : p.form;
+    const uint32_t W = g->width, H = g->height, Px = g->Px, Py = g->Py;
+    const PsfC *Tx = g->tw.get(), *Ty = g->tw.get() + Px / 2u;
+    const float scale = 1.0f / ((float)Px * (float)Py);
+    uint32_t launches = 0u;
+    if (form == PSF_FORM_LDS && d_in == d_out) {
+        // (the last pass writes a component of a pixel while the workgroups of the other components read the pixel: from a copy, then)
+        int rc = g->keep.ensure(psf_pixels(g) * 3u * sizeof(float));
+        if (rc != VK_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(g->keep.get(), d_in, psf_pixels(g) * 3u * sizeof(float), hipMemcpyDeviceToDevice, nullptr));
+        d_in = g->keep.get();
+    }
+    HIP_TRY(hipEventRecord(g->ev[0], nullptr));
+    if (form == PSF_FORM_PLAIN) {
+        PsfPadArgs P;
+        memset(&P, 0, sizeof(P));
+        P.in = d_in; P.F = g->F; P.W = W; P.H = H; P.Px = Px; P.Py = Py; P.threshold = p.threshold;
+        launch_psf_pad(P);
+        launches++;
+        enqueue_psf_fft2(g->F, 3u, Px, Py, Tx, Ty, false, false, PSF_FORM_PLAIN, &launches);
+        PsfProductArgs M;
+        memset(&M, 0, sizeof(M));
+        M.F = g->F; M.G = g->G; M.n = (uint64_t)3u * Px * Py;
+        launch_psf_product(M);
+        launches++;
+        enqueue_psf_fft2(g->F, 3u, Px, Py, Tx, Ty, true, false, PSF_FORM_PLAIN, &launches);
+        PsfCompositeArgs C;
+        memset(&C, 0, sizeof(C));
+        C.in = d_in; C.out = d_out; C.F = g->F; C.W = W; C.H = H; C.Px = Px; C.Py = Py;
+        C.scale = scale; C.strength = p.strength; C.threshold = p.threshold;
+        launch_psf_composite(C);
+        launches++;
+    } else {
+        PsfLineArgs A;
+        memset(&A, 0, sizeof(A));
+        A.a = g->F; A.G = g->G; A.in = d_in; A.out = d_out; A.Px = Px; A.Py = Py; A.planes = 3u; A.W = W; A.H = H; A.valid = H;
+        A.scale = scale; A.strength = p.strength; A.threshold = p.threshold;
+        // rows forward, from the frame: rows >= H are all zero and are neither made nor read
+        A.T = Tx; A.count = H; A.lines = psf_line_tile(Px, false, A.count); A.load = PSF_LOAD_FRAME; A.store = PSF_STORE_PLANE;
+        launch_psf_line(A, false);
+        HIP_TRY(hipEventRecord(g->pass_ev[0], nullptr));
+        // columns forward
+        A.T = Ty; A.count = Px; A.lines = psf_line_tile(Py, true, A.count); A.load = PSF_LOAD_ROWS;
+        launch_psf_line(A, true);
+        HIP_TRY(hipEventRecord(g->pass_ev[1], nullptr));
+        // rows inverse, of the product
+        A.inverse = 1u;
+        A.T = Tx; A.count = Py; A.lines = psf_line_tile(Px, false, A.count); A.load = PSF_LOAD_PRODUCT;
+        launch_psf_line(A, false);
+        HIP_TRY(hipEventRecord(g->pass_ev[2], nullptr));
+        // columns inverse, into the frame: only the columns the frame has
+        A.T = Ty; A.count = W; A.lines = psf_line_tile(Py, true, A.count); A.load = PSF_LOAD_PLANE; A.store = PSF_STORE_FRAME;
+        launch_psf_line(A, true);
+        launches = 4u;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(g->ev[1], nullptr));
+    g->timed = true;
+    g->last_form = form; g->last_launches = launches; g->applies++;
+    return VK_OK;
+}
+
+int psf_elapsed(vk_psf *g, double *ms) {
+    *ms = 0.0;
+    if (!g->timed) return VK_OK;
+    HIP_TRY(hipEventSynchronize(g->ev[1]));
+    float e = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&e, g->ev[0], g->ev[1]));
+    *ms = (double)e;
+    return VK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vk_psf_default_params(vk_psf_params *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    memset(out, 0, sizeof(*out));
+    out->strength = 0.15f; out->threshold = 0.0f; out->form = PSF_FORM_AUTO;
+    return VK_OK;
+}
+
+int vk_psf_star(uint32_t K, uint32_t streaks, float rotation, float sharpness, float chroma, float *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    if (K < PSF_MIN_K || K > PSF_MAX_K || (K & 1u) == 0u) return fail(VK_ERR_BAD_ARG, "K must be odd and in 3..1023");
+    if (streaks > 64u) return fail(VK_ERR_BAD_ARG, "streaks must be in 0..64");
+    if (!std::isfinite(rotation)) return fail(VK_ERR_BAD_ARG, "rotation must be finite");
+    if (!std::isfinite(sharpness) || !(sharpness >= 1.0f)) return fail(VK_ERR_BAD_ARG, "sharpness must be finite and >= 1");
+    if (!std::isfinite(chroma) || !(chroma >= 0.0f) || !(chroma <= 0.5f)) return fail(VK_ERR_BAD_ARG, "chroma must be in [0, 0.5]");
+    psf_star(K, streaks, rotation, sharpness, chroma, out);
+    return VK_OK;
+}
+
+int vk_psf_create(vk_scene *scene, uint32_t width, uint32_t height, uint32_t kmax, vk_psf **out) {
+    if (!scene || !out) return fail(VK_ERR_BAD_ARG, "null argument (scene or out)");
+    if (width == 0u || height == 0u) return fail(VK_ERR_BAD_ARG, "width and height must be >= 1");
+    if (kmax < PSF_MIN_K || kmax > PSF_MAX_K || (kmax & 1u) == 0u) return fail(VK_ERR_BAD_ARG, "kmax must be odd and in 3..1023");
+    if ((uint64_t)width + kmax - 1u > PSF_MAX_N || (uint64_t)height + kmax - 1u > PSF_MAX_N)
+        return fail(VK_ERR_BAD_ARG, "padded size exceeds 4096");
+    return guarded([&]() -> int {
+        std::unique_ptr<vk_psf, void (*)(vk_psf *)> g(new vk_psf(), psf_free);
+        g->scene = scene; g->width = width; g->height = height; g->kmax = kmax;
+        const size_t Px = psf_pow2(width + kmax - 1u), Py = psf_pow2(height + kmax - 1u);
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        int r = VK_OK;
+        handle_alloc(r, g->F, 3u * Px * Py * sizeof(PsfC));
+        handle_alloc(r, g->G, 3u * Px * Py * sizeof(PsfC));
+        handle_alloc(r, g->tw, (Px / 2u + Py / 2u) * sizeof(PsfC));
+        handle_alloc(r, g->kern, (size_t)kmax * kmax * 3u * sizeof(float));
+        if (r != VK_OK) return r;
+        for (Event &e : g->ev) if ((r = e.create()) != VK_OK) return r;
+        for (Event &e : g->pass_ev) if ((r = e.create()) != VK_OK) return r;
+        *out = g.release();
+        return VK_OK;
+    });
+}
+
+int vk_psf_load(vk_psf *g, uint32_t K, const float *kernel) {
+    int rc = check_psf_load(g, K, kernel);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(g->scene)->device));
+        int r = psf_load_host(g, K, kernel);
+        if (r != VK_OK) return r;
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        return VK_OK;
+    });
+}
+
+int vk_psf_load_device(vk_psf *g, uint32_t K, const void *d_kernel) {
+    int rc = check_psf_load(g, K, d_kernel);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(g->scene)->device));
+        // (the kernel is checked and normalised in f64 on the host: it comes back first, which waits for the null stream)
+        std::vector<float> host((size_t)K * K * 3u);
+        HIP_TRY(hipMemcpy(host.data(), d_kernel, host.size() * sizeof(float), hipMemcpyDeviceToHost));
+        return psf_load_host(g, K, host.data());
+    });
+}
+
+int vk_psf_apply(vk_psf *g, const vk_psf_params *p, const float *rgb_in, float *rgb_out) {
+    int rc = check_psf_apply(g, p, rgb_in, rgb_out);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(g->scene)->device));
+        // (the frame in and the frame out side by side in the handle's buffer; only the first is uploaded, only the second comes back)
+        float *const host[2] = {const_cast<float *>(rgb_in), rgb_out};
+        const uint32_t comps[2] = {3u, 3u};
+        StagedImages im;
+        int r = im.upload(g->io, host, comps, 2, psf_pixels(g), 0x1u);
+        if (r != VK_OK) return r;
+        r = enqueue_psf(g, *p, im.dev[0], im.dev[1]);
+        if (r != VK_OK) return r;
+        return im.download(0x2u);                                                         // (waits for the null stream)
+    });
+}
+
+int vk_psf_apply_device(vk_psf *g, const vk_psf_params *p, const void *d_rgb_in, void *d_rgb_out) {
+    int rc = check_psf_apply(g, p, d_rgb_in, d_rgb_out);
+    if (rc != VK_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(g->scene)->device));
+        return enqueue_psf(g, *p, static_cast<const float *>(d_rgb_in), static_cast<float *>(d_rgb_out));
+    });
+}
+
+int vk_psf_reset(vk_psf *g) {
+    if (!g) return fail(VK_ERR_BAD_ARG, "null psf handle");
+    g->K = 0u; g->Px = 0u; g->Py = 0u;
+    return VK_OK;
+}
+
+int vk_psf_get_info(vk_psf *g, vk_psf_info *out) {
+    if (!g || !out) return fail(VK_ERR_BAD_ARG, "null argument (psf handle or out)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(g->scene)->device));
+        double ms = 0.0;
+        int rc = psf_elapsed(g, &ms);
+        if (rc != VK_OK) return rc;
+        memset(out, 0, sizeof(*out));
+        out->width = g->width; out->height = g->height; out->K = g->K; out->Px = g->Px; out->Py = g->Py; out->kmax = g->kmax;
+        out->loads = g->loads; out->applies = g->applies; out->last_form = g->last_form; out->last_launches = g->last_launches;
+        out->last_kernel_ms = ms;
+        out->scratch_bytes = g->F.bytes() + g->G.bytes() + g->tw.bytes() + g->kern.bytes() + g->keep.bytes() + g->io.bytes();
+        return VK_OK;
+    });
+}
+
+void vk_psf_destroy(vk_psf *g) {
+    if (g) psf_free(g);
+}
+
+// test hook (vecchio_amd_debug.h): the four passes of the last apply, from the events recorded between them; zeros unless it was in the
+// LDS form
+int vk_psf_debug_last_pass_ms(vk_psf *g, double ms[4]) {
+    if (!g || !ms) return fail(VK_ERR_BAD_ARG, "null argument (psf handle or ms)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(g->scene)->device));
+        double got[4] = {0.0, 0.0, 0.0, 0.0};
+        if (g->timed && g->last_form == PSF_FORM_LDS) {
+            HIP_TRY(hipEventSynchronize(g->ev[1]));
+            const hipEvent_t at[5] = {g->ev[0], g->pass_ev[0], g->pass_ev[1], g->pass_ev[2], g->ev[1]};
+            for (int k = 0; k < 4; k++) {
+                float e = 0.0f;
+                HIP_TRY(hipEventElapsedTime(&e, at[k], at[k + 1]));
+                got[k] = (double)e;
+            }
+        }
+        for (int k = 0; k < 4; k++) ms[k] = got[k];
+        return VK_OK;
+    });
+}
+
+// test hook (vecchio_amd_debug.h): the library's twiddle table of a length N: N / 2 entries, (re, im) pairs.  Touches no device.
+int vk_psf_debug_twiddles(uint32_t N, float *out) {
+    if (!out) return fail(VK_ERR_BAD_ARG, "null argument");
+    if (N < 2u || N > PSF_MAX_N || (N & (N - 1u)) != 0u) return fail(VK_ERR_BAD_ARG, "N must be a power of two in 2..4096");
+    const std::vector<PsfC> T = psf_twiddles(N);
+    memcpy(out, T.data(), T.size() * sizeof(PsfC));
+    return VK_OK;
+}
+
+// test hook (vecchio_amd_debug.h): one bare 2-D transform of the caller's Px x Py complex values (host memory), in place
+int vk_psf_debug_fft2(vk_scene *scene, uint32_t Px, uint32_t Py, uint32_t inverse, uint32_t form, float *data) {
+    if (!scene || !data) return fail(VK_ERR_BAD_ARG, "null argument (scene or data)");
+    for (uint32_t N : {Px, Py})
+        if (N < 2u || N > PSF_MAX_N || (N & (N - 1u)) != 0u) return fail(VK_ERR_BAD_ARG, "Px and Py must be powers of two in 2..4096");
+    if (inverse > 1u) return fail(VK_ERR_BAD_ARG, "inverse must be 0 or 1");
+    if (form != PSF_FORM_PLAIN && form != PSF_FORM_LDS) return fail(VK_ERR_BAD_ARG, "unknown psf form");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(first_part(scene)->device));
+        const size_t n = (size_t)Px * Py;
+        DeviceBuffer<PsfC> a, tw;
+        int r = VK_OK;
+        handle_alloc(r, a, n * sizeof(PsfC));
+        handle_alloc(r, tw, (Px / 2u + Py / 2u) * sizeof(PsfC));
+        if (r != VK_OK) return r;
+        const std::vector<PsfC> Tx = psf_twiddles(Px), Ty = psf_twiddles(Py);
+        HIP_TRY(hipMemcpy(tw.get(), Tx.data(), Tx.size() * sizeof(PsfC), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(tw.get() + Px / 2u, Ty.data(), Ty.size() * sizeof(PsfC), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(a.get(), data, n * sizeof(PsfC), hipMemcpyHostToDevice));
+        uint32_t launches = 0u;
+        enqueue_psf_fft2(a, 1u, Px, Py, tw.get(), tw.get() + Px / 2u, inverse != 0u, true, form, &launches);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(data, a.get(), n * sizeof(PsfC), hipMemcpyDeviceToHost));      // (waits for the null stream)
         return VK_OK;
     });
 }

@@ -367,6 +367,21 @@ class GlareInfo(C.Structure):
 VK_GLARE_FORM_AUTO, VK_GLARE_FORM_PLAIN, VK_GLARE_FORM_FUSED = 0, 1, 2
 
 
+class PsfParams(C.Structure):
+    """vk_psf_params (vk_psf_apply, vk_psf_apply_device)"""
+    _fields_ = [("strength", C.c_float), ("threshold", C.c_float), ("form", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class PsfInfo(C.Structure):
+    """vk_psf_info (vk_psf_get_info)"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("K", C.c_uint32), ("Px", C.c_uint32), ("Py", C.c_uint32),
+                ("kmax", C.c_uint32), ("last_form", C.c_uint32), ("last_launches", C.c_uint32), ("loads", C.c_uint64),
+                ("applies", C.c_uint64), ("last_kernel_ms", C.c_double), ("scratch_bytes", C.c_uint64)]
+
+
+VK_PSF_FORM_AUTO, VK_PSF_FORM_PLAIN, VK_PSF_FORM_LDS = 0, 1, 2
+
+
 class UpsampleParams(C.Structure):
     """vk_upsample_params (vk_upsample_apply, vk_upsample_apply_device)"""
     _fields_ = [("sigma_z", C.c_float), ("normal_squarings", C.c_uint32), ("albedo_floor", C.c_float), ("flags", C.c_uint32),
@@ -515,6 +530,8 @@ DEVICE_SYMBOLS = [
     "vk_nlm_default_params", "vk_nlm_create", "vk_nlm_load", "vk_nlm_load_device", "vk_nlm_filter", "vk_nlm_filter_device", "vk_nlm_reset",
     "vk_nlm_get_info", "vk_nlm_destroy",
     "vk_glare_default_params", "vk_glare_create", "vk_glare_apply", "vk_glare_apply_device", "vk_glare_get_info", "vk_glare_destroy",
+    "vk_psf_default_params", "vk_psf_star", "vk_psf_create", "vk_psf_load", "vk_psf_load_device", "vk_psf_apply", "vk_psf_apply_device",
+    "vk_psf_reset", "vk_psf_get_info", "vk_psf_destroy",
     "vk_upsample_default_params", "vk_upsample_create", "vk_upsample_load", "vk_upsample_load_device", "vk_upsample_apply",
     "vk_upsample_apply_device", "vk_upsample_reset", "vk_upsample_get_info", "vk_upsample_destroy",
     "vk_matte_default_params", "vk_render_mattes", "vk_matte_merge", "vk_matte_mask",
@@ -759,6 +776,26 @@ def _bind(lib):
     lib.vk_glare_get_info.argtypes = [C.c_void_p, C.POINTER(GlareInfo)]
     lib.vk_glare_destroy.restype = None
     lib.vk_glare_destroy.argtypes = [C.c_void_p]
+    lib.vk_psf_default_params.restype = C.c_int
+    lib.vk_psf_default_params.argtypes = [C.POINTER(PsfParams)]
+    lib.vk_psf_star.restype = C.c_int
+    lib.vk_psf_star.argtypes = [C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_void_p]
+    lib.vk_psf_create.restype = C.c_int
+    lib.vk_psf_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
+    lib.vk_psf_load.restype = C.c_int
+    lib.vk_psf_load.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.vk_psf_load_device.restype = C.c_int
+    lib.vk_psf_load_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    lib.vk_psf_apply.restype = C.c_int
+    lib.vk_psf_apply.argtypes = [C.c_void_p, C.POINTER(PsfParams), C.c_void_p, C.c_void_p]
+    lib.vk_psf_apply_device.restype = C.c_int
+    lib.vk_psf_apply_device.argtypes = [C.c_void_p, C.POINTER(PsfParams), C.c_void_p, C.c_void_p]
+    lib.vk_psf_reset.restype = C.c_int
+    lib.vk_psf_reset.argtypes = [C.c_void_p]
+    lib.vk_psf_get_info.restype = C.c_int
+    lib.vk_psf_get_info.argtypes = [C.c_void_p, C.POINTER(PsfInfo)]
+    lib.vk_psf_destroy.restype = None
+    lib.vk_psf_destroy.argtypes = [C.c_void_p]
     lib.vk_upsample_default_params.restype = C.c_int
     lib.vk_upsample_default_params.argtypes = [C.POINTER(UpsampleParams)]
     lib.vk_upsample_create.restype = C.c_int
@@ -885,6 +922,12 @@ def _bind(lib):
     lib.vk_debug_glare_set_form.argtypes = [C.c_void_p, C.c_uint32]
     lib.vk_debug_glare_last_ms.restype = C.c_int
     lib.vk_debug_glare_last_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    lib.vk_psf_debug_twiddles.restype = C.c_int
+    lib.vk_psf_debug_twiddles.argtypes = [C.c_uint32, C.c_void_p]
+    lib.vk_psf_debug_last_pass_ms.restype = C.c_int
+    lib.vk_psf_debug_last_pass_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double * 4)]
+    lib.vk_psf_debug_fft2.restype = C.c_int
+    lib.vk_psf_debug_fft2.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
     lib.vk_debug_upsample_set_form.restype = C.c_int
     lib.vk_debug_upsample_set_form.argtypes = [C.c_void_p, C.c_uint32]
     lib.vk_debug_upsample_last_ms.restype = C.c_int

@@ -2,7 +2,7 @@
 // scene, build the BVH, upload once, then per Camera of cam_iter: render through the C ABI
 // (the call that replaces main.rs:181-198), write output_%04d.ppm, print the frame time.
 // The reference hard-codes scene/width/spp/depth (main.rs:28-29,159-167,171); here they are
-// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0] [guide_bounces=0] [display=0] [glare=0] [scale=0]
+// arguments:   vecchio_cli <scene> [width=900] [spp=1000] [max_depth=100] [frames=1] [seed=1] [steps=1] [aov_spp=0] [denoise=0] [temporal=0] [guide_bounces=0] [display=0] [glare=0] [scale=0] [psf=0]
 // steps > 1: each frame is rendered progressively (vk_progress_*) in `steps` equal sample windows; after each window the running image
 // is written to output_%04d_step%02d.ppm and the samples done and the image's mean relative standard error are printed.  The final
 // output_%04d.ppm is byte-identical to the one of steps = 1.
@@ -26,6 +26,9 @@
 // glare = 1 .. 100: that frame — display's, whether or not display is on — first goes through the glare stage (vk_glare_*) with strength
 // glare / 100 and the library's other default parameters; the result is written as output_%04d_glare.pfm and is what display encodes.
 // glare = 0 or absent: no such call is made and every file is what it was.
+// psf = 1 .. 64: the number of streaks of an aperture star.  That frame — after glare, if glare is on — goes through the point-spread
+// stage (vk_psf_*) with the 65 x 65 kernel of vk_psf_star(65, psf, 0, 8, 0.1) and the library's default parameters; the result is written
+// as output_%04d_psf.pfm and is what display encodes.  psf = 0 or absent: no such call is made and every file is what it was.
 // scale = 1 .. 99 (needs aov_spp > 0): render scale in percent.  The paths — and with steps > 1 their standard error — are traced at
 // width * scale / 100 (output_%04d.ppm, its steps and output_%04d.pfm are that low frame), the first-hit buffers are rendered at that
 // size too (output_%04d_lo_albedo.pfm, _lo_normal.pfm, _lo_depth.pfm) and at full size, and guided upsampling (vk_upsample_* with the
@@ -73,7 +76,7 @@ static T sym(void *h, const char *name) {
 int main(int argc, char **argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s <balls_demo|random_spheres_demo|random_spheres_iow|perlin_demo|bowser_demo|cornell_box|final_scene|"
-                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal] [guide_bounces] [display] [glare] [scale]\n", argv[0]);
+                        "final_scene_nextweek|stress_spheres:N> [width] [spp] [max_depth] [frames] [seed] [steps] [aov_spp] [denoise] [temporal] [guide_bounces] [display] [glare] [scale] [psf]\n", argv[0]);
         return 2;
     }
     const char *name = argv[1];
@@ -103,6 +106,12 @@ int main(int argc, char **argv) {
         return 2;
     }
     const bool scaled = scale_pct != 0 && scale_pct != 100;
+    const uint32_t psf_streaks = argc > 15 ? (uint32_t)atoi(argv[15]) : 0;
+    if (psf_streaks > 64) {
+        fprintf(stderr, "psf is the number of streaks of the aperture star: 1 to 64; 0 is off\n");
+        return 1;
+    }
+    constexpr uint32_t PSF_K = 65;
     if (scaled && aov_spp == 0) {
         fprintf(stderr, "scale needs the first-hit buffers at both sizes: aov_spp > 0\n");
         return 2;
@@ -160,6 +169,12 @@ int main(int argc, char **argv) {
     auto p_glare_create = sym<int (*)(vk_scene *, uint32_t, uint32_t, vk_glare **)>(h, "vk_glare_create");
     auto p_glare_apply = sym<int (*)(vk_glare *, const vk_glare_params *, const float *, float *)>(h, "vk_glare_apply");
     auto p_glare_destroy = sym<void (*)(vk_glare *)>(h, "vk_glare_destroy");
+    auto p_psf_defaults = sym<int (*)(vk_psf_params *)>(h, "vk_psf_default_params");
+    auto p_psf_star = sym<int (*)(uint32_t, uint32_t, float, float, float, float *)>(h, "vk_psf_star");
+    auto p_psf_create = sym<int (*)(vk_scene *, uint32_t, uint32_t, uint32_t, vk_psf **)>(h, "vk_psf_create");
+    auto p_psf_load = sym<int (*)(vk_psf *, uint32_t, const float *)>(h, "vk_psf_load");
+    auto p_psf_apply = sym<int (*)(vk_psf *, const vk_psf_params *, const float *, float *)>(h, "vk_psf_apply");
+    auto p_psf_destroy = sym<void (*)(vk_psf *)>(h, "vk_psf_destroy");
     auto p_up_defaults = sym<int (*)(vk_upsample_params *)>(h, "vk_upsample_default_params");
     auto p_up_create = sym<int (*)(vk_scene *, uint32_t, uint32_t, uint32_t, uint32_t, vk_upsample **)>(h, "vk_upsample_create");
     auto p_up_load = sym<int (*)(vk_upsample *, const float *, const float *, const float *, const float *, const float *)>(h, "vk_upsample_load");
@@ -199,6 +214,12 @@ int main(int argc, char **argv) {
     if (display && p_tone_create(scene, width, height, &tone) != VK_OK) { fprintf(stderr, "vk_tone_create: %s\n", p_err()); return 1; }
     vk_glare *glare = nullptr;
     if (glare_pct && p_glare_create(scene, width, height, &glare) != VK_OK) { fprintf(stderr, "vk_glare_create: %s\n", p_err()); return 1; }
+    vk_psf *psf = nullptr;
+    if (psf_streaks) {
+        std::vector<float> star((size_t)PSF_K * PSF_K * 3);
+        if (p_psf_star(PSF_K, psf_streaks, 0.0f, 8.0f, 0.1f, star.data()) != VK_OK || p_psf_create(scene, width, height, PSF_K, &psf) != VK_OK ||
+            p_psf_load(psf, PSF_K, star.data()) != VK_OK) { fprintf(stderr, "vk_psf: %s\n", p_err()); return 1; }
+    }
     vk_upsample *upsampler = nullptr;
     if (scaled && p_up_create(scene, lw, lh, width, height, &upsampler) != VK_OK) { fprintf(stderr, "vk_upsample_create: %s\n", p_err()); return 1; }
     vk_camera cam;
@@ -329,7 +350,7 @@ int main(int argc, char **argv) {
                 fprintf(stderr, "  accumulated: %.1f %% of the pixels with history, kernel %.2f ms\n",
                         100.0 * (double)ti.pixels_with_history / (double)np, ts.kernel_ms);
                 dn_color = acc.data(); dn_err = acc_err.data();
-                if (display || glare) shown = acc;
+                if (display || glare || psf) shown = acc;
             }
             if (denoise) {
                 vk_denoise_params dp;
@@ -344,7 +365,7 @@ int main(int argc, char **argv) {
                 snprintf(dfn, sizeof dfn, "output_%04d_denoised.pfm", file_idx);
                 if (!write_pfm(dfn, clean.data(), width, height, 3)) return 1;
                 fprintf(stderr, "  denoised (%u levels): kernels %.2f ms\n", dp.levels, ds.kernel_ms);
-                if (display || glare) shown = clean;
+                if (display || glare || psf) shown = clean;
             }
         }
         if (glare) {
@@ -357,6 +378,16 @@ int main(int argc, char **argv) {
             snprintf(sfn, sizeof sfn, "output_%04d_glare.pfm", file_idx);
             if (!write_pfm(sfn, shown.data(), width, height, 3)) return 1;
             fprintf(stderr, "  glare: strength %.2f over %u levels\n", (double)gp.strength, gp.levels);
+        }
+        if (psf) {
+            vk_psf_params pp;
+            if (shown.empty()) shown = pixels;
+            if (p_psf_defaults(&pp) != VK_OK) { fprintf(stderr, "vk_psf defaults: %s\n", p_err()); return 1; }
+            if (p_psf_apply(psf, &pp, shown.data(), shown.data()) != VK_OK) { fprintf(stderr, "vk_psf_apply: %s\n", p_err()); return 1; }
+            char sfn[64];
+            snprintf(sfn, sizeof sfn, "output_%04d_psf.pfm", file_idx);
+            if (!write_pfm(sfn, shown.data(), width, height, 3)) return 1;
+            fprintf(stderr, "  psf: a star of %u streaks, %u x %u, strength %.2f\n", psf_streaks, PSF_K, PSF_K, (double)pp.strength);
         }
         if (display) {
             vk_tone_meter_params mp;
@@ -380,6 +411,7 @@ int main(int argc, char **argv) {
         file_idx++;
     }
     if (upsampler) p_up_destroy(upsampler);
+    if (psf) p_psf_destroy(psf);
     if (glare) p_glare_destroy(glare);
     if (tone) p_tone_destroy(tone);
     if (history) p_tdestroy(history);

@@ -226,6 +226,13 @@ pub struct vk_glare_params { pub levels: u32, pub strength: f32, pub falloff: f3
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_glare_info { pub width: u32, pub height: u32, pub applies: u64, pub last_levels: u32, pub last_form: u32, pub last_launches: u32, pub _pad: u32, pub last_kernel_ms: f64, pub scratch_bytes: u64 }
 
+// point-spread function: the stage's parameters, and what a handle holds and last did
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_psf_params { pub strength: f32, pub threshold: f32, pub form: u32, pub flags: u32, pub _pad: u32 }
+
+#[repr(C)] #[derive(Copy, Clone, Default)]
+pub struct vk_psf_info { pub width: u32, pub height: u32, pub K: u32, pub Px: u32, pub Py: u32, pub kmax: u32, pub last_form: u32, pub last_launches: u32, pub loads: u64, pub applies: u64, pub last_kernel_ms: f64, pub scratch_bytes: u64 }
+
 // guided upsampling: the filter's parameters, and what a handle holds and last did
 #[repr(C)] #[derive(Copy, Clone, Default)]
 pub struct vk_upsample_params { pub sigma_z: f32, pub normal_squarings: u32, pub albedo_floor: f32, pub flags: u32, pub _pad: u32 }
@@ -255,6 +262,7 @@ pub struct vk_temporal_info { pub frames: u32, pub width: u32, pub height: u32, 
 #[repr(C)] pub struct vk_nlm { _private: [u8; 0] }
 #[repr(C)] pub struct vk_glare { _private: [u8; 0] }
 #[repr(C)] pub struct vk_upsample { _private: [u8; 0] }
+#[repr(C)] pub struct vk_psf { _private: [u8; 0] }
 
 #[link(name = "vecchio_amd")]
 extern "C" {
@@ -421,6 +429,18 @@ extern "C" {
     pub fn vk_glare_apply_device(g: *mut vk_glare, p: *const vk_glare_params, d_rgb_in: *const c_void, d_rgb_out: *mut c_void) -> c_int;
     pub fn vk_glare_get_info(g: *mut vk_glare, out: *mut vk_glare_info) -> c_int;
     pub fn vk_glare_destroy(g: *mut vk_glare);
+    // point-spread function (additive symbols of ABI 7): the share `strength` of a frame's bright part convolved with a caller's K x K x 3
+    // kernel in the Fourier domain, between vk_glare and vk_tone; no function takes a stream
+    pub fn vk_psf_default_params(out: *mut vk_psf_params) -> c_int;
+    pub fn vk_psf_star(K: u32, streaks: u32, rotation: f32, sharpness: f32, chroma: f32, out: *mut f32) -> c_int;
+    pub fn vk_psf_create(scene: *mut vk_scene, width: u32, height: u32, kmax: u32, out: *mut *mut vk_psf) -> c_int;
+    pub fn vk_psf_load(h: *mut vk_psf, K: u32, kernel: *const f32) -> c_int;
+    pub fn vk_psf_load_device(h: *mut vk_psf, K: u32, d_kernel: *const c_void) -> c_int;
+    pub fn vk_psf_apply(h: *mut vk_psf, p: *const vk_psf_params, rgb_in: *const f32, rgb_out: *mut f32) -> c_int;
+    pub fn vk_psf_apply_device(h: *mut vk_psf, p: *const vk_psf_params, d_rgb_in: *const c_void, d_rgb_out: *mut c_void) -> c_int;
+    pub fn vk_psf_reset(h: *mut vk_psf) -> c_int;
+    pub fn vk_psf_get_info(h: *mut vk_psf, out: *mut vk_psf_info) -> c_int;
+    pub fn vk_psf_destroy(h: *mut vk_psf);
     // guided upsampling (additive symbols of ABI 7): a w x h frame and its stderr3 to W x H along the edges of albedo, normal and depth
     // given at both sizes; every image but color_lo and rgb_out may be null; no function takes a stream (the _device calls are enqueued
     // on the null stream)

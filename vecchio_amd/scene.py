@@ -693,6 +693,11 @@ class DeviceScene:
         manager, or close() it before the scene."""
         return Glare(self, width, height)
 
+    def psf(self, width, height, kmax):
+        """A point-spread stage on this scene's device (vk_psf_create) for frames of width x height and kernels up to kmax x kmax: a
+        float frame in, the frame convolved with the loaded kernel out, between glare() and tone().  Close it before the scene."""
+        return Psf(self, width, height, kmax)
+
     def upsample(self, w, h, W, H):
         """A guided upsampler on this scene's device (vk_upsample_create) from w x h to W x H: load() a low frame with its stderr3 and
         first-hit buffers, apply() with the first-hit buffers at the high size.  Use as a context manager, or close() it before the
@@ -1648,6 +1653,105 @@ class NonLocalMeans:
     def close(self):
         if self._h:
             self._lib.vk_nlm_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Psf:
+    """vk_psf handle over a DeviceScene (close it, or leave the `with` block, before the scene is closed): the point-spread stage over
+    one width x height for kernels up to kmax x kmax.  load() a (K, K, 3) kernel (Psf.star() makes one), then apply() a float frame from
+    host memory or apply_device() one on the handle's device (y = 0 the bottom row, 3 floats a pixel); the kernel's transform is kept
+    until the next load."""
+
+    def __init__(self, scene, width, height, kmax):
+        self._lib = scene._lib
+        self._scene = scene
+        self.width, self.height, self.kmax = int(width), int(height), int(kmax)
+        h = C.c_void_p()
+        check(self._lib, self._lib.vk_psf_create(scene._h, width, height, kmax, C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def star(K, streaks=6, rotation=0.0, sharpness=8.0, chroma=0.0, lib=None):
+        """A (K, K, 3) float32 star kernel (vk_psf_star): a compact core and `streaks` rays from `rotation` (radians); `chroma` sets
+        the three channels' radial scales apart"""
+        lib = lib if lib is not None else ffi.load_device_lib()
+        out = np.zeros((K, K, 3), np.float32)
+        check(lib, lib.vk_psf_star(K, streaks, rotation, sharpness, chroma, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def _device(self, t, n=None):
+        if hasattr(t, "data_ptr"):
+            assert t.is_contiguous() and t.numel() == (n if n is not None else self.width * self.height * 3) and t.element_size() == 4
+            return t.data_ptr()
+        return t
+
+    def params(self, **kw):
+        """ffi.PsfParams: the defaults of the handle's library (vk_psf_default_params) with the given fields replaced"""
+        p = ffi.PsfParams()
+        check(self._lib, self._lib.vk_psf_default_params(C.byref(p)))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+
+    def load(self, kernel):
+        """Loads a kernel (vk_psf_load): a float32 (K, K, 3) array, tap (kx, ky) at [ky, kx], y up; it is normalised per channel"""
+        kernel = np.ascontiguousarray(kernel, np.float32)
+        assert kernel.ndim == 3 and kernel.shape[0] == kernel.shape[1] and kernel.shape[2] == 3
+        check(self._lib, self._lib.vk_psf_load(self._h, kernel.shape[0], kernel.ctypes.data_as(C.c_void_p)))
+
+    def load_device(self, K, d_kernel):
+        """Loads a kernel from memory of the handle's device (vk_psf_load_device): a contiguous float32 tensor of K * K * 3 values, or
+        a device pointer"""
+        check(self._lib, self._lib.vk_psf_load_device(self._h, K, C.c_void_p(self._device(d_kernel, K * K * 3))))
+
+    def apply(self, rgb, params=None, **kw):
+        """The frame with the point-spread function's glare (vk_psf_apply): float32 (height, width, 3) from a float32 array of width *
+        height * 3 values.  params: an ffi.PsfParams, or keywords over the defaults (strength, threshold, form)."""
+        p = params if params is not None else self.params(**kw)
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        assert rgb.size == self.width * self.height * 3
+        out = np.zeros((self.height, self.width, 3), np.float32)
+        check(self._lib, self._lib.vk_psf_apply(self._h, C.byref(p), rgb.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def apply_device(self, d_in, d_out=None, params=None, **kw):
+        """The same in memory of the handle's device (vk_psf_apply_device, enqueued on the null stream): contiguous float32 tensors
+        (objects with data_ptr()) of width * height * 3 values, or device pointers; d_out None = in place.  Returns d_out."""
+        p = params if params is not None else self.params(**kw)
+        if d_out is None:
+            d_out = d_in
+        check(self._lib, self._lib.vk_psf_apply_device(self._h, C.byref(p), C.c_void_p(self._device(d_in)), C.c_void_p(self._device(d_out))))
+        return d_out
+
+    def reset(self):
+        check(self._lib, self._lib.vk_psf_reset(self._h))
+
+    def last_pass_ms(self):
+        """device milliseconds of the last apply's four passes in the LDS form (vk_psf_debug_last_pass_ms, a test hook)"""
+        ms = (C.c_double * 4)()
+        check(self._lib, self._lib.vk_psf_debug_last_pass_ms(self._h, C.byref(ms)))
+        return list(ms)
+
+    def info(self):
+        inf = ffi.PsfInfo()
+        check(self._lib, self._lib.vk_psf_get_info(self._h, C.byref(inf)))
+        return inf
+
+    def close(self):
+        if self._h:
+            self._lib.vk_psf_destroy(self._h)
             self._h = None
 
     def __enter__(self):
